@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the BFP quantize + sparsify hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path (reference float_to_bfp_blocked, bfp_ops.py:124-149) over one
 synthetic LLaMA-7B down_proj weight [4096, 11008] bf16: 2:4 magnitude pruning then HBFP4 (sign + 3
@@ -21,7 +21,11 @@ tensor / time of (kernel + all-gather).  The packed form of the gather (4-bit co
 rank 0 checks the gathered tensor bit for bit against an un-sharded run of the same kernel.
 --weak keeps the round-1 measurement: every rank its own [4096, 11008] slab, no collective.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0; `ms_per_step` in it is the wall time of one timed step.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes the arrays the last timed step returned (the dequantised tensor `deq`;
+with --mode packed / both also `codes` and `exps`; N > 1: the gathered tensor) as float32 .npy files.  The inputs depend on the
+arguments only (seeded), so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -59,7 +63,35 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL) for real multi-GPU; gloo only to rehearse N>1 on one GPU")
     ap.add_argument("--one-device", action="store_true", help="rehearsal: every rank uses cuda:0")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32; arrays above "
+                         f"{DUMP_MAX_ELEMS} elements as a fixed, seeded sample of that many)")
     return ap.parse_args()
+
+
+DUMP_MAX_ELEMS = 1 << 22         # per array: 16 MB of float32, so the three outputs of --mode both stay under 64 MB
+DUMP_SEED = 20240917
+
+
+def dump_sample(t):
+    """t as a float32 numpy array: whole if it has at most DUMP_MAX_ELEMS elements, else the elements at DUMP_MAX_ELEMS flat indices
+    drawn with a fixed seed (sorted), the same indices for the same shape in every run"""
+    import torch
+    flat = t.detach().reshape(-1)
+    if flat.numel() > DUMP_MAX_ELEMS:
+        g = torch.Generator().manual_seed(DUMP_SEED)
+        idx = torch.randint(0, flat.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+        return flat[idx.to(flat.device)].float().cpu().numpy()
+    return flat.float().cpu().numpy().reshape(tuple(t.shape))
+
+
+def dump_outputs(out_dir, named):
+    """named: {name: tensor or None}, the arrays the timed call path handed back in its last step"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in named.items():
+        if t is not None:
+            np.save(os.path.join(out_dir, f"{name}.npy"), dump_sample(t))
 
 
 def relaunch_under_torchrun(args):
@@ -241,14 +273,20 @@ def main():
             ins.append((torch.randn(args.rows, args.cols, generator=g) * 0.02).to(dtype).to(dev))
             outs.append(torch.empty(args.rows, args.cols, dtype=dtype, device=dev) if want_deq else None)
 
+        last = {}
+
         def step(i):
             r = i % R
-            return native.quantize_nm(ins[r], args.block, args.mant_bits, 1e-8, N=N, M=M, sparsify_first=(args.first == "s"),
-                                      want_deq=want_deq, code_bits=code_bits, want_exp=want_exp, out=outs[r])
+            last["res"] = native.quantize_nm(ins[r], args.block, args.mant_bits, 1e-8, N=N, M=M, sparsify_first=(args.first == "s"),
+                                             want_deq=want_deq, code_bits=code_bits, want_exp=want_exp, out=outs[r])
+            return last["res"]
 
         use_graph = not args.eager and args.mode == "dropin"
         wall, ev_ms = timed_loop(step, args.steps, args.warmup, use_graph)
         wall = max_over_ranks(wall)
+        if args.dump_outputs and rank == 0 and args.steps > 0:
+            # (under the hipGraph the tensors recorded at capture are the ones its replay wrote: outs[(steps - 1) % R] last)
+            dump_outputs(args.dump_outputs, dict(zip(("deq", "codes", "exps"), last["res"])))
         if world == 1 and args.mode == "dropin" and not args.eager and args.block == 64 and pack_bits == 4 and esize == 2 and not args.headline_only:
             # ---- two more measurements of the same call path on the same rotating inputs (sub-records of the line) ----------
             # (1) north_star's "packed int4 stores": the kernel writes 4-bit codes + int8 exponents and no dequantised tensor
@@ -472,6 +510,8 @@ def main():
         pwall = max_over_ranks(pwall)
         wall, ev_ms = timed_loop(step, args.steps, args.warmup, False)
         wall = max_over_ranks(wall)
+        if args.dump_outputs and rank == 0 and args.steps > 0:
+            dump_outputs(args.dump_outputs, {"deq": wholes[(args.steps - 1) % R]})         # the gathered tensor every rank receives
         value = numel * args.steps / wall
         kern_us = k_ms * 1e3 / short
         extra["per_rank_kernel_us"] = all_ranks(kern_us)

@@ -616,6 +616,9 @@ class PruneQuantizeList:
 
     N_WS = 4                 # lanes: the current stream + 3 side streams, a workspace each (13B list: 1 lane 16.8 ms, 2: 14.2, 3: 12.7, 4: 12.5)
     GRAPH_FROM = 8           # lists of at least this many tensors replay a hipGraph of the pipeline (captured on the first run)
+    CAPTURE_AUX = 1          # side streams when the list is captured into a hipGraph (its own or the caller's): two lanes, the shape the
+                             # other list graphs have.  A four-lane graph replayed after a two-lane list graph segfaulted inside
+                             # hipGraphLaunch (ROCm 7.2, which runs a graph's branches on a per-device set of streams); eager calls keep N_WS
 
     def __init__(self, tensors, ks, block_size, mant_bits, epsilon, outs=None):
         tensors = list(tensors)
@@ -654,9 +657,12 @@ class PruneQuantizeList:
     def _issue(self, pipelined):
         dev = self.device
         with torch.cuda.device(dev):
+            n_aux = len(self._aux) if pipelined else 0
+            if n_aux and torch.cuda.is_current_stream_capturing():
+                n_aux = min(n_aux, self.CAPTURE_AUX)
             rc = self._fn(ctypes.addressof(self._descs), self._n, DTYPE_CODE[self.dtype], self.block_size, self.mant_bits, self.epsilon,
                           self._win.data_ptr(), ctypes.addressof(self._ws_ptrs), self.N_WS, torch.cuda.current_stream(dev).cuda_stream,
-                          ctypes.addressof(self._aux) if pipelined else None, len(self._aux) if pipelined else 0)
+                          ctypes.addressof(self._aux) if n_aux else None, n_aux)
         if rc:
             check(rc, "bfpq_prune_quantize_list")
 

@@ -79,6 +79,7 @@ def test_argument_validation_without_gpu():
     assert L.bfpq_hbfp_linear_decode(one, one, one, one, one, one, 17, 4096, 11008, native.BF16, 3, 7, n) == -1      # row-major layout: <= 16 tokens
     assert L.bfpq_nm8_lut_host(0, one) == -1 and L.bfpq_nm8_lut_host(4, n) == -1
     assert L.bfpq_tune(1, 3) == -1 and L.bfpq_tune(1, 2) == 0 and L.bfpq_tune(1, 0) == 0
+    assert L.bfpq_tune(0, 1024) == 0                   # the settings are process-wide: leave the default workgroup cap to the tests after this one
 
 
 @pytest.mark.gpu

@@ -1,7 +1,8 @@
 """Multi-rank runs of the row-sharded path with the HIP engine (gathered result == single-GPU result,
 byte for byte; the reference has no collectives on this path, so that is the whole contract).
 
-  * test_sharded_equals_single_gpu_rccl: one rank per visible GPU over RCCL (backend "nccl"); skipped with < 2 GPUs.
+  * test_sharded_equals_single_gpu_rccl: one rank per visible GPU over RCCL (backend "nccl"); on a one-GPU box one rank (RCCL
+    does not put two ranks on one device): the same worker, every collective of the path through RCCL on a group of one.
   * test_sharded_equals_single_gpu_ranks_on_one_device: the same worker with two / three ranks sharing cuda:0 and the `gloo`
     backend moving the (host-staged) bytes -- runs on a one-GPU box, so the real kernels see n_ranks > 1: the histogram
     all-gather with its per-rank copies, the tie base read off the gathered histograms, ragged and empty slabs.
@@ -127,9 +128,7 @@ def _run(world, backend, one_device, tmp_path):
 
 def test_sharded_equals_single_gpu_rccl(tmp_path):
     n = torch.cuda.device_count()
-    if n < 2:
-        pytest.skip("needs >= 2 GPUs (the driver's 8-GPU node); the two-ranks-on-one-device test below covers the protocol")
-    _run(min(n, 8), "nccl", False, tmp_path)
+    _run(max(1, min(n, 8)), "nccl", False, tmp_path)            # (several ranks on one device: the gloo test below)
 
 
 @pytest.mark.parametrize("world", [2, 3])
