@@ -259,24 +259,41 @@ def float_to_bfp_blocked(t, mant_bits, epsilon, rounding_mode, device, block_siz
 
 
 # ---- additive public surface (no counterpart in the reference) -------------------------------
-def _unstructured_lean(a, sparsity, sgd_update=False):
-    """the configuration is the s-first unstructured drop-in op (prune int(numel * frac) elements, then HBFP, round-half-even)"""
-    return (sparsity and a['num_format'] == 'bfp' and a['sparsity_num_format'] == 'bfp' and a['sparsity_mode'] == 'unstructured'
-            and a['first'] == 's' and a['rounding_mode'] == rounding_modes.DETERM and a['block_size'] > 0 and a['sparsity_frac'] > 0
-            and not sgd_update)
+def _list_form(a, sparsity, sgd_update):
+    """the list entry point of the library that computes configuration `a` (unpacked) for a list of tensors: 'prune' for
+    s-first unstructured pruning then HBFP, round-half-even (native.PruneQuantizeList: prune int(numel * frac) elements);
+    'fused' for HBFP with structured or no pruning, round-half-even (native.FastQuant's list call); None: the per-tensor call"""
+    if (sgd_update or a['num_format'] != 'bfp' or a['sparsity_num_format'] != 'bfp' or a['rounding_mode'] != rounding_modes.DETERM
+            or not a['block_size'] > 0):
+        return None
+    if not sparsity or (a['sparsity_mode'] == 'structured' and 0 < a['N'] <= a['M']):
+        return 'fused'
+    if a['sparsity_mode'] == 'unstructured' and a['first'] == 's' and a['sparsity_frac'] > 0:
+        return 'prune'
+    return None
 
 
-def _prune_lists(tensors, a):
-    """PruneQuantizeList per (device, dtype) group of `tensors` for configuration `a`; [(indices, list)]"""
+def _by_device_dtype(tensors):
+    """the indices of `tensors` per (device, dtype), groups in order of first appearance"""
     groups = {}
     for i, t in enumerate(tensors):
         native.require_device_tensor(t)
-        k = int(t.numel() * a['sparsity_frac'])
-        if k > t.numel():
-            raise RuntimeError("selected index k out of range")      # what torch.topk raises in the reference
-        groups.setdefault((t.device, t.dtype), []).append((i, k))
-    return [([i for i, _ in g], native.PruneQuantizeList([tensors[i].contiguous() for i, _ in g], [k for _, k in g],
-                                                         a['block_size'], a['mant_bits'], a['epsilon'])) for g in groups.values()]
+        groups.setdefault((t.device, t.dtype), []).append(i)
+    return list(groups.values())
+
+
+def _list_quant(a, sparsity):
+    """the FastQuant plan of a 'fused' configuration"""
+    nm = sparsity and a['N'] < a['M']
+    return _fast_quant(a['block_size'], a['mant_bits'], a['epsilon'], a['N'] if nm else 0, a['M'] if nm else 0, a['first'] == 's')
+
+
+def _prune_list(tensors, a):
+    """the PruneQuantizeList of a 'prune' configuration for tensors of one device and dtype"""
+    ks = [int(t.numel() * a['sparsity_frac']) for t in tensors]
+    if any(k > t.numel() for k, t in zip(ks, tensors)):
+        raise RuntimeError("selected index k out of range")          # what torch.topk raises in the reference
+    return native.PruneQuantizeList(tensors, ks, a['block_size'], a['mant_bits'], a['epsilon'])
 
 
 MANY_LANES = 3                       # streams a list of tensors without a list kernel is dealt to (the current one + side streams)
@@ -291,53 +308,27 @@ def _many_over_streams(tensors, fn):
     big = [t for t in tensors if t.device.type == "cuda" and t.numel() * t.element_size() >= MANY_LANES_MIN_BYTES]
     if MANY_LANES < 2 or len(big) < 2 or len({t.device for t in big}) != 1 or any(t.device != big[0].device for t in tensors):
         return [fn(t) for t in tensors]
-    dev = big[0].device
-    main = torch.cuda.current_stream(dev)
-    streams = [main] + native.aux_streams(dev, MANY_LANES - 1)
-    for s in streams[1:]:
-        s.wait_stream(main)
-    out = []
-    for i, t in enumerate(tensors):
-        s = streams[i % len(streams)]
-        with torch.cuda.stream(s):
-            y = fn(t)
-            if s is not main and y is not t:
-                y.record_stream(main)                       # (allocated on a side stream, consumed on the caller's)
-        out.append(y)
-    for s in streams[1:]:
-        main.wait_stream(s)
-    return out
+    return native._deal_over_streams(big[0].device, tensors, MANY_LANES, lambda _, t: fn(t))
 
 
 def float_to_bfp_blocked_many(tensors, identifier='', **bfp_args):
     """float_to_bfp_blocked (bfp_ops.py:124-149) for a LIST of tensors with one configuration -- e.g. every Linear weight of
     a model -- in as few launches as possible: one per 64 tensors per dtype/device for the 'bfp' format with structured or no
     pruning and round-half-even (large tensors: a launch each, spread over two streams); for unstructured pruning before
-    quantization, two launches per tensor over four independent lanes (native.PruneQuantizeList); anything else is the
-    per-tensor call, large tensors dealt to a few streams (_many_over_streams).  Returns the list of results in order."""
+    quantization, two launches per tensor over four independent lanes (native.PruneQuantizeList, issued eagerly); anything else
+    is the per-tensor call, large tensors dealt to a few streams (_many_over_streams).  Returns the list of results in order."""
     a = unpack_bfp_args(dict(bfp_args))
+    sgd_update = bool(bfp_args.get('sgd_update'))
     tensors = list(tensors)
     sparsity = _select_sparsity(a['in_sparsity'], a['w_sparsity'], a['grad_sparsity'], identifier)
-    if _unstructured_lean(a, sparsity, bool(bfp_args.get('sgd_update'))):
-        out = [None] * len(tensors)
-        for idx, pl in _prune_lists(tensors, a):
-            for i, y in zip(idx, pl.run()):
-                out[i] = y.view(tensors[i].shape)
-        return out
-    lean = (a['num_format'] == 'bfp' and a['sparsity_num_format'] == 'bfp' and a['rounding_mode'] == rounding_modes.DETERM
-            and a['block_size'] > 0 and not bfp_args.get('sgd_update')
-            and (not sparsity or (a['sparsity_mode'] == 'structured' and 0 < a['N'] <= a['M'])))
-    if not lean:
-        return _many_over_streams(tensors, lambda t: float_to_bfp_blocked(t, **a, identifier=identifier, sgd_update=bool(bfp_args.get('sgd_update'))))
-    nm = sparsity and a['N'] < a['M']
-    f = _fast_quant(a['block_size'], a['mant_bits'], a['epsilon'], a['N'] if nm else 0, a['M'] if nm else 0, a['first'] == 's')
+    form = _list_form(a, sparsity, sgd_update)
+    if form is None:
+        return _many_over_streams(tensors, lambda t: float_to_bfp_blocked(t, **a, identifier=identifier, sgd_update=sgd_update))
     out = [None] * len(tensors)
-    groups = {}
-    for i, t in enumerate(tensors):
-        native.require_device_tensor(t)
-        groups.setdefault((t.device, t.dtype), []).append(i)
-    for idx in groups.values():
-        for i, y in zip(idx, f.many([tensors[i] for i in idx])):
+    for idx in _by_device_dtype(tensors):
+        ts = [tensors[i] for i in idx]
+        ys = _prune_list([t.contiguous() for t in ts], a).run(graph=False) if form == 'prune' else _list_quant(a, sparsity).many(ts)
+        for i, y in zip(idx, ys):
             out[i] = y.view(tensors[i].shape)
     return out
 
@@ -345,34 +336,26 @@ def float_to_bfp_blocked_many(tensors, identifier='', **bfp_args):
 class PreparedMany:
     """float_to_bfp_blocked_many with the per-call host work done once: run() re-quantizes the bound tensors (whose storage
     must stay put, e.g. a model's weights) into the same output tensors -- one launch per 64 tensors (structured / dense), or
-    the two-stream pipeline of the unstructured path; one ctypes call per dtype/device group."""
+    the four-lane pipeline of the unstructured path (a hipGraph of it from PruneQuantizeList.GRAPH_FROM tensors on); one ctypes
+    call per dtype/device group."""
 
     def __init__(self, tensors, identifier='', **bfp_args):
         a = unpack_bfp_args(dict(bfp_args))
         self.tensors = list(tensors)
-        self._args, self._ident = a, identifier
+        self._args, self._ident, self._sgd_update = a, identifier, bool(bfp_args.get('sgd_update'))
         sparsity = _select_sparsity(a['in_sparsity'], a['w_sparsity'], a['grad_sparsity'], identifier)
-        lean = (a['num_format'] == 'bfp' and a['sparsity_num_format'] == 'bfp' and a['rounding_mode'] == rounding_modes.DETERM
-                and a['block_size'] > 0 and (not sparsity or (a['sparsity_mode'] == 'structured' and 0 < a['N'] <= a['M'])))
+        form = _list_form(a, sparsity, self._sgd_update)
         self._groups = None
-        if _unstructured_lean(a, sparsity):
-            for t in self.tensors:
-                if not t.is_contiguous():
-                    raise ValueError("PreparedMany needs contiguous inputs (their storage is bound)")
-            self._groups = _prune_lists(self.tensors, a)
-        elif lean:
-            nm = sparsity and a['N'] < a['M']
-            f = _fast_quant(a['block_size'], a['mant_bits'], a['epsilon'], a['N'] if nm else 0, a['M'] if nm else 0, a['first'] == 's')
-            groups = {}
-            for i, t in enumerate(self.tensors):
-                native.require_device_tensor(t)
-                groups.setdefault((t.device, t.dtype), []).append(i)
-            self._groups = [(idx, f.prepare([self.tensors[i] for i in idx])) for idx in groups.values()]
+        if form is not None:
+            self._groups = []
+            for idx in _by_device_dtype(self.tensors):
+                ts = [self.tensors[i] for i in idx]
+                self._groups.append((idx, _prune_list(ts, a) if form == 'prune' else _list_quant(a, sparsity).prepare(ts)))
 
     def run(self):
-        out = [None] * len(self.tensors)
         if self._groups is None:
-            return [float_to_bfp_blocked(t, **self._args, identifier=self._ident) for t in self.tensors]
+            return [float_to_bfp_blocked(t, **self._args, identifier=self._ident, sgd_update=self._sgd_update) for t in self.tensors]
+        out = [None] * len(self.tensors)
         for idx, prep in self._groups:
             for i, y in zip(idx, prep.run()):
                 out[i] = y.view(self.tensors[i].shape)

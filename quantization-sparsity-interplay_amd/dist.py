@@ -179,8 +179,6 @@ def _many_sharded_one_exchange(locals_, rows_totals, group, gather, identifier, 
     assert (bfp_args['block_size'] > 0)                                 # bfp_ops.py:130
     mb = bfp_args['weight_mant_bits'] if bfp_args.get('sgd_update') else bfp_args['mant_bits']
     dev = locals_[0].device
-    main = torch.cuda.current_stream(dev)
-    side = native.aux_streams(dev, 1)[0]
     outs = [None] * n
     for g0 in range(0, n, group_size):
         idx = list(range(g0, min(n, g0 + group_size)))
@@ -196,20 +194,16 @@ def _many_sharded_one_exchange(locals_, rows_totals, group, gather, identifier, 
             ngs.append(ng); ks.append(k)
         wss = _list_workspaces(dev, len(idx))
         native.select_threshold_list([locals_[i] for i in idx], ks, wss, ngs, _block_allgather(group))
-        side.wait_stream(main)
-        for j, i in enumerate(idx):
-            t = locals_[i]
+
+        def finish(j, t):
             if t.numel() == 0:
-                outs[i] = t.clone()
-                continue
-            s = side if (j & 1) else main
-            with torch.cuda.stream(s):
-                seed = bfp_ops._seed_for(bfp_args['rounding_mode'])
-                o = native.quantize_threshold(t, wss[j], bfp_args['block_size'], mb, bfp_args['epsilon'], stoch_seed=seed)[0]
-                outs[i] = bfp_ops._stoc_dtype(o.view(t.shape), bfp_args['rounding_mode'])
-                if s is side:
-                    outs[i].record_stream(main)
-        main.wait_stream(side)                                            # (also: the group's workspaces are free for the next group)
+                return t.clone()
+            seed = bfp_ops._seed_for(bfp_args['rounding_mode'])
+            o = native.quantize_threshold(t, wss[j], bfp_args['block_size'], mb, bfp_args['epsilon'], stoch_seed=seed)[0]
+            return bfp_ops._stoc_dtype(o.view(t.shape), bfp_args['rounding_mode'])
+        # (joined before the next group: its workspaces are free again)
+        for i, y in zip(idx, native._deal_over_streams(dev, [locals_[i] for i in idx], 2, finish)):
+            outs[i] = y
     return [all_gather_rows(o, r, group) for o, r in zip(outs, rows_totals)] if gather else outs
 
 
@@ -245,21 +239,8 @@ def float_to_bfp_blocked_many_sharded(locals_, rows_totals, group=None, gather=F
     if not on_gpu or lanes <= 1 or n < 2:
         return [float_to_bfp_blocked_sharded(t, r, group, gather, compute, engine, identifier=identifier, **bfp_args)
                 for t, r in zip(locals_, rows_totals)]
-    dev = locals_[0].device
-    main = torch.cuda.current_stream(dev)
-    streams = [main] + native.aux_streams(dev, min(lanes, n) - 1)
-    for s in streams[1:]:
-        s.wait_stream(main)
-    outs = [None] * n
-    for i, (t, r) in enumerate(zip(locals_, rows_totals)):
-        s = streams[i % len(streams)]
-        with torch.cuda.stream(s):
-            outs[i] = float_to_bfp_blocked_sharded(t, r, group, gather, compute, engine, identifier=identifier, **bfp_args)
-            if s is not main:
-                outs[i].record_stream(main)                        # (allocated on a side stream, consumed on the caller's)
-    for s in streams[1:]:
-        main.wait_stream(s)
-    return outs
+    return native._deal_over_streams(locals_[0].device, locals_, lanes, lambda i, t: float_to_bfp_blocked_sharded(
+        t, rows_totals[i], group, gather, compute, engine, identifier=identifier, **bfp_args))
 
 
 def float_to_bfp_packed_sharded(local, rows_total, mant_bits, block_size, group=None, gather=False, **kw):

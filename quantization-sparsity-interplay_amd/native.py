@@ -268,6 +268,72 @@ class _TensorDesc(ctypes.Structure):
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
+def _bind(Desc, field, tensors, extras, outs, what, copy=False):
+    """the descriptors (Desc) of a list of tensors of one device and dtype for a list entry point of the library: tensor i gets
+    one with `field` set to extras[i], or is left as it is where extras[i] is None (its result is itself); outs[i], where given,
+    is its output.  Inputs must be contiguous (their storage is bound), or with copy=True are replaced by contiguous copies.
+    Returns (device, dtype, outputs, descs, keep): keep[j] is the tensor descriptor j reads (alive while its launches run)."""
+    n = len(tensors)
+    descs = (Desc * max(n, 1))()
+    outputs = [None] * n
+    keep = []
+    dev = dt = None
+    for i, t in enumerate(tensors):
+        if dev is None:
+            require_device_tensor(t)
+            dev, dt = t.device, t.dtype
+        elif t.device != dev or t.dtype != dt:
+            raise ValueError(f"{what}: the tensors of one list share device and dtype")
+        x = extras[i]
+        if x is None:
+            outputs[i] = t
+            continue
+        if not t.is_contiguous():
+            if not copy:
+                raise ValueError(f"{what} needs contiguous inputs (their storage is bound)")
+            t = t.contiguous()
+        dst = torch.empty_like(t) if outs is None or outs[i] is None else outs[i]
+        outputs[i] = dst
+        if t.numel() == 0:
+            continue
+        cols = t.shape[-1] if t.dim() else 1
+        d = descs[len(keep)]
+        d.in_dev, d.out_dev, d.rows, d.cols = t.data_ptr(), dst.data_ptr(), t.numel() // cols, cols
+        setattr(d, field, x)
+        keep.append(t)
+    return dev, dt, outputs, descs, keep
+
+
+class _BoundList:
+    """A list of tensors of one dtype on one device bound to a list entry point of the library (a _Desc per tensor, its own
+    field _FIELD filled from the subclass's per-tensor values): outputs and descriptors are set up once, run() re-issues the
+    launches.  The inputs are expected to keep their storage between runs (a model's weights); run() checks every bound
+    pointer against the tensor's current one and re-binds a tensor whose storage moved (`model.to(...)`, `p.data = ...`,
+    `load_state_dict(assign=True)`) -- a changed dtype, device or element count raises instead of reading freed memory.
+    Results are written in place into .outputs."""
+
+    def __init__(self, tensors, extras, outs):
+        self.device, self.dtype, self.outputs, self._descs, keep = _bind(self._Desc, self._FIELD, tensors, extras, outs, type(self).__name__)
+        self._k = len(keep)
+        self._bound = [(t, t.data_ptr(), t.numel()) for t in keep]
+        self._addr = ctypes.addressof(self._descs)
+
+    def _rebind(self):
+        """descriptor j reads self._bound[j][0]: follow tensors whose storage moved since they were bound; True if one did"""
+        moved = False
+        for j, (t, ptr, n) in enumerate(self._bound):
+            cur = t.data_ptr()
+            if cur == ptr:
+                continue
+            if t.dtype != self.dtype or t.device != self.device or t.numel() != n or not t.is_contiguous():
+                raise RuntimeError(f"{type(self).__name__}: a bound tensor changed dtype / device / size / layout since it was bound "
+                                   f"(was {n} x {self.dtype} on {self.device}, is {t.numel()} x {t.dtype} on {t.device}); build a new list")
+            self._descs[j].in_dev = cur
+            self._bound[j] = (t, cur, n)
+            moved = True
+        return moved
+
+
 class FastQuant:
     """The drop-in call (round-half-even, dequantised tensor out) with everything constant bound once: per call it costs
     one output allocation and one six-argument ctypes call (bfpq_fake_quantize).  This is what the module wrappers issue
@@ -321,38 +387,21 @@ class FastQuant:
         For tensors whose storage stays put (the weights of a model quantized every forward)."""
         return PreparedList(self, tensors, apply_nm, outs)
 
+    def _apply_nm(self, apply_nm, n):
+        """the apply_nm field of n tensors' descriptors (default: N:M pruning applies to all), None for a tensor the plan leaves
+        as it is (no quantization, and no N:M pruning for it)"""
+        flags = [True] * n if apply_nm is None else [bool(f) for f in apply_nm]
+        return flags if self.block_size else [f if f and self.M else None for f in flags]
+
     def many(self, tensors, apply_nm=None, outs=None):
         """the same for a LIST of tensors of one dtype on one device, in as few launches as possible
         (bfpq_fake_quantize_batched: up to 64 tensors per launch).  apply_nm: per tensor, whether this plan's N:M pruning
         applies to it (default: to all).  Returns the list of results (a tensor the plan leaves untouched comes back itself)."""
-        n = len(tensors)
-        if n == 0:
+        if not tensors:
             return []
-        flags = [True] * n if apply_nm is None else [bool(f) for f in apply_nm]
-        t0 = tensors[0]
-        require_device_tensor(t0)
-        dev, dt = t0.device, t0.dtype
-        res = [None] * n
-        descs = (_TensorDesc * n)()
-        keep = []                                              # contiguous copies live until the call returns (stream-ordered after that)
-        k = 0
-        for i, t in enumerate(tensors):
-            if t.device != dev or t.dtype != dt:
-                raise ValueError("FastQuant.many: the tensors of one call share device and dtype")
-            if self.block_size == 0 and not (flags[i] and self.M > 0):
-                res[i] = t                                     # identity for this tensor
-                continue
-            src = t if t.is_contiguous() else t.contiguous()
-            dst = torch.empty_like(src) if outs is None or outs[i] is None else outs[i]
-            res[i] = dst
-            if src.numel() == 0:
-                continue
-            cols = src.shape[-1] if src.dim() else 1
-            d = descs[k]
-            d.in_dev, d.out_dev, d.rows, d.cols, d.apply_nm = src.data_ptr(), dst.data_ptr(), src.numel() // cols, cols, 1 if flags[i] else 0
-            res[i] = dst
-            k += 1
-            keep.append(src)
+        # (keep: contiguous copies live until the call returns, stream-ordered after that)
+        dev, dt, res, descs, keep = _bind(_TensorDesc, "apply_nm", tensors, self._apply_nm(apply_nm, len(tensors)), outs, "FastQuant.many", copy=True)
+        k = len(keep)
         if k:
             plan = self._plan(dt, dev)
             with torch.cuda.device(dev):
@@ -364,61 +413,20 @@ class FastQuant:
         return res
 
 
-class PreparedList:
-    """A list of tensors bound to one FastQuant plan: input pointers, output tensors and the descriptor array are set up
-    once; run() is ONE ctypes call (bfpq_fake_quantize_batched) whatever the number of tensors.  The inputs are expected to
-    keep their storage between runs (a model's weights); run() checks every bound pointer against the tensor's current one
-    and re-binds a tensor whose storage moved (`model.to(...)`, `p.data = ...`, `load_state_dict(assign=True)`) -- a changed
-    dtype, device or element count raises instead of reading freed memory.  Results are written in place into .outputs."""
+class PreparedList(_BoundList):
+    """A list of tensors bound to one FastQuant plan (see _BoundList): run() is ONE ctypes call (bfpq_fake_quantize_batched)
+    whatever the number of tensors."""
+
+    _Desc, _FIELD = _TensorDesc, "apply_nm"
 
     def __init__(self, fq, tensors, apply_nm=None, outs=None):
         tensors = list(tensors)
-        n = len(tensors)
-        flags = [True] * n if apply_nm is None else [bool(f) for f in apply_nm]
         self.fq = fq
-        self.outputs = [None] * n
-        self._keep = []
-        self._descs = (_TensorDesc * max(n, 1))()
-        self._k = 0
-        self.device = self.dtype = None
-        for i, t in enumerate(tensors):
-            require_device_tensor(t)
-            if self.device is None:
-                self.device, self.dtype = t.device, t.dtype
-            if t.device != self.device or t.dtype != self.dtype:
-                raise ValueError("PreparedList: the tensors of one list share device and dtype")
-            if not t.is_contiguous():
-                raise ValueError("PreparedList needs contiguous inputs (their storage is bound)")
-            if fq.block_size == 0 and not (flags[i] and fq.M > 0):
-                self.outputs[i] = t
-                continue
-            dst = torch.empty_like(t) if outs is None or outs[i] is None else outs[i]
-            self.outputs[i] = dst
-            if t.numel() == 0:
-                continue
-            cols = t.shape[-1] if t.dim() else 1
-            d = self._descs[self._k]
-            d.in_dev, d.out_dev, d.rows, d.cols, d.apply_nm = t.data_ptr(), dst.data_ptr(), t.numel() // cols, cols, 1 if flags[i] else 0
-            self._k += 1
-            self._keep.append(t)
-        self._bound = [(t, t.data_ptr(), t.numel()) for t in self._keep]
+        super().__init__(tensors, fq._apply_nm(apply_nm, len(tensors)), outs)
         self._plan = fq._plan(self.dtype, self.device) if self._k else None
         self._fn = load_library().bfpq_fake_quantize_list
-        self._addr = ctypes.addressof(self._descs)
         # (large tensors of the list get launches of their own, spread over the current stream and this one)
         self._aux = aux_stream_array(self.device, 1) if self._k > 1 else None
-
-    def _rebind(self):
-        """descriptor j reads self._keep[j]: follow tensors whose storage moved since they were bound"""
-        for j, (t, ptr, n) in enumerate(self._bound):
-            cur = t.data_ptr()
-            if cur == ptr:
-                continue
-            if t.dtype != self.dtype or t.device != self.device or t.numel() != n or not t.is_contiguous():
-                raise RuntimeError("PreparedList: a bound tensor changed dtype / device / size / layout since it was bound "
-                                   f"(was {n} x {self.dtype} on {self.device}, is {t.numel()} x {t.dtype} on {t.device}); build a new list")
-            self._descs[j].in_dev = cur
-            self._bound[j] = (t, cur, n)
 
     def run(self):
         if self._k:
@@ -603,16 +611,45 @@ def aux_stream(device):
     return aux_streams(device, 1)[0]
 
 
+_aux_arrays = {}
+
+
 def aux_stream_array(device, n):
-    """the raw handles of aux_streams(device, n) as a C array of void* (the streams themselves live as long as the process)"""
-    return (ctypes.c_void_p * n)(*[s.cuda_stream for s in aux_streams(device, n)])
+    """the raw handles of aux_streams(device, n) as a C array of void*, made once (the streams live as long as the process)"""
+    key = (device.index if device.index is not None else torch.cuda.current_device(), n)
+    arr = _aux_arrays.get(key)
+    if arr is None:
+        arr = _aux_arrays[key] = (ctypes.c_void_p * n)(*[s.cuda_stream for s in aux_streams(device, n)])
+    return arr
 
 
-class PruneQuantizeList:
-    """A list of tensors of one dtype on one device bound to the s-first unstructured drop-in op (bfpq_prune_quantize_list):
-    outputs, descriptors and the workspaces are set up once; run() is ONE ctypes call that spreads the tensors over N_WS
-    independent lanes (the current stream and side streams, a workspace each; a tensor's two launches stay on its lane).
-    ks: elements to prune per tensor, int(numel * frac) as the reference computes it (bfp_ops.py:66)."""
+def _deal_over_streams(device, items, lanes, fn):
+    """[fn(i, item) for i, item in enumerate(items)] for calls that are independent of one another: item i is issued on stream
+    i % S of the caller's stream + aux_streams(device, S - 1), S = min(lanes, len(items)).  The side streams fork from the
+    caller's stream before the first item and are joined back after the last; a result allocated on a side stream (anything fn
+    returns other than the item itself) is recorded as used by the caller's stream."""
+    main = torch.cuda.current_stream(device)
+    streams = [main] + aux_streams(device, min(lanes, len(items)) - 1)
+    for s in streams[1:]:
+        s.wait_stream(main)
+    out = []
+    for i, x in enumerate(items):
+        s = streams[i % len(streams)]
+        with torch.cuda.stream(s):
+            y = fn(i, x)
+        if s is not main and y is not x:
+            y.record_stream(main)
+        out.append(y)
+    for s in streams[1:]:
+        main.wait_stream(s)
+    return out
+
+
+class PruneQuantizeList(_BoundList):
+    """A list of tensors of one dtype on one device bound to the s-first unstructured drop-in op (bfpq_prune_quantize_list; see
+    _BoundList): the workspaces too are set up once; run() is ONE ctypes call that spreads the tensors over N_WS independent
+    lanes (the current stream and side streams, a workspace each; a tensor's two launches stay on its lane), or replays a
+    hipGraph of that call.  ks: elements to prune per tensor, int(numel * frac) as the reference computes it (bfp_ops.py:66)."""
 
     N_WS = 4                 # lanes: the current stream + 3 side streams, a workspace each (13B list: 1 lane 16.8 ms, 2: 14.2, 3: 12.7, 4: 12.5)
     GRAPH_FROM = 8           # lists of at least this many tensors replay a hipGraph of the pipeline (captured on the first run)
@@ -620,32 +657,12 @@ class PruneQuantizeList:
                              # other list graphs have.  A four-lane graph replayed after a two-lane list graph segfaulted inside
                              # hipGraphLaunch (ROCm 7.2, which runs a graph's branches on a per-device set of streams); eager calls keep N_WS
 
+    _Desc, _FIELD = _PruneDesc, "k"
+
     def __init__(self, tensors, ks, block_size, mant_bits, epsilon, outs=None):
-        tensors = list(tensors)
         self.block_size, self.mant_bits, self.epsilon = int(block_size), int(mant_bits), float(epsilon)
-        self.outputs = [None] * len(tensors)
-        self._bound = []
-        self._descs = (_PruneDesc * max(len(tensors), 1))()
-        self._n = 0
-        self.device = self.dtype = None
-        for i, (t, k) in enumerate(zip(tensors, ks)):
-            require_device_tensor(t)
-            if self.device is None:
-                self.device, self.dtype = t.device, t.dtype
-            if t.device != self.device or t.dtype != self.dtype:
-                raise ValueError("PruneQuantizeList: the tensors of one list share device and dtype")
-            if not t.is_contiguous():
-                raise ValueError("PruneQuantizeList needs contiguous inputs (their storage is bound)")
-            dst = torch.empty_like(t) if outs is None or outs[i] is None else outs[i]
-            self.outputs[i] = dst
-            if t.numel() == 0:
-                continue
-            rows, cols = rows_cols(t)
-            d = self._descs[self._n]
-            d.in_dev, d.out_dev, d.rows, d.cols, d.k = t.data_ptr(), dst.data_ptr(), rows, cols, int(k)
-            self._bound.append((t, t.data_ptr(), t.numel()))
-            self._n += 1
-        if self._n:
+        super().__init__(list(tensors), [int(k) for k in ks], outs)
+        if self._k:
             with torch.cuda.device(self.device):
                 self._ws = [SelectWorkspace(self.device) for _ in range(self.N_WS)]
                 self._ws_ptrs = (ctypes.c_void_p * self.N_WS)(*[w.ws.data_ptr() for w in self._ws])
@@ -660,7 +677,7 @@ class PruneQuantizeList:
             n_aux = len(self._aux) if pipelined else 0
             if n_aux and torch.cuda.is_current_stream_capturing():
                 n_aux = min(n_aux, self.CAPTURE_AUX)
-            rc = self._fn(ctypes.addressof(self._descs), self._n, DTYPE_CODE[self.dtype], self.block_size, self.mant_bits, self.epsilon,
+            rc = self._fn(self._addr, self._k, DTYPE_CODE[self.dtype], self.block_size, self.mant_bits, self.epsilon,
                           self._win.data_ptr(), ctypes.addressof(self._ws_ptrs), self.N_WS, torch.cuda.current_stream(dev).cuda_stream,
                           ctypes.addressof(self._aux) if n_aux else None, n_aux)
         if rc:
@@ -670,18 +687,13 @@ class PruneQuantizeList:
         """graph: replay a hipGraph of the whole pipeline (captured on the first such run; every pointer in it is bound --
         a tensor whose storage moved drops the graph).  Default: for lists of GRAPH_FROM tensors or more, outside any
         capture already in progress.  The ~6 host calls per tensor (2 launches, 4 event operations) otherwise cost more
-        host time than a small tensor's launches take on the device."""
-        if self._n:
-            for j, (t, ptr, n) in enumerate(self._bound):                 # follow tensors whose storage moved (see PreparedList)
-                cur = t.data_ptr()
-                if cur != ptr:
-                    if t.dtype != self.dtype or t.device != self.device or t.numel() != n or not t.is_contiguous():
-                        raise RuntimeError("PruneQuantizeList: a bound tensor changed dtype / device / size / layout since it was bound; build a new list")
-                    self._descs[j].in_dev = cur
-                    self._bound[j] = (t, cur, n)
-                    self._graph = None
+        host time than a small tensor's launches take on the device.  The capture (a device synchronise, an eager warm-up run)
+        pays only for a list that is kept and re-run: a list made for one call runs with graph=False."""
+        if self._k:
+            if self._rebind():
+                self._graph = None
             if graph is None:
-                graph = self._n >= self.GRAPH_FROM
+                graph = self._k >= self.GRAPH_FROM
             if graph and pipelined and not torch.cuda.is_current_stream_capturing():
                 if self._graph is None:
                     self._issue(True)                                     # (warm-up outside the capture)

@@ -188,7 +188,8 @@ def test_unstructured_list_pipelined_over_two_streams(dname):
     for idx, pl in prep._groups:                                            # the serial form of the same call
         for o in pl.outputs:
             o.zero_()
-        pl.run(pipelined=False)
+        for i, o in zip(idx, pl.run(pipelined=False)):
+            assert torch.equal(o.view(want[i].shape), want[i]), ("serial", i)
     for g, w in zip(prep.run(), want):
         assert torch.equal(g, w)
     # captured: the side stream joins the capture through the fork event and is joined back before the call returns
@@ -211,3 +212,46 @@ def test_unstructured_list_pipelined_over_two_streams(dname):
         c2 = dict(c, sparsity_frac=frac)
         for g, x in zip(bfp_ops.float_to_bfp_blocked_many(xs[:5], identifier='w', **c2), xs[:5]):
             assert torch.equal(g, bfp_ops.float_to_bfp_blocked(x, **c2, identifier='w'))
+
+
+@pytest.mark.parametrize("sparsity_mode", ["structured", "unstructured"])
+def test_prepared_many_quantizes_with_weight_mant_bits_under_sgd_update(sparsity_mode):
+    """sgd_update=True quantizes with weight_mant_bits (reference bfp_ops.py:104-122): PreparedMany reads it from its arguments
+    as float_to_bfp_blocked_many and the per-tensor call do (2:4, and s-first unstructured)"""
+    c = cfg(w_sparsity=True, sparsity_mode=sparsity_mode, mant_bits=3, weight_mant_bits=7, sgd_update=True)
+    shapes = [(64, 256), (33, 192), (0, 64), (128, 512)]
+    xs = [synth(r, k, torch.bfloat16, seed=300 + i).to(DEV) for i, (r, k) in enumerate(shapes)]
+    want = [bfp_ops.float_to_bfp_blocked(x, **c, identifier='w') for x in xs]
+    assert not torch.equal(want[0], bfp_ops.float_to_bfp_blocked(xs[0], **dict(c, sgd_update=False), identifier='w'))
+    many = bfp_ops.float_to_bfp_blocked_many(xs, identifier='w', **c)
+    prepared = bfp_ops.PreparedMany(xs, identifier='w', **c).run()
+    for i, (w, m, p) in enumerate(zip(want, many, prepared)):
+        assert torch.equal(m.view(torch.int16), w.view(torch.int16)), ("many", i)
+        assert torch.equal(p.view(torch.int16), w.view(torch.int16)), ("PreparedMany", i)
+
+
+def test_unstructured_many_runs_without_a_graph(monkeypatch):
+    """the one-shot float_to_bfp_blocked_many issues its unstructured list eagerly, also from GRAPH_FROM tensors on (a capture
+    pays only for a list that is kept and re-run: PreparedMany).  Empty, small and tie-heavy tensors; == the per-tensor call,
+    also from a non-default stream."""
+    shapes = [(512, 1024), (0, 64), (100, 192), (5, 64), (1024, 1024), (33, 100), (256, 256), (64, 4096), (1, 64), (777, 320)]
+    assert sum(1 for r, k in shapes if r * k) >= native.PruneQuantizeList.GRAPH_FROM
+    xs = [synth(r, k, torch.bfloat16, seed=400 + i).to(DEV) for i, (r, k) in enumerate(shapes)]
+    xs[4] = (xs[4].float() * 64).round().div(64).to(torch.bfloat16)            # a tie-heavy one
+    c = cfg(w_sparsity=True, sparsity_mode='unstructured', sparsity_frac=0.5)
+    want = [bfp_ops.float_to_bfp_blocked(x, **c, identifier='w') for x in xs]
+
+    class NoGraph:
+        def __init__(self, *args, **kwargs):
+            raise AssertionError("the one-shot list call captured a hipGraph")
+    monkeypatch.setattr(torch.cuda, "CUDAGraph", NoGraph)
+    got = bfp_ops.float_to_bfp_blocked_many(xs, identifier='w', **c)
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert g.shape == w.shape and torch.equal(g.view(torch.int16), w.view(torch.int16)), (i, shapes[i])
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        got = bfp_ops.float_to_bfp_blocked_many(xs, identifier='w', **c)
+    torch.cuda.current_stream().wait_stream(side)
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert torch.equal(g.view(torch.int16), w.view(torch.int16)), ("side-stream caller", i, shapes[i])
