@@ -293,6 +293,20 @@ int bfpq_mx8_from_hbfp(const void* codes_dev, const int8_t* exp_dev, void* out8_
  * (take bfpq_quantize_nm with int8 codes + bfpq_mx8_from_hbfp). */
 int bfpq_quantize_mx8(const void* in_dev, void* out8_dev, void* out_scale_dev, int64_t rows, int64_t cols, int dtype, int mant_bits,
                       double epsilon, const uint8_t* exp_win_dev, void* stream);
+/* the same image of a PRUNED activation (float_to_bfp_blocked with in_sparsity, identifier 'in': bfp_ops.py:129-149): N:M along the
+ * rows in either order (sparsify_first != 0: Q(S(in)), bfp_ops.py:141-144; else S(Q(in)), :146-149; S = _structured_N_M_sparsity,
+ * bfp_ops.py:73-91, ties as bfpq_quantize_nm), HBFP(mant_bits + 1) block 64, one pass.  M in {2, 4, 8} (nm_lut: bfpq_nm4_lut_host(N)
+ * for M == 4, required; bfpq_nm8_lut_host(N) or NULL for M == 8; ignored otherwise); N == M is the dense image.  Other M, cols % 64 != 0,
+ * unaligned pointers: BFPQ_E_UNSUPPORTED (take bfpq_quantize_nm with int8 codes + bfpq_mx8_from_hbfp). */
+int bfpq_quantize_mx8_nm(const void* in_dev, void* out8_dev, void* out_scale_dev, int64_t rows, int64_t cols, int dtype, int mant_bits,
+                         double epsilon, int N, int M, int sparsify_first, const uint8_t* exp_win_dev, const uint8_t* nm_lut_dev, void* stream);
+/* the image of an unstructured-pruned activation, prune first (bfp_ops.py:61-71, :141-144): the apply step of the unstructured path
+ * with the threshold that bfpq_select left in ws_dev, writing the image instead of the tensor (so the whole op is two launches:
+ * bfpq_select, then this).  Same threshold and tie rule as bfpq_quantize_threshold.  Neither output may overlap the input (the
+ * cut-segment workgroups re-read it): BFPQ_E_ARG.  cols % 64 != 0, unaligned pointers, more than 2^30 elements of a 16-bit dtype:
+ * BFPQ_E_UNSUPPORTED (take bfpq_quantize_threshold with int8 codes + bfpq_mx8_from_hbfp). */
+int bfpq_quantize_threshold_mx8(const void* in_dev, void* out8_dev, void* out_scale_dev, int64_t rows, int64_t cols, int dtype, int mant_bits,
+                                double epsilon, const uint8_t* exp_win_dev, void* ws_dev, void* stream);
 int bfpq_hbfp_linear_mx8_ok(int64_t T, int64_t N, int64_t K);   /* 1 when the kernel applies */
 int bfpq_hbfp_linear_mx8(const void* x8_dev, const void* xscale_dev, const void* w8_dev, const void* wscale_dev, const void* bias_dev,
                          void* out_dev, int64_t T, int64_t N, int64_t K, int out_dtype, void* stream);

@@ -425,27 +425,32 @@ class PackedBFP:
         N, K = self.shape
         return N % 16 == 0 and K % 128 == 0 and K >= 256
 
-    def linear_decode(self, x, x_mant_bits=7, epsilon=1e-8):
+    def linear_decode(self, x, x_mant_bits=7, epsilon=1e-8, x_sparsity=None, xq=None):
         """x @ W^T for <= 16 tokens (<= 64 with the MFMA-tiled layout) straight from the packed weight (self is W [N, K],
         4-bit codes, block 64):
         the activation is quantized to HBFP(x_mant_bits + 1) block 64 and every block's dot product is an exact
-        integer sum on the int8 matrix cores (native.hbfp_linear_decode)."""
+        integer sum on the int8 matrix cores (native.hbfp_linear_decode).  x_sparsity (native.ActSparsity): the activation
+        is pruned as well (unstructured: one threshold over all of x).  xq: its operand made beforehand (native.act_codes)."""
         assert self.code_bits == 4 and self.block_size == 64 and len(self.shape) == 2
         N, K = self.shape
+        if xq is None and x_sparsity is not None:
+            xq = native.act_codes(x.reshape(-1, K), x_mant_bits, epsilon, x_sparsity)
         if N % 16 == 0 and K % 128 == 0 and K >= 256:                  # MFMA-tiled copy of the weight, built once
             if getattr(self, "_tiles", None) is None:
                 self._tiles = native.mfma_tiles(self.codes, self.exps)
-            return native.hbfp_linear_decode_tiled(x, self._tiles[0], self._tiles[1], N, self.mant_bits, x_mant_bits, epsilon)
-        return native.hbfp_linear_decode(x, self.codes, self.exps, self.mant_bits, x_mant_bits, epsilon)
+            return native.hbfp_linear_decode_tiled(x, self._tiles[0], self._tiles[1], N, self.mant_bits, x_mant_bits, epsilon, xq=xq)
+        return native.hbfp_linear_decode(x, self.codes, self.exps, self.mant_bits, x_mant_bits, epsilon, xq=xq)
 
-    def linear(self, x, bias=None, x_mant_bits=7, epsilon=1e-8, decode_tokens=64):
+    def linear(self, x, bias=None, x_mant_bits=7, epsilon=1e-8, decode_tokens=64, x_sparsity=None):
         """F.linear(Q_in(x), W_packed, bias) for any number of tokens, W = self [N, K] (the forward of a BFPLinear whose
         weight is held packed; activations HBFP(x_mant_bits + 1), block 64, round-half-even).
         Up to `decode_tokens` tokens: chunks of 16 through the integer block-dot-product kernel (linear_decode), which
         never materialises the weight.  More tokens (prefill): when the activation mantissas fit 4 bits (x_mant_bits <= 4)
         and K % 256 == 0, the block-scaled matrix instruction multiplies the two HBFP operands as they are
         (native.hbfp_linear_mx8); otherwise the weight is decoded to its dtype once per call (bfpq_dequantize, a
-        streaming pass) and multiplied by the library GEMM."""
+        streaming pass) and multiplied by the library GEMM.
+        x_sparsity (native.ActSparsity or None): the activation is pruned as the reference's in_sparsity does (N:M per row, or
+        one unstructured threshold over ALL tokens of the call, chosen before the decode path cuts them into chunks)."""
         K = self.shape[-1]
         lead = x.shape[:-1]
         x2 = x.reshape(-1, K)
@@ -453,13 +458,22 @@ class PackedBFP:
         if T == 0:
             return x.new_zeros(lead + (self.shape[0],))
         if T <= decode_tokens and self.code_bits == 4 and self.block_size == 64 and self.shape[0] % 16 == 0 and K % 256 == 0:
-            out = self.linear_decode(x2, x_mant_bits, epsilon) if (T <= 16 or self._tiled_ok()) else \
-                torch.cat([self.linear_decode(x2[i:i + 16], x_mant_bits, epsilon) for i in range(0, T, 16)], 0)
+            if x_sparsity is None:
+                out = self.linear_decode(x2, x_mant_bits, epsilon) if (T <= 16 or self._tiled_ok()) else \
+                    torch.cat([self.linear_decode(x2[i:i + 16], x_mant_bits, epsilon) for i in range(0, T, 16)], 0)
+            else:
+                xc, xe = native.act_codes(x2, x_mant_bits, epsilon, x_sparsity)       # (all tokens at once: one threshold)
+                out = self.linear_decode(x2, x_mant_bits, epsilon, xq=(xc, xe)) if (T <= 16 or self._tiled_ok()) else \
+                    torch.cat([self.linear_decode(x2[i:i + 16], x_mant_bits, epsilon, xq=(xc[i:i + 16], xe[i:i + 16]))
+                               for i in range(0, T, 16)], 0)
         elif self.code_bits in (4, 8) and native.hbfp_linear_mx8_ok(T, self.shape[0], K, self.mant_bits, x_mant_bits, self.block_size):
             # prefill: both operands as e4m3 mantissas + E8M0 block scales on the block-scaled matrix instruction
             # (exact block dot products, fp32 across blocks); the weight's image is made once per device
-            out = native.hbfp_linear_mx8(x2, *self._mx8_image(), x_mant_bits, epsilon, bias=bias)
+            out = native.hbfp_linear_mx8(x2, *self._mx8_image(), x_mant_bits, epsilon, bias=bias, act=x_sparsity)
             return out.view(lead + (self.shape[0],))
+        elif x_sparsity is not None:
+            xq = _act_fake_quant(x2, x_mant_bits, epsilon, x_sparsity)
+            out = F.linear(xq, self.dequantize().to(x.dtype))
         else:
             xq = _quantize_nm_ref_dtype(x2, 64, x_mant_bits, epsilon, rounding_modes.DETERM)
             out = F.linear(xq, self.dequantize().to(x.dtype))
@@ -502,6 +516,15 @@ class PackedBFP:
         shape = tuple(int(d) for d in meta["shape"].split(",")) if meta["shape"] else ()
         return cls(codes.to(device), exps.to(device), shape, getattr(torch, meta["dtype"]), int(meta["mant_bits"]),
                    int(meta["block_size"]), int(meta["code_bits"]))
+
+
+def _act_fake_quant(x, mant_bits, epsilon, act):
+    """the reference's activation operand for an ActSparsity spec: float_to_bfp_blocked(x, in_sparsity=True, identifier='in') with
+    HBFP(mant_bits + 1), block 64, round-half-even"""
+    return float_to_bfp_blocked(x, mant_bits=mant_bits, epsilon=epsilon, rounding_mode=rounding_modes.DETERM, device=str(x.device), block_size=64,
+                                num_format='bfp', weight_mant_bits=0, in_sparsity=True, w_sparsity=False, grad_sparsity=False,
+                                sparsity_frac=act.frac, N=act.N, M=act.M, sparsity_num_format='bfp', first=act.first,
+                                sparsity_mode=act.mode, identifier='in')
 
 
 # ---- module / functional wrappers (reference: bfp_ops.py:151-287) -----------------------------
@@ -676,11 +699,18 @@ class _GradQuantizer(torch.autograd.Function):
 
 def _matrix_unit_ok(x, w, a, cache):
     """the cached Linear forward can run on the block-scaled matrix instruction: HBFP with block 64 and <= 4 mantissa bits (exact in e4m3),
-    round-half-even, dense activations, dense or N:M weights, a 2-D weight with K % 256 == 0, enough tokens to fill a tile row"""
+    round-half-even, dense or pruned activations (structured with 0 < N <= M, or unstructured), dense or N:M weights, a 2-D weight
+    with K % 256 == 0, enough tokens to fill a tile row"""
     if (a['num_format'] != 'bfp' or a['sparsity_num_format'] != 'bfp' or a['block_size'] != 64 or not (1 <= a['mant_bits'] <= 4)
-            or a['rounding_mode'] != rounding_modes.DETERM or a['in_sparsity'] == True or w.dim() != 2 or x.device.type != 'cuda'  # noqa: E712
+            or a['rounding_mode'] != rounding_modes.DETERM or w.dim() != 2 or x.device.type != 'cuda'
             or torch.compiler.is_compiling() or not cache.usable(w, a)):
         return False
+    if a['in_sparsity'] == True:  # noqa: E712
+        if a['sparsity_mode'] == 'structured':
+            if not (0 < a['N'] <= a['M']):
+                return False
+        elif a['sparsity_mode'] != 'unstructured' or not (0 < a['sparsity_frac'] <= 1):
+            return False
     if a['w_sparsity'] == True:  # noqa: E712
         if a['sparsity_mode'] == 'unstructured':
             if a['first'] != 's' or not (0 < a['sparsity_frac'] <= 1) or w.shape[-1] % 64:       # the fused prune + quantize launch writes the codes
@@ -701,7 +731,8 @@ def _gen_bfp_op(op, name, bfp_args, transpose=False, cache=None):
                 cache.mx_calls += 1
                 bias = args[0] if args else kwargs.get('bias')
                 w8, wsc = cache.weight_image(w, bfp_args)
-                return native.hbfp_linear_mx8(x, w8, wsc, bfp_args['mant_bits'], bfp_args['epsilon'], bias=bias)
+                return native.hbfp_linear_mx8(x, w8, wsc, bfp_args['mant_bits'], bfp_args['epsilon'], bias=bias,
+                                              act=native.ActSparsity.from_bfp_args(bfp_args))
             xq, wq = _quantize_operands(x, w, transpose, bfp_args, cache)
             return op(xq, wq, *args, **kwargs)
         xq, wq = _OperandQuantizer.apply(x, w, transpose, bfp_args, cache)

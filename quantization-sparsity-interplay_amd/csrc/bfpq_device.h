@@ -150,6 +150,12 @@ BFPQ_HIDDEN int fused_threshold_2(const FusedArgs& a, hipStream_t s);
 BFPQ_HIDDEN int fused_mx8_0(const FusedArgs& a, hipStream_t s);
 BFPQ_HIDDEN int fused_mx8_1(const FusedArgs& a, hipStream_t s);
 BFPQ_HIDDEN int fused_mx8_2(const FusedArgs& a, hipStream_t s);
+BFPQ_HIDDEN int fused_mx8_nm_0(const FusedArgs& a, int M, bool sfirst, hipStream_t s);
+BFPQ_HIDDEN int fused_mx8_nm_1(const FusedArgs& a, int M, bool sfirst, hipStream_t s);
+BFPQ_HIDDEN int fused_mx8_nm_2(const FusedArgs& a, int M, bool sfirst, hipStream_t s);
+BFPQ_HIDDEN int fused_threshold_mx8_0(const FusedArgs& a, hipStream_t s);
+BFPQ_HIDDEN int fused_threshold_mx8_1(const FusedArgs& a, hipStream_t s);
+BFPQ_HIDDEN int fused_threshold_mx8_2(const FusedArgs& a, hipStream_t s);
 BFPQ_HIDDEN int fused_batched_0(const FusedArgs& a, const BatchArgs& b, int M, bool sfirst, hipStream_t s);
 BFPQ_HIDDEN int fused_batched_1(const FusedArgs& a, const BatchArgs& b, int M, bool sfirst, hipStream_t s);
 BFPQ_HIDDEN int fused_batched_2(const FusedArgs& a, const BatchArgs& b, int M, bool sfirst, hipStream_t s);
@@ -164,6 +170,14 @@ inline int fused_threshold(int dtype, const FusedArgs& a, hipStream_t s)
 inline int fused_mx8(int dtype, const FusedArgs& a, hipStream_t s)
 {
     return dtype == BFPQ_F32 ? fused_mx8_0(a, s) : (dtype == BFPQ_F16 ? fused_mx8_1(a, s) : fused_mx8_2(a, s));
+}
+inline int fused_mx8_nm(int dtype, const FusedArgs& a, int M, bool sfirst, hipStream_t s)
+{
+    return dtype == BFPQ_F32 ? fused_mx8_nm_0(a, M, sfirst, s) : (dtype == BFPQ_F16 ? fused_mx8_nm_1(a, M, sfirst, s) : fused_mx8_nm_2(a, M, sfirst, s));
+}
+inline int fused_threshold_mx8(int dtype, const FusedArgs& a, hipStream_t s)
+{
+    return dtype == BFPQ_F32 ? fused_threshold_mx8_0(a, s) : (dtype == BFPQ_F16 ? fused_threshold_mx8_1(a, s) : fused_threshold_mx8_2(a, s));
 }
 inline int fused_batched(int dtype, const FusedArgs& a, const BatchArgs& b, int M, bool sfirst, hipStream_t s)
 {

@@ -490,19 +490,29 @@ __device__ __forceinline__ void fused_flat_body(const FusedArgs& a, [[maybe_unus
                 // (32-bit byte offsets from a uniform base: one shift per address; the launcher cuts tensors beyond 2^28 items)
                 // (A/B on one box, tools_dev/ab_packed.py: without the code stores 22.3 us, without the exponent stores no change,
                 //  non-temporal code stores +0.7 us, three sweeps of loads ahead instead of two +1.3 us)
-                if constexpr (MX8) *reinterpret_cast<uint2*>(reinterpret_cast<char*>(a.out_codes) + (uint32_t)item * 8u) = make_uint2(pack_w, pack_w2);
-                else *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(a.out_codes) + (uint32_t)item * 4u) = pack_w;
+                char* cbase = reinterpret_cast<char*>(a.out_codes);
+                uint32_t coff = (uint32_t)item * (MX8 ? 8u : 4u);
+                unsigned long long lead = 0x0101010101010101ull;
+                if constexpr (NM == -1) {
+                    // threshold mode: an ordinary workgroup's tile of the cut segment belongs to the cut workgroups -- its codes go to
+                    // the dump and its exponent store runs with no lane enabled (cut_skip is wave-uniform: the tile is the wave's)
+                    const bool skip = __builtin_amdgcn_readfirstlane((int)cut_skip) != 0;
+                    cbase = skip ? reinterpret_cast<char*>(thr.dump) : cbase;
+                    coff = skip ? (uint32_t)(threadIdx.x & 63) * 8u : coff;
+                    lead = skip ? 0ull : lead;
+                }
+                if constexpr (MX8) *reinterpret_cast<uint2*>(cbase + coff) = make_uint2(pack_w, pack_w2);
+                else *reinterpret_cast<uint32_t*>(cbase + coff) = pack_w;
                 // the block's exponent byte: ONE byte store per wave-instruction with only the first lane of each block enabled
                 // (exec narrowed around it by hand -- a branch would make hipcc drain the memory queue at the loop top; the eight
                 // v_readlane + scalar packing this replaces cost 9 vector instructions per item)
                 {
                     unsigned long long saved;
-                    const unsigned long long lead = 0x0101010101010101ull;
                     const uint32_t eoff = (uint32_t)item >> 3;
                     asm volatile("s_and_saveexec_b64 %0, %4\n\tglobal_store_byte %1, %2, %3\n\ts_mov_b64 exec, %0"
                                  : "=&s"(saved) : "v"(eoff), "v"(pack_e), "s"(a.out_exp), "s"(lead) : "memory");                 // (exec is restored inside)
                 }
-            } else if (valid) {
+            } else if (valid && !cut_skip) {
                 if constexpr (MX8) reinterpret_cast<uint2*>(a.out_codes)[item] = make_uint2(pack_w, pack_w2);
                 else reinterpret_cast<uint32_t*>(a.out_codes)[item] = pack_w;
                 if ((item & 7) == 0) a.out_exp[item >> 3] = (int8_t)pack_e;
@@ -966,6 +976,57 @@ int launch_fused_mx8(const FusedArgs& a, hipStream_t s)
         }
         return (int)hipGetLastError();
     } else return BFPQ_E_UNSUPPORTED;
+}
+
+// N:M-pruned quantize of a 16-bit tensor straight into the e4m3 + E8M0 image (M in {2, 4, 8}, either order), block = 8 lane items.
+// One lane item is two groups of 4, four groups of 2 or one group of 8: the mask runs on the input halves (first = 's') or on the
+// integer magnitudes of the lean tier (first = 'q': inside a block codes order like values).
+template <int DT, int NM, bool SFIRST>
+int launch_fused_mx8_nm_t(const FusedArgs& a, int64_t cap, hipStream_t s)
+{
+    const int64_t piece = (int64_t)1 << 27;                   // (32-bit indexing inside: see launch_fused_l)
+    for (int64_t i0 = 0; i0 < a.n_items; i0 += piece) {
+        FusedArgs b = a;
+        b.in = reinterpret_cast<const char*>(a.in) + i0 * 16;
+        b.out_codes = reinterpret_cast<char*>(a.out_codes) + i0 * 8;
+        b.out_exp = a.out_exp + i0 / 8;
+        b.n_items = a.n_items - i0 < piece ? a.n_items - i0 : piece;
+        const dim3 grid(grid_for_cap(b.n_items, cap)), block(kThreads);
+        hipLaunchKernelGGL((k_fused_flat<DT, NM, SFIRST, false, 8, false, false, 8>), grid, block, 0, s, b);
+    }
+    return (int)hipGetLastError();
+}
+
+template <int DT>
+int launch_fused_mx8_nm(const FusedArgs& a, int M, bool sfirst, hipStream_t s)
+{
+    if constexpr (Traits<DT>::VEC == 8) {
+        // grid caps, in units of the drop-in cap kMaxGrid (1024): see DESIGN §5c for the sweep they come from
+        const int64_t cap = M == 8 ? (int64_t)kMaxGrid * 2 : (int64_t)kMaxGrid * 43 / 16;
+        if (M == 2) return sfirst ? launch_fused_mx8_nm_t<DT, 2, true>(a, cap, s) : launch_fused_mx8_nm_t<DT, 2, false>(a, cap, s);
+        if (M == 4) return sfirst ? launch_fused_mx8_nm_t<DT, 4, true>(a, cap, s) : launch_fused_mx8_nm_t<DT, 4, false>(a, cap, s);
+        if (M == 8) return sfirst ? launch_fused_mx8_nm_t<DT, 8, true>(a, cap, s) : launch_fused_mx8_nm_t<DT, 8, false>(a, cap, s);
+        return BFPQ_E_UNSUPPORTED;
+    } else {
+        (void)a; (void)M; (void)sfirst; (void)s;
+        return BFPQ_E_UNSUPPORTED;
+    }
+}
+
+// prune by the global threshold in a.selws, then quantize straight into the e4m3 + E8M0 image (16-bit dtypes; the first kCutWGs
+// workgroups own the cut segment).  32-bit indexing inside and no pieces (the cut bookkeeping is in global item numbers): the
+// caller keeps n_items <= 2^27.
+template <int DT>
+int launch_fused_threshold_mx8(const FusedArgs& a, hipStream_t s)
+{
+    if constexpr (Traits<DT>::VEC == 8) {
+        const dim3 grid(kCutWGs + grid_for_cap(a.n_items, (int64_t)kMaxGrid * 43 / 16)), block(kThreads);
+        hipLaunchKernelGGL((k_fused_flat<DT, -1, true, false, 8, false, false, 8>), grid, block, 0, s, a);
+        return (int)hipGetLastError();
+    } else {
+        (void)a; (void)s;
+        return BFPQ_E_UNSUPPORTED;
+    }
 }
 
 template <int DT>

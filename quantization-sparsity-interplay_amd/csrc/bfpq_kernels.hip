@@ -736,6 +736,67 @@ int bfpq_quantize_mx8(const void* in, void* out8, void* out_scale, int64_t rows,
     return fused_mx8(dtype, a, (hipStream_t)stream);
 }
 
+int bfpq_quantize_mx8_nm(const void* in, void* out8, void* out_scale, int64_t rows, int64_t cols, int dtype, int mant_bits, double epsilon,
+                         int N, int M, int sparsify_first, const uint8_t* exp_win, const uint8_t* nm_lut, void* stream)
+{
+    if (dtype < 0 || dtype > 2 || rows < 0 || cols < 0 || mant_bits < 1 || mant_bits > 4) return BFPQ_E_ARG;
+    if (M < 1 || N < 1 || N > M) return BFPQ_E_ARG;
+    if (M > 64) return BFPQ_E_UNSUPPORTED;
+    if (rows * cols == 0) return 0;
+    if (!in || !out8 || !out_scale || !exp_win) return BFPQ_E_ARG;
+    if (N == M) return bfpq_quantize_mx8(in, out8, out_scale, rows, cols, dtype, mant_bits, epsilon, exp_win, stream);   // keeps everything
+    if (!(M == 2 || M == 4 || M == 8)) return BFPQ_E_UNSUPPORTED;                      // (callers take bfpq_quantize_nm + bfpq_mx8_from_hbfp)
+    if (M == 4 && !nm_lut) return BFPQ_E_ARG;
+    if (cols % 64 != 0) return BFPQ_E_UNSUPPORTED;
+    if ((reinterpret_cast<uintptr_t>(in) & 15u) || (reinterpret_cast<uintptr_t>(out8) & 7u) || (reinterpret_cast<uintptr_t>(out_scale) & 7u)) return BFPQ_E_UNSUPPORTED;
+    const float eps_dt = h_round((float)epsilon, dtype);
+    FusedArgs a;
+    a.in = in; a.out_deq = nullptr; a.out_codes = out8; a.out_exp = reinterpret_cast<int8_t*>(out_scale);
+    a.n_items = rows * cols / dtype_vec(dtype);
+    a.exp_win = exp_win; a.nm_lut = nm_lut; a.seed = 0; a.eps_dt = eps_dt;
+    a.lpb = 64 / dtype_vec(dtype);
+    a.mant_bits = mant_bits; a.N = N; a.code_bits = 8;
+    a.force_slow = 0;
+    set_hot16(a, dtype, mant_bits, eps_dt);
+    a.selws = nullptr;
+    if (dtype == BFPQ_F32) {                                                            // fp32: the general kernel, image bytes in its store epilogue
+        a.code_bits = kCodeBitsE4M3;
+        return fused_launch(dtype, a, M, sparsify_first != 0, (hipStream_t)stream);
+    }
+    return fused_mx8_nm(dtype, a, M, sparsify_first != 0, (hipStream_t)stream);
+}
+
+int bfpq_quantize_threshold_mx8(const void* in, void* out8, void* out_scale, int64_t rows, int64_t cols, int dtype, int mant_bits, double epsilon,
+                                const uint8_t* exp_win, void* ws, void* stream)
+{
+    if (dtype < 0 || dtype > 2 || rows < 0 || cols < 0 || mant_bits < 1 || mant_bits > 4) return BFPQ_E_ARG;
+    if (rows * cols == 0) return 0;
+    if (!in || !out8 || !out_scale || !exp_win || !ws) return BFPQ_E_ARG;
+    // the cut-segment workgroups re-read the input while the others write: no output may overlap it
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), i1 = i0 + (uintptr_t)(rows * cols * dtype_size(dtype));
+    auto overlaps = [&](const void* p, int64_t n) { const uintptr_t o0 = reinterpret_cast<uintptr_t>(p); return o0 < i1 && i0 < o0 + (uintptr_t)n; };
+    if (overlaps(out8, rows * cols) || overlaps(out_scale, rows * (cols / 64 > 0 ? cols / 64 : 1))) return BFPQ_E_ARG;
+    if (cols % 64 != 0) return BFPQ_E_UNSUPPORTED;
+    if ((reinterpret_cast<uintptr_t>(in) & 15u) || (reinterpret_cast<uintptr_t>(out8) & 7u) || (reinterpret_cast<uintptr_t>(out_scale) & 7u)) return BFPQ_E_UNSUPPORTED;
+    const int64_t n_items = rows * cols / dtype_vec(dtype);
+    if (dtype != BFPQ_F32 && n_items > ((int64_t)1 << 27)) return BFPQ_E_UNSUPPORTED;   // (32-bit indexing, no pieces: see launch_fused_threshold_mx8)
+    const float eps_dt = h_round((float)epsilon, dtype);
+    FusedArgs a;
+    a.in = in; a.out_deq = nullptr; a.out_codes = out8; a.out_exp = reinterpret_cast<int8_t*>(out_scale);
+    a.n_items = n_items;
+    a.exp_win = exp_win; a.nm_lut = nullptr; a.seed = 0; a.eps_dt = eps_dt;
+    a.lpb = 64 / dtype_vec(dtype);
+    a.mant_bits = mant_bits; a.N = 0; a.code_bits = 8;
+    a.force_slow = 0;
+    set_hot16(a, dtype, mant_bits, eps_dt);
+    a.selws = (SelWs*)ws;
+    if (dtype == BFPQ_F32) {
+        a.code_bits = kCodeBitsE4M3;
+        return fused_threshold(dtype, a, (hipStream_t)stream);
+    }
+    return fused_threshold_mx8(dtype, a, (hipStream_t)stream);
+}
+
 int bfpq_fake_quantize(const bfpq_plan* p, const void* in, void* out, int64_t rows, int64_t cols, void* stream)
 {
     if (!p) return BFPQ_E_ARG;

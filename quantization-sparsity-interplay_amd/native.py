@@ -4,6 +4,7 @@ PyTorch is plumbing here: it owns device memory and the HIP stream; every byte o
 hot path happens in the HIP kernels of csrc/bfpq_kernels.hip.  There is NO CPU fallback: if the
 library is missing, or a tensor is not on a ROCm device, the calls raise.
 """
+import collections
 import ctypes
 import os
 import subprocess
@@ -102,6 +103,8 @@ def load_library():
         L.bfpq_hbfp_linear_decode_tiled.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, i32, vp]
         L.bfpq_mx8_from_hbfp.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, vp]
         L.bfpq_quantize_mx8.argtypes = [vp, vp, vp, i64, i64, i32, i32, dbl, vp, vp]
+        L.bfpq_quantize_mx8_nm.argtypes = [vp, vp, vp, i64, i64, i32, i32, dbl, i32, i32, i32, vp, vp, vp]
+        L.bfpq_quantize_threshold_mx8.argtypes = [vp, vp, vp, i64, i64, i32, i32, dbl, vp, vp, vp]
         L.bfpq_hbfp_linear_mx8_ok.argtypes = [i64, i64, i64]
         L.bfpq_hbfp_linear_mx8.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, vp]
         L.bfpq_hbfp_linear_mx8_parts.argtypes = [i64, i64, i64]
@@ -112,7 +115,7 @@ def load_library():
                      "bfpq_threshold_apply", "bfpq_quantize_threshold", "bfpq_int_quantize", "bfpq_dequantize", "bfpq_hbfp_linear_slices",
                      "bfpq_hbfp_linear_decode", "bfpq_hbfp_linear_tiled_ok", "bfpq_hbfp_linear_decode_tiled",
                      "bfpq_mx8_from_hbfp", "bfpq_quantize_mx8", "bfpq_hbfp_linear_mx8_ok", "bfpq_hbfp_linear_mx8",
-                     "bfpq_hbfp_linear_mx8_parts", "bfpq_hbfp_linear_mx8_splitk"):
+                     "bfpq_hbfp_linear_mx8_parts", "bfpq_hbfp_linear_mx8_splitk", "bfpq_quantize_mx8_nm", "bfpq_quantize_threshold_mx8"):
             getattr(L, name).restype = i32
         _lib = L
         return _lib
@@ -122,7 +125,7 @@ EXPORTED_SYMBOLS = ("bfpq_hbfp_linear_mx8_parts", "bfpq_hbfp_linear_mx8_splitk",
                     "bfpq_nm_prune_mask_host", "bfpq_quantize_nm", "bfpq_fake_quantize", "bfpq_fake_quantize_batched", "bfpq_fake_quantize_list", "bfpq_is_fused", "bfpq_nm_sparsify",
                     "bfpq_select_passes", "bfpq_select", "bfpq_select_hist", "bfpq_select_resolve", "bfpq_select_resolve_ex", "bfpq_select_reset",
                     "bfpq_prune_quantize", "bfpq_prune_quantize_batched", "bfpq_prune_quantize_list",
-                    "bfpq_threshold_apply", "bfpq_quantize_threshold")
+                    "bfpq_threshold_apply", "bfpq_quantize_threshold", "bfpq_quantize_mx8_nm", "bfpq_quantize_threshold_mx8")
 
 
 def check(rc, what):
@@ -821,8 +824,9 @@ def mfma_tiles(wcodes, wexps):
     return t, e
 
 
-def hbfp_linear_decode_tiled(x, wtiles, wexpt, N, w_mant_bits, x_mant_bits=7, epsilon=1e-8, out_dtype=None):
-    """hbfp_linear_decode on the MFMA-tiled weight (see mfma_tiles)"""
+def hbfp_linear_decode_tiled(x, wtiles, wexpt, N, w_mant_bits, x_mant_bits=7, epsilon=1e-8, out_dtype=None, xq=None):
+    """hbfp_linear_decode on the MFMA-tiled weight (see mfma_tiles).  xq: the activation operand made beforehand (act_codes: int8
+    codes [T, K], int8 exponents [T, K/64]), e.g. pruned over more tokens than this call takes; x then only gives shape and dtype."""
     require_device_tensor(x)
     L = load_library()
     K = x.shape[-1]
@@ -832,10 +836,13 @@ def hbfp_linear_decode_tiled(x, wtiles, wexpt, N, w_mant_bits, x_mant_bits=7, ep
     dev = x.device
     out_dtype = out_dtype or x.dtype
     with torch.cuda.device(dev):
-        xc16 = torch.empty((T, K), dtype=torch.int8, device=dev)          # (token columns past T re-read row T-1: no padding rows)
-        xe16 = torch.empty((T, K // 64), dtype=torch.int8, device=dev)
-        quantize_nm(x.reshape(T, K), 64, x_mant_bits, epsilon, want_deq=False, code_bits=8, want_exp=True,
-                    codes_out=xc16, exps_out=xe16)
+        if xq is not None:
+            xc16, xe16 = xq[0].contiguous(), xq[1].contiguous()
+        else:
+            xc16 = torch.empty((T, K), dtype=torch.int8, device=dev)          # (token columns past T re-read row T-1: no padding rows)
+            xe16 = torch.empty((T, K // 64), dtype=torch.int8, device=dev)
+            quantize_nm(x.reshape(T, K), 64, x_mant_bits, epsilon, want_deq=False, code_bits=8, want_exp=True,
+                        codes_out=xc16, exps_out=xe16)
         out = torch.empty((T, N), dtype=out_dtype, device=dev)
         check(L.bfpq_hbfp_linear_decode_tiled(_ptr(wtiles), _ptr(wexpt), _ptr(xc16), _ptr(xe16), _ptr(out), T, N, K,
                                               DTYPE_CODE[out_dtype], int(w_mant_bits), int(x_mant_bits), _stream(x)),
@@ -843,9 +850,10 @@ def hbfp_linear_decode_tiled(x, wtiles, wexpt, N, w_mant_bits, x_mant_bits=7, ep
     return out.view(tuple(x.shape[:-1]) + (N,))
 
 
-def hbfp_linear_decode(x, wcodes, wexps, w_mant_bits, x_mant_bits=7, epsilon=1e-8, out_dtype=None):
+def hbfp_linear_decode(x, wcodes, wexps, w_mant_bits, x_mant_bits=7, epsilon=1e-8, out_dtype=None, xq=None):
     """out = x @ W^T for <= 16 tokens, W given as packed HBFP (4-bit codes [N, K/2], int8 exponents [N, K/64], block 64),
-    x quantized on the fly to HBFP(x_mant_bits + 1) block 64; integer block dot products on the int8 matrix cores."""
+    x quantized on the fly to HBFP(x_mant_bits + 1) block 64; integer block dot products on the int8 matrix cores.
+    xq: the activation operand made beforehand, as in hbfp_linear_decode_tiled."""
     require_device_tensor(x)
     L = load_library()
     K = x.shape[-1]
@@ -861,8 +869,12 @@ def hbfp_linear_decode(x, wcodes, wexps, w_mant_bits, x_mant_bits=7, epsilon=1e-
         # each token's results live in its own lanes and rows >= T are never read back)
         xc16 = torch.empty((16, K), dtype=torch.int8, device=dev)
         xe16 = torch.empty((16, K // 64), dtype=torch.int8, device=dev)
-        quantize_nm(x.reshape(T, K), 64, x_mant_bits, epsilon, want_deq=False, code_bits=8, want_exp=True,
-                    codes_out=xc16[:T], exps_out=xe16[:T])
+        if xq is not None:
+            xc16[:T].copy_(xq[0])
+            xe16[:T].copy_(xq[1])
+        else:
+            quantize_nm(x.reshape(T, K), 64, x_mant_bits, epsilon, want_deq=False, code_bits=8, want_exp=True,
+                        codes_out=xc16[:T], exps_out=xe16[:T])
         slabs = torch.empty((slices, 16, N), dtype=torch.float32, device=dev)
         out = torch.empty((T, N), dtype=out_dtype, device=dev)
         check(L.bfpq_hbfp_linear_decode(_ptr(wcodes.contiguous()), _ptr(wexps.contiguous()), _ptr(xc16), _ptr(xe16), _ptr(out),
@@ -886,27 +898,118 @@ def mx8_from_hbfp(codes, exps, cols, mant_bits, code_bits):
     return o8, osc
 
 
-def quantize_mx8(x, mant_bits, epsilon=1e-8):
+class ActSparsity(collections.namedtuple("ActSparsity", "mode N M frac first")):
+    """How an activation operand is pruned before (first = 's') or after (first = 'q') its HBFP quantization (as in the reference, any
+    `first` other than 's' quantizes first): the reference's
+    in_sparsity with identifier 'in' (bfp_ops.py:129-149).  mode 'structured' (N of every M along the rows) or 'unstructured'
+    (the int(numel * frac) smallest magnitudes of the whole tensor).  Hashable: part of the activation-image memo key.
+    None stands for dense activations."""
+
+    @classmethod
+    def from_bfp_args(cls, a):
+        """the spec of a bfp_args dict (bfp_ops.unpack_bfp_args), or None when its activations are dense"""
+        if a.get('in_sparsity') != True:  # noqa: E712  (the reference compares with ==)
+            return None
+        mode = a.get('sparsity_mode')
+        if mode == 'structured':
+            N, M = int(a['N']), int(a['M'])
+            if not 0 < N <= M:
+                raise ValueError(f"in_sparsity with N:M = {N}:{M}")
+            return None if N == M else cls('structured', N, M, 0.0, 's' if a.get('first') == 's' else 'q')
+        if mode == 'unstructured':
+            frac = float(a['sparsity_frac'])
+            if not frac > 0:
+                raise ValueError(f"in_sparsity with sparsity_frac = {frac}")
+            return cls('unstructured', 0, 0, frac, 's' if a.get('first') == 's' else 'q')
+        raise ValueError(f'Unknown sparsity mode: {mode} given as argument')
+
+    def as_dict(self):
+        return dict(mode=self.mode, N=int(self.N), M=int(self.M), frac=float(self.frac), first=self.first)
+
+    @classmethod
+    def from_dict(cls, d):
+        return None if d is None else cls(d['mode'], int(d['N']), int(d['M']), float(d['frac']), d['first'])
+
+
+def _act_workspace(device):
+    from .bfp.bfp_ops import _workspace            # (the per-stream select workspaces, capture-safe; a late import: bfp_ops imports this module)
+    return _workspace(device)
+
+
+def _prune_count(t, frac):
+    k = int(t.numel() * frac)
+    if k > t.numel():
+        raise RuntimeError("selected index k out of range")      # what torch.topk raises in the reference
+    return k
+
+
+def act_codes(x, mant_bits, epsilon, act, codes_out=None, exps_out=None):
+    """int8 codes [T, K] + int8 exponents [T, K/64] of the activation x [T, K], HBFP(mant_bits + 1) block 64, pruned by `act`
+    (ActSparsity or None) -- the operands of the decode kernels.  Unstructured pruning picks ONE threshold over all of x."""
+    T, K = x.shape
+    dev = x.device
+    if act is None or act.mode == 'structured':
+        N, M = (act.N, act.M) if act is not None else (0, 0)
+        _, c, e = quantize_nm(x, 64, mant_bits, epsilon, N=N, M=M, sparsify_first=(act is None or act.first == 's'), want_deq=False,
+                              code_bits=8, want_exp=True, codes_out=codes_out, exps_out=exps_out)
+        return c, e
+    k = _prune_count(x, act.frac)
+    ws = _act_workspace(dev)
+    if act.first == 's':
+        select_threshold(x, k, ws)
+        _, c, e = quantize_threshold(x, ws, 64, mant_bits, epsilon, want_deq=False, code_bits=8, want_exp=True)
+    else:
+        # S(Q(x)): quantize (the tensor and its codes at once), select over the quantized tensor, prune it; a pruned element's code is
+        # zeroed -- the exponents stay those of Q(x), so nothing depends on re-quantizing the pruned tensor
+        q, c, e = quantize_nm(x, 64, mant_bits, epsilon, code_bits=8, want_exp=True)
+        select_threshold(q, k, ws)
+        sq = threshold_apply(q, ws).view(T, K)
+        c = torch.where(sq == 0, torch.zeros((), dtype=c.dtype, device=dev), c)
+    if codes_out is not None:
+        codes_out.copy_(c)
+        exps_out.copy_(e)
+        return codes_out, exps_out
+    return c, e
+
+
+def quantize_mx8(x, mant_bits, epsilon=1e-8, act=None):
     """a 2-D tensor [T, K] -> its HBFP(mant_bits + 1) block-64 image for the block-scaled matrix unit: e4m3 bytes [T, K] + E8M0
-    scales [T, K/64], in one pass (bfpq_quantize_mx8); the two-step route (int8 codes + mx8_from_hbfp) only for shapes it refuses."""
+    scales [T, K/64], in one pass (bfpq_quantize_mx8); the two-step route (int8 codes + mx8_from_hbfp) only for shapes it refuses.
+    act (ActSparsity): the image of the pruned activation -- N:M in one pass (bfpq_quantize_mx8_nm), unstructured prune-first as
+    selection + the threshold-mode image (bfpq_quantize_threshold_mx8); what those refuse (and quantize-first unstructured) goes
+    through the codes (act_codes) + mx8_from_hbfp."""
     require_device_tensor(x)
     L = load_library()
     T, K = x.shape
     dev = x.device
     with torch.cuda.device(dev):
-        if K % 64 == 0:
+        if K % 64 == 0 and (act is None or act.mode == 'structured' or act.first == 's'):
             x = x.contiguous()
             x8 = torch.empty((T, K), dtype=torch.uint8, device=dev)
             xs = torch.empty((T, K // 64), dtype=torch.uint8, device=dev)
-            rc = L.bfpq_quantize_mx8(_ptr(x), _ptr(x8), _ptr(xs), T, K, DTYPE_CODE[x.dtype], int(mant_bits), float(epsilon),
-                                     _ptr(exp_window_dev(x.dtype, dev)), _stream(x))
+            win = _ptr(exp_window_dev(x.dtype, dev))
+            if act is None:
+                rc = L.bfpq_quantize_mx8(_ptr(x), _ptr(x8), _ptr(xs), T, K, DTYPE_CODE[x.dtype], int(mant_bits), float(epsilon), win, _stream(x))
+            elif act.mode == 'structured':
+                lut = nm4_lut_dev(act.N, dev) if act.M == 4 else (nm8_lut_dev(act.N, dev) if (act.M == 8 and USE_NM8_TABLE) else None)
+                rc = L.bfpq_quantize_mx8_nm(_ptr(x), _ptr(x8), _ptr(xs), T, K, DTYPE_CODE[x.dtype], int(mant_bits), float(epsilon),
+                                            int(act.N), int(act.M), 1 if act.first == 's' else 0, win, _ptr(lut), _stream(x))
+            else:
+                k = _prune_count(x, act.frac)
+                ws = _act_workspace(dev)
+                select_threshold(x, k, ws)
+                rc = L.bfpq_quantize_threshold_mx8(_ptr(x), _ptr(x8), _ptr(xs), T, K, DTYPE_CODE[x.dtype], int(mant_bits), float(epsilon),
+                                                   win, _ptr(ws.ws), _stream(x))
+                if rc == BFPQ_E_UNSUPPORTED:               # (the selection stands: the codes route below applies the same threshold)
+                    _, xc, xe = quantize_threshold(x, ws, 64, mant_bits, epsilon, want_deq=False, code_bits=8, want_exp=True)
+                    return mx8_from_hbfp(xc, xe, K, mant_bits, 8)
             if rc == 0:
                 return x8, xs
             if rc != BFPQ_E_UNSUPPORTED:
                 check(rc, "bfpq_quantize_mx8")
         xc = torch.empty((T, K), dtype=torch.int8, device=dev)
         xe = torch.empty((T, K // 64), dtype=torch.int8, device=dev)
-        quantize_nm(x, 64, mant_bits, epsilon, want_deq=False, code_bits=8, want_exp=True, codes_out=xc, exps_out=xe)
+        act_codes(x, mant_bits, epsilon, act, codes_out=xc, exps_out=xe)
         return mx8_from_hbfp(xc, xe, K, mant_bits, 8)
 
 
@@ -923,7 +1026,7 @@ def tensor_version(t):
         return None
 
 
-def _shared_image(x2, mant_bits, epsilon):
+def _shared_image(x2, mant_bits, epsilon, act=None):
     """quantize_mx8 with a one-entry memo per device: the projections that share an input (q/k/v, gate/up) quantize it once.
     The entry holds the tensor it was made from, so that tensor's memory cannot be handed to another tensor while the entry
     lives; the key includes the in-place version counter.  The memo is bypassed -- the image is made afresh and nothing is
@@ -933,16 +1036,16 @@ def _shared_image(x2, mant_bits, epsilon):
     this library's own `out=` arguments) are outside what the key can detect: callers that mutate an activation that way
     between two projections must call forget_shared_images() (PackedBFP.linear and the cached BFPLinear never do)."""
     if not SHARE_ACT_IMAGE or torch.cuda.is_current_stream_capturing():
-        return quantize_mx8(x2, mant_bits, epsilon)
+        return quantize_mx8(x2, mant_bits, epsilon, act)
     ver = None if x2.is_inference() else tensor_version(x2)
     if ver is None:
-        return quantize_mx8(x2, mant_bits, epsilon)
+        return quantize_mx8(x2, mant_bits, epsilon, act)
     key = (x2.data_ptr(), ver, tuple(x2.shape), tuple(x2.stride()), x2.dtype, int(mant_bits), float(epsilon),
-           torch.cuda.current_stream(x2.device).cuda_stream)
+           torch.cuda.current_stream(x2.device).cuda_stream, act)          # (act: the activation's pruning is part of its image)
     hit = _last_image.get(x2.device)
     if hit is not None and hit[0] == key:
         return hit[2]
-    img = quantize_mx8(x2, mant_bits, epsilon)
+    img = quantize_mx8(x2, mant_bits, epsilon, act)
     _last_image[x2.device] = (key, x2, img)
     return img
 
@@ -956,10 +1059,11 @@ def hbfp_linear_mx8_ok(T, N, K, w_mant_bits, x_mant_bits, block_size=64):
     return block_size == 64 and 1 <= w_mant_bits <= 4 and 1 <= x_mant_bits <= 4 and bool(load_library().bfpq_hbfp_linear_mx8_ok(T, N, K))
 
 
-def hbfp_linear_mx8(x, w8, wscale, x_mant_bits, epsilon=1e-8, bias=None, out_dtype=None):
+def hbfp_linear_mx8(x, w8, wscale, x_mant_bits, epsilon=1e-8, bias=None, out_dtype=None, act=None):
     """out = Q(x) @ W^T (+ bias) for any number of tokens on the block-scaled matrix instruction: x is quantized to
     HBFP(x_mant_bits + 1) block 64 (int8 codes + exponents), turned into its e4m3 / E8M0 image and multiplied with the
-    weight's image (mx8_from_hbfp of the packed weight, made once)."""
+    weight's image (mx8_from_hbfp of the packed weight, made once).  act (ActSparsity or None): the activation is pruned first
+    (quantize_mx8)."""
     require_device_tensor(x)
     L = load_library()
     K = x.shape[-1]
@@ -970,7 +1074,7 @@ def hbfp_linear_mx8(x, w8, wscale, x_mant_bits, epsilon=1e-8, bias=None, out_dty
     dev = x.device
     out_dtype = out_dtype or x.dtype
     with torch.cuda.device(dev):
-        x8, xs = _shared_image(x.reshape(T, K), x_mant_bits, epsilon)
+        x8, xs = _shared_image(x.reshape(T, K), x_mant_bits, epsilon, act)
         out = torch.empty((T, N), dtype=out_dtype, device=dev)
         if bias is not None:
             bias = bias.to(out_dtype).contiguous()

@@ -6,6 +6,7 @@ gate/up/down become BFPLinear, lm_head stays nn.Linear, llama/modeling_llama.py:
 model the same result is obtained by swapping the modules after construction."""
 import torch
 
+from . import native
 from .bfp import bfp_ops
 
 
@@ -68,12 +69,14 @@ class PackedBFPLinear(torch.nn.Module):
     quantized ONCE.  Up to 64 tokens the product comes straight from the codes (integer block dot products on the int8
     matrix cores, PackedBFP.linear_decode); more tokens decode the weight and use the library GEMM.
     The codes and exponents are registered buffers (`codes`, `exps`): they follow .to() / .cuda(), appear in state_dict()
-    and load back with load_state_dict(); shape / dtype / mantissa width travel as extra state."""
+    and load back with load_state_dict(); shape / dtype / mantissa width / activation pruning travel as extra state.
+    x_sparsity (native.ActSparsity or None): the activations are pruned as the reference's in_sparsity does."""
 
-    def __init__(self, packed, bias=None, x_mant_bits=7, epsilon=1e-8):
+    def __init__(self, packed, bias=None, x_mant_bits=7, epsilon=1e-8, x_sparsity=None):
         super().__init__()
         self.out_features, self.in_features = packed.shape
         self.x_mant_bits, self.epsilon = int(x_mant_bits), float(epsilon)
+        self.x_sparsity = x_sparsity
         self.register_buffer("codes", packed.codes)
         self.register_buffer("exps", packed.exps)
         self._meta = dict(shape=list(packed.shape), dtype=str(packed.dtype).replace("torch.", ""), mant_bits=packed.mant_bits,
@@ -93,19 +96,22 @@ class PackedBFPLinear(torch.nn.Module):
         return p
 
     def get_extra_state(self):
-        return dict(self._meta, x_mant_bits=self.x_mant_bits, epsilon=self.epsilon)
+        return dict(self._meta, x_mant_bits=self.x_mant_bits, epsilon=self.epsilon,
+                    x_sparsity=None if self.x_sparsity is None else self.x_sparsity.as_dict())
 
     def set_extra_state(self, state):
         self._meta = {k: state[k] for k in ('shape', 'dtype', 'mant_bits', 'block_size', 'code_bits')}
         self.x_mant_bits, self.epsilon = int(state['x_mant_bits']), float(state['epsilon'])
+        self.x_sparsity = native.ActSparsity.from_dict(state.get('x_sparsity'))     # (a state saved before activation pruning: dense)
         self._packed = None
 
     @classmethod
     def from_linear(cls, lin, bfp_args):
         """weight -> float_to_bfp_packed with the module's config (format 'bfp', block 64, mant_bits <= 3, round-half-even;
         N:M from the w_sparsity keys, order from `first`); activations use mant_bits of the same config.  Unstructured weight pruning is
-        packed for first='s' (prune, then quantize: one fused launch writes the codes).  Configurations this module cannot reproduce
-        (unstructured pruning after quantization, pruned activations, stochastic rounding) are refused."""
+        packed for first='s' (prune, then quantize: one fused launch writes the codes).  Pruned activations (in_sparsity: N:M or
+        unstructured, either order, the same keys) are pruned in every forward, as the reference does.  Configurations this module
+        cannot reproduce (unstructured WEIGHT pruning after quantization, stochastic rounding) are refused."""
         a = bfp_ops.unpack_bfp_args(dict(bfp_args))
         assert a['num_format'] == 'bfp' and a['sparsity_num_format'] == 'bfp' and a['block_size'] == 64 and 1 <= a['mant_bits'] <= 3, \
             "PackedBFPLinear holds 4-bit codes: an HBFP config with block_size 64 and mant_bits <= 3 (HBFP4)"
@@ -113,22 +119,22 @@ class PackedBFPLinear(torch.nn.Module):
             raise ValueError("PackedBFPLinear: unstructured pruning AFTER quantization (first='q') is not packed here")
         if a['w_sparsity'] and a['sparsity_mode'] not in ('structured', 'unstructured'):
             raise ValueError('Sparsity mode not implemented')
-        if a['in_sparsity']:
-            raise ValueError("PackedBFPLinear quantizes activations densely: in_sparsity is not reproduced")
         if a['rounding_mode'] != 'determ':
             raise ValueError("PackedBFPLinear packs with round-half-even: rounding_mode must be 'determ'")
+        act = native.ActSparsity.from_bfp_args(a)
         sp = a['w_sparsity'] and a['sparsity_mode'] == 'structured'
         if a['w_sparsity'] and a['sparsity_mode'] == 'unstructured':
             pw = bfp_ops.PackedBFP.quantize_unstructured(lin.weight.detach(), a['mant_bits'], 64, a['sparsity_frac'], a['epsilon'])
-            return cls(pw, lin.bias, a['mant_bits'], a['epsilon'])
+            return cls(pw, lin.bias, a['mant_bits'], a['epsilon'], act)
         pw = bfp_ops.PackedBFP.quantize(lin.weight.detach(), a['mant_bits'], 64, a['epsilon'], a['N'] if sp else 0, a['M'] if sp else 0, a['first'])
-        return cls(pw, lin.bias, a['mant_bits'], a['epsilon'])
+        return cls(pw, lin.bias, a['mant_bits'], a['epsilon'], act)
 
     def forward(self, x):
-        return self.packed.linear(x, self.bias, self.x_mant_bits, self.epsilon)
+        return self.packed.linear(x, self.bias, self.x_mant_bits, self.epsilon, x_sparsity=self.x_sparsity)
 
     def extra_repr(self):
-        return f"in_features={self.in_features}, out_features={self.out_features}, packed_bytes={self.packed.nbytes()}"
+        act = "" if self.x_sparsity is None else f", x_sparsity={tuple(self.x_sparsity)}"
+        return f"in_features={self.in_features}, out_features={self.out_features}, packed_bytes={self.packed.nbytes()}{act}"
 
 
 def pack_linear_layers(model, bfp_args, skip=("lm_head", "classifier", "score")):
