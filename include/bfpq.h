@@ -258,6 +258,8 @@ int bfpq_expand24(const void* vals_dev, const void* idx_dev, void* codes_dev, in
  * bfp_ops.py:187-190): out[t][n] = sum_k x[t][k] W[n][k], T <= 16 tokens, W packed HBFP
  * (4-bit codes, mant_bits <= 3) and x packed HBFP (int8 codes, mant_bits <= 7), both block 64, exact integer
  * block sums on the int8 matrix cores, fp32 across blocks.  N % 16 == 0, K % 256 == 0.
+ * NaN blocks propagate: a block whose exponent byte is -128 (the NaN block marker bfpq_quantize_nm writes), in x or in W,
+ * makes every output it contributes to NaN, as the reference's product of the fake-quantised tensors does.
  *   xcodes_dev [16, K] int8 and xexp_dev [16, K/64] (rows >= T: any content, their results are discarded),
  *   slabs_dev [bfpq_hbfp_linear_slices(N, K), 16, N] fp32 scratch, out_dev [T, N] of out_dtype. */
 int bfpq_hbfp_linear_slices(int64_t N, int64_t K);
@@ -272,7 +274,7 @@ int bfpq_hbfp_linear_decode(const void* wcodes_dev, const int8_t* wexp_dev, cons
  * Up to 64 tokens per call here (groups of 16 tokens walk the weight one after the other inside the one launch; xcodes_dev /
  * xexp_dev then hold T rows).
  * One launch, no workspace: each workgroup owns one or two 16-row tiles, its waves split K and are summed in slice order
- * through LDS, so the result is reproducible. */
+ * through LDS, so the result is reproducible.  NaN blocks propagate as in bfpq_hbfp_linear_decode. */
 int bfpq_hbfp_linear_tiled_ok(int64_t N, int64_t K);   /* 1 when the tiled layout applies to [N, K] */
 int bfpq_hbfp_linear_decode_tiled(const void* wtiles_dev, const void* wexpt_dev, const int8_t* xcodes_dev, const int8_t* xexp_dev,
                                   void* out_dev, int64_t T, int64_t N, int64_t K,

@@ -73,7 +73,9 @@ __global__ void __launch_bounds__(256) k_hbfp_linear_decode(const uint8_t* __res
             for (int j = 0; j < 4; j++) {
                 const int we_b = (int)(int8_t)(we[j] >> (8 * bb));
                 const int cj = j == 0 ? c.x : (j == 1 ? c.y : (j == 2 ? c.z : c.w));
-                acc[j] += (float)(cj - 8 * xs_b) * ldexpf(1.0f, we_b - wm + xe_b - xm);
+                // -128 marks a NaN block (the reference's quantization of it is NaN): the pair contributes NaN
+                const float sc = (we_b == -128 || xe_b == -128) ? __builtin_nanf("") : ldexpf(1.0f, we_b - wm + xe_b - xm);
+                acc[j] += (float)(cj - 8 * xs_b) * sc;
             }
         }
     }
@@ -121,6 +123,14 @@ __global__ void __launch_bounds__(RT == 1 ? 1024 : 512) k_hbfp_linear_decode_til
     float acc[RT][4];
 #pragma unroll
     for (int i = 0; i < RT; i++) acc[i][0] = acc[i][1] = acc[i][2] = acc[i][3] = 0.f;
+    // NaN blocks (exponent byte -128 = 0x80): bit 7 of a byte of these words is set once a 0x80 byte met that position -- the x pair
+    // (bytes 0-1 of xnan) and each tile's exponent words (bytes 2j, 2j+1: row 4q + j).  A clamped past-the-end load re-reads the
+    // slice's last pair, which was counted anyway, so no pair needs masking.  Applied once, after the loop: NaN wherever one of the
+    // summed block pairs had a NaN block, as the fp32 sum of NaN-scaled terms would give.
+    uint32_t xnan = 0, wnan[RT][2];
+#pragma unroll
+    for (int i = 0; i < RT; i++) wnan[i][0] = wnan[i][1] = 0;
+    auto nan_bytes = [](uint32_t w) __attribute__((always_inline)) { return w & ~((w & 0x7f7f7f7fu) + 0x7f7f7f7fu); };   // bit 7: byte == 0x80
     auto unpack = [&](uint32_t s0, uint32_t s1) __attribute__((always_inline)) {
         // 16 nibbles -> 16 bytes u = code + 8 (two's-complement nibble ^ 8), in k order
         const uint32_t lo0 = (s0 & 0x0f0f0f0fu) ^ 0x08080808u, hi0 = ((s0 >> 4) & 0x0f0f0f0fu) ^ 0x08080808u;
@@ -160,12 +170,15 @@ __global__ void __launch_bounds__(RT == 1 ? 1024 : 512) k_hbfp_linear_decode_til
         const int eoff = valid ? -(wm + xm) : -1000;                // past-the-end pair (wave-uniform): 2^-1000 flushes its scale to +0
         const uint32_t xe2 = t.xe4 >> t.xsh;
         const int xe0 = (int)(int8_t)(xe2 & 0xff) + eoff, xe1 = (int)(int8_t)((xe2 >> 8) & 0xff) + eoff;
+        xnan |= nan_bytes(xe2);
 #pragma unroll
         for (int i = 0; i < RT; i++) {
             const int4v c0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(unpack((uint32_t)t.w[i].x, (uint32_t)t.w[i].y), t.b0, zero, 0, 0, 0);
             const int4v c1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(unpack((uint32_t)t.w[i].z, (uint32_t)t.w[i].w), t.b1, zero, 0, 0, 0);
             const int c0v[4] = {c0.x, c0.y, c0.z, c0.w}, c1v[4] = {c1.x, c1.y, c1.z, c1.w};
             const uint32_t ew[2] = {t.e[i].x, t.e[i].y};            // rows 4q..4q+3: byte 2j = block 2p, byte 2j+1 = block 2p+1
+            wnan[i][0] |= nan_bytes(ew[0]);
+            wnan[i][1] |= nan_bytes(ew[1]);
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const uint32_t pr = (ew[j >> 1] >> (16 * (j & 1))) & 0xffffu;
@@ -198,6 +211,12 @@ __global__ void __launch_bounds__(RT == 1 ? 1024 : 512) k_hbfp_linear_decode_til
             compute(C, p + 2 < p1);
         }
     }
+    const bool xn = (xnan & 0x8080u) != 0;
+#pragma unroll
+    for (int i = 0; i < RT; i++)
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            if (xn || ((wnan[i][j >> 1] >> (16 * (j & 1))) & 0x8080u)) acc[i][j] = __builtin_nanf("");
 #pragma unroll
     for (int i = 0; i < RT; i++)
         *reinterpret_cast<float4*>(&red[(((size_t)slice * RT + i) * 16 + r) * 16 + 4 * q]) = make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]);

@@ -13,6 +13,7 @@ from quantization_sparsity_interplay_amd import native
 from quantization_sparsity_interplay_amd.bfp import bfp_ops
 from util import DT, load, from_bits, bits, assert_bits_equal
 from gen import int_bits_tensor
+import gemm_cases
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -761,11 +762,15 @@ def test_packed_consumer_decode_linear(N, K, T, dname):
     err = (got.double().cpu() - want).abs().max() / want.abs().max()
     tol = {"f32": 2e-6, "bf16": 6e-3, "f16": 8e-4}[dname]          # output rounding of the dtype; the sums themselves are fp32 of exact block sums
     assert float(err) < tol, (float(err), tol)
+    # per element: fp32 sums of K/64 exact block products plus at most 16 slices, then one rounding to the dtype
+    absprod = xq.abs() @ wq.abs().t()
+    gemm_cases.elementwise_bound(got.cpu(), want, absprod, K // 64 + 16, dt)
     # fp32 output: only the cross-block fp32 accumulation order separates it from the fp64 reference
     if K % 256 == 0 and T <= 16:
         got32 = native.hbfp_linear_decode(x, pw.codes, pw.exps, 3, 7, out_dtype=torch.float32)
         err32 = (got32.double().cpu() - want).abs().max() / want.abs().max()
         assert float(err32) < 2e-6, float(err32)
+        gemm_cases.elementwise_bound(got32.cpu(), want, absprod, K // 64 + 16, torch.float32)
     if K % 128 == 0 and K >= 256:                                   # HBFP4 activations (the W4A4 pairing of an HBFP4 config)
         g4 = pw.linear_decode(x, x_mant_bits=3)
         xq4 = bfp_ops.float_to_bfp_blocked(x, **cfg(mant_bits=3, block_size=64), identifier='in').double().cpu()
@@ -777,6 +782,7 @@ def test_packed_consumer_decode_linear(N, K, T, dname):
         got32t = native.hbfp_linear_decode_tiled(x, tiles, expt, N, 3, 7, out_dtype=torch.float32)
         err32t = (got32t.double().cpu() - want).abs().max() / want.abs().max()
         assert float(err32t) < 2e-6, float(err32t)
+        gemm_cases.elementwise_bound(got32t.cpu(), want, absprod, K // 64 + 16, torch.float32)
         try:                                                        # every tiles-per-wave variant gives the same sums
             for rt in (1, 2, 4):
                 native.load_library().bfpq_tune(1, rt)
@@ -812,6 +818,8 @@ def test_packed_consumer_prefill_mx8(N, K, T, dname):
         assert torch.equal(torch.isnan(g), nan) and bool(nan.any()) == (dname == "f16")
         err32 = (g - want)[~nan].abs().max() / want[~nan].abs().max()
         assert float(err32) < 2e-6, (xm, float(err32))              # only the fp32 accumulation order across blocks differs
+        # per element (the row scaled by 4096 no longer sets the tolerance of every other row): K/64 blocks, at most 8 split-K parts
+        gemm_cases.elementwise_bound(g, want, xq.abs() @ wq.abs().t(), K // 64 + 8, torch.float32)
     # through the module-level entry point, with bias, in the tensor's dtype
     got = pw.linear(x, bias, x_mant_bits=3, decode_tokens=0)
     assert got.shape == (T, N) and got.dtype == dt
@@ -821,6 +829,7 @@ def test_packed_consumer_prefill_mx8(N, K, T, dname):
     err = (got.double().cpu() - want)[~nan].abs().max() / want[~nan].abs().max()
     tol = {"f32": 2e-6, "bf16": 6e-3, "f16": 8e-4}[dname]
     assert float(err) < tol and torch.equal(torch.isnan(got.cpu()), nan), (float(err), tol)
+    gemm_cases.elementwise_bound(got.cpu(), want, xq.abs() @ wq.abs().t() + bias.double().cpu().abs(), K // 64 + 9, dt)
     # 8-bit activations do not fit e4m3: the entry point must take the decode-and-library route, not a wrong product
     assert not native.hbfp_linear_mx8_ok(T, N, K, 3, 7)
     # projections that share an input quantize it once (one-entry memo keyed on the tensor and its version counter)
@@ -935,6 +944,10 @@ def test_packed_consumer_prefill_random_shapes():
         if bool((~nan).any()):
             err = float((got.double().cpu() - want)[~nan].abs().max() / want[~nan].abs().max().clamp_min(1e-30))
             assert err < {"f32": 2e-6, "bf16": 6e-3, "f16": 8e-4}[dname], (case, T, N, K, dname, wm, xm, nm, err)
+            absprod = xq.abs() @ pw.dequantize().double().cpu().abs().t()
+            if bias is not None:
+                absprod = absprod + bias.double().cpu().abs()
+            gemm_cases.elementwise_bound(got.cpu(), want, absprod, K // 64 + 9, dt)
 
 
 @pytest.mark.parametrize("N,K,T", [(512, 4096, 100), (256, 11008, 128), (384, 1024, 33)])
@@ -953,6 +966,8 @@ def test_packed_consumer_prefill_split_k(N, K, T):
     want = xq @ pw.dequantize().double().cpu().t() + bias.double().cpu()
     got = native.hbfp_linear_mx8(x, w8, wsc, 3, bias=bias, out_dtype=torch.float32)
     assert float((got.double().cpu() - want).abs().max() / want.abs().max()) < 2e-6
+    absprod = xq.abs() @ pw.dequantize().double().cpu().abs().t() + bias.double().cpu().abs()
+    gemm_cases.elementwise_bound(got.cpu(), want, absprod, K // 64 + parts + 1, torch.float32)
     assert torch.equal(got, native.hbfp_linear_mx8(x, w8, wsc, 3, bias=bias, out_dtype=torch.float32))
     try:
         native.SPLIT_K = False
@@ -962,6 +977,7 @@ def test_packed_consumer_prefill_split_k(N, K, T):
     assert float((got - one).abs().max() / want.abs().max()) < 2e-6
     gb = native.hbfp_linear_mx8(x, w8, wsc, 3, bias=bias)                 # bf16 output through the reduce launch
     assert gb.dtype == dt and float((gb.double().cpu() - want).abs().max() / want.abs().max()) < 6e-3
+    gemm_cases.elementwise_bound(gb.cpu(), want, absprod, K // 64 + parts + 1, dt)
 
 
 @pytest.mark.parametrize("dname", ["bf16", "f32"])
