@@ -50,6 +50,8 @@ int bfpq_version(void);
 #define BFPQ_TUNE_GEMM_ROW_TILES 1 /* 16-row tiles per wave in bfpq_hbfp_linear_decode_tiled: 0 = choose (default), 1, 2, 4 */
 #define BFPQ_TUNE_LIST_OWN_MB 3    /* list calls: tensors from this many MB on get launches of their own (default 24; 0 = all, a huge value = none) */
 #define BFPQ_TUNE_MX8_VARIANT 2    /* tile shape of bfpq_hbfp_linear_mx8: -1 = choose (default), 0..6 force (A/B measurements) */
+#define BFPQ_TUNE_I8_VARIANT 4     /* tile shape of bfpq_hbfp_linear_i8 / _splitk: -1 = choose (default), 0..2 force */
+#define BFPQ_TUNE_I8_PARTS 5       /* K parts bfpq_hbfp_linear_i8_parts returns: 0 = choose (default), 1..64 force (capped at K / 256) */
 int bfpq_tune(int key, int value);
 const char* bfpq_error_string(int code);
 
@@ -320,6 +322,37 @@ int bfpq_hbfp_linear_mx8(const void* x8_dev, const void* xscale_dev, const void*
 int bfpq_hbfp_linear_mx8_parts(int64_t T, int64_t N, int64_t K);
 int bfpq_hbfp_linear_mx8_splitk(const void* x8_dev, const void* xscale_dev, const void* w8_dev, const void* wscale_dev, const void* bias_dev,
                                 void* out_dev, float* slabs_dev, int parts, int64_t T, int64_t N, int64_t K, int out_dtype, void* stream);
+
+/* ---- packed-format consumer for HBFP5-HBFP8 (replaces F.linear on the two fake-quantised operands, bfp_ops.py:187-190):
+ * out[T, N] = x[T, K] W[N, K]^T (+ bias[N]), both operands int8 codes + int8 block exponents, block 64, mantissa widths
+ * x_mant_bits, w_mant_bits in 1..7 (value = code * 2^(exp - mant_bits)), as bfpq_quantize_nm writes them with code_bits 8.
+ * Each block's dot product is an exact integer sum on the int8 matrix unit (|sum| < 2^20), scaled once by its two power-of-two
+ * block scales and added in block order in fp32.  An exponent byte of -128 (the NaN block marker) on either side makes the block
+ * contribute NaN.  The result does not depend on the tile variant or the K split beyond fp32 summation order, and the same inputs
+ * give the same bits on every call.
+ *   xcodes_dev [T, K] int8, xexp_dev [T, K/64] int8, wcodes_dev [N, K] int8, wexp_dev [N, K/64] int8, bias_dev [N] of out_dtype
+ *   (nullable), out_dev [T, N] of out_dtype.
+ * bfpq_hbfp_linear_i8 / _splitk (the LDS-tiled prefill kernel): 1 == bfpq_hbfp_linear_i8_ok(T, N, K), i.e. N % 16 == 0 and
+ * K % 256 == 0 (other shapes: bfpq_hbfp_linear_decode8); codes and out 16-byte aligned, exponents 4-byte aligned.
+ * _splitk: K split over `parts` workgroups per output tile, each writing an fp32 slab, added in part order by a second small launch;
+ * slabs_dev: parts * T * N floats, 16-byte aligned.  bfpq_hbfp_linear_i8_parts: the parts the plan wants (1: call bfpq_hbfp_linear_i8). */
+int bfpq_hbfp_linear_i8_ok(int64_t T, int64_t N, int64_t K);   /* 1 when the tile kernel applies */
+int bfpq_hbfp_linear_i8_parts(int64_t T, int64_t N, int64_t K);
+int bfpq_hbfp_linear_i8(const void* xcodes_dev, const int8_t* xexp_dev, const void* wcodes_dev, const int8_t* wexp_dev, const void* bias_dev,
+                        void* out_dev, int64_t T, int64_t N, int64_t K, int out_dtype, int w_mant_bits, int x_mant_bits, void* stream);
+int bfpq_hbfp_linear_i8_splitk(const void* xcodes_dev, const int8_t* xexp_dev, const void* wcodes_dev, const int8_t* wexp_dev, const void* bias_dev,
+                               void* out_dev, float* slabs_dev, int parts, int64_t T, int64_t N, int64_t K, int out_dtype,
+                               int w_mant_bits, int x_mant_bits, void* stream);
+/* the same product for few tokens (the decode shape; any T >= 1, N % 16 == 0, K % 64 == 0): a wave owns 16 output features x 16 tokens
+ * x a slice of K, the slices' fp32 slabs are added in slice order.  bfpq_hbfp_linear_decode8_ws: floats of slabs_dev (16-byte aligned)
+ * for this shape, or BFPQ_E_UNSUPPORTED.  Codes 16-byte aligned. */
+int64_t bfpq_hbfp_linear_decode8_ws(int64_t T, int64_t N, int64_t K);
+int bfpq_hbfp_linear_decode8(const void* xcodes_dev, const int8_t* xexp_dev, const void* wcodes_dev, const int8_t* wexp_dev, const void* bias_dev,
+                             void* out_dev, float* slabs_dev, int64_t T, int64_t N, int64_t K, int out_dtype,
+                             int w_mant_bits, int x_mant_bits, void* stream);
+/* 4-bit codes (two's-complement nibbles, low nibble first, as bfpq_quantize_nm writes them) -> int8 codes, so that HBFP4 weights
+ * run on the entry points above; n_codes % 8 == 0, codes4_dev 4-byte and codes8_dev 8-byte aligned. */
+int bfpq_codes4_to_i8(const void* codes4_dev, void* codes8_dev, int64_t n_codes, void* stream);
 
 /* the first BFPQ_SELECT_STATE_BYTES of ws_dev, as read back by a host that wants tau / counts (little-endian) */
 typedef struct bfpq_select_state {

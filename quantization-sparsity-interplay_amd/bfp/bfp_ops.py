@@ -481,6 +481,29 @@ class PackedBFP:
             out = out + bias
         return out.view(lead + (self.shape[0],))
 
+    def linear_i8(self, x, bias=None, x_mant_bits=7, epsilon=1e-8, x_sparsity=None):
+        """F.linear(Q_in(x), W_packed, bias) for any number of tokens on the int8 matrix unit (native.hbfp_linear_i8): self is W [N, K]
+        with 4- or 8-bit codes, block 64, mant_bits 1..7; activations HBFP(x_mant_bits + 1), x_mant_bits 1..7, block 64,
+        round-half-even, pruned by x_sparsity (native.ActSparsity or None) as in linear().  Every block product is an exact integer
+        sum, fp32 across blocks.  4-bit codes are expanded to int8 codes once per device (kept with the weight)."""
+        assert self.code_bits in (4, 8) and self.block_size == 64 and len(self.shape) == 2, \
+            "linear_i8 takes a 2-D weight with 4- or 8-bit codes and block 64"
+        N, K = self.shape
+        lead = x.shape[:-1]
+        x2 = x.reshape(-1, K)
+        if x2.shape[0] == 0:
+            return x.new_zeros(lead + (N,))
+        out = native.hbfp_linear_i8(x2, self._i8_codes(), self.exps, self.mant_bits, x_mant_bits, epsilon, bias=bias, act=x_sparsity)
+        return out.view(lead + (N,))
+
+    def _i8_codes(self):
+        """the weight's codes as int8 [N, K]: the codes themselves (code_bits 8), or their one-time expansion (code_bits 4)"""
+        if self.code_bits == 8:
+            return self.codes
+        if getattr(self, "_i8", None) is None or self._i8.device != self.codes.device:
+            self._i8 = native.codes4_to_i8(self.codes, self.shape[0] * self.shape[1]).view(self.shape)
+        return self._i8
+
     def _mx8_image(self):
         if getattr(self, "_mx8", None) is None or self._mx8[0].device != self.codes.device:
             self._mx8 = native.mx8_from_hbfp(self.codes, self.exps, self.shape[-1], self.mant_bits, self.code_bits)
@@ -571,10 +594,16 @@ class WeightCache:
         # matrix_unit: F.linear on the two fake-quantised operands is replaced by the block-scaled matrix instruction on their e4m3 + E8M0
         # images where the configuration allows it (same products and block sums, fp32 across blocks; see PackedBFP.linear); the weight's
         # image is cached like the fake-quantised weight, under the same key
-        self.matrix_unit = bool(matrix_unit)
+        # matrix_unit='int8': the same for HBFP up to 8 bits (mant_bits <= 7) on the int8 matrix instruction (native.hbfp_linear_i8); the
+        # cached image is then the weight's int8 codes + exponents
+        if isinstance(matrix_unit, str) or matrix_unit not in (True, False):
+            if matrix_unit != 'int8':
+                raise ValueError(f"matrix_unit must be False, True or 'int8' (got {matrix_unit!r})")
+        self.matrix_unit = 'int8' if matrix_unit == 'int8' else bool(matrix_unit)
         self.image_key = None
         self.image = None
         self.mx_calls = 0
+        self.i8_calls = 0
 
     @staticmethod
     def _key(w, bfp_args):
@@ -627,6 +656,21 @@ class WeightCache:
             else:
                 codes, exps = float_to_bfp_packed(w.detach(), a['mant_bits'], 64, a['epsilon'], a['N'] if sp else 0, a['M'] if sp else 0, a['first'], cb)
             self.image = native.mx8_from_hbfp(codes, exps, w.shape[-1], a['mant_bits'], cb)
+            self.image_key = key
+        return self.image
+
+    def weight_codes_i8(self, w, bfp_args):
+        """int8 codes [N, K] + int8 exponents [N, K/64] of Q_w(w) for the int8 matrix unit (matrix_unit='int8'), kept under the same key"""
+        key = self._key(w, bfp_args)
+        if self.image_key != key:
+            a = bfp_args
+            sp = a['w_sparsity'] == True  # noqa: E712
+            if sp and a['sparsity_mode'] == 'unstructured':
+                pk = PackedBFP.quantize_unstructured(w.detach(), a['mant_bits'], 64, a['sparsity_frac'], a['epsilon'], 8)
+                self.image = (pk.codes.view(w.shape), pk.exps)
+            else:
+                codes, exps = float_to_bfp_packed(w.detach(), a['mant_bits'], 64, a['epsilon'], a['N'] if sp else 0, a['M'] if sp else 0, a['first'], 8)
+                self.image = (codes.view(w.shape), exps)
             self.image_key = key
         return self.image
 
@@ -701,7 +745,26 @@ def _matrix_unit_ok(x, w, a, cache):
     """the cached Linear forward can run on the block-scaled matrix instruction: HBFP with block 64 and <= 4 mantissa bits (exact in e4m3),
     round-half-even, dense or pruned activations (structured with 0 < N <= M, or unstructured), dense or N:M weights, a 2-D weight
     with K % 256 == 0, enough tokens to fill a tile row"""
-    if (a['num_format'] != 'bfp' or a['sparsity_num_format'] != 'bfp' or a['block_size'] != 64 or not (1 <= a['mant_bits'] <= 4)
+    if not _cached_route_ok(x, w, a, cache, 4):
+        return False
+    K = x.shape[-1]
+    T = x.numel() // K if K else 0
+    return T >= 32 and native.hbfp_linear_mx8_ok(T, w.shape[0], K, a['mant_bits'], a['mant_bits'], 64)
+
+
+def _int8_unit_ok(x, w, a, cache):
+    """the cached Linear forward can run on the int8 matrix instruction (matrix_unit='int8'): as _matrix_unit_ok but with 1..7 mantissa bits,
+    any number of tokens, N % 16 == 0 and K % 64 == 0"""
+    if not _cached_route_ok(x, w, a, cache, 7):
+        return False
+    K = x.shape[-1]
+    T = x.numel() // K if K else 0
+    return T >= 1 and native.hbfp_linear_i8_ok(T, w.shape[0], K, a['mant_bits'], a['mant_bits'], 64)
+
+
+def _cached_route_ok(x, w, a, cache, max_mant_bits):
+    """the configuration checks shared by the matrix-unit routes of the cached Linear (format, rounding, sparsity coverage)"""
+    if (a['num_format'] != 'bfp' or a['sparsity_num_format'] != 'bfp' or a['block_size'] != 64 or not (1 <= a['mant_bits'] <= max_mant_bits)
             or a['rounding_mode'] != rounding_modes.DETERM or w.dim() != 2 or x.device.type != 'cuda'
             or torch.compiler.is_compiling() or not cache.usable(w, a)):
         return False
@@ -717,9 +780,7 @@ def _matrix_unit_ok(x, w, a, cache):
                 return False
         elif a['sparsity_mode'] != 'structured' or not (0 < a['N'] <= a['M']) or a['M'] not in (2, 4, 8):
             return False
-    K = x.shape[-1]
-    T = x.numel() // K if K else 0
-    return T >= 32 and native.hbfp_linear_mx8_ok(T, w.shape[0], K, a['mant_bits'], a['mant_bits'], 64)
+    return True
 
 
 def _gen_bfp_op(op, name, bfp_args, transpose=False, cache=None):
@@ -727,7 +788,13 @@ def _gen_bfp_op(op, name, bfp_args, transpose=False, cache=None):
     (and sparsified) on the way in and the output gradient on the way back.  cache: optional WeightCache."""
     def bfp_op(x, w, *args, **kwargs):
         if not torch.is_grad_enabled():                 # inference: same values, no autograd nodes to build
-            if cache is not None and cache.matrix_unit and op is F.linear and _matrix_unit_ok(x, w, bfp_args, cache):
+            if cache is not None and cache.matrix_unit == 'int8' and op is F.linear and _int8_unit_ok(x, w, bfp_args, cache):
+                cache.i8_calls += 1
+                bias = args[0] if args else kwargs.get('bias')
+                wc, we = cache.weight_codes_i8(w, bfp_args)
+                return native.hbfp_linear_i8(x, wc, we, bfp_args['mant_bits'], bfp_args['mant_bits'], bfp_args['epsilon'], bias=bias,
+                                             act=native.ActSparsity.from_bfp_args(bfp_args))
+            if cache is not None and cache.matrix_unit is True and op is F.linear and _matrix_unit_ok(x, w, bfp_args, cache):
                 cache.mx_calls += 1
                 bias = args[0] if args else kwargs.get('bias')
                 w8, wsc = cache.weight_image(w, bfp_args)
@@ -788,7 +855,9 @@ class _BFPModule:
         """opt in to (or out of) caching the quantized weight across forwards; see WeightCache.  matrix_unit=True additionally
         runs the Linear itself on the block-scaled matrix instruction where the configuration allows (HBFP4-class, block 64,
         >= 32 tokens): the same block products, summed exactly inside a block and in fp32 across blocks instead of by the bf16
-        library GEMM -- results agree with F.linear on the fake-quantised operands up to that summation order."""
+        library GEMM -- results agree with F.linear on the fake-quantised operands up to that summation order.  matrix_unit='int8' runs it
+        instead on the int8 matrix instruction for HBFP up to 8 bits (block 64, mant_bits 1..7, any number of tokens, N % 16 == 0 and
+        K % 64 == 0; WeightCache.i8_calls counts these calls).  Any other value raises ValueError."""
         cache = WeightCache(self, matrix_unit=matrix_unit) if enabled else None
         self._weight_cache = cache                               # (patch.prime_weight_caches fills it for a whole model in one list call)
         op = _get_bfp_op(self._functional, self._op_name, self.bfp_args, cache=cache)

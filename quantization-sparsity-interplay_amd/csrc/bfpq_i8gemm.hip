@@ -1,0 +1,488 @@
+// bfpq_i8gemm.hip -- consumer of packed HBFP with mantissas of up to 7 bits (HBFP5-HBFP8): out[t][n] = sum_k x[t][k] W[n][k] (+ bias[n])
+// with x and W both int8 codes + one int8 exponent per block of 64, mantissa widths xm, wm in 1..7.  Replaces F.linear on the two
+// fake-quantised operands (bfp_ops.py:187-190).
+//
+// Arithmetic: inside a block the dot product is an exact integer sum on the int8 matrix unit (v_mfma_i32_16x16x64_i8, K = 64 = one
+// block; |sum| <= 64 * 127^2 < 2^20), multiplied once by 2^(ex - xm) * 2^(ew - wm) and added to fp32 accumulators in block order.
+// The e4m3 route of bfpq_mxgemm.hip does not apply above 4-bit mantissas (a 7-bit code is not exact in e4m3).
+//
+// The rescale is the VALU cost the block-scaled instruction does not have.  It is kept to two packed fp32 ops per pair of outputs:
+//   - the MFMA's C operand is the integer 0x4B400000 (the bits of 1.5 * 2^23), so its int32 result, read as a float, is exactly
+//     1.5 * 2^23 + sum (floats in [2^23, 2^24) step by 1): no int -> float conversion;
+//   - u = fma(f, sx, -1.5 * 2^23 * sx) = sum * 2^(ex - xm) (exact: both products are exact, the difference is an integer < 2^20 times
+//     a power of two);
+//   - acc = fma(u, sw, acc), with sw = 2^(ew - wm).
+// Both are v_pk_fma_f32 on two outputs; one 16x16x64 MFMA (16 cycles) leaves 4 outputs per lane, i.e. 4 packed ops.  A block
+// exponent of -128 (the NaN block marker) makes its scale NaN, so the block contributes NaN.  (Scales are exact powers of two down to
+// fp32's subnormal 2^-149; products below that flush, as the fp32 product of the fake-quantised values would.)
+//
+// Lane map of v_mfma_i32_16x16x64_i8 (as in bfpq_gemm.hip): A lane l = row l & 15, bytes k = 16 (l >> 4) .. +15; B lane l = column
+// l & 15, same k; D lane l holds rows 4 (l >> 4) + j (j = 0..3) of column l & 15.  A = weight rows, B = tokens, so a lane's four results
+// are four consecutive output features of one token (one 8- or 16-byte store).
+//
+// Kernels:
+//   k_i8_gemm     prefill tile: WM x WN waves, each TM x TN instruction tiles; K staged global -> LDS by 16-byte LDS-DMA, two LDS
+//                 stages of two blocks each (double buffered: the next stage's DMA is in flight during the current stage's matrix
+//                 work), LDS rows of 128 bytes with the 16-byte slot XOR-swizzled by ((row >> 1) & 7).  K % 256 == 0 (the block
+//                 exponents are read one dword = 4 blocks per trip).  SPLIT: part p of K goes to fp32 slab p (plain stores) and
+//                 k_i8_slab_reduce adds the slabs in part order.
+//   k_i8_decode   few tokens: a wave owns 16 output features x up to 16 tokens x a slice of K (any K % 64 == 0), slabs reduced as above.
+//   k_codes4_to_i8  4-bit two's-complement nibbles (low first) -> int8 codes.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "bfpq.h"
+#include "bfpq_common.h"
+
+using namespace bfpq;
+
+namespace {
+
+typedef int v4i __attribute__((ext_vector_type(4)));
+typedef float v2f __attribute__((ext_vector_type(2)));
+typedef float v4f __attribute__((ext_vector_type(4)));
+
+constexpr int BK = 128;                                   // bytes of K per LDS stage: two blocks
+constexpr int MAGIC_I = 0x4B400000;                       // bits of 1.5 * 2^23
+constexpr float MAGIC_F = 12582912.0f;
+
+__device__ __forceinline__ float block_scale(int e, int m)   // 2^(e - m); NaN for the NaN block marker
+{
+    return e == -128 ? __builtin_nanf("") : ldexpf(1.0f, e - m);
+}
+
+__device__ __forceinline__ v4i read16(const uint8_t* tile, int row, int c)      // logical 16-byte slot c of an LDS row
+{
+    return *reinterpret_cast<const v4i*>(tile + row * BK + ((c ^ ((row >> 1) & 7)) << 4));
+}
+
+template <int WM, int WN, int TM, int TN>
+struct I8Cfg {
+    static constexpr int NW = WM * WN, BN = 16 * WM * TM, BT = 16 * WN * TN, STAGE = (BN + BT) * BK;
+};
+
+// out tile: BN output features (weight rows) x BT tokens.  trips [a, b) of K (256 each).  SPLIT: out is the fp32 slab of this part.
+template <int OUT_DT, int WM, int WN, int TM, int TN, bool SPLIT>
+__global__ void __launch_bounds__(64 * WM * WN) k_i8_gemm(const int8_t* __restrict__ xc, const int8_t* __restrict__ xe, const int8_t* __restrict__ wc,
+                                                          const int8_t* __restrict__ we, const void* __restrict__ bias, void* __restrict__ out,
+                                                          int T, int N, int K, int tiles_t, int tiles, int trips_per_part, int xm, int wm)
+{
+    using C = I8Cfg<WM, WN, TM, TN>;
+    constexpr int NW = C::NW, BN = C::BN, BT = C::BT, STAGE = C::STAGE;
+    constexpr int GW = BN / 8 / NW, GX = BT / 8 / NW;            // LDS-DMA instructions per wave and stage (8 rows = 1 KB each)
+    static_assert(BN % (8 * NW) == 0 && BT % (8 * NW) == 0, "tile rows must split evenly over the waves");
+    __shared__ __attribute__((aligned(16))) uint8_t lds[2 * STAGE];
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63, r = l & 15, q = l >> 4;
+    const int part = SPLIT ? (int)blockIdx.x / tiles : 0, tile = SPLIT ? (int)blockIdx.x % tiles : (int)blockIdx.x;
+    const int t0 = (tile % tiles_t) * BT, n0 = (tile / tiles_t) * BN;
+    const int trips = K >> 8, nb4 = K >> 8;                      // dwords of exponents per row
+    const int ta = part * trips_per_part, tb = ta + trips_per_part < trips ? ta + trips_per_part : trips;
+
+    // staging: instruction i of wave w fills LDS rows (NW i + w) * 8 .. +7; lane l = row l >> 3, physical slot l & 7 holds the row's
+    // logical slot (l & 7) ^ ((row >> 1) & 7).  Rows past N / T repeat the last row (their results are not stored).
+    uint32_t offW[GW], offX[GX];
+#pragma unroll
+    for (int i = 0; i < GW; i++) {
+        const int row = (NW * i + w) * 8 + (l >> 3), piece = ((l & 7) ^ ((row >> 1) & 7)) << 4;
+        const int na = n0 + row < N ? n0 + row : N - 1;
+        offW[i] = (uint32_t)na * (uint32_t)K + piece;
+    }
+#pragma unroll
+    for (int i = 0; i < GX; i++) {
+        const int row = (NW * i + w) * 8 + (l >> 3), piece = ((l & 7) ^ ((row >> 1) & 7)) << 4;
+        const int tr = t0 + row < T ? t0 + row : T - 1;
+        offX[i] = (uint32_t)tr * (uint32_t)K + piece;
+    }
+    const int wr = w / WN, wcl = w % WN;
+    const int rowW = wr * (16 * TM), rowX = wcl * (16 * TN);     // the wave's first LDS row of each operand
+    // exponent dwords: weight rows n0 + rowW + 16 i + 4 q + j, token rows t0 + rowX + 16 jt + r
+    uint32_t ewo[TM][4], exo[TN];
+#pragma unroll
+    for (int i = 0; i < TM; i++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int n = n0 + rowW + 16 * i + 4 * q + j;
+            ewo[i][j] = (uint32_t)(n < N ? n : N - 1) * (uint32_t)nb4;
+        }
+#pragma unroll
+    for (int jt = 0; jt < TN; jt++) {
+        const int t = t0 + rowX + 16 * jt + r;
+        exo[jt] = (uint32_t)(t < T ? t : T - 1) * (uint32_t)nb4;
+    }
+    const uint32_t* const we32 = reinterpret_cast<const uint32_t*>(we);
+    const uint32_t* const xe32 = reinterpret_cast<const uint32_t*>(xe);
+
+    v2f acc[TM][TN][2];
+#pragma unroll
+    for (int i = 0; i < TM; i++)
+#pragma unroll
+        for (int jt = 0; jt < TN; jt++) acc[i][jt][0] = acc[i][jt][1] = v2f{0.f, 0.f};
+
+    auto stage = [&](int k0, int buf) __attribute__((always_inline)) {
+        uint8_t* const sW = lds + buf * STAGE;
+        uint8_t* const sX = sW + BN * BK;
+#pragma unroll
+        for (int i = 0; i < GW; i++)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wc + offW[i] + k0),
+                                             (__attribute__((address_space(3))) void*)(sW + (NW * i + w) * 1024), 16, 0, 0);
+#pragma unroll
+        for (int i = 0; i < GX; i++)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(xc + offX[i] + k0),
+                                             (__attribute__((address_space(3))) void*)(sX + (NW * i + w) * 1024), 16, 0, 0);
+    };
+    auto landed = [&]() __attribute__((always_inline)) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); };
+
+    // one block of the stage in buffer buf: byte BB (0..3) of the trip's exponent dwords
+    auto block = [&](int buf, int b, int BB, const uint32_t (&ewd)[TM][4], const uint32_t (&exd)[TN]) __attribute__((always_inline)) {
+        const uint8_t* const sW = lds + buf * STAGE;
+        const uint8_t* const sX = sW + BN * BK;
+        const int c = b * 4 + q;
+        v4i aF[TM], bF[TN];
+#pragma unroll
+        for (int i = 0; i < TM; i++) aF[i] = read16(sW, rowW + 16 * i + r, c);
+#pragma unroll
+        for (int jt = 0; jt < TN; jt++) bF[jt] = read16(sX, rowX + 16 * jt + r, c);
+        v2f sx[TN], nm[TN];
+#pragma unroll
+        for (int jt = 0; jt < TN; jt++) {
+            const float s = block_scale((int)(int8_t)(exd[jt] >> (8 * BB)), xm);
+            sx[jt] = v2f{s, s};
+            nm[jt] = v2f{-MAGIC_F * s, -MAGIC_F * s};
+        }
+        const v4i magic = {MAGIC_I, MAGIC_I, MAGIC_I, MAGIC_I};
+#pragma unroll
+        for (int i = 0; i < TM; i++) {
+            v2f sw[2];
+#pragma unroll
+            for (int h = 0; h < 2; h++)
+                sw[h] = v2f{block_scale((int)(int8_t)(ewd[i][2 * h] >> (8 * BB)), wm), block_scale((int)(int8_t)(ewd[i][2 * h + 1] >> (8 * BB)), wm)};
+#pragma unroll
+            for (int jt = 0; jt < TN; jt++) {
+                const v4i d = __builtin_amdgcn_mfma_i32_16x16x64_i8(aF[i], bF[jt], magic, 0, 0, 0);
+                const v4f f = __builtin_bit_cast(v4f, d);
+                const v2f f01 = f.xy, f23 = f.zw;
+                const v2f u01 = __builtin_elementwise_fma(f01, sx[jt], nm[jt]);
+                const v2f u23 = __builtin_elementwise_fma(f23, sx[jt], nm[jt]);
+                acc[i][jt][0] = __builtin_elementwise_fma(u01, sw[0], acc[i][jt][0]);
+                acc[i][jt][1] = __builtin_elementwise_fma(u23, sw[1], acc[i][jt][1]);
+            }
+        }
+    };
+
+    if (ta < tb) {
+        uint32_t ewd[TM][4], exd[TN];
+#pragma unroll
+        for (int i = 0; i < TM; i++)
+#pragma unroll
+            for (int j = 0; j < 4; j++) ewd[i][j] = we32[ewo[i][j] + ta];
+#pragma unroll
+        for (int jt = 0; jt < TN; jt++) exd[jt] = xe32[exo[jt] + ta];
+        stage(ta << 8, 0);
+        landed();
+        for (int tr = ta; tr < tb; tr++) {
+            const int trn = tr + 1 < tb ? tr + 1 : tr;               // (last trip: re-reads its own exponents, re-stages its first half)
+            uint32_t ewn[TM][4], exn[TN];
+#pragma unroll
+            for (int i = 0; i < TM; i++)
+#pragma unroll
+                for (int j = 0; j < 4; j++) ewn[i][j] = we32[ewo[i][j] + trn];
+#pragma unroll
+            for (int jt = 0; jt < TN; jt++) exn[jt] = xe32[exo[jt] + trn];
+            stage((tr << 8) + BK, 1);
+            block(0, 0, 0, ewd, exd);
+            block(0, 1, 1, ewd, exd);
+            landed();
+            stage(trn << 8, 0);
+            block(1, 0, 2, ewd, exd);
+            block(1, 1, 3, ewd, exd);
+            landed();
+#pragma unroll
+            for (int i = 0; i < TM; i++)
+#pragma unroll
+                for (int j = 0; j < 4; j++) ewd[i][j] = ewn[i][j];
+#pragma unroll
+            for (int jt = 0; jt < TN; jt++) exd[jt] = exn[jt];
+        }
+    }
+
+    // epilogue: lane holds features n .. n + 3 of token t
+#pragma unroll
+    for (int i = 0; i < TM; i++) {
+        const int n = n0 + rowW + 16 * i + 4 * q;
+        if (n >= N) continue;                                    // (N % 16 == 0: all four or none)
+#pragma unroll
+        for (int jt = 0; jt < TN; jt++) {
+            const int t = t0 + rowX + 16 * jt + r;
+            if (t >= T) continue;
+            const v2f a01 = acc[i][jt][0], a23 = acc[i][jt][1];
+            if constexpr (SPLIT) {
+                *reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + ((size_t)part * T + t) * N + n) = make_float4(a01.x, a01.y, a23.x, a23.y);
+            } else {
+                using raw_t = typename Traits<OUT_DT>::raw_t;
+                float v[4] = {a01.x, a01.y, a23.x, a23.y};
+                if (bias) {
+#pragma unroll
+                    for (int j = 0; j < 4; j++) v[j] += raw_to_f32<OUT_DT>((uint32_t)reinterpret_cast<const raw_t*>(bias)[n + j]);
+                }
+                if constexpr (OUT_DT == BFPQ_F32) {
+                    *reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + (size_t)t * N + n) = make_float4(v[0], v[1], v[2], v[3]);
+                } else {
+                    const uint32_t lo = f32_to_raw<OUT_DT>(v[0]) | (f32_to_raw<OUT_DT>(v[1]) << 16);
+                    const uint32_t hi = f32_to_raw<OUT_DT>(v[2]) | (f32_to_raw<OUT_DT>(v[3]) << 16);
+                    *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(out) + (size_t)t * N + n) = make_uint2(lo, hi);
+                }
+            }
+        }
+    }
+}
+
+// few tokens: wave = 16 features x 16 tokens (token group blockIdx.y) x a slice of the blocks; fp32 slab [slice][Tpad][N]
+__global__ void __launch_bounds__(256) k_i8_decode(const int8_t* __restrict__ wc, const int8_t* __restrict__ we, const int8_t* __restrict__ xc,
+                                                   const int8_t* __restrict__ xe, float* __restrict__ slabs, int T, int N, int K,
+                                                   int blocks_per_slice, int slices, int wm, int xm)
+{
+    const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
+    const int row_tiles = N / 16;
+    const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
+    const int rt = wave % row_tiles, slice = wave / row_tiles;
+    if (slice >= slices) return;                                 // grid rounded up to whole workgroups
+    const int nb = K / 64, Tpad = gridDim.y * 16;
+    const int b0 = slice * blocks_per_slice;
+    const int b1 = b0 + blocks_per_slice < nb ? b0 + blocks_per_slice : nb;
+    const int n0 = rt * 16, tok = blockIdx.y * 16 + r;
+    const int tx = tok < T ? tok : T - 1;                        // token columns past T repeat the last token (results dropped)
+    const int8_t* wrow = wc + (size_t)(n0 + r) * K + q * 16;
+    const int8_t* xrow = xc + (size_t)tx * K + q * 16;
+    const int8_t* wer = we + (size_t)(n0 + 4 * q) * nb;
+    const int8_t* xer = xe + (size_t)tx * nb;
+    const v4i zero = {0, 0, 0, 0};
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int b = b0; b < b1; b++) {
+        const v4i av = *reinterpret_cast<const v4i*>(wrow + (size_t)b * 64);
+        const v4i bv = *reinterpret_cast<const v4i*>(xrow + (size_t)b * 64);
+        const v4i c = __builtin_amdgcn_mfma_i32_16x16x64_i8(av, bv, zero, 0, 0, 0);
+        const int xe_b = xer[b];
+        const int cv[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int we_b = wer[(size_t)j * nb + b];
+            // -128 marks a NaN block: the pair contributes NaN
+            const float sc = (we_b == -128 || xe_b == -128) ? __builtin_nanf("") : ldexpf(1.0f, we_b - wm + xe_b - xm);
+            acc[j] += (float)cv[j] * sc;
+        }
+    }
+    *reinterpret_cast<float4*>(slabs + ((size_t)slice * Tpad + blockIdx.y * 16 + r) * N + n0 + 4 * q) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+}
+
+// out[t][n] = sum over parts in part order (+ bias), rounded once; slab p at slabs + p * stride, rows of N
+template <int OUT_DT>
+__global__ void __launch_bounds__(256) k_i8_slab_reduce(const float* __restrict__ slabs, size_t stride, const void* __restrict__ bias,
+                                                        void* __restrict__ out, int64_t TN_, int N, int parts)
+{
+    using raw_t = typename Traits<OUT_DT>::raw_t;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < TN_; i += (int64_t)gridDim.x * 256) {
+        float acc = slabs[i];
+        for (int p = 1; p < parts; p++) acc += slabs[(size_t)p * stride + i];
+        if (bias) acc += raw_to_f32<OUT_DT>((uint32_t)reinterpret_cast<const raw_t*>(bias)[i % N]);
+        reinterpret_cast<raw_t*>(out)[i] = (raw_t)f32_to_raw<OUT_DT>(acc);
+    }
+}
+
+// one thread = 8 codes (4 bytes of nibbles -> 8 bytes)
+__global__ void __launch_bounds__(256) k_codes4_to_i8(const uint32_t* __restrict__ in, uint2* __restrict__ out, int64_t n_items)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_items; i += (int64_t)gridDim.x * 256) {
+        const uint32_t v = in[i];
+        uint32_t lo = 0, hi = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const uint32_t nib = (v >> (4 * j)) & 15u;
+            const uint32_t b = nib >= 8 ? nib + 0xf0u : nib;    // sign-extend the nibble to a byte
+            if (j < 4) lo |= b << (8 * j); else hi |= b << (8 * (j - 4));
+        }
+        out[i] = make_uint2(lo, hi);
+    }
+}
+
+template <int OUT_DT>
+void launch_reduce(const float* slabs, size_t stride, const void* bias, void* out, int64_t T, int64_t N, int parts, hipStream_t s)
+{
+    const int64_t tn = T * N;
+    int64_t g = (tn + 255) / 256;
+    if (g > 2048) g = 2048;
+    hipLaunchKernelGGL((k_i8_slab_reduce<OUT_DT>), dim3((unsigned)g), dim3(256), 0, s, slabs, stride, bias, out, tn, (int)N, parts);
+}
+
+void reduce_dt(int out_dtype, const float* slabs, size_t stride, const void* bias, void* out, int64_t T, int64_t N, int parts, hipStream_t s)
+{
+    if (out_dtype == BFPQ_F32) launch_reduce<BFPQ_F32>(slabs, stride, bias, out, T, N, parts, s);
+    else if (out_dtype == BFPQ_F16) launch_reduce<BFPQ_F16>(slabs, stride, bias, out, T, N, parts, s);
+    else launch_reduce<BFPQ_BF16>(slabs, stride, bias, out, T, N, parts, s);
+}
+
+// tile variants (bfpq_tune key BFPQ_TUNE_I8_VARIANT): 0 = 128 features x 128 tokens, 1 = 128 x 64, 2 = 64 x 64; all 4 waves
+constexpr int kI8Variants = 3;
+template <int V> struct I8Var;
+template <> struct I8Var<0> { static constexpr int WM = 2, WN = 2, TM = 4, TN = 4; };
+template <> struct I8Var<1> { static constexpr int WM = 2, WN = 2, TM = 4, TN = 2; };
+template <> struct I8Var<2> { static constexpr int WM = 2, WN = 2, TM = 2, TN = 2; };
+
+template <int V> int var_bn() { return 16 * I8Var<V>::WM * I8Var<V>::TM; }
+template <int V> int var_bt() { return 16 * I8Var<V>::WN * I8Var<V>::TN; }
+int var_tile_n(int v) { return v == 0 ? var_bn<0>() : (v == 1 ? var_bn<1>() : var_bn<2>()); }
+int var_tile_t(int v) { return v == 0 ? var_bt<0>() : (v == 1 ? var_bt<1>() : var_bt<2>()); }
+
+template <int V, int OUT_DT, bool SPLIT>
+void launch_tile(dim3 grid, hipStream_t s, const int8_t* xc, const int8_t* xe, const int8_t* wc, const int8_t* we, const void* bias, void* out,
+                 int T, int N, int K, int tiles_t, int tiles, int tpp, int xm, int wm)
+{
+    using P = I8Var<V>;
+    hipLaunchKernelGGL((k_i8_gemm<OUT_DT, P::WM, P::WN, P::TM, P::TN, SPLIT>), grid, dim3(64 * P::WM * P::WN), 0, s, xc, xe, wc, we, bias, out,
+                       T, N, K, tiles_t, tiles, tpp, xm, wm);
+}
+
+template <int V>
+void launch_var(int out_dtype, bool split, dim3 grid, hipStream_t s, const int8_t* xc, const int8_t* xe, const int8_t* wc, const int8_t* we,
+                const void* bias, void* out, int T, int N, int K, int tiles_t, int tiles, int tpp, int xm, int wm)
+{
+    if (split) launch_tile<V, BFPQ_F32, true>(grid, s, xc, xe, wc, we, nullptr, out, T, N, K, tiles_t, tiles, tpp, xm, wm);
+    else if (out_dtype == BFPQ_F32) launch_tile<V, BFPQ_F32, false>(grid, s, xc, xe, wc, we, bias, out, T, N, K, tiles_t, tiles, tpp, xm, wm);
+    else if (out_dtype == BFPQ_F16) launch_tile<V, BFPQ_F16, false>(grid, s, xc, xe, wc, we, bias, out, T, N, K, tiles_t, tiles, tpp, xm, wm);
+    else launch_tile<V, BFPQ_BF16, false>(grid, s, xc, xe, wc, we, bias, out, T, N, K, tiles_t, tiles, tpp, xm, wm);
+}
+
+}  // namespace
+
+extern "C" __attribute__((visibility("hidden"))) int bfpq_g_i8_variant = -1;    // -1 = choose; 0..2 force (bfpq_tune, BFPQ_TUNE_I8_VARIANT)
+extern "C" __attribute__((visibility("hidden"))) int bfpq_g_i8_parts = 0;       // 0 = choose; >= 1 force (bfpq_tune, BFPQ_TUNE_I8_PARTS)
+
+static int i8_variant(int64_t T)
+{
+    if (bfpq_g_i8_variant >= 0 && bfpq_g_i8_variant < kI8Variants) return bfpq_g_i8_variant;
+    return T > 64 ? 0 : 1;
+}
+
+static bool i8_args_ok(int out_dtype, int w_mant_bits, int x_mant_bits)
+{
+    return out_dtype >= 0 && out_dtype <= 2 && w_mant_bits >= 1 && w_mant_bits <= 7 && x_mant_bits >= 1 && x_mant_bits <= 7;
+}
+
+extern "C" {
+
+int bfpq_hbfp_linear_i8_ok(int64_t T, int64_t N, int64_t K)
+{
+    return T >= 1 && N >= 16 && N % 16 == 0 && K >= 256 && K % 256 == 0 && T * K < ((int64_t)1 << 32) && N * K < ((int64_t)1 << 32) &&
+           ((T + 63) / 64) * ((N + 63) / 64) < ((int64_t)1 << 30);
+}
+
+int bfpq_hbfp_linear_i8_parts(int64_t T, int64_t N, int64_t K)
+{
+    if (!bfpq_hbfp_linear_i8_ok(T, N, K)) return 1;
+    const int64_t trips = K / 256;
+    if (bfpq_g_i8_parts > 0) return (int)(bfpq_g_i8_parts < trips ? bfpq_g_i8_parts : trips);
+    const int v = i8_variant(T);
+    const int64_t tiles = ((T + var_tile_t(v) - 1) / var_tile_t(v)) * ((N + var_tile_n(v) - 1) / var_tile_n(v));
+    if (tiles >= 256 || trips < 4) return 1;
+    int64_t parts = 512 / tiles;                                  // aim at two workgroups per CU
+    if (parts > 8) parts = 8;
+    if (parts > trips / 2) parts = trips / 2;                     // at least two trips per part
+    return parts < 2 ? 1 : (int)parts;
+}
+
+static int i8_launch(const int8_t* xc, const int8_t* xe, const int8_t* wc, const int8_t* we, const void* bias, void* out, float* slabs, int parts,
+                     int64_t T, int64_t N, int64_t K, int out_dtype, int wm, int xm, hipStream_t s)
+{
+    const int v = i8_variant(T);
+    const int trips = (int)(K / 256);
+    if (parts > trips) parts = trips;
+    const int tpp = (trips + parts - 1) / parts;
+    parts = (trips + tpp - 1) / tpp;                              // (no empty part)
+    const int tiles_t = (int)((T + var_tile_t(v) - 1) / var_tile_t(v)), tiles = tiles_t * (int)((N + var_tile_n(v) - 1) / var_tile_n(v));
+    const bool split = slabs != nullptr;
+    void* dst = split ? (void*)slabs : out;
+    const dim3 grid((unsigned)(tiles * (split ? parts : 1)));
+    if (v == 0) launch_var<0>(out_dtype, split, grid, s, xc, xe, wc, we, bias, dst, (int)T, (int)N, (int)K, tiles_t, tiles, tpp, xm, wm);
+    else if (v == 1) launch_var<1>(out_dtype, split, grid, s, xc, xe, wc, we, bias, dst, (int)T, (int)N, (int)K, tiles_t, tiles, tpp, xm, wm);
+    else launch_var<2>(out_dtype, split, grid, s, xc, xe, wc, we, bias, dst, (int)T, (int)N, (int)K, tiles_t, tiles, tpp, xm, wm);
+    if (split) reduce_dt(out_dtype, slabs, (size_t)(T * N), bias, out, T, N, parts, s);
+    return (int)hipGetLastError();
+}
+
+static bool i8_ptrs_ok(const void* xc, const void* xe, const void* wc, const void* we, const void* out)
+{
+    if (!xc || !xe || !wc || !we || !out) return false;
+    // LDS-DMA sources: 16-byte aligned codes; exponent dwords: 4-byte aligned; vector stores of 4 outputs: 8-byte aligned
+    return !((reinterpret_cast<uintptr_t>(xc) | reinterpret_cast<uintptr_t>(wc) | reinterpret_cast<uintptr_t>(out)) & 15u) &&
+           !((reinterpret_cast<uintptr_t>(xe) | reinterpret_cast<uintptr_t>(we)) & 3u);
+}
+
+int bfpq_hbfp_linear_i8(const void* xcodes, const int8_t* xexp, const void* wcodes, const int8_t* wexp, const void* bias, void* out,
+                        int64_t T, int64_t N, int64_t K, int out_dtype, int w_mant_bits, int x_mant_bits, void* stream)
+{
+    if (!i8_args_ok(out_dtype, w_mant_bits, x_mant_bits) || T < 0 || N < 0) return BFPQ_E_ARG;
+    if (T == 0 || N == 0) return 0;
+    if (!bfpq_hbfp_linear_i8_ok(T, N, K)) return BFPQ_E_UNSUPPORTED;
+    if (!i8_ptrs_ok(xcodes, xexp, wcodes, wexp, out)) return BFPQ_E_ARG;
+    return i8_launch((const int8_t*)xcodes, xexp, (const int8_t*)wcodes, wexp, bias, out, nullptr, 1, T, N, K, out_dtype, w_mant_bits, x_mant_bits,
+                     (hipStream_t)stream);
+}
+
+int bfpq_hbfp_linear_i8_splitk(const void* xcodes, const int8_t* xexp, const void* wcodes, const int8_t* wexp, const void* bias, void* out,
+                               float* slabs, int parts, int64_t T, int64_t N, int64_t K, int out_dtype, int w_mant_bits, int x_mant_bits, void* stream)
+{
+    if (!i8_args_ok(out_dtype, w_mant_bits, x_mant_bits) || T < 0 || N < 0 || parts < 1 || parts > 64) return BFPQ_E_ARG;
+    if (T == 0 || N == 0) return 0;
+    if (!bfpq_hbfp_linear_i8_ok(T, N, K)) return BFPQ_E_UNSUPPORTED;
+    if (!i8_ptrs_ok(xcodes, xexp, wcodes, wexp, out) || !slabs || (reinterpret_cast<uintptr_t>(slabs) & 15u)) return BFPQ_E_ARG;
+    return i8_launch((const int8_t*)xcodes, xexp, (const int8_t*)wcodes, wexp, bias, out, slabs, parts, T, N, K, out_dtype, w_mant_bits, x_mant_bits,
+                     (hipStream_t)stream);
+}
+
+static int decode8_slices(int64_t T, int64_t N, int64_t K)
+{
+    const int64_t nb = K / 64, waves = (N / 16) * ((T + 15) / 16);
+    int64_t slices = (4096 + waves - 1) / waves;                  // aim at ~4096 waves on the chip
+    if (slices > nb) slices = nb;
+    if (slices < 1) slices = 1;
+    const int64_t bps = (nb + slices - 1) / slices;
+    return (int)((nb + bps - 1) / bps);
+}
+
+int64_t bfpq_hbfp_linear_decode8_ws(int64_t T, int64_t N, int64_t K)
+{
+    if (T < 1 || N < 16 || K < 64 || N % 16 != 0 || K % 64 != 0 || T > 65535 * 16 || N * K >= ((int64_t)1 << 32) || T * K >= ((int64_t)1 << 32))
+        return BFPQ_E_UNSUPPORTED;
+    return (int64_t)decode8_slices(T, N, K) * ((T + 15) / 16 * 16) * N;
+}
+
+int bfpq_hbfp_linear_decode8(const void* xcodes, const int8_t* xexp, const void* wcodes, const int8_t* wexp, const void* bias, void* out,
+                             float* slabs, int64_t T, int64_t N, int64_t K, int out_dtype, int w_mant_bits, int x_mant_bits, void* stream)
+{
+    if (!i8_args_ok(out_dtype, w_mant_bits, x_mant_bits) || T < 1 || N < 1) return BFPQ_E_ARG;
+    if (bfpq_hbfp_linear_decode8_ws(T, N, K) < 0) return BFPQ_E_UNSUPPORTED;
+    if (!xcodes || !xexp || !wcodes || !wexp || !out || !slabs) return BFPQ_E_ARG;
+    if ((reinterpret_cast<uintptr_t>(xcodes) | reinterpret_cast<uintptr_t>(wcodes) | reinterpret_cast<uintptr_t>(slabs)) & 15u) return BFPQ_E_ARG;
+    const int slices = decode8_slices(T, N, K);
+    const int64_t nb = K / 64;
+    const int bps = (int)((nb + slices - 1) / slices);
+    const int64_t waves = (N / 16) * slices, groups = (T + 15) / 16;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_i8_decode, dim3((unsigned)((waves + 3) / 4), (unsigned)groups), dim3(256), 0, s, (const int8_t*)wcodes, wexp,
+                       (const int8_t*)xcodes, xexp, slabs, (int)T, (int)N, (int)K, bps, slices, w_mant_bits, x_mant_bits);
+    // slabs are [slices][Tpad][N]: the first T rows of each slab are the outputs' partial sums
+    reduce_dt(out_dtype, slabs, (size_t)(groups * 16 * N), bias, out, T, N, slices, s);
+    return (int)hipGetLastError();
+}
+
+int bfpq_codes4_to_i8(const void* codes4, void* codes8, int64_t n_codes, void* stream)
+{
+    if (n_codes < 0 || n_codes % 8 != 0) return BFPQ_E_ARG;
+    if (n_codes == 0) return 0;
+    if (!codes4 || !codes8 || (reinterpret_cast<uintptr_t>(codes4) & 3u) || (reinterpret_cast<uintptr_t>(codes8) & 7u)) return BFPQ_E_ARG;
+    const int64_t items = n_codes / 8;
+    int64_t g = (items + 255) / 256;
+    if (g > 8192) g = 8192;
+    hipLaunchKernelGGL(k_codes4_to_i8, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)codes4, (uint2*)codes8, items);
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -26,6 +26,8 @@ using namespace bfpq;
 
 extern "C" __attribute__((visibility("hidden"))) int bfpq_g_gemm_rt;   // bfpq_gemm.hip
 extern "C" __attribute__((visibility("hidden"))) int bfpq_g_mx8_variant;   // bfpq_mxgemm.hip
+extern "C" __attribute__((visibility("hidden"))) int bfpq_g_i8_variant;    // bfpq_i8gemm.hip
+extern "C" __attribute__((visibility("hidden"))) int bfpq_g_i8_parts;      // bfpq_i8gemm.hip
 
 #include "bfpq_device.h"
 #include "bfpq_quant_math.h"
@@ -551,6 +553,8 @@ int bfpq_tune(int key, int value)
     if (key == BFPQ_TUNE_GEMM_ROW_TILES && (value == 0 || value == 1 || value == 2 || value == 4)) { bfpq_g_gemm_rt = value; return 0; }
     if (key == BFPQ_TUNE_MX8_VARIANT && value >= -1 && value <= 6) { bfpq_g_mx8_variant = value; return 0; }
     if (key == BFPQ_TUNE_LIST_OWN_MB && value >= 0) { bfpq_g_list_own_mb = value; return 0; }
+    if (key == BFPQ_TUNE_I8_VARIANT && value >= -1 && value <= 2) { bfpq_g_i8_variant = value; return 0; }
+    if (key == BFPQ_TUNE_I8_PARTS && value >= 0 && value <= 64) { bfpq_g_i8_parts = value; return 0; }
     return BFPQ_E_ARG;
 }
 

@@ -109,13 +109,23 @@ def load_library():
         L.bfpq_hbfp_linear_mx8.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, vp]
         L.bfpq_hbfp_linear_mx8_parts.argtypes = [i64, i64, i64]
         L.bfpq_hbfp_linear_mx8_splitk.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, i64, i32, vp]
+        L.bfpq_hbfp_linear_i8_ok.argtypes = [i64, i64, i64]
+        L.bfpq_hbfp_linear_i8_parts.argtypes = [i64, i64, i64]
+        L.bfpq_hbfp_linear_i8.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, i32, vp]
+        L.bfpq_hbfp_linear_i8_splitk.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, i64, i32, i32, i32, vp]
+        L.bfpq_hbfp_linear_decode8_ws.argtypes = [i64, i64, i64]
+        L.bfpq_hbfp_linear_decode8_ws.restype = i64
+        L.bfpq_hbfp_linear_decode8.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, i32, vp]
+        L.bfpq_codes4_to_i8.argtypes = [vp, vp, i64, vp]
         for name in ("bfpq_exp_window_host", "bfpq_nm4_lut_host", "bfpq_nm8_lut_host", "bfpq_compact24", "bfpq_expand24", "bfpq_quantize_nm", "bfpq_fake_quantize", "bfpq_fake_quantize_batched", "bfpq_fake_quantize_list", "bfpq_is_fused", "bfpq_nm_sparsify",
                      "bfpq_select_passes", "bfpq_select", "bfpq_select_hist", "bfpq_select_resolve", "bfpq_select_resolve_ex", "bfpq_select_reset",
                      "bfpq_prune_quantize", "bfpq_prune_quantize_batched", "bfpq_prune_quantize_list",
                      "bfpq_threshold_apply", "bfpq_quantize_threshold", "bfpq_int_quantize", "bfpq_dequantize", "bfpq_hbfp_linear_slices",
                      "bfpq_hbfp_linear_decode", "bfpq_hbfp_linear_tiled_ok", "bfpq_hbfp_linear_decode_tiled",
                      "bfpq_mx8_from_hbfp", "bfpq_quantize_mx8", "bfpq_hbfp_linear_mx8_ok", "bfpq_hbfp_linear_mx8",
-                     "bfpq_hbfp_linear_mx8_parts", "bfpq_hbfp_linear_mx8_splitk", "bfpq_quantize_mx8_nm", "bfpq_quantize_threshold_mx8"):
+                     "bfpq_hbfp_linear_mx8_parts", "bfpq_hbfp_linear_mx8_splitk", "bfpq_quantize_mx8_nm", "bfpq_quantize_threshold_mx8",
+                     "bfpq_hbfp_linear_i8_ok", "bfpq_hbfp_linear_i8_parts", "bfpq_hbfp_linear_i8", "bfpq_hbfp_linear_i8_splitk",
+                     "bfpq_hbfp_linear_decode8", "bfpq_codes4_to_i8"):
             getattr(L, name).restype = i32
         _lib = L
         return _lib
@@ -125,7 +135,9 @@ EXPORTED_SYMBOLS = ("bfpq_hbfp_linear_mx8_parts", "bfpq_hbfp_linear_mx8_splitk",
                     "bfpq_nm_prune_mask_host", "bfpq_quantize_nm", "bfpq_fake_quantize", "bfpq_fake_quantize_batched", "bfpq_fake_quantize_list", "bfpq_is_fused", "bfpq_nm_sparsify",
                     "bfpq_select_passes", "bfpq_select", "bfpq_select_hist", "bfpq_select_resolve", "bfpq_select_resolve_ex", "bfpq_select_reset",
                     "bfpq_prune_quantize", "bfpq_prune_quantize_batched", "bfpq_prune_quantize_list",
-                    "bfpq_threshold_apply", "bfpq_quantize_threshold", "bfpq_quantize_mx8_nm", "bfpq_quantize_threshold_mx8")
+                    "bfpq_threshold_apply", "bfpq_quantize_threshold", "bfpq_quantize_mx8_nm", "bfpq_quantize_threshold_mx8",
+                    "bfpq_hbfp_linear_i8_ok", "bfpq_hbfp_linear_i8_parts", "bfpq_hbfp_linear_i8", "bfpq_hbfp_linear_i8_splitk",
+                    "bfpq_hbfp_linear_decode8_ws", "bfpq_hbfp_linear_decode8", "bfpq_codes4_to_i8")
 
 
 def check(rc, what):
@@ -1086,4 +1098,71 @@ def hbfp_linear_mx8(x, w8, wscale, x_mant_bits, epsilon=1e-8, bias=None, out_dty
         else:
             check(L.bfpq_hbfp_linear_mx8(_ptr(x8), _ptr(xs), _ptr(w8), _ptr(wscale), _ptr(bias) if bias is not None else None, _ptr(out),
                                          T, N, K, DTYPE_CODE[out_dtype], _stream(x)), "bfpq_hbfp_linear_mx8")
+    return out.view(tuple(x.shape[:-1]) + (N,))
+
+
+# ---- HBFP5-HBFP8 on the int8 matrix unit (bfpq_i8gemm.hip) ---------------------------------------
+DECODE8_TOKENS = 16       # up to this many tokens the decode-shaped kernel runs; more take the LDS-tiled kernel where K % 256 == 0
+
+
+def hbfp_linear_i8_ok(T, N, K, w_mant_bits, x_mant_bits, block_size=64):
+    """hbfp_linear_i8 takes this problem: block 64, mantissas of 1..7 bits on both sides, N % 16 == 0, K % 64 == 0 (the tiled kernel
+    needs K % 256 == 0; other K go to the decode-shaped kernel at any token count)"""
+    return (block_size == 64 and 1 <= w_mant_bits <= 7 and 1 <= x_mant_bits <= 7 and T >= 1 and N >= 16 and N % 16 == 0
+            and K >= 64 and K % 64 == 0 and load_library().bfpq_hbfp_linear_decode8_ws(T, N, K) >= 0)
+
+
+def codes4_to_i8(codes4, n_codes):
+    """4-bit packed codes (two's-complement nibbles, low first) -> int8 codes [n_codes] (bfpq_codes4_to_i8)"""
+    require_device_tensor_any(codes4)
+    L = load_library()
+    dev = codes4.device
+    with torch.cuda.device(dev):
+        out = torch.empty(n_codes, dtype=torch.int8, device=dev)
+        check(L.bfpq_codes4_to_i8(_ptr(codes4.contiguous()), _ptr(out), int(n_codes), torch.cuda.current_stream(dev).cuda_stream), "bfpq_codes4_to_i8")
+    return out
+
+
+def hbfp_linear_i8(x, wcodes8, wexps, w_mant_bits, x_mant_bits, epsilon=1e-8, bias=None, out_dtype=None, act=None, xq=None):
+    """out = Q(x) @ W^T (+ bias) for any number of tokens with W packed as int8 codes [N, K] + int8 exponents [N, K/64] (block 64,
+    w_mant_bits 1..7) and x quantized to HBFP(x_mant_bits + 1) block 64 (x_mant_bits 1..7, round-half-even), pruned by `act`
+    (ActSparsity or None; unstructured: one threshold over all tokens of the call).  Block dot products are exact integer sums on the
+    int8 matrix unit, fp32 across blocks in block order.  xq: the activation operand made beforehand (act_codes); x then only gives
+    shape and dtype."""
+    require_device_tensor(x)
+    L = load_library()
+    K = x.shape[-1]
+    T = x.numel() // K
+    N = wexps.shape[0]
+    if not hbfp_linear_i8_ok(T, N, K, w_mant_bits, x_mant_bits):
+        raise ValueError(f"hbfp_linear_i8 needs N % 16 == 0, K % 64 == 0 and mantissas of 1..7 bits "
+                         f"(got T={T}, N={N}, K={K}, w_mant_bits={w_mant_bits}, x_mant_bits={x_mant_bits})")
+    if wcodes8.dtype != torch.int8 or wcodes8.numel() != N * K:
+        raise ValueError("hbfp_linear_i8 takes int8 weight codes [N, K] (4-bit codes: codes4_to_i8 first)")
+    dev = x.device
+    out_dtype = out_dtype or x.dtype
+    with torch.cuda.device(dev):
+        if xq is not None:
+            xc, xe = xq[0].contiguous(), xq[1].contiguous()
+        else:
+            xc, xe = act_codes(x.reshape(T, K), x_mant_bits, epsilon, act)
+        wc, we = wcodes8.contiguous(), wexps.contiguous()
+        out = torch.empty((T, N), dtype=out_dtype, device=dev)
+        if bias is not None:
+            bias = bias.to(out_dtype).contiguous()
+        bp = _ptr(bias) if bias is not None else None
+        args = (int(w_mant_bits), int(x_mant_bits), _stream(x))
+        if T > DECODE8_TOKENS and L.bfpq_hbfp_linear_i8_ok(T, N, K):
+            parts = L.bfpq_hbfp_linear_i8_parts(T, N, K) if SPLIT_K else 1
+            if parts > 1:                                              # few output tiles: K split, fp32 slabs added in part order
+                slabs = torch.empty((parts, T, N), dtype=torch.float32, device=dev)
+                check(L.bfpq_hbfp_linear_i8_splitk(_ptr(xc), _ptr(xe), _ptr(wc), _ptr(we), bp, _ptr(out), _ptr(slabs), parts, T, N, K,
+                                                   DTYPE_CODE[out_dtype], *args), "bfpq_hbfp_linear_i8_splitk")
+            else:
+                check(L.bfpq_hbfp_linear_i8(_ptr(xc), _ptr(xe), _ptr(wc), _ptr(we), bp, _ptr(out), T, N, K, DTYPE_CODE[out_dtype], *args),
+                      "bfpq_hbfp_linear_i8")
+        else:
+            slabs = torch.empty(int(L.bfpq_hbfp_linear_decode8_ws(T, N, K)), dtype=torch.float32, device=dev)
+            check(L.bfpq_hbfp_linear_decode8(_ptr(xc), _ptr(xe), _ptr(wc), _ptr(we), bp, _ptr(out), _ptr(slabs), T, N, K,
+                                             DTYPE_CODE[out_dtype], *args), "bfpq_hbfp_linear_decode8")
     return out.view(tuple(x.shape[:-1]) + (N,))

@@ -13,7 +13,11 @@ from .bfp import bfp_ops
 def patch_linear_layers(model, bfp_args, skip=("lm_head", "classifier", "score"), convs=False, cache_weights=False, matrix_unit=False):
     """Replace nn.Linear children by bfp_ops.BFPLinear(**bfp_args) that reuse weight / bias.  Modules whose
     qualified name ends with an entry of `skip` stay as they are (the reference leaves the LM heads alone).
+    matrix_unit (False, True or 'int8'): with cache_weights, the cached Linear forward's matrix-unit route (BFPLinear.enable_weight_cache).
     Returns the list of patched module names."""
+    if isinstance(matrix_unit, str) or matrix_unit not in (True, False):
+        if matrix_unit != 'int8':
+            raise ValueError(f"matrix_unit must be False, True or 'int8' (got {matrix_unit!r})")
     patched = []
     for parent_name, parent in list(model.named_modules()):
         for child_name, child in list(parent.named_children()):
@@ -32,7 +36,7 @@ def patch_linear_layers(model, bfp_args, skip=("lm_head", "classifier", "score")
             new.bias = child.bias
             new.train(child.training)
             if cache_weights:
-                new.enable_weight_cache(matrix_unit=matrix_unit and isinstance(new, bfp_ops.BFPLinear))
+                new.enable_weight_cache(matrix_unit=matrix_unit if isinstance(new, bfp_ops.BFPLinear) else False)
             setattr(parent, child_name, new)
             patched.append(full)
     return patched
@@ -63,11 +67,18 @@ def prime_weight_caches(model):
     return n
 
 
+# 8-bit-code modules run PackedBFP.linear_i8 up to this many tokens; above it PackedBFP.linear's routes (weight decoded once per call +
+# the library GEMM) measured faster (LLaMA-7B projections at 2048 tokens, 1.2-1.5x)
+I8_MAX_TOKENS = 512
+
+
 class PackedBFPLinear(torch.nn.Module):
-    """Inference-only Linear whose weight lives in packed HBFP form (4-bit codes + one int8 exponent per block of 64:
-    0.516 B per weight instead of 2) -- what a BFPLinear with w_sparsity / HBFP4 computes in its forward, with the weight
-    quantized ONCE.  Up to 64 tokens the product comes straight from the codes (integer block dot products on the int8
-    matrix cores, PackedBFP.linear_decode); more tokens decode the weight and use the library GEMM.
+    """Inference-only Linear whose weight lives in packed HBFP form -- what a BFPLinear with w_sparsity / HBFP computes in its forward,
+    with the weight quantized ONCE.  HBFP4 (mant_bits <= 3): 4-bit codes + one int8 exponent per block of 64 (0.516 B per weight
+    instead of 2), run by PackedBFP.linear (up to 64 tokens straight from the codes on the int8 matrix cores, more tokens on the
+    block-scaled matrix instruction or the library GEMM).  HBFP5-HBFP8 (mant_bits 4..7): 8-bit codes (1.016 B per weight), run by
+    PackedBFP.linear_i8 on the int8 matrix instruction up to I8_MAX_TOKENS tokens; more than 64 tokens of HBFP5 (activation and weight
+    mantissas <= 4 bits) take PackedBFP.linear's block-scaled route, and more than I8_MAX_TOKENS tokens its other routes.
     The codes and exponents are registered buffers (`codes`, `exps`): they follow .to() / .cuda(), appear in state_dict()
     and load back with load_state_dict(); shape / dtype / mantissa width / activation pruning travel as extra state.
     x_sparsity (native.ActSparsity or None): the activations are pruned as the reference's in_sparsity does."""
@@ -107,14 +118,15 @@ class PackedBFPLinear(torch.nn.Module):
 
     @classmethod
     def from_linear(cls, lin, bfp_args):
-        """weight -> float_to_bfp_packed with the module's config (format 'bfp', block 64, mant_bits <= 3, round-half-even;
+        """weight -> float_to_bfp_packed with the module's config (format 'bfp', block 64, mant_bits 1..7 -- 4-bit codes up to 3, 8-bit codes
+        from 4 --, round-half-even;
         N:M from the w_sparsity keys, order from `first`); activations use mant_bits of the same config.  Unstructured weight pruning is
         packed for first='s' (prune, then quantize: one fused launch writes the codes).  Pruned activations (in_sparsity: N:M or
         unstructured, either order, the same keys) are pruned in every forward, as the reference does.  Configurations this module
         cannot reproduce (unstructured WEIGHT pruning after quantization, stochastic rounding) are refused."""
         a = bfp_ops.unpack_bfp_args(dict(bfp_args))
-        assert a['num_format'] == 'bfp' and a['sparsity_num_format'] == 'bfp' and a['block_size'] == 64 and 1 <= a['mant_bits'] <= 3, \
-            "PackedBFPLinear holds 4-bit codes: an HBFP config with block_size 64 and mant_bits <= 3 (HBFP4)"
+        assert a['num_format'] == 'bfp' and a['sparsity_num_format'] == 'bfp' and a['block_size'] == 64 and 1 <= a['mant_bits'] <= 7, \
+            "PackedBFPLinear holds 4- or 8-bit codes: an HBFP config with block_size 64 and mant_bits <= 7 (HBFP2-HBFP8)"
         if a['w_sparsity'] and a['sparsity_mode'] == 'unstructured' and a['first'] != 's':
             raise ValueError("PackedBFPLinear: unstructured pruning AFTER quantization (first='q') is not packed here")
         if a['w_sparsity'] and a['sparsity_mode'] not in ('structured', 'unstructured'):
@@ -130,7 +142,14 @@ class PackedBFPLinear(torch.nn.Module):
         return cls(pw, lin.bias, a['mant_bits'], a['epsilon'], act)
 
     def forward(self, x):
-        return self.packed.linear(x, self.bias, self.x_mant_bits, self.epsilon, x_sparsity=self.x_sparsity)
+        p = self.packed
+        if p.code_bits == 8:
+            T = x.numel() // x.shape[-1] if x.shape[-1] else 0
+            hbfp5_prefill = T > 64 and p.mant_bits <= 4 and self.x_mant_bits <= 4 and native.hbfp_linear_mx8_ok(T, p.shape[0], p.shape[1], p.mant_bits,
+                                                                                                                   self.x_mant_bits)
+            if T <= I8_MAX_TOKENS and not hbfp5_prefill:
+                return p.linear_i8(x, self.bias, self.x_mant_bits, self.epsilon, x_sparsity=self.x_sparsity)
+        return p.linear(x, self.bias, self.x_mant_bits, self.epsilon, x_sparsity=self.x_sparsity)
 
     def extra_repr(self):
         act = "" if self.x_sparsity is None else f", x_sparsity={tuple(self.x_sparsity)}"
@@ -139,16 +158,18 @@ class PackedBFPLinear(torch.nn.Module):
 
 def pack_linear_layers(model, bfp_args, skip=("lm_head", "classifier", "score")):
     """Inference deployment: replace nn.Linear / BFPLinear children by PackedBFPLinear (weights quantized once and
-    held as 4-bit codes; the original bf16/fp16 weight is dropped).  Needs an HBFP config with block_size 64 and
-    weight mantissa <= 3 bits (+ optional N:M).  Returns the patched names and the bytes saved."""
+    held as 4-bit codes for mant_bits <= 3, 8-bit codes for 4..7; the original bf16/fp16 weight is dropped).  Needs an HBFP config with
+    block_size 64 and mant_bits <= 7 (+ optional N:M or unstructured pruning).  Returns the patched names and the bytes saved."""
     patched, saved = [], 0
+    a = bfp_ops.unpack_bfp_args(dict(bfp_args))
+    k_mult = 256 if a['mant_bits'] <= 3 else 64             # 8-bit codes (mant_bits >= 4) run at any K % 64 == 0 (PackedBFP.linear_i8)
     for parent_name, parent in list(model.named_modules()):
         for child_name, child in list(parent.named_children()):
             full = f"{parent_name}.{child_name}" if parent_name else child_name
             if any(full.endswith(s) for s in skip) or not isinstance(child, torch.nn.Linear):
                 continue
-            if child.in_features % 256 or child.out_features % 16:
-                continue                                    # shapes the decode kernel does not take stay as they are
+            if child.in_features % k_mult or child.out_features % 16:
+                continue                                    # shapes the packed kernels do not take stay as they are
             new = PackedBFPLinear.from_linear(child, bfp_args)
             saved += child.weight.numel() * child.weight.element_size() - new.packed.nbytes()
             setattr(parent, child_name, new)
