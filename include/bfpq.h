@@ -246,6 +246,11 @@ int bfpq_int_quantize(const void* in_dev, float* out_dev, int64_t outer, int64_t
 int bfpq_dequantize(const void* codes_dev, const int8_t* exp_dev, void* out_dev, int64_t rows, int64_t cols, int dtype,
                     int block_size, int mant_bits, int code_bits, void* stream);
 
+/* ---- 'stoc' rounding of an fp16 tensor, fp16 result -> the reference's fp32 result (n elements): a plain widening,
+ * except that +-inf becomes +-65536 -- the one fp32 result of a finite fp16 input that fp16 cannot hold (a block whose
+ * 2^e overflows).  in_dev 8-byte aligned, out_dev 16-byte aligned. */
+int bfpq_stoc_widen_f16(const void* in_dev, void* out_dev, int64_t n, void* stream);
+
 /* ---- 2:4 compaction of 4-bit codes (optional part of the packed format) --------------------
  * codes_dev: n_bytes bytes of 4-bit codes as bfpq_quantize_nm writes them (n_bytes % 4 == 0; 8 elements per 4 bytes),
  * every aligned group of 4 codes holding at most 2 non-zeros (N=2, M=4 in either order guarantees it).

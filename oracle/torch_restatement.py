@@ -8,7 +8,8 @@ G2 / G3 / G4), which is what makes it a faithful stand-in.
 
 What follows which reference lines (src/transformers/bfp/bfp_ops.py):
     shared_exponent   :29-33   abs, max(dim=1), + eps, log2, ceil -- all in the tensor's dtype
-    snap_blocks       :35-44   pow, pow, sub, div, round (half-even), mul_, neg, max, min
+    snap_blocks       :35-44   pow, pow, sub, div, round (half-even; 'stoc': fp32 torch.rand - 0.5 added first, :20-24),
+                               mul_, neg, max, min
     hbfp              :46-59   pad to the block width, view(-1, block), snap, un-view, narrow
     prune_groups      :73-91   pad to M, view(-1, M), topk(|.|, M-N, smallest), int64 ones mask, scatter_, where
     prune_global      :61-71   the same recipe on the tensor flattened to one row, k = int(numel * frac)
@@ -22,11 +23,14 @@ def shared_exponent(blocks, eps):
     return (blocks.abs().max(dim=1, keepdim=True)[0] + eps).log2().ceil()
 
 
-def snap_blocks(blocks, mant_bits, eps):
+def snap_blocks(blocks, mant_bits, eps, rounding_mode='determ'):
     e = shared_exponent(blocks, eps)
     step = torch.pow(2.0, e - mant_bits)
     top = torch.pow(2.0, e) - step
-    q = (blocks / step).round()
+    q = blocks / step
+    if rounding_mode == 'stoc':                            # fp32 dither: everything after it is fp32
+        q = (torch.rand(q.shape) - 0.5).add_(q)
+    q = q.round()
     q *= step
     return torch.min(torch.max(q, -top), top)
 
@@ -41,10 +45,10 @@ def _rows_of(t, width):
     return t.contiguous().view(-1, width), shape
 
 
-def hbfp(t, block_size, mant_bits, eps=1e-8):
+def hbfp(t, block_size, mant_bits, eps=1e-8, rounding_mode='determ'):
     cols = t.shape[-1]
     rows, shape = _rows_of(t, block_size)
-    return snap_blocks(rows, mant_bits, eps).contiguous().view(shape).narrow(-1, 0, cols)
+    return snap_blocks(rows, mant_bits, eps, rounding_mode).contiguous().view(shape).narrow(-1, 0, cols)
 
 
 def _zero_smallest(rows, drop):
@@ -70,8 +74,8 @@ def prune_global(t, frac):
 def fake_quantize(t, mant_bits, epsilon, rounding_mode, device, block_size, num_format, weight_mant_bits,
                   in_sparsity, w_sparsity, grad_sparsity, sparsity_frac, N, M, sparsity_num_format, first,
                   sparsity_mode, identifier='', sgd_update=False, **_unused):
-    """float_to_bfp_blocked for the 'bfp' / 'fp32' formats and round-half-even ('determ')"""
-    assert num_format == 'bfp' and rounding_mode == 'determ'
+    """float_to_bfp_blocked for the 'bfp' / 'fp32' formats, 'determ' or 'stoc' (torch.rand on the CPU generator)"""
+    assert num_format == 'bfp' and rounding_mode in ('determ', 'stoc')
     on = {'in': in_sparsity, 'w': w_sparsity, 'grad': grad_sparsity}.get(identifier, False) == True  # noqa: E712
 
     def S(x):
@@ -87,7 +91,7 @@ def fake_quantize(t, mant_bits, epsilon, rounding_mode, device, block_size, num_
         if sparsity_num_format == 'fp32':
             return x
         if sparsity_num_format == 'bfp':
-            return hbfp(x, block_size, weight_mant_bits if sgd_update else mant_bits, epsilon)
+            return hbfp(x, block_size, weight_mant_bits if sgd_update else mant_bits, epsilon, rounding_mode)
         raise ValueError(sparsity_num_format)
 
     return Q(S(t)) if first == 's' else S(Q(t))

@@ -11,6 +11,8 @@ Differences from the reference, all documented in DESIGN.md:
     index first"; the reference's choice is an artefact of a sequential introselect.
 """
 import collections
+import contextlib
+import threading
 
 import torch
 import torch.nn.functional as F
@@ -28,12 +30,40 @@ class rounding_modes:
     modes = [STOC, DETERM]
 
 
+_seed_salt = threading.local()     # .value non-zero inside seed_salt(): mixed into every 'stoc' seed drawn on this thread
+
+
+@contextlib.contextmanager
+def seed_salt(salt):
+    """'stoc' seeds drawn inside (on this thread) are mixed with `salt`; the torch generator advances as without it.  The
+    sharded paths (dist.py) salt with the global rank: jobs seed every process alike, and the dither is keyed by the
+    shard-local element index, so without it every shard would round with the same dither field."""
+    prev = getattr(_seed_salt, 'value', 0)
+    _seed_salt.value = int(salt)
+    try:
+        yield
+    finally:
+        _seed_salt.value = prev
+
+
+def _mix_seed(seed, salt):
+    """splitmix64 finalizer of seed ^ salt * golden ratio, cut to a non-zero 62-bit seed"""
+    m = (1 << 64) - 1
+    z = (seed ^ (salt * 0x9E3779B97F4A7C15)) & m
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+    z = (z ^ (z >> 31)) & ((1 << 62) - 1)
+    return z or 1
+
+
 def _seed_for(mode):
-    """0 -> round-half-even; otherwise a non-zero 62-bit seed taken from torch's CPU generator"""
+    """0 -> round-half-even; otherwise a non-zero 62-bit seed taken from torch's CPU generator (salted by seed_salt)"""
     if mode == rounding_modes.DETERM:
         return 0
     if mode == rounding_modes.STOC:
-        return int(torch.randint(1, 2 ** 62, (1,)).item())
+        seed = int(torch.randint(1, 2 ** 62, (1,)).item())
+        salt = getattr(_seed_salt, 'value', 0)
+        return _mix_seed(seed, salt) if salt else seed
     raise NotImplementedError("Rounding mode %s is not implemented", mode)
 
 
@@ -67,8 +97,11 @@ def _fast_quant(block_size, mant_bits, epsilon, N, M, sparsify_first):
 
 
 def _stoc_dtype(t, mode):
-    """reference quirk: 'stoc' adds fp32 noise, so a half input comes back as fp32"""
-    return t.float() if (mode == rounding_modes.STOC and t.dtype != torch.float32) else t
+    """reference quirk: 'stoc' adds fp32 noise, so a half input comes back as fp32.  t is the result written in
+    the input's dtype; for fp16 its +-inf stands for the fp32 result +-65536 (native.stoc_widen_f16)."""
+    if mode != rounding_modes.STOC or t.dtype == torch.float32:
+        return t
+    return native.stoc_widen_f16(t) if t.dtype == torch.float16 else t.float()
 
 
 def round_tensor(t, mode, device):
@@ -95,7 +128,12 @@ def _convert_blocked_float_to_bfp(t, mant_bits, epsilon, rounding_mode, device):
     """reference: bfp_ops.py:35-44 -- every row of the 2-D t is one block"""
     native.require_device_tensor(t)
     assert t.dim() == 2
-    y, _, _ = native.quantize_nm(t, t.shape[1], mant_bits, epsilon, stoch_seed=_seed_for(rounding_mode))
+    seed = _seed_for(rounding_mode)
+    src = t.contiguous()
+    if seed and t.dtype != torch.float32 and t.numel() and native.is_fused(src, t.shape[1]):
+        _, y, _ = native.quantize_nm(src, t.shape[1], mant_bits, epsilon, want_deq=False, code_bits=32, stoch_seed=seed)
+        return y                                       # the fp32 result, written by the kernel
+    y, _, _ = native.quantize_nm(src, t.shape[1], mant_bits, epsilon, stoch_seed=seed)
     return _stoc_dtype(y, rounding_mode)
 
 

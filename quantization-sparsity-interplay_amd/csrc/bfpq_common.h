@@ -176,6 +176,15 @@ __device__ __forceinline__ float quant_elem(float x, const BlockScale& b, bool s
     return t_min(t_max(y, -b.max_v), b.max_v);
 }
 
+// fp32 image of an fp16 'stoc' result.  The reference's result is fp32 (its fp32 dither promotes the round, the multiply and
+// the clamp); from a finite fp16 input every value it can take is an fp16 value except +-65536 -- a block whose 2^e overflows
+// has max_v = inf and r * interval = 2^16 -- which the fp16 store turns into +-inf.  A finite input gives +-inf in no other
+// way (a block holding an inf is a NaN block), so +-inf decodes to +-65536.
+__device__ __forceinline__ uint32_t stoc_f16_image(uint32_t h)
+{
+    return (h & 0x7fffu) == 0x7c00u ? ((h & 0x8000u) << 16) | 0x47800000u : f2u(raw_to_f32<BFPQ_F16>(h));
+}
+
 __device__ __forceinline__ int8_t sat_exp(const BlockScale& b)
 {
     if (b.mode == 2) return (int8_t)-128;

@@ -248,6 +248,9 @@ __device__ __forceinline__ void fused_flat_body(const FusedArgs& a, [[maybe_unus
         float code[VEC];
 #pragma unroll
         for (int j = 0; j < VEC; j++) code[j] = 0.f;
+        // 'stoc' on fp16: only the cold tier can write the +-inf that stands for the reference's +-65536 (stoc_f16_image); the
+        // hot tier's blocks have a finite 2^e.  Wave-uniform: the cold tier runs for the whole wave.
+        [[maybe_unused]] bool stoc_cold = false;
         int e_blk = 0;
         bool nan_blk = false;
         [[maybe_unused]] uint32_t pack_w = 0, pack_w2 = 0;        // PACK4: the item's eight 4-bit codes (MX8: eight e4m3 bytes), the block's exponent byte
@@ -402,6 +405,7 @@ __device__ __forceinline__ void fused_flat_body(const FusedArgs& a, [[maybe_unus
                 if (__builtin_expect(__any(slow), 0)) {
                     // cold: replay the reference's op sequence step by step (exact for every block)
                     const BlockScale bs = block_scale<DT>(mx, a.mant_bits, a.eps_dt, s_win);
+                    if constexpr (STOCH && DT == BFPQ_F16) stoc_cold = true;
                     e_blk = bs.e;
                     nan_blk = bs.mode == 2;
                     uint32_t outraw[VEC];
@@ -529,6 +533,12 @@ __device__ __forceinline__ void fused_flat_body(const FusedArgs& a, [[maybe_unus
             uint32_t f[VEC];
 #pragma unroll
             for (int j = 0; j < VEC; j++) f[j] = f2u(raw_to_f32<DT>((od[j >> 1] >> (16 * (j & 1))) & 0xffffu));
+            if constexpr (STOCH && DT == BFPQ_F16) {
+                if (__builtin_expect(stoc_cold, 0)) {
+#pragma unroll
+                    for (int j = 0; j < VEC; j++) f[j] = stoc_f16_image((od[j >> 1] >> (16 * (j & 1))) & 0xffffu);   // +-inf -> +-65536
+                }
+            }
             // A lane's eight results are 32 bytes; stored as they lie, each of the two store instructions of a wave writes 16 bytes of
             // every 32 (measured on the 'int' format's kernels: launches up to 1.7 x slower, at random).  The wave's 2 KB go through a
             // wave-private LDS tile instead and leave as two instructions of 1 KB without holes (a wave's items are consecutive:
@@ -571,6 +581,12 @@ __device__ __forceinline__ void fused_flat_body(const FusedArgs& a, [[maybe_unus
 #pragma unroll
                 for (int j = 0; j < VEC; j++)
                     f[j] = VEC == 4 ? od[j] : f2u(raw_to_f32<DT>((od[j >> 1] >> (16 * (j & 1))) & 0xffffu));
+                if constexpr (STOCH && DT == BFPQ_F16) {
+                    if (__builtin_expect(stoc_cold, 0)) {
+#pragma unroll
+                        for (int j = 0; j < VEC; j++) f[j] = stoc_f16_image((od[j >> 1] >> (16 * (j & 1))) & 0xffffu);
+                    }
+                }
                 uint4* dst = reinterpret_cast<uint4*>(a.out_codes) + item * (VEC / 4);
                 dst[0] = make_uint4(f[0], f[1], f[2], f[3]);
                 if constexpr (VEC == 8) dst[1] = make_uint4(f[4], f[5], f[6], f[7]);

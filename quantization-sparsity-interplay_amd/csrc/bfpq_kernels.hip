@@ -1040,3 +1040,32 @@ int bfpq_prune_quantize_batched(const bfpq_prune_desc* descs, int n, int dtype, 
 }
 
 }  // extern "C"
+
+// 'stoc' result of an fp16 tensor written in fp16 -> the reference's fp32 result (stoc_f16_image: +-inf is +-65536).
+// Four elements per thread and step (8-byte loads, 16-byte stores).
+__global__ void __launch_bounds__(256) k_stoc_widen_f16(const uint16_t* __restrict__ in, uint32_t* __restrict__ out, int64_t n)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t n4 = n >> 2;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const uint2 w = reinterpret_cast<const uint2*>(in)[i];
+        reinterpret_cast<uint4*>(out)[i] = make_uint4(stoc_f16_image(w.x & 0xffffu), stoc_f16_image(w.x >> 16),
+                                                      stoc_f16_image(w.y & 0xffffu), stoc_f16_image(w.y >> 16));
+    }
+    for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = stoc_f16_image(in[i]);
+}
+
+extern "C" {
+
+int bfpq_stoc_widen_f16(const void* in, void* out, int64_t n, void* stream)
+{
+    if (n < 0) return BFPQ_E_ARG;
+    if (n == 0) return 0;
+    if (!in || !out || (reinterpret_cast<uintptr_t>(in) & 7u) || (reinterpret_cast<uintptr_t>(out) & 15u)) return BFPQ_E_ARG;
+    const int64_t want = ((n >> 2) + 255) / 256;
+    const int grid = (int)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
+    hipLaunchKernelGGL(k_stoc_widen_f16, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)in, (uint32_t*)out, n);
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

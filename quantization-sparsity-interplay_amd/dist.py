@@ -12,6 +12,8 @@ the result happens only when the caller asks for the tensor whole; on a fully co
 maps to concurrent point-to-point sends, so packed codes (2.9 MB per rank at the headline shape) or
 the dequantised slab (11.3 MB) move at per-link rate on all 7 links at once.
 """
+import functools
+
 import torch
 import torch.distributed as dist
 
@@ -100,6 +102,19 @@ class _NativeEngine:
         return native.quantize_threshold(t, ws, block_size, mant_bits, epsilon, stoch_seed=seed)[0]
 
 
+def _rank_seeds(fn):
+    """run fn with the 'stoc' seeds salted by this process's GLOBAL rank (bfp_ops.seed_salt): processes seeded alike by
+    torch.manual_seed draw the same seed, and the dither is keyed by the slab-local element index.  The global rank, not
+    the rank in `group`: with several groups (2-D parallelism) group ranks repeat across groups."""
+    @functools.wraps(fn)
+    def wrapped(*args, **kw):
+        rank = dist.get_rank() if (dist.is_available() and dist.is_initialized()) else 0
+        with bfp_ops.seed_salt(rank + 1):
+            return fn(*args, **kw)
+    return wrapped
+
+
+@_rank_seeds
 def float_to_bfp_blocked_sharded(local, rows_total, group=None, gather=False, compute=None, engine=None,
                                  identifier='', **bfp_args):
     """float_to_bfp_blocked (bfp_ops.py:124-149) on this rank's row slab of a [rows_total, ...] tensor.
@@ -207,6 +222,7 @@ def _many_sharded_one_exchange(locals_, rows_totals, group, gather, identifier, 
     return [all_gather_rows(o, r, group) for o, r in zip(outs, rows_totals)] if gather else outs
 
 
+@_rank_seeds
 def float_to_bfp_blocked_many_sharded(locals_, rows_totals, group=None, gather=False, identifier='', lanes=4, compute=None, engine=None,
                                       exchange='list', group_size=32, **bfp_args):
     """float_to_bfp_blocked_sharded for a LIST of row-sharded tensors -- every Linear weight of a model, each rank holding its

@@ -97,6 +97,7 @@ def load_library():
         L.bfpq_int_workspace_elems.restype = i64
         L.bfpq_int_quantize.argtypes = [vp, vp, i64, i64, i64, i32, i32, vp, vp]
         L.bfpq_dequantize.argtypes = [vp, vp, vp, i64, i64, i32, i32, i32, i32, vp]
+        L.bfpq_stoc_widen_f16.argtypes = [vp, vp, i64, vp]
         L.bfpq_hbfp_linear_slices.argtypes = [i64, i64]
         L.bfpq_hbfp_linear_decode.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, i32, vp]
         L.bfpq_hbfp_linear_tiled_ok.argtypes = [i64, i64]
@@ -120,7 +121,7 @@ def load_library():
         for name in ("bfpq_exp_window_host", "bfpq_nm4_lut_host", "bfpq_nm8_lut_host", "bfpq_compact24", "bfpq_expand24", "bfpq_quantize_nm", "bfpq_fake_quantize", "bfpq_fake_quantize_batched", "bfpq_fake_quantize_list", "bfpq_is_fused", "bfpq_nm_sparsify",
                      "bfpq_select_passes", "bfpq_select", "bfpq_select_hist", "bfpq_select_resolve", "bfpq_select_resolve_ex", "bfpq_select_reset",
                      "bfpq_prune_quantize", "bfpq_prune_quantize_batched", "bfpq_prune_quantize_list",
-                     "bfpq_threshold_apply", "bfpq_quantize_threshold", "bfpq_int_quantize", "bfpq_dequantize", "bfpq_hbfp_linear_slices",
+                     "bfpq_threshold_apply", "bfpq_quantize_threshold", "bfpq_int_quantize", "bfpq_dequantize", "bfpq_stoc_widen_f16", "bfpq_hbfp_linear_slices",
                      "bfpq_hbfp_linear_decode", "bfpq_hbfp_linear_tiled_ok", "bfpq_hbfp_linear_decode_tiled",
                      "bfpq_mx8_from_hbfp", "bfpq_quantize_mx8", "bfpq_hbfp_linear_mx8_ok", "bfpq_hbfp_linear_mx8",
                      "bfpq_hbfp_linear_mx8_parts", "bfpq_hbfp_linear_mx8_splitk", "bfpq_quantize_mx8_nm", "bfpq_quantize_threshold_mx8",
@@ -131,7 +132,7 @@ def load_library():
         return _lib
 
 
-EXPORTED_SYMBOLS = ("bfpq_hbfp_linear_mx8_parts", "bfpq_hbfp_linear_mx8_splitk", "bfpq_quantize_mx8", "bfpq_mx8_from_hbfp", "bfpq_hbfp_linear_mx8_ok", "bfpq_hbfp_linear_mx8", "bfpq_hbfp_linear_tiled_ok", "bfpq_hbfp_linear_decode_tiled", "bfpq_hbfp_linear_slices", "bfpq_hbfp_linear_decode", "bfpq_dequantize", "bfpq_tune", "bfpq_int_workspace_elems", "bfpq_int_quantize", "bfpq_select_ws_bytes", "bfpq_version", "bfpq_error_string", "bfpq_exp_window_host", "bfpq_nm4_lut_host", "bfpq_nm8_lut_host", "bfpq_compact24", "bfpq_expand24",
+EXPORTED_SYMBOLS = ("bfpq_hbfp_linear_mx8_parts", "bfpq_hbfp_linear_mx8_splitk", "bfpq_quantize_mx8", "bfpq_mx8_from_hbfp", "bfpq_hbfp_linear_mx8_ok", "bfpq_hbfp_linear_mx8", "bfpq_hbfp_linear_tiled_ok", "bfpq_hbfp_linear_decode_tiled", "bfpq_hbfp_linear_slices", "bfpq_hbfp_linear_decode", "bfpq_dequantize", "bfpq_stoc_widen_f16", "bfpq_tune", "bfpq_int_workspace_elems", "bfpq_int_quantize", "bfpq_select_ws_bytes", "bfpq_version", "bfpq_error_string", "bfpq_exp_window_host", "bfpq_nm4_lut_host", "bfpq_nm8_lut_host", "bfpq_compact24", "bfpq_expand24",
                     "bfpq_nm_prune_mask_host", "bfpq_quantize_nm", "bfpq_fake_quantize", "bfpq_fake_quantize_batched", "bfpq_fake_quantize_list", "bfpq_is_fused", "bfpq_nm_sparsify",
                     "bfpq_select_passes", "bfpq_select", "bfpq_select_hist", "bfpq_select_resolve", "bfpq_select_resolve_ex", "bfpq_select_reset",
                     "bfpq_prune_quantize", "bfpq_prune_quantize_batched", "bfpq_prune_quantize_list",
@@ -785,6 +786,19 @@ def dequantize(codes, exps, cols, dtype, block_size, mant_bits, code_bits, out=N
         check(L.bfpq_dequantize(_ptr(c), _ptr(e), _ptr(dst), rows, int(cols), DTYPE_CODE[dtype], int(block_size), int(mant_bits),
                                 int(code_bits), ctypes.c_void_p(torch.cuda.current_stream(exps.device).cuda_stream)), "bfpq_dequantize")
     return dst
+
+
+def stoc_widen_f16(t):
+    """fp32 image of an fp16 'stoc' result (bfpq_stoc_widen_f16): +-inf -> +-65536, the reference's value"""
+    require_device_tensor(t)
+    assert t.dtype == torch.float16
+    src = t.contiguous()
+    if src.data_ptr() % 8:
+        src = src.clone()
+    out = torch.empty(src.shape, dtype=torch.float32, device=src.device)
+    with torch.cuda.device(src.device):
+        check(load_library().bfpq_stoc_widen_f16(_ptr(src), _ptr(out), src.numel(), _stream(src)), "bfpq_stoc_widen_f16")
+    return out
 
 
 def is_fused(t, block_size, N=0, M=0):
