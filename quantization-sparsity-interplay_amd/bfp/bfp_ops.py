@@ -405,16 +405,49 @@ def sparsify(t, sparsity_mode, N=0, M=0, sparsity_frac=0):
     return _sparsify(t, True, sparsity_mode, str(t.device), N, M, sparsity_frac)
 
 
+def code_bits_for(mant_bits):
+    """the code width that holds a sign and `mant_bits` mantissa bits: 4, 8 or 16"""
+    return 4 if mant_bits <= 3 else (8 if mant_bits <= 7 else 16)
+
+
 def float_to_bfp_packed(t, mant_bits, block_size, epsilon=1e-8, N=0, M=0, first='s', code_bits=None, with_dequant=False):
     """Packed HBFP: integer mantissas (two's complement, 4/8/16 bits; 4-bit = two per byte, low nibble
     first) + one int8 shared exponent per block, value = code * 2**(exp - mant_bits).  N:M pruning is
     implied by zero codes.  Returns (codes, exps) or (codes, exps, dequantised)."""
     native.require_device_tensor(t)
     if code_bits is None:
-        code_bits = 4 if mant_bits <= 3 else (8 if mant_bits <= 7 else 16)
+        code_bits = code_bits_for(mant_bits)
     deq, codes, exps = native.quantize_nm(t, block_size, mant_bits, epsilon, N=N, M=M, sparsify_first=(first == 's'),
                                           want_deq=with_dequant, code_bits=code_bits, want_exp=True)
     return (codes, exps, deq.view(t.shape)) if with_dequant else (codes, exps)
+
+
+DECODE_TOKENS = 64           # up to this many tokens: the decode kernel (4-bit codes), and the int8 unit ahead of the block-scaled one
+I8_MAX_TOKENS = 512          # 8-bit-code PackedBFPLinear: the int8 unit up to here; above, the other routes measured faster (DESIGN §5d)
+CACHED_MX8_MIN_TOKENS = 32   # the cached BFPLinear(matrix_unit=True) takes the block-scaled route from here on (a tile row)
+
+
+def linear_route(T, N, K, code_bits, w_mant_bits, x_mant_bits, decode_tokens=DECODE_TOKENS, i8_max_tokens=0, mx8_min_tokens=1,
+                 block_size=64):
+    """Which kernel runs F.linear(Q_in(x), W) for T tokens, W [N, K] packed with `code_bits`-bit codes: 'empty' (nothing to launch),
+    'decode4' (PackedBFP.linear_decode), 'int8' (native.hbfp_linear_i8), 'mx8' (native.hbfp_linear_mx8) or 'fake' (the fake-quantised
+    activation times the dequantised weight).  The consumer's options: decode_tokens; i8_max_tokens, up to how many tokens 8-bit codes
+    run on the int8 unit (0: never, None: no limit; past decode_tokens 'mx8' goes first); mx8_min_tokens (None: never 'mx8')."""
+    if T == 0:
+        return 'empty'
+    if code_bits == 4 and block_size == 64 and T <= decode_tokens and N % 16 == 0 and K % 256 == 0:
+        return 'decode4'
+    mx8_allowed = code_bits in (4, 8) and mx8_min_tokens is not None and T >= mx8_min_tokens
+    int8 = code_bits == 8 and (i8_max_tokens is None or T <= i8_max_tokens)
+    mx8 = None
+    if int8 and T > decode_tokens:
+        mx8 = mx8_allowed and native.hbfp_linear_mx8_ok(T, N, K, w_mant_bits, x_mant_bits, block_size)
+        int8 = not mx8
+    if int8 and native.hbfp_linear_i8_ok(T, N, K, w_mant_bits, x_mant_bits, block_size):
+        return 'int8'
+    if mx8 is None:
+        mx8 = mx8_allowed and native.hbfp_linear_mx8_ok(T, N, K, w_mant_bits, x_mant_bits, block_size)
+    return 'mx8' if mx8 else 'fake'
 
 
 class PackedBFP:
@@ -429,7 +462,7 @@ class PackedBFP:
     @classmethod
     def quantize(cls, t, mant_bits, block_size, epsilon=1e-8, N=0, M=0, first='s', code_bits=None):
         if code_bits is None:
-            code_bits = 4 if mant_bits <= 3 else (8 if mant_bits <= 7 else 16)
+            code_bits = code_bits_for(mant_bits)
         codes, exps = float_to_bfp_packed(t, mant_bits, block_size, epsilon, N, M, first, code_bits)
         return cls(codes, exps, t.shape, t.dtype, mant_bits, block_size, code_bits)
 
@@ -440,7 +473,7 @@ class PackedBFP:
         unstructured path, the last one writing codes + exponents instead of the tensor"""
         native.require_device_tensor(t)
         if code_bits is None:
-            code_bits = 4 if mant_bits <= 3 else (8 if mant_bits <= 7 else 16)
+            code_bits = code_bits_for(mant_bits)
         assert sparsity_frac > 0
         k = int(t.numel() * sparsity_frac)
         if k > t.numel():
@@ -449,6 +482,25 @@ class PackedBFP:
         native.select_threshold(t, k, ws)
         _, codes, exps = native.quantize_threshold(t, ws, block_size, mant_bits, epsilon, want_deq=False, code_bits=code_bits, want_exp=True)
         return cls(codes, exps, t.shape, t.dtype, mant_bits, block_size, code_bits)
+
+    @classmethod
+    def from_bfp_args(cls, w, a, code_bits=None):
+        """the weight operand Q_w(w) of configuration `a` (unpacked bfp_args), packed: format 'bfp', block 64, mant_bits 1..7,
+        round-half-even; N:M pruning from the w_sparsity keys (order from `first`), unstructured pruning for first='s' (prune, then
+        quantize: one fused launch writes the codes).  Configurations that cannot be packed (unstructured pruning after quantization,
+        stochastic rounding) are refused.  code_bits: the code width, code_bits_for(mant_bits) by default."""
+        assert a['num_format'] == 'bfp' and a['sparsity_num_format'] == 'bfp' and a['block_size'] == 64 and 1 <= a['mant_bits'] <= 7, \
+            "a packed weight holds 4- or 8-bit codes: an HBFP config with block_size 64 and mant_bits <= 7 (HBFP2-HBFP8)"
+        if a['w_sparsity'] and a['sparsity_mode'] == 'unstructured' and a['first'] != 's':
+            raise ValueError("unstructured pruning AFTER quantization (first='q') is not packed")
+        if a['w_sparsity'] and a['sparsity_mode'] not in ('structured', 'unstructured'):
+            raise ValueError('Sparsity mode not implemented')
+        if a['rounding_mode'] != 'determ':
+            raise ValueError("a packed weight is quantized with round-half-even: rounding_mode must be 'determ'")
+        if a['w_sparsity'] and a['sparsity_mode'] == 'unstructured':
+            return cls.quantize_unstructured(w, a['mant_bits'], 64, a['sparsity_frac'], a['epsilon'], code_bits)
+        N, M = (a['N'], a['M']) if a['w_sparsity'] else (0, 0)                  # (structured: the other modes returned or raised above)
+        return cls.quantize(w, a['mant_bits'], 64, a['epsilon'], N, M, a['first'], code_bits)
 
     def dequantize(self, out=None):
         """== the reference's fake-quantised tensor (a -0.0 there is +0.0 here)"""
@@ -459,65 +511,55 @@ class PackedBFP:
     def nbytes(self):
         return self.codes.numel() * self.codes.element_size() + self.exps.numel()
 
-    def _tiled_ok(self):
-        N, K = self.shape
-        return N % 16 == 0 and K % 128 == 0 and K >= 256
-
     def linear_decode(self, x, x_mant_bits=7, epsilon=1e-8, x_sparsity=None, xq=None):
-        """x @ W^T for <= 16 tokens (<= 64 with the MFMA-tiled layout) straight from the packed weight (self is W [N, K],
-        4-bit codes, block 64):
+        """x @ W^T for <= 64 tokens straight from the packed weight (self is W [N, K], 4-bit codes, block 64, N % 16 == 0,
+        K % 128 == 0, K >= 256), in one launch on an MFMA-tiled copy of the weight made once (native.hbfp_linear_decode_tiled):
         the activation is quantized to HBFP(x_mant_bits + 1) block 64 and every block's dot product is an exact
-        integer sum on the int8 matrix cores (native.hbfp_linear_decode).  x_sparsity (native.ActSparsity): the activation
+        integer sum on the int8 matrix cores.  x_sparsity (native.ActSparsity): the activation
         is pruned as well (unstructured: one threshold over all of x).  xq: its operand made beforehand (native.act_codes)."""
         assert self.code_bits == 4 and self.block_size == 64 and len(self.shape) == 2
         N, K = self.shape
+        if not (N % 16 == 0 and K % 128 == 0 and K >= 256):
+            raise ValueError(f"linear_decode needs N % 16 == 0, K % 128 == 0 and K >= 256 (got N={N}, K={K})")
         if xq is None and x_sparsity is not None:
             xq = native.act_codes(x.reshape(-1, K), x_mant_bits, epsilon, x_sparsity)
-        if N % 16 == 0 and K % 128 == 0 and K >= 256:                  # MFMA-tiled copy of the weight, built once
-            if getattr(self, "_tiles", None) is None:
-                self._tiles = native.mfma_tiles(self.codes, self.exps)
-            return native.hbfp_linear_decode_tiled(x, self._tiles[0], self._tiles[1], N, self.mant_bits, x_mant_bits, epsilon, xq=xq)
-        return native.hbfp_linear_decode(x, self.codes, self.exps, self.mant_bits, x_mant_bits, epsilon, xq=xq)
+        if getattr(self, "_tiles", None) is None:
+            self._tiles = native.mfma_tiles(self.codes, self.exps)
+        return native.hbfp_linear_decode_tiled(x, self._tiles[0], self._tiles[1], N, self.mant_bits, x_mant_bits, epsilon, xq=xq)
 
-    def linear(self, x, bias=None, x_mant_bits=7, epsilon=1e-8, decode_tokens=64, x_sparsity=None):
+    def linear(self, x, bias=None, x_mant_bits=7, epsilon=1e-8, decode_tokens=DECODE_TOKENS, x_sparsity=None):
         """F.linear(Q_in(x), W_packed, bias) for any number of tokens, W = self [N, K] (the forward of a BFPLinear whose
-        weight is held packed; activations HBFP(x_mant_bits + 1), block 64, round-half-even).
-        Up to `decode_tokens` tokens: chunks of 16 through the integer block-dot-product kernel (linear_decode), which
-        never materialises the weight.  More tokens (prefill): when the activation mantissas fit 4 bits (x_mant_bits <= 4)
-        and K % 256 == 0, the block-scaled matrix instruction multiplies the two HBFP operands as they are
-        (native.hbfp_linear_mx8); otherwise the weight is decoded to its dtype once per call (bfpq_dequantize, a
-        streaming pass) and multiplied by the library GEMM.
+        weight is held packed; activations HBFP(x_mant_bits + 1), block 64, round-half-even), on the kernel linear_route picks:
+        4-bit codes up to `decode_tokens` tokens straight from the codes (linear_decode); else the block-scaled matrix instruction
+        where both operands' mantissas fit 4 bits; else the weight decoded once per call and the library GEMM.
         x_sparsity (native.ActSparsity or None): the activation is pruned as the reference's in_sparsity does (N:M per row, or
-        one unstructured threshold over ALL tokens of the call, chosen before the decode path cuts them into chunks)."""
+        one unstructured threshold over ALL tokens of the call)."""
         K = self.shape[-1]
+        T = x.numel() // K if K else 0
+        route = linear_route(T, self.shape[0], K, self.code_bits, self.mant_bits, x_mant_bits, decode_tokens, block_size=self.block_size)
+        return self._run_linear(route, x, bias, x_mant_bits, epsilon, x_sparsity)
+
+    def _run_linear(self, route, x, bias, x_mant_bits, epsilon, x_sparsity):
+        """F.linear(Q_in(x), W_packed, bias) on `route` (a linear_route name)"""
+        if route == 'int8':
+            return self.linear_i8(x, bias, x_mant_bits, epsilon, x_sparsity)
+        N, K = self.shape[0], self.shape[-1]
         lead = x.shape[:-1]
         x2 = x.reshape(-1, K)
-        T = x2.shape[0]
-        if T == 0:
-            return x.new_zeros(lead + (self.shape[0],))
-        if T <= decode_tokens and self.code_bits == 4 and self.block_size == 64 and self.shape[0] % 16 == 0 and K % 256 == 0:
-            if x_sparsity is None:
-                out = self.linear_decode(x2, x_mant_bits, epsilon) if (T <= 16 or self._tiled_ok()) else \
-                    torch.cat([self.linear_decode(x2[i:i + 16], x_mant_bits, epsilon) for i in range(0, T, 16)], 0)
-            else:
-                xc, xe = native.act_codes(x2, x_mant_bits, epsilon, x_sparsity)       # (all tokens at once: one threshold)
-                out = self.linear_decode(x2, x_mant_bits, epsilon, xq=(xc, xe)) if (T <= 16 or self._tiled_ok()) else \
-                    torch.cat([self.linear_decode(x2[i:i + 16], x_mant_bits, epsilon, xq=(xc[i:i + 16], xe[i:i + 16]))
-                               for i in range(0, T, 16)], 0)
-        elif self.code_bits in (4, 8) and native.hbfp_linear_mx8_ok(T, self.shape[0], K, self.mant_bits, x_mant_bits, self.block_size):
-            # prefill: both operands as e4m3 mantissas + E8M0 block scales on the block-scaled matrix instruction
-            # (exact block dot products, fp32 across blocks); the weight's image is made once per device
-            out = native.hbfp_linear_mx8(x2, *self._mx8_image(), x_mant_bits, epsilon, bias=bias, act=x_sparsity)
-            return out.view(lead + (self.shape[0],))
-        elif x_sparsity is not None:
-            xq = _act_fake_quant(x2, x_mant_bits, epsilon, x_sparsity)
-            out = F.linear(xq, self.dequantize().to(x.dtype))
+        if route == 'empty':
+            return x.new_zeros(lead + (N,))
+        if route == 'mx8':
+            # both operands as e4m3 mantissas + E8M0 block scales on the block-scaled matrix instruction (exact block dot products,
+            # fp32 across blocks, bias fused); the weight's image is made once per device
+            return native.hbfp_linear_mx8(x2, *self._mx8_image(), x_mant_bits, epsilon, bias=bias, act=x_sparsity).view(lead + (N,))
+        if route == 'decode4':
+            xq = None if x_sparsity is None else native.act_codes(x2, x_mant_bits, epsilon, x_sparsity)   # (all tokens: one threshold)
+            out = self.linear_decode(x2, x_mant_bits, epsilon, xq=xq)
         else:
-            xq = _quantize_nm_ref_dtype(x2, 64, x_mant_bits, epsilon, rounding_modes.DETERM)
-            out = F.linear(xq, self.dequantize().to(x.dtype))
+            out = F.linear(_act_fake_quant(x2, x_mant_bits, epsilon, x_sparsity), self.dequantize().to(x.dtype))
         if bias is not None:
             out = out + bias
-        return out.view(lead + (self.shape[0],))
+        return out.view(lead + (N,))
 
     def linear_i8(self, x, bias=None, x_mant_bits=7, epsilon=1e-8, x_sparsity=None):
         """F.linear(Q_in(x), W_packed, bias) for any number of tokens on the int8 matrix unit (native.hbfp_linear_i8): self is W [N, K]
@@ -579,13 +621,13 @@ class PackedBFP:
                    int(meta["block_size"]), int(meta["code_bits"]))
 
 
-def _act_fake_quant(x, mant_bits, epsilon, act):
-    """the reference's activation operand for an ActSparsity spec: float_to_bfp_blocked(x, in_sparsity=True, identifier='in') with
-    HBFP(mant_bits + 1), block 64, round-half-even"""
+def _act_fake_quant(x, mant_bits, epsilon, act=None):
+    """the reference's activation operand: float_to_bfp_blocked(x, identifier='in') with HBFP(mant_bits + 1), block 64,
+    round-half-even, pruned as the ActSparsity spec `act` says (None: dense)"""
+    mode, N, M, frac, first = act if act is not None else ('structured', 0, 0, 0.0, 's')
     return float_to_bfp_blocked(x, mant_bits=mant_bits, epsilon=epsilon, rounding_mode=rounding_modes.DETERM, device=str(x.device), block_size=64,
-                                num_format='bfp', weight_mant_bits=0, in_sparsity=True, w_sparsity=False, grad_sparsity=False,
-                                sparsity_frac=act.frac, N=act.N, M=act.M, sparsity_num_format='bfp', first=act.first,
-                                sparsity_mode=act.mode, identifier='in')
+                                num_format='bfp', weight_mant_bits=0, in_sparsity=act is not None, w_sparsity=False, grad_sparsity=False,
+                                sparsity_frac=frac, N=N, M=M, sparsity_num_format='bfp', first=first, sparsity_mode=mode, identifier='in')
 
 
 # ---- module / functional wrappers (reference: bfp_ops.py:151-287) -----------------------------
@@ -606,6 +648,13 @@ def _get_op_name(name, epsilon, mant_bits, rounding_mode, **kwargs):
 
 
 FUSE_OPERAND_PAIR = True           # BFPLinear / BFPConv2d forward: quantize activation and weight in one launch when possible
+
+
+def matrix_unit_value(matrix_unit):
+    """WeightCache's matrix_unit switch, checked: False, True or 'int8' (anything else raises ValueError)"""
+    if (isinstance(matrix_unit, str) or matrix_unit not in (True, False)) and matrix_unit != 'int8':
+        raise ValueError(f"matrix_unit must be False, True or 'int8' (got {matrix_unit!r})")
+    return 'int8' if matrix_unit == 'int8' else bool(matrix_unit)
 
 
 _CACHE_KEYS = ('mant_bits', 'epsilon', 'rounding_mode', 'block_size', 'num_format', 'weight_mant_bits', 'w_sparsity',
@@ -634,10 +683,7 @@ class WeightCache:
         # image is cached like the fake-quantised weight, under the same key
         # matrix_unit='int8': the same for HBFP up to 8 bits (mant_bits <= 7) on the int8 matrix instruction (native.hbfp_linear_i8); the
         # cached image is then the weight's int8 codes + exponents
-        if isinstance(matrix_unit, str) or matrix_unit not in (True, False):
-            if matrix_unit != 'int8':
-                raise ValueError(f"matrix_unit must be False, True or 'int8' (got {matrix_unit!r})")
-        self.matrix_unit = 'int8' if matrix_unit == 'int8' else bool(matrix_unit)
+        self.matrix_unit = matrix_unit_value(matrix_unit)
         self.image_key = None
         self.image = None
         self.mx_calls = 0
@@ -685,15 +731,8 @@ class WeightCache:
         tensor: HBFP quantization is not idempotent on a block whose maximum rounded down to a power of two)"""
         key = self._key(w, bfp_args)
         if self.image_key != key:
-            a = bfp_args
-            sp = a['w_sparsity'] == True  # noqa: E712
-            cb = 4 if a['mant_bits'] <= 3 else 8
-            if sp and a['sparsity_mode'] == 'unstructured':
-                pk = PackedBFP.quantize_unstructured(w.detach(), a['mant_bits'], 64, a['sparsity_frac'], a['epsilon'], cb)
-                codes, exps = pk.codes, pk.exps
-            else:
-                codes, exps = float_to_bfp_packed(w.detach(), a['mant_bits'], 64, a['epsilon'], a['N'] if sp else 0, a['M'] if sp else 0, a['first'], cb)
-            self.image = native.mx8_from_hbfp(codes, exps, w.shape[-1], a['mant_bits'], cb)
+            pk = PackedBFP.from_bfp_args(w.detach(), bfp_args)
+            self.image = native.mx8_from_hbfp(pk.codes, pk.exps, w.shape[-1], pk.mant_bits, pk.code_bits)
             self.image_key = key
         return self.image
 
@@ -701,14 +740,8 @@ class WeightCache:
         """int8 codes [N, K] + int8 exponents [N, K/64] of Q_w(w) for the int8 matrix unit (matrix_unit='int8'), kept under the same key"""
         key = self._key(w, bfp_args)
         if self.image_key != key:
-            a = bfp_args
-            sp = a['w_sparsity'] == True  # noqa: E712
-            if sp and a['sparsity_mode'] == 'unstructured':
-                pk = PackedBFP.quantize_unstructured(w.detach(), a['mant_bits'], 64, a['sparsity_frac'], a['epsilon'], 8)
-                self.image = (pk.codes.view(w.shape), pk.exps)
-            else:
-                codes, exps = float_to_bfp_packed(w.detach(), a['mant_bits'], 64, a['epsilon'], a['N'] if sp else 0, a['M'] if sp else 0, a['first'], 8)
-                self.image = (codes.view(w.shape), exps)
+            pk = PackedBFP.from_bfp_args(w.detach(), bfp_args, code_bits=8)
+            self.image = (pk.codes.view(w.shape), pk.exps)
             self.image_key = key
         return self.image
 
@@ -779,46 +812,34 @@ class _GradQuantizer(torch.autograd.Function):
         return float_to_bfp_blocked(grad_out, **ctx.bfp_args, identifier='grad'), None
 
 
-def _matrix_unit_ok(x, w, a, cache):
-    """the cached Linear forward can run on the block-scaled matrix instruction: HBFP with block 64 and <= 4 mantissa bits (exact in e4m3),
-    round-half-even, dense or pruned activations (structured with 0 < N <= M, or unstructured), dense or N:M weights, a 2-D weight
-    with K % 256 == 0, enough tokens to fill a tile row"""
-    if not _cached_route_ok(x, w, a, cache, 4):
-        return False
-    K = x.shape[-1]
-    T = x.numel() // K if K else 0
-    return T >= 32 and native.hbfp_linear_mx8_ok(T, w.shape[0], K, a['mant_bits'], a['mant_bits'], 64)
-
-
-def _int8_unit_ok(x, w, a, cache):
-    """the cached Linear forward can run on the int8 matrix instruction (matrix_unit='int8'): as _matrix_unit_ok but with 1..7 mantissa bits,
-    any number of tokens, N % 16 == 0 and K % 64 == 0"""
-    if not _cached_route_ok(x, w, a, cache, 7):
-        return False
-    K = x.shape[-1]
-    T = x.numel() // K if K else 0
-    return T >= 1 and native.hbfp_linear_i8_ok(T, w.shape[0], K, a['mant_bits'], a['mant_bits'], 64)
-
-
-def _cached_route_ok(x, w, a, cache, max_mant_bits):
-    """the configuration checks shared by the matrix-unit routes of the cached Linear (format, rounding, sparsity coverage)"""
-    if (a['num_format'] != 'bfp' or a['sparsity_num_format'] != 'bfp' or a['block_size'] != 64 or not (1 <= a['mant_bits'] <= max_mant_bits)
+def _cached_route(x, w, a, cache):
+    """linear_route of the cached Linear forward; anything but 'int8' or 'mx8' means the fake-quantize path.  matrix_unit=True: the
+    block-scaled matrix instruction on the weight's e4m3 + E8M0 image (<= 4 mantissa bits, exact in e4m3; K % 256 == 0; from
+    CACHED_MX8_MIN_TOKENS tokens, a tile row).  matrix_unit='int8': the int8 matrix instruction on its int8 codes (1..7 mantissa bits, any
+    number of tokens, N % 16 == 0, K % 64 == 0).  Both need HBFP block 64, round-half-even, dense or pruned activations (structured with
+    0 < N <= M, or unstructured), dense, N:M or prune-first unstructured weights and a 2-D weight."""
+    int8 = cache.matrix_unit == 'int8'
+    if (a['num_format'] != 'bfp' or a['sparsity_num_format'] != 'bfp' or a['block_size'] != 64 or not (1 <= a['mant_bits'] <= (7 if int8 else 4))
             or a['rounding_mode'] != rounding_modes.DETERM or w.dim() != 2 or x.device.type != 'cuda'
             or torch.compiler.is_compiling() or not cache.usable(w, a)):
-        return False
+        return 'fake'
     if a['in_sparsity'] == True:  # noqa: E712
         if a['sparsity_mode'] == 'structured':
             if not (0 < a['N'] <= a['M']):
-                return False
+                return 'fake'
         elif a['sparsity_mode'] != 'unstructured' or not (0 < a['sparsity_frac'] <= 1):
-            return False
+            return 'fake'
     if a['w_sparsity'] == True:  # noqa: E712
         if a['sparsity_mode'] == 'unstructured':
             if a['first'] != 's' or not (0 < a['sparsity_frac'] <= 1) or w.shape[-1] % 64:       # the fused prune + quantize launch writes the codes
-                return False
+                return 'fake'
         elif a['sparsity_mode'] != 'structured' or not (0 < a['N'] <= a['M']) or a['M'] not in (2, 4, 8):
-            return False
-    return True
+            return 'fake'
+    K, m = x.shape[-1], a['mant_bits']
+    T = x.numel() // K if K else 0
+    if int8:
+        return linear_route(T, w.shape[0], K, 8, m, m, decode_tokens=0, i8_max_tokens=None, mx8_min_tokens=None)
+    return linear_route(T, w.shape[0], K, code_bits_for(m), m, m, decode_tokens=0, mx8_min_tokens=CACHED_MX8_MIN_TOKENS)
 
 
 def _gen_bfp_op(op, name, bfp_args, transpose=False, cache=None):
@@ -826,18 +847,15 @@ def _gen_bfp_op(op, name, bfp_args, transpose=False, cache=None):
     (and sparsified) on the way in and the output gradient on the way back.  cache: optional WeightCache."""
     def bfp_op(x, w, *args, **kwargs):
         if not torch.is_grad_enabled():                 # inference: same values, no autograd nodes to build
-            if cache is not None and cache.matrix_unit == 'int8' and op is F.linear and _int8_unit_ok(x, w, bfp_args, cache):
-                cache.i8_calls += 1
+            route = _cached_route(x, w, bfp_args, cache) if cache is not None and cache.matrix_unit and op is F.linear else 'fake'
+            if route in ('int8', 'mx8'):
                 bias = args[0] if args else kwargs.get('bias')
-                wc, we = cache.weight_codes_i8(w, bfp_args)
-                return native.hbfp_linear_i8(x, wc, we, bfp_args['mant_bits'], bfp_args['mant_bits'], bfp_args['epsilon'], bias=bias,
-                                             act=native.ActSparsity.from_bfp_args(bfp_args))
-            if cache is not None and cache.matrix_unit is True and op is F.linear and _matrix_unit_ok(x, w, bfp_args, cache):
+                m, eps, act = bfp_args['mant_bits'], bfp_args['epsilon'], native.ActSparsity.from_bfp_args(bfp_args)
+                if route == 'int8':
+                    cache.i8_calls += 1
+                    return native.hbfp_linear_i8(x, *cache.weight_codes_i8(w, bfp_args), m, m, eps, bias=bias, act=act)
                 cache.mx_calls += 1
-                bias = args[0] if args else kwargs.get('bias')
-                w8, wsc = cache.weight_image(w, bfp_args)
-                return native.hbfp_linear_mx8(x, w8, wsc, bfp_args['mant_bits'], bfp_args['epsilon'], bias=bias,
-                                              act=native.ActSparsity.from_bfp_args(bfp_args))
+                return native.hbfp_linear_mx8(x, *cache.weight_image(w, bfp_args), m, eps, bias=bias, act=act)
             xq, wq = _quantize_operands(x, w, transpose, bfp_args, cache)
             return op(xq, wq, *args, **kwargs)
         xq, wq = _OperandQuantizer.apply(x, w, transpose, bfp_args, cache)

@@ -15,9 +15,7 @@ def patch_linear_layers(model, bfp_args, skip=("lm_head", "classifier", "score")
     qualified name ends with an entry of `skip` stay as they are (the reference leaves the LM heads alone).
     matrix_unit (False, True or 'int8'): with cache_weights, the cached Linear forward's matrix-unit route (BFPLinear.enable_weight_cache).
     Returns the list of patched module names."""
-    if isinstance(matrix_unit, str) or matrix_unit not in (True, False):
-        if matrix_unit != 'int8':
-            raise ValueError(f"matrix_unit must be False, True or 'int8' (got {matrix_unit!r})")
+    bfp_ops.matrix_unit_value(matrix_unit)                  # (a wrong value raises before any module is replaced)
     patched = []
     for parent_name, parent in list(model.named_modules()):
         for child_name, child in list(parent.named_children()):
@@ -67,18 +65,13 @@ def prime_weight_caches(model):
     return n
 
 
-# 8-bit-code modules run PackedBFP.linear_i8 up to this many tokens; above it PackedBFP.linear's routes (weight decoded once per call +
-# the library GEMM) measured faster (LLaMA-7B projections at 2048 tokens, 1.2-1.5x)
-I8_MAX_TOKENS = 512
-
-
 class PackedBFPLinear(torch.nn.Module):
     """Inference-only Linear whose weight lives in packed HBFP form -- what a BFPLinear with w_sparsity / HBFP computes in its forward,
     with the weight quantized ONCE.  HBFP4 (mant_bits <= 3): 4-bit codes + one int8 exponent per block of 64 (0.516 B per weight
     instead of 2), run by PackedBFP.linear (up to 64 tokens straight from the codes on the int8 matrix cores, more tokens on the
     block-scaled matrix instruction or the library GEMM).  HBFP5-HBFP8 (mant_bits 4..7): 8-bit codes (1.016 B per weight), run by
-    PackedBFP.linear_i8 on the int8 matrix instruction up to I8_MAX_TOKENS tokens; more than 64 tokens of HBFP5 (activation and weight
-    mantissas <= 4 bits) take PackedBFP.linear's block-scaled route, and more than I8_MAX_TOKENS tokens its other routes.
+    PackedBFP.linear_i8 on the int8 matrix instruction up to bfp_ops.I8_MAX_TOKENS tokens; more than 64 tokens of HBFP5, more tokens
+    and shapes the int8 unit does not take run PackedBFP.linear's routes (bfp_ops.linear_route picks the route of every forward).
     The codes and exponents are registered buffers (`codes`, `exps`): they follow .to() / .cuda(), appear in state_dict()
     and load back with load_state_dict(); shape / dtype / mantissa width / activation pruning travel as extra state.
     x_sparsity (native.ActSparsity or None): the activations are pruned as the reference's in_sparsity does."""
@@ -118,38 +111,22 @@ class PackedBFPLinear(torch.nn.Module):
 
     @classmethod
     def from_linear(cls, lin, bfp_args):
-        """weight -> float_to_bfp_packed with the module's config (format 'bfp', block 64, mant_bits 1..7 -- 4-bit codes up to 3, 8-bit codes
-        from 4 --, round-half-even;
-        N:M from the w_sparsity keys, order from `first`); activations use mant_bits of the same config.  Unstructured weight pruning is
-        packed for first='s' (prune, then quantize: one fused launch writes the codes).  Pruned activations (in_sparsity: N:M or
-        unstructured, either order, the same keys) are pruned in every forward, as the reference does.  Configurations this module
-        cannot reproduce (unstructured WEIGHT pruning after quantization, stochastic rounding) are refused."""
+        """weight -> PackedBFP.from_bfp_args with the module's config (format 'bfp', block 64, mant_bits 1..7 -- 4-bit codes up to 3,
+        8-bit codes from 4 --, round-half-even, N:M or prune-first unstructured weight pruning); activations use mant_bits of the same
+        config.  Pruned activations (in_sparsity: N:M or unstructured, either order, the same keys) are pruned in every forward, as the
+        reference does.  Configurations this module cannot reproduce (unstructured WEIGHT pruning after quantization, stochastic
+        rounding) are refused."""
         a = bfp_ops.unpack_bfp_args(dict(bfp_args))
-        assert a['num_format'] == 'bfp' and a['sparsity_num_format'] == 'bfp' and a['block_size'] == 64 and 1 <= a['mant_bits'] <= 7, \
-            "PackedBFPLinear holds 4- or 8-bit codes: an HBFP config with block_size 64 and mant_bits <= 7 (HBFP2-HBFP8)"
-        if a['w_sparsity'] and a['sparsity_mode'] == 'unstructured' and a['first'] != 's':
-            raise ValueError("PackedBFPLinear: unstructured pruning AFTER quantization (first='q') is not packed here")
-        if a['w_sparsity'] and a['sparsity_mode'] not in ('structured', 'unstructured'):
-            raise ValueError('Sparsity mode not implemented')
-        if a['rounding_mode'] != 'determ':
-            raise ValueError("PackedBFPLinear packs with round-half-even: rounding_mode must be 'determ'")
-        act = native.ActSparsity.from_bfp_args(a)
-        sp = a['w_sparsity'] and a['sparsity_mode'] == 'structured'
-        if a['w_sparsity'] and a['sparsity_mode'] == 'unstructured':
-            pw = bfp_ops.PackedBFP.quantize_unstructured(lin.weight.detach(), a['mant_bits'], 64, a['sparsity_frac'], a['epsilon'])
-            return cls(pw, lin.bias, a['mant_bits'], a['epsilon'], act)
-        pw = bfp_ops.PackedBFP.quantize(lin.weight.detach(), a['mant_bits'], 64, a['epsilon'], a['N'] if sp else 0, a['M'] if sp else 0, a['first'])
-        return cls(pw, lin.bias, a['mant_bits'], a['epsilon'], act)
+        pw = bfp_ops.PackedBFP.from_bfp_args(lin.weight.detach(), a)
+        return cls(pw, lin.bias, a['mant_bits'], a['epsilon'], native.ActSparsity.from_bfp_args(a))
 
     def forward(self, x):
         p = self.packed
-        if p.code_bits == 8:
-            T = x.numel() // x.shape[-1] if x.shape[-1] else 0
-            hbfp5_prefill = T > 64 and p.mant_bits <= 4 and self.x_mant_bits <= 4 and native.hbfp_linear_mx8_ok(T, p.shape[0], p.shape[1], p.mant_bits,
-                                                                                                                   self.x_mant_bits)
-            if T <= I8_MAX_TOKENS and not hbfp5_prefill:
-                return p.linear_i8(x, self.bias, self.x_mant_bits, self.epsilon, x_sparsity=self.x_sparsity)
-        return p.linear(x, self.bias, self.x_mant_bits, self.epsilon, x_sparsity=self.x_sparsity)
+        N, K = p.shape
+        T = x.numel() // K if K else 0
+        route = bfp_ops.linear_route(T, N, K, p.code_bits, p.mant_bits, self.x_mant_bits, i8_max_tokens=bfp_ops.I8_MAX_TOKENS,
+                                     block_size=p.block_size)
+        return p._run_linear(route, x, self.bias, self.x_mant_bits, self.epsilon, self.x_sparsity)
 
     def extra_repr(self):
         act = "" if self.x_sparsity is None else f", x_sparsity={tuple(self.x_sparsity)}"
@@ -162,7 +139,7 @@ def pack_linear_layers(model, bfp_args, skip=("lm_head", "classifier", "score"))
     block_size 64 and mant_bits <= 7 (+ optional N:M or unstructured pruning).  Returns the patched names and the bytes saved."""
     patched, saved = [], 0
     a = bfp_ops.unpack_bfp_args(dict(bfp_args))
-    k_mult = 256 if a['mant_bits'] <= 3 else 64             # 8-bit codes (mant_bits >= 4) run at any K % 64 == 0 (PackedBFP.linear_i8)
+    k_mult = 256 if bfp_ops.code_bits_for(a['mant_bits']) == 4 else 64     # 8-bit codes run at any K % 64 == 0 (PackedBFP.linear_i8)
     for parent_name, parent in list(model.named_modules()):
         for child_name, child in list(parent.named_children()):
             full = f"{parent_name}.{child_name}" if parent_name else child_name

@@ -245,22 +245,28 @@ def _reference(x, lin, a):
     return xv @ wv.t() + lin.bias.double(), xv.abs() @ wv.abs().t() + lin.bias.double().abs()
 
 
-MODULE_CASES = [(m, wf, af) for m in (5, 7) for wf in WEIGHT_FORMS for af in ACT_FORMS if _cfg(m, wf, af) is not None]
+MODULE_CASES = [(m, wf, af, (256, 512)) for m in (5, 7) for wf in WEIGHT_FORMS for af in ACT_FORMS if _cfg(m, wf, af) is not None]
+MODULE_CASES.append((7, 'dense', 'dense', (24, 512)))          # out_features % 16 != 0: a shape the int8 unit refuses
 
 
-@pytest.mark.parametrize("m,wform,aform", MODULE_CASES)
-def test_packed_module_matches_fake_quantised_bfplinear(m, wform, aform):
+@pytest.mark.parametrize("m,wform,aform,shape", MODULE_CASES,
+                         ids=[f"{m}-{wf}-{af}" + ("" if shape == (256, 512) else f"-{shape[0]}x{shape[1]}") for m, wf, af, shape in MODULE_CASES])
+def test_packed_module_matches_fake_quantised_bfplinear(m, wform, aform, shape):
     a = _cfg(m, wform, aform)
+    N, K = shape
     torch.manual_seed(m)
-    lin = torch.nn.Linear(512, 256).to(DEV).to(torch.bfloat16)
+    lin = torch.nn.Linear(K, N).to(DEV).to(torch.bfloat16)
+    if shape != (256, 512):
+        with torch.no_grad():        # (the fallback route adds the bias to the GEMM's rounded output: a second rounding, not in the bound)
+            lin.bias.zero_()
     mod = PackedBFPLinear.from_linear(lin, a)
     assert mod.packed.code_bits == 8 and mod.codes.dtype == torch.int8
     for T in (7, 200):
-        x = torch.randn(T, 512, device=DEV).to(torch.bfloat16)
+        x = torch.randn(T, K, device=DEV).to(torch.bfloat16)
         with torch.no_grad():
             got = mod(x)
         want, absprod = _reference(x, lin, a)
-        G.elementwise_bound(got, want, absprod, 512 // 64 + 10, torch.bfloat16)
+        G.elementwise_bound(got, want, absprod, K // 64 + 10, torch.bfloat16)
 
 
 def test_packed_module_hbfp5_prefill_keeps_the_block_scaled_route_and_state_dict():
