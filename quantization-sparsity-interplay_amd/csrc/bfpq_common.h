@@ -7,9 +7,27 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
+#include <type_traits>
 #include "bfpq.h"
 
 namespace bfpq {
+
+// host-side argument checks shared by the entry points (each entry point keeps its own order and return codes)
+inline bool dtype_ok(int dtype) { return dtype >= 0 && dtype <= 2; }
+// integer codes of code_bits hold a mantissa of mant_bits (the fp32-image codes, 32, take any)
+inline bool codes_fit(int code_bits, int mant_bits)
+{
+    return !((code_bits == 4 && mant_bits > 3) || (code_bits == 8 && mant_bits > 7) || (code_bits == 16 && mant_bits > 15));
+}
+template <class... P> bool aligned16(const P*... p) { return ((reinterpret_cast<uintptr_t>(p) | ... | 0u) & 15u) == 0; }
+
+// f(std::integral_constant<int, DT>{}) for a dtype code; anything that is not F32 or F16 is taken as BF16
+template <class F> decltype(auto) with_dtype(int dtype, F&& f)
+{
+    if (dtype == BFPQ_F32) return f(std::integral_constant<int, BFPQ_F32>{});
+    if (dtype == BFPQ_F16) return f(std::integral_constant<int, BFPQ_F16>{});
+    return f(std::integral_constant<int, BFPQ_BF16>{});
+}
 
 template <int DT> struct Traits;
 template <> struct Traits<BFPQ_F32> {
@@ -190,5 +208,33 @@ __device__ __forceinline__ int8_t sat_exp(const BlockScale& b)
     if (b.mode == 2) return (int8_t)-128;
     return (int8_t)(b.e < -127 ? -127 : (b.e > 127 ? 127 : b.e));
 }
+
+namespace {
+// split-K epilogue of the GEMMs: out[i] = the fp32 slabs summed in part order (+ bias[i % N]), rounded once to OUT_DT;
+// slab p at slabs + p * stride, its first tn entries the outputs
+template <int OUT_DT>
+__global__ void __launch_bounds__(256) k_slab_reduce(const float* __restrict__ slabs, size_t stride, const void* __restrict__ bias,
+                                                     void* __restrict__ out, int64_t TN_, int N, int parts)
+{
+    using raw_t = typename Traits<OUT_DT>::raw_t;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < TN_; i += (int64_t)gridDim.x * 256) {
+        float acc = slabs[i];
+        for (int p = 1; p < parts; p++) acc += slabs[(size_t)p * stride + i];
+        if (bias) acc += raw_to_f32<OUT_DT>((uint32_t)reinterpret_cast<const raw_t*>(bias)[i % N]);
+        reinterpret_cast<raw_t*>(out)[i] = (raw_t)f32_to_raw<OUT_DT>(acc);
+    }
+}
+
+// (a template so that only the files that call it compile the kernel)
+template <class = void>
+void launch_slab_reduce(int out_dtype, const float* slabs, size_t stride, const void* bias, void* out, int64_t tn, int64_t N, int parts,
+                        hipStream_t s)
+{
+    const dim3 grid((unsigned)((tn + 255) / 256 < 2048 ? (tn + 255) / 256 : 2048));
+    with_dtype(out_dtype, [&](auto dt) {
+        hipLaunchKernelGGL((k_slab_reduce<dt>), grid, dim3(256), 0, s, slabs, stride, bias, out, tn, (int)N, parts);
+    });
+}
+}  // namespace
 
 }  // namespace bfpq

@@ -233,18 +233,6 @@ __global__ void __launch_bounds__(RT == 1 ? 1024 : 512) k_hbfp_linear_decode_til
     }
 }
 
-template <int DT>
-__global__ void __launch_bounds__(256) k_slab_reduce(const float* __restrict__ slabs, void* __restrict__ out, int T, int N, int slices)
-{
-    using raw_t = typename Traits<DT>::raw_t;
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)T * N) return;
-    const int t = (int)(i / N), n = (int)(i - (int64_t)t * N);
-    float s = 0.f;
-    for (int sl = 0; sl < slices; sl++) s += slabs[((size_t)sl * 16 + t) * N + n];
-    reinterpret_cast<raw_t*>(out)[i] = (raw_t)f32_to_raw<DT>(s);
-}
-
 }  // namespace
 
 extern "C" {
@@ -264,7 +252,7 @@ int bfpq_hbfp_linear_decode(const void* wcodes, const int8_t* wexp, const int8_t
                             void* out, float* slabs, int64_t T, int64_t N, int64_t K, int out_dtype,
                             int w_mant_bits, int x_mant_bits, void* stream)
 {
-    if (T < 1 || T > 16 || out_dtype < 0 || out_dtype > 2) return BFPQ_E_ARG;
+    if (T < 1 || T > 16 || !dtype_ok(out_dtype)) return BFPQ_E_ARG;
     if (w_mant_bits < 1 || w_mant_bits > 3 || x_mant_bits < 1 || x_mant_bits > 7) return BFPQ_E_ARG;
     const int slices = bfpq_hbfp_linear_slices(N, K);
     if (slices < 0) return slices;
@@ -275,10 +263,9 @@ int bfpq_hbfp_linear_decode(const void* wcodes, const int8_t* wexp, const int8_t
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_hbfp_linear_decode, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s,
                        (const uint8_t*)wcodes, wexp, xcodes, xexp, slabs, (int)N, (int)K, gps, slices, w_mant_bits, x_mant_bits);
-    const dim3 rg((unsigned)((T * N + 255) / 256));
-    if (out_dtype == BFPQ_F32) hipLaunchKernelGGL((k_slab_reduce<BFPQ_F32>), rg, dim3(256), 0, s, (const float*)slabs, out, (int)T, (int)N, slices);
-    else if (out_dtype == BFPQ_F16) hipLaunchKernelGGL((k_slab_reduce<BFPQ_F16>), rg, dim3(256), 0, s, (const float*)slabs, out, (int)T, (int)N, slices);
-    else hipLaunchKernelGGL((k_slab_reduce<BFPQ_BF16>), rg, dim3(256), 0, s, (const float*)slabs, out, (int)T, (int)N, slices);
+    // slabs are [slices][16][N].  The sum starts from slab 0, not from +0: the two differ only if every slab holds -0, and
+    // k_hbfp_linear_decode starts its accumulators at +0, so no slab entry is ever -0
+    launch_slab_reduce(out_dtype, slabs, (size_t)(16 * N), nullptr, out, T * N, N, slices, s);
     return (int)hipGetLastError();
 }
 
@@ -316,7 +303,7 @@ int bfpq_hbfp_linear_decode_tiled(const void* wtiles, const void* wexpt, const i
                                   void* out, int64_t T, int64_t N, int64_t K, int out_dtype,
                                   int w_mant_bits, int x_mant_bits, void* stream)
 {
-    if (T < 1 || T > 64 || out_dtype < 0 || out_dtype > 2) return BFPQ_E_ARG;
+    if (T < 1 || T > 64 || !dtype_ok(out_dtype)) return BFPQ_E_ARG;
     if (w_mant_bits < 1 || w_mant_bits > 3 || x_mant_bits < 1 || x_mant_bits > 7) return BFPQ_E_ARG;
     if (!bfpq_hbfp_linear_tiled_ok(N, K)) return BFPQ_E_UNSUPPORTED;
     if (!wtiles || !wexpt || !xcodes || !xexp || !out) return BFPQ_E_ARG;
@@ -327,19 +314,14 @@ int bfpq_hbfp_linear_decode_tiled(const void* wtiles, const void* wexpt, const i
     const dim3 grid((unsigned)(N / 16 / rt), (unsigned)((T + 15) / 16)), wg((unsigned)(64 * slices));
     const size_t lds = (size_t)slices * rt * 256 * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
-#define BFPQ_LAUNCH_TILED(DT, RT)                                                                                                \
-    hipLaunchKernelGGL((k_hbfp_linear_decode_tiled<DT, RT>), grid, wg, lds, s, (const uint4*)wtiles, (const uint2*)wexpt, xcodes, \
-                       xexp, out, (int)T, (int)N, (int)K, pps, w_mant_bits, x_mant_bits)
-#define BFPQ_LAUNCH_TILED_DT(RT)                                                                                                 \
-    do {                                                                                                                          \
-        if (out_dtype == BFPQ_F32) BFPQ_LAUNCH_TILED(BFPQ_F32, RT);                                                               \
-        else if (out_dtype == BFPQ_F16) BFPQ_LAUNCH_TILED(BFPQ_F16, RT);                                                          \
-        else BFPQ_LAUNCH_TILED(BFPQ_BF16, RT);                                                                                    \
-    } while (0)
-    if (rt == 4) BFPQ_LAUNCH_TILED_DT(4);
-    else if (rt == 2) BFPQ_LAUNCH_TILED_DT(2);
-    else BFPQ_LAUNCH_TILED_DT(1);
-#undef BFPQ_LAUNCH_TILED_DT
+#define BFPQ_LAUNCH_TILED(RT)                                                                                                     \
+    with_dtype(out_dtype, [&](auto dt) {                                                                                           \
+        hipLaunchKernelGGL((k_hbfp_linear_decode_tiled<dt, RT>), grid, wg, lds, s, (const uint4*)wtiles, (const uint2*)wexpt, xcodes, \
+                           xexp, out, (int)T, (int)N, (int)K, pps, w_mant_bits, x_mant_bits);                                       \
+    })
+    if (rt == 4) BFPQ_LAUNCH_TILED(4);
+    else if (rt == 2) BFPQ_LAUNCH_TILED(2);
+    else BFPQ_LAUNCH_TILED(1);
 #undef BFPQ_LAUNCH_TILED
     return (int)hipGetLastError();
 }

@@ -25,7 +25,7 @@
 //                 stages of two blocks each (double buffered: the next stage's DMA is in flight during the current stage's matrix
 //                 work), LDS rows of 128 bytes with the 16-byte slot XOR-swizzled by ((row >> 1) & 7).  K % 256 == 0 (the block
 //                 exponents are read one dword = 4 blocks per trip).  SPLIT: part p of K goes to fp32 slab p (plain stores) and
-//                 k_i8_slab_reduce adds the slabs in part order.
+//                 k_slab_reduce (bfpq_common.h) adds the slabs in part order.
 //   k_i8_decode   few tokens: a wave owns 16 output features x up to 16 tokens x a slice of K (any K % 64 == 0), slabs reduced as above.
 //   k_codes4_to_i8  4-bit two's-complement nibbles (low first) -> int8 codes.
 #include <hip/hip_runtime.h>
@@ -273,20 +273,6 @@ __global__ void __launch_bounds__(256) k_i8_decode(const int8_t* __restrict__ wc
     *reinterpret_cast<float4*>(slabs + ((size_t)slice * Tpad + blockIdx.y * 16 + r) * N + n0 + 4 * q) = make_float4(acc[0], acc[1], acc[2], acc[3]);
 }
 
-// out[t][n] = sum over parts in part order (+ bias), rounded once; slab p at slabs + p * stride, rows of N
-template <int OUT_DT>
-__global__ void __launch_bounds__(256) k_i8_slab_reduce(const float* __restrict__ slabs, size_t stride, const void* __restrict__ bias,
-                                                        void* __restrict__ out, int64_t TN_, int N, int parts)
-{
-    using raw_t = typename Traits<OUT_DT>::raw_t;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < TN_; i += (int64_t)gridDim.x * 256) {
-        float acc = slabs[i];
-        for (int p = 1; p < parts; p++) acc += slabs[(size_t)p * stride + i];
-        if (bias) acc += raw_to_f32<OUT_DT>((uint32_t)reinterpret_cast<const raw_t*>(bias)[i % N]);
-        reinterpret_cast<raw_t*>(out)[i] = (raw_t)f32_to_raw<OUT_DT>(acc);
-    }
-}
-
 // one thread = 8 codes (4 bytes of nibbles -> 8 bytes)
 __global__ void __launch_bounds__(256) k_codes4_to_i8(const uint32_t* __restrict__ in, uint2* __restrict__ out, int64_t n_items)
 {
@@ -301,22 +287,6 @@ __global__ void __launch_bounds__(256) k_codes4_to_i8(const uint32_t* __restrict
         }
         out[i] = make_uint2(lo, hi);
     }
-}
-
-template <int OUT_DT>
-void launch_reduce(const float* slabs, size_t stride, const void* bias, void* out, int64_t T, int64_t N, int parts, hipStream_t s)
-{
-    const int64_t tn = T * N;
-    int64_t g = (tn + 255) / 256;
-    if (g > 2048) g = 2048;
-    hipLaunchKernelGGL((k_i8_slab_reduce<OUT_DT>), dim3((unsigned)g), dim3(256), 0, s, slabs, stride, bias, out, tn, (int)N, parts);
-}
-
-void reduce_dt(int out_dtype, const float* slabs, size_t stride, const void* bias, void* out, int64_t T, int64_t N, int parts, hipStream_t s)
-{
-    if (out_dtype == BFPQ_F32) launch_reduce<BFPQ_F32>(slabs, stride, bias, out, T, N, parts, s);
-    else if (out_dtype == BFPQ_F16) launch_reduce<BFPQ_F16>(slabs, stride, bias, out, T, N, parts, s);
-    else launch_reduce<BFPQ_BF16>(slabs, stride, bias, out, T, N, parts, s);
 }
 
 // tile variants (bfpq_tune key BFPQ_TUNE_I8_VARIANT): 0 = 128 features x 128 tokens, 1 = 128 x 64, 2 = 64 x 64; all 4 waves
@@ -345,9 +315,7 @@ void launch_var(int out_dtype, bool split, dim3 grid, hipStream_t s, const int8_
                 const void* bias, void* out, int T, int N, int K, int tiles_t, int tiles, int tpp, int xm, int wm)
 {
     if (split) launch_tile<V, BFPQ_F32, true>(grid, s, xc, xe, wc, we, nullptr, out, T, N, K, tiles_t, tiles, tpp, xm, wm);
-    else if (out_dtype == BFPQ_F32) launch_tile<V, BFPQ_F32, false>(grid, s, xc, xe, wc, we, bias, out, T, N, K, tiles_t, tiles, tpp, xm, wm);
-    else if (out_dtype == BFPQ_F16) launch_tile<V, BFPQ_F16, false>(grid, s, xc, xe, wc, we, bias, out, T, N, K, tiles_t, tiles, tpp, xm, wm);
-    else launch_tile<V, BFPQ_BF16, false>(grid, s, xc, xe, wc, we, bias, out, T, N, K, tiles_t, tiles, tpp, xm, wm);
+    else with_dtype(out_dtype, [&](auto dt) { launch_tile<V, dt, false>(grid, s, xc, xe, wc, we, bias, out, T, N, K, tiles_t, tiles, tpp, xm, wm); });
 }
 
 }  // namespace
@@ -363,7 +331,7 @@ static int i8_variant(int64_t T)
 
 static bool i8_args_ok(int out_dtype, int w_mant_bits, int x_mant_bits)
 {
-    return out_dtype >= 0 && out_dtype <= 2 && w_mant_bits >= 1 && w_mant_bits <= 7 && x_mant_bits >= 1 && x_mant_bits <= 7;
+    return dtype_ok(out_dtype) && w_mant_bits >= 1 && w_mant_bits <= 7 && x_mant_bits >= 1 && x_mant_bits <= 7;
 }
 
 extern "C" {
@@ -403,7 +371,7 @@ static int i8_launch(const int8_t* xc, const int8_t* xe, const int8_t* wc, const
     if (v == 0) launch_var<0>(out_dtype, split, grid, s, xc, xe, wc, we, bias, dst, (int)T, (int)N, (int)K, tiles_t, tiles, tpp, xm, wm);
     else if (v == 1) launch_var<1>(out_dtype, split, grid, s, xc, xe, wc, we, bias, dst, (int)T, (int)N, (int)K, tiles_t, tiles, tpp, xm, wm);
     else launch_var<2>(out_dtype, split, grid, s, xc, xe, wc, we, bias, dst, (int)T, (int)N, (int)K, tiles_t, tiles, tpp, xm, wm);
-    if (split) reduce_dt(out_dtype, slabs, (size_t)(T * N), bias, out, T, N, parts, s);
+    if (split) launch_slab_reduce(out_dtype, slabs, (size_t)(T * N), bias, out, T * N, N, parts, s);
     return (int)hipGetLastError();
 }
 
@@ -411,7 +379,7 @@ static bool i8_ptrs_ok(const void* xc, const void* xe, const void* wc, const voi
 {
     if (!xc || !xe || !wc || !we || !out) return false;
     // LDS-DMA sources: 16-byte aligned codes; exponent dwords: 4-byte aligned; vector stores of 4 outputs: 8-byte aligned
-    return !((reinterpret_cast<uintptr_t>(xc) | reinterpret_cast<uintptr_t>(wc) | reinterpret_cast<uintptr_t>(out)) & 15u) &&
+    return aligned16(xc, wc, out) &&
            !((reinterpret_cast<uintptr_t>(xe) | reinterpret_cast<uintptr_t>(we)) & 3u);
 }
 
@@ -432,7 +400,7 @@ int bfpq_hbfp_linear_i8_splitk(const void* xcodes, const int8_t* xexp, const voi
     if (!i8_args_ok(out_dtype, w_mant_bits, x_mant_bits) || T < 0 || N < 0 || parts < 1 || parts > 64) return BFPQ_E_ARG;
     if (T == 0 || N == 0) return 0;
     if (!bfpq_hbfp_linear_i8_ok(T, N, K)) return BFPQ_E_UNSUPPORTED;
-    if (!i8_ptrs_ok(xcodes, xexp, wcodes, wexp, out) || !slabs || (reinterpret_cast<uintptr_t>(slabs) & 15u)) return BFPQ_E_ARG;
+    if (!i8_ptrs_ok(xcodes, xexp, wcodes, wexp, out) || !slabs || !aligned16(slabs)) return BFPQ_E_ARG;
     return i8_launch((const int8_t*)xcodes, xexp, (const int8_t*)wcodes, wexp, bias, out, slabs, parts, T, N, K, out_dtype, w_mant_bits, x_mant_bits,
                      (hipStream_t)stream);
 }
@@ -460,7 +428,7 @@ int bfpq_hbfp_linear_decode8(const void* xcodes, const int8_t* xexp, const void*
     if (!i8_args_ok(out_dtype, w_mant_bits, x_mant_bits) || T < 1 || N < 1) return BFPQ_E_ARG;
     if (bfpq_hbfp_linear_decode8_ws(T, N, K) < 0) return BFPQ_E_UNSUPPORTED;
     if (!xcodes || !xexp || !wcodes || !wexp || !out || !slabs) return BFPQ_E_ARG;
-    if ((reinterpret_cast<uintptr_t>(xcodes) | reinterpret_cast<uintptr_t>(wcodes) | reinterpret_cast<uintptr_t>(slabs)) & 15u) return BFPQ_E_ARG;
+    if (!aligned16(xcodes, wcodes, slabs)) return BFPQ_E_ARG;
     const int slices = decode8_slices(T, N, K);
     const int64_t nb = K / 64;
     const int bps = (int)((nb + slices - 1) / slices);
@@ -469,7 +437,7 @@ int bfpq_hbfp_linear_decode8(const void* xcodes, const int8_t* xexp, const void*
     hipLaunchKernelGGL(k_i8_decode, dim3((unsigned)((waves + 3) / 4), (unsigned)groups), dim3(256), 0, s, (const int8_t*)wcodes, wexp,
                        (const int8_t*)xcodes, xexp, slabs, (int)T, (int)N, (int)K, bps, slices, w_mant_bits, x_mant_bits);
     // slabs are [slices][Tpad][N]: the first T rows of each slab are the outputs' partial sums
-    reduce_dt(out_dtype, slabs, (size_t)(groups * 16 * N), bias, out, T, N, slices, s);
+    launch_slab_reduce(out_dtype, slabs, (size_t)(groups * 16 * N), bias, out, T * N, N, slices, s);
     return (int)hipGetLastError();
 }
 

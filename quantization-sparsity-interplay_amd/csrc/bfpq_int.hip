@@ -547,7 +547,7 @@ template <int DT>
 int run_int(const void* in, float* out, int64_t outer, int64_t C, int64_t inner, float maxq, float zero, uint32_t* ws, hipStream_t s)
 {
     if (outer == 1 && inner % Traits<DT>::VEC == 0 && inner / Traits<DT>::VEC <= 8 * kT && inner / Traits<DT>::VEC >= kT / 2 &&
-        ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0) {
+        aligned16(in, out)) {
         const int64_t ipr = inner / Traits<DT>::VEC;
         const dim3 grid((unsigned)(C > 16384 ? 16384 : C));
         if (ipr <= 2 * kT) hipLaunchKernelGGL((k_int_rows_reg<DT, 2>), grid, dim3(kT), 0, s, in, out, C, inner, maxq, zero);
@@ -556,8 +556,7 @@ int run_int(const void* in, float* out, int64_t outer, int64_t C, int64_t inner,
         else hipLaunchKernelGGL((k_int_rows_reg<DT, 8>), grid, dim3(kT), 0, s, in, out, C, inner, maxq, zero);
         return (int)hipGetLastError();
     }
-    if (outer == 1 && inner % Traits<DT>::VEC == 0 &&
-        ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0) {
+    if (outer == 1 && inner % Traits<DT>::VEC == 0 && aligned16(in, out)) {
         if (inner <= 16384) {
             int64_t g = (C + 3) / 4;
             hipLaunchKernelGGL((k_int_rows_vec<DT, 64>), dim3((unsigned)(g > 8192 ? 8192 : g)), dim3(kT), 0, s, in, out, C, inner, maxq, zero);
@@ -581,7 +580,7 @@ int run_int(const void* in, float* out, int64_t outer, int64_t C, int64_t inner,
     // the fill launch was built and measured: no faster on large tensors, 14.6 against 10.8 us on [1576,1024] f32: a thousand
     // tickets on one address serialise at ~9 ns each, and the fill launch hides behind its predecessor's write-back.)
     hipLaunchKernelGGL(k_int_fill, dim3((unsigned)((2 * C + 4 * kT - 1) / (4 * kT) > 64 ? 64 : (2 * C + 4 * kT - 1) / (4 * kT))), dim3(kT), 0, s, ws, 2 * C);   // (hipMemsetAsync: a 4.9 us node)
-    if (inner == 1 && C % Traits<DT>::VEC == 0 && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0) {
+    if (inner == 1 && C % Traits<DT>::VEC == 0 && aligned16(in, out)) {
         const int64_t ipr = C / Traits<DT>::VEC;
         const int64_t gxw = (ipr + 63) / 64;
         {
@@ -601,7 +600,7 @@ int run_int(const void* in, float* out, int64_t outer, int64_t C, int64_t inner,
         int64_t a = upr, b = kT;
         while (b) { const int64_t t = a % b; a = b; b = t; }
         const int64_t m = upr / a;                                     // its grid: a multiple of upr / gcd(upr, 256)
-        if (m <= 2048 && (reinterpret_cast<uintptr_t>(ws) & 15u) == 0) {
+        if (m <= 2048 && aligned16(ws)) {
             const int64_t n_units = outer * upr;
             // workgroups (tools_dev/ab_int.py): a column count that divides the grid stride as it stands ran fastest with two per CU ([4096,4096]
             // bf16: 29.4 us at 512, 31-32 at 768 / 1024); the others with many ([2048,11008]: 42.8 at 516, 38.2 at 2021; [2048,13824]: 51.2 / 45.8)
@@ -722,7 +721,7 @@ extern "C" {
 int bfpq_dequantize(const void* codes, const int8_t* exps, void* out, int64_t rows, int64_t cols, int dtype,
                     int block_size, int mant_bits, int code_bits, void* stream)
 {
-    if (rows < 0 || cols < 0 || dtype < 0 || dtype > 2 || block_size <= 0 || mant_bits < 0 || mant_bits > 15) return BFPQ_E_ARG;
+    if (rows < 0 || cols < 0 || !dtype_ok(dtype) || block_size <= 0 || mant_bits < 0 || mant_bits > 15) return BFPQ_E_ARG;
     if (!(code_bits == 4 || code_bits == 8 || code_bits == 16)) return BFPQ_E_ARG;
     if (rows * cols == 0) return 0;
     if (!codes || !exps || !out) return BFPQ_E_ARG;
@@ -735,18 +734,18 @@ int bfpq_dequantize(const void* codes, const int8_t* exps, void* out, int64_t ro
         int64_t g4 = (n_items + kT - 1) / kT;
         const dim3 grid4((unsigned)(g4 > 2048 ? 2048 : g4));
         hipStream_t s4 = (hipStream_t)stream;
-        if (dtype == BFPQ_F32) hipLaunchKernelGGL((k_dequant4_vec<BFPQ_F32>), grid4, dim3(kT), 0, s4, (const uint32_t*)codes, exps, out, n_items, ipb4, ipb4_shift, mant_bits);
-        else if (dtype == BFPQ_F16) hipLaunchKernelGGL((k_dequant4_vec<BFPQ_F16>), grid4, dim3(kT), 0, s4, (const uint32_t*)codes, exps, out, n_items, ipb4, ipb4_shift, mant_bits);
-        else hipLaunchKernelGGL((k_dequant4_vec<BFPQ_BF16>), grid4, dim3(kT), 0, s4, (const uint32_t*)codes, exps, out, n_items, ipb4, ipb4_shift, mant_bits);
+        with_dtype(dtype, [&](auto dt) {
+            hipLaunchKernelGGL((k_dequant4_vec<dt>), grid4, dim3(kT), 0, s4, (const uint32_t*)codes, exps, out, n_items, ipb4, ipb4_shift, mant_bits);
+        });
         return (int)hipGetLastError();
     }
     const int vec = dtype == BFPQ_F32 ? 4 : 8;
     int64_t g = (rows * ((cols + vec - 1) / vec) + kT - 1) / kT;
     const dim3 grid((unsigned)(g > 2048 ? 2048 : g));
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == BFPQ_F32) hipLaunchKernelGGL((k_dequant<BFPQ_F32>), grid, dim3(kT), 0, s, codes, exps, out, rows, cols, block_size, mant_bits, code_bits);
-    else if (dtype == BFPQ_F16) hipLaunchKernelGGL((k_dequant<BFPQ_F16>), grid, dim3(kT), 0, s, codes, exps, out, rows, cols, block_size, mant_bits, code_bits);
-    else hipLaunchKernelGGL((k_dequant<BFPQ_BF16>), grid, dim3(kT), 0, s, codes, exps, out, rows, cols, block_size, mant_bits, code_bits);
+    with_dtype(dtype, [&](auto dt) {
+        hipLaunchKernelGGL((k_dequant<dt>), grid, dim3(kT), 0, s, codes, exps, out, rows, cols, block_size, mant_bits, code_bits);
+    });
     return (int)hipGetLastError();
 }
 
@@ -779,15 +778,13 @@ int64_t bfpq_int_workspace_elems(int64_t C) { return C < 0 ? BFPQ_E_ARG : 2 * C;
 int bfpq_int_quantize(const void* in, float* out, int64_t outer, int64_t C, int64_t inner, int dtype, int bits,
                       uint32_t* ws, void* stream)
 {
-    if (outer < 0 || C < 0 || inner < 0 || dtype < 0 || dtype > 2 || bits < 0 || bits > 30) return BFPQ_E_ARG;
+    if (outer < 0 || C < 0 || inner < 0 || !dtype_ok(dtype) || bits < 0 || bits > 30) return BFPQ_E_ARG;
     if (outer * C * inner == 0) return 0;
     if (!in || !out) return BFPQ_E_ARG;
     const float maxq = (float)((1u << bits) - 1u);
     const float zero = (maxq + 1.0f) / 2.0f;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == BFPQ_F32) return run_int<BFPQ_F32>(in, out, outer, C, inner, maxq, zero, ws, s);
-    if (dtype == BFPQ_F16) return run_int<BFPQ_F16>(in, out, outer, C, inner, maxq, zero, ws, s);
-    return run_int<BFPQ_BF16>(in, out, outer, C, inner, maxq, zero, ws, s);
+    return with_dtype(dtype, [&](auto dt) { return run_int<dt>(in, out, outer, C, inner, maxq, zero, ws, s); });
 }
 
 }  // extern "C"

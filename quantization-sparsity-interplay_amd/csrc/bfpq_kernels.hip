@@ -451,18 +451,33 @@ int launch_nm_rows(const void* in, void* out, void* codes, int code_bits, int64_
     int64_t g = (total + threads - 1) / threads;
     const int grid = (int)(g > 4096 ? 4096 : g);
     const size_t lds = (size_t)M * threads * sizeof(uint64_t);
-    if (lds > 48 * 1024) {
-        (void)hipFuncSetAttribute((const void*)k_nm_rows<BFPQ_F32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)k_nm_rows<BFPQ_F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)k_nm_rows<BFPQ_BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
-    if (dtype == BFPQ_F32) hipLaunchKernelGGL((k_nm_rows<BFPQ_F32>), dim3(grid), dim3(threads), lds, s, in, out, codes, code_bits, rows, cols, N, M, lut8);
-    else if (dtype == BFPQ_F16) hipLaunchKernelGGL((k_nm_rows<BFPQ_F16>), dim3(grid), dim3(threads), lds, s, in, out, codes, code_bits, rows, cols, N, M, lut8);
-    else hipLaunchKernelGGL((k_nm_rows<BFPQ_BF16>), dim3(grid), dim3(threads), lds, s, in, out, codes, code_bits, rows, cols, N, M, lut8);
+    with_dtype(dtype, [&](auto dt) {
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k_nm_rows<dt>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL((k_nm_rows<dt>), dim3(grid), dim3(threads), lds, s, in, out, codes, code_bits, rows, cols, N, M, lut8);
+    });
     return (int)hipGetLastError();
 }
 
 void set_hot16(FusedArgs& a, int dtype, int mant_bits, float eps_dt);
+
+// FusedArgs of one quantizer configuration (eps_dt: epsilon already rounded to the dtype), every I/O field empty
+FusedArgs fused_args(int dtype, int block_size, int mant_bits, float eps_dt, const uint8_t* exp_win)
+{
+    FusedArgs a{};
+    a.exp_win = exp_win; a.eps_dt = eps_dt; a.mant_bits = mant_bits;
+    a.lpb = block_size ? block_size / dtype_vec(dtype) : 0;
+    a.force_slow = mant_bits > (dtype == BFPQ_F32 ? 24 : (dtype == BFPQ_F16 ? 11 : 8));    // wider than the dtype significand
+    set_hot16(a, dtype, mant_bits, eps_dt);                                               // (reads force_slow)
+    return a;
+}
+
+// the e4m3 image quantizers (bfpq_quantize_mx8*): blocks of 64, 8-bit codes, one E8M0 scale byte per block
+FusedArgs mx8_args(const void* in, void* out8, void* out_scale, int64_t n_items, int dtype, int mant_bits, double epsilon, const uint8_t* exp_win)
+{
+    FusedArgs a = fused_args(dtype, 64, mant_bits, h_round((float)epsilon, dtype), exp_win);
+    a.in = in; a.out_codes = out8; a.out_exp = reinterpret_cast<int8_t*>(out_scale); a.n_items = n_items; a.code_bits = 8;
+    return a;
+}
 
 int launch_quant_rows(const void* in, void* out_deq, void* out_codes, int8_t* out_exp, int64_t rows, int64_t cols, int dtype,
                       int block, int mant_bits, float eps_dt, int code_bits, uint64_t seed, const uint8_t* exp_win, hipStream_t s)
@@ -470,37 +485,32 @@ int launch_quant_rows(const void* in, void* out_deq, void* out_codes, int8_t* ou
     const int64_t total = rows * ((cols + block - 1) / block);
     if (total == 0) return 0;
     const int vec = dtype_vec(dtype);
-    const bool aligned = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out_deq) | reinterpret_cast<uintptr_t>(out_codes)) & 15u) == 0;
+    const bool aligned = aligned16(in, out_deq, out_codes);
     if (aligned && out_deq && !out_codes && !out_exp && seed == 0 && cols % vec == 0 && block % vec == 0 && is_pow2(block / vec) && block / vec <= 64) {
-        FusedArgs a;
-        a.in = in; a.out_deq = out_deq; a.out_codes = nullptr; a.out_exp = nullptr; a.n_items = rows * cols / vec;
-        a.exp_win = exp_win; a.nm_lut = nullptr; a.seed = 0; a.eps_dt = eps_dt; a.lpb = block / vec;
-        a.mant_bits = mant_bits; a.N = 0; a.code_bits = 0;
-        a.force_slow = mant_bits > (dtype == BFPQ_F32 ? 24 : (dtype == BFPQ_F16 ? 11 : 8));
-        set_hot16(a, dtype, mant_bits, eps_dt);
-        a.selws = nullptr;
+        FusedArgs a = fused_args(dtype, block, mant_bits, eps_dt, exp_win);
+        a.in = in; a.out_deq = out_deq; a.n_items = rows * cols / vec;
         const int64_t ipr = cols / vec;
         const int grid = (int)(rows < 2048 ? rows : 2048);
-        if (dtype == BFPQ_F32) hipLaunchKernelGGL((k_quant_rows_tiled<BFPQ_F32>), dim3(grid), dim3(kThreads), 0, s, a, rows, ipr);
-        else if (dtype == BFPQ_F16) hipLaunchKernelGGL((k_quant_rows_tiled<BFPQ_F16>), dim3(grid), dim3(kThreads), 0, s, a, rows, ipr);
-        else hipLaunchKernelGGL((k_quant_rows_tiled<BFPQ_BF16>), dim3(grid), dim3(kThreads), 0, s, a, rows, ipr);
+        with_dtype(dtype, [&](auto dt) { hipLaunchKernelGGL((k_quant_rows_tiled<dt>), dim3(grid), dim3(kThreads), 0, s, a, rows, ipr); });
         return (int)hipGetLastError();
     }
     if (aligned && cols % vec == 0 && block % vec == 0 && block / vec <= 64 && (code_bits != 4 || cols % 2 == 0)) {
         int GP = 1;
         while (GP < block / vec) GP <<= 1;
         const int grid = grid_for(total * GP);
-        if (dtype == BFPQ_F32) hipLaunchKernelGGL((k_quant_rows_vec<BFPQ_F32>), dim3(grid), dim3(kThreads), 0, s, in, out_deq, out_codes, out_exp, rows, cols, block, GP, mant_bits, eps_dt, code_bits, seed, exp_win);
-        else if (dtype == BFPQ_F16) hipLaunchKernelGGL((k_quant_rows_vec<BFPQ_F16>), dim3(grid), dim3(kThreads), 0, s, in, out_deq, out_codes, out_exp, rows, cols, block, GP, mant_bits, eps_dt, code_bits, seed, exp_win);
-        else hipLaunchKernelGGL((k_quant_rows_vec<BFPQ_BF16>), dim3(grid), dim3(kThreads), 0, s, in, out_deq, out_codes, out_exp, rows, cols, block, GP, mant_bits, eps_dt, code_bits, seed, exp_win);
+        with_dtype(dtype, [&](auto dt) {
+            hipLaunchKernelGGL((k_quant_rows_vec<dt>), dim3(grid), dim3(kThreads), 0, s, in, out_deq, out_codes, out_exp, rows, cols, block, GP, mant_bits,
+                               eps_dt, code_bits, seed, exp_win);
+        });
         return (int)hipGetLastError();
     }
     int G = 1;
     while (G < 64 && 2 * G < block) G <<= 1;       // two elements per lane per step
     const int grid = grid_for(total * G);
-    if (dtype == BFPQ_F32) hipLaunchKernelGGL((k_quant_rows<BFPQ_F32>), dim3(grid), dim3(kThreads), 0, s, in, out_deq, out_codes, out_exp, rows, cols, block, G, mant_bits, eps_dt, code_bits, seed, exp_win);
-    else if (dtype == BFPQ_F16) hipLaunchKernelGGL((k_quant_rows<BFPQ_F16>), dim3(grid), dim3(kThreads), 0, s, in, out_deq, out_codes, out_exp, rows, cols, block, G, mant_bits, eps_dt, code_bits, seed, exp_win);
-    else hipLaunchKernelGGL((k_quant_rows<BFPQ_BF16>), dim3(grid), dim3(kThreads), 0, s, in, out_deq, out_codes, out_exp, rows, cols, block, G, mant_bits, eps_dt, code_bits, seed, exp_win);
+    with_dtype(dtype, [&](auto dt) {
+        hipLaunchKernelGGL((k_quant_rows<dt>), dim3(grid), dim3(kThreads), 0, s, in, out_deq, out_codes, out_exp, rows, cols, block, G, mant_bits, eps_dt,
+                           code_bits, seed, exp_win);
+    });
     return (int)hipGetLastError();
 }
 
@@ -571,7 +581,7 @@ const char* bfpq_error_string(int code)
 
 int bfpq_exp_window_host(int dtype, uint8_t* table)
 {
-    if (!table || dtype < 0 || dtype > 2) return BFPQ_E_ARG;
+    if (!table || !dtype_ok(dtype)) return BFPQ_E_ARG;
     const int mbits = dtype == BFPQ_F32 ? 23 : (dtype == BFPQ_F16 ? 10 : 7);
     for (int idx = 0; idx < BFPQ_EXP_WIN_ENTRIES; idx++) {
         const int k = idx - 160;
@@ -641,7 +651,7 @@ int bfpq_nm8_lut_host(int N, uint8_t* lut)
 
 int bfpq_is_fused(int64_t rows, int64_t cols, int dtype, int block_size, int N, int M)
 {
-    if (dtype < 0 || dtype > 2) return 0;
+    if (!dtype_ok(dtype)) return 0;
     return fused_shape_ok(rows, cols, dtype, block_size, N, M) ? 1 : 0;
 }
 
@@ -651,50 +661,35 @@ int bfpq_quantize_nm(const void* in, void* out_deq, void* out_codes, int8_t* out
                      const uint8_t* exp_win, const uint8_t* nm4_lut, void* scratch, void* stream)
 {
     hipStream_t s = (hipStream_t)stream;
-    if (dtype < 0 || dtype > 2 || rows < 0 || cols < 0 || block_size < 0) return BFPQ_E_ARG;
+    if (!dtype_ok(dtype) || rows < 0 || cols < 0 || block_size < 0) return BFPQ_E_ARG;
     if (M < 0 || N < 0 || (M > 0 && !(N > 0 && N <= M)) || M > 64) return M > 64 ? BFPQ_E_UNSUPPORTED : BFPQ_E_ARG;
     if (rows * cols == 0) return 0;
     if (!in || (!out_deq && !out_codes && !out_exp)) return BFPQ_E_ARG;
     if (block_size > 0 && (mant_bits < 0 || mant_bits > 23 || !exp_win)) return BFPQ_E_ARG;
     if (out_codes && !(code_bits == 4 || code_bits == 8 || code_bits == 16 || code_bits == 32)) return BFPQ_E_ARG;
     if (out_codes && block_size == 0) return BFPQ_E_ARG;
-    if (out_codes && ((code_bits == 4 && mant_bits > 3) || (code_bits == 8 && mant_bits > 7) || (code_bits == 16 && mant_bits > 15))) return BFPQ_E_ARG;
+    if (out_codes && !codes_fit(code_bits, mant_bits)) return BFPQ_E_ARG;
     if (block_size == 0 && M == 0) return BFPQ_E_ARG;                   // identity: the caller returns its input
     const float eps_dt = h_round((float)epsilon, dtype);
-    const bool aligned = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out_deq) |
-                           reinterpret_cast<uintptr_t>(out_codes)) & 15u) == 0;
-
-    if (aligned && fused_shape_ok(rows, cols, dtype, block_size, N, M) && (M != 4 || nm4_lut)) {
-        FusedArgs a;
-        a.in = in; a.out_deq = out_deq; a.out_codes = out_codes; a.out_exp = out_exp;
+    // the fused kernel's arguments for one input: this configuration, this call's outputs, an N:M stage (n = 0: none)
+    auto fused = [&](const void* src, void* deq, int n, const uint8_t* lut) {
+        FusedArgs a = fused_args(dtype, block_size, mant_bits, eps_dt, exp_win);
+        a.in = src; a.out_deq = deq; a.out_codes = out_codes; a.out_exp = out_exp;
         a.n_items = rows * cols / dtype_vec(dtype);
-        a.exp_win = exp_win; a.nm_lut = nm4_lut; a.seed = stoch_seed; a.eps_dt = eps_dt;
-        a.lpb = block_size ? block_size / dtype_vec(dtype) : 0;
-        a.mant_bits = mant_bits; a.N = N; a.code_bits = code_bits;
-        a.force_slow = mant_bits > (dtype == BFPQ_F32 ? 24 : (dtype == BFPQ_F16 ? 11 : 8));
-        set_hot16(a, dtype, mant_bits, eps_dt);
-        a.selws = nullptr;
-        return fused_launch(dtype, a, M, sparsify_first != 0, s);
-    }
+        a.seed = stoch_seed; a.N = n; a.nm_lut = lut; a.code_bits = code_bits;
+        return a;
+    };
+
+    if (aligned16(in, out_deq, out_codes) && fused_shape_ok(rows, cols, dtype, block_size, N, M) && (M != 4 || nm4_lut))
+        return fused_launch(dtype, fused(in, out_deq, N, nm4_lut), M, sparsify_first != 0, s);
 
     if (out_codes && code_bits == 32) return BFPQ_E_UNSUPPORTED;       // fp32 image: fused kernel only
     // general path: separate launches.  The quantize stage still takes the flat fused kernel when the shape
     // allows it (e.g. M = 8 on a regular weight: only the N:M replay needs the general kernel).
     if (out_codes && code_bits == 4 && ((block_size & 1) || (M & 1))) return BFPQ_E_UNSUPPORTED;
     auto quantize_stage = [&](const void* src, void* deq) -> int {
-        const bool al = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(deq) | reinterpret_cast<uintptr_t>(out_codes)) & 15u) == 0;
-        if (al && fused_shape_ok(rows, cols, dtype, block_size, 0, 0)) {
-            FusedArgs a;
-            a.in = src; a.out_deq = deq; a.out_codes = out_codes; a.out_exp = out_exp;
-            a.n_items = rows * cols / dtype_vec(dtype);
-            a.exp_win = exp_win; a.nm_lut = nullptr; a.seed = stoch_seed; a.eps_dt = eps_dt;
-            a.lpb = block_size / dtype_vec(dtype);
-            a.mant_bits = mant_bits; a.N = 0; a.code_bits = code_bits;
-            a.force_slow = mant_bits > (dtype == BFPQ_F32 ? 24 : (dtype == BFPQ_F16 ? 11 : 8));
-            set_hot16(a, dtype, mant_bits, eps_dt);
-            a.selws = nullptr;
-            return fused_launch(dtype, a, 0, true, s);
-        }
+        if (aligned16(src, deq, out_codes) && fused_shape_ok(rows, cols, dtype, block_size, 0, 0))
+            return fused_launch(dtype, fused(src, deq, 0, nullptr), 0, true, s);
         return launch_quant_rows(src, deq, out_codes, out_exp, rows, cols, dtype, block_size, mant_bits, eps_dt, code_bits, stoch_seed, exp_win, s);
     };
     if (block_size == 0) {                                               // sparsify only
@@ -718,21 +713,12 @@ int bfpq_quantize_nm(const void* in, void* out_deq, void* out_codes, int8_t* out
 int bfpq_quantize_mx8(const void* in, void* out8, void* out_scale, int64_t rows, int64_t cols, int dtype, int mant_bits, double epsilon,
                       const uint8_t* exp_win, void* stream)
 {
-    if (dtype < 0 || dtype > 2 || rows < 0 || cols < 0 || mant_bits < 1 || mant_bits > 4) return BFPQ_E_ARG;
+    if (!dtype_ok(dtype) || rows < 0 || cols < 0 || mant_bits < 1 || mant_bits > 4) return BFPQ_E_ARG;
     if (rows * cols == 0) return 0;
     if (!in || !out8 || !out_scale || !exp_win) return BFPQ_E_ARG;
     if (cols % 64 != 0) return BFPQ_E_UNSUPPORTED;                                     // (callers take bfpq_quantize_nm + bfpq_mx8_from_hbfp)
-    if ((reinterpret_cast<uintptr_t>(in) & 15u) || (reinterpret_cast<uintptr_t>(out8) & 7u) || (reinterpret_cast<uintptr_t>(out_scale) & 7u)) return BFPQ_E_UNSUPPORTED;
-    const float eps_dt = h_round((float)epsilon, dtype);
-    FusedArgs a;
-    a.in = in; a.out_deq = nullptr; a.out_codes = out8; a.out_exp = reinterpret_cast<int8_t*>(out_scale);
-    a.n_items = rows * cols / dtype_vec(dtype);
-    a.exp_win = exp_win; a.nm_lut = nullptr; a.seed = 0; a.eps_dt = eps_dt;
-    a.lpb = 64 / dtype_vec(dtype);
-    a.mant_bits = mant_bits; a.N = 0; a.code_bits = 8;
-    a.force_slow = 0;
-    set_hot16(a, dtype, mant_bits, eps_dt);
-    a.selws = nullptr;
+    if (!aligned16(in) || (reinterpret_cast<uintptr_t>(out8) & 7u) || (reinterpret_cast<uintptr_t>(out_scale) & 7u)) return BFPQ_E_UNSUPPORTED;
+    FusedArgs a = mx8_args(in, out8, out_scale, rows * cols / dtype_vec(dtype), dtype, mant_bits, epsilon, exp_win);
     if (dtype == BFPQ_F32) {                                                            // fp32: the general arithmetic of the fused kernel, image bytes in its store epilogue
         a.code_bits = kCodeBitsE4M3;
         return fused_launch(dtype, a, 0, true, (hipStream_t)stream);
@@ -743,7 +729,7 @@ int bfpq_quantize_mx8(const void* in, void* out8, void* out_scale, int64_t rows,
 int bfpq_quantize_mx8_nm(const void* in, void* out8, void* out_scale, int64_t rows, int64_t cols, int dtype, int mant_bits, double epsilon,
                          int N, int M, int sparsify_first, const uint8_t* exp_win, const uint8_t* nm_lut, void* stream)
 {
-    if (dtype < 0 || dtype > 2 || rows < 0 || cols < 0 || mant_bits < 1 || mant_bits > 4) return BFPQ_E_ARG;
+    if (!dtype_ok(dtype) || rows < 0 || cols < 0 || mant_bits < 1 || mant_bits > 4) return BFPQ_E_ARG;
     if (M < 1 || N < 1 || N > M) return BFPQ_E_ARG;
     if (M > 64) return BFPQ_E_UNSUPPORTED;
     if (rows * cols == 0) return 0;
@@ -752,17 +738,9 @@ int bfpq_quantize_mx8_nm(const void* in, void* out8, void* out_scale, int64_t ro
     if (!(M == 2 || M == 4 || M == 8)) return BFPQ_E_UNSUPPORTED;                      // (callers take bfpq_quantize_nm + bfpq_mx8_from_hbfp)
     if (M == 4 && !nm_lut) return BFPQ_E_ARG;
     if (cols % 64 != 0) return BFPQ_E_UNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(in) & 15u) || (reinterpret_cast<uintptr_t>(out8) & 7u) || (reinterpret_cast<uintptr_t>(out_scale) & 7u)) return BFPQ_E_UNSUPPORTED;
-    const float eps_dt = h_round((float)epsilon, dtype);
-    FusedArgs a;
-    a.in = in; a.out_deq = nullptr; a.out_codes = out8; a.out_exp = reinterpret_cast<int8_t*>(out_scale);
-    a.n_items = rows * cols / dtype_vec(dtype);
-    a.exp_win = exp_win; a.nm_lut = nm_lut; a.seed = 0; a.eps_dt = eps_dt;
-    a.lpb = 64 / dtype_vec(dtype);
-    a.mant_bits = mant_bits; a.N = N; a.code_bits = 8;
-    a.force_slow = 0;
-    set_hot16(a, dtype, mant_bits, eps_dt);
-    a.selws = nullptr;
+    if (!aligned16(in) || (reinterpret_cast<uintptr_t>(out8) & 7u) || (reinterpret_cast<uintptr_t>(out_scale) & 7u)) return BFPQ_E_UNSUPPORTED;
+    FusedArgs a = mx8_args(in, out8, out_scale, rows * cols / dtype_vec(dtype), dtype, mant_bits, epsilon, exp_win);
+    a.nm_lut = nm_lut; a.N = N;
     if (dtype == BFPQ_F32) {                                                            // fp32: the general kernel, image bytes in its store epilogue
         a.code_bits = kCodeBitsE4M3;
         return fused_launch(dtype, a, M, sparsify_first != 0, (hipStream_t)stream);
@@ -773,7 +751,7 @@ int bfpq_quantize_mx8_nm(const void* in, void* out8, void* out_scale, int64_t ro
 int bfpq_quantize_threshold_mx8(const void* in, void* out8, void* out_scale, int64_t rows, int64_t cols, int dtype, int mant_bits, double epsilon,
                                 const uint8_t* exp_win, void* ws, void* stream)
 {
-    if (dtype < 0 || dtype > 2 || rows < 0 || cols < 0 || mant_bits < 1 || mant_bits > 4) return BFPQ_E_ARG;
+    if (!dtype_ok(dtype) || rows < 0 || cols < 0 || mant_bits < 1 || mant_bits > 4) return BFPQ_E_ARG;
     if (rows * cols == 0) return 0;
     if (!in || !out8 || !out_scale || !exp_win || !ws) return BFPQ_E_ARG;
     // the cut-segment workgroups re-read the input while the others write: no output may overlap it
@@ -781,18 +759,10 @@ int bfpq_quantize_threshold_mx8(const void* in, void* out8, void* out_scale, int
     auto overlaps = [&](const void* p, int64_t n) { const uintptr_t o0 = reinterpret_cast<uintptr_t>(p); return o0 < i1 && i0 < o0 + (uintptr_t)n; };
     if (overlaps(out8, rows * cols) || overlaps(out_scale, rows * (cols / 64 > 0 ? cols / 64 : 1))) return BFPQ_E_ARG;
     if (cols % 64 != 0) return BFPQ_E_UNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(in) & 15u) || (reinterpret_cast<uintptr_t>(out8) & 7u) || (reinterpret_cast<uintptr_t>(out_scale) & 7u)) return BFPQ_E_UNSUPPORTED;
+    if (!aligned16(in) || (reinterpret_cast<uintptr_t>(out8) & 7u) || (reinterpret_cast<uintptr_t>(out_scale) & 7u)) return BFPQ_E_UNSUPPORTED;
     const int64_t n_items = rows * cols / dtype_vec(dtype);
     if (dtype != BFPQ_F32 && n_items > ((int64_t)1 << 27)) return BFPQ_E_UNSUPPORTED;   // (32-bit indexing, no pieces: see launch_fused_threshold_mx8)
-    const float eps_dt = h_round((float)epsilon, dtype);
-    FusedArgs a;
-    a.in = in; a.out_deq = nullptr; a.out_codes = out8; a.out_exp = reinterpret_cast<int8_t*>(out_scale);
-    a.n_items = n_items;
-    a.exp_win = exp_win; a.nm_lut = nullptr; a.seed = 0; a.eps_dt = eps_dt;
-    a.lpb = 64 / dtype_vec(dtype);
-    a.mant_bits = mant_bits; a.N = 0; a.code_bits = 8;
-    a.force_slow = 0;
-    set_hot16(a, dtype, mant_bits, eps_dt);
+    FusedArgs a = mx8_args(in, out8, out_scale, n_items, dtype, mant_bits, epsilon, exp_win);
     a.selws = (SelWs*)ws;
     if (dtype == BFPQ_F32) {
         a.code_bits = kCodeBitsE4M3;
@@ -880,19 +850,13 @@ int bfpq_fake_quantize_list(const bfpq_plan* p, const bfpq_tensor_desc* descs, i
     Lanes lanes(stream, aux_streams, n_aux);
     auto join = [&](int rc) { return lanes.join(rc); };
     const int dtype = p->dtype;
-    if (dtype < 0 || dtype > 2 || p->block_size < 0 || (p->block_size > 0 && !p->exp_win_dev)) return BFPQ_E_ARG;
+    if (!dtype_ok(dtype) || p->block_size < 0 || (p->block_size > 0 && !p->exp_win_dev)) return BFPQ_E_ARG;
     const bool any_nm_cfg = p->M > 0;
     // tensors the single-pass kernel takes go into launches of up to kMaxBatch; the rest (ragged shapes, N:8, ...) one by one
     BatchArgs b;
     b.n = 0; b.total_chunks = 0;
-    FusedArgs a;
-    a.in = nullptr; a.out_deq = nullptr; a.out_codes = nullptr; a.out_exp = nullptr; a.n_items = 0;
-    a.exp_win = p->exp_win_dev; a.nm_lut = p->nm_lut_dev; a.seed = 0; a.eps_dt = h_round((float)p->epsilon, dtype);
-    a.lpb = p->block_size ? p->block_size / dtype_vec(dtype) : 0;
-    a.mant_bits = p->mant_bits; a.N = p->N; a.code_bits = 0;
-    a.force_slow = p->mant_bits > (dtype == BFPQ_F32 ? 24 : (dtype == BFPQ_F16 ? 11 : 8));
-    set_hot16(a, dtype, p->mant_bits, a.eps_dt);
-    a.selws = nullptr;
+    FusedArgs a = fused_args(dtype, p->block_size, p->mant_bits, h_round((float)p->epsilon, dtype), p->exp_win_dev);
+    a.nm_lut = p->nm_lut_dev; a.N = p->N;
     bool batch_has_nm = false;
     // (the small tensors' list launches stay on the caller's stream: spread over the lanes in byte-budgeted batches they were SLOWER --
     // OPT-125m's 72 weights 147 us against 122-131, ViT-L's 144 weights 462 against 417-439: the fork and the join cost more than two
@@ -922,8 +886,7 @@ int bfpq_fake_quantize_list(const bfpq_plan* p, const bfpq_tensor_desc* descs, i
         const bool nm = any_nm_cfg && d.apply_nm != 0;
         const int N = nm ? p->N : 0, M = nm ? p->M : 0;
         if (p->block_size == 0 && M == 0) return join(BFPQ_E_ARG);         // identity: the caller keeps its tensor
-        const bool aligned = ((reinterpret_cast<uintptr_t>(d.in_dev) | reinterpret_cast<uintptr_t>(d.out_dev)) & 15u) == 0;
-        const bool ok = aligned && (M == 0 || (M == 4 && p->nm_lut_dev)) && p->block_size > 0 &&
+        const bool ok = aligned16(d.in_dev, d.out_dev) && (M == 0 || (M == 4 && p->nm_lut_dev)) && p->block_size > 0 &&
                         fused_shape_ok(d.rows, d.cols, dtype, p->block_size, N, M) &&
                         (d.rows * d.cols / dtype_vec(dtype)) % kThreads == 0 &&          // whole chunks of 256 lane items only
                         (d.rows * d.cols / dtype_vec(dtype) + kThreads - 1) / kThreads < ((int64_t)1 << 31);
@@ -954,7 +917,7 @@ int bfpq_fake_quantize_batched(const bfpq_plan* p, const bfpq_tensor_desc* descs
 int bfpq_nm_sparsify(const void* in, void* out, int64_t rows, int64_t cols, int dtype, int N, int M,
                      const uint8_t* nm4_lut, void* stream)
 {
-    if (!in || !out || dtype < 0 || dtype > 2 || rows < 0 || cols < 0) return BFPQ_E_ARG;
+    if (!in || !out || !dtype_ok(dtype) || rows < 0 || cols < 0) return BFPQ_E_ARG;
     if (!(N > 0 && M > 0 && N <= M)) return BFPQ_E_ARG;
     if (M > 64) return BFPQ_E_UNSUPPORTED;
     return bfpq_quantize_nm(in, out, nullptr, nullptr, rows, cols, dtype, 0, 0, 0.0, N, M, 1, 0, 0, nullptr, nm4_lut, nullptr, stream);
@@ -966,24 +929,18 @@ int bfpq_quantize_threshold(const void* in, void* out_deq, void* out_codes, int8
                             void* ws, void* scratch, void* stream)
 {
     hipStream_t s = (hipStream_t)stream;
-    if (dtype < 0 || dtype > 2 || rows < 0 || cols < 0 || block_size <= 0) return BFPQ_E_ARG;
+    if (!dtype_ok(dtype) || rows < 0 || cols < 0 || block_size <= 0) return BFPQ_E_ARG;
     if (rows * cols == 0) return 0;
     if (!in || !ws || !exp_win || (!out_deq && !out_codes && !out_exp)) return BFPQ_E_ARG;
     if (mant_bits < 0 || mant_bits > 23) return BFPQ_E_ARG;
     if (out_codes && !(code_bits == 4 || code_bits == 8 || code_bits == 16)) return BFPQ_E_ARG;
-    if (out_codes && ((code_bits == 4 && mant_bits > 3) || (code_bits == 8 && mant_bits > 7) || (code_bits == 16 && mant_bits > 15))) return BFPQ_E_ARG;
+    if (out_codes && !codes_fit(code_bits, mant_bits)) return BFPQ_E_ARG;
     const float eps_dt = h_round((float)epsilon, dtype);
-    const bool aligned = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out_deq) |
-                           reinterpret_cast<uintptr_t>(out_codes)) & 15u) == 0;
-    if (aligned && fused_shape_ok(rows, cols, dtype, block_size, 0, 0)) {
-        FusedArgs a;
+    if (aligned16(in, out_deq, out_codes) && fused_shape_ok(rows, cols, dtype, block_size, 0, 0)) {
+        FusedArgs a = fused_args(dtype, block_size, mant_bits, eps_dt, exp_win);
         a.in = in; a.out_deq = out_deq; a.out_codes = out_codes; a.out_exp = out_exp;
         a.n_items = rows * cols / dtype_vec(dtype);
-        a.exp_win = exp_win; a.nm_lut = nullptr; a.seed = stoch_seed; a.eps_dt = eps_dt;
-        a.lpb = block_size / dtype_vec(dtype);
-        a.mant_bits = mant_bits; a.N = 0; a.code_bits = code_bits;
-        a.force_slow = mant_bits > (dtype == BFPQ_F32 ? 24 : (dtype == BFPQ_F16 ? 11 : 8));
-        set_hot16(a, dtype, mant_bits, eps_dt);
+        a.seed = stoch_seed; a.code_bits = code_bits;
         a.selws = (SelWs*)ws;
         return fused_threshold(dtype, a, s);
     }
@@ -998,7 +955,7 @@ int bfpq_quantize_threshold(const void* in, void* out_deq, void* out_codes, int8
 int bfpq_prune_quantize(const void* in, void* out, int64_t rows, int64_t cols, int dtype, int block_size, int mant_bits,
                         double epsilon, int64_t k, const uint8_t* exp_win, void* ws, void* stream)
 {
-    if (dtype < 0 || dtype > 2 || rows < 0 || cols < 0 || block_size <= 0 || k < 0 || k > rows * cols) return BFPQ_E_ARG;
+    if (!dtype_ok(dtype) || rows < 0 || cols < 0 || block_size <= 0 || k < 0 || k > rows * cols) return BFPQ_E_ARG;
     if (rows * cols == 0) return 0;
     if (!in || !out || !ws || !exp_win || in == out || mant_bits < 0 || mant_bits > 23) return BFPQ_E_ARG;
     if (rows * cols >= ((int64_t)1 << 32)) return BFPQ_E_UNSUPPORTED;
@@ -1026,7 +983,7 @@ int bfpq_prune_quantize_list(const bfpq_prune_desc* descs, int n, int dtype, int
         if (d.rows < 0 || d.cols < 0 || d.k < 0 || d.k > d.rows * d.cols) { rc = BFPQ_E_ARG; break; }
         if (d.rows * d.cols == 0) continue;
         if (!d.in_dev || !d.out_dev || d.in_dev == d.out_dev) { rc = BFPQ_E_ARG; break; }
-        const int l = n > 1 ? lanes.pick(d.rows * d.cols * dtype_size(dtype < 0 || dtype > 2 ? 0 : dtype)) : 0;
+        const int l = n > 1 ? lanes.pick(d.rows * d.cols * dtype_size(dtype_ok(dtype) ? dtype : 0)) : 0;
         rc = bfpq_prune_quantize(d.in_dev, d.out_dev, d.rows, d.cols, dtype, block_size, mant_bits, epsilon, d.k, exp_win, wss[l], lanes.s[l]);
     }
     return lanes.join(rc);
@@ -1061,7 +1018,7 @@ int bfpq_stoc_widen_f16(const void* in, void* out, int64_t n, void* stream)
 {
     if (n < 0) return BFPQ_E_ARG;
     if (n == 0) return 0;
-    if (!in || !out || (reinterpret_cast<uintptr_t>(in) & 7u) || (reinterpret_cast<uintptr_t>(out) & 15u)) return BFPQ_E_ARG;
+    if (!in || !out || (reinterpret_cast<uintptr_t>(in) & 7u) || !aligned16(out)) return BFPQ_E_ARG;
     const int64_t want = ((n >> 2) + 255) / 256;
     const int grid = (int)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
     hipLaunchKernelGGL(k_stoc_widen_f16, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)in, (uint32_t*)out, n);

@@ -467,7 +467,7 @@ __global__ void __launch_bounds__(64 * WM * WN) k_mx8_gemm_ring(const uint8_t* _
 }
 
 // K split over `splits` workgroups per output tile (short token counts: too few tiles for the chip, e.g. 128 tokens x down_proj = 32 tiles
-// over K = 11008): workgroup (tile, part) accumulates its trips of K into the fp32 slab `part`; k_mx8_splitk_reduce adds the slabs in part
+// over K = 11008): workgroup (tile, part) accumulates its trips of K into the fp32 slab `part`; k_slab_reduce adds the slabs in part
 // order (deterministic), the bias, and rounds to the output dtype.
 template <int WM, int WN, int TM, int TN, int KB, int NS>
 __global__ void __launch_bounds__(64 * WM * WN) k_mx8_gemm_ring_splitk(const uint8_t* __restrict__ x8, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ w8,
@@ -478,18 +478,6 @@ __global__ void __launch_bounds__(64 * WM * WN) k_mx8_gemm_ring_splitk(const uin
     const int part = (int)blockIdx.x / tiles, tile = (int)blockIdx.x % tiles;
     const int trips = K >> 8, a = part * trips_per_part, b = a + trips_per_part < trips ? a + trips_per_part : trips;
     ring_tile<BFPQ_F32, WM, WN, TM, TN, KB, NS>(lds, tile, tiles, 0, x8, xs, w8, wsc, nullptr, slabs + (size_t)part * T * N, T, N, K, tiles_t, a, b);
-}
-
-template <int OUT_DT>
-__global__ void __launch_bounds__(256) k_mx8_splitk_reduce(const float* __restrict__ slabs, const void* __restrict__ bias, void* __restrict__ out, int64_t TN_, int N, int parts)
-{
-    using raw_t = typename Traits<OUT_DT>::raw_t;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < TN_; i += (int64_t)gridDim.x * 256) {
-        float acc = slabs[i];
-        for (int p = 1; p < parts; p++) acc += slabs[(size_t)p * TN_ + i];
-        if (bias) acc += raw_to_f32<OUT_DT>((uint32_t)reinterpret_cast<const raw_t*>(bias)[i % N]);
-        reinterpret_cast<raw_t*>(out)[i] = (raw_t)f32_to_raw<OUT_DT>(acc);
-    }
 }
 
 // Two tile shapes in one launch.  256 x 256 tiles need half the operand bytes per flop, but N / 256 x T / 256 of them rarely fill
@@ -590,11 +578,11 @@ __attribute__((visibility("hidden"))) int bfpq_g_mx8_variant = -1;             /
 int bfpq_hbfp_linear_mx8(const void* x8, const void* xs, const void* w8, const void* ws, const void* bias, void* out,
                          int64_t T, int64_t N, int64_t K, int out_dtype, void* stream)
 {
-    if (out_dtype < 0 || out_dtype > 2 || T < 0 || N < 0) return BFPQ_E_ARG;
+    if (!dtype_ok(out_dtype) || T < 0 || N < 0) return BFPQ_E_ARG;
     if (T == 0 || N == 0) return 0;
     if (!bfpq_hbfp_linear_mx8_ok(T, N, K)) return BFPQ_E_UNSUPPORTED;
     if (!x8 || !xs || !w8 || !ws || !out) return BFPQ_E_ARG;
-    if ((reinterpret_cast<uintptr_t>(x8) | reinterpret_cast<uintptr_t>(w8)) & 15u) return BFPQ_E_ARG;
+    if (!aligned16(x8, w8)) return BFPQ_E_ARG;
     if ((reinterpret_cast<uintptr_t>(xs) | reinterpret_cast<uintptr_t>(ws)) & 3u) return BFPQ_E_ARG;
     int variant = bfpq_g_mx8_variant;
     if (variant < 0 || variant >= kMxVariants) {
@@ -610,9 +598,7 @@ int bfpq_hbfp_linear_mx8(const void* x8, const void* xs, const void* w8, const v
     }
     hipStream_t s = (hipStream_t)stream;
     const uint8_t *a = (const uint8_t*)x8, *as = (const uint8_t*)xs, *b = (const uint8_t*)w8, *bs = (const uint8_t*)ws;
-    if (out_dtype == BFPQ_F32) return launch_mx8<BFPQ_F32>(variant, a, as, b, bs, bias, out, (int)T, (int)N, (int)K, s);
-    if (out_dtype == BFPQ_F16) return launch_mx8<BFPQ_F16>(variant, a, as, b, bs, bias, out, (int)T, (int)N, (int)K, s);
-    return launch_mx8<BFPQ_BF16>(variant, a, as, b, bs, bias, out, (int)T, (int)N, (int)K, s);
+    return with_dtype(out_dtype, [&](auto dt) { return launch_mx8<dt>(variant, a, as, b, bs, bias, out, (int)T, (int)N, (int)K, s); });
 }
 
 /* K split for short token counts: how many parts the plan wants (1: call bfpq_hbfp_linear_mx8), and the call that takes the
@@ -631,11 +617,11 @@ int bfpq_hbfp_linear_mx8_parts(int64_t T, int64_t N, int64_t K)
 int bfpq_hbfp_linear_mx8_splitk(const void* x8, const void* xs, const void* w8, const void* ws, const void* bias, void* out, float* slabs, int parts,
                                 int64_t T, int64_t N, int64_t K, int out_dtype, void* stream)
 {
-    if (out_dtype < 0 || out_dtype > 2 || T < 0 || N < 0 || parts < 1 || parts > 64) return BFPQ_E_ARG;
+    if (!dtype_ok(out_dtype) || T < 0 || N < 0 || parts < 1 || parts > 64) return BFPQ_E_ARG;
     if (T == 0 || N == 0) return 0;
     if (!bfpq_hbfp_linear_mx8_ok(T, N, K)) return BFPQ_E_UNSUPPORTED;
     if (!x8 || !xs || !w8 || !ws || !out || !slabs) return BFPQ_E_ARG;
-    if ((reinterpret_cast<uintptr_t>(x8) | reinterpret_cast<uintptr_t>(w8) | reinterpret_cast<uintptr_t>(slabs)) & 15u) return BFPQ_E_ARG;
+    if (!aligned16(x8, w8, slabs)) return BFPQ_E_ARG;
     if ((reinterpret_cast<uintptr_t>(xs) | reinterpret_cast<uintptr_t>(ws)) & 3u) return BFPQ_E_ARG;
     const int trips = (int)(K / 256);
     if (parts > trips) parts = trips;
@@ -645,12 +631,7 @@ int bfpq_hbfp_linear_mx8_splitk(const void* x8, const void* xs, const void* w8, 
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL((k_mx8_gemm_ring_splitk<2, 2, 2, 2, 2, 3>), dim3((unsigned)(tiles * parts)), dim3(256), 0, s, (const uint8_t*)x8, (const uint8_t*)xs,
                        (const uint8_t*)w8, (const uint8_t*)ws, slabs, (int)T, (int)N, (int)K, tiles_t, tiles, tpp);
-    const int64_t tn = T * N;
-    int64_t g = (tn + 255) / 256;
-    if (g > 2048) g = 2048;
-    if (out_dtype == BFPQ_F32) hipLaunchKernelGGL((k_mx8_splitk_reduce<BFPQ_F32>), dim3((unsigned)g), dim3(256), 0, s, (const float*)slabs, bias, out, tn, (int)N, parts);
-    else if (out_dtype == BFPQ_F16) hipLaunchKernelGGL((k_mx8_splitk_reduce<BFPQ_F16>), dim3((unsigned)g), dim3(256), 0, s, (const float*)slabs, bias, out, tn, (int)N, parts);
-    else hipLaunchKernelGGL((k_mx8_splitk_reduce<BFPQ_BF16>), dim3((unsigned)g), dim3(256), 0, s, (const float*)slabs, bias, out, tn, (int)N, parts);
+    launch_slab_reduce(out_dtype, slabs, (size_t)(T * N), bias, out, T * N, N, parts, s);
     return (int)hipGetLastError();
 }
 

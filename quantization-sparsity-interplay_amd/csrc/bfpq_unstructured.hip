@@ -582,7 +582,7 @@ int64_t bfpq_select_ws_bytes(void) { return (int64_t)sizeof(SelWs); }
 // numel and k are counted in 32 bits on the device
 static bool select_args_ok(const void* in, int64_t numel, int dtype, int pass, int64_t k, const void* ws)
 {
-    return ws && dtype >= 0 && dtype <= 2 && numel >= 0 && (in || numel == 0) && pass >= 0 && pass < bfpq_select_passes(dtype) && k >= 0;
+    return ws && dtype_ok(dtype) && numel >= 0 && (in || numel == 0) && pass >= 0 && pass < bfpq_select_passes(dtype) && k >= 0;
 }
 
 static int launch_select_hist(const void* in, int64_t numel, int dtype, int pass, int64_t k, int64_t numel_global,
@@ -595,21 +595,18 @@ static int launch_select_hist(const void* in, int64_t numel, int dtype, int pass
     const size_t lds = sizeof(uint32_t) << nbits;
     const int vec = dtype_vec(dtype);
     const SegGeom g = seg_geom((numel + vec - 1) / vec);
-    const bool fast = (reinterpret_cast<uintptr_t>(in) & 15u) == 0 && numel % vec == 0;
+    const bool fast = aligned16(in) && numel % vec == 0;
     hipStream_t s = (hipStream_t)stream;
     SelWs* w = (SelWs*)ws;
-#define BFPQ_SH(DT, F) do { \
-        if (lds > 48 * 1024) { \
-            const hipError_t err = hipFuncSetAttribute((const void*)k_select_hist<DT, F>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            if (err != hipSuccess) return (int)err; \
-        } \
-        hipLaunchKernelGGL((k_select_hist<DT, F>), dim3(g.G), dim3(kSelThreads), lds, s, in, numel, pass, shift, nbits, first, last, w, hist, k, numel_global, fuse); \
-    } while (0)
-    if (dtype == BFPQ_F32) { if (fast) BFPQ_SH(BFPQ_F32, true); else BFPQ_SH(BFPQ_F32, false); }
-    else if (dtype == BFPQ_F16) { if (fast) BFPQ_SH(BFPQ_F16, true); else BFPQ_SH(BFPQ_F16, false); }
-    else { if (fast) BFPQ_SH(BFPQ_BF16, true); else BFPQ_SH(BFPQ_BF16, false); }
-#undef BFPQ_SH
-    return (int)hipGetLastError();
+    return with_dtype(dtype, [&](auto dt) -> int {
+        const auto kernel = fast ? k_select_hist<dt, true> : k_select_hist<dt, false>;
+        if (lds > 48 * 1024) {
+            const hipError_t err = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (err != hipSuccess) return (int)err;
+        }
+        hipLaunchKernelGGL(kernel, dim3(g.G), dim3(kSelThreads), lds, s, in, numel, pass, shift, nbits, first, last, w, hist, k, numel_global, fuse);
+        return (int)hipGetLastError();
+    });
 }
 
 int bfpq_select_hist(const void* in, int64_t numel, int dtype, int pass, int64_t k, int64_t numel_global,
@@ -633,16 +630,14 @@ int bfpq_select_resolve_ex(const void* in, int64_t numel, int dtype, int pass, i
     select_digit(dtype, pass, &shift, &nbits);
     const int vec = dtype_vec(dtype);
     const SegGeom g = seg_geom((numel + vec - 1) / vec);
-    const bool fast = (reinterpret_cast<uintptr_t>(in) & 15u) == 0 && numel % vec == 0;
+    const bool fast = aligned16(in) && numel % vec == 0;
     const int first = pass == 0, last = pass == bfpq_select_passes(dtype) - 1;
     hipStream_t s = (hipStream_t)stream;
     SelWs* w = (SelWs*)ws;
-#define BFPQ_SR(DT, F) hipLaunchKernelGGL((k_select_resolve<DT, F>), dim3(g.G), dim3(kResThreads), 0, s, in, numel, pass, shift, nbits, first, last, \
-                                          hist_all, n_ranks, rank, copies, rank_stride_words, k, w, zero_hist, hist_all ? 0 : 1)
-    if (dtype == BFPQ_F32) { if (fast) BFPQ_SR(BFPQ_F32, true); else BFPQ_SR(BFPQ_F32, false); }
-    else if (dtype == BFPQ_F16) { if (fast) BFPQ_SR(BFPQ_F16, true); else BFPQ_SR(BFPQ_F16, false); }
-    else { if (fast) BFPQ_SR(BFPQ_BF16, true); else BFPQ_SR(BFPQ_BF16, false); }
-#undef BFPQ_SR
+    with_dtype(dtype, [&](auto dt) {
+        hipLaunchKernelGGL((fast ? k_select_resolve<dt, true> : k_select_resolve<dt, false>), dim3(g.G), dim3(kResThreads), 0, s, in, numel, pass, shift,
+                           nbits, first, last, hist_all, n_ranks, rank, copies, rank_stride_words, k, w, zero_hist, hist_all ? 0 : 1);
+    });
     return (int)hipGetLastError();
 }
 
@@ -667,7 +662,7 @@ int bfpq_select(const void* in, int64_t numel, int dtype, int64_t k, void* ws, v
     if (rc) return rc;
     const size_t lds = sizeof(uint32_t) * kFineBins;
     const SegGeom g = seg_geom((numel + 3) / 4);
-    const bool fast = (reinterpret_cast<uintptr_t>(in) & 15u) == 0 && numel % 4 == 0;
+    const bool fast = aligned16(in) && numel % 4 == 0;
     hipStream_t s = (hipStream_t)stream;
     static bool attr_set = false;
     if (!attr_set) {
@@ -690,18 +685,17 @@ int bfpq_select_reset(void* ws, void* stream)
 
 int bfpq_threshold_apply(const void* in, void* out, int64_t numel, int dtype, void* ws, void* stream)
 {
-    if (!in || !out || !ws || dtype < 0 || dtype > 2 || numel < 0) return BFPQ_E_ARG;
+    if (!in || !out || !ws || !dtype_ok(dtype) || numel < 0) return BFPQ_E_ARG;
     if (numel == 0) return 0;
     if (in == out) return BFPQ_E_ARG;                         // (tie ranks are counted from the input while other tiles are written)
     hipStream_t s = (hipStream_t)stream;
     SelWs* w = (SelWs*)ws;
     const int vec = dtype_vec(dtype);
-    const bool fast = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0 && numel % vec == 0;
+    const bool fast = aligned16(in, out) && numel % vec == 0;
     const dim3 grid(kCutWGs + grid_for((numel + vec - 1) / vec)), block(kThreads);
-#define BFPQ_TA(DT) do { if (fast) hipLaunchKernelGGL((k_threshold_apply<DT, true>), grid, block, 0, s, in, out, numel, w); \
-                         else hipLaunchKernelGGL((k_threshold_apply<DT, false>), grid, block, 0, s, in, out, numel, w); } while (0)
-    if (dtype == BFPQ_F32) BFPQ_TA(BFPQ_F32); else if (dtype == BFPQ_F16) BFPQ_TA(BFPQ_F16); else BFPQ_TA(BFPQ_BF16);
-#undef BFPQ_TA
+    with_dtype(dtype, [&](auto dt) {
+        hipLaunchKernelGGL((fast ? k_threshold_apply<dt, true> : k_threshold_apply<dt, false>), grid, block, 0, s, in, out, numel, w);
+    });
     return (int)hipGetLastError();
 }
 

@@ -30,6 +30,62 @@ SELECT_HIST_ENTRIES = 32768 + 256
 SELECT_HIST_COPIES = 8
 
 
+# include/bfpq.h, entry by entry: name -> (restype, argtypes)
+_vp, _i64, _i32, _u64, _dbl = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_uint64, ctypes.c_double
+PROTOTYPES = {
+    "bfpq_version": (_i32, []),
+    "bfpq_tune": (_i32, [_i32, _i32]),
+    "bfpq_error_string": (ctypes.c_char_p, [_i32]),
+    "bfpq_exp_window_host": (_i32, [_i32, _vp]),
+    "bfpq_nm4_lut_host": (_i32, [_i32, _vp]),
+    "bfpq_nm8_lut_host": (_i32, [_i32, _vp]),
+    "bfpq_compact24": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "bfpq_expand24": (_i32, [_vp, _vp, _vp, _i64, _vp]),
+    "bfpq_nm_prune_mask_host": (_u64, [_vp, _i32, _i32]),
+    "bfpq_quantize_nm": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _dbl, _i32, _i32, _i32, _i32, _u64, _vp, _vp, _vp, _vp]),
+    "bfpq_fake_quantize": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp]),
+    "bfpq_fake_quantize_batched": (_i32, [_vp, _vp, _i32, _vp]),
+    "bfpq_fake_quantize_list": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32]),
+    "bfpq_is_fused": (_i32, [_i64, _i64, _i32, _i32, _i32, _i32]),
+    "bfpq_nm_sparsify": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "bfpq_select_passes": (_i32, [_i32]),
+    "bfpq_select_ws_bytes": (_i64, []),
+    "bfpq_select": (_i32, [_vp, _i64, _i32, _i64, _vp, _vp]),
+    "bfpq_prune_quantize": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _dbl, _i64, _vp, _vp, _vp]),
+    "bfpq_prune_quantize_batched": (_i32, [_vp, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _i32, _vp, _vp]),
+    "bfpq_prune_quantize_list": (_i32, [_vp, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _i32, _vp, _vp, _i32]),
+    "bfpq_select_hist": (_i32, [_vp, _i64, _i32, _i32, _i64, _i64, _vp, _vp, _vp]),
+    "bfpq_select_resolve": (_i32, [_vp, _i64, _i32, _i32, _i64, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "bfpq_select_resolve_ex": (_i32, [_vp, _i64, _i32, _i32, _i64, _vp, _i32, _i32, _i32, _i64, _vp, _vp, _vp]),
+    "bfpq_threshold_apply": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp]),
+    "bfpq_select_reset": (_i32, [_vp, _vp]),
+    "bfpq_quantize_threshold": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _dbl, _i32, _u64, _vp, _vp, _vp, _vp]),
+    "bfpq_int_workspace_elems": (_i64, [_i64]),
+    "bfpq_int_quantize": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp]),
+    "bfpq_dequantize": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "bfpq_stoc_widen_f16": (_i32, [_vp, _vp, _i64, _vp]),
+    "bfpq_hbfp_linear_slices": (_i32, [_i64, _i64]),
+    "bfpq_hbfp_linear_decode": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp]),
+    "bfpq_hbfp_linear_tiled_ok": (_i32, [_i64, _i64]),
+    "bfpq_hbfp_linear_decode_tiled": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp]),
+    "bfpq_mx8_from_hbfp": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp]),
+    "bfpq_quantize_mx8": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _dbl, _vp, _vp]),
+    "bfpq_quantize_mx8_nm": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _dbl, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "bfpq_quantize_threshold_mx8": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _dbl, _vp, _vp, _vp]),
+    "bfpq_hbfp_linear_mx8_ok": (_i32, [_i64, _i64, _i64]),
+    "bfpq_hbfp_linear_mx8": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp]),
+    "bfpq_hbfp_linear_mx8_parts": (_i32, [_i64, _i64, _i64]),
+    "bfpq_hbfp_linear_mx8_splitk": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp]),
+    "bfpq_hbfp_linear_i8_ok": (_i32, [_i64, _i64, _i64]),
+    "bfpq_hbfp_linear_i8_parts": (_i32, [_i64, _i64, _i64]),
+    "bfpq_hbfp_linear_i8": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp]),
+    "bfpq_hbfp_linear_i8_splitk": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _vp]),
+    "bfpq_hbfp_linear_decode8_ws": (_i64, [_i64, _i64, _i64]),
+    "bfpq_hbfp_linear_decode8": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp]),
+    "bfpq_codes4_to_i8": (_i32, [_vp, _vp, _i64, _vp]),
+}
+
+
 class NativeUnavailable(RuntimeError):
     """libbfpq.so is not built / not loadable, or the tensor is not on a ROCm device."""
 
@@ -61,84 +117,14 @@ def load_library():
             L = ctypes.CDLL(path)
         except OSError as e:  # pragma: no cover
             raise NativeUnavailable(f"cannot load {path}: {e}") from e
-        vp, i64, i32, u64, dbl = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_uint64, ctypes.c_double
-        L.bfpq_version.restype = i32
-        L.bfpq_tune.argtypes = [i32, i32]
-        L.bfpq_tune.restype = i32
-        L.bfpq_error_string.restype = ctypes.c_char_p
-        L.bfpq_error_string.argtypes = [i32]
-        L.bfpq_exp_window_host.argtypes = [i32, vp]
-        L.bfpq_nm4_lut_host.argtypes = [i32, vp]
-        L.bfpq_nm8_lut_host.argtypes = [i32, vp]
-        L.bfpq_compact24.argtypes = [vp, vp, vp, i64, vp, vp]
-        L.bfpq_expand24.argtypes = [vp, vp, vp, i64, vp]
-        L.bfpq_nm_prune_mask_host.argtypes = [vp, i32, i32]
-        L.bfpq_nm_prune_mask_host.restype = u64
-        L.bfpq_quantize_nm.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, i32, dbl, i32, i32, i32, i32, u64, vp, vp, vp, vp]
-        L.bfpq_fake_quantize.argtypes = [vp, vp, vp, i64, i64, vp]
-        L.bfpq_fake_quantize_batched.argtypes = [vp, vp, i32, vp]
-        L.bfpq_fake_quantize_list.argtypes = [vp, vp, i32, vp, vp, i32]
-        L.bfpq_is_fused.argtypes = [i64, i64, i32, i32, i32, i32]
-        L.bfpq_nm_sparsify.argtypes = [vp, vp, i64, i64, i32, i32, i32, vp, vp]
-        L.bfpq_select_passes.argtypes = [i32]
-        L.bfpq_select_ws_bytes.argtypes = []
-        L.bfpq_select_ws_bytes.restype = i64
-        L.bfpq_select.argtypes = [vp, i64, i32, i64, vp, vp]
-        L.bfpq_prune_quantize.argtypes = [vp, vp, i64, i64, i32, i32, i32, dbl, i64, vp, vp, vp]
-        L.bfpq_prune_quantize_batched.argtypes = [vp, i32, i32, i32, i32, dbl, vp, vp, i32, vp, vp]
-        L.bfpq_prune_quantize_list.argtypes = [vp, i32, i32, i32, i32, dbl, vp, vp, i32, vp, vp, i32]
-        L.bfpq_select_hist.argtypes = [vp, i64, i32, i32, i64, i64, vp, vp, vp]
-        L.bfpq_select_resolve.argtypes = [vp, i64, i32, i32, i64, vp, i32, i32, vp, vp, vp]
-        L.bfpq_select_resolve_ex.argtypes = [vp, i64, i32, i32, i64, vp, i32, i32, i32, i64, vp, vp, vp]
-        L.bfpq_threshold_apply.argtypes = [vp, vp, i64, i32, vp, vp]
-        L.bfpq_select_reset.argtypes = [vp, vp]
-        L.bfpq_quantize_threshold.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, i32, dbl, i32, u64, vp, vp, vp, vp]
-        L.bfpq_int_workspace_elems.argtypes = [i64]
-        L.bfpq_int_workspace_elems.restype = i64
-        L.bfpq_int_quantize.argtypes = [vp, vp, i64, i64, i64, i32, i32, vp, vp]
-        L.bfpq_dequantize.argtypes = [vp, vp, vp, i64, i64, i32, i32, i32, i32, vp]
-        L.bfpq_stoc_widen_f16.argtypes = [vp, vp, i64, vp]
-        L.bfpq_hbfp_linear_slices.argtypes = [i64, i64]
-        L.bfpq_hbfp_linear_decode.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, i32, vp]
-        L.bfpq_hbfp_linear_tiled_ok.argtypes = [i64, i64]
-        L.bfpq_hbfp_linear_decode_tiled.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, i32, vp]
-        L.bfpq_mx8_from_hbfp.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, vp]
-        L.bfpq_quantize_mx8.argtypes = [vp, vp, vp, i64, i64, i32, i32, dbl, vp, vp]
-        L.bfpq_quantize_mx8_nm.argtypes = [vp, vp, vp, i64, i64, i32, i32, dbl, i32, i32, i32, vp, vp, vp]
-        L.bfpq_quantize_threshold_mx8.argtypes = [vp, vp, vp, i64, i64, i32, i32, dbl, vp, vp, vp]
-        L.bfpq_hbfp_linear_mx8_ok.argtypes = [i64, i64, i64]
-        L.bfpq_hbfp_linear_mx8.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, vp]
-        L.bfpq_hbfp_linear_mx8_parts.argtypes = [i64, i64, i64]
-        L.bfpq_hbfp_linear_mx8_splitk.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, i64, i32, vp]
-        L.bfpq_hbfp_linear_i8_ok.argtypes = [i64, i64, i64]
-        L.bfpq_hbfp_linear_i8_parts.argtypes = [i64, i64, i64]
-        L.bfpq_hbfp_linear_i8.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, i32, vp]
-        L.bfpq_hbfp_linear_i8_splitk.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, i64, i32, i32, i32, vp]
-        L.bfpq_hbfp_linear_decode8_ws.argtypes = [i64, i64, i64]
-        L.bfpq_hbfp_linear_decode8_ws.restype = i64
-        L.bfpq_hbfp_linear_decode8.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, i32, vp]
-        L.bfpq_codes4_to_i8.argtypes = [vp, vp, i64, vp]
-        for name in ("bfpq_exp_window_host", "bfpq_nm4_lut_host", "bfpq_nm8_lut_host", "bfpq_compact24", "bfpq_expand24", "bfpq_quantize_nm", "bfpq_fake_quantize", "bfpq_fake_quantize_batched", "bfpq_fake_quantize_list", "bfpq_is_fused", "bfpq_nm_sparsify",
-                     "bfpq_select_passes", "bfpq_select", "bfpq_select_hist", "bfpq_select_resolve", "bfpq_select_resolve_ex", "bfpq_select_reset",
-                     "bfpq_prune_quantize", "bfpq_prune_quantize_batched", "bfpq_prune_quantize_list",
-                     "bfpq_threshold_apply", "bfpq_quantize_threshold", "bfpq_int_quantize", "bfpq_dequantize", "bfpq_stoc_widen_f16", "bfpq_hbfp_linear_slices",
-                     "bfpq_hbfp_linear_decode", "bfpq_hbfp_linear_tiled_ok", "bfpq_hbfp_linear_decode_tiled",
-                     "bfpq_mx8_from_hbfp", "bfpq_quantize_mx8", "bfpq_hbfp_linear_mx8_ok", "bfpq_hbfp_linear_mx8",
-                     "bfpq_hbfp_linear_mx8_parts", "bfpq_hbfp_linear_mx8_splitk", "bfpq_quantize_mx8_nm", "bfpq_quantize_threshold_mx8",
-                     "bfpq_hbfp_linear_i8_ok", "bfpq_hbfp_linear_i8_parts", "bfpq_hbfp_linear_i8", "bfpq_hbfp_linear_i8_splitk",
-                     "bfpq_hbfp_linear_decode8", "bfpq_codes4_to_i8"):
-            getattr(L, name).restype = i32
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
         return _lib
 
 
-EXPORTED_SYMBOLS = ("bfpq_hbfp_linear_mx8_parts", "bfpq_hbfp_linear_mx8_splitk", "bfpq_quantize_mx8", "bfpq_mx8_from_hbfp", "bfpq_hbfp_linear_mx8_ok", "bfpq_hbfp_linear_mx8", "bfpq_hbfp_linear_tiled_ok", "bfpq_hbfp_linear_decode_tiled", "bfpq_hbfp_linear_slices", "bfpq_hbfp_linear_decode", "bfpq_dequantize", "bfpq_stoc_widen_f16", "bfpq_tune", "bfpq_int_workspace_elems", "bfpq_int_quantize", "bfpq_select_ws_bytes", "bfpq_version", "bfpq_error_string", "bfpq_exp_window_host", "bfpq_nm4_lut_host", "bfpq_nm8_lut_host", "bfpq_compact24", "bfpq_expand24",
-                    "bfpq_nm_prune_mask_host", "bfpq_quantize_nm", "bfpq_fake_quantize", "bfpq_fake_quantize_batched", "bfpq_fake_quantize_list", "bfpq_is_fused", "bfpq_nm_sparsify",
-                    "bfpq_select_passes", "bfpq_select", "bfpq_select_hist", "bfpq_select_resolve", "bfpq_select_resolve_ex", "bfpq_select_reset",
-                    "bfpq_prune_quantize", "bfpq_prune_quantize_batched", "bfpq_prune_quantize_list",
-                    "bfpq_threshold_apply", "bfpq_quantize_threshold", "bfpq_quantize_mx8_nm", "bfpq_quantize_threshold_mx8",
-                    "bfpq_hbfp_linear_i8_ok", "bfpq_hbfp_linear_i8_parts", "bfpq_hbfp_linear_i8", "bfpq_hbfp_linear_i8_splitk",
-                    "bfpq_hbfp_linear_decode8_ws", "bfpq_hbfp_linear_decode8", "bfpq_codes4_to_i8")
+EXPORTED_SYMBOLS = tuple(PROTOTYPES)
 
 
 def check(rc, what):

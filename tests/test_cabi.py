@@ -79,6 +79,48 @@ def test_argument_validation_without_gpu():
     assert L.bfpq_hbfp_linear_decode(one, one, one, one, one, one, 17, 4096, 11008, native.BF16, 3, 7, n) == -1      # row-major layout: <= 16 tokens
     assert L.bfpq_nm8_lut_host(0, one) == -1 and L.bfpq_nm8_lut_host(4, n) == -1
     assert L.bfpq_tune(1, 3) == -1 and L.bfpq_tune(1, 2) == 0 and L.bfpq_tune(1, 0) == 0
+    # each entry point's own checks, in its own order and with its own codes: a rejected call and an empty one
+    odd = ctypes.c_void_p(8)                 # 8-byte but not 16-byte aligned
+    far = ctypes.c_void_p(1 << 40)           # an output that overlaps no input
+    assert L.bfpq_quantize_threshold(one, one, n, n, 4, 64, 9, 64, 3, 1e-8, 0, 0, one, one, n, n) == -1              # bad dtype
+    assert L.bfpq_quantize_threshold(one, one, one, n, 4, 64, native.BF16, 64, 7, 1e-8, 4, 0, one, one, n, n) == -1   # 4-bit codes, 7-bit mantissa
+    assert L.bfpq_quantize_threshold(one, one, n, n, 0, 64, native.BF16, 64, 3, 1e-8, 0, 0, one, one, n, n) == 0      # empty
+    assert L.bfpq_quantize_mx8(odd, one, one, 4, 64, native.BF16, 3, 1e-8, one, n) == -2                             # input not 16-byte aligned
+    assert L.bfpq_quantize_mx8_nm(one, far, far, 4, 64, 9, 3, 1e-8, 2, 4, 1, one, one, n) == -1                      # bad dtype
+    assert L.bfpq_quantize_mx8_nm(one, far, far, 4, 64, native.BF16, 3, 1e-8, 2, 65, 1, one, one, n) == -2           # M > 64
+    assert L.bfpq_quantize_mx8_nm(odd, far, far, 4, 64, native.BF16, 3, 1e-8, 2, 4, 1, one, one, n) == -2            # input not 16-byte aligned
+    assert L.bfpq_quantize_mx8_nm(one, far, far, 0, 64, native.BF16, 3, 1e-8, 2, 4, 1, one, one, n) == 0             # empty
+    assert L.bfpq_quantize_threshold_mx8(one, far, far, 4, 64, native.BF16, 5, 1e-8, one, one, n) == -1              # 5 mantissa bits
+    assert L.bfpq_quantize_threshold_mx8(one, one, far, 4, 64, native.BF16, 3, 1e-8, one, one, n) == -1              # output overlaps the input
+    assert L.bfpq_quantize_threshold_mx8(odd, far, far, 4, 64, native.BF16, 3, 1e-8, one, one, n) == -2              # input not 16-byte aligned
+    assert L.bfpq_quantize_threshold_mx8(one, far, far, 0, 64, native.BF16, 3, 1e-8, one, one, n) == 0               # empty
+    assert L.bfpq_dequantize(one, one, one, 4, 64, 9, 64, 3, 8, n) == -1                                             # bad dtype
+    assert L.bfpq_dequantize(one, one, one, 4, 64, native.BF16, 64, 3, 5, n) == -1                                   # 5-bit codes
+    assert L.bfpq_dequantize(one, one, one, 0, 64, native.BF16, 64, 3, 8, n) == 0                                    # empty
+    assert L.bfpq_stoc_widen_f16(one, odd, 64, n) == -1 and L.bfpq_stoc_widen_f16(n, n, 0, n) == 0                   # output not 16-byte aligned; empty
+    assert L.bfpq_int_quantize(one, one, 0, 4, 4, native.BF16, 8, n, n) == 0                                         # empty
+    assert L.bfpq_exp_window_host(3, one) == -1
+    assert L.bfpq_threshold_apply(one, far, 64, 3, one, n) == -1 and L.bfpq_select(one, 64, 3, 5, one, n) == -1     # bad dtype
+    assert L.bfpq_hbfp_linear_i8(one, one, one, one, n, one, 16, 256, 1024, 9, 3, 7, n) == -1                        # bad dtype
+    assert L.bfpq_hbfp_linear_i8(odd, one, one, one, n, one, 16, 256, 1024, native.BF16, 3, 7, n) == -1             # codes not 16-byte aligned
+    assert L.bfpq_hbfp_linear_i8(one, one, one, one, n, one, 16, 256, 200, native.BF16, 3, 7, n) == -2              # K % 256 != 0
+    assert L.bfpq_hbfp_linear_i8(one, one, one, one, n, one, 0, 256, 1024, native.BF16, 3, 7, n) == 0                # no tokens: ok
+    assert L.bfpq_hbfp_linear_i8_splitk(one, one, one, one, n, one, one, 0, 16, 256, 1024, native.BF16, 3, 7, n) == -1   # parts < 1
+    assert L.bfpq_hbfp_linear_i8_splitk(one, one, one, one, n, one, odd, 2, 16, 256, 1024, native.BF16, 3, 7, n) == -1   # slabs not aligned
+    assert L.bfpq_hbfp_linear_i8_splitk(one, one, one, one, n, one, one, 2, 0, 256, 1024, native.BF16, 3, 7, n) == 0     # no tokens: ok
+    assert L.bfpq_hbfp_linear_decode8(one, one, one, one, n, one, odd, 4, 256, 1024, native.BF16, 3, 7, n) == -1     # slabs not aligned
+    assert L.bfpq_hbfp_linear_decode8(one, one, one, one, n, one, one, 4, 256, 1024, 9, 3, 7, n) == -1               # bad dtype
+    assert L.bfpq_hbfp_linear_decode8(one, one, one, one, n, one, one, 4, 256, 1000, native.BF16, 3, 7, n) == -2     # K % 64 != 0
+    assert L.bfpq_hbfp_linear_decode8(one, one, one, one, n, one, one, 0, 256, 1024, native.BF16, 3, 7, n) == -1     # no tokens: refused
+    assert L.bfpq_hbfp_linear_decode(one, one, one, one, one, one, 4, 4096, 11008, 9, 3, 7, n) == -1                # bad dtype
+    assert L.bfpq_hbfp_linear_decode(one, one, one, one, one, one, 4, 100, 11008, native.BF16, 3, 7, n) == -2       # N % 16 != 0
+    assert L.bfpq_hbfp_linear_decode(one, one, one, one, one, n, 4, 4096, 11008, native.BF16, 3, 7, n) == -1        # no slabs
+    assert L.bfpq_hbfp_linear_decode(one, one, one, one, one, one, 0, 4096, 11008, native.BF16, 3, 7, n) == -1      # no tokens: refused
+    assert L.bfpq_hbfp_linear_decode_tiled(one, one, one, one, one, 0, 4096, 11008, native.BF16, 3, 7, n) == -1     # no tokens: refused
+    assert L.bfpq_hbfp_linear_decode_tiled(one, one, one, one, one, 4, 4096, 11008, 9, 3, 7, n) == -1               # bad dtype
+    assert L.bfpq_hbfp_linear_mx8_splitk(one, one, one, one, n, one, odd, 4, 8, 8, 256, native.BF16, n) == -1       # slabs not aligned
+    assert L.bfpq_hbfp_linear_mx8_splitk(one, one, one, one, n, one, one, 4, 8, 8, 256, 9, n) == -1                 # bad dtype
+    assert L.bfpq_hbfp_linear_mx8_splitk(one, one, one, one, n, one, one, 4, 0, 8, 256, native.BF16, n) == 0        # no tokens: ok
     assert L.bfpq_tune(0, 1024) == 0                   # the settings are process-wide: leave the default workgroup cap to the tests after this one
 
 
