@@ -355,6 +355,26 @@ int64_t bfpq_hbfp_linear_decode8_ws(int64_t T, int64_t N, int64_t K);
 int bfpq_hbfp_linear_decode8(const void* xcodes_dev, const int8_t* xexp_dev, const void* wcodes_dev, const int8_t* wexp_dev, const void* bias_dev,
                              void* out_dev, float* slabs_dev, int64_t T, int64_t N, int64_t K, int out_dtype,
                              int w_mant_bits, int x_mant_bits, void* stream);
+/* The same product with blocks of 16 or 32 (block_size; any other value: BFPQ_E_ARG, before anything touches the device).  Each block's
+ * dot product is one v_mfma_i32_16x16x32_i8 (block 16: the second half of K zero in the weight operand), |sum| <= 32 * 127^2 < 2^19,
+ * exact; the rescale, the NaN block marker, the block-order fp32 sum and the reproducibility are those of the block-64 entries above.
+ *   xexp_dev [T, K/block_size] int8, wexp_dev [N, K/block_size] int8; the rest as above.
+ * bfpq_hbfp_linear_i8b / _splitk (the LDS-tiled kernel, 256 of K = 8 or 16 blocks per trip): 1 == bfpq_hbfp_linear_i8b_ok(T, N, K,
+ * block_size) (0 for other blocks); codes and out 16-byte aligned, exponents 4-byte (block 32) or 8-byte (block 16) aligned.
+ * bfpq_hbfp_linear_i8b_parts: as bfpq_hbfp_linear_i8_parts.  bfpq_hbfp_linear_decode8b / _ws: the few-token kernel (any T >= 1,
+ * N % 16 == 0, K % 64 == 0), slabs as for bfpq_hbfp_linear_decode8. */
+int bfpq_hbfp_linear_i8b_ok(int64_t T, int64_t N, int64_t K, int block_size);
+int bfpq_hbfp_linear_i8b_parts(int64_t T, int64_t N, int64_t K, int block_size);
+int bfpq_hbfp_linear_i8b(const void* xcodes_dev, const int8_t* xexp_dev, const void* wcodes_dev, const int8_t* wexp_dev, const void* bias_dev,
+                         void* out_dev, int64_t T, int64_t N, int64_t K, int block_size, int out_dtype, int w_mant_bits, int x_mant_bits,
+                         void* stream);
+int bfpq_hbfp_linear_i8b_splitk(const void* xcodes_dev, const int8_t* xexp_dev, const void* wcodes_dev, const int8_t* wexp_dev,
+                                const void* bias_dev, void* out_dev, float* slabs_dev, int parts, int64_t T, int64_t N, int64_t K, int block_size,
+                                int out_dtype, int w_mant_bits, int x_mant_bits, void* stream);
+int64_t bfpq_hbfp_linear_decode8b_ws(int64_t T, int64_t N, int64_t K, int block_size);
+int bfpq_hbfp_linear_decode8b(const void* xcodes_dev, const int8_t* xexp_dev, const void* wcodes_dev, const int8_t* wexp_dev, const void* bias_dev,
+                              void* out_dev, float* slabs_dev, int64_t T, int64_t N, int64_t K, int block_size, int out_dtype,
+                              int w_mant_bits, int x_mant_bits, void* stream);
 /* 4-bit codes (two's-complement nibbles, low nibble first, as bfpq_quantize_nm writes them) -> int8 codes, so that HBFP4 weights
  * run on the entry points above; n_codes % 8 == 0, codes4_dev 4-byte and codes8_dev 8-byte aligned. */
 int bfpq_codes4_to_i8(const void* codes4_dev, void* codes8_dev, int64_t n_codes, void* stream);

@@ -425,16 +425,34 @@ def float_to_bfp_packed(t, mant_bits, block_size, epsilon=1e-8, N=0, M=0, first=
 DECODE_TOKENS = 64           # up to this many tokens: the decode kernel (4-bit codes), and the int8 unit ahead of the block-scaled one
 I8_MAX_TOKENS = 512          # 8-bit-code PackedBFPLinear: the int8 unit up to here; above, the other routes measured faster
 CACHED_MX8_MIN_TOKENS = 32   # the cached BFPLinear(matrix_unit=True) takes the block-scaled route from here on (a tile row)
+# blocks 16 and 32, by (block, activation dtype): PackedBFP.linear and PackedBFPLinear take the int8 unit up to this many tokens (None: any
+# number), measured against the fake route on the OPT-125m and ViT-L shapes (profiles/r06_i8gemm_b16.json / _b32.json): fp32 wins
+# at every measured count, bf16 up to 16 (block 16) / 197 (block 32) tokens; fp16 takes the bf16 limits, as does a dtype not listed
+I8_SMALL_BLOCK_MAX_TOKENS = {(16, torch.float32): None, (32, torch.float32): None,
+                             (16, torch.bfloat16): 16, (32, torch.bfloat16): 197, (16, torch.float16): 16, (32, torch.float16): 197}
+
+
+def i8_small_block_max_tokens(block_size, dtype):
+    """I8_SMALL_BLOCK_MAX_TOKENS of this block and activation dtype (dtype None or not listed: the bf16 entry)"""
+    return I8_SMALL_BLOCK_MAX_TOKENS.get((block_size, dtype), I8_SMALL_BLOCK_MAX_TOKENS[(block_size, torch.bfloat16)])
 
 
 def linear_route(T, N, K, code_bits, w_mant_bits, x_mant_bits, decode_tokens=DECODE_TOKENS, i8_max_tokens=0, mx8_min_tokens=1,
-                 block_size=64):
+                 block_size=64, dtype=None):
     """Which kernel runs F.linear(Q_in(x), W) for T tokens, W [N, K] packed with `code_bits`-bit codes: 'empty' (nothing to launch),
     'decode4' (PackedBFP.linear_decode), 'int8' (native.hbfp_linear_i8), 'mx8' (native.hbfp_linear_mx8) or 'fake' (the fake-quantised
     activation times the dequantised weight).  The consumer's options: decode_tokens; i8_max_tokens, up to how many tokens 8-bit codes
-    run on the int8 unit (0: never, None: no limit; past decode_tokens 'mx8' goes first); mx8_min_tokens (None: never 'mx8')."""
+    run on the int8 unit (0: never, None: no limit; past decode_tokens 'mx8' goes first); mx8_min_tokens (None: never 'mx8').
+    Blocks 16 and 32 have one matrix-unit route, the int8 unit (4-bit codes through their int8 expansion): i8_max_tokens=None takes it at
+    any token count (the cached forward, as at block 64), any other value up to i8_small_block_max_tokens(block_size, dtype), dtype being
+    the activation's; decode_tokens and mx8_min_tokens apply to block 64 only."""
     if T == 0:
         return 'empty'
+    if block_size in native.I8_BLOCKS:
+        lim = None if i8_max_tokens is None else i8_small_block_max_tokens(block_size, dtype)
+        if code_bits in (4, 8) and (lim is None or T <= lim) and native.hbfp_linear_i8_blocks_ok(T, N, K, w_mant_bits, x_mant_bits, block_size):
+            return 'int8'
+        return 'fake'
     if code_bits == 4 and block_size == 64 and T <= decode_tokens and N % 16 == 0 and K % 256 == 0:
         return 'decode4'
     mx8_allowed = code_bits in (4, 8) and mx8_min_tokens is not None and T >= mx8_min_tokens
@@ -448,6 +466,9 @@ def linear_route(T, N, K, code_bits, w_mant_bits, x_mant_bits, decode_tokens=DEC
     if mx8 is None:
         mx8 = mx8_allowed and native.hbfp_linear_mx8_ok(T, N, K, w_mant_bits, x_mant_bits, block_size)
     return 'mx8' if mx8 else 'fake'
+
+
+PACKED_BLOCKS = (64, 32, 16)  # the blocks PackedBFP.from_bfp_args packs (16 and 32 run on the int8 unit only)
 
 
 class PackedBFP:
@@ -485,12 +506,12 @@ class PackedBFP:
 
     @classmethod
     def from_bfp_args(cls, w, a, code_bits=None):
-        """the weight operand Q_w(w) of configuration `a` (unpacked bfp_args), packed: format 'bfp', block 64, mant_bits 1..7,
+        """the weight operand Q_w(w) of configuration `a` (unpacked bfp_args), packed: format 'bfp', block 64, 32 or 16, mant_bits 1..7,
         round-half-even; N:M pruning from the w_sparsity keys (order from `first`), unstructured pruning for first='s' (prune, then
         quantize: one fused launch writes the codes).  Configurations that cannot be packed (unstructured pruning after quantization,
         stochastic rounding) are refused.  code_bits: the code width, code_bits_for(mant_bits) by default."""
-        assert a['num_format'] == 'bfp' and a['sparsity_num_format'] == 'bfp' and a['block_size'] == 64 and 1 <= a['mant_bits'] <= 7, \
-            "a packed weight holds 4- or 8-bit codes: an HBFP config with block_size 64 and mant_bits <= 7 (HBFP2-HBFP8)"
+        assert a['num_format'] == 'bfp' and a['sparsity_num_format'] == 'bfp' and a['block_size'] in PACKED_BLOCKS and 1 <= a['mant_bits'] <= 7, \
+            "a packed weight holds 4- or 8-bit codes: an HBFP config with block_size 64, 32 or 16 and mant_bits <= 7 (HBFP2-HBFP8)"
         if a['w_sparsity'] and a['sparsity_mode'] == 'unstructured' and a['first'] != 's':
             raise ValueError("unstructured pruning AFTER quantization (first='q') is not packed")
         if a['w_sparsity'] and a['sparsity_mode'] not in ('structured', 'unstructured'):
@@ -498,9 +519,9 @@ class PackedBFP:
         if a['rounding_mode'] != 'determ':
             raise ValueError("a packed weight is quantized with round-half-even: rounding_mode must be 'determ'")
         if a['w_sparsity'] and a['sparsity_mode'] == 'unstructured':
-            return cls.quantize_unstructured(w, a['mant_bits'], 64, a['sparsity_frac'], a['epsilon'], code_bits)
+            return cls.quantize_unstructured(w, a['mant_bits'], a['block_size'], a['sparsity_frac'], a['epsilon'], code_bits)
         N, M = (a['N'], a['M']) if a['w_sparsity'] else (0, 0)                  # (structured: the other modes returned or raised above)
-        return cls.quantize(w, a['mant_bits'], 64, a['epsilon'], N, M, a['first'], code_bits)
+        return cls.quantize(w, a['mant_bits'], a['block_size'], a['epsilon'], N, M, a['first'], code_bits)
 
     def dequantize(self, out=None):
         """== the reference's fake-quantised tensor (a -0.0 there is +0.0 here)"""
@@ -536,7 +557,8 @@ class PackedBFP:
         one unstructured threshold over ALL tokens of the call)."""
         K = self.shape[-1]
         T = x.numel() // K if K else 0
-        route = linear_route(T, self.shape[0], K, self.code_bits, self.mant_bits, x_mant_bits, decode_tokens, block_size=self.block_size)
+        route = linear_route(T, self.shape[0], K, self.code_bits, self.mant_bits, x_mant_bits, decode_tokens, block_size=self.block_size,
+                             dtype=x.dtype)
         return self._run_linear(route, x, bias, x_mant_bits, epsilon, x_sparsity)
 
     def _run_linear(self, route, x, bias, x_mant_bits, epsilon, x_sparsity):
@@ -556,24 +578,25 @@ class PackedBFP:
             xq = None if x_sparsity is None else native.act_codes(x2, x_mant_bits, epsilon, x_sparsity)   # (all tokens: one threshold)
             out = self.linear_decode(x2, x_mant_bits, epsilon, xq=xq)
         else:
-            out = F.linear(_act_fake_quant(x2, x_mant_bits, epsilon, x_sparsity), self.dequantize().to(x.dtype))
+            out = F.linear(_act_fake_quant(x2, x_mant_bits, epsilon, x_sparsity, self.block_size), self.dequantize().to(x.dtype))
         if bias is not None:
             out = out + bias
         return out.view(lead + (N,))
 
     def linear_i8(self, x, bias=None, x_mant_bits=7, epsilon=1e-8, x_sparsity=None):
         """F.linear(Q_in(x), W_packed, bias) for any number of tokens on the int8 matrix unit (native.hbfp_linear_i8): self is W [N, K]
-        with 4- or 8-bit codes, block 64, mant_bits 1..7; activations HBFP(x_mant_bits + 1), x_mant_bits 1..7, block 64,
-        round-half-even, pruned by x_sparsity (native.ActSparsity or None) as in linear().  Every block product is an exact integer
+        with 4- or 8-bit codes, block 64, 32 or 16, mant_bits 1..7; activations HBFP(x_mant_bits + 1), x_mant_bits 1..7, the weight's
+        block, round-half-even, pruned by x_sparsity (native.ActSparsity or None) as in linear().  Every block product is an exact integer
         sum, fp32 across blocks.  4-bit codes are expanded to int8 codes once per device (kept with the weight)."""
-        assert self.code_bits in (4, 8) and self.block_size == 64 and len(self.shape) == 2, \
-            "linear_i8 takes a 2-D weight with 4- or 8-bit codes and block 64"
+        assert self.code_bits in (4, 8) and self.block_size in PACKED_BLOCKS and len(self.shape) == 2, \
+            "linear_i8 takes a 2-D weight with 4- or 8-bit codes and block 64, 32 or 16"
         N, K = self.shape
         lead = x.shape[:-1]
         x2 = x.reshape(-1, K)
         if x2.shape[0] == 0:
             return x.new_zeros(lead + (N,))
-        out = native.hbfp_linear_i8(x2, self._i8_codes(), self.exps, self.mant_bits, x_mant_bits, epsilon, bias=bias, act=x_sparsity)
+        out = native.hbfp_linear_i8(x2, self._i8_codes(), self.exps, self.mant_bits, x_mant_bits, epsilon, bias=bias, act=x_sparsity,
+                                    block_size=self.block_size)
         return out.view(lead + (N,))
 
     def _i8_codes(self):
@@ -621,11 +644,11 @@ class PackedBFP:
                    int(meta["block_size"]), int(meta["code_bits"]))
 
 
-def _act_fake_quant(x, mant_bits, epsilon, act=None):
-    """the reference's activation operand: float_to_bfp_blocked(x, identifier='in') with HBFP(mant_bits + 1), block 64,
+def _act_fake_quant(x, mant_bits, epsilon, act=None, block_size=64):
+    """the reference's activation operand: float_to_bfp_blocked(x, identifier='in') with HBFP(mant_bits + 1), blocks of block_size,
     round-half-even, pruned as the ActSparsity spec `act` says (None: dense)"""
     mode, N, M, frac, first = act if act is not None else ('structured', 0, 0, 0.0, 's')
-    return float_to_bfp_blocked(x, mant_bits=mant_bits, epsilon=epsilon, rounding_mode=rounding_modes.DETERM, device=str(x.device), block_size=64,
+    return float_to_bfp_blocked(x, mant_bits=mant_bits, epsilon=epsilon, rounding_mode=rounding_modes.DETERM, device=str(x.device), block_size=block_size,
                                 num_format='bfp', weight_mant_bits=0, in_sparsity=act is not None, w_sparsity=False, grad_sparsity=False,
                                 sparsity_frac=frac, N=N, M=M, sparsity_num_format='bfp', first=first, sparsity_mode=mode, identifier='in')
 
@@ -737,7 +760,7 @@ class WeightCache:
         return self.image
 
     def weight_codes_i8(self, w, bfp_args):
-        """int8 codes [N, K] + int8 exponents [N, K/64] of Q_w(w) for the int8 matrix unit (matrix_unit='int8'), kept under the same key"""
+        """int8 codes [N, K] + int8 exponents [N, K/block] of Q_w(w) for the int8 matrix unit (matrix_unit='int8'), kept under the same key"""
         key = self._key(w, bfp_args)
         if self.image_key != key:
             pk = PackedBFP.from_bfp_args(w.detach(), bfp_args, code_bits=8)
@@ -816,10 +839,11 @@ def _cached_route(x, w, a, cache):
     """linear_route of the cached Linear forward; anything but 'int8' or 'mx8' means the fake-quantize path.  matrix_unit=True: the
     block-scaled matrix instruction on the weight's e4m3 + E8M0 image (<= 4 mantissa bits, exact in e4m3; K % 256 == 0; from
     CACHED_MX8_MIN_TOKENS tokens, a tile row).  matrix_unit='int8': the int8 matrix instruction on its int8 codes (1..7 mantissa bits, any
-    number of tokens, N % 16 == 0, K % 64 == 0).  Both need HBFP block 64, round-half-even, dense or pruned activations (structured with
+    number of tokens, N % 16 == 0, K % 64 == 0; blocks 64, 32 and 16 alike).  Both need HBFP block 64 (or, for 'int8', 32 or 16), round-half-even, dense or pruned activations (structured with
     0 < N <= M, or unstructured), dense, N:M or prune-first unstructured weights and a 2-D weight."""
     int8 = cache.matrix_unit == 'int8'
-    if (a['num_format'] != 'bfp' or a['sparsity_num_format'] != 'bfp' or a['block_size'] != 64 or not (1 <= a['mant_bits'] <= (7 if int8 else 4))
+    block_ok = a['block_size'] == 64 or (int8 and a['block_size'] in native.I8_BLOCKS)
+    if (a['num_format'] != 'bfp' or a['sparsity_num_format'] != 'bfp' or not block_ok or not (1 <= a['mant_bits'] <= (7 if int8 else 4))
             or a['rounding_mode'] != rounding_modes.DETERM or w.dim() != 2 or x.device.type != 'cuda'
             or torch.compiler.is_compiling() or not cache.usable(w, a)):
         return 'fake'
@@ -838,7 +862,7 @@ def _cached_route(x, w, a, cache):
     K, m = x.shape[-1], a['mant_bits']
     T = x.numel() // K if K else 0
     if int8:
-        return linear_route(T, w.shape[0], K, 8, m, m, decode_tokens=0, i8_max_tokens=None, mx8_min_tokens=None)
+        return linear_route(T, w.shape[0], K, 8, m, m, decode_tokens=0, i8_max_tokens=None, mx8_min_tokens=None, block_size=a['block_size'])
     return linear_route(T, w.shape[0], K, code_bits_for(m), m, m, decode_tokens=0, mx8_min_tokens=CACHED_MX8_MIN_TOKENS)
 
 
@@ -853,7 +877,8 @@ def _gen_bfp_op(op, name, bfp_args, transpose=False, cache=None):
                 m, eps, act = bfp_args['mant_bits'], bfp_args['epsilon'], native.ActSparsity.from_bfp_args(bfp_args)
                 if route == 'int8':
                     cache.i8_calls += 1
-                    return native.hbfp_linear_i8(x, *cache.weight_codes_i8(w, bfp_args), m, m, eps, bias=bias, act=act)
+                    return native.hbfp_linear_i8(x, *cache.weight_codes_i8(w, bfp_args), m, m, eps, bias=bias, act=act,
+                                                 block_size=bfp_args['block_size'])
                 cache.mx_calls += 1
                 return native.hbfp_linear_mx8(x, *cache.weight_image(w, bfp_args), m, eps, bias=bias, act=act)
             xq, wq = _quantize_operands(x, w, transpose, bfp_args, cache)
@@ -912,8 +937,8 @@ class _BFPModule:
         runs the Linear itself on the block-scaled matrix instruction where the configuration allows (HBFP4-class, block 64,
         >= 32 tokens): the same block products, summed exactly inside a block and in fp32 across blocks instead of by the bf16
         library GEMM -- results agree with F.linear on the fake-quantised operands up to that summation order.  matrix_unit='int8' runs it
-        instead on the int8 matrix instruction for HBFP up to 8 bits (block 64, mant_bits 1..7, any number of tokens, N % 16 == 0 and
-        K % 64 == 0; WeightCache.i8_calls counts these calls).  Any other value raises ValueError."""
+        instead on the int8 matrix instruction for HBFP up to 8 bits (block 64, 32 or 16, mant_bits 1..7, any number of tokens,
+        N % 16 == 0 and K % 64 == 0; WeightCache.i8_calls counts these calls).  Any other value raises ValueError."""
         cache = WeightCache(self, matrix_unit=matrix_unit) if enabled else None
         self._weight_cache = cache                               # (patch.prime_weight_caches fills it for a whole model in one list call)
         op = _get_bfp_op(self._functional, self._op_name, self.bfp_args, cache=cache)

@@ -83,6 +83,12 @@ PROTOTYPES = {
     "bfpq_hbfp_linear_decode8_ws": (_i64, [_i64, _i64, _i64]),
     "bfpq_hbfp_linear_decode8": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp]),
     "bfpq_codes4_to_i8": (_i32, [_vp, _vp, _i64, _vp]),
+    "bfpq_hbfp_linear_i8b_ok": (_i32, [_i64, _i64, _i64, _i32]),
+    "bfpq_hbfp_linear_i8b_parts": (_i32, [_i64, _i64, _i64, _i32]),
+    "bfpq_hbfp_linear_i8b": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "bfpq_hbfp_linear_i8b_splitk": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "bfpq_hbfp_linear_decode8b_ws": (_i64, [_i64, _i64, _i64, _i32]),
+    "bfpq_hbfp_linear_decode8b": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
 }
 
 
@@ -955,25 +961,26 @@ def _prune_count(t, frac):
     return k
 
 
-def act_codes(x, mant_bits, epsilon, act, codes_out=None, exps_out=None):
-    """int8 codes [T, K] + int8 exponents [T, K/64] of the activation x [T, K], HBFP(mant_bits + 1) block 64, pruned by `act`
-    (ActSparsity or None) -- the operands of the decode kernels.  Unstructured pruning picks ONE threshold over all of x."""
+def act_codes(x, mant_bits, epsilon, act, codes_out=None, exps_out=None, block_size=64):
+    """int8 codes [T, K] + int8 exponents [T, K/block_size] of the activation x [T, K], HBFP(mant_bits + 1) with blocks of block_size
+    (64 for the decode kernels; 16 or 32 for hbfp_linear_i8 at those blocks), pruned by `act` (ActSparsity or None).  Unstructured
+    pruning picks ONE threshold over all of x."""
     T, K = x.shape
     dev = x.device
     if act is None or act.mode == 'structured':
         N, M = (act.N, act.M) if act is not None else (0, 0)
-        _, c, e = quantize_nm(x, 64, mant_bits, epsilon, N=N, M=M, sparsify_first=(act is None or act.first == 's'), want_deq=False,
+        _, c, e = quantize_nm(x, block_size, mant_bits, epsilon, N=N, M=M, sparsify_first=(act is None or act.first == 's'), want_deq=False,
                               code_bits=8, want_exp=True, codes_out=codes_out, exps_out=exps_out)
         return c, e
     k = _prune_count(x, act.frac)
     ws = _act_workspace(dev)
     if act.first == 's':
         select_threshold(x, k, ws)
-        _, c, e = quantize_threshold(x, ws, 64, mant_bits, epsilon, want_deq=False, code_bits=8, want_exp=True)
+        _, c, e = quantize_threshold(x, ws, block_size, mant_bits, epsilon, want_deq=False, code_bits=8, want_exp=True)
     else:
         # S(Q(x)): quantize (the tensor and its codes at once), select over the quantized tensor, prune it; a pruned element's code is
         # zeroed -- the exponents stay those of Q(x), so nothing depends on re-quantizing the pruned tensor
-        q, c, e = quantize_nm(x, 64, mant_bits, epsilon, code_bits=8, want_exp=True)
+        q, c, e = quantize_nm(x, block_size, mant_bits, epsilon, code_bits=8, want_exp=True)
         select_threshold(q, k, ws)
         sq = threshold_apply(q, ws).view(T, K)
         c = torch.where(sq == 0, torch.zeros((), dtype=c.dtype, device=dev), c)
@@ -1112,6 +1119,16 @@ def hbfp_linear_i8_ok(T, N, K, w_mant_bits, x_mant_bits, block_size=64):
             and K >= 64 and K % 64 == 0 and load_library().bfpq_hbfp_linear_decode8_ws(T, N, K) >= 0)
 
 
+I8_BLOCKS = (16, 32)      # the blocks besides 64 that hbfp_linear_i8 runs (one v_mfma_i32_16x16x32_i8 per block)
+
+
+def hbfp_linear_i8_blocks_ok(T, N, K, w_mant_bits, x_mant_bits, block_size):
+    """hbfp_linear_i8 takes this problem at block 16 or 32: mantissas of 1..7 bits on both sides, N % 16 == 0, K % 64 == 0 (the tiled
+    kernel needs K % 256 == 0; other K go to the decode-shaped kernel at any token count)"""
+    return (block_size in I8_BLOCKS and 1 <= w_mant_bits <= 7 and 1 <= x_mant_bits <= 7 and T >= 1 and N >= 16 and N % 16 == 0
+            and K >= 64 and K % 64 == 0 and load_library().bfpq_hbfp_linear_decode8b_ws(T, N, K, block_size) >= 0)
+
+
 def codes4_to_i8(codes4, n_codes):
     """4-bit packed codes (two's-complement nibbles, low first) -> int8 codes [n_codes] (bfpq_codes4_to_i8)"""
     require_device_tensor_any(codes4)
@@ -1123,36 +1140,44 @@ def codes4_to_i8(codes4, n_codes):
     return out
 
 
-def hbfp_linear_i8(x, wcodes8, wexps, w_mant_bits, x_mant_bits, epsilon=1e-8, bias=None, out_dtype=None, act=None, xq=None):
-    """out = Q(x) @ W^T (+ bias) for any number of tokens with W packed as int8 codes [N, K] + int8 exponents [N, K/64] (block 64,
-    w_mant_bits 1..7) and x quantized to HBFP(x_mant_bits + 1) block 64 (x_mant_bits 1..7, round-half-even), pruned by `act`
-    (ActSparsity or None; unstructured: one threshold over all tokens of the call).  Block dot products are exact integer sums on the
-    int8 matrix unit, fp32 across blocks in block order.  xq: the activation operand made beforehand (act_codes); x then only gives
-    shape and dtype."""
+def hbfp_linear_i8(x, wcodes8, wexps, w_mant_bits, x_mant_bits, epsilon=1e-8, bias=None, out_dtype=None, act=None, xq=None, block_size=64):
+    """out = Q(x) @ W^T (+ bias) for any number of tokens with W packed as int8 codes [N, K] + int8 exponents [N, K/block_size]
+    (w_mant_bits 1..7) and x quantized to HBFP(x_mant_bits + 1) with the same blocks (x_mant_bits 1..7, round-half-even), pruned by
+    `act` (ActSparsity or None; unstructured: one threshold over all tokens of the call).  block_size 64, 32 or 16.  Block dot products
+    are exact integer sums on the int8 matrix unit, fp32 across blocks in block order.  xq: the activation operand made beforehand
+    (act_codes with the same block_size); x then only gives shape and dtype."""
     require_device_tensor(x)
     L = load_library()
     K = x.shape[-1]
     T = x.numel() // K
     N = wexps.shape[0]
-    if not hbfp_linear_i8_ok(T, N, K, w_mant_bits, x_mant_bits):
-        raise ValueError(f"hbfp_linear_i8 needs N % 16 == 0, K % 64 == 0 and mantissas of 1..7 bits "
-                         f"(got T={T}, N={N}, K={K}, w_mant_bits={w_mant_bits}, x_mant_bits={x_mant_bits})")
+    small = block_size != 64
+    if not (hbfp_linear_i8_blocks_ok(T, N, K, w_mant_bits, x_mant_bits, block_size) if small else hbfp_linear_i8_ok(T, N, K, w_mant_bits, x_mant_bits)):
+        raise ValueError(f"hbfp_linear_i8 needs block 16, 32 or 64, N % 16 == 0, K % 64 == 0 and mantissas of 1..7 bits "
+                         f"(got T={T}, N={N}, K={K}, w_mant_bits={w_mant_bits}, x_mant_bits={x_mant_bits}, block_size={block_size})")
     if wcodes8.dtype != torch.int8 or wcodes8.numel() != N * K:
         raise ValueError("hbfp_linear_i8 takes int8 weight codes [N, K] (4-bit codes: codes4_to_i8 first)")
+    nb = K // block_size
+    if wexps.numel() != N * nb or (xq is not None and (xq[0].numel() != T * K or xq[1].numel() != T * nb)):
+        raise ValueError(f"hbfp_linear_i8 at block {block_size} takes exponents [N, K/{block_size}] = [{N}, {nb}] and an activation operand "
+                         f"[T, K] + [T, K/{block_size}] (got {tuple(wexps.shape)}"
+                         + ("" if xq is None else f", {tuple(xq[0].shape)} + {tuple(xq[1].shape)}") + ")")
     dev = x.device
     out_dtype = out_dtype or x.dtype
     with torch.cuda.device(dev):
         if xq is not None:
             xc, xe = xq[0].contiguous(), xq[1].contiguous()
         else:
-            xc, xe = act_codes(x.reshape(T, K), x_mant_bits, epsilon, act)
+            xc, xe = act_codes(x.reshape(T, K), x_mant_bits, epsilon, act, block_size=block_size)
         wc, we = wcodes8.contiguous(), wexps.contiguous()
         out = torch.empty((T, N), dtype=out_dtype, device=dev)
         if bias is not None:
             bias = bias.to(out_dtype).contiguous()
         bp = _ptr(bias) if bias is not None else None
         args = (int(w_mant_bits), int(x_mant_bits), _stream(x))
-        if T > DECODE8_TOKENS and L.bfpq_hbfp_linear_i8_ok(T, N, K):
+        if small:
+            _i8_small_blocks(L, xc, xe, wc, we, bp, out, T, N, K, int(block_size), DTYPE_CODE[out_dtype], args)
+        elif T > DECODE8_TOKENS and L.bfpq_hbfp_linear_i8_ok(T, N, K):
             parts = L.bfpq_hbfp_linear_i8_parts(T, N, K) if SPLIT_K else 1
             if parts > 1:                                              # few output tiles: K split, fp32 slabs added in part order
                 slabs = torch.empty((parts, T, N), dtype=torch.float32, device=dev)
@@ -1166,3 +1191,21 @@ def hbfp_linear_i8(x, wcodes8, wexps, w_mant_bits, x_mant_bits, epsilon=1e-8, bi
             check(L.bfpq_hbfp_linear_decode8(_ptr(xc), _ptr(xe), _ptr(wc), _ptr(we), bp, _ptr(out), _ptr(slabs), T, N, K,
                                              DTYPE_CODE[out_dtype], *args), "bfpq_hbfp_linear_decode8")
     return out.view(tuple(x.shape[:-1]) + (N,))
+
+
+def _i8_small_blocks(L, xc, xe, wc, we, bp, out, T, N, K, block, dt, args):
+    """the launches of hbfp_linear_i8 at block 16 or 32: the tile kernel past DECODE8_TOKENS tokens where K % 256 == 0 (K split when
+    the plan asks for it), else the decode-shaped kernel"""
+    dev = out.device
+    if T > DECODE8_TOKENS and L.bfpq_hbfp_linear_i8b_ok(T, N, K, block):
+        parts = L.bfpq_hbfp_linear_i8b_parts(T, N, K, block) if SPLIT_K else 1
+        if parts > 1:
+            slabs = torch.empty((parts, T, N), dtype=torch.float32, device=dev)
+            check(L.bfpq_hbfp_linear_i8b_splitk(_ptr(xc), _ptr(xe), _ptr(wc), _ptr(we), bp, _ptr(out), _ptr(slabs), parts, T, N, K, block, dt,
+                                                *args), "bfpq_hbfp_linear_i8b_splitk")
+        else:
+            check(L.bfpq_hbfp_linear_i8b(_ptr(xc), _ptr(xe), _ptr(wc), _ptr(we), bp, _ptr(out), T, N, K, block, dt, *args), "bfpq_hbfp_linear_i8b")
+    else:
+        slabs = torch.empty(int(L.bfpq_hbfp_linear_decode8b_ws(T, N, K, block)), dtype=torch.float32, device=dev)
+        check(L.bfpq_hbfp_linear_decode8b(_ptr(xc), _ptr(xe), _ptr(wc), _ptr(we), bp, _ptr(out), _ptr(slabs), T, N, K, block, dt, *args),
+              "bfpq_hbfp_linear_decode8b")

@@ -72,6 +72,8 @@ class PackedBFPLinear(torch.nn.Module):
     block-scaled matrix instruction or the library GEMM).  HBFP5-HBFP8 (mant_bits 4..7): 8-bit codes (1.016 B per weight), run by
     PackedBFP.linear_i8 on the int8 matrix instruction up to bfp_ops.I8_MAX_TOKENS tokens; more than 64 tokens of HBFP5, more tokens
     and shapes the int8 unit does not take run PackedBFP.linear's routes (bfp_ops.linear_route picks the route of every forward).
+    HBFP blocks of 32 or 16 (4- or 8-bit codes) run on the int8 matrix instruction up to bfp_ops.i8_small_block_max_tokens(block, x.dtype)
+    tokens (any number for fp32 activations).
     The codes and exponents are registered buffers (`codes`, `exps`): they follow .to() / .cuda(), appear in state_dict()
     and load back with load_state_dict(); shape / dtype / mantissa width / activation pruning travel as extra state.
     x_sparsity (native.ActSparsity or None): the activations are pruned as the reference's in_sparsity does."""
@@ -111,7 +113,7 @@ class PackedBFPLinear(torch.nn.Module):
 
     @classmethod
     def from_linear(cls, lin, bfp_args):
-        """weight -> PackedBFP.from_bfp_args with the module's config (format 'bfp', block 64, mant_bits 1..7 -- 4-bit codes up to 3,
+        """weight -> PackedBFP.from_bfp_args with the module's config (format 'bfp', block 64, 32 or 16, mant_bits 1..7 -- 4-bit codes up to 3,
         8-bit codes from 4 --, round-half-even, N:M or prune-first unstructured weight pruning); activations use mant_bits of the same
         config.  Pruned activations (in_sparsity: N:M or unstructured, either order, the same keys) are pruned in every forward, as the
         reference does.  Configurations this module cannot reproduce (unstructured WEIGHT pruning after quantization, stochastic
@@ -125,7 +127,7 @@ class PackedBFPLinear(torch.nn.Module):
         N, K = p.shape
         T = x.numel() // K if K else 0
         route = bfp_ops.linear_route(T, N, K, p.code_bits, p.mant_bits, self.x_mant_bits, i8_max_tokens=bfp_ops.I8_MAX_TOKENS,
-                                     block_size=p.block_size)
+                                     block_size=p.block_size, dtype=x.dtype)
         return p._run_linear(route, x, self.bias, self.x_mant_bits, self.epsilon, self.x_sparsity)
 
     def extra_repr(self):
@@ -136,10 +138,11 @@ class PackedBFPLinear(torch.nn.Module):
 def pack_linear_layers(model, bfp_args, skip=("lm_head", "classifier", "score")):
     """Inference deployment: replace nn.Linear / BFPLinear children by PackedBFPLinear (weights quantized once and
     held as 4-bit codes for mant_bits <= 3, 8-bit codes for 4..7; the original bf16/fp16 weight is dropped).  Needs an HBFP config with
-    block_size 64 and mant_bits <= 7 (+ optional N:M or unstructured pruning).  Returns the patched names and the bytes saved."""
+    block_size 64, 32 or 16 and mant_bits <= 7 (+ optional N:M or unstructured pruning).  Returns the patched names and the bytes saved."""
     patched, saved = [], 0
     a = bfp_ops.unpack_bfp_args(dict(bfp_args))
-    k_mult = 256 if bfp_ops.code_bits_for(a['mant_bits']) == 4 else 64     # 8-bit codes run at any K % 64 == 0 (PackedBFP.linear_i8)
+    # 8-bit codes, and every code width at blocks 16 / 32, run at any K % 64 == 0 (PackedBFP.linear_i8)
+    k_mult = 256 if bfp_ops.code_bits_for(a['mant_bits']) == 4 and a['block_size'] == 64 else 64
     for parent_name, parent in list(model.named_modules()):
         for child_name, child in list(parent.named_children()):
             full = f"{parent_name}.{child_name}" if parent_name else child_name
