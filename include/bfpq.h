@@ -201,7 +201,9 @@ int bfpq_select_reset(void* ws_dev, void* stream);
 int bfpq_threshold_apply(const void* in_dev, void* out_dev, int64_t numel, int dtype, void* ws_dev, void* stream);
 /* step 3 fused with the quantizer: out = Q(S_threshold(in)) in one pass over the tensor (first == 's',
  * bfp_ops.py:141-144 with sparsity_mode 'unstructured'); same outputs / tables / fallbacks as
- * bfpq_quantize_nm (scratch_dev only when the shape needs the two-launch path and out_deq_dev is NULL). */
+ * bfpq_quantize_nm (scratch_dev only when the shape needs the two-launch path and out_deq_dev is NULL).  Not in place: in_dev == out_deq_dev
+ * or in_dev == out_codes_dev returns BFPQ_E_ARG before any launch (the workgroups of the cut re-read in_dev to rank the ties while
+ * other workgroups write their pruned tiles), as bfpq_threshold_apply and bfpq_prune_quantize refuse in == out. */
 int bfpq_quantize_threshold(const void* in_dev, void* out_deq_dev, void* out_codes_dev, int8_t* out_exp_dev,
                             int64_t rows, int64_t cols, int dtype, int block_size, int mant_bits, double epsilon,
                             int code_bits, uint64_t stoch_seed, const uint8_t* exp_win_dev,

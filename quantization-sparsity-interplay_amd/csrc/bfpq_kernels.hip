@@ -932,6 +932,7 @@ int bfpq_quantize_threshold(const void* in, void* out_deq, void* out_codes, int8
     if (!dtype_ok(dtype) || rows < 0 || cols < 0 || block_size <= 0) return BFPQ_E_ARG;
     if (rows * cols == 0) return 0;
     if (!in || !ws || !exp_win || (!out_deq && !out_codes && !out_exp)) return BFPQ_E_ARG;
+    if (in == out_deq || in == out_codes) return BFPQ_E_ARG;       // (cut workgroups re-read `in` to rank ties while other tiles are written)
     if (mant_bits < 0 || mant_bits > 23) return BFPQ_E_ARG;
     if (out_codes && !(code_bits == 4 || code_bits == 8 || code_bits == 16)) return BFPQ_E_ARG;
     if (out_codes && !codes_fit(code_bits, mant_bits)) return BFPQ_E_ARG;

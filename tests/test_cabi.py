@@ -85,6 +85,9 @@ def test_argument_validation_without_gpu():
     assert L.bfpq_quantize_threshold(one, one, n, n, 4, 64, 9, 64, 3, 1e-8, 0, 0, one, one, n, n) == -1              # bad dtype
     assert L.bfpq_quantize_threshold(one, one, one, n, 4, 64, native.BF16, 64, 7, 1e-8, 4, 0, one, one, n, n) == -1   # 4-bit codes, 7-bit mantissa
     assert L.bfpq_quantize_threshold(one, one, n, n, 0, 64, native.BF16, 64, 3, 1e-8, 0, 0, one, one, n, n) == 0      # empty
+    assert L.bfpq_quantize_threshold(one, one, n, n, 4, 64, native.BF16, 64, 3, 1e-8, 0, 0, one, one, n, n) == -1     # in place (deq): refused
+    assert L.bfpq_quantize_threshold(one, far, one, n, 4, 64, native.BF16, 64, 3, 1e-8, 8, 0, one, one, n, n) == -1   # in place (codes): refused
+    assert L.bfpq_quantize_threshold(one, n, one, one, 4, 64, native.F32, 64, 3, 1e-8, 8, 0, one, one, n, n) == -1    # in place, codes only: refused
     assert L.bfpq_quantize_mx8(odd, one, one, 4, 64, native.BF16, 3, 1e-8, one, n) == -2                             # input not 16-byte aligned
     assert L.bfpq_quantize_mx8_nm(one, far, far, 4, 64, 9, 3, 1e-8, 2, 4, 1, one, one, n) == -1                      # bad dtype
     assert L.bfpq_quantize_mx8_nm(one, far, far, 4, 64, native.BF16, 3, 1e-8, 2, 65, 1, one, one, n) == -2           # M > 64

@@ -14,6 +14,7 @@ from quantization_sparsity_interplay_amd.bfp import bfp_ops
 from util import DT, load, from_bits, bits, assert_bits_equal
 from gen import int_bits_tensor
 import gemm_cases
+from unstructured_ref import flat_order_prune as _flat_order_prune
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -1061,30 +1062,6 @@ def test_dist_paths_with_the_native_engine_on_rccl():
         assert torch.equal(codes, c1) and torch.equal(exps, e1)
     finally:
         dist.destroy_process_group()
-
-
-def _flat_order_prune(xc, frac):
-    """the engine's own rule, restated in numpy: everything below the k-th smallest magnitude, plus the first `need`
-    elements EQUAL to it in flat index order (NaNs form one largest class, as in ATen's comparator)"""
-    dt = xc.dtype
-    if dt == torch.float32:
-        keys = xc.contiguous().view(torch.int32).numpy().reshape(-1).astype(np.int64) & 0x7FFFFFFF
-        inf = 0x7F800000
-    else:
-        keys = xc.contiguous().view(torch.int16).numpy().view(np.uint16).reshape(-1).astype(np.int64) & 0x7FFF
-        inf = 0x7F80 if dt == torch.bfloat16 else 0x7C00
-    keys = np.minimum(keys, inf + 1)
-    k = int(xc.numel() * frac)
-    out = xc.contiguous().view(-1).clone()
-    if k == 0:
-        return out.view(xc.shape)
-    tau = np.partition(keys, k - 1)[k - 1]
-    below = keys < tau
-    eq = keys == tau
-    need = k - int(below.sum())
-    rank = np.cumsum(eq) - 1
-    out[torch.from_numpy(below | (eq & (rank < need)))] = 0
-    return out.view(xc.shape)
 
 
 @pytest.mark.parametrize("dname", ["bf16", "f16", "f32"])
