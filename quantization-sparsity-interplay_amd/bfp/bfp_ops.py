@@ -450,7 +450,7 @@ def linear_route(T, N, K, code_bits, w_mant_bits, x_mant_bits, decode_tokens=DEC
         return 'empty'
     if block_size in native.I8_BLOCKS:
         lim = None if i8_max_tokens is None else i8_small_block_max_tokens(block_size, dtype)
-        if code_bits in (4, 8) and (lim is None or T <= lim) and native.hbfp_linear_i8_blocks_ok(T, N, K, w_mant_bits, x_mant_bits, block_size):
+        if code_bits in (4, 8) and (lim is None or T <= lim) and native.hbfp_linear_i8_ok(T, N, K, w_mant_bits, x_mant_bits, block_size):
             return 'int8'
         return 'fake'
     if code_bits == 4 and block_size == 64 and T <= decode_tokens and N % 16 == 0 and K % 256 == 0:

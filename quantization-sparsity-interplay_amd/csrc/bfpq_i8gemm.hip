@@ -20,17 +20,15 @@
 // l & 15, same k; D lane l holds rows 4 (l >> 4) + j (j = 0..3) of column l & 15.  A = weight rows, B = tokens, so a lane's four results
 // are four consecutive output features of one token (one 8- or 16-byte store).
 //
-// Kernels:
-//   k_i8_gemm     prefill tile: WM x WN waves, each TM x TN instruction tiles; K staged global -> LDS by 16-byte LDS-DMA, two LDS
-//                 stages of two blocks each (double buffered: the next stage's DMA is in flight during the current stage's matrix
-//                 work), LDS rows of 128 bytes with the 16-byte slot XOR-swizzled by ((row >> 1) & 7).  K % 256 == 0 (the block
-//                 exponents are read one dword = 4 blocks per trip).  SPLIT: part p of K goes to fp32 slab p (plain stores) and
-//                 k_slab_reduce (bfpq_common.h) adds the slabs in part order.
-//   k_i8_decode   few tokens: a wave owns 16 output features x up to 16 tokens x a slice of K (any K % 64 == 0), slabs reduced as above.
+// Kernels (BLK = 64, 32 or 16; blocks 16 and 32 serve bfpq_hbfp_linear_i8b* and bfpq_hbfp_linear_decode8b*):
+//   k_i8_gemm<BLK>  prefill tile: WM x WN waves, each TM x TN instruction tiles; K staged global -> LDS by 16-byte LDS-DMA, two LDS
+//                 stages of 128 bytes of K each (double buffered: the next stage's DMA is in flight during the current stage's matrix
+//                 work), LDS rows of 128 bytes with the 16-byte slot XOR-swizzled by ((row >> 1) & 7).  K % 256 == 0.  Block 64 reads
+//                 its exponents one dword = 4 blocks per trip ahead, blocks 16 / 32 one stage (4 or 8 blocks) ahead.  SPLIT: part p of
+//                 K goes to fp32 slab p (plain stores) and k_slab_reduce (bfpq_common.h) adds the slabs in part order.
+//   k_i8_decode<BLK>  few tokens: a wave owns 16 output features x up to 16 tokens x a slice of K (any K % 64 == 0), slabs reduced as above.
 //   k_codes4_to_i8  4-bit two's-complement nibbles (low first) -> int8 codes.
-//   k_i8_gemm_sb, k_i8_decode_sb  the same two kernels for blocks of 16 and 32 (bfpq_hbfp_linear_i8b*, bfpq_hbfp_linear_decode8b*): one
-//                 v_mfma_i32_16x16x32_i8 per block (block 16: half of K zero in A), 8-byte operands read from the same LDS stages, the
-//                 tile's exponents read one stage (128 of K = 4 or 8 blocks) ahead; block-64 kernels and entries unchanged.
+// Blocks 16 and 32 take one v_mfma_i32_16x16x32_i8 per block (I8Blk below), 8-byte operands read from the same LDS stages.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "bfpq.h"
@@ -58,299 +56,93 @@ __device__ __forceinline__ v4i read16(const uint8_t* tile, int row, int c)      
     return *reinterpret_cast<const v4i*>(tile + row * BK + ((c ^ ((row >> 1) & 7)) << 4));
 }
 
-template <int WM, int WN, int TM, int TN>
-struct I8Cfg {
-    static constexpr int NW = WM * WN, BN = 16 * WM * TM, BT = 16 * WN * TN, STAGE = (BN + BT) * BK;
+// What depends on the block: the lane's operand (its first byte of the block), whether the weight operand is live, and the instruction.
+// Block 64: 16 bytes k = 16 (l >> 4) .. +15 of v_mfma_i32_16x16x64_i8.  Blocks 32 / 16: v_mfma_i32_16x16x32_i8, whose A lane l = row
+// l & 15, bytes k = 8 (l >> 4) .. +7 (B: column l & 15, same k; D as for 16x16x64, so the epilogue and the rescale are shared).  Block 32
+// fills all 32 k; block 16 puts its 16 bytes in lanes l >> 4 = 0, 1 and zeros in the A operand of lanes 2, 3 (the only K = 16 int8 shape,
+// 32x32x16, gives 16 outputs per lane to rescale: the same VALU work per output, which is what bounds these blocks).  Only the pairing of
+// A and B bytes matters inside a block (the sum is exact), so a lane's 8 bytes are just its share of the block.
+template <int BLK> struct I8Blk {
+    static_assert(BLK == 16 || BLK == 32, "blocks of 16, 32 or 64");
+    using op_t = long;
+    __device__ __forceinline__ static int lane(int q) { return 8 * (BLK == 32 ? q : (q & 1)); }
+    __device__ __forceinline__ static bool a_live(int q) { return BLK == 32 || q < 2; }
+    __device__ __forceinline__ static v4i mfma(long a, long b, v4i c) { return __builtin_amdgcn_mfma_i32_16x16x32_i8(a, b, c, 0, 0, 0); }
 };
-
-// out tile: BN output features (weight rows) x BT tokens.  trips [a, b) of K (256 each).  SPLIT: out is the fp32 slab of this part.
-template <int OUT_DT, int WM, int WN, int TM, int TN, bool SPLIT>
-__global__ void __launch_bounds__(64 * WM * WN) k_i8_gemm(const int8_t* __restrict__ xc, const int8_t* __restrict__ xe, const int8_t* __restrict__ wc,
-                                                          const int8_t* __restrict__ we, const void* __restrict__ bias, void* __restrict__ out,
-                                                          int T, int N, int K, int tiles_t, int tiles, int trips_per_part, int xm, int wm)
-{
-    using C = I8Cfg<WM, WN, TM, TN>;
-    constexpr int NW = C::NW, BN = C::BN, BT = C::BT, STAGE = C::STAGE;
-    constexpr int GW = BN / 8 / NW, GX = BT / 8 / NW;            // LDS-DMA instructions per wave and stage (8 rows = 1 KB each)
-    static_assert(BN % (8 * NW) == 0 && BT % (8 * NW) == 0, "tile rows must split evenly over the waves");
-    __shared__ __attribute__((aligned(16))) uint8_t lds[2 * STAGE];
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63, r = l & 15, q = l >> 4;
-    const int part = SPLIT ? (int)blockIdx.x / tiles : 0, tile = SPLIT ? (int)blockIdx.x % tiles : (int)blockIdx.x;
-    const int t0 = (tile % tiles_t) * BT, n0 = (tile / tiles_t) * BN;
-    const int trips = K >> 8, nb4 = K >> 8;                      // dwords of exponents per row
-    const int ta = part * trips_per_part, tb = ta + trips_per_part < trips ? ta + trips_per_part : trips;
-
-    // staging: instruction i of wave w fills LDS rows (NW i + w) * 8 .. +7; lane l = row l >> 3, physical slot l & 7 holds the row's
-    // logical slot (l & 7) ^ ((row >> 1) & 7).  Rows past N / T repeat the last row (their results are not stored).
-    uint32_t offW[GW], offX[GX];
-#pragma unroll
-    for (int i = 0; i < GW; i++) {
-        const int row = (NW * i + w) * 8 + (l >> 3), piece = ((l & 7) ^ ((row >> 1) & 7)) << 4;
-        const int na = n0 + row < N ? n0 + row : N - 1;
-        offW[i] = (uint32_t)na * (uint32_t)K + piece;
-    }
-#pragma unroll
-    for (int i = 0; i < GX; i++) {
-        const int row = (NW * i + w) * 8 + (l >> 3), piece = ((l & 7) ^ ((row >> 1) & 7)) << 4;
-        const int tr = t0 + row < T ? t0 + row : T - 1;
-        offX[i] = (uint32_t)tr * (uint32_t)K + piece;
-    }
-    const int wr = w / WN, wcl = w % WN;
-    const int rowW = wr * (16 * TM), rowX = wcl * (16 * TN);     // the wave's first LDS row of each operand
-    // exponent dwords: weight rows n0 + rowW + 16 i + 4 q + j, token rows t0 + rowX + 16 jt + r
-    uint32_t ewo[TM][4], exo[TN];
-#pragma unroll
-    for (int i = 0; i < TM; i++)
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int n = n0 + rowW + 16 * i + 4 * q + j;
-            ewo[i][j] = (uint32_t)(n < N ? n : N - 1) * (uint32_t)nb4;
-        }
-#pragma unroll
-    for (int jt = 0; jt < TN; jt++) {
-        const int t = t0 + rowX + 16 * jt + r;
-        exo[jt] = (uint32_t)(t < T ? t : T - 1) * (uint32_t)nb4;
-    }
-    const uint32_t* const we32 = reinterpret_cast<const uint32_t*>(we);
-    const uint32_t* const xe32 = reinterpret_cast<const uint32_t*>(xe);
-
-    v2f acc[TM][TN][2];
-#pragma unroll
-    for (int i = 0; i < TM; i++)
-#pragma unroll
-        for (int jt = 0; jt < TN; jt++) acc[i][jt][0] = acc[i][jt][1] = v2f{0.f, 0.f};
-
-    auto stage = [&](int k0, int buf) __attribute__((always_inline)) {
-        uint8_t* const sW = lds + buf * STAGE;
-        uint8_t* const sX = sW + BN * BK;
-#pragma unroll
-        for (int i = 0; i < GW; i++)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wc + offW[i] + k0),
-                                             (__attribute__((address_space(3))) void*)(sW + (NW * i + w) * 1024), 16, 0, 0);
-#pragma unroll
-        for (int i = 0; i < GX; i++)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(xc + offX[i] + k0),
-                                             (__attribute__((address_space(3))) void*)(sX + (NW * i + w) * 1024), 16, 0, 0);
-    };
-    auto landed = [&]() __attribute__((always_inline)) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); };
-
-    // one block of the stage in buffer buf: byte BB (0..3) of the trip's exponent dwords
-    auto block = [&](int buf, int b, int BB, const uint32_t (&ewd)[TM][4], const uint32_t (&exd)[TN]) __attribute__((always_inline)) {
-        const uint8_t* const sW = lds + buf * STAGE;
-        const uint8_t* const sX = sW + BN * BK;
-        const int c = b * 4 + q;
-        v4i aF[TM], bF[TN];
-#pragma unroll
-        for (int i = 0; i < TM; i++) aF[i] = read16(sW, rowW + 16 * i + r, c);
-#pragma unroll
-        for (int jt = 0; jt < TN; jt++) bF[jt] = read16(sX, rowX + 16 * jt + r, c);
-        v2f sx[TN], nm[TN];
-#pragma unroll
-        for (int jt = 0; jt < TN; jt++) {
-            const float s = block_scale((int)(int8_t)(exd[jt] >> (8 * BB)), xm);
-            sx[jt] = v2f{s, s};
-            nm[jt] = v2f{-MAGIC_F * s, -MAGIC_F * s};
-        }
-        const v4i magic = {MAGIC_I, MAGIC_I, MAGIC_I, MAGIC_I};
-#pragma unroll
-        for (int i = 0; i < TM; i++) {
-            v2f sw[2];
-#pragma unroll
-            for (int h = 0; h < 2; h++)
-                sw[h] = v2f{block_scale((int)(int8_t)(ewd[i][2 * h] >> (8 * BB)), wm), block_scale((int)(int8_t)(ewd[i][2 * h + 1] >> (8 * BB)), wm)};
-#pragma unroll
-            for (int jt = 0; jt < TN; jt++) {
-                const v4i d = __builtin_amdgcn_mfma_i32_16x16x64_i8(aF[i], bF[jt], magic, 0, 0, 0);
-                const v4f f = __builtin_bit_cast(v4f, d);
-                const v2f f01 = f.xy, f23 = f.zw;
-                const v2f u01 = __builtin_elementwise_fma(f01, sx[jt], nm[jt]);
-                const v2f u23 = __builtin_elementwise_fma(f23, sx[jt], nm[jt]);
-                acc[i][jt][0] = __builtin_elementwise_fma(u01, sw[0], acc[i][jt][0]);
-                acc[i][jt][1] = __builtin_elementwise_fma(u23, sw[1], acc[i][jt][1]);
-            }
-        }
-    };
-
-    if (ta < tb) {
-        uint32_t ewd[TM][4], exd[TN];
-#pragma unroll
-        for (int i = 0; i < TM; i++)
-#pragma unroll
-            for (int j = 0; j < 4; j++) ewd[i][j] = we32[ewo[i][j] + ta];
-#pragma unroll
-        for (int jt = 0; jt < TN; jt++) exd[jt] = xe32[exo[jt] + ta];
-        stage(ta << 8, 0);
-        landed();
-        for (int tr = ta; tr < tb; tr++) {
-            const int trn = tr + 1 < tb ? tr + 1 : tr;               // (last trip: re-reads its own exponents, re-stages its first half)
-            uint32_t ewn[TM][4], exn[TN];
-#pragma unroll
-            for (int i = 0; i < TM; i++)
-#pragma unroll
-                for (int j = 0; j < 4; j++) ewn[i][j] = we32[ewo[i][j] + trn];
-#pragma unroll
-            for (int jt = 0; jt < TN; jt++) exn[jt] = xe32[exo[jt] + trn];
-            stage((tr << 8) + BK, 1);
-            block(0, 0, 0, ewd, exd);
-            block(0, 1, 1, ewd, exd);
-            landed();
-            stage(trn << 8, 0);
-            block(1, 0, 2, ewd, exd);
-            block(1, 1, 3, ewd, exd);
-            landed();
-#pragma unroll
-            for (int i = 0; i < TM; i++)
-#pragma unroll
-                for (int j = 0; j < 4; j++) ewd[i][j] = ewn[i][j];
-#pragma unroll
-            for (int jt = 0; jt < TN; jt++) exd[jt] = exn[jt];
-        }
-    }
-
-    // epilogue: lane holds features n .. n + 3 of token t
-#pragma unroll
-    for (int i = 0; i < TM; i++) {
-        const int n = n0 + rowW + 16 * i + 4 * q;
-        if (n >= N) continue;                                    // (N % 16 == 0: all four or none)
-#pragma unroll
-        for (int jt = 0; jt < TN; jt++) {
-            const int t = t0 + rowX + 16 * jt + r;
-            if (t >= T) continue;
-            const v2f a01 = acc[i][jt][0], a23 = acc[i][jt][1];
-            if constexpr (SPLIT) {
-                *reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + ((size_t)part * T + t) * N + n) = make_float4(a01.x, a01.y, a23.x, a23.y);
-            } else {
-                using raw_t = typename Traits<OUT_DT>::raw_t;
-                float v[4] = {a01.x, a01.y, a23.x, a23.y};
-                if (bias) {
-#pragma unroll
-                    for (int j = 0; j < 4; j++) v[j] += raw_to_f32<OUT_DT>((uint32_t)reinterpret_cast<const raw_t*>(bias)[n + j]);
-                }
-                if constexpr (OUT_DT == BFPQ_F32) {
-                    *reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + (size_t)t * N + n) = make_float4(v[0], v[1], v[2], v[3]);
-                } else {
-                    const uint32_t lo = f32_to_raw<OUT_DT>(v[0]) | (f32_to_raw<OUT_DT>(v[1]) << 16);
-                    const uint32_t hi = f32_to_raw<OUT_DT>(v[2]) | (f32_to_raw<OUT_DT>(v[3]) << 16);
-                    *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(out) + (size_t)t * N + n) = make_uint2(lo, hi);
-                }
-            }
-        }
-    }
-}
-
-// few tokens: wave = 16 features x 16 tokens (token group blockIdx.y) x a slice of the blocks; fp32 slab [slice][Tpad][N]
-__global__ void __launch_bounds__(256) k_i8_decode(const int8_t* __restrict__ wc, const int8_t* __restrict__ we, const int8_t* __restrict__ xc,
-                                                   const int8_t* __restrict__ xe, float* __restrict__ slabs, int T, int N, int K,
-                                                   int blocks_per_slice, int slices, int wm, int xm)
-{
-    const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
-    const int row_tiles = N / 16;
-    const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
-    const int rt = wave % row_tiles, slice = wave / row_tiles;
-    if (slice >= slices) return;                                 // grid rounded up to whole workgroups
-    const int nb = K / 64, Tpad = gridDim.y * 16;
-    const int b0 = slice * blocks_per_slice;
-    const int b1 = b0 + blocks_per_slice < nb ? b0 + blocks_per_slice : nb;
-    const int n0 = rt * 16, tok = blockIdx.y * 16 + r;
-    const int tx = tok < T ? tok : T - 1;                        // token columns past T repeat the last token (results dropped)
-    const int8_t* wrow = wc + (size_t)(n0 + r) * K + q * 16;
-    const int8_t* xrow = xc + (size_t)tx * K + q * 16;
-    const int8_t* wer = we + (size_t)(n0 + 4 * q) * nb;
-    const int8_t* xer = xe + (size_t)tx * nb;
-    const v4i zero = {0, 0, 0, 0};
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int b = b0; b < b1; b++) {
-        const v4i av = *reinterpret_cast<const v4i*>(wrow + (size_t)b * 64);
-        const v4i bv = *reinterpret_cast<const v4i*>(xrow + (size_t)b * 64);
-        const v4i c = __builtin_amdgcn_mfma_i32_16x16x64_i8(av, bv, zero, 0, 0, 0);
-        const int xe_b = xer[b];
-        const int cv[4] = {c.x, c.y, c.z, c.w};
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int we_b = wer[(size_t)j * nb + b];
-            // -128 marks a NaN block: the pair contributes NaN
-            const float sc = (we_b == -128 || xe_b == -128) ? __builtin_nanf("") : ldexpf(1.0f, we_b - wm + xe_b - xm);
-            acc[j] += (float)cv[j] * sc;
-        }
-    }
-    *reinterpret_cast<float4*>(slabs + ((size_t)slice * Tpad + blockIdx.y * 16 + r) * N + n0 + 4 * q) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-}
-
-// ---- blocks of 16 and 32: one v_mfma_i32_16x16x32_i8 per block ----------------------------------------------------------------------
-// Lane map of v_mfma_i32_16x16x32_i8: A lane l = row l & 15, bytes k = 8 (l >> 4) .. +7; B lane l = column l & 15, same k; D as for
-// 16x16x64 (lane l: rows 4 (l >> 4) + j of column l & 15), so the epilogue and the rescale are those above.  Block 32 fills all 32 k;
-// block 16 puts its 16 bytes in lanes l >> 4 = 0, 1 and zeros in the A operand of lanes 2, 3 (the only K = 16 int8 shape, 32x32x16, gives
-// 16 outputs per lane to rescale: the same VALU work per output, which is what bounds these blocks).  Only the pairing of A and B bytes
-// matters inside a block (the sum is exact), so a lane's 8 bytes are just its share of the block.
-template <int BLK>
-__device__ __forceinline__ long blk_a8(const uint8_t* base, int q)      // A (or B) operand of the lane: its 8 bytes of the block at base
-{
-    return *reinterpret_cast<const long*>(base + 8 * (BLK == 32 ? q : (q & 1)));
-}
+template <> struct I8Blk<64> {
+    using op_t = v4i;
+    __device__ __forceinline__ static int lane(int q) { return q * 16; }
+    __device__ __forceinline__ static bool a_live(int) { return true; }
+    __device__ __forceinline__ static v4i mfma(v4i a, v4i b, v4i c) { return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0); }
+};
 
 __device__ __forceinline__ long read8(const uint8_t* tile, int row, int o)     // logical bytes o .. o + 7 (o % 8 == 0) of an LDS row
 {
     return *reinterpret_cast<const long*>(tile + row * BK + ((((o >> 4) ^ ((row >> 1) & 7))) << 4) + (o & 8));
 }
 
-// the prefill tile of k_i8_gemm for blocks of BLK = 16 or 32: same staging, swizzle, split and epilogue; a stage of 128 bytes of K holds
-// NBS = 128 / BLK blocks, whose exponents (NBS bytes per row: ED dwords) are read one stage ahead
-template <int BLK, int OUT_DT, int WM, int WN, int TM, int TN, bool SPLIT>
-__global__ void __launch_bounds__(64 * WM * WN) k_i8_gemm_sb(const int8_t* __restrict__ xc, const int8_t* __restrict__ xe, const int8_t* __restrict__ wc,
-                                                             const int8_t* __restrict__ we, const void* __restrict__ bias, void* __restrict__ out,
-                                                             int T, int N, int K, int tiles_t, int tiles, int trips_per_part, int xm, int wm)
-{
-    using C = I8Cfg<WM, WN, TM, TN>;
-    constexpr int NW = C::NW, BN = C::BN, BT = C::BT, STAGE = C::STAGE;
-    constexpr int GW = BN / 8 / NW, GX = BT / 8 / NW;
-    constexpr int NBS = BK / BLK, ED = NBS / 4;                  // blocks per stage; exponent dwords per row and stage
-    static_assert(BLK == 16 || BLK == 32, "blocks of 16 or 32");
-    static_assert(BN % (8 * NW) == 0 && BT % (8 * NW) == 0, "tile rows must split evenly over the waves");
-    __shared__ __attribute__((aligned(16))) uint8_t lds[2 * STAGE];
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63, r = l & 15, q = l >> 4;
-    const int part = SPLIT ? (int)blockIdx.x / tiles : 0, tile = SPLIT ? (int)blockIdx.x % tiles : (int)blockIdx.x;
-    const int t0 = (tile % tiles_t) * BT, n0 = (tile / tiles_t) * BN;
-    const int trips = K >> 8, nbd = K / BLK / 4;                 // exponent dwords per row
-    const int ta = part * trips_per_part, tb = ta + trips_per_part < trips ? ta + trips_per_part : trips;
+__device__ __forceinline__ void landed() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); }
 
+// What the tile kernel does the same at every block: one lane's share of an output tile of BN output features (weight rows) x BT tokens,
+// trips [ta, tb) of K (256 each).  SPLIT: the part's trips go to fp32 slab `part`.
+template <int BLK, int WM, int WN, int TM, int TN, bool SPLIT>
+struct I8Tile {
+    static constexpr int NW = WM * WN, BN = 16 * WM * TM, BT = 16 * WN * TN, STAGE = (BN + BT) * BK;
+    static constexpr int GW = BN / 8 / NW, GX = BT / 8 / NW;            // LDS-DMA instructions per wave and stage (8 rows = 1 KB each)
+    static_assert(BN % (8 * NW) == 0 && BT % (8 * NW) == 0, "tile rows must split evenly over the waves");
+    int w, r, q, part, t0, n0, ta, tb, rowW, rowX;
     uint32_t offW[GW], offX[GX];
-#pragma unroll
-    for (int i = 0; i < GW; i++) {
-        const int row = (NW * i + w) * 8 + (l >> 3), piece = ((l & 7) ^ ((row >> 1) & 7)) << 4;
-        const int na = n0 + row < N ? n0 + row : N - 1;
-        offW[i] = (uint32_t)na * (uint32_t)K + piece;
-    }
-#pragma unroll
-    for (int i = 0; i < GX; i++) {
-        const int row = (NW * i + w) * 8 + (l >> 3), piece = ((l & 7) ^ ((row >> 1) & 7)) << 4;
-        const int tr = t0 + row < T ? t0 + row : T - 1;
-        offX[i] = (uint32_t)tr * (uint32_t)K + piece;
-    }
-    const int wr = w / WN, wcl = w % WN;
-    const int rowW = wr * (16 * TM), rowX = wcl * (16 * TN);
     uint32_t ewo[TM][4], exo[TN];                                // first exponent dword of each row the lane scales
+    v2f acc[TM][TN][2];
+
+    __device__ __forceinline__ I8Tile(int T, int N, int K, int tiles_t, int tiles, int trips_per_part)
+    {
+        w = threadIdx.x >> 6;
+        const int l = threadIdx.x & 63;
+        r = l & 15, q = l >> 4;
+        part = SPLIT ? (int)blockIdx.x / tiles : 0;
+        const int tile = SPLIT ? (int)blockIdx.x % tiles : (int)blockIdx.x;
+        t0 = (tile % tiles_t) * BT, n0 = (tile / tiles_t) * BN;
+        const int trips = K >> 8, nd = BLK == 64 ? K >> 8 : K / BLK / 4;     // exponent dwords per row
+        ta = part * trips_per_part, tb = ta + trips_per_part < trips ? ta + trips_per_part : trips;
+        // staging: instruction i of wave w fills LDS rows (NW i + w) * 8 .. +7; lane l = row l >> 3, physical slot l & 7 holds the row's
+        // logical slot (l & 7) ^ ((row >> 1) & 7).  Rows past N / T repeat the last row (their results are not stored).
 #pragma unroll
-    for (int i = 0; i < TM; i++)
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int n = n0 + rowW + 16 * i + 4 * q + j;
-            ewo[i][j] = (uint32_t)(n < N ? n : N - 1) * (uint32_t)nbd;
+        for (int i = 0; i < GW; i++) {
+            const int row = (NW * i + w) * 8 + (l >> 3), piece = ((l & 7) ^ ((row >> 1) & 7)) << 4;
+            const int na = n0 + row < N ? n0 + row : N - 1;
+            offW[i] = (uint32_t)na * (uint32_t)K + piece;
         }
 #pragma unroll
-    for (int jt = 0; jt < TN; jt++) {
-        const int t = t0 + rowX + 16 * jt + r;
-        exo[jt] = (uint32_t)(t < T ? t : T - 1) * (uint32_t)nbd;
+        for (int i = 0; i < GX; i++) {
+            const int row = (NW * i + w) * 8 + (l >> 3), piece = ((l & 7) ^ ((row >> 1) & 7)) << 4;
+            const int tr = t0 + row < T ? t0 + row : T - 1;
+            offX[i] = (uint32_t)tr * (uint32_t)K + piece;
+        }
+        const int wr = w / WN, wcl = w % WN;
+        rowW = wr * (16 * TM), rowX = wcl * (16 * TN);               // the wave's first LDS row of each operand
+        // exponent rows: weight rows n0 + rowW + 16 i + 4 q + j, token rows t0 + rowX + 16 jt + r
+#pragma unroll
+        for (int i = 0; i < TM; i++)
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int n = n0 + rowW + 16 * i + 4 * q + j;
+                ewo[i][j] = (uint32_t)(n < N ? n : N - 1) * (uint32_t)nd;
+            }
+#pragma unroll
+        for (int jt = 0; jt < TN; jt++) {
+            const int t = t0 + rowX + 16 * jt + r;
+            exo[jt] = (uint32_t)(t < T ? t : T - 1) * (uint32_t)nd;
+        }
+#pragma unroll
+        for (int i = 0; i < TM; i++)
+#pragma unroll
+            for (int jt = 0; jt < TN; jt++) acc[i][jt][0] = acc[i][jt][1] = v2f{0.f, 0.f};
     }
-    const uint32_t* const we32 = reinterpret_cast<const uint32_t*>(we);
-    const uint32_t* const xe32 = reinterpret_cast<const uint32_t*>(xe);
 
-    v2f acc[TM][TN][2];
-#pragma unroll
-    for (int i = 0; i < TM; i++)
-#pragma unroll
-        for (int jt = 0; jt < TN; jt++) acc[i][jt][0] = acc[i][jt][1] = v2f{0.f, 0.f};
-
-    auto stage = [&](int k0, int buf) __attribute__((always_inline)) {
+    // LDS-DMA of the 128 bytes of K from k0 into stage buffer buf
+    __device__ __forceinline__ void stage(uint8_t* lds, const int8_t* wc, const int8_t* xc, int k0, int buf) const
+    {
         uint8_t* const sW = lds + buf * STAGE;
         uint8_t* const sX = sW + BN * BK;
 #pragma unroll
@@ -361,147 +153,240 @@ __global__ void __launch_bounds__(64 * WM * WN) k_i8_gemm_sb(const int8_t* __res
         for (int i = 0; i < GX; i++)
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(xc + offX[i] + k0),
                                              (__attribute__((address_space(3))) void*)(sX + (NW * i + w) * 1024), 16, 0, 0);
-    };
-    auto landed = [&]() __attribute__((always_inline)) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); };
-    // exponent dwords of stage s (128 bytes of K from s * 128)
-    auto exps = [&](int s, uint32_t (&ewd)[TM][4][ED], uint32_t (&exd)[TN][ED]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < TM; i++)
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-#pragma unroll
-                for (int e = 0; e < ED; e++) ewd[i][j][e] = we32[ewo[i][j] + s * ED + e];
-#pragma unroll
-        for (int jt = 0; jt < TN; jt++)
-#pragma unroll
-            for (int e = 0; e < ED; e++) exd[jt][e] = xe32[exo[jt] + s * ED + e];
-    };
+    }
 
-    const v4i magic = {MAGIC_I, MAGIC_I, MAGIC_I, MAGIC_I};
-    // every block of the stage in buffer buf
-    auto blocks = [&](int buf, const uint32_t (&ewd)[TM][4][ED], const uint32_t (&exd)[TN][ED]) __attribute__((always_inline)) {
-        const uint8_t* const sW = lds + buf * STAGE;
-        const uint8_t* const sX = sW + BN * BK;
-        const int o = 8 * (BLK == 32 ? q : (q & 1));
+    // acc[i][jt] += (d - 1.5 * 2^23) * sx * sw for the MFMA result d of instruction tile (i, jt): nm = -1.5 * 2^23 * sx
+    __device__ __forceinline__ void rescale(int i, int jt, v4i d, v2f sx, v2f nm, const v2f (&sw)[2])
+    {
+        const v4f f = __builtin_bit_cast(v4f, d);
+        const v2f f01 = f.xy, f23 = f.zw;
+        const v2f u01 = __builtin_elementwise_fma(f01, sx, nm);
+        const v2f u23 = __builtin_elementwise_fma(f23, sx, nm);
+        acc[i][jt][0] = __builtin_elementwise_fma(u01, sw[0], acc[i][jt][0]);
+        acc[i][jt][1] = __builtin_elementwise_fma(u23, sw[1], acc[i][jt][1]);
+    }
+
+    // epilogue: lane holds features n .. n + 3 of token t
+    template <int OUT_DT>
+    __device__ __forceinline__ void store(const void* bias, void* out, int T, int N) const
+    {
 #pragma unroll
-        for (int b = 0; b < NBS; b++) {
-            const int e = b >> 2, sh = 8 * (b & 3);
-            long aF[TM], bF[TN];
+        for (int i = 0; i < TM; i++) {
+            const int n = n0 + rowW + 16 * i + 4 * q;
+            if (n >= N) continue;                                    // (N % 16 == 0: all four or none)
 #pragma unroll
-            for (int i = 0; i < TM; i++) {
-                aF[i] = read8(sW, rowW + 16 * i + r, b * BLK + o);
-                if (BLK == 16 && q >= 2) aF[i] = 0;              // (block 16: the second half of K is empty)
+            for (int jt = 0; jt < TN; jt++) {
+                const int t = t0 + rowX + 16 * jt + r;
+                if (t >= T) continue;
+                const v2f a01 = acc[i][jt][0], a23 = acc[i][jt][1];
+                if constexpr (SPLIT) {
+                    *reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + ((size_t)part * T + t) * N + n) = make_float4(a01.x, a01.y, a23.x, a23.y);
+                } else {
+                    using raw_t = typename Traits<OUT_DT>::raw_t;
+                    float v[4] = {a01.x, a01.y, a23.x, a23.y};
+                    if (bias) {
+#pragma unroll
+                        for (int j = 0; j < 4; j++) v[j] += raw_to_f32<OUT_DT>((uint32_t)reinterpret_cast<const raw_t*>(bias)[n + j]);
+                    }
+                    if constexpr (OUT_DT == BFPQ_F32) {
+                        *reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + (size_t)t * N + n) = make_float4(v[0], v[1], v[2], v[3]);
+                    } else {
+                        const uint32_t lo = f32_to_raw<OUT_DT>(v[0]) | (f32_to_raw<OUT_DT>(v[1]) << 16);
+                        const uint32_t hi = f32_to_raw<OUT_DT>(v[2]) | (f32_to_raw<OUT_DT>(v[3]) << 16);
+                        *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(out) + (size_t)t * N + n) = make_uint2(lo, hi);
+                    }
+                }
             }
+        }
+    }
+};
+
+// the prefill tile.  The exponent schedule is the block's: block 64 reads one dword (4 blocks) per row and trip, one trip ahead; blocks
+// 16 and 32 read the NBS = 128 / BLK blocks of a stage (ED dwords per row), one stage ahead, which keeps their registers down.
+template <int BLK, int OUT_DT, int WM, int WN, int TM, int TN, bool SPLIT>
+__global__ void __launch_bounds__(64 * WM * WN) k_i8_gemm(const int8_t* __restrict__ xc, const int8_t* __restrict__ xe, const int8_t* __restrict__ wc,
+                                                          const int8_t* __restrict__ we, const void* __restrict__ bias, void* __restrict__ out,
+                                                          int T, int N, int K, int tiles_t, int tiles, int trips_per_part, int xm, int wm)
+{
+    using Tile = I8Tile<BLK, WM, WN, TM, TN, SPLIT>;
+    constexpr int BN = Tile::BN, STAGE = Tile::STAGE;
+    __shared__ __attribute__((aligned(16))) uint8_t lds[2 * STAGE];
+    Tile t(T, N, K, tiles_t, tiles, trips_per_part);
+    const int r = t.r, q = t.q, ta = t.ta, tb = t.tb;
+    const uint32_t* const we32 = reinterpret_cast<const uint32_t*>(we);
+    const uint32_t* const xe32 = reinterpret_cast<const uint32_t*>(xe);
+
+    if constexpr (BLK == 64) {
+        // one block of the stage in buffer buf: byte BB (0..3) of the trip's exponent dwords
+        auto block = [&](int buf, int b, int BB, const uint32_t (&ewd)[TM][4], const uint32_t (&exd)[TN]) __attribute__((always_inline)) {
+            const uint8_t* const sW = lds + buf * STAGE;
+            const uint8_t* const sX = sW + BN * BK;
+            const int c = b * 4 + q;
+            v4i aF[TM], bF[TN];
 #pragma unroll
-            for (int jt = 0; jt < TN; jt++) bF[jt] = read8(sX, rowX + 16 * jt + r, b * BLK + o);
+            for (int i = 0; i < TM; i++) aF[i] = read16(sW, t.rowW + 16 * i + r, c);
+#pragma unroll
+            for (int jt = 0; jt < TN; jt++) bF[jt] = read16(sX, t.rowX + 16 * jt + r, c);
             v2f sx[TN], nm[TN];
 #pragma unroll
             for (int jt = 0; jt < TN; jt++) {
-                const float s = block_scale((int)(int8_t)(exd[jt][e] >> sh), xm);
+                const float s = block_scale((int)(int8_t)(exd[jt] >> (8 * BB)), xm);
                 sx[jt] = v2f{s, s};
                 nm[jt] = v2f{-MAGIC_F * s, -MAGIC_F * s};
             }
+            const v4i magic = {MAGIC_I, MAGIC_I, MAGIC_I, MAGIC_I};
 #pragma unroll
             for (int i = 0; i < TM; i++) {
                 v2f sw[2];
 #pragma unroll
                 for (int h = 0; h < 2; h++)
-                    sw[h] = v2f{block_scale((int)(int8_t)(ewd[i][2 * h][e] >> sh), wm), block_scale((int)(int8_t)(ewd[i][2 * h + 1][e] >> sh), wm)};
+                    sw[h] = v2f{block_scale((int)(int8_t)(ewd[i][2 * h] >> (8 * BB)), wm), block_scale((int)(int8_t)(ewd[i][2 * h + 1] >> (8 * BB)), wm)};
+#pragma unroll
+                for (int jt = 0; jt < TN; jt++) t.rescale(i, jt, I8Blk<64>::mfma(aF[i], bF[jt], magic), sx[jt], nm[jt], sw);
+            }
+        };
+
+        if (ta < tb) {
+            uint32_t ewd[TM][4], exd[TN];
+#pragma unroll
+            for (int i = 0; i < TM; i++)
+#pragma unroll
+                for (int j = 0; j < 4; j++) ewd[i][j] = we32[t.ewo[i][j] + ta];
+#pragma unroll
+            for (int jt = 0; jt < TN; jt++) exd[jt] = xe32[t.exo[jt] + ta];
+            t.stage(lds, wc, xc, ta << 8, 0);
+            landed();
+            for (int tr = ta; tr < tb; tr++) {
+                const int trn = tr + 1 < tb ? tr + 1 : tr;               // (last trip: re-reads its own exponents, re-stages its first half)
+                uint32_t ewn[TM][4], exn[TN];
+#pragma unroll
+                for (int i = 0; i < TM; i++)
+#pragma unroll
+                    for (int j = 0; j < 4; j++) ewn[i][j] = we32[t.ewo[i][j] + trn];
+#pragma unroll
+                for (int jt = 0; jt < TN; jt++) exn[jt] = xe32[t.exo[jt] + trn];
+                t.stage(lds, wc, xc, (tr << 8) + BK, 1);
+                block(0, 0, 0, ewd, exd);
+                block(0, 1, 1, ewd, exd);
+                landed();
+                t.stage(lds, wc, xc, trn << 8, 0);
+                block(1, 0, 2, ewd, exd);
+                block(1, 1, 3, ewd, exd);
+                landed();
+#pragma unroll
+                for (int i = 0; i < TM; i++)
+#pragma unroll
+                    for (int j = 0; j < 4; j++) ewd[i][j] = ewn[i][j];
+#pragma unroll
+                for (int jt = 0; jt < TN; jt++) exd[jt] = exn[jt];
+            }
+        }
+    } else {
+        constexpr int NBS = BK / BLK, ED = NBS / 4;                  // blocks per stage; exponent dwords per row and stage
+        // exponent dwords of stage s (128 bytes of K from s * 128)
+        auto exps = [&](int s, uint32_t (&ewd)[TM][4][ED], uint32_t (&exd)[TN][ED]) __attribute__((always_inline)) {
+#pragma unroll
+            for (int i = 0; i < TM; i++)
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+#pragma unroll
+                    for (int e = 0; e < ED; e++) ewd[i][j][e] = we32[t.ewo[i][j] + s * ED + e];
+#pragma unroll
+            for (int jt = 0; jt < TN; jt++)
+#pragma unroll
+                for (int e = 0; e < ED; e++) exd[jt][e] = xe32[t.exo[jt] + s * ED + e];
+        };
+        const v4i magic = {MAGIC_I, MAGIC_I, MAGIC_I, MAGIC_I};
+        // every block of the stage in buffer buf
+        auto blocks = [&](int buf, const uint32_t (&ewd)[TM][4][ED], const uint32_t (&exd)[TN][ED]) __attribute__((always_inline)) {
+            const uint8_t* const sW = lds + buf * STAGE;
+            const uint8_t* const sX = sW + BN * BK;
+            const int o = I8Blk<BLK>::lane(q);
+#pragma unroll
+            for (int b = 0; b < NBS; b++) {
+                const int e = b >> 2, sh = 8 * (b & 3);
+                long aF[TM], bF[TN];
+#pragma unroll
+                for (int i = 0; i < TM; i++) {
+                    aF[i] = read8(sW, t.rowW + 16 * i + r, b * BLK + o);
+                    if (!I8Blk<BLK>::a_live(q)) aF[i] = 0;
+                }
+#pragma unroll
+                for (int jt = 0; jt < TN; jt++) bF[jt] = read8(sX, t.rowX + 16 * jt + r, b * BLK + o);
+                v2f sx[TN], nm[TN];
 #pragma unroll
                 for (int jt = 0; jt < TN; jt++) {
-                    const v4i d = __builtin_amdgcn_mfma_i32_16x16x32_i8(aF[i], bF[jt], magic, 0, 0, 0);
-                    const v4f f = __builtin_bit_cast(v4f, d);
-                    const v2f f01 = f.xy, f23 = f.zw;
-                    const v2f u01 = __builtin_elementwise_fma(f01, sx[jt], nm[jt]);
-                    const v2f u23 = __builtin_elementwise_fma(f23, sx[jt], nm[jt]);
-                    acc[i][jt][0] = __builtin_elementwise_fma(u01, sw[0], acc[i][jt][0]);
-                    acc[i][jt][1] = __builtin_elementwise_fma(u23, sw[1], acc[i][jt][1]);
+                    const float s = block_scale((int)(int8_t)(exd[jt][e] >> sh), xm);
+                    sx[jt] = v2f{s, s};
+                    nm[jt] = v2f{-MAGIC_F * s, -MAGIC_F * s};
+                }
+#pragma unroll
+                for (int i = 0; i < TM; i++) {
+                    v2f sw[2];
+#pragma unroll
+                    for (int h = 0; h < 2; h++)
+                        sw[h] = v2f{block_scale((int)(int8_t)(ewd[i][2 * h][e] >> sh), wm), block_scale((int)(int8_t)(ewd[i][2 * h + 1][e] >> sh), wm)};
+#pragma unroll
+                    for (int jt = 0; jt < TN; jt++) t.rescale(i, jt, I8Blk<BLK>::mfma(aF[i], bF[jt], magic), sx[jt], nm[jt], sw);
                 }
             }
-        }
-    };
+        };
 
-    if (ta < tb) {
-        uint32_t ewd[TM][4][ED], exd[TN][ED], ewn[TM][4][ED], exn[TN][ED];
-        exps(2 * ta, ewd, exd);
-        stage(ta << 8, 0);
-        landed();
-        for (int tr = ta; tr < tb; tr++) {
-            const int trn = tr + 1 < tb ? tr + 1 : tr;               // (last trip: re-reads its own first stage)
-            exps(2 * tr + 1, ewn, exn);
-            stage((tr << 8) + BK, 1);
-            blocks(0, ewd, exd);
+        if (ta < tb) {
+            uint32_t ewd[TM][4][ED], exd[TN][ED], ewn[TM][4][ED], exn[TN][ED];
+            exps(2 * ta, ewd, exd);
+            t.stage(lds, wc, xc, ta << 8, 0);
             landed();
-            exps(2 * trn, ewd, exd);
-            stage(trn << 8, 0);
-            blocks(1, ewn, exn);
-            landed();
-        }
-    }
-
-    // epilogue (as k_i8_gemm): lane holds features n .. n + 3 of token t
-#pragma unroll
-    for (int i = 0; i < TM; i++) {
-        const int n = n0 + rowW + 16 * i + 4 * q;
-        if (n >= N) continue;
-#pragma unroll
-        for (int jt = 0; jt < TN; jt++) {
-            const int t = t0 + rowX + 16 * jt + r;
-            if (t >= T) continue;
-            const v2f a01 = acc[i][jt][0], a23 = acc[i][jt][1];
-            if constexpr (SPLIT) {
-                *reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + ((size_t)part * T + t) * N + n) = make_float4(a01.x, a01.y, a23.x, a23.y);
-            } else {
-                using raw_t = typename Traits<OUT_DT>::raw_t;
-                float v[4] = {a01.x, a01.y, a23.x, a23.y};
-                if (bias) {
-#pragma unroll
-                    for (int j = 0; j < 4; j++) v[j] += raw_to_f32<OUT_DT>((uint32_t)reinterpret_cast<const raw_t*>(bias)[n + j]);
-                }
-                if constexpr (OUT_DT == BFPQ_F32) {
-                    *reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + (size_t)t * N + n) = make_float4(v[0], v[1], v[2], v[3]);
-                } else {
-                    const uint32_t lo = f32_to_raw<OUT_DT>(v[0]) | (f32_to_raw<OUT_DT>(v[1]) << 16);
-                    const uint32_t hi = f32_to_raw<OUT_DT>(v[2]) | (f32_to_raw<OUT_DT>(v[3]) << 16);
-                    *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(out) + (size_t)t * N + n) = make_uint2(lo, hi);
-                }
+            for (int tr = ta; tr < tb; tr++) {
+                const int trn = tr + 1 < tb ? tr + 1 : tr;               // (last trip: re-reads its own first stage)
+                exps(2 * tr + 1, ewn, exn);
+                t.stage(lds, wc, xc, (tr << 8) + BK, 1);
+                blocks(0, ewd, exd);
+                landed();
+                exps(2 * trn, ewd, exd);
+                t.stage(lds, wc, xc, trn << 8, 0);
+                blocks(1, ewn, exn);
+                landed();
             }
         }
     }
+    t.template store<OUT_DT>(bias, out, T, N);
 }
 
-// few tokens, blocks of BLK = 16 or 32 (k_i8_decode with one 16x16x32 instruction per block); K % BLK == 0
+// few tokens: wave = 16 features x 16 tokens (token group blockIdx.y) x a slice of the blocks; fp32 slab [slice][Tpad][N]; K % BLK == 0
 template <int BLK>
-__global__ void __launch_bounds__(256) k_i8_decode_sb(const int8_t* __restrict__ wc, const int8_t* __restrict__ we, const int8_t* __restrict__ xc,
-                                                      const int8_t* __restrict__ xe, float* __restrict__ slabs, int T, int N, int K,
-                                                      int blocks_per_slice, int slices, int wm, int xm)
+__global__ void __launch_bounds__(256) k_i8_decode(const int8_t* __restrict__ wc, const int8_t* __restrict__ we, const int8_t* __restrict__ xc,
+                                                   const int8_t* __restrict__ xe, float* __restrict__ slabs, int T, int N, int K,
+                                                   int blocks_per_slice, int slices, int wm, int xm)
 {
+    using B = I8Blk<BLK>;
+    using op_t = typename B::op_t;
     const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
     const int row_tiles = N / 16;
     const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
     const int rt = wave % row_tiles, slice = wave / row_tiles;
-    if (slice >= slices) return;
+    if (slice >= slices) return;                                 // grid rounded up to whole workgroups
     const int nb = K / BLK, Tpad = gridDim.y * 16;
     const int b0 = slice * blocks_per_slice;
     const int b1 = b0 + blocks_per_slice < nb ? b0 + blocks_per_slice : nb;
     const int n0 = rt * 16, tok = blockIdx.y * 16 + r;
-    const int tx = tok < T ? tok : T - 1;
-    const uint8_t* wrow = reinterpret_cast<const uint8_t*>(wc) + (size_t)(n0 + r) * K;
-    const uint8_t* xrow = reinterpret_cast<const uint8_t*>(xc) + (size_t)tx * K;
+    const int tx = tok < T ? tok : T - 1;                        // token columns past T repeat the last token (results dropped)
+    const int8_t* wrow = wc + (size_t)(n0 + r) * K + B::lane(q);
+    const int8_t* xrow = xc + (size_t)tx * K + B::lane(q);
     const int8_t* wer = we + (size_t)(n0 + 4 * q) * nb;
     const int8_t* xer = xe + (size_t)tx * nb;
     const v4i zero = {0, 0, 0, 0};
-    const bool a_live = BLK == 32 || q < 2;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     for (int b = b0; b < b1; b++) {
-        const long av = a_live ? blk_a8<BLK>(wrow + (size_t)b * BLK, q) : 0;
-        const long bv = blk_a8<BLK>(xrow + (size_t)b * BLK, q);
-        const v4i c = __builtin_amdgcn_mfma_i32_16x16x32_i8(av, bv, zero, 0, 0, 0);
+        const op_t av = B::a_live(q) ? *reinterpret_cast<const op_t*>(wrow + (size_t)b * BLK) : op_t{};
+        const op_t bv = *reinterpret_cast<const op_t*>(xrow + (size_t)b * BLK);
+        const v4i c = B::mfma(av, bv, zero);
         const int xe_b = xer[b];
         const int cv[4] = {c.x, c.y, c.z, c.w};
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const int we_b = wer[(size_t)j * nb + b];
+            // -128 marks a NaN block: the pair contributes NaN
             const float sc = (we_b == -128 || xe_b == -128) ? __builtin_nanf("") : ldexpf(1.0f, we_b - wm + xe_b - xm);
             acc[j] += (float)cv[j] * sc;
         }
@@ -537,47 +422,21 @@ template <int V> int var_bt() { return 16 * I8Var<V>::WN * I8Var<V>::TN; }
 int var_tile_n(int v) { return v == 0 ? var_bn<0>() : (v == 1 ? var_bn<1>() : var_bn<2>()); }
 int var_tile_t(int v) { return v == 0 ? var_bt<0>() : (v == 1 ? var_bt<1>() : var_bt<2>()); }
 
-template <int V, int OUT_DT, bool SPLIT>
+template <int BLK, int V, int OUT_DT, bool SPLIT>
 void launch_tile(dim3 grid, hipStream_t s, const int8_t* xc, const int8_t* xe, const int8_t* wc, const int8_t* we, const void* bias, void* out,
                  int T, int N, int K, int tiles_t, int tiles, int tpp, int xm, int wm)
 {
     using P = I8Var<V>;
-    hipLaunchKernelGGL((k_i8_gemm<OUT_DT, P::WM, P::WN, P::TM, P::TN, SPLIT>), grid, dim3(64 * P::WM * P::WN), 0, s, xc, xe, wc, we, bias, out,
-                       T, N, K, tiles_t, tiles, tpp, xm, wm);
-}
-
-template <int V>
-void launch_var(int out_dtype, bool split, dim3 grid, hipStream_t s, const int8_t* xc, const int8_t* xe, const int8_t* wc, const int8_t* we,
-                const void* bias, void* out, int T, int N, int K, int tiles_t, int tiles, int tpp, int xm, int wm)
-{
-    if (split) launch_tile<V, BFPQ_F32, true>(grid, s, xc, xe, wc, we, nullptr, out, T, N, K, tiles_t, tiles, tpp, xm, wm);
-    else with_dtype(out_dtype, [&](auto dt) { launch_tile<V, dt, false>(grid, s, xc, xe, wc, we, bias, out, T, N, K, tiles_t, tiles, tpp, xm, wm); });
-}
-
-template <int BLK, int V, int OUT_DT, bool SPLIT>
-void launch_tile_sb(dim3 grid, hipStream_t s, const int8_t* xc, const int8_t* xe, const int8_t* wc, const int8_t* we, const void* bias, void* out,
-                    int T, int N, int K, int tiles_t, int tiles, int tpp, int xm, int wm)
-{
-    using P = I8Var<V>;
-    hipLaunchKernelGGL((k_i8_gemm_sb<BLK, OUT_DT, P::WM, P::WN, P::TM, P::TN, SPLIT>), grid, dim3(64 * P::WM * P::WN), 0, s, xc, xe, wc, we, bias,
+    hipLaunchKernelGGL((k_i8_gemm<BLK, OUT_DT, P::WM, P::WN, P::TM, P::TN, SPLIT>), grid, dim3(64 * P::WM * P::WN), 0, s, xc, xe, wc, we, bias,
                        out, T, N, K, tiles_t, tiles, tpp, xm, wm);
 }
 
-template <int BLK, int V>
-void launch_var_sb(int out_dtype, bool split, dim3 grid, hipStream_t s, const int8_t* xc, const int8_t* xe, const int8_t* wc, const int8_t* we,
-                   const void* bias, void* out, int T, int N, int K, int tiles_t, int tiles, int tpp, int xm, int wm)
+// f(std::integral_constant<int, BLK>{}) for a block of 16, 32 or 64
+template <class F> void with_block(int block_size, F&& f)
 {
-    if (split) launch_tile_sb<BLK, V, BFPQ_F32, true>(grid, s, xc, xe, wc, we, nullptr, out, T, N, K, tiles_t, tiles, tpp, xm, wm);
-    else with_dtype(out_dtype, [&](auto dt) { launch_tile_sb<BLK, V, dt, false>(grid, s, xc, xe, wc, we, bias, out, T, N, K, tiles_t, tiles, tpp, xm, wm); });
-}
-
-template <int BLK>
-void launch_sb(int v, int out_dtype, bool split, dim3 grid, hipStream_t s, const int8_t* xc, const int8_t* xe, const int8_t* wc, const int8_t* we,
-               const void* bias, void* out, int T, int N, int K, int tiles_t, int tiles, int tpp, int xm, int wm)
-{
-    if (v == 0) launch_var_sb<BLK, 0>(out_dtype, split, grid, s, xc, xe, wc, we, bias, out, T, N, K, tiles_t, tiles, tpp, xm, wm);
-    else if (v == 1) launch_var_sb<BLK, 1>(out_dtype, split, grid, s, xc, xe, wc, we, bias, out, T, N, K, tiles_t, tiles, tpp, xm, wm);
-    else launch_var_sb<BLK, 2>(out_dtype, split, grid, s, xc, xe, wc, we, bias, out, T, N, K, tiles_t, tiles, tpp, xm, wm);
+    if (block_size == 32) f(std::integral_constant<int, 32>{});
+    else if (block_size == 16) f(std::integral_constant<int, 16>{});
+    else f(std::integral_constant<int, 64>{});
 }
 
 }  // namespace
@@ -585,88 +444,81 @@ void launch_sb(int v, int out_dtype, bool split, dim3 grid, hipStream_t s, const
 extern "C" __attribute__((visibility("hidden"))) int bfpq_g_i8_variant = -1;    // -1 = choose; 0..2 force (bfpq_tune, BFPQ_TUNE_I8_VARIANT)
 extern "C" __attribute__((visibility("hidden"))) int bfpq_g_i8_parts = 0;       // 0 = choose; >= 1 force (bfpq_tune, BFPQ_TUNE_I8_PARTS)
 
-static int i8_variant(int64_t T)
-{
-    if (bfpq_g_i8_variant >= 0 && bfpq_g_i8_variant < kI8Variants) return bfpq_g_i8_variant;
-    return T > 64 ? 0 : 1;
-}
-
 static bool i8_args_ok(int out_dtype, int w_mant_bits, int x_mant_bits)
 {
     return dtype_ok(out_dtype) && w_mant_bits >= 1 && w_mant_bits <= 7 && x_mant_bits >= 1 && x_mant_bits <= 7;
 }
 
-extern "C" {
+static bool small_block(int block_size) { return block_size == 16 || block_size == 32; }      // the blocks of the `b` entries
 
-int bfpq_hbfp_linear_i8_ok(int64_t T, int64_t N, int64_t K)
+static int64_t i8_tiles(int64_t T, int64_t N, int v)
 {
-    return T >= 1 && N >= 16 && N % 16 == 0 && K >= 256 && K % 256 == 0 && T * K < ((int64_t)1 << 32) && N * K < ((int64_t)1 << 32) &&
-           ((T + 63) / 64) * ((N + 63) / 64) < ((int64_t)1 << 30);
+    return ((T + var_tile_t(v) - 1) / var_tile_t(v)) * ((N + var_tile_n(v) - 1) / var_tile_n(v));
 }
 
-int bfpq_hbfp_linear_i8_parts(int64_t T, int64_t N, int64_t K)
+// The plan.  Block 64: variant 0 past 64 tokens, else 1; K split in parts of at least two trips.  Blocks 16 / 32: a trip holds 4x / 2x
+// the matrix and rescale work of block 64 (the tile is VALU-bound on the rescale), so the plan fills the chip first -- the largest tile
+// variant with >= 256 tiles, else the smallest, and K split down to one trip per part.
+static int i8_variant(int64_t T, int64_t N, int block_size)
+{
+    if (bfpq_g_i8_variant >= 0 && bfpq_g_i8_variant < kI8Variants) return bfpq_g_i8_variant;
+    if (block_size == 64) return T > 64 ? 0 : 1;
+    return i8_tiles(T, N, 0) >= 256 ? 0 : (i8_tiles(T, N, 1) >= 256 ? 1 : 2);
+}
+
+static int i8_parts(int64_t T, int64_t N, int64_t K, int block_size)
 {
     if (!bfpq_hbfp_linear_i8_ok(T, N, K)) return 1;
     const int64_t trips = K / 256;
     if (bfpq_g_i8_parts > 0) return (int)(bfpq_g_i8_parts < trips ? bfpq_g_i8_parts : trips);
-    const int v = i8_variant(T);
-    const int64_t tiles = ((T + var_tile_t(v) - 1) / var_tile_t(v)) * ((N + var_tile_n(v) - 1) / var_tile_n(v));
-    if (tiles >= 256 || trips < 4) return 1;
+    const int64_t min_trips = block_size == 64 ? 2 : 1;           // trips per part
+    const int64_t tiles = i8_tiles(T, N, i8_variant(T, N, block_size));
+    if (tiles >= 256 || trips < 2 * min_trips) return 1;
     int64_t parts = 512 / tiles;                                  // aim at two workgroups per CU
     if (parts > 8) parts = 8;
-    if (parts > trips / 2) parts = trips / 2;                     // at least two trips per part
+    if (parts > trips / min_trips) parts = trips / min_trips;
     return parts < 2 ? 1 : (int)parts;
 }
 
-// the tile launch (and its slab sum) of every block: 64 (variant v of k_i8_gemm) or 16 / 32 (variant v of k_i8_gemm_sb)
-static int i8_launch(const int8_t* xc, const int8_t* xe, const int8_t* wc, const int8_t* we, const void* bias, void* out, float* slabs, int parts,
-                     int64_t T, int64_t N, int64_t K, int block_size, int v, int out_dtype, int wm, int xm, hipStream_t s)
+static bool i8_ptrs_ok(const void* xc, const void* xe, const void* wc, const void* we, const void* out, int block_size)
 {
-    const int trips = (int)(K / 256);
+    if (!xc || !xe || !wc || !we || !out) return false;
+    // LDS-DMA sources: 16-byte aligned codes; vector stores of 4 outputs: 8-byte aligned; exponents read as dwords, two per row and
+    // stage at block 16
+    const uintptr_t emask = block_size == 16 ? 7u : 3u;
+    return aligned16(xc, wc, out) && !((reinterpret_cast<uintptr_t>(xe) | reinterpret_cast<uintptr_t>(we)) & emask);
+}
+
+// the tile entries of every block, with (split) or without the K split: checks, the launch and the slab sum
+static int i8_tile(const void* xcodes, const int8_t* xexp, const void* wcodes, const int8_t* wexp, const void* bias, void* out, bool split,
+                   float* slabs, int parts, int64_t T, int64_t N, int64_t K, int block_size, int out_dtype, int wm, int xm, void* stream)
+{
+    if (!i8_args_ok(out_dtype, wm, xm) || T < 0 || N < 0 || (split && (parts < 1 || parts > 64))) return BFPQ_E_ARG;
+    if (T == 0 || N == 0) return 0;
+    if (!bfpq_hbfp_linear_i8_ok(T, N, K)) return BFPQ_E_UNSUPPORTED;
+    if (!i8_ptrs_ok(xcodes, xexp, wcodes, wexp, out, block_size) || (split && (!slabs || !aligned16(slabs)))) return BFPQ_E_ARG;
+    const int v = i8_variant(T, N, block_size), trips = (int)(K / 256);
     if (parts > trips) parts = trips;
     const int tpp = (trips + parts - 1) / parts;
     parts = (trips + tpp - 1) / tpp;                              // (no empty part)
     const int tiles_t = (int)((T + var_tile_t(v) - 1) / var_tile_t(v)), tiles = tiles_t * (int)((N + var_tile_n(v) - 1) / var_tile_n(v));
-    const bool split = slabs != nullptr;
-    void* dst = split ? (void*)slabs : out;
     const dim3 grid((unsigned)(tiles * (split ? parts : 1)));
-    if (block_size == 32) launch_sb<32>(v, out_dtype, split, grid, s, xc, xe, wc, we, bias, dst, (int)T, (int)N, (int)K, tiles_t, tiles, tpp, xm, wm);
-    else if (block_size == 16) launch_sb<16>(v, out_dtype, split, grid, s, xc, xe, wc, we, bias, dst, (int)T, (int)N, (int)K, tiles_t, tiles, tpp, xm, wm);
-    else if (v == 0) launch_var<0>(out_dtype, split, grid, s, xc, xe, wc, we, bias, dst, (int)T, (int)N, (int)K, tiles_t, tiles, tpp, xm, wm);
-    else if (v == 1) launch_var<1>(out_dtype, split, grid, s, xc, xe, wc, we, bias, dst, (int)T, (int)N, (int)K, tiles_t, tiles, tpp, xm, wm);
-    else launch_var<2>(out_dtype, split, grid, s, xc, xe, wc, we, bias, dst, (int)T, (int)N, (int)K, tiles_t, tiles, tpp, xm, wm);
+    hipStream_t s = (hipStream_t)stream;
+    const int8_t *xc = (const int8_t*)xcodes, *wc = (const int8_t*)wcodes;
+    with_block(block_size, [&](auto blk) {
+        constexpr int BLK = decltype(blk)::value;
+        auto go = [&](auto var) {
+            if (split) launch_tile<BLK, var, BFPQ_F32, true>(grid, s, xc, xexp, wc, wexp, nullptr, slabs, (int)T, (int)N, (int)K, tiles_t, tiles, tpp, xm, wm);
+            else with_dtype(out_dtype, [&](auto dt) {
+                launch_tile<BLK, var, dt, false>(grid, s, xc, xexp, wc, wexp, bias, out, (int)T, (int)N, (int)K, tiles_t, tiles, tpp, xm, wm);
+            });
+        };
+        if (v == 0) go(std::integral_constant<int, 0>{});
+        else if (v == 1) go(std::integral_constant<int, 1>{});
+        else go(std::integral_constant<int, 2>{});
+    });
     if (split) launch_slab_reduce(out_dtype, slabs, (size_t)(T * N), bias, out, T * N, N, parts, s);
     return (int)hipGetLastError();
-}
-
-static bool i8_ptrs_ok(const void* xc, const void* xe, const void* wc, const void* we, const void* out)
-{
-    if (!xc || !xe || !wc || !we || !out) return false;
-    // LDS-DMA sources: 16-byte aligned codes; exponent dwords: 4-byte aligned; vector stores of 4 outputs: 8-byte aligned
-    return aligned16(xc, wc, out) &&
-           !((reinterpret_cast<uintptr_t>(xe) | reinterpret_cast<uintptr_t>(we)) & 3u);
-}
-
-int bfpq_hbfp_linear_i8(const void* xcodes, const int8_t* xexp, const void* wcodes, const int8_t* wexp, const void* bias, void* out,
-                        int64_t T, int64_t N, int64_t K, int out_dtype, int w_mant_bits, int x_mant_bits, void* stream)
-{
-    if (!i8_args_ok(out_dtype, w_mant_bits, x_mant_bits) || T < 0 || N < 0) return BFPQ_E_ARG;
-    if (T == 0 || N == 0) return 0;
-    if (!bfpq_hbfp_linear_i8_ok(T, N, K)) return BFPQ_E_UNSUPPORTED;
-    if (!i8_ptrs_ok(xcodes, xexp, wcodes, wexp, out)) return BFPQ_E_ARG;
-    return i8_launch((const int8_t*)xcodes, xexp, (const int8_t*)wcodes, wexp, bias, out, nullptr, 1, T, N, K, 64, i8_variant(T), out_dtype,
-                     w_mant_bits, x_mant_bits, (hipStream_t)stream);
-}
-
-int bfpq_hbfp_linear_i8_splitk(const void* xcodes, const int8_t* xexp, const void* wcodes, const int8_t* wexp, const void* bias, void* out,
-                               float* slabs, int parts, int64_t T, int64_t N, int64_t K, int out_dtype, int w_mant_bits, int x_mant_bits, void* stream)
-{
-    if (!i8_args_ok(out_dtype, w_mant_bits, x_mant_bits) || T < 0 || N < 0 || parts < 1 || parts > 64) return BFPQ_E_ARG;
-    if (T == 0 || N == 0) return 0;
-    if (!bfpq_hbfp_linear_i8_ok(T, N, K)) return BFPQ_E_UNSUPPORTED;
-    if (!i8_ptrs_ok(xcodes, xexp, wcodes, wexp, out) || !slabs || !aligned16(slabs)) return BFPQ_E_ARG;
-    return i8_launch((const int8_t*)xcodes, xexp, (const int8_t*)wcodes, wexp, bias, out, slabs, parts, T, N, K, 64, i8_variant(T), out_dtype,
-                     w_mant_bits, x_mant_bits, (hipStream_t)stream);
 }
 
 static int decode8_slices(int64_t T, int64_t N, int64_t K)
@@ -679,6 +531,49 @@ static int decode8_slices(int64_t T, int64_t N, int64_t K)
     return (int)((nb + bps - 1) / bps);
 }
 
+// the few-token entries of every block.  Every block slices K in whole 64-byte runs (finer slices would multiply the fp32 slab
+// traffic, which is what a few-token call pays for).
+static int i8_decode(const void* xcodes, const int8_t* xexp, const void* wcodes, const int8_t* wexp, const void* bias, void* out, float* slabs,
+                     int64_t T, int64_t N, int64_t K, int block_size, int out_dtype, int wm, int xm, void* stream)
+{
+    if (!i8_args_ok(out_dtype, wm, xm) || T < 1 || N < 1) return BFPQ_E_ARG;
+    if (bfpq_hbfp_linear_decode8_ws(T, N, K) < 0) return BFPQ_E_UNSUPPORTED;
+    if (!xcodes || !xexp || !wcodes || !wexp || !out || !slabs) return BFPQ_E_ARG;
+    if (!aligned16(xcodes, wcodes, slabs)) return BFPQ_E_ARG;
+    const int slices = decode8_slices(T, N, K), bps = (int)((K / 64 + slices - 1) / slices) * (64 / block_size);
+    const int64_t waves = (N / 16) * slices, groups = (T + 15) / 16;
+    hipStream_t s = (hipStream_t)stream;
+    with_block(block_size, [&](auto blk) {
+        hipLaunchKernelGGL(k_i8_decode<blk>, dim3((unsigned)((waves + 3) / 4), (unsigned)groups), dim3(256), 0, s, (const int8_t*)wcodes, wexp,
+                           (const int8_t*)xcodes, xexp, slabs, (int)T, (int)N, (int)K, bps, slices, wm, xm);
+    });
+    // slabs are [slices][Tpad][N]: the first T rows of each slab are the outputs' partial sums
+    launch_slab_reduce(out_dtype, slabs, (size_t)(groups * 16 * N), bias, out, T * N, N, slices, s);
+    return (int)hipGetLastError();
+}
+
+extern "C" {
+
+int bfpq_hbfp_linear_i8_ok(int64_t T, int64_t N, int64_t K)
+{
+    return T >= 1 && N >= 16 && N % 16 == 0 && K >= 256 && K % 256 == 0 && T * K < ((int64_t)1 << 32) && N * K < ((int64_t)1 << 32) &&
+           ((T + 63) / 64) * ((N + 63) / 64) < ((int64_t)1 << 30);
+}
+
+int bfpq_hbfp_linear_i8_parts(int64_t T, int64_t N, int64_t K) { return i8_parts(T, N, K, 64); }
+
+int bfpq_hbfp_linear_i8(const void* xcodes, const int8_t* xexp, const void* wcodes, const int8_t* wexp, const void* bias, void* out,
+                        int64_t T, int64_t N, int64_t K, int out_dtype, int w_mant_bits, int x_mant_bits, void* stream)
+{
+    return i8_tile(xcodes, xexp, wcodes, wexp, bias, out, false, nullptr, 1, T, N, K, 64, out_dtype, w_mant_bits, x_mant_bits, stream);
+}
+
+int bfpq_hbfp_linear_i8_splitk(const void* xcodes, const int8_t* xexp, const void* wcodes, const int8_t* wexp, const void* bias, void* out,
+                               float* slabs, int parts, int64_t T, int64_t N, int64_t K, int out_dtype, int w_mant_bits, int x_mant_bits, void* stream)
+{
+    return i8_tile(xcodes, xexp, wcodes, wexp, bias, out, true, slabs, parts, T, N, K, 64, out_dtype, w_mant_bits, x_mant_bits, stream);
+}
+
 int64_t bfpq_hbfp_linear_decode8_ws(int64_t T, int64_t N, int64_t K)
 {
     if (T < 1 || N < 16 || K < 64 || N % 16 != 0 || K % 64 != 0 || T > 65535 * 16 || N * K >= ((int64_t)1 << 32) || T * K >= ((int64_t)1 << 32))
@@ -689,120 +584,46 @@ int64_t bfpq_hbfp_linear_decode8_ws(int64_t T, int64_t N, int64_t K)
 int bfpq_hbfp_linear_decode8(const void* xcodes, const int8_t* xexp, const void* wcodes, const int8_t* wexp, const void* bias, void* out,
                              float* slabs, int64_t T, int64_t N, int64_t K, int out_dtype, int w_mant_bits, int x_mant_bits, void* stream)
 {
-    if (!i8_args_ok(out_dtype, w_mant_bits, x_mant_bits) || T < 1 || N < 1) return BFPQ_E_ARG;
-    if (bfpq_hbfp_linear_decode8_ws(T, N, K) < 0) return BFPQ_E_UNSUPPORTED;
-    if (!xcodes || !xexp || !wcodes || !wexp || !out || !slabs) return BFPQ_E_ARG;
-    if (!aligned16(xcodes, wcodes, slabs)) return BFPQ_E_ARG;
-    const int slices = decode8_slices(T, N, K);
-    const int64_t nb = K / 64;
-    const int bps = (int)((nb + slices - 1) / slices);
-    const int64_t waves = (N / 16) * slices, groups = (T + 15) / 16;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_i8_decode, dim3((unsigned)((waves + 3) / 4), (unsigned)groups), dim3(256), 0, s, (const int8_t*)wcodes, wexp,
-                       (const int8_t*)xcodes, xexp, slabs, (int)T, (int)N, (int)K, bps, slices, w_mant_bits, x_mant_bits);
-    // slabs are [slices][Tpad][N]: the first T rows of each slab are the outputs' partial sums
-    launch_slab_reduce(out_dtype, slabs, (size_t)(groups * 16 * N), bias, out, T * N, N, slices, s);
-    return (int)hipGetLastError();
+    return i8_decode(xcodes, xexp, wcodes, wexp, bias, out, slabs, T, N, K, 64, out_dtype, w_mant_bits, x_mant_bits, stream);
 }
 
-// ---- blocks of 16 and 32 ------------------------------------------------------------------------------------------------------------
-static bool small_block(int block_size) { return block_size == 16 || block_size == 32; }
-
+// ---- the same entries at blocks 16 and 32 (any other block_size: BFPQ_E_ARG, or 0 from _ok) ---------------------------------------
 int bfpq_hbfp_linear_i8b_ok(int64_t T, int64_t N, int64_t K, int block_size)
 {
     return small_block(block_size) && bfpq_hbfp_linear_i8_ok(T, N, K);
 }
 
-// the plan at blocks 16 / 32: a trip holds 4x / 2x the matrix and rescale work of block 64 (the tile is VALU-bound on the rescale), so
-// the plan fills the chip first -- the largest tile variant with >= 256 tiles, else the smallest, and K split down to one trip per part
-static int64_t i8_tiles(int64_t T, int64_t N, int v)
-{
-    return ((T + var_tile_t(v) - 1) / var_tile_t(v)) * ((N + var_tile_n(v) - 1) / var_tile_n(v));
-}
-
-static int i8b_variant(int64_t T, int64_t N)
-{
-    if (bfpq_g_i8_variant >= 0 && bfpq_g_i8_variant < kI8Variants) return bfpq_g_i8_variant;
-    return i8_tiles(T, N, 0) >= 256 ? 0 : (i8_tiles(T, N, 1) >= 256 ? 1 : 2);
-}
-
 int bfpq_hbfp_linear_i8b_parts(int64_t T, int64_t N, int64_t K, int block_size)
 {
-    if (!small_block(block_size)) return BFPQ_E_ARG;
-    if (!bfpq_hbfp_linear_i8_ok(T, N, K)) return 1;
-    const int64_t trips = K / 256;
-    if (bfpq_g_i8_parts > 0) return (int)(bfpq_g_i8_parts < trips ? bfpq_g_i8_parts : trips);
-    const int64_t tiles = i8_tiles(T, N, i8b_variant(T, N));
-    if (tiles >= 256 || trips < 2) return 1;
-    int64_t parts = 512 / tiles;                                  // aim at two workgroups per CU
-    if (parts > 8) parts = 8;
-    if (parts > trips) parts = trips;
-    return parts < 2 ? 1 : (int)parts;
-}
-
-static bool i8b_ptrs_ok(const void* xc, const void* xe, const void* wc, const void* we, const void* out, int block_size)
-{
-    if (!xc || !xe || !wc || !we || !out) return false;
-    // exponents: one dword (block 32) or two (block 16) per row and stage, read as dwords
-    const uintptr_t emask = block_size == 16 ? 7u : 3u;
-    return aligned16(xc, wc, out) && !((reinterpret_cast<uintptr_t>(xe) | reinterpret_cast<uintptr_t>(we)) & emask);
+    return small_block(block_size) ? i8_parts(T, N, K, block_size) : BFPQ_E_ARG;
 }
 
 int bfpq_hbfp_linear_i8b(const void* xcodes, const int8_t* xexp, const void* wcodes, const int8_t* wexp, const void* bias, void* out,
                          int64_t T, int64_t N, int64_t K, int block_size, int out_dtype, int w_mant_bits, int x_mant_bits, void* stream)
 {
-    if (!small_block(block_size) || !i8_args_ok(out_dtype, w_mant_bits, x_mant_bits) || T < 0 || N < 0) return BFPQ_E_ARG;
-    if (T == 0 || N == 0) return 0;
-    if (!bfpq_hbfp_linear_i8_ok(T, N, K)) return BFPQ_E_UNSUPPORTED;
-    if (!i8b_ptrs_ok(xcodes, xexp, wcodes, wexp, out, block_size)) return BFPQ_E_ARG;
-    return i8_launch((const int8_t*)xcodes, xexp, (const int8_t*)wcodes, wexp, bias, out, nullptr, 1, T, N, K, block_size, i8b_variant(T, N),
-                     out_dtype, w_mant_bits, x_mant_bits, (hipStream_t)stream);
+    if (!small_block(block_size)) return BFPQ_E_ARG;
+    return i8_tile(xcodes, xexp, wcodes, wexp, bias, out, false, nullptr, 1, T, N, K, block_size, out_dtype, w_mant_bits, x_mant_bits, stream);
 }
 
 int bfpq_hbfp_linear_i8b_splitk(const void* xcodes, const int8_t* xexp, const void* wcodes, const int8_t* wexp, const void* bias, void* out,
                                 float* slabs, int parts, int64_t T, int64_t N, int64_t K, int block_size, int out_dtype, int w_mant_bits,
                                 int x_mant_bits, void* stream)
 {
-    if (!small_block(block_size) || !i8_args_ok(out_dtype, w_mant_bits, x_mant_bits) || T < 0 || N < 0 || parts < 1 || parts > 64) return BFPQ_E_ARG;
-    if (T == 0 || N == 0) return 0;
-    if (!bfpq_hbfp_linear_i8_ok(T, N, K)) return BFPQ_E_UNSUPPORTED;
-    if (!i8b_ptrs_ok(xcodes, xexp, wcodes, wexp, out, block_size) || !slabs || !aligned16(slabs)) return BFPQ_E_ARG;
-    return i8_launch((const int8_t*)xcodes, xexp, (const int8_t*)wcodes, wexp, bias, out, slabs, parts, T, N, K, block_size, i8b_variant(T, N),
-                     out_dtype, w_mant_bits, x_mant_bits, (hipStream_t)stream);
-}
-
-// the slicing of the block-64 plan (slices of whole 64-byte runs of K): finer slices would multiply the fp32 slab traffic, which is
-// what a few-token call pays for
-static int decode8b_bps(int64_t T, int64_t N, int64_t K, int block_size)
-{
-    const int slices = decode8_slices(T, N, K);
-    return (int)((K / 64 + slices - 1) / slices) * (64 / block_size);
+    if (!small_block(block_size)) return BFPQ_E_ARG;
+    return i8_tile(xcodes, xexp, wcodes, wexp, bias, out, true, slabs, parts, T, N, K, block_size, out_dtype, w_mant_bits, x_mant_bits, stream);
 }
 
 int64_t bfpq_hbfp_linear_decode8b_ws(int64_t T, int64_t N, int64_t K, int block_size)
 {
-    if (!small_block(block_size)) return BFPQ_E_ARG;
-    if (T < 1 || N < 16 || K < 64 || N % 16 != 0 || K % 64 != 0 || T > 65535 * 16 || N * K >= ((int64_t)1 << 32) || T * K >= ((int64_t)1 << 32))
-        return BFPQ_E_UNSUPPORTED;
-    return (int64_t)decode8_slices(T, N, K) * ((T + 15) / 16 * 16) * N;
+    return small_block(block_size) ? bfpq_hbfp_linear_decode8_ws(T, N, K) : BFPQ_E_ARG;
 }
 
 int bfpq_hbfp_linear_decode8b(const void* xcodes, const int8_t* xexp, const void* wcodes, const int8_t* wexp, const void* bias, void* out,
                               float* slabs, int64_t T, int64_t N, int64_t K, int block_size, int out_dtype, int w_mant_bits, int x_mant_bits,
                               void* stream)
 {
-    if (!small_block(block_size) || !i8_args_ok(out_dtype, w_mant_bits, x_mant_bits) || T < 1 || N < 1) return BFPQ_E_ARG;
-    if (bfpq_hbfp_linear_decode8b_ws(T, N, K, block_size) < 0) return BFPQ_E_UNSUPPORTED;
-    if (!xcodes || !xexp || !wcodes || !wexp || !out || !slabs) return BFPQ_E_ARG;
-    if (!aligned16(xcodes, wcodes, slabs)) return BFPQ_E_ARG;
-    const int slices = decode8_slices(T, N, K), bps = decode8b_bps(T, N, K, block_size);
-    const int64_t waves = (N / 16) * slices, groups = (T + 15) / 16;
-    hipStream_t s = (hipStream_t)stream;
-    auto kern = block_size == 32 ? k_i8_decode_sb<32> : k_i8_decode_sb<16>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((waves + 3) / 4), (unsigned)groups), dim3(256), 0, s, (const int8_t*)wcodes, wexp,
-                       (const int8_t*)xcodes, xexp, slabs, (int)T, (int)N, (int)K, bps, slices, w_mant_bits, x_mant_bits);
-    launch_slab_reduce(out_dtype, slabs, (size_t)(groups * 16 * N), bias, out, T * N, N, slices, s);
-    return (int)hipGetLastError();
+    if (!small_block(block_size)) return BFPQ_E_ARG;
+    return i8_decode(xcodes, xexp, wcodes, wexp, bias, out, slabs, T, N, K, block_size, out_dtype, w_mant_bits, x_mant_bits, stream);
 }
 
 int bfpq_codes4_to_i8(const void* codes4, void* codes8, int64_t n_codes, void* stream)

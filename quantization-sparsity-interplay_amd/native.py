@@ -1112,21 +1112,14 @@ def hbfp_linear_mx8(x, w8, wscale, x_mant_bits, epsilon=1e-8, bias=None, out_dty
 DECODE8_TOKENS = 16       # up to this many tokens the decode-shaped kernel runs; more take the LDS-tiled kernel where K % 256 == 0
 
 
-def hbfp_linear_i8_ok(T, N, K, w_mant_bits, x_mant_bits, block_size=64):
-    """hbfp_linear_i8 takes this problem: block 64, mantissas of 1..7 bits on both sides, N % 16 == 0, K % 64 == 0 (the tiled kernel
-    needs K % 256 == 0; other K go to the decode-shaped kernel at any token count)"""
-    return (block_size == 64 and 1 <= w_mant_bits <= 7 and 1 <= x_mant_bits <= 7 and T >= 1 and N >= 16 and N % 16 == 0
-            and K >= 64 and K % 64 == 0 and load_library().bfpq_hbfp_linear_decode8_ws(T, N, K) >= 0)
-
-
 I8_BLOCKS = (16, 32)      # the blocks besides 64 that hbfp_linear_i8 runs (one v_mfma_i32_16x16x32_i8 per block)
 
 
-def hbfp_linear_i8_blocks_ok(T, N, K, w_mant_bits, x_mant_bits, block_size):
-    """hbfp_linear_i8 takes this problem at block 16 or 32: mantissas of 1..7 bits on both sides, N % 16 == 0, K % 64 == 0 (the tiled
+def hbfp_linear_i8_ok(T, N, K, w_mant_bits, x_mant_bits, block_size=64):
+    """hbfp_linear_i8 takes this problem: block 64, 32 or 16, mantissas of 1..7 bits on both sides, N % 16 == 0, K % 64 == 0 (the tiled
     kernel needs K % 256 == 0; other K go to the decode-shaped kernel at any token count)"""
-    return (block_size in I8_BLOCKS and 1 <= w_mant_bits <= 7 and 1 <= x_mant_bits <= 7 and T >= 1 and N >= 16 and N % 16 == 0
-            and K >= 64 and K % 64 == 0 and load_library().bfpq_hbfp_linear_decode8b_ws(T, N, K, block_size) >= 0)
+    return (block_size in (64,) + I8_BLOCKS and 1 <= w_mant_bits <= 7 and 1 <= x_mant_bits <= 7 and T >= 1 and N >= 16 and N % 16 == 0
+            and K >= 64 and K % 64 == 0 and load_library().bfpq_hbfp_linear_decode8_ws(T, N, K) >= 0)
 
 
 def codes4_to_i8(codes4, n_codes):
@@ -1151,8 +1144,7 @@ def hbfp_linear_i8(x, wcodes8, wexps, w_mant_bits, x_mant_bits, epsilon=1e-8, bi
     K = x.shape[-1]
     T = x.numel() // K
     N = wexps.shape[0]
-    small = block_size != 64
-    if not (hbfp_linear_i8_blocks_ok(T, N, K, w_mant_bits, x_mant_bits, block_size) if small else hbfp_linear_i8_ok(T, N, K, w_mant_bits, x_mant_bits)):
+    if not hbfp_linear_i8_ok(T, N, K, w_mant_bits, x_mant_bits, block_size):
         raise ValueError(f"hbfp_linear_i8 needs block 16, 32 or 64, N % 16 == 0, K % 64 == 0 and mantissas of 1..7 bits "
                          f"(got T={T}, N={N}, K={K}, w_mant_bits={w_mant_bits}, x_mant_bits={x_mant_bits}, block_size={block_size})")
     if wcodes8.dtype != torch.int8 or wcodes8.numel() != N * K:
@@ -1174,38 +1166,22 @@ def hbfp_linear_i8(x, wcodes8, wexps, w_mant_bits, x_mant_bits, epsilon=1e-8, bi
         if bias is not None:
             bias = bias.to(out_dtype).contiguous()
         bp = _ptr(bias) if bias is not None else None
-        args = (int(w_mant_bits), int(x_mant_bits), _stream(x))
-        if small:
-            _i8_small_blocks(L, xc, xe, wc, we, bp, out, T, N, K, int(block_size), DTYPE_CODE[out_dtype], args)
-        elif T > DECODE8_TOKENS and L.bfpq_hbfp_linear_i8_ok(T, N, K):
-            parts = L.bfpq_hbfp_linear_i8_parts(T, N, K) if SPLIT_K else 1
+        ops = (_ptr(xc), _ptr(xe), _ptr(wc), _ptr(we), bp, _ptr(out))
+        # the C entry family of the block: block 64's take no block argument, the `b` entries take 16 or 32
+        blk, sfx = ((), '') if block_size == 64 else ((int(block_size),), 'b')
+        tail = blk + (DTYPE_CODE[out_dtype], int(w_mant_bits), int(x_mant_bits), _stream(x))
+        if T > DECODE8_TOKENS and L.bfpq_hbfp_linear_i8_ok(T, N, K):
+            parts = getattr(L, f"bfpq_hbfp_linear_i8{sfx}_parts")(T, N, K, *blk) if SPLIT_K else 1
             if parts > 1:                                              # few output tiles: K split, fp32 slabs added in part order
                 slabs = torch.empty((parts, T, N), dtype=torch.float32, device=dev)
-                check(L.bfpq_hbfp_linear_i8_splitk(_ptr(xc), _ptr(xe), _ptr(wc), _ptr(we), bp, _ptr(out), _ptr(slabs), parts, T, N, K,
-                                                   DTYPE_CODE[out_dtype], *args), "bfpq_hbfp_linear_i8_splitk")
+                name = f"bfpq_hbfp_linear_i8{sfx}_splitk"
+                check(getattr(L, name)(*ops, _ptr(slabs), parts, T, N, K, *tail), name)
             else:
-                check(L.bfpq_hbfp_linear_i8(_ptr(xc), _ptr(xe), _ptr(wc), _ptr(we), bp, _ptr(out), T, N, K, DTYPE_CODE[out_dtype], *args),
-                      "bfpq_hbfp_linear_i8")
+                name = f"bfpq_hbfp_linear_i8{sfx}"
+                check(getattr(L, name)(*ops, T, N, K, *tail), name)
         else:
             slabs = torch.empty(int(L.bfpq_hbfp_linear_decode8_ws(T, N, K)), dtype=torch.float32, device=dev)
-            check(L.bfpq_hbfp_linear_decode8(_ptr(xc), _ptr(xe), _ptr(wc), _ptr(we), bp, _ptr(out), _ptr(slabs), T, N, K,
-                                             DTYPE_CODE[out_dtype], *args), "bfpq_hbfp_linear_decode8")
+            name = f"bfpq_hbfp_linear_decode8{sfx}"
+            check(getattr(L, name)(*ops, _ptr(slabs), T, N, K, *tail), name)
     return out.view(tuple(x.shape[:-1]) + (N,))
 
-
-def _i8_small_blocks(L, xc, xe, wc, we, bp, out, T, N, K, block, dt, args):
-    """the launches of hbfp_linear_i8 at block 16 or 32: the tile kernel past DECODE8_TOKENS tokens where K % 256 == 0 (K split when
-    the plan asks for it), else the decode-shaped kernel"""
-    dev = out.device
-    if T > DECODE8_TOKENS and L.bfpq_hbfp_linear_i8b_ok(T, N, K, block):
-        parts = L.bfpq_hbfp_linear_i8b_parts(T, N, K, block) if SPLIT_K else 1
-        if parts > 1:
-            slabs = torch.empty((parts, T, N), dtype=torch.float32, device=dev)
-            check(L.bfpq_hbfp_linear_i8b_splitk(_ptr(xc), _ptr(xe), _ptr(wc), _ptr(we), bp, _ptr(out), _ptr(slabs), parts, T, N, K, block, dt,
-                                                *args), "bfpq_hbfp_linear_i8b_splitk")
-        else:
-            check(L.bfpq_hbfp_linear_i8b(_ptr(xc), _ptr(xe), _ptr(wc), _ptr(we), bp, _ptr(out), T, N, K, block, dt, *args), "bfpq_hbfp_linear_i8b")
-    else:
-        slabs = torch.empty(int(L.bfpq_hbfp_linear_decode8b_ws(T, N, K, block)), dtype=torch.float32, device=dev)
-        check(L.bfpq_hbfp_linear_decode8b(_ptr(xc), _ptr(xe), _ptr(wc), _ptr(we), bp, _ptr(out), _ptr(slabs), T, N, K, block, dt, *args),
-              "bfpq_hbfp_linear_decode8b")

@@ -1,110 +1,20 @@
-"""The int8 matrix-unit GEMM at HBFP blocks 16 and 32 (bfpq_i8gemm.hip, k_i8_gemm_sb / k_i8_decode_sb): bit for bit on certified exact
+"""The int8 matrix-unit GEMM at HBFP blocks 16 and 32 (bfpq_i8gemm.hip, k_i8_gemm<BLK> / k_i8_decode<BLK>): bit for bit on certified exact
 operands, NaN blocks, random OPT-125m / ViT-L shapes within the fp32 summation bound, the packed and cached modules of BASELINE configs 1
-and 5, a packed model and a captured prefill (run with `-m gpu` on an MI355X).  Exact operands: tests/gemm_cases_blocks.py."""
+and 5, a packed model and a captured prefill (run with `-m gpu` on an MI355X).  Exact operands and drivers: tests/gemm_cases.py and tests/test_i8gemm_gpu.py."""
 import copy
-import ctypes
 
 import pytest
 import torch
 
 import gemm_cases as G
-import gemm_cases_blocks as GB
 from quantization_sparsity_interplay_amd import native
 from quantization_sparsity_interplay_amd.bfp import bfp_ops
 from quantization_sparsity_interplay_amd.patch import PackedBFPLinear, pack_linear_layers, patch_linear_layers
+from test_i8gemm_gpu import DEV, DTS, TUNE_I8_VARIANT, WIDTHS, L, assert_bits, certified, every_plan, expected, i8, run_c
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-DTS = (torch.float32, torch.bfloat16, torch.float16)
-TUNE_I8_VARIANT = 4
-DT_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
-WIDTHS = (1, 3, 4, 5, 7)
 TOKENS = tuple(range(1, 18)) + (64, 65, 128, 197, 512, 2048, 301)
 BLOCKS = (16, 32)
-
-
-def L():
-    return native.load_library()
-
-
-def ptr(t):
-    return ctypes.c_void_p(0) if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def stream():
-    return ctypes.c_void_p(torch.cuda.current_stream(torch.device(DEV)).cuda_stream)
-
-
-def i8(t):
-    return t.to(torch.int8).contiguous()
-
-
-def certified(T, N, K, xm, wm, blk, seed, nm=(0, 0), with_bias=False):
-    for sx, sw in ((3, 3), (3, 2), (2, 2), (2, 1), (1, 1)):
-        xc, xe = GB.hbfp_operand(T, K, xm, -3, sx, seed, blk, device=DEV)
-        wc, we = GB.hbfp_operand(N, K, wm, -2, sw, seed + 1, blk, nm=nm, pattern=(5, 7, 2), device=DEV)
-        bq = None
-        if with_bias:
-            g = torch.Generator(device=DEV).manual_seed(seed + 2)
-            bq = torch.randint(-60, 61, (N,), generator=g, device=DEV).double() * 4
-        q, worst = GB.exact_certificate(xc, xe, xm, wc, we, wm, blk, bq)
-        if worst < 2.0 ** 24:
-            return xc, xe, wc, we, None if bq is None else bq * q
-    raise AssertionError(f"no certified spread for T={T} N={N} K={K} xm={xm} wm={wm} block {blk}")
-
-
-def expected(xc, xe, xm, wc, we, wm, blk, bias, dt):
-    want = GB.values(xc, xe, xm, blk) @ GB.values(wc, we, wm, blk).t()
-    if bias is not None:
-        want = want + bias.view(1, -1)
-    return want.to(dt)
-
-
-def run_c(route, blk, xc8, xe8, wc8, we8, bias, T, N, K, dt, wm, xm, parts=1):
-    out = torch.empty((T, N), dtype=dt, device=DEV)
-    if route == 'decode8':
-        slabs = torch.empty(int(L().bfpq_hbfp_linear_decode8b_ws(T, N, K, blk)), dtype=torch.float32, device=DEV)
-        rc = L().bfpq_hbfp_linear_decode8b(ptr(xc8), ptr(xe8), ptr(wc8), ptr(we8), ptr(bias), ptr(out), ptr(slabs), T, N, K, blk, DT_CODE[dt],
-                                           wm, xm, stream())
-    elif route == 'tile':
-        rc = L().bfpq_hbfp_linear_i8b(ptr(xc8), ptr(xe8), ptr(wc8), ptr(we8), ptr(bias), ptr(out), T, N, K, blk, DT_CODE[dt], wm, xm, stream())
-    else:
-        slabs = torch.empty((parts, T, N), dtype=torch.float32, device=DEV)
-        rc = L().bfpq_hbfp_linear_i8b_splitk(ptr(xc8), ptr(xe8), ptr(wc8), ptr(we8), ptr(bias), ptr(out), ptr(slabs), parts, T, N, K, blk,
-                                             DT_CODE[dt], wm, xm, stream())
-    assert rc == 0, (route, rc)
-    return out
-
-
-def assert_bits(got, want, what):
-    g, w = got.cpu(), want.cpu()
-    iv = torch.int16 if g.dtype != torch.float32 else torch.int32
-    same = (g.view(iv) == w.view(iv)) | (torch.isnan(g) & torch.isnan(w))
-    if not bool(same.all()):
-        i = int((~same).flatten().nonzero()[0])
-        raise AssertionError(f"{what}: {int((~same).sum())}/{same.numel()} outputs differ; first at flat {i}: got {float(g.flatten()[i])!r} "
-                             f"want {float(w.flatten()[i])!r}")
-
-
-def every_plan(xc, xe, xm, wc, we, wm, blk, bias, T, N, K, dt, what, variants=range(3)):
-    """the public wrapper, the decode kernel and (K % 256 == 0) every tile variant unsplit and split in 2, 3 and the maximum parts"""
-    want = expected(xc, xe, xm, wc, we, wm, blk, bias, dt)
-    b = None if bias is None else bias.to(dt)
-    xq = (i8(xc), i8(xe))
-    got = native.hbfp_linear_i8(torch.empty((T, K), dtype=dt, device=DEV), i8(wc), i8(we), wm, xm, bias=b, out_dtype=dt, xq=xq, block_size=blk)
-    assert_bits(got, want, f"{what} default plan")
-    assert_bits(run_c('decode8', blk, *xq, i8(wc), i8(we), b, T, N, K, dt, wm, xm), want, f"{what} decode8")
-    if not L().bfpq_hbfp_linear_i8b_ok(T, N, K, blk):
-        return
-    trips = K // 256
-    try:
-        for v in variants:
-            assert L().bfpq_tune(TUNE_I8_VARIANT, v) == 0
-            assert_bits(run_c('tile', blk, *xq, i8(wc), i8(we), b, T, N, K, dt, wm, xm), want, f"{what} variant {v}")
-            for p in sorted({2, 3, trips} - {1}):
-                assert_bits(run_c('split', blk, *xq, i8(wc), i8(we), b, T, N, K, dt, wm, xm, parts=p), want, f"{what} variant {v} parts {p}")
-    finally:
-        L().bfpq_tune(TUNE_I8_VARIANT, -1)
 
 
 @pytest.mark.parametrize("blk", BLOCKS)
@@ -113,8 +23,8 @@ def every_plan(xc, xe, xm, wc, we, wm, blk, bias, T, N, K, dt, what, variants=ra
 def test_exact_every_width(blk, xm, wm):
     for T in (1, 33, 257):
         N, K = 80, 512
-        xc, xe, wc, we, bias = certified(T, N, K, xm, wm, blk, seed=100 * xm + 10 * wm + T + blk, with_bias=(T % 2 == 1))
-        every_plan(xc, xe, xm, wc, we, wm, blk, bias, T, N, K, torch.bfloat16, f"b{blk} xm {xm} wm {wm} T {T}")
+        xc, xe, wc, we, bias = certified(T, N, K, xm, wm, seed=100 * xm + 10 * wm + T + blk, with_bias=(T % 2 == 1), block=blk)
+        every_plan(xc, xe, xm, wc, we, wm, bias, T, N, K, torch.bfloat16, f"b{blk} xm {xm} wm {wm} T {T}", block=blk)
 
 
 @pytest.mark.parametrize("blk", BLOCKS)
@@ -123,16 +33,16 @@ def test_exact_every_token_count(blk, dt):
     for T in TOKENS:
         for with_bias in (False, True):
             N, K = 144, 768
-            xc, xe, wc, we, bias = certified(T, N, K, 5, 7, blk, seed=T * 3 + int(with_bias) + blk, with_bias=with_bias)
-            every_plan(xc, xe, 5, wc, we, 7, blk, bias, T, N, K, dt, f"b{blk} {dt} T {T} bias {with_bias}",
+            xc, xe, wc, we, bias = certified(T, N, K, 5, 7, seed=T * 3 + int(with_bias) + blk, with_bias=with_bias, block=blk)
+            every_plan(xc, xe, 5, wc, we, 7, bias, T, N, K, dt, f"b{blk} {dt} T {T} bias {with_bias}", block=blk,
                        variants=range(3) if T in (1, 17, 197, 2048) else (0,))
 
 
 @pytest.mark.parametrize("blk", BLOCKS)
 def test_exact_k_not_multiple_of_256_and_nm_weights(blk):
     for (T, N, K, nm) in ((20, 48, 320, (0, 0)), (300, 32, 192, (0, 0)), (65, 128, 512, (2, 4)), (197, 64, 1024, (1, 4)), (17, 64, 1024, (4, 8))):
-        xc, xe, wc, we, bias = certified(T, N, K, 7, 6, blk, seed=T + N + blk, nm=nm, with_bias=True)
-        every_plan(xc, xe, 7, wc, we, 6, blk, bias, T, N, K, torch.float32, f"b{blk} T {T} N {N} K {K} nm {nm}")
+        xc, xe, wc, we, bias = certified(T, N, K, 7, 6, seed=T + N + blk, nm=nm, with_bias=True, block=blk)
+        every_plan(xc, xe, 7, wc, we, 6, bias, T, N, K, torch.float32, f"b{blk} T {T} N {N} K {K} nm {nm}", block=blk)
 
 
 @pytest.mark.parametrize("blk", BLOCKS)
@@ -140,10 +50,10 @@ def test_exact_k_not_multiple_of_256_and_nm_weights(blk):
 def test_exact_4bit_weights_through_the_expansion(blk, T):
     N, K = 96, 512
     for wm in (1, 3):
-        xc, xe, wc, we, bias = certified(T, N, K, 7, wm, blk, seed=T + wm + blk, with_bias=True)
+        xc, xe, wc, we, bias = certified(T, N, K, 7, wm, seed=T + wm + blk, with_bias=True, block=blk)
         pk = bfp_ops.PackedBFP(G.pack4(wc), i8(we), (N, K), torch.float32, wm, blk, 4)
         assert torch.equal(pk._i8_codes(), i8(wc))
-        want = expected(xc, xe, 7, wc, we, wm, blk, bias, torch.float32)
+        want = expected(xc, xe, 7, wc, we, wm, bias, torch.float32, block=blk)
         got = native.hbfp_linear_i8(torch.empty((T, K), dtype=torch.float32, device=DEV), pk._i8_codes(), pk.exps, wm, 7,
                                     bias=bias.float(), xq=(i8(xc), i8(xe)), block_size=blk)
         assert_bits(got, want, f"b{blk} 4-bit weights wm {wm} T {T}")
@@ -153,20 +63,20 @@ def test_exact_4bit_weights_through_the_expansion(blk, T):
 def test_nan_blocks_every_route(blk):
     N, K = 64, 512
     for T in (3, 40):
-        xc, xe, wc, we, _ = certified(T, N, K, 7, 7, blk, seed=77 + blk)
+        xc, xe, wc, we, _ = certified(T, N, K, 7, 7, seed=77 + blk, block=blk)
         xe, we = xe.clone(), we.clone()
         xe[1, 5] = -128
         we[5, 11] = -128
-        want = expected(xc, xe.clamp_min(-127), 7, wc, we.clamp_min(-127), 7, blk, None, torch.float32)
+        want = expected(xc, xe.clamp_min(-127), 7, wc, we.clamp_min(-127), 7, None, torch.float32, block=blk)
         want[1, :] = float("nan")
         want[:, 5] = float("nan")
         xq = (i8(xc), i8(xe))
-        assert_bits(run_c('decode8', blk, *xq, i8(wc), i8(we), None, T, N, K, torch.float32, 7, 7), want, f"b{blk} decode8 NaN T {T}")
+        assert_bits(run_c('decode8', *xq, i8(wc), i8(we), None, T, N, K, torch.float32, 7, 7, block=blk), want, f"b{blk} decode8 NaN T {T}")
         try:
             for v in range(3):
                 L().bfpq_tune(TUNE_I8_VARIANT, v)
-                assert_bits(run_c('tile', blk, *xq, i8(wc), i8(we), None, T, N, K, torch.float32, 7, 7), want, f"b{blk} tile {v} NaN T {T}")
-                assert_bits(run_c('split', blk, *xq, i8(wc), i8(we), None, T, N, K, torch.float32, 7, 7, parts=2), want, f"b{blk} split {v} NaN")
+                assert_bits(run_c('tile', *xq, i8(wc), i8(we), None, T, N, K, torch.float32, 7, 7, block=blk), want, f"b{blk} tile {v} NaN T {T}")
+                assert_bits(run_c('split', *xq, i8(wc), i8(we), None, T, N, K, torch.float32, 7, 7, parts=2, block=blk), want, f"b{blk} split {v} NaN")
         finally:
             L().bfpq_tune(TUNE_I8_VARIANT, -1)
 
@@ -178,12 +88,12 @@ def test_random_opt_vit_shapes(blk, shape):
     g = torch.Generator(device=DEV).manual_seed(N + K + blk)
     w = torch.randn(N, K, generator=g, device=DEV) * 0.02
     wc, we = bfp_ops.float_to_bfp_packed(w, m, blk, code_bits=8)
-    wv = GB.values(wc.view(N, K).int(), we.int(), m, blk)
+    wv = G.values(wc.view(N, K).int(), we.int(), m, block=blk)
     cfg = bfp_ops.unpack_bfp_args(dict(mant_bits=m, block_size=blk, num_format='bfp', sparsity_num_format='bfp', rounding_mode='determ', device=DEV))
     for T in (1, 16, 197, 2048):
         x = torch.randn(T, K, generator=g, device=DEV)
         xc, xe = native.act_codes(x, m, 1e-8, None, block_size=blk)
-        xv = GB.values(xc.int(), xe.int(), m, blk)
+        xv = G.values(xc.int(), xe.int(), m, block=blk)
         assert torch.equal(xv.float(), bfp_ops.float_to_bfp_blocked(x, **cfg, identifier='in'))
         want, absprod = xv @ wv.t(), xv.abs() @ wv.abs().t()
         got = native.hbfp_linear_i8(x, wc.view(N, K), we, m, m, block_size=blk)

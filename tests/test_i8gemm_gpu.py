@@ -1,5 +1,6 @@
 """HBFP5-HBFP8 on the int8 matrix unit (bfpq_i8gemm.hip), bit for bit on exact operands and within the fp32 summation bound on random
-data (run with `-m gpu` on an MI355X).
+data (run with `-m gpu` on an MI355X).  The drivers here (certified, expected, run_c, every_plan, ...) take the block; the runs at blocks
+16 and 32 are in tests/test_i8gemm_blocks_gpu.py.
 
 Exact operands come from tests/gemm_cases.py: every case asserts the certificate first (every fp32 partial sum exact in any order), so
 the fp64 product rounded once to the output dtype IS the expected output, whatever tile variant, K split or kernel the plan picks.
@@ -37,49 +38,56 @@ def stream():
     return ctypes.c_void_p(torch.cuda.current_stream(torch.device(DEV)).cuda_stream)
 
 
-def certified(T, N, K, xm, wm, seed, nm=(0, 0), with_bias=False):
+def certified(T, N, K, xm, wm, seed, nm=(0, 0), with_bias=False, block=64):
     """exact operands with the widest exponent spreads (3 down to 1) that keep the certificate; returns the codes / exponents and the bias"""
     for sx, sw in ((3, 3), (3, 2), (2, 2), (2, 1), (1, 1)):
-        xc, xe = G.hbfp_operand(T, K, xm, -3, sx, seed, device=DEV)
-        wc, we = G.hbfp_operand(N, K, wm, -2, sw, seed + 1, nm=nm, pattern=(5, 7, 2), device=DEV)
+        xc, xe = G.hbfp_operand(T, K, xm, -3, sx, seed, device=DEV, block=block)
+        wc, we = G.hbfp_operand(N, K, wm, -2, sw, seed + 1, nm=nm, pattern=(5, 7, 2), device=DEV, block=block)
         bq = None
         if with_bias:
             g = torch.Generator(device=DEV).manual_seed(seed + 2)
             bq = torch.randint(-60, 61, (N,), generator=g, device=DEV).double() * 4
-        q, worst = G.exact_certificate(xc, xe, xm, wc, we, wm, bq)
+        q, worst = G.exact_certificate(xc, xe, xm, wc, we, wm, bq, block=block)
         if worst < 2.0 ** 24:
             bias = None if bq is None else bq * q
             return xc, xe, wc, we, bias
-    raise AssertionError(f"no certified spread for T={T} N={N} K={K} xm={xm} wm={wm}")
+    raise AssertionError(f"no certified spread for T={T} N={N} K={K} xm={xm} wm={wm} block {block}")
 
 
-def expected(xc, xe, xm, wc, we, wm, bias, dt):
-    want = G.values(xc, xe, xm) @ G.values(wc, we, wm).t()
+def expected(xc, xe, xm, wc, we, wm, bias, dt, block=64):
+    want = G.values(xc, xe, xm, block=block) @ G.values(wc, we, wm, block=block).t()
     if bias is not None:
         want = want + bias.view(1, -1)
     return want.to(dt)
 
 
-def run_c(route, xc8, xe8, wc8, we8, bias, T, N, K, dt, wm, xm, parts=1):
-    """one C entry point directly: 'decode8', 'tile' (bfpq_hbfp_linear_i8) or 'split' (bfpq_hbfp_linear_i8_splitk with `parts`)"""
+def family(block):
+    """the C entries of a block: (name suffix, block argument) -- block 64 '' and none, blocks 16 / 32 the `b` entries and the block"""
+    return ('', ()) if block == 64 else ('b', (block,))
+
+
+def run_c(route, xc8, xe8, wc8, we8, bias, T, N, K, dt, wm, xm, parts=1, block=64):
+    """one C entry point of the block's family directly: 'decode8', 'tile' (bfpq_hbfp_linear_i8[b]) or 'split'
+    (bfpq_hbfp_linear_i8[b]_splitk with `parts`)"""
+    sfx, blk = family(block)
+    ops, tail = (ptr(xc8), ptr(xe8), ptr(wc8), ptr(we8), ptr(bias)), (*blk, DT_CODE[dt], wm, xm, stream())
     out = torch.empty((T, N), dtype=dt, device=DEV)
     if route == 'decode8':
-        slabs = torch.empty(int(L().bfpq_hbfp_linear_decode8_ws(T, N, K)), dtype=torch.float32, device=DEV)
-        rc = L().bfpq_hbfp_linear_decode8(ptr(xc8), ptr(xe8), ptr(wc8), ptr(we8), ptr(bias), ptr(out), ptr(slabs), T, N, K, DT_CODE[dt], wm, xm, stream())
+        slabs = torch.empty(int(getattr(L(), f"bfpq_hbfp_linear_decode8{sfx}_ws")(T, N, K, *blk)), dtype=torch.float32, device=DEV)
+        rc = getattr(L(), f"bfpq_hbfp_linear_decode8{sfx}")(*ops, ptr(out), ptr(slabs), T, N, K, *tail)
     elif route == 'tile':
-        rc = L().bfpq_hbfp_linear_i8(ptr(xc8), ptr(xe8), ptr(wc8), ptr(we8), ptr(bias), ptr(out), T, N, K, DT_CODE[dt], wm, xm, stream())
+        rc = getattr(L(), f"bfpq_hbfp_linear_i8{sfx}")(*ops, ptr(out), T, N, K, *tail)
     else:
         slabs = torch.empty((parts, T, N), dtype=torch.float32, device=DEV)
-        rc = L().bfpq_hbfp_linear_i8_splitk(ptr(xc8), ptr(xe8), ptr(wc8), ptr(we8), ptr(bias), ptr(out), ptr(slabs), parts, T, N, K,
-                                            DT_CODE[dt], wm, xm, stream())
+        rc = getattr(L(), f"bfpq_hbfp_linear_i8{sfx}_splitk")(*ops, ptr(out), ptr(slabs), parts, T, N, K, *tail)
     assert rc == 0, (route, rc)
     return out
 
 
 def assert_bits(got, want, what):
     g, w = got.cpu(), want.cpu()
-    same = (g.view(torch.int16 if g.dtype != torch.float32 else torch.int32) == w.view(torch.int16 if w.dtype != torch.float32 else torch.int32))
-    same |= torch.isnan(g) & torch.isnan(w)
+    iv = torch.int16 if g.dtype != torch.float32 else torch.int32
+    same = (g.view(iv) == w.view(iv)) | (torch.isnan(g) & torch.isnan(w))
     if not bool(same.all()):
         i = int((~same).flatten().nonzero()[0])
         raise AssertionError(f"{what}: {int((~same).sum())}/{same.numel()} outputs differ; first at flat {i}: got {float(g.flatten()[i])!r} "
@@ -90,23 +98,26 @@ def i8(t):
     return t.to(torch.int8).contiguous()
 
 
-def every_plan(xc, xe, xm, wc, we, wm, bias, T, N, K, dt, what):
+def every_plan(xc, xe, xm, wc, we, wm, bias, T, N, K, dt, what, block=64, variants=range(3)):
     """the public wrapper, the decode kernel, and (K % 256 == 0) every tile variant unsplit and split in 2, 3 and the maximum parts"""
-    want = expected(xc, xe, xm, wc, we, wm, bias, dt)
+    want = expected(xc, xe, xm, wc, we, wm, bias, dt, block=block)
     b = None if bias is None else bias.to(dt)
     xq = (i8(xc), i8(xe))
-    got = native.hbfp_linear_i8(torch.empty((T, K), dtype=torch.bfloat16, device=DEV), i8(wc), i8(we), wm, xm, bias=b, out_dtype=dt, xq=xq)
+    got = native.hbfp_linear_i8(torch.empty((T, K), dtype=dt, device=DEV), i8(wc), i8(we), wm, xm, bias=b, out_dtype=dt, xq=xq,
+                                block_size=block)
     assert_bits(got, want, f"{what} default plan")
-    assert_bits(run_c('decode8', *xq, i8(wc), i8(we), b, T, N, K, dt, wm, xm), want, f"{what} decode8")
-    if not L().bfpq_hbfp_linear_i8_ok(T, N, K):
+    assert_bits(run_c('decode8', *xq, i8(wc), i8(we), b, T, N, K, dt, wm, xm, block=block), want, f"{what} decode8")
+    sfx, blk = family(block)
+    if not getattr(L(), f"bfpq_hbfp_linear_i8{sfx}_ok")(T, N, K, *blk):
         return
     trips = K // 256
     try:
-        for v in range(3):
+        for v in variants:
             assert L().bfpq_tune(TUNE_I8_VARIANT, v) == 0
-            assert_bits(run_c('tile', *xq, i8(wc), i8(we), b, T, N, K, dt, wm, xm), want, f"{what} variant {v}")
+            assert_bits(run_c('tile', *xq, i8(wc), i8(we), b, T, N, K, dt, wm, xm, block=block), want, f"{what} variant {v}")
             for p in sorted({2, 3, trips} - {1}):
-                assert_bits(run_c('split', *xq, i8(wc), i8(we), b, T, N, K, dt, wm, xm, parts=p), want, f"{what} variant {v} parts {p}")
+                assert_bits(run_c('split', *xq, i8(wc), i8(we), b, T, N, K, dt, wm, xm, parts=p, block=block), want,
+                            f"{what} variant {v} parts {p}")
     finally:
         L().bfpq_tune(TUNE_I8_VARIANT, -1)
 

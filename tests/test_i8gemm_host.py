@@ -79,10 +79,11 @@ def test_shapes_and_pointers():
     assert c4(P, P, 12, s) == E_ARG and c4(P, P, -8, s) == E_ARG and c4(Z, P, 8, s) == E_ARG and c4(P, P, 0, s) == 0
 
 
-def test_python_ok():
+def test_python_ok_every_block():
     ok = native.hbfp_linear_i8_ok
     assert ok(1, 4096, 11008, 7, 7) and ok(2048, 11008, 4096, 5, 5) and ok(3, 16, 64, 1, 1)
-    assert not ok(1, 4096, 4096, 8, 7) and not ok(1, 4096, 4096, 7, 0) and not ok(1, 4096, 4096, 7, 7, block_size=32)
+    assert ok(1, 4096, 4096, 7, 7, block_size=32) and ok(1, 4096, 4096, 7, 7, block_size=16)        # one predicate for every block
+    assert not ok(1, 4096, 4096, 8, 7) and not ok(1, 4096, 4096, 7, 0) and not ok(1, 4096, 4096, 7, 7, block_size=48)
     assert not ok(1, 24, 256, 7, 7) and not ok(1, 16, 96, 7, 7)
 
 
