@@ -380,6 +380,10 @@ int bfpq_hbfp_linear_decode8b(const void* xcodes_dev, const int8_t* xexp_dev, co
 /* 4-bit codes (two's-complement nibbles, low nibble first, as bfpq_quantize_nm writes them) -> int8 codes, so that HBFP4 weights
  * run on the entry points above; n_codes % 8 == 0, codes4_dev 4-byte and codes8_dev 8-byte aligned. */
 int bfpq_codes4_to_i8(const void* codes4_dev, void* codes8_dev, int64_t n_codes, void* stream);
+/* *flag_dev = 1 if some byte of the exponent arrays exp_a [n_a] / exp_b [n_b] (either may be empty) is 127, else 0: the blocks whose
+ * 2^e can overflow the operand dtype.  A stochastically rounded block there may hold +-2^m codes (the reference's clamp bound is
+ * infinite), which no int8 or e4m3 operand carries, so the caller redoes such a call on the fake-quantize route. */
+int bfpq_exp_top_flag(const int8_t* exp_a, int64_t n_a, const int8_t* exp_b, int64_t n_b, int* flag_dev, void* stream);
 
 /* the first BFPQ_SELECT_STATE_BYTES of ws_dev, as read back by a host that wants tau / counts (little-endian) */
 typedef struct bfpq_select_state {

@@ -56,11 +56,26 @@ def _mix_seed(seed, salt):
     return z or 1
 
 
+@contextlib.contextmanager
+def _replay_seeds(seeds):
+    """'stoc' seeds drawn inside (on this thread) are taken from `seeds` in order, without touching torch's generator: a call that
+    redoes itself on another route rounds with the seeds it already drew"""
+    prev = getattr(_seed_salt, 'replay', None)
+    _seed_salt.replay = list(seeds)
+    try:
+        yield
+    finally:
+        _seed_salt.replay = prev
+
+
 def _seed_for(mode):
     """0 -> round-half-even; otherwise a non-zero 62-bit seed taken from torch's CPU generator (salted by seed_salt)"""
     if mode == rounding_modes.DETERM:
         return 0
     if mode == rounding_modes.STOC:
+        replay = getattr(_seed_salt, 'replay', None)
+        if replay:
+            return replay.pop(0)
         seed = int(torch.randint(1, 2 ** 62, (1,)).item())
         salt = getattr(_seed_salt, 'value', 0)
         return _mix_seed(seed, salt) if salt else seed
@@ -866,11 +881,118 @@ def _cached_route(x, w, a, cache):
     return linear_route(T, w.shape[0], K, code_bits_for(m), m, m, decode_tokens=0, mx8_min_tokens=CACHED_MX8_MIN_TOKENS)
 
 
-def _gen_bfp_op(op, name, bfp_args, transpose=False, cache=None):
+class StocMatrixUnit:
+    """Opt-in switch of a BFPLinear: its stochastically rounded ('stoc') inference forwards run on a matrix unit instead of F.linear on two
+    fp32 operands.  Both operands are rounded with the seeds the fake route draws, straight into codes (native.stoc_codes); nothing is
+    cached -- the reference draws fresh noise for the weight in every forward.  matrix_unit: True (the block-scaled unit where _stoc_route
+    allows, else the int8 unit) or 'int8'.  stoc_mx_calls / stoc_i8_calls count the forwards each unit ran, fallbacks the calls redone on
+    the fake route because a block's exponent could overflow the dtype."""
+
+    def __init__(self, matrix_unit=True):
+        self.matrix_unit = matrix_unit_value(matrix_unit)
+        self.stoc_mx_calls = 0
+        self.stoc_i8_calls = 0
+        self.fallbacks = 0
+
+
+# the stochastic matrix-unit route from this many tokens on, by operand dtype (None: never).  Measured against the fake 'stoc' route, both
+# eager (the route reads a flag back per call), profiles/r07_stoc_linear.json: bf16 LLaMA-7B rows win from 512 tokens on (1.11-5.96x) and
+# lose at 1-16 tokens (0.61-0.99x); fp32 OPT-125m rows lose at every count up to 2048 (0.61-0.90x).  A dtype not listed: the bf16 entry.
+STOC_MIN_TOKENS = {torch.bfloat16: 512, torch.float32: None}
+
+
+def _stoc_route(T, N, K, a, matrix_unit, dtype=None):
+    """the GEMM of a 'stoc' forward of T tokens on an [N, K] weight under BFPLinear.enable_stochastic_matrix_unit(matrix_unit), for a
+    configuration _stoc_eligible accepts, operands of `dtype`: 'mx8', 'int8' or 'fake'"""
+    m, block = a['mant_bits'], a['block_size']
+    lim = STOC_MIN_TOKENS.get(dtype, STOC_MIN_TOKENS[torch.bfloat16])
+    if not matrix_unit or T < 1 or lim is None or T < lim:
+        return 'fake'
+    if (matrix_unit is True and T >= CACHED_MX8_MIN_TOKENS and block == 64 and m <= 4
+            and native.hbfp_linear_mx8_ok(T, N, K, m, m, block)):
+        return 'mx8'
+    if native.hbfp_linear_i8_ok(T, N, K, m, m, block):
+        return 'int8'
+    return 'fake'
+
+
+def _stoc_eligible(x, w, bias, a):
+    """the forwards the stochastic matrix-unit route takes (the caller checks no_grad and the op): 'stoc', 'bfp' in both formats,
+    blocks 64 / 32 / 16, 1..7 mantissa bits, bf16 or fp32 operands of one dtype on one ROCm device, a 2-D weight, no bias or an fp32
+    one, pruning as the cached route takes it plus quantize-first unstructured weights"""
+    if (a['rounding_mode'] != rounding_modes.STOC or a['num_format'] != 'bfp' or a['sparsity_num_format'] != 'bfp'
+            or a['block_size'] not in (64,) + native.I8_BLOCKS or not (1 <= a['mant_bits'] <= 7)
+            or w.dim() != 2 or x.dtype != w.dtype or x.dtype not in (torch.bfloat16, torch.float32)
+            or x.device.type != 'cuda' or x.device != w.device or torch.compiler.is_compiling()
+            or (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())   # (the exponent check reads a flag back)
+            or (bias is not None and bias.dtype != torch.float32)):
+        return False
+    if a['in_sparsity'] == True:  # noqa: E712
+        if a['sparsity_mode'] == 'structured':
+            if not (0 < a['N'] <= a['M']):
+                return False
+        elif a['sparsity_mode'] != 'unstructured' or not (0 < a['sparsity_frac'] <= 1):
+            return False
+    if a['w_sparsity'] == True:  # noqa: E712
+        if a['sparsity_mode'] == 'unstructured':
+            if not (0 < a['sparsity_frac'] <= 1):
+                return False
+        elif a['sparsity_mode'] != 'structured' or not (0 < a['N'] <= a['M']) or a['M'] not in (2, 4, 8):
+            return False
+    return True
+
+
+def _weight_sparsity(a):
+    """the weight operand's pruning as an ActSparsity (None: dense), as float_to_bfp_blocked(identifier='w') applies it"""
+    if a['w_sparsity'] != True:  # noqa: E712
+        return None
+    return native.ActSparsity.from_bfp_args(dict(a, in_sparsity=True))
+
+
+def _stoc_linear(x, w, bias, a, stoc):
+    """F.linear(Q_in(x), Q_w(w), bias) of a 'stoc' forward on a matrix unit, or None when _stoc_route says 'fake' (nothing drawn then).
+    The two seeds are drawn as the fake route draws them (activation first), so the operands are the fake route's, bit for bit, and
+    torch's generator ends where it would.  A block whose exponent could overflow the dtype redoes the call on the fake route with the
+    same seeds (one flag read back per call)."""
+    if not _stoc_eligible(x, w, bias, a):
+        return None
+    N, K = w.shape
+    x2 = x.reshape(-1, K)
+    T = x2.shape[0]
+    route = _stoc_route(T, N, K, a, stoc.matrix_unit, x.dtype)
+    if route == 'fake':
+        return None
+    m, eps, block = a['mant_bits'], a['epsilon'], a['block_size']
+    sx = _seed_for(rounding_modes.STOC)
+    sw = _seed_for(rounding_modes.STOC)
+    xc, xe = native.stoc_codes(x2.contiguous(), block, m, eps, sx, native.ActSparsity.from_bfp_args(a))
+    wc, we = native.stoc_codes(w.contiguous(), block, m, eps, sw, _weight_sparsity(a))
+    flag = native.exp_top_flag(xe, we)
+    if route == 'mx8':
+        stoc.stoc_mx_calls += 1
+        out = native.hbfp_linear_mx8(x2, *native.mx8_from_hbfp(wc, we, K, m, 8), m, eps, bias=bias, out_dtype=torch.float32,
+                                     x_image=native.mx8_from_hbfp(xc, xe, K, m, 8))
+    else:
+        stoc.stoc_i8_calls += 1
+        out = native.hbfp_linear_i8(x2, wc, we, m, m, eps, bias=bias, out_dtype=torch.float32, xq=(xc, xe), block_size=block)
+    if int(flag.item()):
+        stoc.fallbacks += 1
+        with _replay_seeds((sx, sw)):
+            xq, wq = MxM_pre_processing(x, w, False, **a)
+        return F.linear(xq, wq, bias)
+    return out.view(tuple(x.shape[:-1]) + (N,))
+
+
+def _gen_bfp_op(op, name, bfp_args, transpose=False, cache=None, stoc=None):
     """reference: bfp_ops.py:160-192 -- wraps `op(x, w, ...)` so that both operands are BFP-quantized
-    (and sparsified) on the way in and the output gradient on the way back.  cache: optional WeightCache."""
+    (and sparsified) on the way in and the output gradient on the way back.  cache: optional WeightCache; stoc: optional
+    StocMatrixUnit."""
     def bfp_op(x, w, *args, **kwargs):
         if not torch.is_grad_enabled():                 # inference: same values, no autograd nodes to build
+            if stoc is not None and stoc.matrix_unit and op is F.linear and transpose is False:
+                out = _stoc_linear(x, w, args[0] if args else kwargs.get('bias'), bfp_args, stoc)
+                if out is not None:
+                    return out
             route = _cached_route(x, w, bfp_args, cache) if cache is not None and cache.matrix_unit and op is F.linear else 'fake'
             if route in ('int8', 'mx8'):
                 bias = args[0] if args else kwargs.get('bias')
@@ -888,12 +1010,13 @@ def _gen_bfp_op(op, name, bfp_args, transpose=False, cache=None):
 
     bfp_op.__name__ = _get_op_name(name, **bfp_args)
     bfp_op.weight_cache = cache
+    bfp_op.stoc_matrix_unit = stoc
     return bfp_op
 
 
-def _get_bfp_op(op, name, bfp_args, transpose=False, cache=None):
+def _get_bfp_op(op, name, bfp_args, transpose=False, cache=None, stoc=None):
     """reference: bfp_ops.py:194-200 (its cache dict is a local, so there too every layer gets its own op)"""
-    return _gen_bfp_op(op, name, bfp_args, transpose, cache)
+    return _gen_bfp_op(op, name, bfp_args, transpose, cache, stoc)
 
 
 _BFP_ARG_DEFAULTS = dict(num_format='fp32', sparsity_num_format='fp32', rounding_mode='stoc', epsilon=1e-8,
@@ -941,7 +1064,11 @@ class _BFPModule:
         N % 16 == 0 and K % 64 == 0; WeightCache.i8_calls counts these calls).  Any other value raises ValueError."""
         cache = WeightCache(self, matrix_unit=matrix_unit) if enabled else None
         self._weight_cache = cache                               # (patch.prime_weight_caches fills it for a whole model in one list call)
-        op = _get_bfp_op(self._functional, self._op_name, self.bfp_args, cache=cache)
+        return self._bfp_rebuild_op()
+
+    def _bfp_rebuild_op(self):
+        op = _get_bfp_op(self._functional, self._op_name, self.bfp_args, cache=getattr(self, '_weight_cache', None),
+                         stoc=getattr(self, '_stoc_matrix_unit', None))
         if hasattr(self, 'linear_op'):
             self.linear_op = op
         else:
@@ -980,3 +1107,13 @@ class BFPLinear(_BFPModule, torch.nn.Linear):
 
     def forward(self, input):
         return self._bfp_forward(self.linear_op, input, self.weight, self.bias)
+
+    def enable_stochastic_matrix_unit(self, matrix_unit=True):
+        """opt in to (or, with False, out of) running 'stoc' inference forwards on a matrix unit (StocMatrixUnit): True takes the
+        block-scaled unit where _stoc_route allows and the int8 unit elsewhere, 'int8' the int8 unit only; any other value raises
+        ValueError.  It applies under no_grad to 'bfp' configurations with bf16 or fp32 operands of one dtype, a 2-D weight and no
+        bias or an fp32 one; every other forward runs as without it.  The operands are those of the fake route for the same seeds; the
+        output is fp32, the block products summed exactly and in fp32 across blocks.  Independent of enable_weight_cache."""
+        mu = matrix_unit_value(matrix_unit)
+        self._stoc_matrix_unit = StocMatrixUnit(mu) if mu else None
+        return self._bfp_rebuild_op()

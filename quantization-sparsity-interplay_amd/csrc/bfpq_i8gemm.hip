@@ -394,6 +394,30 @@ __global__ void __launch_bounds__(256) k_i8_decode(const int8_t* __restrict__ wc
     *reinterpret_cast<float4*>(slabs + ((size_t)slice * Tpad + blockIdx.y * 16 + r) * N + n0 + 4 * q) = make_float4(acc[0], acc[1], acc[2], acc[3]);
 }
 
+// exponent bytes of two operands -> *flag = 1 when some block's byte is 127 (the saturated top exponent: the only blocks whose 2^e can
+// overflow the operand dtype, where a stochastically rounded value may be +-2^m codes).  One thread = 4 bytes of a 4-aligned run;
+// the stray bytes of each run's ends are read one by one.  Threads that find nothing store nothing.
+__device__ __forceinline__ bool has_top_exp(uint32_t w) { return ((w ^ 0x7f7f7f7fu) - 0x01010101u) & ~(w ^ 0x7f7f7f7fu) & 0x80808080u; }
+__global__ void __launch_bounds__(256) k_exp_top_flag(const int8_t* __restrict__ ea, int64_t na, const int8_t* __restrict__ eb, int64_t nb,
+                                                      int* __restrict__ flag)
+{
+    bool hit = false;
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
+    auto run = [&](const int8_t* e, int64_t n) __attribute__((always_inline)) {
+        const int64_t mis = (int64_t)((4u - (reinterpret_cast<uintptr_t>(e) & 3u)) & 3u);     // bytes in front of the first aligned word
+        const int64_t head = mis < n ? mis : n;
+        const int64_t words = (n - head) / 4;
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(e + head);
+        for (int64_t i = tid; i < words; i += step) hit = hit || has_top_exp(w[i]);
+        if (tid < head) hit = hit || e[tid] == 127;
+        const int64_t tail0 = head + 4 * words;
+        if (tid < n - tail0) hit = hit || e[tail0 + tid] == 127;
+    };
+    if (ea) run(ea, na);
+    if (eb) run(eb, nb);
+    if (hit) *flag = 1;
+}
+
 // one thread = 8 codes (4 bytes of nibbles -> 8 bytes)
 __global__ void __launch_bounds__(256) k_codes4_to_i8(const uint32_t* __restrict__ in, uint2* __restrict__ out, int64_t n_items)
 {
@@ -624,6 +648,19 @@ int bfpq_hbfp_linear_decode8b(const void* xcodes, const int8_t* xexp, const void
 {
     if (!small_block(block_size)) return BFPQ_E_ARG;
     return i8_decode(xcodes, xexp, wcodes, wexp, bias, out, slabs, T, N, K, block_size, out_dtype, w_mant_bits, x_mant_bits, stream);
+}
+
+int bfpq_exp_top_flag(const int8_t* exp_a, int64_t n_a, const int8_t* exp_b, int64_t n_b, int* flag, void* stream)
+{
+    if (n_a < 0 || n_b < 0 || !flag || (n_a && !exp_a) || (n_b && !exp_b)) return BFPQ_E_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const hipError_t h = hipMemsetAsync(flag, 0, sizeof(int), s);
+    if (h != hipSuccess) return (int)h;
+    const int64_t most = (n_a > n_b ? n_a : n_b) / 4 + 4;
+    int64_t g = (most + 255) / 256;
+    if (g > 1024) g = 1024;
+    hipLaunchKernelGGL(k_exp_top_flag, dim3((unsigned)g), dim3(256), 0, s, n_a ? exp_a : nullptr, n_a, n_b ? exp_b : nullptr, n_b, flag);
+    return (int)hipGetLastError();
 }
 
 int bfpq_codes4_to_i8(const void* codes4, void* codes8, int64_t n_codes, void* stream)

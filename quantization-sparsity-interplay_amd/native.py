@@ -83,6 +83,7 @@ PROTOTYPES = {
     "bfpq_hbfp_linear_decode8_ws": (_i64, [_i64, _i64, _i64]),
     "bfpq_hbfp_linear_decode8": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp]),
     "bfpq_codes4_to_i8": (_i32, [_vp, _vp, _i64, _vp]),
+    "bfpq_exp_top_flag": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp]),
     "bfpq_hbfp_linear_i8b_ok": (_i32, [_i64, _i64, _i64, _i32]),
     "bfpq_hbfp_linear_i8b_parts": (_i32, [_i64, _i64, _i64, _i32]),
     "bfpq_hbfp_linear_i8b": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
@@ -991,6 +992,45 @@ def act_codes(x, mant_bits, epsilon, act, codes_out=None, exps_out=None, block_s
     return c, e
 
 
+def stoc_codes(t, block_size, mant_bits, epsilon, seed, act=None):
+    """int8 codes [rows, cols] + int8 exponents [rows, cols/block_size] of the 2-D tensor t, HBFP(mant_bits + 1) rounded
+    stochastically with `seed`, pruned by `act` (ActSparsity or None) -- the operand that bfp_ops.float_to_bfp_blocked(t, ..., 'stoc')
+    makes with that seed, as codes.  Each form is the launch that route makes, with codes + exponents as its outputs: the quantizer picks
+    its arithmetic tier per wave and its dither per element from the seed and the element's index alone, never from what it writes, so
+    code * 2^(exp - mant_bits) is that route's value bit for bit.  The one exception is a block whose 2^e overflows the dtype: there the
+    reference's clamp bound is infinite and a value may be +-2^m codes; exp_top_flag finds such blocks.  Dense and N:M: one launch
+    (bfpq_quantize_nm).  Unstructured, prune first: the selection launch + the threshold quantizer.  Quantize first: quantize once to
+    the tensor and its codes with one dither, select over the quantized tensor, then zero the pruned codes (the exponents stay those of
+    Q(t), as in act_codes)."""
+    if act is None or act.mode == 'structured':
+        N, M = (act.N, act.M) if act is not None else (0, 0)
+        # (N:M off the single-pass kernel is a pruning launch + a quantize launch that meet in the dequantised tensor)
+        _, c, e = quantize_nm(t, block_size, mant_bits, epsilon, N=N, M=M, sparsify_first=(act is None or act.first == 's'),
+                              want_deq=M > 0 and not is_fused(t, block_size, N, M), code_bits=8, want_exp=True, stoch_seed=seed)
+        return c, e
+    k = _prune_count(t, act.frac)
+    ws = _act_workspace(t.device)
+    if act.first == 's':
+        select_threshold(t, k, ws)
+        _, c, e = quantize_threshold(t, ws, block_size, mant_bits, epsilon, want_deq=not is_fused(t, block_size), code_bits=8, want_exp=True,
+                                     stoch_seed=seed)
+        return c, e
+    q, c, e = quantize_nm(t, block_size, mant_bits, epsilon, code_bits=8, want_exp=True, stoch_seed=seed)
+    select_threshold(q, k, ws)
+    sq = threshold_apply(q, ws).view(c.shape)
+    return torch.where(sq == 0, torch.zeros((), dtype=c.dtype, device=c.device), c), e
+
+
+def exp_top_flag(exp_a, exp_b):
+    """int32 device tensor [1]: 1 when an exponent byte of exp_a or exp_b is 127 (bfpq_exp_top_flag), else 0"""
+    dev = exp_a.device
+    with torch.cuda.device(dev):
+        flag = torch.empty(1, dtype=torch.int32, device=dev)
+        a, b = exp_a.contiguous(), exp_b.contiguous()
+        check(load_library().bfpq_exp_top_flag(_ptr(a), a.numel(), _ptr(b), b.numel(), _ptr(flag), _stream(a)), "bfpq_exp_top_flag")
+    return flag
+
+
 def quantize_mx8(x, mant_bits, epsilon=1e-8, act=None):
     """a 2-D tensor [T, K] -> its HBFP(mant_bits + 1) block-64 image for the block-scaled matrix unit: e4m3 bytes [T, K] + E8M0
     scales [T, K/64], in one pass (bfpq_quantize_mx8); the two-step route (int8 codes + mx8_from_hbfp) only for shapes it refuses.
@@ -1078,11 +1118,11 @@ def hbfp_linear_mx8_ok(T, N, K, w_mant_bits, x_mant_bits, block_size=64):
     return block_size == 64 and 1 <= w_mant_bits <= 4 and 1 <= x_mant_bits <= 4 and bool(load_library().bfpq_hbfp_linear_mx8_ok(T, N, K))
 
 
-def hbfp_linear_mx8(x, w8, wscale, x_mant_bits, epsilon=1e-8, bias=None, out_dtype=None, act=None):
+def hbfp_linear_mx8(x, w8, wscale, x_mant_bits, epsilon=1e-8, bias=None, out_dtype=None, act=None, x_image=None):
     """out = Q(x) @ W^T (+ bias) for any number of tokens on the block-scaled matrix instruction: x is quantized to
     HBFP(x_mant_bits + 1) block 64 (int8 codes + exponents), turned into its e4m3 / E8M0 image and multiplied with the
     weight's image (mx8_from_hbfp of the packed weight, made once).  act (ActSparsity or None): the activation is pruned first
-    (quantize_mx8)."""
+    (quantize_mx8).  x_image: the activation's image made beforehand (e4m3 [T, K], E8M0 [T, K/64]); x then only gives shape."""
     require_device_tensor(x)
     L = load_library()
     K = x.shape[-1]
@@ -1093,7 +1133,7 @@ def hbfp_linear_mx8(x, w8, wscale, x_mant_bits, epsilon=1e-8, bias=None, out_dty
     dev = x.device
     out_dtype = out_dtype or x.dtype
     with torch.cuda.device(dev):
-        x8, xs = _shared_image(x.reshape(T, K), x_mant_bits, epsilon, act)
+        x8, xs = x_image if x_image is not None else _shared_image(x.reshape(T, K), x_mant_bits, epsilon, act)
         out = torch.empty((T, N), dtype=out_dtype, device=dev)
         if bias is not None:
             bias = bias.to(out_dtype).contiguous()

@@ -10,12 +10,15 @@ from . import native
 from .bfp import bfp_ops
 
 
-def patch_linear_layers(model, bfp_args, skip=("lm_head", "classifier", "score"), convs=False, cache_weights=False, matrix_unit=False):
+def patch_linear_layers(model, bfp_args, skip=("lm_head", "classifier", "score"), convs=False, cache_weights=False, matrix_unit=False,
+                        stoc_matrix_unit=False):
     """Replace nn.Linear children by bfp_ops.BFPLinear(**bfp_args) that reuse weight / bias.  Modules whose
     qualified name ends with an entry of `skip` stay as they are (the reference leaves the LM heads alone).
     matrix_unit (False, True or 'int8'): with cache_weights, the cached Linear forward's matrix-unit route (BFPLinear.enable_weight_cache).
+    stoc_matrix_unit (False, True or 'int8'): the 'stoc' inference forwards' matrix-unit route (BFPLinear.enable_stochastic_matrix_unit).
     Returns the list of patched module names."""
     bfp_ops.matrix_unit_value(matrix_unit)                  # (a wrong value raises before any module is replaced)
+    stoc_matrix_unit = bfp_ops.matrix_unit_value(stoc_matrix_unit)
     patched = []
     for parent_name, parent in list(model.named_modules()):
         for child_name, child in list(parent.named_children()):
@@ -35,6 +38,8 @@ def patch_linear_layers(model, bfp_args, skip=("lm_head", "classifier", "score")
             new.train(child.training)
             if cache_weights:
                 new.enable_weight_cache(matrix_unit=matrix_unit if isinstance(new, bfp_ops.BFPLinear) else False)
+            if stoc_matrix_unit and isinstance(new, bfp_ops.BFPLinear):
+                new.enable_stochastic_matrix_unit(stoc_matrix_unit)
             setattr(parent, child_name, new)
             patched.append(full)
     return patched
