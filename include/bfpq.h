@@ -380,6 +380,31 @@ int bfpq_hbfp_linear_decode8b(const void* xcodes_dev, const int8_t* xexp_dev, co
 /* 4-bit codes (two's-complement nibbles, low nibble first, as bfpq_quantize_nm writes them) -> int8 codes, so that HBFP4 weights
  * run on the entry points above; n_codes % 8 == 0, codes4_dev 4-byte and codes8_dev 8-byte aligned. */
 int bfpq_codes4_to_i8(const void* codes4_dev, void* codes8_dev, int64_t n_codes, void* stream);
+/* ---- 2:4-compressed packed weights (format sp24) and their few-token product on v_smfmac_i32_16x16x64_i8 -------------------------
+ * A weight pruned N:M with M = 4, N <= 2 along K (_structured_N_M_sparsity, reference bfp_ops.py:73-91) and quantized to HBFP block 64
+ * holds at most 2 non-zero codes per group of 4.  sp24 keeps those two codes and their 2-bit positions, tiled for the decode kernel
+ * (16 rows per tile; per lane and block of 64 K: 8 values + 16 position bits; layout in csrc/bfpq_sp24.hip), and the [N, K/64] int8
+ * exponents of the dense packed weight unchanged (-128 = NaN block).  N % 16 == 0, K % 64 == 0, code_bits 4 or 8:
+ *   vals_dev: N * K / 4 bytes (4-bit codes) or N * K / 2 bytes (8-bit codes); idx_dev: N * K / 8 bytes -- 0.391 / 0.641 B per weight
+ *   with the exponents.  All sp24 arrays 16-byte aligned.
+ * bfpq_sp24_pack: dense codes (as bfpq_quantize_nm writes them with code_bits 4 or 8, [N, K] elements) -> sp24.  status_dev[0]
+ * (int32, zeroed by the caller) is set to 1 if some group had more than 2 non-zero codes; a group with fewer keeps the lowest free
+ * positions, with zero values.  bfpq_sp24_unpack: the exact inverse, into codes of the same width (codes_dev) and / or int8 codes
+ * (codes8_dev, [N, K]); either may be NULL, not both. */
+int bfpq_sp24_pack(const void* codes_dev, void* vals_dev, void* idx_dev, int64_t N, int64_t K, int code_bits, int32_t* status_dev, void* stream);
+int bfpq_sp24_unpack(const void* vals_dev, const void* idx_dev, void* codes_dev, void* codes8_dev, int64_t N, int64_t K, int code_bits,
+                     void* stream);
+/* out[T, N] = x[T, K] W[N, K]^T (+ bias[N]) for 1 <= T <= BFPQ_SP24_MAX_TOKENS, W in sp24 form (w_mant_bits 1..3 for 4-bit codes, 1..7
+ * for 8-bit codes), x as int8 codes [T, K] + int8 exponents [T, K/64] (x_mant_bits 1..7), the product of the two fake-quantised operands
+ * of the reference (bfp_ops.py:187-190).  One sparse instruction per block: an exact integer sum, scaled once by the two block scales,
+ * added in block order in fp32; the K slices' fp32 slabs are added in slice order (with the bias) by a second launch.  An exponent of
+ * -128 on either side makes the block contribute NaN.  slabs_dev: bfpq_hbfp_linear_sp24_ws(T, N, K) floats (BFPQ_E_UNSUPPORTED for
+ * shapes this entry does not take).  xcodes_dev 16-byte aligned.  Checks return before anything is launched. */
+#define BFPQ_SP24_MAX_TOKENS 64
+int64_t bfpq_hbfp_linear_sp24_ws(int64_t T, int64_t N, int64_t K);
+int bfpq_hbfp_linear_sp24(const void* xcodes_dev, const int8_t* xexp_dev, const void* wvals_dev, const void* widx_dev, const int8_t* wexp_dev,
+                          const void* bias_dev, void* out_dev, float* slabs_dev, int64_t T, int64_t N, int64_t K, int code_bits,
+                          int out_dtype, int w_mant_bits, int x_mant_bits, void* stream);
 /* *flag_dev = 1 if some byte of the exponent arrays exp_a [n_a] / exp_b [n_b] (either may be empty) is 127, else 0: the blocks whose
  * 2^e can overflow the operand dtype.  A stochastically rounded block there may hold +-2^m codes (the reference's clamp bound is
  * infinite), which no int8 or e4m3 operand carries, so the caller redoes such a call on the fake-quantize route. */

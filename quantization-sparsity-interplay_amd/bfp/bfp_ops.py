@@ -659,6 +659,112 @@ class PackedBFP:
                    int(meta["block_size"]), int(meta["code_bits"]))
 
 
+SP24_DECODE_TOKENS = 64      # SparseBFP24.linear: up to this many tokens the sp24 kernel, more a transient expansion
+
+
+def sp24_config_check(a):
+    """raise ValueError unless configuration `a` (unpacked bfp_args) guarantees what the sp24 form holds: HBFP block 64, mant_bits 1..7,
+    round-half-even, weights pruned N:M with M == 4 and N <= 2 (either order: at most N non-zeros in every group of 4 along K)"""
+    if a['num_format'] != 'bfp' or a['sparsity_num_format'] != 'bfp' or a['block_size'] != 64 or not 1 <= a['mant_bits'] <= 7:
+        raise ValueError("sp24 holds HBFP block-64 weights with mant_bits 1..7 (got num_format=%r, block_size=%r, mant_bits=%r)"
+                         % (a['num_format'], a['block_size'], a['mant_bits']))
+    if a['rounding_mode'] != 'determ':
+        raise ValueError("an sp24 weight is quantized with round-half-even: rounding_mode must be 'determ'")
+    if not a['w_sparsity'] or a['sparsity_mode'] != 'structured' or int(a['M']) != 4 or not 0 < int(a['N']) <= 2:
+        raise ValueError("sp24 needs structured weight pruning N:4 with N <= 2 (got w_sparsity=%r, sparsity_mode=%r, N:M=%r:%r)"
+                         % (a['w_sparsity'], a['sparsity_mode'], a.get('N'), a.get('M')))
+
+
+class SparseBFP24:
+    """A 2:4 (or 1:4) pruned HBFP weight [N, K] held compressed: the two kept 4- or 8-bit codes of every group of 4 along K (`vals`),
+    their 2-bit positions (`idx`) and the [N, K/64] int8 block exponents of the dense packed weight (`exps`): 0.391 B per weight for
+    4-bit codes, 0.641 B for 8-bit codes (native.sp24_nbytes; layout in csrc/bfpq_sp24.hip).  linear() runs up to SP24_DECODE_TOKENS
+    tokens on the sparse int8 matrix instruction straight from this form; more tokens expand the weight, for that call only, to the
+    operand the dense PackedBFP route of the same token count reads, and run that route.  No dense copy is kept."""
+    block_size = 64
+
+    def __init__(self, vals, idx, exps, shape, dtype, mant_bits, code_bits):
+        self.vals, self.idx, self.exps = vals, idx, exps
+        self.shape, self.dtype = tuple(shape), dtype
+        self.mant_bits, self.code_bits = int(mant_bits), int(code_bits)
+
+    @classmethod
+    def from_packed(cls, p):
+        """the sp24 form of a 2-D PackedBFP (block 64, 4- or 8-bit codes); ValueError if some group of 4 holds more than 2 non-zeros"""
+        if p.block_size != 64 or p.code_bits not in (4, 8) or len(p.shape) != 2:
+            raise ValueError("sp24 holds 2-D block-64 weights of 4- or 8-bit codes")
+        N, K = p.shape
+        if not native.sp24_shape_ok(N, K):
+            raise ValueError(f"sp24 needs N % 16 == 0 and K % 64 == 0 (got N={N}, K={K})")
+        vals, idx = native.sp24_pack(p.codes, N, K, p.code_bits)
+        return cls(vals, idx, p.exps.contiguous(), p.shape, p.dtype, p.mant_bits, p.code_bits)
+
+    @classmethod
+    def from_bfp_args(cls, w, a):
+        """Q_w(w) of configuration `a` (unpacked bfp_args) in sp24 form.  Only configurations that guarantee the pattern are taken
+        (sp24_config_check); anything else raises ValueError.  The dense packed weight is made, compressed and dropped."""
+        sp24_config_check(a)
+        N, K = w.shape
+        if not native.sp24_shape_ok(N, K):
+            raise ValueError(f"sp24 needs N % 16 == 0 and K % 64 == 0 (got N={N}, K={K})")
+        return cls.from_packed(PackedBFP.from_bfp_args(w, a))
+
+    def to_packed(self):
+        """the dense PackedBFP (codes of the same width; a new tensor, not kept here)"""
+        N, K = self.shape
+        return PackedBFP(native.sp24_unpack(self.vals, self.idx, N, K, self.code_bits), self.exps, self.shape, self.dtype, self.mant_bits,
+                         64, self.code_bits)
+
+    def dequantize(self, out=None):
+        return self.to_packed().dequantize(out)
+
+    def nbytes(self):
+        return self.vals.numel() + self.idx.numel() + self.exps.numel()
+
+    def linear(self, x, bias=None, x_mant_bits=7, epsilon=1e-8, x_sparsity=None, decode_tokens=None):
+        """F.linear(Q_in(x), W, bias), W = self, activations HBFP(x_mant_bits + 1) block 64 round-half-even, pruned by x_sparsity
+        (native.ActSparsity or None) as PackedBFP.linear does.  Up to decode_tokens (default SP24_DECODE_TOKENS) tokens:
+        native.hbfp_linear_sp24.  More: the route PackedBFPLinear.forward takes for the same call (linear_route), on a transient
+        expansion of the weight -- int8 codes for 'int8', the dense codes (whose e4m3 image or dequantised weight that route makes)
+        for the others -- freed when the call returns."""
+        N, K = self.shape
+        T = x.numel() // K if K else 0
+        lead = x.shape[:-1]
+        if T == 0:
+            return x.new_zeros(lead + (N,))
+        lim = SP24_DECODE_TOKENS if decode_tokens is None else decode_tokens
+        if T <= lim and native.hbfp_linear_sp24_ok(T, N, K, self.code_bits, self.mant_bits, x_mant_bits):
+            return native.hbfp_linear_sp24(x.reshape(T, K), self.vals, self.idx, self.exps, N, self.code_bits, self.mant_bits, x_mant_bits,
+                                           epsilon, bias=bias, act=x_sparsity).view(lead + (N,))
+        route = linear_route(T, N, K, self.code_bits, self.mant_bits, x_mant_bits, i8_max_tokens=I8_MAX_TOKENS, block_size=64, dtype=x.dtype)
+        if route == 'int8':
+            c8 = native.sp24_unpack(self.vals, self.idx, N, K, self.code_bits, codes=self.code_bits == 8, codes8=self.code_bits == 4)
+            return native.hbfp_linear_i8(x.reshape(T, K), c8, self.exps, self.mant_bits, x_mant_bits, epsilon, bias=bias,
+                                         act=x_sparsity).view(lead + (N,))
+        return self.to_packed()._run_linear(route, x, bias, x_mant_bits, epsilon, x_sparsity)
+
+    def save(self, path):
+        """safetensors file: tensors `vals`, `idx`, `exps`; the rest as string metadata"""
+        from safetensors.torch import save_file
+        meta = dict(format="hbfp-sp24-v1", shape=",".join(str(d) for d in self.shape), dtype=str(self.dtype).replace("torch.", ""),
+                    mant_bits=str(self.mant_bits), block_size="64", code_bits=str(self.code_bits))
+        save_file({"vals": self.vals.cpu().contiguous(), "idx": self.idx.cpu().contiguous(), "exps": self.exps.cpu().contiguous()}, path,
+                  metadata=meta)
+
+    @classmethod
+    def load(cls, path, device="cuda"):
+        """a file of save(), or a PackedBFP.save file (compact24 or dense codes): its codes are expanded and compressed on the device,
+        and only the sp24 form is kept"""
+        from safetensors import safe_open
+        with safe_open(path, framework="pt", device="cpu") as f:
+            meta = f.metadata()
+            if meta.get("format") == "hbfp-sp24-v1":
+                shape = tuple(int(d) for d in meta["shape"].split(","))
+                return cls(f.get_tensor("vals").to(device), f.get_tensor("idx").to(device), f.get_tensor("exps").to(device), shape,
+                           getattr(torch, meta["dtype"]), int(meta["mant_bits"]), int(meta["code_bits"]))
+        return cls.from_packed(PackedBFP.load(path, device))
+
+
 def _act_fake_quant(x, mant_bits, epsilon, act=None, block_size=64):
     """the reference's activation operand: float_to_bfp_blocked(x, identifier='in') with HBFP(mant_bits + 1), blocks of block_size,
     round-half-even, pruned as the ActSparsity spec `act` says (None: dense)"""

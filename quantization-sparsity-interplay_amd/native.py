@@ -90,6 +90,10 @@ PROTOTYPES = {
     "bfpq_hbfp_linear_i8b_splitk": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
     "bfpq_hbfp_linear_decode8b_ws": (_i64, [_i64, _i64, _i64, _i32]),
     "bfpq_hbfp_linear_decode8b": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "bfpq_sp24_pack": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
+    "bfpq_sp24_unpack": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),
+    "bfpq_hbfp_linear_sp24_ws": (_i64, [_i64, _i64, _i64]),
+    "bfpq_hbfp_linear_sp24": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
 }
 
 
@@ -1225,3 +1229,96 @@ def hbfp_linear_i8(x, wcodes8, wexps, w_mant_bits, x_mant_bits, epsilon=1e-8, bi
             check(getattr(L, name)(*ops, _ptr(slabs), T, N, K, *tail), name)
     return out.view(tuple(x.shape[:-1]) + (N,))
 
+
+
+# ---- 2:4-compressed packed weights on the sparse int8 matrix unit (bfpq_sp24.hip) -----------------
+SP24_MAX_TOKENS = 64      # BFPQ_SP24_MAX_TOKENS: hbfp_linear_sp24 takes 1..64 tokens
+
+
+def sp24_nbytes(N, K, code_bits):
+    """(value bytes, position bytes) of an [N, K] weight in sp24 form: 2 kept codes + 2 x 2-bit positions per group of 4"""
+    return N * K * code_bits // 16, N * K // 8
+
+
+def sp24_shape_ok(N, K):
+    return N >= 16 and N % 16 == 0 and K >= 64 and K % 64 == 0 and N * K < (1 << 32)
+
+
+def sp24_pack(codes, N, K, code_bits):
+    """dense packed codes of an [N, K] weight (4-bit: uint8 [N, K/2]; 8-bit: int8 [N, K], as quantize_nm writes them) -> sp24
+    (vals uint8, idx uint8; bfpq_sp24_pack).  Raises ValueError if some group of 4 codes has more than 2 non-zeros (synchronises to
+    read the flag, as compact24 does)."""
+    require_device_tensor_any(codes)
+    if code_bits not in (4, 8) or not sp24_shape_ok(N, K):
+        raise ValueError(f"sp24 needs 4- or 8-bit codes, N % 16 == 0 and K % 64 == 0 (got N={N}, K={K}, code_bits={code_bits})")
+    c = codes.contiguous()
+    nv, ni = sp24_nbytes(N, K, code_bits)
+    if c.numel() * c.element_size() != N * K * code_bits // 8:
+        raise ValueError(f"sp24_pack: {tuple(c.shape)} {c.dtype} codes are not an [{N}, {K}] weight of {code_bits}-bit codes")
+    dev = c.device
+    with torch.cuda.device(dev):
+        vals = torch.empty(nv, dtype=torch.uint8, device=dev)
+        idx = torch.empty(ni, dtype=torch.uint8, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        check(load_library().bfpq_sp24_pack(_ptr(c), _ptr(vals), _ptr(idx), N, K, int(code_bits), _ptr(status), _stream(c)), "bfpq_sp24_pack")
+    if int(status.item()):
+        raise ValueError("sp24_pack: a group of 4 codes has more than 2 non-zeros (the weight is not 2:4 sparse)")
+    return vals, idx
+
+
+def sp24_unpack(vals, idx, N, K, code_bits, codes=True, codes8=False):
+    """sp24 -> dense codes of the same width (4-bit: uint8 [N, K/2]; 8-bit: int8 [N, K]) and / or int8 codes [N, K]
+    (bfpq_sp24_unpack, one launch).  Returns the codes, the int8 codes, or (codes, int8 codes) when both are asked for."""
+    require_device_tensor_any(vals)
+    if not (codes or codes8):
+        raise ValueError("sp24_unpack: ask for codes, int8 codes or both")
+    dev = vals.device
+    with torch.cuda.device(dev):
+        c = None
+        if codes:
+            c = torch.empty((N, K // 2), dtype=torch.uint8, device=dev) if code_bits == 4 else torch.empty((N, K), dtype=torch.int8, device=dev)
+        c8 = torch.empty((N, K), dtype=torch.int8, device=dev) if codes8 else None
+        check(load_library().bfpq_sp24_unpack(_ptr(vals.contiguous()), _ptr(idx.contiguous()), _ptr(c), _ptr(c8), N, K, int(code_bits),
+                                              _stream(vals)), "bfpq_sp24_unpack")
+    if codes and codes8:
+        return c, c8
+    return c if codes else c8
+
+
+def hbfp_linear_sp24_ok(T, N, K, code_bits, w_mant_bits, x_mant_bits):
+    """hbfp_linear_sp24 takes this problem: 1..SP24_MAX_TOKENS tokens, 4-bit codes with 1..3 mantissa bits or 8-bit codes with 1..7,
+    activations of 1..7 mantissa bits, N % 16 == 0, K % 64 == 0"""
+    return (code_bits in (4, 8) and 1 <= w_mant_bits <= (3 if code_bits == 4 else 7) and 1 <= x_mant_bits <= 7 and 1 <= T <= SP24_MAX_TOKENS
+            and sp24_shape_ok(N, K) and load_library().bfpq_hbfp_linear_sp24_ws(T, N, K) >= 0)
+
+
+def hbfp_linear_sp24(x, wvals, widx, wexps, N, code_bits, w_mant_bits, x_mant_bits, epsilon=1e-8, bias=None, out_dtype=None, act=None, xq=None):
+    """out = Q(x) @ W^T (+ bias) for 1..SP24_MAX_TOKENS tokens with W [N, K] in sp24 form (vals / idx of sp24_pack + the dense packed
+    weight's int8 exponents [N, K/64]), x quantized to HBFP(x_mant_bits + 1) block 64, round-half-even, pruned by `act` (ActSparsity or
+    None).  One v_smfmac_i32_16x16x64_i8 per block: exact integer block sums, fp32 across blocks.  xq: the activation operand made
+    beforehand (act_codes); x then only gives shape and dtype."""
+    require_device_tensor(x)
+    L = load_library()
+    K = x.shape[-1]
+    T = x.numel() // K
+    if not hbfp_linear_sp24_ok(T, N, K, code_bits, w_mant_bits, x_mant_bits):
+        raise ValueError(f"hbfp_linear_sp24 needs 1..{SP24_MAX_TOKENS} tokens, N % 16 == 0, K % 64 == 0 and mantissas that fit the codes "
+                         f"(got T={T}, N={N}, K={K}, code_bits={code_bits}, w_mant_bits={w_mant_bits}, x_mant_bits={x_mant_bits})")
+    nv, ni = sp24_nbytes(N, K, code_bits)
+    if wvals.numel() != nv or widx.numel() != ni or wexps.numel() != N * (K // 64):
+        raise ValueError(f"hbfp_linear_sp24: an [{N}, {K}] weight has {nv} value bytes, {ni} position bytes and {N * (K // 64)} exponents")
+    dev = x.device
+    out_dtype = out_dtype or x.dtype
+    with torch.cuda.device(dev):
+        if xq is not None:
+            xc, xe = xq[0].contiguous(), xq[1].contiguous()
+        else:
+            xc, xe = act_codes(x.reshape(T, K), x_mant_bits, epsilon, act)
+        out = torch.empty((T, N), dtype=out_dtype, device=dev)
+        if bias is not None:
+            bias = bias.to(out_dtype).contiguous()
+        slabs = torch.empty(int(L.bfpq_hbfp_linear_sp24_ws(T, N, K)), dtype=torch.float32, device=dev)
+        check(L.bfpq_hbfp_linear_sp24(_ptr(xc), _ptr(xe), _ptr(wvals.contiguous()), _ptr(widx.contiguous()), _ptr(wexps.contiguous()),
+                                      _ptr(bias) if bias is not None else None, _ptr(out), _ptr(slabs), T, N, K, int(code_bits),
+                                      DTYPE_CODE[out_dtype], int(w_mant_bits), int(x_mant_bits), _stream(x)), "bfpq_hbfp_linear_sp24")
+    return out.view(tuple(x.shape[:-1]) + (N,))

@@ -140,14 +140,75 @@ class PackedBFPLinear(torch.nn.Module):
         return f"in_features={self.in_features}, out_features={self.out_features}, packed_bytes={self.packed.nbytes()}{act}"
 
 
-def pack_linear_layers(model, bfp_args, skip=("lm_head", "classifier", "score")):
+class Sparse24BFPLinear(torch.nn.Module):
+    """Inference-only Linear whose N:4-pruned (N <= 2) HBFP block-64 weight lives in the 2:4-compressed form (bfp_ops.SparseBFP24): the two
+    kept codes of every group of 4 + their positions + the block exponents, 0.391 B per weight for 4-bit codes (mant_bits <= 3), 0.641 B
+    for 8-bit codes (4..7).  Up to bfp_ops.SP24_DECODE_TOKENS tokens the forward runs on the sparse int8 matrix instruction straight from
+    that form; more tokens run the route PackedBFPLinear takes, on an expansion of the weight made for that call only.  A sibling of
+    PackedBFPLinear with the same conventions: buffers `vals`, `idx`, `exps` follow .to() and round-trip through state_dict(); shape /
+    dtype / mantissa width / activation pruning travel as extra state; x_sparsity prunes the activations as the reference's in_sparsity."""
+
+    def __init__(self, sparse, bias=None, x_mant_bits=7, epsilon=1e-8, x_sparsity=None):
+        super().__init__()
+        self.out_features, self.in_features = sparse.shape
+        self.x_mant_bits, self.epsilon = int(x_mant_bits), float(epsilon)
+        self.x_sparsity = x_sparsity
+        self.register_buffer("vals", sparse.vals)
+        self.register_buffer("idx", sparse.idx)
+        self.register_buffer("exps", sparse.exps)
+        self._meta = dict(shape=list(sparse.shape), dtype=str(sparse.dtype).replace("torch.", ""), mant_bits=sparse.mant_bits,
+                          code_bits=sparse.code_bits)
+        self._sparse = sparse
+        self.bias = None if bias is None else torch.nn.Parameter(bias.detach(), requires_grad=False)
+
+    @property
+    def sparse(self):
+        """the SparseBFP24 view of the buffers (rebuilt when .to() / load_state_dict() replaced them)"""
+        s = self._sparse
+        if s is None or s.vals is not self.vals or s.idx is not self.idx or s.exps is not self.exps:
+            m = self._meta
+            s = self._sparse = bfp_ops.SparseBFP24(self.vals, self.idx, self.exps, tuple(m['shape']), getattr(torch, m['dtype']),
+                                                   m['mant_bits'], m['code_bits'])
+        return s
+
+    def get_extra_state(self):
+        return dict(self._meta, x_mant_bits=self.x_mant_bits, epsilon=self.epsilon,
+                    x_sparsity=None if self.x_sparsity is None else self.x_sparsity.as_dict())
+
+    def set_extra_state(self, state):
+        self._meta = {k: state[k] for k in ('shape', 'dtype', 'mant_bits', 'code_bits')}
+        self.x_mant_bits, self.epsilon = int(state['x_mant_bits']), float(state['epsilon'])
+        self.x_sparsity = native.ActSparsity.from_dict(state.get('x_sparsity'))
+        self._sparse = None
+
+    @classmethod
+    def from_linear(cls, lin, bfp_args):
+        """weight -> SparseBFP24.from_bfp_args with the module's config (which must guarantee the 2:4 / 1:4 pattern: ValueError
+        otherwise); activations use mant_bits of the same config and are pruned as its in_sparsity keys say"""
+        a = bfp_ops.unpack_bfp_args(dict(bfp_args))
+        sp = bfp_ops.SparseBFP24.from_bfp_args(lin.weight.detach(), a)
+        return cls(sp, lin.bias, a['mant_bits'], a['epsilon'], native.ActSparsity.from_bfp_args(a))
+
+    def forward(self, x):
+        return self.sparse.linear(x, self.bias, self.x_mant_bits, self.epsilon, self.x_sparsity)
+
+    def extra_repr(self):
+        act = "" if self.x_sparsity is None else f", x_sparsity={tuple(self.x_sparsity)}"
+        return f"in_features={self.in_features}, out_features={self.out_features}, sp24_bytes={self.sparse.nbytes()}{act}"
+
+
+def pack_linear_layers(model, bfp_args, skip=("lm_head", "classifier", "score"), sparse24=False):
     """Inference deployment: replace nn.Linear / BFPLinear children by PackedBFPLinear (weights quantized once and
     held as 4-bit codes for mant_bits <= 3, 8-bit codes for 4..7; the original bf16/fp16 weight is dropped).  Needs an HBFP config with
-    block_size 64, 32 or 16 and mant_bits <= 7 (+ optional N:M or unstructured pruning).  Returns the patched names and the bytes saved."""
+    block_size 64, 32 or 16 and mant_bits <= 7 (+ optional N:M or unstructured pruning).  Returns the patched names and the bytes saved.
+    sparse24=True: Sparse24BFPLinear instead (the 2:4-compressed form); the config must guarantee the pattern -- block 64, N:4 weight
+    pruning with N <= 2 (bfp_ops.sp24_config_check) -- or ValueError is raised before any module is replaced."""
     patched, saved = [], 0
     a = bfp_ops.unpack_bfp_args(dict(bfp_args))
-    # 8-bit codes, and every code width at blocks 16 / 32, run at any K % 64 == 0 (PackedBFP.linear_i8)
-    k_mult = 256 if bfp_ops.code_bits_for(a['mant_bits']) == 4 and a['block_size'] == 64 else 64
+    if sparse24:
+        bfp_ops.sp24_config_check(a)
+    # 8-bit codes, and every code width at blocks 16 / 32, run at any K % 64 == 0 (PackedBFP.linear_i8); sp24 takes any K % 64 == 0
+    k_mult = 256 if bfp_ops.code_bits_for(a['mant_bits']) == 4 and a['block_size'] == 64 and not sparse24 else 64
     for parent_name, parent in list(model.named_modules()):
         for child_name, child in list(parent.named_children()):
             full = f"{parent_name}.{child_name}" if parent_name else child_name
@@ -155,8 +216,8 @@ def pack_linear_layers(model, bfp_args, skip=("lm_head", "classifier", "score"))
                 continue
             if child.in_features % k_mult or child.out_features % 16:
                 continue                                    # shapes the packed kernels do not take stay as they are
-            new = PackedBFPLinear.from_linear(child, bfp_args)
-            saved += child.weight.numel() * child.weight.element_size() - new.packed.nbytes()
+            new = (Sparse24BFPLinear if sparse24 else PackedBFPLinear).from_linear(child, bfp_args)
+            saved += child.weight.numel() * child.weight.element_size() - (new.sparse if sparse24 else new.packed).nbytes()
             setattr(parent, child_name, new)
             patched.append(full)
     return patched, saved
