@@ -410,6 +410,44 @@ int bfpq_hbfp_linear_sp24(const void* xcodes_dev, const int8_t* xexp_dev, const 
  * infinite), which no int8 or e4m3 operand carries, so the caller redoes such a call on the fake-quantize route. */
 int bfpq_exp_top_flag(const int8_t* exp_a, int64_t n_a, const int8_t* exp_b, int64_t n_b, int* flag_dev, void* stream);
 
+/* ---- fused BFPAdam step (replaces BFPAdam.step's per-parameter body, bfp_optim_lstm.py:62-87, and its snap
+ * float_to_bfp_blocked(p, sgd_update=True) = _no_sparsity_float_to_bfp, bfp_ops.py:46-59) ------------------------------------
+ * For every fp32 tensor of the list, in place, element by element:
+ *     g' = weight_decay != 0 ? g + weight_decay * p : g              (grad is only read)
+ *     m = m * beta1 + (1 - beta1) g';   v = v * beta2 + (1 - beta2) g'^2;   amsgrad: vmax = max(vmax, v) (NaN propagates)
+ *     p = p - step_size * m / (sqrt(amsgrad ? vmax : v) + eps)
+ *     block_size > 0: p = Q(p), blocks of block_size along the last dim (per-row zero pad), mant_bits, epsilon, round-half-even
+ *                     (stoch == 0) or stochastic with the tensor's own seed
+ * bit for bit what the loop of torch ops and the engine's quantizer compute on the same GPU: the scalars are the fp32 values of
+ * the doubles given here, (1 - beta) is formed in double as in Python, step_size is the tensor's own double (lr * sqrt(bc2) / bc1
+ * at its own step) and the stochastic dither is keyed by (seed, element index) as bfpq_quantize_nm keys it for that shape.
+ * One launch per 64 tensors (descriptors in the kernel arguments: no device memory, no synchronisation); tensors with no elements
+ * are skipped.  block_size: 0 (no snap) or a power of two 4..256 with 1 <= mant_bits <= 23 (bfpq_adam_step_list_ok); exp_win_dev:
+ * bfpq_exp_window_host(BFPQ_F32) on the device.  A NULL pointer, a missing max_exp_avg_sq with amsgrad, or two arrays of one
+ * tensor that overlap (p aliasing grad, exp_avg, ...) return BFPQ_E_ARG before anything is launched. */
+typedef struct bfpq_adam_hparams {
+    double beta1, beta2, eps, weight_decay;
+    int amsgrad;
+    int block_size;                 /* 0: no snap */
+    int mant_bits;                  /* weight_mant_bits */
+    int stoch;                      /* 0: round-half-even, else stochastic rounding with each tensor's seed */
+    double epsilon;                 /* the quantizer's epsilon */
+    const uint8_t* exp_win_dev;     /* BFPQ_EXP_WIN_ENTRIES for BFPQ_F32 (NULL when block_size == 0) */
+} bfpq_adam_hparams;
+typedef struct bfpq_adam_tensor {
+    float* p_dev;
+    const float* grad_dev;
+    float* exp_avg_dev;
+    float* exp_avg_sq_dev;
+    float* max_exp_avg_sq_dev;      /* amsgrad only, else ignored */
+    int64_t rows, cols;             /* dense row-major; blocks run along cols */
+    double step_size;               /* lr * sqrt(1 - beta2^step) / (1 - beta1^step) at this tensor's step */
+    uint64_t seed;                  /* stochastic snap: non-zero seed (as _seed_for draws it); else ignored */
+} bfpq_adam_tensor;
+int bfpq_adam_step_list(const bfpq_adam_hparams* hparams_host, const bfpq_adam_tensor* tensors_host, int n, void* stream);
+/* 1 if bfpq_adam_step_list takes this snap configuration (block_size 0: no snap) */
+int bfpq_adam_step_list_ok(int block_size, int mant_bits);
+
 /* the first BFPQ_SELECT_STATE_BYTES of ws_dev, as read back by a host that wants tau / counts (little-endian) */
 typedef struct bfpq_select_state {
     uint32_t prefix;      /* magnitude bits decided so far (high digits)                         */

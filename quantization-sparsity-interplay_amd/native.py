@@ -94,6 +94,8 @@ PROTOTYPES = {
     "bfpq_sp24_unpack": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),
     "bfpq_hbfp_linear_sp24_ws": (_i64, [_i64, _i64, _i64]),
     "bfpq_hbfp_linear_sp24": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "bfpq_adam_step_list": (_i32, [_vp, _vp, _i32, _vp]),
+    "bfpq_adam_step_list_ok": (_i32, [_i32, _i32]),
 }
 
 
@@ -1322,3 +1324,88 @@ def hbfp_linear_sp24(x, wvals, widx, wexps, N, code_bits, w_mant_bits, x_mant_bi
                                       _ptr(bias) if bias is not None else None, _ptr(out), _ptr(slabs), T, N, K, int(code_bits),
                                       DTYPE_CODE[out_dtype], int(w_mant_bits), int(x_mant_bits), _stream(x)), "bfpq_hbfp_linear_sp24")
     return out.view(tuple(x.shape[:-1]) + (N,))
+
+
+# ---- fused BFPAdam step (bfpq_adam_step_list) -------------------------------------------------------------------------------
+ADAM_MAX_LIST = 64                 # tensors per launch of bfpq_adam_step_list
+adam_launches = 0                  # launches issued by AdamStepList.run so far (tests count them)
+
+
+class _AdamHparams(ctypes.Structure):
+    """include/bfpq.h: bfpq_adam_hparams"""
+    _fields_ = [("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double), ("weight_decay", ctypes.c_double),
+                ("amsgrad", ctypes.c_int), ("block_size", ctypes.c_int), ("mant_bits", ctypes.c_int), ("stoch", ctypes.c_int),
+                ("epsilon", ctypes.c_double), ("exp_win_dev", ctypes.c_void_p)]
+
+
+class _AdamTensor(ctypes.Structure):
+    """include/bfpq.h: bfpq_adam_tensor"""
+    _fields_ = [("p_dev", ctypes.c_void_p), ("grad_dev", ctypes.c_void_p), ("exp_avg_dev", ctypes.c_void_p), ("exp_avg_sq_dev", ctypes.c_void_p),
+                ("max_exp_avg_sq_dev", ctypes.c_void_p), ("rows", ctypes.c_int64), ("cols", ctypes.c_int64), ("step_size", ctypes.c_double),
+                ("seed", ctypes.c_uint64)]
+
+
+def adam_snap_ok(block_size, mant_bits):
+    """True if the fused step takes this snap (block_size 0: no snap)"""
+    return bool(load_library().bfpq_adam_step_list_ok(int(block_size), int(mant_bits)))
+
+
+_ADAM_FIELDS = ("p_dev", "grad_dev", "exp_avg_dev", "exp_avg_sq_dev", "max_exp_avg_sq_dev")
+
+
+class AdamStepList:
+    """A list of fp32 parameters with their grads and Adam states bound to bfpq_adam_step_list: the descriptors are built once;
+    run() writes each tensor's step size and seed, re-points a descriptor whose tensors moved (a grad set to None and made again
+    has new storage), and issues one launch per 64 tensors on the current stream of the list's device.
+    slots: per tensor the tuple (p, grad, exp_avg, exp_avg_sq, max_exp_avg_sq or None), contiguous fp32 on one ROCm device."""
+
+    def __init__(self, slots, betas, eps, weight_decay, amsgrad, block_size=0, mant_bits=0, stoch=False, epsilon=0.0):
+        slots = [tuple(s) for s in slots]
+        self.n = len(slots)
+        self.device = slots[0][0].device if slots else None
+        self._descs = (_AdamTensor * max(self.n, 1))()
+        self._ptrs = [[0] * 5 for _ in range(self.n)]
+        for i, s in enumerate(slots):
+            p = s[0]
+            cols = p.shape[-1] if p.dim() else 1
+            d = self._descs[i]
+            d.rows, d.cols = (p.numel() // cols if cols else 0), cols
+        self.hp = _AdamHparams(float(betas[0]), float(betas[1]), float(eps), float(weight_decay), 1 if amsgrad else 0, int(block_size),
+                               int(mant_bits), 1 if stoch else 0, float(epsilon), None)
+        self._win = None
+        if block_size and self.device is not None:
+            self._win = exp_window_dev(torch.float32, self.device)
+            self.hp.exp_win_dev = self._win.data_ptr()
+        self._fn = load_library().bfpq_adam_step_list
+        self.launches = -(-sum(1 for i in range(self.n) if self._descs[i].rows * self._descs[i].cols) // ADAM_MAX_LIST)
+
+    def run(self, slots, step_sizes, seeds=None):
+        """slots: the same tensors as bound (their storage may have moved); step_sizes: per tensor the double step size; seeds: per
+        tensor the stochastic snap's seed (None: round-half-even)"""
+        global adam_launches
+        descs, ptrs = self._descs, self._ptrs
+        for i, s in enumerate(slots):
+            d, pp = descs[i], ptrs[i]
+            for j in range(5):
+                t = s[j]
+                cur = t.data_ptr() if t is not None else 0
+                if cur != pp[j]:
+                    setattr(d, _ADAM_FIELDS[j], cur)
+                    pp[j] = cur
+            d.step_size = step_sizes[i]
+            if seeds is not None:
+                d.seed = seeds[i]
+        if not self.n:
+            return
+        dev = self.device
+        with torch.cuda.device(dev):
+            rc = self._fn(ctypes.addressof(self.hp), ctypes.addressof(descs), self.n, torch.cuda.current_stream(dev).cuda_stream)
+        check(rc, "bfpq_adam_step_list")
+        adam_launches += self.launches
+
+
+def adam_step_list(slots, step_sizes, betas, eps, weight_decay=0.0, amsgrad=False, block_size=0, mant_bits=0, seeds=None, epsilon=0.0):
+    """one fused Adam step (+ HBFP snap when block_size > 0; stochastic when seeds are given) over `slots` (see AdamStepList), bound
+    for this call only; BFPAdam(fused=True) keeps its AdamStepList from step to step instead"""
+    bound = AdamStepList(slots, betas, eps, weight_decay, amsgrad, block_size, mant_bits, seeds is not None, epsilon)
+    bound.run(slots, step_sizes, seeds)
