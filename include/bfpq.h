@@ -330,6 +330,26 @@ int bfpq_hbfp_linear_mx8_parts(int64_t T, int64_t N, int64_t K);
 int bfpq_hbfp_linear_mx8_splitk(const void* x8_dev, const void* xscale_dev, const void* w8_dev, const void* wscale_dev, const void* bias_dev,
                                 void* out_dev, float* slabs_dev, int parts, int64_t T, int64_t N, int64_t K, int out_dtype, void* stream);
 
+/* The same product (replaces F.linear on the two fake-quantised operands, bfp_ops.py:187-190) with the PACKED TENSOR ITSELF as the
+ * weight operand: wcodes4_dev = the 4-bit codes as bfpq_quantize_nm writes them with code_bits 4 (two's-complement nibbles, low nibble
+ * first, row-major [N, K/2] bytes, 16-byte aligned), wexp_dev = their int8 exponents [N, K/64] (4-byte aligned; -128 = NaN block).  The
+ * kernel turns nibbles into e4m3 bytes and exponents into E8M0 scales (the rule of bfpq_mx8_from_hbfp) on the way to the matrix
+ * instruction, so no weight image exists; the activation operand is its mx8 image as above.  Same tile plans, same walk over K and the
+ * same bits as bfpq_hbfp_linear_mx8 on the image of the same weight.  Takes what bfpq_hbfp_linear_mx8_ok takes, with w_mant_bits 1..3
+ * (else BFPQ_E_ARG).  BFPQ_TUNE_MX8_VARIANT forces the tile shape here too (0, 1: the 128 x 128 ring; 2: the 256 x 256 ring). */
+int bfpq_hbfp_linear_mx4w_ok(int64_t T, int64_t N, int64_t K);
+int bfpq_hbfp_linear_mx4w(const void* x8_dev, const void* xscale_dev, const void* wcodes4_dev, const int8_t* wexp_dev, const void* bias_dev,
+                          void* out_dev, int64_t T, int64_t N, int64_t K, int out_dtype, int w_mant_bits, void* stream);
+/* its split of K for short token counts (replaces the same lines, bfp_ops.py:187-190): the plan and the slabs of
+ * bfpq_hbfp_linear_mx8_parts / _splitk, slabs added in part order */
+int bfpq_hbfp_linear_mx4w_parts(int64_t T, int64_t N, int64_t K);
+int bfpq_hbfp_linear_mx4w_splitk(const void* x8_dev, const void* xscale_dev, const void* wcodes4_dev, const int8_t* wexp_dev, const void* bias_dev,
+                                 void* out_dev, float* slabs_dev, int parts, int64_t T, int64_t N, int64_t K, int out_dtype, int w_mant_bits,
+                                 void* stream);
+/* host: the e4m3 byte (OCP e4m3: sign, 4 exponent bits with bias 7, 3 mantissa bits) that the kernel makes of each 4-bit code 0..15,
+ * computed by the kernel's own conversion routine compiled for the host */
+int bfpq_e4m3_of_code4_host(uint8_t table[16]);
+
 /* ---- packed-format consumer for HBFP5-HBFP8 (replaces F.linear on the two fake-quantised operands, bfp_ops.py:187-190):
  * out[T, N] = x[T, K] W[N, K]^T (+ bias[N]), both operands int8 codes + int8 block exponents, block 64, mantissa widths
  * x_mant_bits, w_mant_bits in 1..7 (value = code * 2^(exp - mant_bits)), as bfpq_quantize_nm writes them with code_bits 8.

@@ -447,6 +447,21 @@ I8_SMALL_BLOCK_MAX_TOKENS = {(16, torch.float32): None, (32, torch.float32): Non
                              (16, torch.bfloat16): 16, (32, torch.bfloat16): 197, (16, torch.float16): 16, (32, torch.float16): 197}
 
 
+# hold_image=False: the codes-operand GEMM (native.hbfp_linear_mx4w) runs the 'mx8' route of a 4-bit weight, except where it did not beat the other
+# image-free route (dequantize per call + library GEMM) by more than the run-to-run spread: from this many tokens on, for weights of up to
+# this many elements (profiles/r10_prefill_codes.json: q_proj [4096, 4096] at 8192 tokens 190.2 against 192.2 us, spread 9.8; every other
+# measured shape -- 128..2048 tokens, and gate_proj / down_proj at 8192 -- 7..66 % faster)
+CODES_FAKE_MIN_TOKENS, CODES_FAKE_MAX_WEIGHT = 8192, 4096 * 4096
+# time of a hold_image=False forward over the hold_image=True forward (image already made), bf16 HBFP4 x HBFP4, LLaMA-7B projections, at
+# 128 / 512 / 2048 / 8192 tokens (same file; the spread of the image route against itself is 1-5 % there)
+HOLD_IMAGE_TIME = {'gate_proj': (1.40, 1.73, 1.46, 1.19), 'down_proj': (1.13, 1.51, 1.65, 1.07), 'q_proj': (1.14, 1.35, 1.63, 1.27)}
+
+
+def codes_route(T, N, K):
+    """what the 'mx8' route of a 4-bit block-64 weight runs with hold_image=False: 'mx4w' (native.hbfp_linear_mx4w) or 'fake'"""
+    return 'fake' if T >= CODES_FAKE_MIN_TOKENS and N * K <= CODES_FAKE_MAX_WEIGHT else 'mx4w'
+
+
 def i8_small_block_max_tokens(block_size, dtype):
     """I8_SMALL_BLOCK_MAX_TOKENS of this block and activation dtype (dtype None or not listed: the bf16 entry)"""
     return I8_SMALL_BLOCK_MAX_TOKENS.get((block_size, dtype), I8_SMALL_BLOCK_MAX_TOKENS[(block_size, torch.bfloat16)])
@@ -547,6 +562,17 @@ class PackedBFP:
     def nbytes(self):
         return self.codes.numel() * self.codes.element_size() + self.exps.numel()
 
+    def resident_bytes(self):
+        """bytes this weight holds on its device right now: codes, exponents and every derived copy that is alive -- the MFMA-tiled copy
+        of the decode kernel (`_tiles`, made by the first forward of <= 64 tokens), the int8 expansion of 4-bit codes (`_i8`) and the
+        e4m3 / E8M0 image of the block-scaled GEMM (`_mx8`, made by the first prefill unless hold_image=False)"""
+        n = self.nbytes()
+        for name in ("_tiles", "_i8", "_mx8"):
+            held = getattr(self, name, None)
+            if held is not None:
+                n += sum(t.numel() * t.element_size() for t in (held if isinstance(held, (tuple, list)) else (held,)))
+        return n
+
     def linear_decode(self, x, x_mant_bits=7, epsilon=1e-8, x_sparsity=None, xq=None):
         """x @ W^T for <= 64 tokens straight from the packed weight (self is W [N, K], 4-bit codes, block 64, N % 16 == 0,
         K % 128 == 0, K >= 256), in one launch on an MFMA-tiled copy of the weight made once (native.hbfp_linear_decode_tiled):
@@ -563,21 +589,25 @@ class PackedBFP:
             self._tiles = native.mfma_tiles(self.codes, self.exps)
         return native.hbfp_linear_decode_tiled(x, self._tiles[0], self._tiles[1], N, self.mant_bits, x_mant_bits, epsilon, xq=xq)
 
-    def linear(self, x, bias=None, x_mant_bits=7, epsilon=1e-8, decode_tokens=DECODE_TOKENS, x_sparsity=None):
+    def linear(self, x, bias=None, x_mant_bits=7, epsilon=1e-8, decode_tokens=DECODE_TOKENS, x_sparsity=None, hold_image=True):
         """F.linear(Q_in(x), W_packed, bias) for any number of tokens, W = self [N, K] (the forward of a BFPLinear whose
         weight is held packed; activations HBFP(x_mant_bits + 1), block 64, round-half-even), on the kernel linear_route picks:
         4-bit codes up to `decode_tokens` tokens straight from the codes (linear_decode); else the block-scaled matrix instruction
         where both operands' mantissas fit 4 bits; else the weight decoded once per call and the library GEMM.
         x_sparsity (native.ActSparsity or None): the activation is pruned as the reference's in_sparsity does (N:M per row, or
-        one unstructured threshold over ALL tokens of the call)."""
+        one unstructured threshold over ALL tokens of the call).
+        hold_image=False: the 'mx8' route of 4-bit block-64 codes reads the codes themselves (native.hbfp_linear_mx4w) and the
+        1.016 B per weight image is never made: same bits, 1.07-1.73 x the image route's
+        time (bfp_ops.HOLD_IMAGE_TIME has the ratio per measured shape; codes_route: a small weight at >= 8192 tokens takes the
+        dequantize + library GEMM route instead, which keeps no image either)."""
         K = self.shape[-1]
         T = x.numel() // K if K else 0
         route = linear_route(T, self.shape[0], K, self.code_bits, self.mant_bits, x_mant_bits, decode_tokens, block_size=self.block_size,
                              dtype=x.dtype)
-        return self._run_linear(route, x, bias, x_mant_bits, epsilon, x_sparsity)
+        return self._run_linear(route, x, bias, x_mant_bits, epsilon, x_sparsity, hold_image)
 
-    def _run_linear(self, route, x, bias, x_mant_bits, epsilon, x_sparsity):
-        """F.linear(Q_in(x), W_packed, bias) on `route` (a linear_route name)"""
+    def _run_linear(self, route, x, bias, x_mant_bits, epsilon, x_sparsity, hold_image=True):
+        """F.linear(Q_in(x), W_packed, bias) on `route` (a linear_route name); hold_image as in linear()"""
         if route == 'int8':
             return self.linear_i8(x, bias, x_mant_bits, epsilon, x_sparsity)
         N, K = self.shape[0], self.shape[-1]
@@ -585,6 +615,12 @@ class PackedBFP:
         x2 = x.reshape(-1, K)
         if route == 'empty':
             return x.new_zeros(lead + (N,))
+        if route == 'mx8' and not hold_image and self.code_bits == 4 and self.block_size == 64:
+            route = codes_route(x2.shape[0], N, K)
+        if route == 'mx4w':
+            # the same GEMM with the codes and exponents themselves as the weight operand: nothing derived from the weight is kept
+            return native.hbfp_linear_mx4w(x2, self.codes, self.exps, self.mant_bits, x_mant_bits, epsilon, bias=bias,
+                                           act=x_sparsity).view(lead + (N,))
         if route == 'mx8':
             # both operands as e4m3 mantissas + E8M0 block scales on the block-scaled matrix instruction (exact block dot products,
             # fp32 across blocks, bias fused); the weight's image is made once per device

@@ -275,29 +275,98 @@ __device__ __forceinline__ v8i read_frag_ring(const uint8_t* tile, int row, int 
     return v8i{a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
 }
 
+// ---- the weight operand as the packed tensor itself (4-bit codes + int8 exponents): bfpq_hbfp_linear_mx4w ----------------------------
+// The nibbles travel global -> LDS by the same LDS-DMA (32 bytes per row and HBFP block) and become e4m3 bytes when a wave reads its
+// fragment: one ds_read_b128 = the lane's 32 codes, eight dwords of e4m3 after 15 vector instructions per dword of nibbles.  A 4-bit
+// code needs a 16-entry table and v_perm_b32 selects among 8 bytes, so the low three bits index two 8-entry tables (nibbles 0..7 =
+// 0..7, nibbles 8..15 = -8..-1) and a third v_perm_b32, whose selector carries the nibble's sign bit, picks between the two results.
+// The low and the high nibbles of a dword are its even and odd elements; two more v_perm_b32 interleave them, so that byte j of the
+// fragment is element j as in the activation's image (both operands must meet in the same k order).
+constexpr uint32_t kCode4E4m3[4] = {0x44403800u, 0x4E4C4A48u, 0xCACCCED0u, 0xB8C0C4C8u};   // e4m3 of 0..3, 4..7, -8..-5, -4..-1
+
+__host__ __device__ __forceinline__ uint32_t perm_b32(uint32_t hi, uint32_t lo, uint32_t sel)   // v_perm_b32 for selector bytes 0..7
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(hi, lo, sel);
+#else
+    const uint64_t src = ((uint64_t)hi << 32) | lo;
+    uint32_t r = 0;
+    for (int j = 0; j < 4; j++) r |= (uint32_t)((src >> (8 * ((sel >> (8 * j)) & 7u))) & 0xffu) << (8 * j);
+    return r;
+#endif
+}
+
+// 8 two's-complement nibbles (element 2 i = low nibble of byte i, 2 i + 1 = its high nibble) -> their e4m3 bytes in element order
+__host__ __device__ __forceinline__ void e4m3x8_of_code4(uint32_t w, uint32_t& o0, uint32_t& o1)
+{
+    const uint32_t wh = w >> 4;
+    const uint32_t il = w & 0x07070707u, ih = wh & 0x07070707u;
+    const uint32_t sl = ((w >> 1) & 0x04040404u) | 0x03020100u, sh = ((wh >> 1) & 0x04040404u) | 0x03020100u;   // byte j: j + 4 * sign
+    const uint32_t lo = perm_b32(perm_b32(kCode4E4m3[3], kCode4E4m3[2], il), perm_b32(kCode4E4m3[1], kCode4E4m3[0], il), sl);
+    const uint32_t hi = perm_b32(perm_b32(kCode4E4m3[3], kCode4E4m3[2], ih), perm_b32(kCode4E4m3[1], kCode4E4m3[0], ih), sh);
+    o0 = perm_b32(hi, lo, 0x05010400u);
+    o1 = perm_b32(hi, lo, 0x07030602u);
+}
+
+// four int8 block exponents -> four E8M0 scale bytes, by the rule of k_mx8_from_codes (-128, the NaN block marker, -> 0xff)
+__device__ __forceinline__ int e8m0x4_of_exp(uint32_t e4, int mant_bits)
+{
+    uint32_t r = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int e = (int)(int8_t)(e4 >> (8 * j));
+        int s = e - mant_bits + 127;
+        s = s < 0 ? 0 : (s > 254 ? 254 : s);
+        r |= (e == -128 ? 0xffu : (uint32_t)s) << (8 * j);
+    }
+    return (int)r;
+}
+
+// LDS rows of the code tile are 32 KB bytes (KB blocks per stage): 16-byte slot' = slot ^ swz_code4(row) spreads the 16 rows of a
+// ds_read_b128 lane group over all 64 banks (32-byte rows: 8 rows span the banks and rows r, r + 16 share a group; 64-byte rows: as
+// the 64-byte rows of the e4m3 ring)
+template <int KB> __device__ __forceinline__ int swz_code4(int row) { return KB == 1 ? (row >> 4) & 1 : (row >> 2) & 3; }
+
+// the 32 codes of block b (of KB per LDS row), lane half `half`, as 32 e4m3 bytes
+template <int KB>
+__device__ __forceinline__ v8i read_frag_code4(const uint8_t* tile, int row, int b, int half)
+{
+    const int c = 2 * b + half;
+    const v4i a = *reinterpret_cast<const v4i*>(tile + row * (32 * KB) + ((c ^ swz_code4<KB>(row)) << 4));
+    uint32_t o[8];
+    e4m3x8_of_code4((uint32_t)a.x, o[0], o[1]);
+    e4m3x8_of_code4((uint32_t)a.y, o[2], o[3]);
+    e4m3x8_of_code4((uint32_t)a.z, o[4], o[5]);
+    e4m3x8_of_code4((uint32_t)a.w, o[6], o[7]);
+    return v8i{(int)o[0], (int)o[1], (int)o[2], (int)o[3], (int)o[4], (int)o[5], (int)o[6], (int)o[7]};
+}
+
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // KB = HBFP blocks (64 B of K) per ring stage, NS = stages in the ring (the DMA runs NS - 1 stages ahead)
-template <int WM, int WN, int TM, int TN, int KB, int NS> struct RingCfg {
-    static constexpr int NW = WM * WN, NT = 64 * NW, BM = 32 * WM * TM, BN = 32 * WN * TN, STAGE = (BM + BN) * 64 * KB;
+// W4: the weight rows of a stage are 4-bit codes (32 B per block) and the scale ring holds their int8 exponents
+template <int WM, int WN, int TM, int TN, int KB, int NS, bool W4 = false> struct RingCfg {
+    static constexpr int NW = WM * WN, NT = 64 * NW, BM = 32 * WM * TM, BN = 32 * WN * TN, STAGE = (BM * 64 + BN * (W4 ? 32 : 64)) * KB;
     static constexpr int LDS_BYTES = NS * STAGE + 2 * NT * 4;
 };
 
 // one output tile: `orig` of `nwg` workgroups of this tile shape (ids remapped per XCD), columns starting at n_base
-template <int OUT_DT, int WM, int WN, int TM, int TN, int KB, int NS>
+// W4: w8 / wsc are the packed tensor (codes [N, K/2], int8 exponents [N, K/64]) and w_mant_bits its mantissa width
+template <int OUT_DT, int WM, int WN, int TM, int TN, int KB, int NS, bool W4 = false>
 __device__ __forceinline__ void ring_tile(uint8_t* lds, int orig, int nwg, int n_base,
                                           const uint8_t* __restrict__ x8, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ w8,
                                           const uint8_t* __restrict__ wsc, const void* __restrict__ bias, void* __restrict__ out,
-                                          int T, int N, int K, int tiles_t, int tr0 = 0, int tr1 = -1)
+                                          int T, int N, int K, int tiles_t, int tr0 = 0, int tr1 = -1, int w_mant_bits = 0)
 {
-    using C = RingCfg<WM, WN, TM, TN, KB, NS>;
+    using C = RingCfg<WM, WN, TM, TN, KB, NS, W4>;
     constexpr int NW = C::NW, NT = C::NT, BM = C::BM, BN = C::BN, STAGE = C::STAGE;
     constexpr int RPP = 16 / KB, SLOTS = 4 * KB;                               // tile rows per DMA piece (1 KB), 16-byte slots per row
-    constexpr int GA = BM / RPP / NW, GB = BN / RPP / NW, G = GA + GB;         // DMA pieces per wave and stage
+    constexpr int RBB = (W4 ? 32 : 64) * KB, RPPB = 1024 / RBB, SLOTSB = RBB / 16; // weight rows: bytes per row and stage, rows per piece, slots
+    constexpr int GA = BM / RPP / NW, GB = BN / RPPB / NW, G = GA + GB;        // DMA pieces per wave and stage
     constexpr int D = NS - 1, SPT = 4 / KB;                                    // stages the DMA runs ahead; stages per trip of 4 blocks (one scale dword)
     static_assert(KB == 1 || KB == 2, "one or two blocks per stage");
     static_assert(D >= 1 && D <= SPT, "the next trip's scales must have landed when the trip begins");
-    static_assert(BM % (RPP * NW) == 0 && BN % (RPP * NW) == 0, "tile rows must split evenly over the waves");
+    static_assert(BM % (RPP * NW) == 0 && BN % (RPPB * NW) == 0, "tile rows must split evenly over the waves");
     static_assert(NT >= BM + BN, "one thread per tile row carries the row's scales");
     uint8_t* const sscale = lds + NS * STAGE;                                  // [2][NT] dwords: scales of the 4 blocks of a trip, per tile row
     const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
@@ -318,9 +387,12 @@ __device__ __forceinline__ void ring_tile(uint8_t* lds, int orig, int nwg, int n
     }
 #pragma unroll
     for (int i = 0; i < GB; i++) {
-        const int row = (NW * i + w) * RPP + l / SLOTS, piece = ((l % SLOTS) ^ swz(row)) << 4;
+        const int row = (NW * i + w) * RPPB + l / SLOTSB;
+        int sw;
+        if constexpr (W4) sw = swz_code4<KB>(row); else sw = swz(row);
+        const int piece = ((l % SLOTSB) ^ sw) << 4;
         const int na = n0 + row < N ? n0 + row : N - 1;
-        offB[i] = (size_t)na * K + piece;
+        offB[i] = (size_t)na * (W4 ? K >> 1 : K) + piece;
     }
     // this thread's tile row for the scale DMA: rows 0 .. BM-1 = tokens, BM .. BM+BN-1 = output features (threads past that repeat the last)
     const uint32_t* srow;
@@ -349,7 +421,7 @@ __device__ __forceinline__ void ring_tile(uint8_t* lds, int orig, int nwg, int n
                                              (__attribute__((address_space(3))) void*)(sA + (NW * i + w) * 1024), 16, 0, 0);
 #pragma unroll
         for (int i = 0; i < GB; i++)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(w8 + offB[i] + k0),
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(w8 + offB[i] + s * RBB),
                                              (__attribute__((address_space(3))) void*)(sB + (NW * i + w) * 1024), 16, 0, 0);
     };
     auto stage_scales = [&](int trip) __attribute__((always_inline)) {          // one dword per tile row -> sscale[trip & 1][thread]
@@ -365,7 +437,10 @@ __device__ __forceinline__ void ring_tile(uint8_t* lds, int orig, int nwg, int n
 #pragma unroll
         for (int i = 0; i < TM; i++) aF[i] = read_frag_ring<KB>(sA, rowA + 32 * i, b, half);
 #pragma unroll
-        for (int j = 0; j < TN; j++) bF[j] = read_frag_ring<KB>(sB, rowB + 32 * j, b, half);
+        for (int j = 0; j < TN; j++) {
+            if constexpr (W4) bF[j] = read_frag_code4<KB>(sB, rowB + 32 * j, b, half);
+            else bF[j] = read_frag_ring<KB>(sB, rowB + 32 * j, b, half);
+        }
 #pragma unroll
         for (int i = 0; i < TM; i++)
 #pragma unroll
@@ -402,7 +477,10 @@ __device__ __forceinline__ void ring_tile(uint8_t* lds, int orig, int nwg, int n
 #pragma unroll
         for (int i = 0; i < TM; i++) sa[i] = (int)sc[rowA + 32 * i];
 #pragma unroll
-        for (int j = 0; j < TN; j++) sb[j] = (int)sc[BM + rowB + 32 * j];
+        for (int j = 0; j < TN; j++) {
+            if constexpr (W4) sb[j] = e8m0x4_of_exp(sc[BM + rowB + 32 * j], w_mant_bits);
+            else sb[j] = (int)sc[BM + rowB + 32 * j];
+        }
         step(template_int<0>{}, s, slot, trn);
         if constexpr (SPT > 1) step(template_int<1>{}, s + 1, slot, trn);
         if constexpr (SPT > 2) { step(template_int<2>{}, s + 2, slot, trn); step(template_int<3>{}, s + 3, slot, trn); }
@@ -497,6 +575,42 @@ __global__ void __launch_bounds__(512) k_mx8_gemm_ring_mixed(const uint8_t* __re
         ring_tile<OUT_DT, 4, 2, 2, 2, SKB, SNS>(lds, (int)blockIdx.x - n_big, (int)gridDim.x - n_big, n_base_small, x8, xs, w8, wsc, bias, out, T, N, K, tiles_t);
 }
 
+// The same three launches with the packed tensor as the weight operand (ring_tile<..., W4 = true>)
+template <int OUT_DT, int WM, int WN, int TM, int TN, int KB, int NS>
+__global__ void __launch_bounds__(64 * WM * WN) k_mx4w_gemm_ring(const uint8_t* __restrict__ x8, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ wc4,
+                                                                 const uint8_t* __restrict__ wexp, const void* __restrict__ bias, void* __restrict__ out,
+                                                                 int T, int N, int K, int tiles_t, int w_mant_bits)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lds[RingCfg<WM, WN, TM, TN, KB, NS, true>::LDS_BYTES];
+    ring_tile<OUT_DT, WM, WN, TM, TN, KB, NS, true>(lds, (int)blockIdx.x, (int)gridDim.x, 0, x8, xs, wc4, wexp, bias, out, T, N, K, tiles_t, 0, -1, w_mant_bits);
+}
+
+template <int WM, int WN, int TM, int TN, int KB, int NS>
+__global__ void __launch_bounds__(64 * WM * WN) k_mx4w_gemm_ring_splitk(const uint8_t* __restrict__ x8, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ wc4,
+                                                                        const uint8_t* __restrict__ wexp, float* __restrict__ slabs,
+                                                                        int T, int N, int K, int tiles_t, int tiles, int trips_per_part, int w_mant_bits)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lds[RingCfg<WM, WN, TM, TN, KB, NS, true>::LDS_BYTES];
+    const int part = (int)blockIdx.x / tiles, tile = (int)blockIdx.x % tiles;
+    const int trips = K >> 8, a = part * trips_per_part, b = a + trips_per_part < trips ? a + trips_per_part : trips;
+    ring_tile<BFPQ_F32, WM, WN, TM, TN, KB, NS, true>(lds, tile, tiles, 0, x8, xs, wc4, wexp, nullptr, slabs + (size_t)part * T * N, T, N, K, tiles_t, a, b,
+                                                      w_mant_bits);
+}
+
+template <int OUT_DT, int SKB, int SNS>
+__global__ void __launch_bounds__(512) k_mx4w_gemm_ring_mixed(const uint8_t* __restrict__ x8, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ wc4,
+                                                              const uint8_t* __restrict__ wexp, const void* __restrict__ bias, void* __restrict__ out,
+                                                              int T, int N, int K, int tiles_t, int n_big, int n_base_small, int w_mant_bits)
+{
+    constexpr int LB = RingCfg<2, 4, 4, 2, 1, 4, true>::LDS_BYTES, LS = RingCfg<4, 2, 2, 2, SKB, SNS, true>::LDS_BYTES;
+    __shared__ __attribute__((aligned(16))) uint8_t lds[LB > LS ? LB : LS];
+    if ((int)blockIdx.x < n_big)
+        ring_tile<OUT_DT, 2, 4, 4, 2, 1, 4, true>(lds, (int)blockIdx.x, n_big, 0, x8, xs, wc4, wexp, bias, out, T, N, K, tiles_t, 0, -1, w_mant_bits);
+    else
+        ring_tile<OUT_DT, 4, 2, 2, 2, SKB, SNS, true>(lds, (int)blockIdx.x - n_big, (int)gridDim.x - n_big, n_base_small, x8, xs, wc4, wexp, bias, out, T, N, K,
+                                                      tiles_t, 0, -1, w_mant_bits);
+}
+
 // Tile variants (bfpq_tune key BFPQ_TUNE_MX8_VARIANT; measured with tools_dev/ab_mx8.py, interleaved in one process, all bit-identical).
 // gate_proj [2048 x 4096 x 11008] / 8192 tokens / q_proj [2048 x 4096 x 4096] / down_proj [2048 x 11008 x 4096], us:
 //   0: 128 x 128, 4 waves, one LDS stage of 128 B of K, ~3 workgroups per CU                      119 / 469 / 49 / 108
@@ -514,6 +628,19 @@ struct MxCfg { int bm, bn; };
 constexpr MxCfg kMxCfg[] = {{128, 128}, {128, 128}, {256, 256}, {256, 256}, {256, 128}, {256, 256}, {128, 128}};
 constexpr int kMxVariants = 7;
 
+// the mixed launch: whole rounds of the chip in 256 x 256 tiles, the rest of the columns in 256 x 128 tiles (kCUs: the part has 256)
+struct MixedPlan { unsigned grid; int n_big, n_base; };
+inline MixedPlan mixed_plan(int tiles_t, int tiles_n, int N)
+{
+    constexpr int kCUs = 256;
+    const int rounds = tiles_t * tiles_n / kCUs;
+    int big_cols = rounds > 0 ? rounds * kCUs / tiles_t : 0;                   // column tiles of 256 that go as big tiles
+    if (big_cols > tiles_n) big_cols = tiles_n;
+    const int n_big = big_cols * tiles_t, n_base = big_cols * 256;
+    const int small_cols = n_base < N ? (N - n_base + 127) / 128 : 0;
+    return {(unsigned)(n_big + small_cols * tiles_t), n_big, n_base};
+}
+
 template <int OUT_DT>
 int launch_mx8(int variant, const uint8_t* a, const uint8_t* as, const uint8_t* b, const uint8_t* bs, const void* bias, void* out,
                int T, int N, int K, hipStream_t s)
@@ -522,15 +649,8 @@ int launch_mx8(int variant, const uint8_t* a, const uint8_t* as, const uint8_t* 
     const int tiles_t = (T + bm - 1) / bm, tiles_n = (N + bn - 1) / bn;
     const dim3 grid((unsigned)(tiles_t * tiles_n));
     if (variant == 5) {
-        // whole rounds of the chip in 256 x 256 tiles, the rest of the columns in 256 x 128 tiles (kCUs: the part has 256)
-        constexpr int kCUs = 256;
-        const int rounds = tiles_t * tiles_n / kCUs;
-        int big_cols = rounds > 0 ? rounds * kCUs / tiles_t : 0;               // column tiles of 256 that go as big tiles
-        if (big_cols > tiles_n) big_cols = tiles_n;
-        const int n_big = big_cols * tiles_t, n_base = big_cols * 256;
-        const int small_cols = n_base < N ? (N - n_base + 127) / 128 : 0;
-        const dim3 g2((unsigned)(n_big + small_cols * tiles_t));
-        hipLaunchKernelGGL((k_mx8_gemm_ring_mixed<OUT_DT, 2, 3>), g2, dim3(512), 0, s, a, as, b, bs, bias, out, T, N, K, tiles_t, n_big, n_base);
+        const MixedPlan p = mixed_plan(tiles_t, tiles_n, N);
+        hipLaunchKernelGGL((k_mx8_gemm_ring_mixed<OUT_DT, 2, 3>), dim3(p.grid), dim3(512), 0, s, a, as, b, bs, bias, out, T, N, K, tiles_t, p.n_big, p.n_base);
         return (int)hipGetLastError();
     }
     switch (variant) {
@@ -540,6 +660,30 @@ int launch_mx8(int variant, const uint8_t* a, const uint8_t* as, const uint8_t* 
         case 3: hipLaunchKernelGGL((k_mx8_gemm_ring<OUT_DT, 2, 4, 4, 2, 1, 4>), grid, dim3(512), 0, s, a, as, b, bs, bias, out, T, N, K, tiles_t); break;
         case 6: hipLaunchKernelGGL((k_mx8_gemm_ring<OUT_DT, 2, 2, 2, 2, 2, 3>), grid, dim3(256), 0, s, a, as, b, bs, bias, out, T, N, K, tiles_t); break;
         default: hipLaunchKernelGGL((k_mx8_gemm_ring<OUT_DT, 4, 2, 2, 2, 2, 3>), grid, dim3(512), 0, s, a, as, b, bs, bias, out, T, N, K, tiles_t); break;
+    }
+    return (int)hipGetLastError();
+}
+
+// the codes-operand form has the ring kernels only: a forced variant 0 or 1 (128 x 128, the first kernel form) runs the 128 x 128 ring,
+// variant 2 (256 x 256) the 256 x 256 ring
+template <int OUT_DT>
+int launch_mx4w(int variant, const uint8_t* a, const uint8_t* as, const uint8_t* b, const uint8_t* be, const void* bias, void* out,
+                int T, int N, int K, int wm, hipStream_t s)
+{
+    if (variant <= 1) variant = 6;
+    if (variant == 2) variant = 3;
+    const int bm = kMxCfg[variant].bm, bn = kMxCfg[variant].bn;
+    const int tiles_t = (T + bm - 1) / bm, tiles_n = (N + bn - 1) / bn;
+    const dim3 grid((unsigned)(tiles_t * tiles_n));
+    switch (variant) {
+        case 5: {
+            const MixedPlan p = mixed_plan(tiles_t, tiles_n, N);
+            hipLaunchKernelGGL((k_mx4w_gemm_ring_mixed<OUT_DT, 2, 3>), dim3(p.grid), dim3(512), 0, s, a, as, b, be, bias, out, T, N, K, tiles_t, p.n_big, p.n_base, wm);
+            break;
+        }
+        case 3: hipLaunchKernelGGL((k_mx4w_gemm_ring<OUT_DT, 2, 4, 4, 2, 1, 4>), grid, dim3(512), 0, s, a, as, b, be, bias, out, T, N, K, tiles_t, wm); break;
+        case 6: hipLaunchKernelGGL((k_mx4w_gemm_ring<OUT_DT, 2, 2, 2, 2, 2, 3>), grid, dim3(256), 0, s, a, as, b, be, bias, out, T, N, K, tiles_t, wm); break;
+        default: hipLaunchKernelGGL((k_mx4w_gemm_ring<OUT_DT, 4, 2, 2, 2, 2, 3>), grid, dim3(512), 0, s, a, as, b, be, bias, out, T, N, K, tiles_t, wm); break;
     }
     return (int)hipGetLastError();
 }
@@ -575,15 +719,9 @@ static bool mx8_short(int64_t T, int64_t N) { return T <= 256 || ((T + 255) / 25
 
 __attribute__((visibility("hidden"))) int bfpq_g_mx8_variant = -1;             // -1 = choose; 0..6 force (bfpq_tune, BFPQ_TUNE_MX8_VARIANT)
 
-int bfpq_hbfp_linear_mx8(const void* x8, const void* xs, const void* w8, const void* ws, const void* bias, void* out,
-                         int64_t T, int64_t N, int64_t K, int out_dtype, void* stream)
+// the tile plan of one launch: the forced variant (bfpq_tune), else by shape
+static int mx8_variant(int64_t T, int64_t N)
 {
-    if (!dtype_ok(out_dtype) || T < 0 || N < 0) return BFPQ_E_ARG;
-    if (T == 0 || N == 0) return 0;
-    if (!bfpq_hbfp_linear_mx8_ok(T, N, K)) return BFPQ_E_UNSUPPORTED;
-    if (!x8 || !xs || !w8 || !ws || !out) return BFPQ_E_ARG;
-    if (!aligned16(x8, w8)) return BFPQ_E_ARG;
-    if ((reinterpret_cast<uintptr_t>(xs) | reinterpret_cast<uintptr_t>(ws)) & 3u) return BFPQ_E_ARG;
     int variant = bfpq_g_mx8_variant;
     if (variant < 0 || variant >= kMxVariants) {
         // rounds of the chip, measured: a 256 x 128 tile costs 0.60 of a 256 x 256 one, a partly filled last round 0.72 of a full one
@@ -596,6 +734,19 @@ int bfpq_hbfp_linear_mx8(const void* x8, const void* xs, const void* w8, const v
         const double est_mixed = (double)(big_cols * tt) / 256.0 + 0.60 * ((double)(n_small / 256) + (n_small % 256 ? 0.72 : 0.0));
         variant = mx8_short(T, N) ? 6 : (est_mixed < 0.92 * est_big ? 5 : 3);
     }
+    return variant;
+}
+
+int bfpq_hbfp_linear_mx8(const void* x8, const void* xs, const void* w8, const void* ws, const void* bias, void* out,
+                         int64_t T, int64_t N, int64_t K, int out_dtype, void* stream)
+{
+    if (!dtype_ok(out_dtype) || T < 0 || N < 0) return BFPQ_E_ARG;
+    if (T == 0 || N == 0) return 0;
+    if (!bfpq_hbfp_linear_mx8_ok(T, N, K)) return BFPQ_E_UNSUPPORTED;
+    if (!x8 || !xs || !w8 || !ws || !out) return BFPQ_E_ARG;
+    if (!aligned16(x8, w8)) return BFPQ_E_ARG;
+    if ((reinterpret_cast<uintptr_t>(xs) | reinterpret_cast<uintptr_t>(ws)) & 3u) return BFPQ_E_ARG;
+    const int variant = mx8_variant(T, N);
     hipStream_t s = (hipStream_t)stream;
     const uint8_t *a = (const uint8_t*)x8, *as = (const uint8_t*)xs, *b = (const uint8_t*)w8, *bs = (const uint8_t*)ws;
     return with_dtype(out_dtype, [&](auto dt) { return launch_mx8<dt>(variant, a, as, b, bs, bias, out, (int)T, (int)N, (int)K, s); });
@@ -631,6 +782,68 @@ int bfpq_hbfp_linear_mx8_splitk(const void* x8, const void* xs, const void* w8, 
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL((k_mx8_gemm_ring_splitk<2, 2, 2, 2, 2, 3>), dim3((unsigned)(tiles * parts)), dim3(256), 0, s, (const uint8_t*)x8, (const uint8_t*)xs,
                        (const uint8_t*)w8, (const uint8_t*)ws, slabs, (int)T, (int)N, (int)K, tiles_t, tiles, tpp);
+    launch_slab_reduce(out_dtype, slabs, (size_t)(T * N), bias, out, T * N, N, parts, s);
+    return (int)hipGetLastError();
+}
+
+/* ---- the same GEMM with the packed tensor itself as the weight operand (no weight image) ---- */
+int bfpq_e4m3_of_code4_host(uint8_t table[16])
+{
+    if (!table) return BFPQ_E_ARG;
+    for (uint32_t n = 0; n < 16; n++) {
+        // the kernel's conversion on every nibble in every position of a dword, beside nibbles of the other sign
+        uint8_t got = 0;
+        for (int pos = 0; pos < 8; pos++) {
+            const uint32_t fill = (pos & 1) ? 0x5d3a91c7u : 0xa2c56e38u;
+            const uint32_t w = (fill & ~(15u << (4 * pos))) | (n << (4 * pos));
+            uint32_t o[2];
+            e4m3x8_of_code4(w, o[0], o[1]);
+            const uint8_t b = (uint8_t)(o[pos >> 2] >> (8 * (pos & 3)));
+            if (pos && b != got) return BFPQ_E_UNSUPPORTED;                      // (cannot happen: the conversion is position-independent)
+            got = b;
+        }
+        table[n] = got;
+    }
+    return 0;
+}
+
+int bfpq_hbfp_linear_mx4w_ok(int64_t T, int64_t N, int64_t K) { return bfpq_hbfp_linear_mx8_ok(T, N, K); }
+
+int bfpq_hbfp_linear_mx4w(const void* x8, const void* xs, const void* wcodes4, const int8_t* wexp, const void* bias, void* out,
+                          int64_t T, int64_t N, int64_t K, int out_dtype, int w_mant_bits, void* stream)
+{
+    if (!dtype_ok(out_dtype) || T < 0 || N < 0 || w_mant_bits < 1 || w_mant_bits > 3) return BFPQ_E_ARG;
+    if (T == 0 || N == 0) return 0;
+    if (!bfpq_hbfp_linear_mx4w_ok(T, N, K)) return BFPQ_E_UNSUPPORTED;
+    if (!x8 || !xs || !wcodes4 || !wexp || !out) return BFPQ_E_ARG;
+    if (!aligned16(x8, wcodes4)) return BFPQ_E_ARG;
+    if ((reinterpret_cast<uintptr_t>(xs) | reinterpret_cast<uintptr_t>(wexp)) & 3u) return BFPQ_E_ARG;
+    const int variant = mx8_variant(T, N);
+    hipStream_t s = (hipStream_t)stream;
+    const uint8_t *a = (const uint8_t*)x8, *as = (const uint8_t*)xs, *b = (const uint8_t*)wcodes4, *be = (const uint8_t*)wexp;
+    return with_dtype(out_dtype, [&](auto dt) { return launch_mx4w<dt>(variant, a, as, b, be, bias, out, (int)T, (int)N, (int)K, w_mant_bits, s); });
+}
+
+/* the split of K is the image form's: same plan, same slabs, same order of the sum */
+int bfpq_hbfp_linear_mx4w_parts(int64_t T, int64_t N, int64_t K) { return bfpq_hbfp_linear_mx8_parts(T, N, K); }
+
+int bfpq_hbfp_linear_mx4w_splitk(const void* x8, const void* xs, const void* wcodes4, const int8_t* wexp, const void* bias, void* out, float* slabs,
+                                 int parts, int64_t T, int64_t N, int64_t K, int out_dtype, int w_mant_bits, void* stream)
+{
+    if (!dtype_ok(out_dtype) || T < 0 || N < 0 || parts < 1 || parts > 64 || w_mant_bits < 1 || w_mant_bits > 3) return BFPQ_E_ARG;
+    if (T == 0 || N == 0) return 0;
+    if (!bfpq_hbfp_linear_mx4w_ok(T, N, K)) return BFPQ_E_UNSUPPORTED;
+    if (!x8 || !xs || !wcodes4 || !wexp || !out || !slabs) return BFPQ_E_ARG;
+    if (!aligned16(x8, wcodes4, slabs)) return BFPQ_E_ARG;
+    if ((reinterpret_cast<uintptr_t>(xs) | reinterpret_cast<uintptr_t>(wexp)) & 3u) return BFPQ_E_ARG;
+    const int trips = (int)(K / 256);
+    if (parts > trips) parts = trips;
+    const int tpp = (trips + parts - 1) / parts;
+    parts = (trips + tpp - 1) / tpp;                                            // (no empty part)
+    const int tiles_t = (int)((T + 127) / 128), tiles = tiles_t * (int)((N + 127) / 128);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL((k_mx4w_gemm_ring_splitk<2, 2, 2, 2, 2, 3>), dim3((unsigned)(tiles * parts)), dim3(256), 0, s, (const uint8_t*)x8, (const uint8_t*)xs,
+                       (const uint8_t*)wcodes4, (const uint8_t*)wexp, slabs, (int)T, (int)N, (int)K, tiles_t, tiles, tpp, w_mant_bits);
     launch_slab_reduce(out_dtype, slabs, (size_t)(T * N), bias, out, T * N, N, parts, s);
     return (int)hipGetLastError();
 }

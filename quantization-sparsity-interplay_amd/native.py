@@ -76,6 +76,11 @@ PROTOTYPES = {
     "bfpq_hbfp_linear_mx8": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp]),
     "bfpq_hbfp_linear_mx8_parts": (_i32, [_i64, _i64, _i64]),
     "bfpq_hbfp_linear_mx8_splitk": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp]),
+    "bfpq_hbfp_linear_mx4w_ok": (_i32, [_i64, _i64, _i64]),
+    "bfpq_hbfp_linear_mx4w": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp]),
+    "bfpq_hbfp_linear_mx4w_parts": (_i32, [_i64, _i64, _i64]),
+    "bfpq_hbfp_linear_mx4w_splitk": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _i32, _vp]),
+    "bfpq_e4m3_of_code4_host": (_i32, [_vp]),
     "bfpq_hbfp_linear_i8_ok": (_i32, [_i64, _i64, _i64]),
     "bfpq_hbfp_linear_i8_parts": (_i32, [_i64, _i64, _i64]),
     "bfpq_hbfp_linear_i8": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp]),
@@ -1124,18 +1129,15 @@ def hbfp_linear_mx8_ok(T, N, K, w_mant_bits, x_mant_bits, block_size=64):
     return block_size == 64 and 1 <= w_mant_bits <= 4 and 1 <= x_mant_bits <= 4 and bool(load_library().bfpq_hbfp_linear_mx8_ok(T, N, K))
 
 
-def hbfp_linear_mx8(x, w8, wscale, x_mant_bits, epsilon=1e-8, bias=None, out_dtype=None, act=None, x_image=None):
-    """out = Q(x) @ W^T (+ bias) for any number of tokens on the block-scaled matrix instruction: x is quantized to
-    HBFP(x_mant_bits + 1) block 64 (int8 codes + exponents), turned into its e4m3 / E8M0 image and multiplied with the
-    weight's image (mx8_from_hbfp of the packed weight, made once).  act (ActSparsity or None): the activation is pruned first
-    (quantize_mx8).  x_image: the activation's image made beforehand (e4m3 [T, K], E8M0 [T, K/64]); x then only gives shape."""
+def _mx_linear(entry, x, w_ops, N, tail, x_mant_bits, epsilon, bias, out_dtype, act, x_image):
+    """the launch both forms of the block-scaled prefill GEMM share: C entries `entry`, `entry`_parts and `entry`_splitk, the weight
+    operand `w_ops` (two tensors: image + scales, or codes + exponents), `tail` = the entry's arguments between out_dtype and stream"""
     require_device_tensor(x)
     L = load_library()
     K = x.shape[-1]
     T = x.numel() // K
-    N = w8.shape[0]
     if not hbfp_linear_mx8_ok(T, N, K, 1, x_mant_bits):
-        raise ValueError(f"hbfp_linear_mx8 needs K % 256 == 0 and activation mantissas of <= 4 bits (got T={T}, N={N}, K={K}, x_mant_bits={x_mant_bits})")
+        raise ValueError(f"{entry[5:]} needs K % 256 == 0 and activation mantissas of <= 4 bits (got T={T}, N={N}, K={K}, x_mant_bits={x_mant_bits})")
     dev = x.device
     out_dtype = out_dtype or x.dtype
     with torch.cuda.device(dev):
@@ -1143,15 +1145,44 @@ def hbfp_linear_mx8(x, w8, wscale, x_mant_bits, epsilon=1e-8, bias=None, out_dty
         out = torch.empty((T, N), dtype=out_dtype, device=dev)
         if bias is not None:
             bias = bias.to(out_dtype).contiguous()
-        parts = L.bfpq_hbfp_linear_mx8_parts(T, N, K) if SPLIT_K else 1
+        ops = (_ptr(x8), _ptr(xs), _ptr(w_ops[0]), _ptr(w_ops[1]), _ptr(bias) if bias is not None else None, _ptr(out))
+        tail = (DTYPE_CODE[out_dtype],) + tuple(tail) + (_stream(x),)
+        parts = getattr(L, entry + "_parts")(T, N, K) if SPLIT_K else 1
         if parts > 1:                                                  # few tokens: K split over several workgroups per tile, fp32 slabs
             slabs = torch.empty((parts, T, N), dtype=torch.float32, device=dev)
-            check(L.bfpq_hbfp_linear_mx8_splitk(_ptr(x8), _ptr(xs), _ptr(w8), _ptr(wscale), _ptr(bias) if bias is not None else None, _ptr(out),
-                                                _ptr(slabs), parts, T, N, K, DTYPE_CODE[out_dtype], _stream(x)), "bfpq_hbfp_linear_mx8_splitk")
+            check(getattr(L, entry + "_splitk")(*ops, _ptr(slabs), parts, T, N, K, *tail), entry + "_splitk")
         else:
-            check(L.bfpq_hbfp_linear_mx8(_ptr(x8), _ptr(xs), _ptr(w8), _ptr(wscale), _ptr(bias) if bias is not None else None, _ptr(out),
-                                         T, N, K, DTYPE_CODE[out_dtype], _stream(x)), "bfpq_hbfp_linear_mx8")
+            check(getattr(L, entry)(*ops, T, N, K, *tail), entry)
     return out.view(tuple(x.shape[:-1]) + (N,))
+
+
+def hbfp_linear_mx8(x, w8, wscale, x_mant_bits, epsilon=1e-8, bias=None, out_dtype=None, act=None, x_image=None):
+    """out = Q(x) @ W^T (+ bias) for any number of tokens on the block-scaled matrix instruction: x is quantized to
+    HBFP(x_mant_bits + 1) block 64 (int8 codes + exponents), turned into its e4m3 / E8M0 image and multiplied with the
+    weight's image (mx8_from_hbfp of the packed weight, made once).  act (ActSparsity or None): the activation is pruned first
+    (quantize_mx8).  x_image: the activation's image made beforehand (e4m3 [T, K], E8M0 [T, K/64]); x then only gives shape."""
+    return _mx_linear("bfpq_hbfp_linear_mx8", x, (w8, wscale), w8.shape[0], (), x_mant_bits, epsilon, bias, out_dtype, act, x_image)
+
+
+def hbfp_linear_mx4w_ok(T, N, K, w_mant_bits, x_mant_bits, block_size=64):
+    return block_size == 64 and 1 <= w_mant_bits <= 3 and 1 <= x_mant_bits <= 4 and bool(load_library().bfpq_hbfp_linear_mx4w_ok(T, N, K))
+
+
+def hbfp_linear_mx4w(x, codes4, exps, w_mant_bits, x_mant_bits, epsilon=1e-8, bias=None, out_dtype=None, act=None, x_image=None):
+    """hbfp_linear_mx8 with the packed weight itself as the weight operand: codes4 [N, K/2] (two's-complement nibbles, low nibble
+    first) and exps [N, K/64] (int8) as PackedBFP holds them, w_mant_bits 1..3.  The kernel makes e4m3 bytes and E8M0 scales of them
+    on the way to the matrix instruction, so no weight image is made, cached or kept; the result has the bits of hbfp_linear_mx8 on
+    mx8_from_hbfp(codes4, exps).  The activation operand (act, x_image, the shared-image memo) is handled as there."""
+    require_device_tensor_any(codes4)
+    K = x.shape[-1]
+    N = exps.shape[0]
+    if not 1 <= int(w_mant_bits) <= 3:
+        raise ValueError(f"hbfp_linear_mx4w takes 4-bit codes: w_mant_bits 1..3 (got {w_mant_bits})")
+    if codes4.dtype != torch.uint8 or codes4.numel() * 2 != N * K or exps.dtype != torch.int8 or exps.numel() * 64 != N * K:
+        raise ValueError(f"hbfp_linear_mx4w takes uint8 codes [N, K/2] and int8 exponents [N, K/64] (got {tuple(codes4.shape)} {codes4.dtype}, "
+                         f"{tuple(exps.shape)} {exps.dtype}, K={K})")
+    return _mx_linear("bfpq_hbfp_linear_mx4w", x, (codes4.contiguous(), exps.contiguous()), N, (int(w_mant_bits),), x_mant_bits, epsilon, bias,
+                      out_dtype, act, x_image)
 
 
 # ---- HBFP5-HBFP8 on the int8 matrix unit (bfpq_i8gemm.hip) ---------------------------------------

@@ -81,13 +81,19 @@ class PackedBFPLinear(torch.nn.Module):
     tokens (any number for fp32 activations).
     The codes and exponents are registered buffers (`codes`, `exps`): they follow .to() / .cuda(), appear in state_dict()
     and load back with load_state_dict(); shape / dtype / mantissa width / activation pruning travel as extra state.
-    x_sparsity (native.ActSparsity or None): the activations are pruned as the reference's in_sparsity does."""
+    x_sparsity (native.ActSparsity or None): the activations are pruned as the reference's in_sparsity does.
+    hold_image (default True): prefill forwards of a 4-bit block-64 weight keep an e4m3 image of the weight (1.016 B per weight on top
+    of the 0.516 of the codes) from the first one on.  False: they read the codes themselves (native.hbfp_linear_mx4w), the image is
+    never made and the outputs are the same bit for bit, at 1.07-1.73 x the time of the default
+    (measured per shape: bfp_ops.HOLD_IMAGE_TIME; from 8192 tokens on a weight of up to 4096 x 4096 runs the dequantize + library GEMM route
+    instead, bfp_ops.codes_route, which keeps no image either but sums in another order).  Travels as extra state."""
 
-    def __init__(self, packed, bias=None, x_mant_bits=7, epsilon=1e-8, x_sparsity=None):
+    def __init__(self, packed, bias=None, x_mant_bits=7, epsilon=1e-8, x_sparsity=None, hold_image=True):
         super().__init__()
         self.out_features, self.in_features = packed.shape
         self.x_mant_bits, self.epsilon = int(x_mant_bits), float(epsilon)
         self.x_sparsity = x_sparsity
+        self.hold_image = bool(hold_image)
         self.register_buffer("codes", packed.codes)
         self.register_buffer("exps", packed.exps)
         self._meta = dict(shape=list(packed.shape), dtype=str(packed.dtype).replace("torch.", ""), mant_bits=packed.mant_bits,
@@ -108,24 +114,25 @@ class PackedBFPLinear(torch.nn.Module):
 
     def get_extra_state(self):
         return dict(self._meta, x_mant_bits=self.x_mant_bits, epsilon=self.epsilon,
-                    x_sparsity=None if self.x_sparsity is None else self.x_sparsity.as_dict())
+                    x_sparsity=None if self.x_sparsity is None else self.x_sparsity.as_dict(), hold_image=self.hold_image)
 
     def set_extra_state(self, state):
         self._meta = {k: state[k] for k in ('shape', 'dtype', 'mant_bits', 'block_size', 'code_bits')}
         self.x_mant_bits, self.epsilon = int(state['x_mant_bits']), float(state['epsilon'])
         self.x_sparsity = native.ActSparsity.from_dict(state.get('x_sparsity'))     # (a state saved before activation pruning: dense)
+        self.hold_image = bool(state.get('hold_image', True))                       # (a state saved before the switch: the image is held)
         self._packed = None
 
     @classmethod
-    def from_linear(cls, lin, bfp_args):
+    def from_linear(cls, lin, bfp_args, hold_image=True):
         """weight -> PackedBFP.from_bfp_args with the module's config (format 'bfp', block 64, 32 or 16, mant_bits 1..7 -- 4-bit codes up to 3,
         8-bit codes from 4 --, round-half-even, N:M or prune-first unstructured weight pruning); activations use mant_bits of the same
         config.  Pruned activations (in_sparsity: N:M or unstructured, either order, the same keys) are pruned in every forward, as the
         reference does.  Configurations this module cannot reproduce (unstructured WEIGHT pruning after quantization, stochastic
-        rounding) are refused."""
+        rounding) are refused.  hold_image: as the constructor's."""
         a = bfp_ops.unpack_bfp_args(dict(bfp_args))
         pw = bfp_ops.PackedBFP.from_bfp_args(lin.weight.detach(), a)
-        return cls(pw, lin.bias, a['mant_bits'], a['epsilon'], native.ActSparsity.from_bfp_args(a))
+        return cls(pw, lin.bias, a['mant_bits'], a['epsilon'], native.ActSparsity.from_bfp_args(a), hold_image=hold_image)
 
     def forward(self, x):
         p = self.packed
@@ -133,11 +140,13 @@ class PackedBFPLinear(torch.nn.Module):
         T = x.numel() // K if K else 0
         route = bfp_ops.linear_route(T, N, K, p.code_bits, p.mant_bits, self.x_mant_bits, i8_max_tokens=bfp_ops.I8_MAX_TOKENS,
                                      block_size=p.block_size, dtype=x.dtype)
-        return p._run_linear(route, x, self.bias, self.x_mant_bits, self.epsilon, self.x_sparsity)
+        return p._run_linear(route, x, self.bias, self.x_mant_bits, self.epsilon, self.x_sparsity, self.hold_image)
 
     def extra_repr(self):
         act = "" if self.x_sparsity is None else f", x_sparsity={tuple(self.x_sparsity)}"
-        return f"in_features={self.in_features}, out_features={self.out_features}, packed_bytes={self.packed.nbytes()}{act}"
+        lean = "" if self.hold_image else ", hold_image=False"
+        return (f"in_features={self.in_features}, out_features={self.out_features}, packed_bytes={self.packed.nbytes()}, "
+                f"resident_bytes={self.packed.resident_bytes()}{act}{lean}")
 
 
 class Sparse24BFPLinear(torch.nn.Module):
@@ -197,12 +206,14 @@ class Sparse24BFPLinear(torch.nn.Module):
         return f"in_features={self.in_features}, out_features={self.out_features}, sp24_bytes={self.sparse.nbytes()}{act}"
 
 
-def pack_linear_layers(model, bfp_args, skip=("lm_head", "classifier", "score"), sparse24=False):
+def pack_linear_layers(model, bfp_args, skip=("lm_head", "classifier", "score"), sparse24=False, hold_image=True):
     """Inference deployment: replace nn.Linear / BFPLinear children by PackedBFPLinear (weights quantized once and
     held as 4-bit codes for mant_bits <= 3, 8-bit codes for 4..7; the original bf16/fp16 weight is dropped).  Needs an HBFP config with
     block_size 64, 32 or 16 and mant_bits <= 7 (+ optional N:M or unstructured pruning).  Returns the patched names and the bytes saved.
     sparse24=True: Sparse24BFPLinear instead (the 2:4-compressed form); the config must guarantee the pattern -- block 64, N:4 weight
-    pruning with N <= 2 (bfp_ops.sp24_config_check) -- or ValueError is raised before any module is replaced."""
+    pruning with N <= 2 (bfp_ops.sp24_config_check) -- or ValueError is raised before any module is replaced.
+    hold_image=False: the PackedBFPLinear modules run their prefill forwards from the codes and never make the weight's e4m3 image
+    (PackedBFPLinear; Sparse24BFPLinear holds no image and ignores it).  The bytes saved count codes and exponents either way."""
     patched, saved = [], 0
     a = bfp_ops.unpack_bfp_args(dict(bfp_args))
     if sparse24:
@@ -216,7 +227,7 @@ def pack_linear_layers(model, bfp_args, skip=("lm_head", "classifier", "score"),
                 continue
             if child.in_features % k_mult or child.out_features % 16:
                 continue                                    # shapes the packed kernels do not take stay as they are
-            new = (Sparse24BFPLinear if sparse24 else PackedBFPLinear).from_linear(child, bfp_args)
+            new = Sparse24BFPLinear.from_linear(child, bfp_args) if sparse24 else PackedBFPLinear.from_linear(child, bfp_args, hold_image)
             saved += child.weight.numel() * child.weight.element_size() - (new.sparse if sparse24 else new.packed).nbytes()
             setattr(parent, child_name, new)
             patched.append(full)
