@@ -400,6 +400,29 @@ int bfpq_hbfp_linear_decode8b(const void* xcodes_dev, const int8_t* xexp_dev, co
 /* 4-bit codes (two's-complement nibbles, low nibble first, as bfpq_quantize_nm writes them) -> int8 codes, so that HBFP4 weights
  * run on the entry points above; n_codes % 8 == 0, codes4_dev 4-byte and codes8_dev 8-byte aligned. */
 int bfpq_codes4_to_i8(const void* codes4_dev, void* codes8_dev, int64_t n_codes, void* stream);
+/* ---- the batched product of two HBFP activations on the int8 matrix unit (csrc/bfpq_bmm.hip) ----------------------------------------
+ * out[b][t][n] = sum_k x[b][t][k] w[b][n][k] for b < B: torch.matmul on the two fake-quantised operands of F_matmul_bfp (reference
+ * bfp_ops.py:240-245, the op of :187-190 with the second operand quantized along its contraction dimension, :153), the attention
+ * matmuls of the reference's GPT-2 (modeling_gpt2.py:207, 243, 297).  Arithmetic as bfpq_hbfp_linear_i8 / _i8b: one int8 matrix
+ * instruction per block of 64, 32 or 16 (an exact integer sum), one rescale by the two block scales, fp32 across blocks in block order,
+ * one rounding to out_dtype; an exponent of -128 on either side makes the block contribute NaN.  No bias.
+ *   xcodes_dev [B, T, ldk] int8, xexp_dev [B, T, K/block_size] int8, wcodes_dev [B, N, ldk] int8, wexp_dev [B, N, K/block_size] int8,
+ *   out_dev [B, T, N] of out_dtype, all dense in b.  ldk: the pitch of a code row, a multiple of 64 and >= K, the codes past K zero.
+ * Any T >= 1, N % 16 == 0, K % block_size == 0 (1 == bfpq_hbfp_bmm_i8_ok; else BFPQ_E_UNSUPPORTED).  A block_size other than 16, 32
+ * or 64, an unknown out_dtype or a mantissa width outside 1..7: BFPQ_E_ARG.  B, T or N of 0: returns 0, nothing is launched.  Codes
+ * and out 16-byte aligned (else, or NULL: BFPQ_E_ARG); exponents any alignment.  Every check returns before anything is launched. */
+int bfpq_hbfp_bmm_i8_ok(int64_t B, int64_t T, int64_t N, int64_t K, int64_t ldk, int block_size);
+int bfpq_hbfp_bmm_i8(const void* xcodes_dev, const int8_t* xexp_dev, const void* wcodes_dev, const int8_t* wexp_dev, void* out_dev, int64_t B,
+                     int64_t T, int64_t N, int64_t K, int64_t ldk, int block_size, int out_dtype, int w_mant_bits, int x_mant_bits, void* stream);
+/* The second operand of that product when its blocks run along its second-to-last dimension (V of P V): in_dev [B, S, D] of dtype,
+ * dense -> int8 codes [B, D, ldk] + int8 exponents [B, D, S/block_size] of float_to_bfp_blocked(in.transpose(-1, -2), identifier 'w')
+ * (reference bfp_ops.py:153 with :29-59: the transposed copy, the quantizer and the transpose back), round-half-even, no pruning; one
+ * read of in_dev, a tile transpose through LDS.  code * 2^(exp - mant_bits) is that operand bit for bit (up to the sign of zero); the
+ * codes from S to ldk are written as zeros.  block_size 16, 32 or 64 and mant_bits 1..7 (else BFPQ_E_ARG); S % block_size == 0,
+ * D % 16 == 0, ldk % 64 == 0, ldk >= S (else BFPQ_E_UNSUPPORTED); B, S or D of 0 returns 0.  in_dev and codes_dev 16-byte aligned;
+ * exp_win_dev: bfpq_exp_window_host(dtype) on the device. */
+int bfpq_hbfp_codes_t(const void* in_dev, void* codes_dev, int8_t* exps_dev, int64_t B, int64_t S, int64_t D, int64_t ldk, int dtype,
+                      int block_size, int mant_bits, double epsilon, const uint8_t* exp_win_dev, void* stream);
 /* ---- 2:4-compressed packed weights (format sp24) and their few-token product on v_smfmac_i32_16x16x64_i8 -------------------------
  * A weight pruned N:M with M = 4, N <= 2 along K (_structured_N_M_sparsity, reference bfp_ops.py:73-91) and quantized to HBFP block 64
  * holds at most 2 non-zero codes per group of 4.  sp24 keeps those two codes and their 2-bit positions, tiled for the decode kernel

@@ -1179,10 +1179,127 @@ def F_linear_bfp(**kwargs):
     return _get_bfp_op(F.linear, 'linear', bfp_args) if bfp_args['num_format'] == 'bfp' else F.linear
 
 
-def F_matmul_bfp(**kwargs):
-    """reference: bfp_ops.py:240-245"""
+class MatmulStats:
+    """what an F_matmul_bfp(matrix_unit='int8') op ran: i8_calls on the int8 matrix unit, fake_calls as the plain composition"""
+
+    def __init__(self):
+        self.i8_calls = 0
+        self.fake_calls = 0
+
+
+# The batched int8 route by default: from this many rows of the first operand (T = x.shape[-2]) on, None: never.  Keyed by (operand
+# dtype, block 64 or not, family): 'qk' is a contraction no longer than the output is wide (K <= N: Q K^T, bound by the output write),
+# 'pv' the other one (K > N: P V, bound by reading P).  Measured against the fake route timed on the parent commit, hipGraph replay,
+# GPT-2 small at batch 1 and 8 (T 1024 and 128) and a 32-head D = 128, T = 2048 shape (profiles/r11_bmm.json): fp32 block 64 wins
+# everywhere (1.32-2.01x); bf16 block 64 wins P V (1.17-1.34x) and loses Q K^T from T = 1024 on (0.53-0.91x; 0.96-1.03x at T = 128);
+# block 16 with a 1:4-pruned second operand wins only fp32 Q K^T (1.09-1.45x), is even or slower on fp32 P V (0.78-1.01x) and slower on
+# bf16 (0.31-0.83x).  Block 32 and dense block 16 were not measured and take the block-16 entries; fp16 takes the bf16 ones.
+MATMUL_I8_MIN = {
+    (torch.float32, True, 'qk'): 1, (torch.float32, True, 'pv'): 1, (torch.float32, False, 'qk'): 1, (torch.float32, False, 'pv'): None,
+    (torch.bfloat16, True, 'qk'): None, (torch.bfloat16, True, 'pv'): 1, (torch.bfloat16, False, 'qk'): None, (torch.bfloat16, False, 'pv'): None,
+}
+
+
+def matmul_i8_min(dtype, block_size, N, K):
+    """the MATMUL_I8_MIN entry of a problem (a dtype not listed: the bf16 entry)"""
+    key = (block_size == 64, 'qk' if K <= N else 'pv')
+    return MATMUL_I8_MIN.get((dtype,) + key, MATMUL_I8_MIN.get((torch.bfloat16,) + key))
+
+
+def _matmul_pruning_ok(a):
+    """pruning of either matmul operand as _stoc_eligible accepts it: in_sparsity on x, w_sparsity on w"""
+    if a['in_sparsity'] == True:  # noqa: E712
+        if a['sparsity_mode'] == 'structured':
+            if not (0 < a['N'] <= a['M']):
+                return False
+        elif a['sparsity_mode'] != 'unstructured' or not (0 < a['sparsity_frac'] <= 1):
+            return False
+    if a['w_sparsity'] == True:  # noqa: E712
+        if a['sparsity_mode'] == 'unstructured':
+            if not (0 < a['sparsity_frac'] <= 1):
+                return False
+        elif a['sparsity_mode'] != 'structured' or not (0 < a['N'] <= a['M']) or a['M'] not in (2, 4, 8):
+            return False
+    return True
+
+
+def matmul_route(x, w, a, matrix_unit):
+    """the contraction of F_matmul_bfp(matrix_unit=...)(x, w) under the bfp_args a: 'int8' (native.hbfp_bmm_i8 on codes of both operands)
+    or 'fake' (MxM_pre_processing + torch.matmul).  'int8' needs all of: matrix_unit 'int8'; no gradient recording; 'bfp' in both formats,
+    round-half-even, block 16, 32 or 64, 1..7 mantissa bits; both operands of one dtype (fp32, bf16, fp16) on one ROCm device; not
+    compiling; equal leading batch dimensions (broadcasting: 'fake'); x contiguous along its last dimension; K % block == 0,
+    N % 16 == 0 and the C predicate; pruning as _stoc_eligible takes it; T >= the problem's MATMUL_I8_MIN entry (matmul_i8_min).  Host
+    logic only."""
+    if matrix_unit != 'int8' or torch.is_grad_enabled():
+        return 'fake'
+    if (a['num_format'] != 'bfp' or a['sparsity_num_format'] != 'bfp' or a['rounding_mode'] != rounding_modes.DETERM
+            or a['block_size'] not in (64,) + native.I8_BLOCKS or not (1 <= a['mant_bits'] <= 7)):
+        return 'fake'
+    if (not isinstance(x, torch.Tensor) or not isinstance(w, torch.Tensor) or x.dim() < 2 or w.dim() < 2 or x.dtype != w.dtype
+            or x.dtype not in native.DTYPE_CODE or x.device.type != 'cuda' or x.device != w.device or torch.compiler.is_compiling()):
+        return 'fake'
+    if tuple(x.shape[:-2]) != tuple(w.shape[:-2]) or x.shape[-1] != w.shape[-2] or x.stride(-1) != 1:
+        return 'fake'
+    T, K, N = x.shape[-2], x.shape[-1], w.shape[-1]
+    B = x.numel() // (T * K) if T * K else 0
+    if B < 1 or K % a['block_size'] or N % 16 or not _matmul_pruning_ok(a):
+        return 'fake'
+    lim = matmul_i8_min(x.dtype, a['block_size'], N, K)
+    if lim is None or T < lim or not native.hbfp_bmm_i8_ok(B, T, N, K, a['mant_bits'], a['mant_bits'], a['block_size']):
+        return 'fake'
+    return 'int8'
+
+
+def _matmul_i8(x, w, a):
+    """torch.matmul(Q_in(x), Q_w(w^T)^T) on the int8 matrix unit for a call matmul_route sends there.  x's codes: act_codes on its
+    [B T, K] rows.  w's codes, blocks along K = its second-to-last dimension: where w^T is contiguous (key.transpose(-1, -2)) act_codes on
+    the [B N, K] rows of that view, no copy; a dense w goes through the transposed quantizer (native.codes_transposed), one read; a pruned
+    w through the transposed copy and act_codes, where the N:M tie order and the whole-tensor threshold live."""
+    m, eps, block = a['mant_bits'], a['epsilon'], a['block_size']
+    T, K, N = x.shape[-2], x.shape[-1], w.shape[-1]
+    B = x.numel() // (T * K)
+    xq = native.act_codes(x.reshape(B * T, K), m, eps, native.ActSparsity.from_bfp_args(a), block_size=block)
+    wt, w_act = w.transpose(-1, -2), _weight_sparsity(a)
+    if wt.is_contiguous():
+        wq = native.act_codes(wt.reshape(B * N, K), m, eps, w_act, block_size=block)
+    elif w_act is None:
+        wq = native.codes_transposed(w.reshape(B, K, N), block, m, eps)
+    else:
+        wq = native.act_codes(wt.contiguous().view(B * N, K), m, eps, w_act, block_size=block)
+    out = native.hbfp_bmm_i8(xq, wq, B, T, N, K, m, m, block_size=block, out_dtype=x.dtype)
+    return out.view(tuple(x.shape[:-1]) + (N,))
+
+
+def _gen_matmul_i8_op(bfp_args, matrix_unit):
+    """the F_matmul_bfp op with the matrix-unit switch on: per call matmul_route picks the batched int8 GEMM or the plain composition
+    (every gradient-recording call, and whatever the route refuses).  The op's matmul_stats (MatmulStats) counts both."""
+    fake = _get_bfp_op(torch.matmul, 'matmul', bfp_args, True)
+    stats = MatmulStats()
+
+    def bfp_op(x, w, *args, **kwargs):
+        if not args and not kwargs and matmul_route(x, w, bfp_args, matrix_unit) == 'int8':
+            stats.i8_calls += 1
+            return _matmul_i8(x, w, bfp_args)
+        stats.fake_calls += 1
+        return fake(x, w, *args, **kwargs)
+
+    bfp_op.__name__ = fake.__name__
+    bfp_op.matmul_stats = stats
+    return bfp_op
+
+
+def F_matmul_bfp(matrix_unit=False, **kwargs):
+    """reference: bfp_ops.py:240-245.  matrix_unit='int8': inference calls that matmul_route accepts run as one batched GEMM on the int8
+    matrix unit (exact block sums, fp32 across blocks; agrees with the plain composition up to that summation order), everything else as
+    without it; the op then carries matmul_stats.  False (the default): the reference's composition.  Any other value raises ValueError --
+    True included: there is no block-scaled batched route."""
+    mu = matrix_unit_value(matrix_unit)
+    if mu is True:
+        raise ValueError("F_matmul_bfp: matrix_unit must be False or 'int8' (there is no block-scaled batched route)")
     bfp_args = unpack_bfp_args(kwargs)
-    return _get_bfp_op(torch.matmul, 'matmul', bfp_args, True) if bfp_args['num_format'] == 'bfp' else torch.matmul
+    if bfp_args['num_format'] != 'bfp':
+        return torch.matmul
+    return _gen_matmul_i8_op(bfp_args, mu) if mu else _get_bfp_op(torch.matmul, 'matmul', bfp_args, True)
 
 
 class _BFPModule:

@@ -1,0 +1,360 @@
+// bfpq_bmm.hip -- the batched contraction of two activations, both HBFP: out[b][t][n] = sum_k x[b][t][k] w[b][n][k], b < B, with x and w
+// int8 codes + one int8 exponent per block of 64, 32 or 16, mantissa widths xm, wm in 1..7.  Replaces torch.matmul on the two
+// fake-quantised operands of F_matmul_bfp (reference bfp_ops.py:240-245 through :187-190), the attention matmuls of the reference's
+// GPT-2 (modeling_gpt2.py:207, 243, 297).  Neither operand is a weight: both sets of codes are made per call.
+//
+// Arithmetic: that of bfpq_i8gemm.hip.  One v_mfma_i32_16x16x64_i8 per block of 64 (v_mfma_i32_16x16x32_i8 per block of 32 or 16, block
+// 16 with zeros in the A operand of lanes 32..63), an exact integer block sum (|sum| <= 64 * 127^2 < 2^20), one rescale by
+// 2^(ex - xm) * 2^(ew - wm), fp32 accumulation across blocks in block order.  The MFMA's C operand is the integer 0x4B400000 (the bits
+// of 1.5 * 2^23), so its int32 result read as a float is 1.5 * 2^23 + sum: u = fma(f, sx, -1.5 * 2^23 * sx) is sum * sx exactly, then
+// acc = fma(u, sw, acc); both are packed fp32 ops on two outputs.  A block exponent of -128 (the NaN block marker) makes the scale NaN.
+//
+// Layout: code rows have a pitch ldk (a multiple of 64, >= K) with zero codes in the pad, so K is walked in 64-byte chunks whatever
+// K % 64 is (K = 32 and K = 64 take the same path; blocks past K / BLK are skipped, their exponents do not exist).  Exponent rows are
+// dense, [rows, K / BLK]; they are read a dword = 4 blocks at a time where the rows are 4-byte aligned, byte by byte elsewhere.  No
+// K % 256 requirement, no split-K, no LDS: the two shape families of attention leave nothing for a staged tile to re-use --
+//   Q K^T: K = 64 or 128 is one or two chunks, the time goes to the [T, N] output write;
+//   P V:   N = 64 or 128 is one tile row, x = P's codes are read exactly once, w = V's codes ([N, ldk], 64-256 KB) stay in L2 / L1.
+// A wave owns 16 TM output features (w rows, the MFMA's A) x 16 TN tokens (x rows, B) and reads its operands straight from global
+// memory, 16 bytes per lane and row (no register double buffer: it spilled; 2-4 waves per SIMD cover the latency).  The four waves of a workgroup are neighbours along T (they share
+// the w rows, so those hit in L1).  Batch is gridDim.y (a grid-stride loop past 65535).  Lane map as in bfpq_i8gemm.hip: A lane l = row
+// l & 15, bytes 16 (l >> 4) .. +15 of the block; D lane l holds rows 4 (l >> 4) + j of column l & 15, i.e. four consecutive output
+// features of one token -- one 8- or 16-byte store.
+//
+// k_codes_t: the quantizer for an operand whose blocks run along its second-to-last dimension (V in P V): reads v[B, S, D] once and
+// writes int8 codes [B, D, ldk] + int8 exponents [B, D, S / BLK], the operand float_to_bfp_blocked(v.transpose(-1, -2)) as codes
+// (reference bfp_ops.py:153: the transposed copy, the quantizer launch and the transpose back).  A workgroup transposes a tile of
+// 64 s x 64 d through LDS: 16-byte loads along d, the block maximum and the step-by-step scale of bfpq_common.h per (d, block), 16 codes
+// of one d per thread, and 16-byte stores along s from a second LDS tile.  Rows s >= S of a tile read as zeros and quantize to zero
+// codes: that is the pad up to ldk.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "bfpq.h"
+#include "bfpq_common.h"
+#include "bfpq_device.h"
+
+using namespace bfpq;
+
+namespace {
+
+typedef int v4i __attribute__((ext_vector_type(4)));
+typedef float v2f __attribute__((ext_vector_type(2)));
+typedef float v4f __attribute__((ext_vector_type(4)));
+
+constexpr int MAGIC_I = 0x4B400000;                       // bits of 1.5 * 2^23
+constexpr float MAGIC_F = 12582912.0f;
+constexpr int kWaves = 4;                                 // waves of a workgroup, neighbours along T
+
+__device__ __forceinline__ float pow2_scale(int e, int m)    // 2^(e - m); NaN for the NaN block marker
+{
+    return e == -128 ? __builtin_nanf("") : ldexpf(1.0f, e - m);
+}
+
+// What depends on the block (as I8Blk of bfpq_i8gemm.hip): the lane's bytes inside a block, whether its A operand is live, the
+// instruction.  Blocks 32 / 16 use v_mfma_i32_16x16x32_i8 (A lane l = row l & 15, bytes 8 (l >> 4) .. +7); block 16 puts its 16 bytes in
+// lanes l >> 4 = 0, 1 and zeros in the A operand of the others.
+template <int BLK> struct BmmBlk {
+    static_assert(BLK == 16 || BLK == 32, "blocks of 16, 32 or 64");
+    using op_t = long;
+    __device__ __forceinline__ static int lane(int q) { return 8 * (BLK == 32 ? q : (q & 1)); }
+    __device__ __forceinline__ static bool a_live(int q) { return BLK == 32 || q < 2; }
+    __device__ __forceinline__ static v4i mfma(long a, long b, v4i c) { return __builtin_amdgcn_mfma_i32_16x16x32_i8(a, b, c, 0, 0, 0); }
+};
+template <> struct BmmBlk<64> {
+    using op_t = v4i;
+    __device__ __forceinline__ static int lane(int q) { return q * 16; }
+    __device__ __forceinline__ static bool a_live(int) { return true; }
+    __device__ __forceinline__ static v4i mfma(v4i a, v4i b, v4i c) { return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0); }
+};
+
+// exponents of blocks 4 g .. 4 g + 3 of one row as a dword (byte i = block 4 g + i; blocks past the row's end read as 0 and are never
+// used).  off = row * nb + 4 g, left = nb - 4 g; dw: the rows are 4-byte aligned (nb % 4 == 0 and an aligned base)
+__device__ __forceinline__ uint32_t exp4(const int8_t* __restrict__ e, uint32_t off, int left, bool dw)
+{
+    if (dw) return *reinterpret_cast<const uint32_t*>(e + off);
+    uint32_t v = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+        if (i < left) v |= (uint32_t)(uint8_t)e[off + i] << (8 * i);
+    return v;
+}
+
+// (the second launch bound is waves per SIMD: without it the compiler spends the whole register file on hoisted loads at occupancy 1)
+template <int BLK, int OUT_DT, int TM, int TN>
+__global__ void __launch_bounds__(64 * kWaves, TN == 4 ? 2 : 3) k_bmm_i8(const int8_t* __restrict__ xc, const int8_t* __restrict__ xe, const int8_t* __restrict__ wc,
+                                                        const int8_t* __restrict__ we, void* __restrict__ out, int B, int T, int N, int K, int ldk,
+                                                        int tiles_t, int xm, int wm)
+{
+    using Blk = BmmBlk<BLK>;
+    using op_t = typename Blk::op_t;
+    constexpr int NBS = 64 / BLK;                                // blocks per 64-byte chunk
+    constexpr int CPG = 4 / NBS > 0 ? 4 / NBS : 1;               // chunks per exponent dword (4 blocks)
+    constexpr int BN = 16 * TM, BT = 16 * TN;
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63, r = l & 15, q = l >> 4;
+    const int t0 = (((int)blockIdx.x % tiles_t) * kWaves + w) * BT, n0 = ((int)blockIdx.x / tiles_t) * BN;
+    if (t0 >= T) return;                                         // (wave-uniform; the kernel has no barrier)
+    const int nb = K / BLK, nch = (K + 63) >> 6;
+    const bool dw = !(nb & 3) && !((reinterpret_cast<uintptr_t>(xe) | reinterpret_cast<uintptr_t>(we)) & 3u);
+
+    // rows past N / T repeat the last row (their results are not stored)
+    uint32_t offW[TM], offX[TN], ewo[TM][4], exo[TN];
+#pragma unroll
+    for (int i = 0; i < TM; i++) {
+        const int n = n0 + 16 * i + r;
+        offW[i] = (uint32_t)(n < N ? n : N - 1) * (uint32_t)ldk + Blk::lane(q);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int ne = n0 + 16 * i + 4 * q + j;
+            ewo[i][j] = (uint32_t)(ne < N ? ne : N - 1) * (uint32_t)nb;
+        }
+    }
+#pragma unroll
+    for (int jt = 0; jt < TN; jt++) {
+        const int t = t0 + 16 * jt + r;
+        offX[jt] = (uint32_t)(t < T ? t : T - 1) * (uint32_t)ldk + Blk::lane(q);
+        exo[jt] = (uint32_t)(t < T ? t : T - 1) * (uint32_t)nb;
+    }
+    const v4i magic = {MAGIC_I, MAGIC_I, MAGIC_I, MAGIC_I};
+
+    for (int b = blockIdx.y; b < B; b += gridDim.y) {
+        const int8_t* const xcb = xc + (size_t)b * T * ldk;
+        const int8_t* const wcb = wc + (size_t)b * N * ldk;
+        const int8_t* const xeb = xe + (size_t)b * T * nb;
+        const int8_t* const web = we + (size_t)b * N * nb;
+
+        // the lane's operands of chunk c: NBS pieces per row (one 16-byte piece at block 64, 8-byte pieces at blocks 32 / 16)
+        auto codes = [&](int c, op_t (&aF)[TM][NBS], op_t (&bF)[TN][NBS]) __attribute__((always_inline)) {
+#pragma unroll
+            for (int i = 0; i < TM; i++)
+#pragma unroll
+                for (int s = 0; s < NBS; s++) {
+                    aF[i][s] = *reinterpret_cast<const op_t*>(wcb + offW[i] + (c << 6) + s * BLK);
+                    if (!Blk::a_live(q)) aF[i][s] = op_t{};
+                }
+#pragma unroll
+            for (int jt = 0; jt < TN; jt++)
+#pragma unroll
+                for (int s = 0; s < NBS; s++) bF[jt][s] = *reinterpret_cast<const op_t*>(xcb + offX[jt] + (c << 6) + s * BLK);
+        };
+        auto exps = [&](int g, uint32_t (&ewd)[TM][4], uint32_t (&exd)[TN]) __attribute__((always_inline)) {
+#pragma unroll
+            for (int i = 0; i < TM; i++)
+#pragma unroll
+                for (int j = 0; j < 4; j++) ewd[i][j] = exp4(web, ewo[i][j] + 4 * g, nb - 4 * g, dw);
+#pragma unroll
+            for (int jt = 0; jt < TN; jt++) exd[jt] = exp4(xeb, exo[jt] + 4 * g, nb - 4 * g, dw);
+        };
+
+        v2f acc[TM][TN][2];
+#pragma unroll
+        for (int i = 0; i < TM; i++)
+#pragma unroll
+            for (int jt = 0; jt < TN; jt++) acc[i][jt][0] = acc[i][jt][1] = v2f{0.f, 0.f};
+
+        op_t aF[TM][NBS], bF[TN][NBS];
+        uint32_t ewd[TM][4], exd[TN];
+#pragma unroll 1
+        for (int c = 0; c < nch; c++) {
+            if (c % CPG == 0) exps(c / CPG, ewd, exd);           // a new exponent dword
+            codes(c, aF, bF);
+#pragma unroll
+            for (int s = 0; s < NBS; s++) {
+                const int blk = c * NBS + s;
+                if (blk < nb) {                                  // (K % 64 != 0: the tail of the last chunk is pad)
+                    const int sh = 8 * (blk & 3);
+                    v2f sx[TN], nm[TN];
+#pragma unroll
+                    for (int jt = 0; jt < TN; jt++) {
+                        const float sc = pow2_scale((int)(int8_t)(exd[jt] >> sh), xm);
+                        sx[jt] = v2f{sc, sc};
+                        nm[jt] = v2f{-MAGIC_F * sc, -MAGIC_F * sc};
+                    }
+#pragma unroll
+                    for (int i = 0; i < TM; i++) {
+                        const v2f sw0 = v2f{pow2_scale((int)(int8_t)(ewd[i][0] >> sh), wm), pow2_scale((int)(int8_t)(ewd[i][1] >> sh), wm)};
+                        const v2f sw1 = v2f{pow2_scale((int)(int8_t)(ewd[i][2] >> sh), wm), pow2_scale((int)(int8_t)(ewd[i][3] >> sh), wm)};
+#pragma unroll
+                        for (int jt = 0; jt < TN; jt++) {
+                            const v4f f = __builtin_bit_cast(v4f, Blk::mfma(aF[i][s], bF[jt][s], magic));
+                            const v2f f01 = f.xy, f23 = f.zw;
+                            const v2f u01 = __builtin_elementwise_fma(f01, sx[jt], nm[jt]);
+                            const v2f u23 = __builtin_elementwise_fma(f23, sx[jt], nm[jt]);
+                            acc[i][jt][0] = __builtin_elementwise_fma(u01, sw0, acc[i][jt][0]);
+                            acc[i][jt][1] = __builtin_elementwise_fma(u23, sw1, acc[i][jt][1]);
+                        }
+                    }
+                }
+            }
+        }
+
+        // the lane holds features n .. n + 3 of token t
+        const size_t ob = (size_t)b * T * N;
+#pragma unroll
+        for (int i = 0; i < TM; i++) {
+            const int n = n0 + 16 * i + 4 * q;
+            if (n >= N) continue;                                // (N % 16 == 0: all four or none)
+#pragma unroll
+            for (int jt = 0; jt < TN; jt++) {
+                const int t = t0 + 16 * jt + r;
+                if (t >= T) continue;
+                const v2f a01 = acc[i][jt][0], a23 = acc[i][jt][1];
+                const size_t o = ob + (size_t)t * N + n;
+                if constexpr (OUT_DT == BFPQ_F32) {
+                    *reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + o) = make_float4(a01.x, a01.y, a23.x, a23.y);
+                } else {
+                    const uint32_t lo = f32_to_raw<OUT_DT>(a01.x) | (f32_to_raw<OUT_DT>(a01.y) << 16);
+                    const uint32_t hi = f32_to_raw<OUT_DT>(a23.x) | (f32_to_raw<OUT_DT>(a23.y) << 16);
+                    *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(out) + o) = make_uint2(lo, hi);
+                }
+            }
+        }
+    }
+}
+
+// ---- the transposed quantizer ----------------------------------------------------------------------------------------------------
+constexpr int kTS = 64, kTD = 64;                            // tile: s x d
+constexpr int kPitch = kTD + 1;                              // words per s row of the value tile (column reads hit 64 banks)
+
+template <int DT>
+__global__ void __launch_bounds__(256) k_codes_t(const void* __restrict__ in, int8_t* __restrict__ codes, int8_t* __restrict__ exps, int B, int S,
+                                                 int D, int ldk, int block, int mant_bits, float eps_dt, const uint8_t* __restrict__ exp_win)
+{
+    using Tr = Traits<DT>;
+    using raw_t = typename Tr::raw_t;
+    constexpr int VEC = Tr::VEC, LPR = kTD / VEC, RPP = 256 / LPR;        // lanes per tile row, rows per pass
+    __shared__ uint8_t s_win[BFPQ_EXP_WIN_ENTRIES];
+    __shared__ uint32_t s_val[kTS * kPitch];                              // raw values, [s][d]
+    __shared__ uint32_t s_max[4 * kTD];                                   // magnitude maximum of each wave's 16 s, per d
+    __shared__ __attribute__((aligned(16))) int8_t s_code[kTD * kTS];     // codes, [d][s]
+    const int tid = threadIdx.x;
+    for (int i = tid; i < BFPQ_EXP_WIN_ENTRIES; i += 256) s_win[i] = exp_win[i];
+    const int s0 = blockIdx.x * kTS, d0 = blockIdx.y * kTD;
+    const int nb = S / block;
+    const int d = tid & 63, sq = tid >> 6;                                // this thread's column and its 16 rows sq * 16 .. +15
+    const int per = block >> 4;                                           // waves that share a block (1, 2 or 4)
+    for (int b = blockIdx.z; b < B; b += gridDim.z) {
+        const raw_t* const src = reinterpret_cast<const raw_t*>(in) + (size_t)b * S * D;
+        __syncthreads();                                                  // (the previous batch's tiles are read; s_win is written)
+        // load: 16 bytes per lane along d; rows past S and columns past D read as zeros
+#pragma unroll
+        for (int p = 0; p < kTS / RPP; p++) {
+            const int row = p * RPP + tid / LPR, col = (tid % LPR) * VEC;
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if (s0 + row < S && d0 + col < D) v = *reinterpret_cast<const uint4*>(src + (size_t)(s0 + row) * D + d0 + col);
+            uint32_t* const dst = s_val + row * kPitch + col;
+            if constexpr (VEC == 4) {
+                dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
+            } else {
+                dst[0] = v.x & 0xffffu; dst[1] = v.x >> 16; dst[2] = v.y & 0xffffu; dst[3] = v.y >> 16;
+                dst[4] = v.z & 0xffffu; dst[5] = v.z >> 16; dst[6] = v.w & 0xffffu; dst[7] = v.w >> 16;
+            }
+        }
+        __syncthreads();
+        uint32_t raw[16], mx = 0;
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            raw[i] = s_val[(sq * 16 + i) * kPitch + d];
+            const uint32_t k = raw[i] & Tr::ABS;
+            mx = k > mx ? k : mx;
+        }
+        s_max[sq * kTD + d] = mx;
+        __syncthreads();
+        const int first = sq & ~(per - 1);                                // first wave of this thread's block
+        for (int o = 0; o < per; o++) { const uint32_t k = s_max[(first + o) * kTD + d]; mx = k > mx ? k : mx; }
+        const BlockScale bs = block_scale<DT>(mx, mant_bits, eps_dt, s_win);
+        uint32_t pk[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            float c;
+            quant_elem<DT>(raw_to_f32<DT>(raw[i]), bs, false, 0.f, &c);
+            pk[i >> 2] |= ((uint32_t)(int)c & 0xffu) << (8 * (i & 3));
+        }
+        *reinterpret_cast<uint4*>(s_code + d * kTS + sq * 16) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
+        const int s = s0 + sq * 16;
+        if (sq == first && s < S && d0 + d < D) exps[((size_t)b * D + d0 + d) * nb + s / block] = sat_exp(bs);
+        __syncthreads();
+        // store: 16 bytes per lane along s, four lanes per d row
+        const int dr = tid >> 2, piece = (tid & 3) * 16;
+        if (d0 + dr < D && s0 + piece < ldk)
+            *reinterpret_cast<uint4*>(codes + ((size_t)b * D + d0 + dr) * ldk + s0 + piece) = *reinterpret_cast<const uint4*>(s_code + dr * kTS + piece);
+    }
+}
+
+template <class F> void with_block(int block_size, F&& f)
+{
+    if (block_size == 32) f(std::integral_constant<int, 32>{});
+    else if (block_size == 16) f(std::integral_constant<int, 16>{});
+    else f(std::integral_constant<int, 64>{});
+}
+
+bool block_ok(int block_size) { return block_size == 16 || block_size == 32 || block_size == 64; }
+
+// tokens per wave: 16 TN.  The widest tile that still gives every SIMD of the chip two waves, else the narrowest (P V at batch 1 has
+// few tiles; Q K^T has thousands)
+int bmm_tn(int64_t B, int64_t T, int64_t N)
+{
+    const int64_t rows = (N + 63) / 64;
+    for (int tn = 4; tn > 1; tn >>= 1)
+        if (B * rows * ((T + 16 * tn - 1) / (16 * tn)) >= 2048) return tn;
+    return 1;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bfpq_hbfp_bmm_i8_ok(int64_t B, int64_t T, int64_t N, int64_t K, int64_t ldk, int block_size)
+{
+    const int64_t lim = (int64_t)1 << 31;
+    return block_ok(block_size) && B >= 1 && T >= 1 && N >= 16 && N % 16 == 0 && K >= block_size && K % block_size == 0 && ldk >= K &&
+           ldk % 64 == 0 && T * ldk < lim && N * ldk < lim && T * N < lim && ((T + 15) / 16) * ((N + 63) / 64) < lim / 4;
+}
+
+int bfpq_hbfp_bmm_i8(const void* xcodes, const int8_t* xexp, const void* wcodes, const int8_t* wexp, void* out, int64_t B, int64_t T, int64_t N,
+                     int64_t K, int64_t ldk, int block_size, int out_dtype, int w_mant_bits, int x_mant_bits, void* stream)
+{
+    if (!dtype_ok(out_dtype) || !block_ok(block_size) || w_mant_bits < 1 || w_mant_bits > 7 || x_mant_bits < 1 || x_mant_bits > 7 || B < 0 ||
+        T < 0 || N < 0)
+        return BFPQ_E_ARG;
+    if (B == 0 || T == 0 || N == 0) return 0;
+    if (!bfpq_hbfp_bmm_i8_ok(B, T, N, K, ldk, block_size)) return BFPQ_E_UNSUPPORTED;
+    if (!xcodes || !xexp || !wcodes || !wexp || !out || !aligned16(xcodes, wcodes, out)) return BFPQ_E_ARG;
+    const int tn = bmm_tn(B, T, N);
+    const int tiles_t = (int)((T + 16 * tn * kWaves - 1) / (16 * tn * kWaves));
+    const dim3 grid((unsigned)(tiles_t * ((N + 63) / 64)), (unsigned)(B < 65535 ? B : 65535));
+    hipStream_t s = (hipStream_t)stream;
+    with_block(block_size, [&](auto blk) {
+        with_dtype(out_dtype, [&](auto dt) {
+            auto go = [&](auto tnc) {
+                hipLaunchKernelGGL((k_bmm_i8<decltype(blk)::value, decltype(dt)::value, 4, decltype(tnc)::value>), grid, dim3(64 * kWaves), 0, s,
+                                   (const int8_t*)xcodes, xexp, (const int8_t*)wcodes, wexp, out, (int)B, (int)T, (int)N, (int)K, (int)ldk, tiles_t,
+                                   x_mant_bits, w_mant_bits);
+            };
+            if (tn == 4) go(std::integral_constant<int, 4>{});
+            else if (tn == 2) go(std::integral_constant<int, 2>{});
+            else go(std::integral_constant<int, 1>{});
+        });
+    });
+    return (int)hipGetLastError();
+}
+
+int bfpq_hbfp_codes_t(const void* in, void* codes, int8_t* exps, int64_t B, int64_t S, int64_t D, int64_t ldk, int dtype, int block_size,
+                      int mant_bits, double epsilon, const uint8_t* exp_win, void* stream)
+{
+    if (!dtype_ok(dtype) || !block_ok(block_size) || mant_bits < 1 || mant_bits > 7 || B < 0 || S < 0 || D < 0) return BFPQ_E_ARG;
+    if (B == 0 || S == 0 || D == 0) return 0;
+    const int64_t lim = (int64_t)1 << 31;
+    if (S % block_size != 0 || D % 16 != 0 || ldk < S || ldk % 64 != 0 || S * D >= lim || D * ldk >= lim || ldk / 64 >= lim ||
+        (D + kTD - 1) / kTD > 65535)
+        return BFPQ_E_UNSUPPORTED;
+    if (!in || !codes || !exps || !exp_win || !aligned16(in, codes)) return BFPQ_E_ARG;
+    const float eps_dt = bfpq_dev::h_round((float)epsilon, dtype);
+    const dim3 grid((unsigned)(ldk / kTS), (unsigned)((D + kTD - 1) / kTD), (unsigned)(B < 65535 ? B : 65535));
+    with_dtype(dtype, [&](auto dt) {
+        hipLaunchKernelGGL((k_codes_t<decltype(dt)::value>), grid, dim3(256), 0, (hipStream_t)stream, in, (int8_t*)codes, exps, (int)B, (int)S,
+                           (int)D, (int)ldk, block_size, mant_bits, eps_dt, exp_win);
+    });
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

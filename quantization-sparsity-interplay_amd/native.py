@@ -101,6 +101,9 @@ PROTOTYPES = {
     "bfpq_hbfp_linear_sp24": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
     "bfpq_adam_step_list": (_i32, [_vp, _vp, _i32, _vp]),
     "bfpq_adam_step_list_ok": (_i32, [_i32, _i32]),
+    "bfpq_hbfp_bmm_i8_ok": (_i32, [_i64, _i64, _i64, _i64, _i64, _i32]),
+    "bfpq_hbfp_bmm_i8": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "bfpq_hbfp_codes_t": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _dbl, _vp, _vp]),
 }
 
 
@@ -1263,6 +1266,76 @@ def hbfp_linear_i8(x, wcodes8, wexps, w_mant_bits, x_mant_bits, epsilon=1e-8, bi
     return out.view(tuple(x.shape[:-1]) + (N,))
 
 
+
+# ---- two HBFP activations on the int8 matrix unit, batched (bfpq_bmm.hip) ---------------------------------
+def code_pitch(K):
+    """the pitch of a code row of hbfp_bmm_i8: K rounded up to 64-byte chunks"""
+    return (int(K) + 63) // 64 * 64
+
+
+def hbfp_bmm_i8_ok(B, T, N, K, w_mant_bits, x_mant_bits, block_size=64):
+    """hbfp_bmm_i8 takes this problem: block 64, 32 or 16, mantissas of 1..7 bits on both sides, any T >= 1, N % 16 == 0,
+    K % block_size == 0 (bfpq_hbfp_bmm_i8_ok at the pitch code_pitch(K))"""
+    return bool(1 <= w_mant_bits <= 7 and 1 <= x_mant_bits <= 7 and block_size in (64,) + I8_BLOCKS
+                and load_library().bfpq_hbfp_bmm_i8_ok(int(B), int(T), int(N), int(K), code_pitch(K), int(block_size)))
+
+
+def _pitched_codes(codes, rows, K, what):
+    """int8 codes [rows, K] (or already [rows, code_pitch(K)]) -> [rows, code_pitch(K)] with zeros in the pad"""
+    ldk = code_pitch(K)
+    if codes.dtype != torch.int8 or codes.numel() not in (rows * K, rows * ldk):
+        raise ValueError(f"hbfp_bmm_i8 takes int8 {what} codes [{rows}, {K}] or [{rows}, {ldk}] (got {tuple(codes.shape)}, {codes.dtype})")
+    if codes.numel() == rows * ldk:
+        return codes.contiguous()
+    return torch.nn.functional.pad(codes.reshape(rows, K), (0, ldk - K))
+
+
+def hbfp_bmm_i8(xq, wq, B, T, N, K, w_mant_bits, x_mant_bits, block_size=64, out_dtype=torch.float32):
+    """out[b] = X[b] @ W[b]^T for b < B, both operands ready-made HBFP codes: xq = (int8 codes [B*T, K], int8 exponents [B*T, K/block_size])
+    as act_codes makes them, wq = (codes [B*N, K], exponents [B*N, K/block_size]) from act_codes or codes_transposed (codes may also come
+    with the pitch code_pitch(K), zeros in the pad; K % 64 != 0 is padded here).  Block dot products are exact integer sums on the int8
+    matrix unit, fp32 across blocks in block order, one rounding to out_dtype.  Returns [B, T, N]."""
+    if not hbfp_bmm_i8_ok(B, T, N, K, w_mant_bits, x_mant_bits, block_size):
+        raise ValueError(f"hbfp_bmm_i8 needs block 16, 32 or 64, N % 16 == 0, K % block_size == 0 and mantissas of 1..7 bits "
+                         f"(got B={B}, T={T}, N={N}, K={K}, w_mant_bits={w_mant_bits}, x_mant_bits={x_mant_bits}, block_size={block_size})")
+    if out_dtype not in DTYPE_CODE:
+        raise TypeError(f"unsupported dtype {out_dtype}")
+    (xc, xe), (wc, we) = xq, wq
+    nb = K // block_size
+    if xe.numel() != B * T * nb or we.numel() != B * N * nb or xe.dtype != torch.int8 or we.dtype != torch.int8:
+        raise ValueError(f"hbfp_bmm_i8 at block {block_size} takes int8 exponents [{B * T}, {nb}] and [{B * N}, {nb}] "
+                         f"(got {tuple(xe.shape)} and {tuple(we.shape)})")
+    xc, wc = _pitched_codes(xc, B * T, K, "x"), _pitched_codes(wc, B * N, K, "w")
+    require_device_tensor_any(xc)
+    dev = xc.device
+    with torch.cuda.device(dev):
+        xe, we = xe.contiguous(), we.contiguous()
+        out = torch.empty((B, T, N), dtype=out_dtype, device=dev)
+        check(load_library().bfpq_hbfp_bmm_i8(_ptr(xc), _ptr(xe), _ptr(wc), _ptr(we), _ptr(out), B, T, N, K, code_pitch(K), int(block_size),
+                                              DTYPE_CODE[out_dtype], int(w_mant_bits), int(x_mant_bits),
+                                              ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "bfpq_hbfp_bmm_i8")
+    return out
+
+
+def codes_transposed(v, block_size, mant_bits, epsilon):
+    """v [B, S, D] -> int8 codes [B, D, code_pitch(S)] + int8 exponents [B, D, S/block_size] of float_to_bfp_blocked(v.transpose(-1, -2)),
+    HBFP(mant_bits + 1) round-half-even with blocks of block_size along S, dense (bfpq_hbfp_codes_t: one read of v, no transposed copy)"""
+    require_device_tensor(v)
+    if v.dim() != 3:
+        raise ValueError(f"codes_transposed takes a [B, S, D] tensor (got {tuple(v.shape)})")
+    B, S, D = v.shape
+    if block_size not in (64,) + I8_BLOCKS or not 1 <= mant_bits <= 7 or S % block_size or D % 16:
+        raise ValueError(f"codes_transposed needs block 16, 32 or 64, mant_bits 1..7, S % block_size == 0 and D % 16 == 0 "
+                         f"(got S={S}, D={D}, block_size={block_size}, mant_bits={mant_bits})")
+    src = v.contiguous()
+    dev, ldk = src.device, code_pitch(S)
+    with torch.cuda.device(dev):
+        codes = torch.empty((B, D, ldk), dtype=torch.int8, device=dev)
+        exps = torch.empty((B, D, S // block_size), dtype=torch.int8, device=dev)
+        check(load_library().bfpq_hbfp_codes_t(_ptr(src), _ptr(codes), _ptr(exps), B, S, D, ldk, DTYPE_CODE[src.dtype], int(block_size),
+                                               int(mant_bits), float(epsilon), _ptr(exp_window_dev(src.dtype, dev)), _stream(src)),
+              "bfpq_hbfp_codes_t")
+    return codes, exps
 
 # ---- 2:4-compressed packed weights on the sparse int8 matrix unit (bfpq_sp24.hip) -----------------
 SP24_MAX_TOKENS = 64      # BFPQ_SP24_MAX_TOKENS: hbfp_linear_sp24 takes 1..64 tokens
