@@ -206,9 +206,7 @@ def _unstructured_sparsity(t, device, sparsity_frac=0):
     native.require_device_tensor(t)
     if t.numel() == 0:
         return t.clone()
-    k = int(t.numel() * sparsity_frac)
-    if k > t.numel():
-        raise RuntimeError("selected index k out of range")      # what torch.topk raises in the reference
+    k = native.prune_count(t, sparsity_frac)
     ws = _workspace(t.device)
     native.select_threshold(t, k, ws)
     return native.threshold_apply(t, ws).view(t.shape)
@@ -291,9 +289,7 @@ def float_to_bfp_blocked(t, mant_bits, epsilon, rounding_mode, device, block_siz
         native.require_device_tensor(t)
         if t.numel() == 0:
             return t.clone()
-        k = int(t.numel() * sparsity_frac)
-        if k > t.numel():
-            raise RuntimeError("selected index k out of range")
+        k = native.prune_count(t, sparsity_frac)
         mb = weight_mant_bits if sgd_update else mant_bits
         ws = _workspace(t.device)
         if rounding_mode == rounding_modes.DETERM:
@@ -343,9 +339,7 @@ def _list_quant(a, sparsity):
 
 def _prune_list(tensors, a):
     """the PruneQuantizeList of a 'prune' configuration for tensors of one device and dtype"""
-    ks = [int(t.numel() * a['sparsity_frac']) for t in tensors]
-    if any(k > t.numel() for k, t in zip(ks, tensors)):
-        raise RuntimeError("selected index k out of range")          # what torch.topk raises in the reference
+    ks = [native.prune_count(t, a['sparsity_frac']) for t in tensors]
     return native.PruneQuantizeList(tensors, ks, a['block_size'], a['mant_bits'], a['epsilon'])
 
 
@@ -526,9 +520,7 @@ class PackedBFP:
         if code_bits is None:
             code_bits = code_bits_for(mant_bits)
         assert sparsity_frac > 0
-        k = int(t.numel() * sparsity_frac)
-        if k > t.numel():
-            raise RuntimeError("selected index k out of range")
+        k = native.prune_count(t, sparsity_frac)
         ws = _workspace(t.device)
         native.select_threshold(t, k, ws)
         _, codes, exps = native.quantize_threshold(t, ws, block_size, mant_bits, epsilon, want_deq=False, code_bits=code_bits, want_exp=True)
@@ -992,6 +984,25 @@ class _GradQuantizer(torch.autograd.Function):
         return float_to_bfp_blocked(grad_out, **ctx.bfp_args, identifier='grad'), None
 
 
+def _pruning_ok(a, w_quantize_first):
+    """the operand pruning the matrix-unit routes take: in_sparsity structured with 0 < N <= M or unstructured with 0 < sparsity_frac <= 1;
+    w_sparsity N:M with M in (2, 4, 8) or unstructured -- prune-first only, unless w_quantize_first (the routes that make the weight's
+    codes per call; the cached route's fused prune + quantize launch cannot prune after quantizing)"""
+    if a['in_sparsity'] == True:  # noqa: E712
+        if a['sparsity_mode'] == 'structured':
+            if not (0 < a['N'] <= a['M']):
+                return False
+        elif a['sparsity_mode'] != 'unstructured' or not (0 < a['sparsity_frac'] <= 1):
+            return False
+    if a['w_sparsity'] == True:  # noqa: E712
+        if a['sparsity_mode'] == 'unstructured':
+            if not (0 < a['sparsity_frac'] <= 1) or not (w_quantize_first or a['first'] == 's'):
+                return False
+        elif a['sparsity_mode'] != 'structured' or not (0 < a['N'] <= a['M']) or a['M'] not in (2, 4, 8):
+            return False
+    return True
+
+
 def _cached_route(x, w, a, cache):
     """linear_route of the cached Linear forward; anything but 'int8' or 'mx8' means the fake-quantize path.  matrix_unit=True: the
     block-scaled matrix instruction on the weight's e4m3 + E8M0 image (<= 4 mantissa bits, exact in e4m3; K % 256 == 0; from
@@ -1004,18 +1015,10 @@ def _cached_route(x, w, a, cache):
             or a['rounding_mode'] != rounding_modes.DETERM or w.dim() != 2 or x.device.type != 'cuda'
             or torch.compiler.is_compiling() or not cache.usable(w, a)):
         return 'fake'
-    if a['in_sparsity'] == True:  # noqa: E712
-        if a['sparsity_mode'] == 'structured':
-            if not (0 < a['N'] <= a['M']):
-                return 'fake'
-        elif a['sparsity_mode'] != 'unstructured' or not (0 < a['sparsity_frac'] <= 1):
-            return 'fake'
-    if a['w_sparsity'] == True:  # noqa: E712
-        if a['sparsity_mode'] == 'unstructured':
-            if a['first'] != 's' or not (0 < a['sparsity_frac'] <= 1) or w.shape[-1] % 64:       # the fused prune + quantize launch writes the codes
-                return 'fake'
-        elif a['sparsity_mode'] != 'structured' or not (0 < a['N'] <= a['M']) or a['M'] not in (2, 4, 8):
-            return 'fake'
+    if not _pruning_ok(a, w_quantize_first=False):
+        return 'fake'
+    if a['w_sparsity'] == True and a['sparsity_mode'] == 'unstructured' and w.shape[-1] % 64:  # noqa: E712  (the fused prune + quantize launch writes the codes)
+        return 'fake'
     K, m = x.shape[-1], a['mant_bits']
     T = x.numel() // K if K else 0
     if int8:
@@ -1069,19 +1072,7 @@ def _stoc_eligible(x, w, bias, a):
             or (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())   # (the exponent check reads a flag back)
             or (bias is not None and bias.dtype != torch.float32)):
         return False
-    if a['in_sparsity'] == True:  # noqa: E712
-        if a['sparsity_mode'] == 'structured':
-            if not (0 < a['N'] <= a['M']):
-                return False
-        elif a['sparsity_mode'] != 'unstructured' or not (0 < a['sparsity_frac'] <= 1):
-            return False
-    if a['w_sparsity'] == True:  # noqa: E712
-        if a['sparsity_mode'] == 'unstructured':
-            if not (0 < a['sparsity_frac'] <= 1):
-                return False
-        elif a['sparsity_mode'] != 'structured' or not (0 < a['N'] <= a['M']) or a['M'] not in (2, 4, 8):
-            return False
-    return True
+    return _pruning_ok(a, w_quantize_first=True)
 
 
 def _weight_sparsity(a):
@@ -1206,29 +1197,12 @@ def matmul_i8_min(dtype, block_size, N, K):
     return MATMUL_I8_MIN.get((dtype,) + key, MATMUL_I8_MIN.get((torch.bfloat16,) + key))
 
 
-def _matmul_pruning_ok(a):
-    """pruning of either matmul operand as _stoc_eligible accepts it: in_sparsity on x, w_sparsity on w"""
-    if a['in_sparsity'] == True:  # noqa: E712
-        if a['sparsity_mode'] == 'structured':
-            if not (0 < a['N'] <= a['M']):
-                return False
-        elif a['sparsity_mode'] != 'unstructured' or not (0 < a['sparsity_frac'] <= 1):
-            return False
-    if a['w_sparsity'] == True:  # noqa: E712
-        if a['sparsity_mode'] == 'unstructured':
-            if not (0 < a['sparsity_frac'] <= 1):
-                return False
-        elif a['sparsity_mode'] != 'structured' or not (0 < a['N'] <= a['M']) or a['M'] not in (2, 4, 8):
-            return False
-    return True
-
-
 def matmul_route(x, w, a, matrix_unit):
     """the contraction of F_matmul_bfp(matrix_unit=...)(x, w) under the bfp_args a: 'int8' (native.hbfp_bmm_i8 on codes of both operands)
     or 'fake' (MxM_pre_processing + torch.matmul).  'int8' needs all of: matrix_unit 'int8'; no gradient recording; 'bfp' in both formats,
     round-half-even, block 16, 32 or 64, 1..7 mantissa bits; both operands of one dtype (fp32, bf16, fp16) on one ROCm device; not
     compiling; equal leading batch dimensions (broadcasting: 'fake'); x contiguous along its last dimension; K % block == 0,
-    N % 16 == 0 and the C predicate; pruning as _stoc_eligible takes it; T >= the problem's MATMUL_I8_MIN entry (matmul_i8_min).  Host
+    N % 16 == 0 and the C predicate; pruning as _pruning_ok takes it with quantize-first weights; T >= the problem's MATMUL_I8_MIN entry (matmul_i8_min).  Host
     logic only."""
     if matrix_unit != 'int8' or torch.is_grad_enabled():
         return 'fake'
@@ -1242,7 +1216,7 @@ def matmul_route(x, w, a, matrix_unit):
         return 'fake'
     T, K, N = x.shape[-2], x.shape[-1], w.shape[-1]
     B = x.numel() // (T * K) if T * K else 0
-    if B < 1 or K % a['block_size'] or N % 16 or not _matmul_pruning_ok(a):
+    if B < 1 or K % a['block_size'] or N % 16 or not _pruning_ok(a, w_quantize_first=True):
         return 'fake'
     lim = matmul_i8_min(x.dtype, a['block_size'], N, K)
     if lim is None or T < lim or not native.hbfp_bmm_i8_ok(B, T, N, K, a['mant_bits'], a['mant_bits'], a['block_size']):

@@ -3,11 +3,9 @@
 // fake-quantised operands of F_matmul_bfp (reference bfp_ops.py:240-245 through :187-190), the attention matmuls of the reference's
 // GPT-2 (modeling_gpt2.py:207, 243, 297).  Neither operand is a weight: both sets of codes are made per call.
 //
-// Arithmetic: that of bfpq_i8gemm.hip.  One v_mfma_i32_16x16x64_i8 per block of 64 (v_mfma_i32_16x16x32_i8 per block of 32 or 16, block
-// 16 with zeros in the A operand of lanes 32..63), an exact integer block sum (|sum| <= 64 * 127^2 < 2^20), one rescale by
-// 2^(ex - xm) * 2^(ew - wm), fp32 accumulation across blocks in block order.  The MFMA's C operand is the integer 0x4B400000 (the bits
-// of 1.5 * 2^23), so its int32 result read as a float is 1.5 * 2^23 + sum: u = fma(f, sx, -1.5 * 2^23 * sx) is sum * sx exactly, then
-// acc = fma(u, sw, acc); both are packed fp32 ops on two outputs.  A block exponent of -128 (the NaN block marker) makes the scale NaN.
+// Arithmetic: the int8 block product of bfpq_i8mma.h (exactness argument, NaN marker and lane map are there).  One
+// v_mfma_i32_16x16x64_i8 per block of 64 (v_mfma_i32_16x16x32_i8 per block of 32 or 16), an exact integer block sum, one rescale by
+// 2^(ex - xm) * 2^(ew - wm), fp32 accumulation across blocks in block order.
 //
 // Layout: code rows have a pitch ldk (a multiple of 64, >= K) with zero codes in the pad, so K is walked in 64-byte chunks whatever
 // K % 64 is (K = 32 and K = 64 take the same path; blocks past K / BLK are skipped, their exponents do not exist).  Exponent rows are
@@ -17,9 +15,8 @@
 //   P V:   N = 64 or 128 is one tile row, x = P's codes are read exactly once, w = V's codes ([N, ldk], 64-256 KB) stay in L2 / L1.
 // A wave owns 16 TM output features (w rows, the MFMA's A) x 16 TN tokens (x rows, B) and reads its operands straight from global
 // memory, 16 bytes per lane and row (no register double buffer: it spilled; 2-4 waves per SIMD cover the latency).  The four waves of a workgroup are neighbours along T (they share
-// the w rows, so those hit in L1).  Batch is gridDim.y (a grid-stride loop past 65535).  Lane map as in bfpq_i8gemm.hip: A lane l = row
-// l & 15, bytes 16 (l >> 4) .. +15 of the block; D lane l holds rows 4 (l >> 4) + j of column l & 15, i.e. four consecutive output
-// features of one token -- one 8- or 16-byte store.
+// the w rows, so those hit in L1).  Batch is gridDim.y (a grid-stride loop past 65535).  A lane ends with four consecutive
+// output features of one token -- one 8- or 16-byte store.
 //
 // k_codes_t: the quantizer for an operand whose blocks run along its second-to-last dimension (V in P V): reads v[B, S, D] once and
 // writes int8 codes [B, D, ldk] + int8 exponents [B, D, S / BLK], the operand float_to_bfp_blocked(v.transpose(-1, -2)) as codes
@@ -32,52 +29,13 @@
 #include "bfpq.h"
 #include "bfpq_common.h"
 #include "bfpq_device.h"
+#include "bfpq_i8mma.h"
 
 using namespace bfpq;
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-constexpr int MAGIC_I = 0x4B400000;                       // bits of 1.5 * 2^23
-constexpr float MAGIC_F = 12582912.0f;
 constexpr int kWaves = 4;                                 // waves of a workgroup, neighbours along T
-
-__device__ __forceinline__ float pow2_scale(int e, int m)    // 2^(e - m); NaN for the NaN block marker
-{
-    return e == -128 ? __builtin_nanf("") : ldexpf(1.0f, e - m);
-}
-
-// What depends on the block (as I8Blk of bfpq_i8gemm.hip): the lane's bytes inside a block, whether its A operand is live, the
-// instruction.  Blocks 32 / 16 use v_mfma_i32_16x16x32_i8 (A lane l = row l & 15, bytes 8 (l >> 4) .. +7); block 16 puts its 16 bytes in
-// lanes l >> 4 = 0, 1 and zeros in the A operand of the others.
-template <int BLK> struct BmmBlk {
-    static_assert(BLK == 16 || BLK == 32, "blocks of 16, 32 or 64");
-    using op_t = long;
-    __device__ __forceinline__ static int lane(int q) { return 8 * (BLK == 32 ? q : (q & 1)); }
-    __device__ __forceinline__ static bool a_live(int q) { return BLK == 32 || q < 2; }
-    __device__ __forceinline__ static v4i mfma(long a, long b, v4i c) { return __builtin_amdgcn_mfma_i32_16x16x32_i8(a, b, c, 0, 0, 0); }
-};
-template <> struct BmmBlk<64> {
-    using op_t = v4i;
-    __device__ __forceinline__ static int lane(int q) { return q * 16; }
-    __device__ __forceinline__ static bool a_live(int) { return true; }
-    __device__ __forceinline__ static v4i mfma(v4i a, v4i b, v4i c) { return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0); }
-};
-
-// exponents of blocks 4 g .. 4 g + 3 of one row as a dword (byte i = block 4 g + i; blocks past the row's end read as 0 and are never
-// used).  off = row * nb + 4 g, left = nb - 4 g; dw: the rows are 4-byte aligned (nb % 4 == 0 and an aligned base)
-__device__ __forceinline__ uint32_t exp4(const int8_t* __restrict__ e, uint32_t off, int left, bool dw)
-{
-    if (dw) return *reinterpret_cast<const uint32_t*>(e + off);
-    uint32_t v = 0;
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-        if (i < left) v |= (uint32_t)(uint8_t)e[off + i] << (8 * i);
-    return v;
-}
 
 // (the second launch bound is waves per SIMD: without it the compiler spends the whole register file on hoisted loads at occupancy 1)
 template <int BLK, int OUT_DT, int TM, int TN>
@@ -85,7 +43,7 @@ __global__ void __launch_bounds__(64 * kWaves, TN == 4 ? 2 : 3) k_bmm_i8(const i
                                                         const int8_t* __restrict__ we, void* __restrict__ out, int B, int T, int N, int K, int ldk,
                                                         int tiles_t, int xm, int wm)
 {
-    using Blk = BmmBlk<BLK>;
+    using Blk = I8Blk<BLK>;
     using op_t = typename Blk::op_t;
     constexpr int NBS = 64 / BLK;                                // blocks per 64-byte chunk
     constexpr int CPG = 4 / NBS > 0 ? 4 / NBS : 1;               // chunks per exponent dword (4 blocks)
@@ -161,27 +119,17 @@ __global__ void __launch_bounds__(64 * kWaves, TN == 4 ? 2 : 3) k_bmm_i8(const i
             for (int s = 0; s < NBS; s++) {
                 const int blk = c * NBS + s;
                 if (blk < nb) {                                  // (K % 64 != 0: the tail of the last chunk is pad)
-                    const int sh = 8 * (blk & 3);
+                    const int sh = 8 * (blk & 3);                // its byte of the exponent dwords
                     v2f sx[TN], nm[TN];
 #pragma unroll
-                    for (int jt = 0; jt < TN; jt++) {
-                        const float sc = pow2_scale((int)(int8_t)(exd[jt] >> sh), xm);
-                        sx[jt] = v2f{sc, sc};
-                        nm[jt] = v2f{-MAGIC_F * sc, -MAGIC_F * sc};
-                    }
+                    for (int jt = 0; jt < TN; jt++) token_scale(exp_byte(exd[jt], sh), xm, sx[jt], nm[jt]);
 #pragma unroll
                     for (int i = 0; i < TM; i++) {
-                        const v2f sw0 = v2f{pow2_scale((int)(int8_t)(ewd[i][0] >> sh), wm), pow2_scale((int)(int8_t)(ewd[i][1] >> sh), wm)};
-                        const v2f sw1 = v2f{pow2_scale((int)(int8_t)(ewd[i][2] >> sh), wm), pow2_scale((int)(int8_t)(ewd[i][3] >> sh), wm)};
+                        const v2f sw01 = v2f{pow2_scale(exp_byte(ewd[i][0], sh), wm), pow2_scale(exp_byte(ewd[i][1], sh), wm)};
+                        const v2f sw23 = v2f{pow2_scale(exp_byte(ewd[i][2], sh), wm), pow2_scale(exp_byte(ewd[i][3], sh), wm)};
 #pragma unroll
-                        for (int jt = 0; jt < TN; jt++) {
-                            const v4f f = __builtin_bit_cast(v4f, Blk::mfma(aF[i][s], bF[jt][s], magic));
-                            const v2f f01 = f.xy, f23 = f.zw;
-                            const v2f u01 = __builtin_elementwise_fma(f01, sx[jt], nm[jt]);
-                            const v2f u23 = __builtin_elementwise_fma(f23, sx[jt], nm[jt]);
-                            acc[i][jt][0] = __builtin_elementwise_fma(u01, sw0, acc[i][jt][0]);
-                            acc[i][jt][1] = __builtin_elementwise_fma(u23, sw1, acc[i][jt][1]);
-                        }
+                        for (int jt = 0; jt < TN; jt++)
+                            rescale(Blk::mfma(aF[i][s], bF[jt][s], magic), sx[jt], nm[jt], sw01, sw23, acc[i][jt][0], acc[i][jt][1]);
                     }
                 }
             }
@@ -197,15 +145,7 @@ __global__ void __launch_bounds__(64 * kWaves, TN == 4 ? 2 : 3) k_bmm_i8(const i
             for (int jt = 0; jt < TN; jt++) {
                 const int t = t0 + 16 * jt + r;
                 if (t >= T) continue;
-                const v2f a01 = acc[i][jt][0], a23 = acc[i][jt][1];
-                const size_t o = ob + (size_t)t * N + n;
-                if constexpr (OUT_DT == BFPQ_F32) {
-                    *reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + o) = make_float4(a01.x, a01.y, a23.x, a23.y);
-                } else {
-                    const uint32_t lo = f32_to_raw<OUT_DT>(a01.x) | (f32_to_raw<OUT_DT>(a01.y) << 16);
-                    const uint32_t hi = f32_to_raw<OUT_DT>(a23.x) | (f32_to_raw<OUT_DT>(a23.y) << 16);
-                    *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(out) + o) = make_uint2(lo, hi);
-                }
+                store4<OUT_DT>(out, ob + (size_t)t * N + n, acc[i][jt][0], acc[i][jt][1]);
             }
         }
     }
@@ -280,15 +220,6 @@ __global__ void __launch_bounds__(256) k_codes_t(const void* __restrict__ in, in
     }
 }
 
-template <class F> void with_block(int block_size, F&& f)
-{
-    if (block_size == 32) f(std::integral_constant<int, 32>{});
-    else if (block_size == 16) f(std::integral_constant<int, 16>{});
-    else f(std::integral_constant<int, 64>{});
-}
-
-bool block_ok(int block_size) { return block_size == 16 || block_size == 32 || block_size == 64; }
-
 // tokens per wave: 16 TN.  The widest tile that still gives every SIMD of the chip two waves, else the narrowest (P V at batch 1 has
 // few tiles; Q K^T has thousands)
 int bmm_tn(int64_t B, int64_t T, int64_t N)
@@ -306,14 +237,14 @@ extern "C" {
 int bfpq_hbfp_bmm_i8_ok(int64_t B, int64_t T, int64_t N, int64_t K, int64_t ldk, int block_size)
 {
     const int64_t lim = (int64_t)1 << 31;
-    return block_ok(block_size) && B >= 1 && T >= 1 && N >= 16 && N % 16 == 0 && K >= block_size && K % block_size == 0 && ldk >= K &&
+    return i8_block_ok(block_size) && B >= 1 && T >= 1 && N >= 16 && N % 16 == 0 && K >= block_size && K % block_size == 0 && ldk >= K &&
            ldk % 64 == 0 && T * ldk < lim && N * ldk < lim && T * N < lim && ((T + 15) / 16) * ((N + 63) / 64) < lim / 4;
 }
 
 int bfpq_hbfp_bmm_i8(const void* xcodes, const int8_t* xexp, const void* wcodes, const int8_t* wexp, void* out, int64_t B, int64_t T, int64_t N,
                      int64_t K, int64_t ldk, int block_size, int out_dtype, int w_mant_bits, int x_mant_bits, void* stream)
 {
-    if (!dtype_ok(out_dtype) || !block_ok(block_size) || w_mant_bits < 1 || w_mant_bits > 7 || x_mant_bits < 1 || x_mant_bits > 7 || B < 0 ||
+    if (!dtype_ok(out_dtype) || !i8_block_ok(block_size) || !i8_mant_ok(w_mant_bits) || !i8_mant_ok(x_mant_bits) || B < 0 ||
         T < 0 || N < 0)
         return BFPQ_E_ARG;
     if (B == 0 || T == 0 || N == 0) return 0;
@@ -341,7 +272,7 @@ int bfpq_hbfp_bmm_i8(const void* xcodes, const int8_t* xexp, const void* wcodes,
 int bfpq_hbfp_codes_t(const void* in, void* codes, int8_t* exps, int64_t B, int64_t S, int64_t D, int64_t ldk, int dtype, int block_size,
                       int mant_bits, double epsilon, const uint8_t* exp_win, void* stream)
 {
-    if (!dtype_ok(dtype) || !block_ok(block_size) || mant_bits < 1 || mant_bits > 7 || B < 0 || S < 0 || D < 0) return BFPQ_E_ARG;
+    if (!dtype_ok(dtype) || !i8_block_ok(block_size) || !i8_mant_ok(mant_bits) || B < 0 || S < 0 || D < 0) return BFPQ_E_ARG;
     if (B == 0 || S == 0 || D == 0) return 0;
     const int64_t lim = (int64_t)1 << 31;
     if (S % block_size != 0 || D % 16 != 0 || ldk < S || ldk % 64 != 0 || S * D >= lim || D * ldk >= lim || ldk / 64 >= lim ||

@@ -2,23 +2,10 @@
 // with x and W both int8 codes + one int8 exponent per block of 64, mantissa widths xm, wm in 1..7.  Replaces F.linear on the two
 // fake-quantised operands (bfp_ops.py:187-190).
 //
-// Arithmetic: inside a block the dot product is an exact integer sum on the int8 matrix unit (v_mfma_i32_16x16x64_i8, K = 64 = one
-// block; |sum| <= 64 * 127^2 < 2^20), multiplied once by 2^(ex - xm) * 2^(ew - wm) and added to fp32 accumulators in block order.
-// The e4m3 route of bfpq_mxgemm.hip does not apply above 4-bit mantissas (a 7-bit code is not exact in e4m3).
-//
-// The rescale is the VALU cost the block-scaled instruction does not have.  It is kept to two packed fp32 ops per pair of outputs:
-//   - the MFMA's C operand is the integer 0x4B400000 (the bits of 1.5 * 2^23), so its int32 result, read as a float, is exactly
-//     1.5 * 2^23 + sum (floats in [2^23, 2^24) step by 1): no int -> float conversion;
-//   - u = fma(f, sx, -1.5 * 2^23 * sx) = sum * 2^(ex - xm) (exact: both products are exact, the difference is an integer < 2^20 times
-//     a power of two);
-//   - acc = fma(u, sw, acc), with sw = 2^(ew - wm).
-// Both are v_pk_fma_f32 on two outputs; one 16x16x64 MFMA (16 cycles) leaves 4 outputs per lane, i.e. 4 packed ops.  A block
-// exponent of -128 (the NaN block marker) makes its scale NaN, so the block contributes NaN.  (Scales are exact powers of two down to
-// fp32's subnormal 2^-149; products below that flush, as the fp32 product of the fake-quantised values would.)
-//
-// Lane map of v_mfma_i32_16x16x64_i8 (as in bfpq_gemm.hip): A lane l = row l & 15, bytes k = 16 (l >> 4) .. +15; B lane l = column
-// l & 15, same k; D lane l holds rows 4 (l >> 4) + j (j = 0..3) of column l & 15.  A = weight rows, B = tokens, so a lane's four results
-// are four consecutive output features of one token (one 8- or 16-byte store).
+// Arithmetic: the int8 block product of bfpq_i8mma.h -- an exact integer sum per block on the int8 matrix unit, one rescale by
+// 2^(ex - xm) * 2^(ew - wm) in two packed fp32 FMAs per pair of outputs, fp32 across blocks in block order; the exactness argument, the
+// NaN block marker and the lane map are written down there.  The e4m3 route of bfpq_mxgemm.hip does not apply above 4-bit mantissas (a
+// 7-bit code is not exact in e4m3).
 //
 // Kernels (BLK = 64, 32 or 16; blocks 16 and 32 serve bfpq_hbfp_linear_i8b* and bfpq_hbfp_linear_decode8b*):
 //   k_i8_gemm<BLK>  prefill tile: WM x WN waves, each TM x TN instruction tiles; K staged global -> LDS by 16-byte LDS-DMA, two LDS
@@ -28,53 +15,23 @@
 //                 K goes to fp32 slab p (plain stores) and k_slab_reduce (bfpq_common.h) adds the slabs in part order.
 //   k_i8_decode<BLK>  few tokens: a wave owns 16 output features x up to 16 tokens x a slice of K (any K % 64 == 0), slabs reduced as above.
 //   k_codes4_to_i8  4-bit two's-complement nibbles (low first) -> int8 codes.
-// Blocks 16 and 32 take one v_mfma_i32_16x16x32_i8 per block (I8Blk below), 8-byte operands read from the same LDS stages.
+// Blocks 16 and 32 take one v_mfma_i32_16x16x32_i8 per block (I8Blk of bfpq_i8mma.h), 8-byte operands read from the same LDS stages.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "bfpq.h"
 #include "bfpq_common.h"
+#include "bfpq_i8mma.h"
 
 using namespace bfpq;
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-
 constexpr int BK = 128;                                   // bytes of K per LDS stage: two blocks
-constexpr int MAGIC_I = 0x4B400000;                       // bits of 1.5 * 2^23
-constexpr float MAGIC_F = 12582912.0f;
-
-__device__ __forceinline__ float block_scale(int e, int m)   // 2^(e - m); NaN for the NaN block marker
-{
-    return e == -128 ? __builtin_nanf("") : ldexpf(1.0f, e - m);
-}
 
 __device__ __forceinline__ v4i read16(const uint8_t* tile, int row, int c)      // logical 16-byte slot c of an LDS row
 {
     return *reinterpret_cast<const v4i*>(tile + row * BK + ((c ^ ((row >> 1) & 7)) << 4));
 }
-
-// What depends on the block: the lane's operand (its first byte of the block), whether the weight operand is live, and the instruction.
-// Block 64: 16 bytes k = 16 (l >> 4) .. +15 of v_mfma_i32_16x16x64_i8.  Blocks 32 / 16: v_mfma_i32_16x16x32_i8, whose A lane l = row
-// l & 15, bytes k = 8 (l >> 4) .. +7 (B: column l & 15, same k; D as for 16x16x64, so the epilogue and the rescale are shared).  Block 32
-// fills all 32 k; block 16 puts its 16 bytes in lanes l >> 4 = 0, 1 and zeros in the A operand of lanes 2, 3 (the only K = 16 int8 shape,
-// 32x32x16, gives 16 outputs per lane to rescale: the same VALU work per output, which is what bounds these blocks).  Only the pairing of
-// A and B bytes matters inside a block (the sum is exact), so a lane's 8 bytes are just its share of the block.
-template <int BLK> struct I8Blk {
-    static_assert(BLK == 16 || BLK == 32, "blocks of 16, 32 or 64");
-    using op_t = long;
-    __device__ __forceinline__ static int lane(int q) { return 8 * (BLK == 32 ? q : (q & 1)); }
-    __device__ __forceinline__ static bool a_live(int q) { return BLK == 32 || q < 2; }
-    __device__ __forceinline__ static v4i mfma(long a, long b, v4i c) { return __builtin_amdgcn_mfma_i32_16x16x32_i8(a, b, c, 0, 0, 0); }
-};
-template <> struct I8Blk<64> {
-    using op_t = v4i;
-    __device__ __forceinline__ static int lane(int q) { return q * 16; }
-    __device__ __forceinline__ static bool a_live(int) { return true; }
-    __device__ __forceinline__ static v4i mfma(v4i a, v4i b, v4i c) { return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0); }
-};
 
 __device__ __forceinline__ long read8(const uint8_t* tile, int row, int o)     // logical bytes o .. o + 7 (o % 8 == 0) of an LDS row
 {
@@ -155,18 +112,46 @@ struct I8Tile {
                                              (__attribute__((address_space(3))) void*)(sX + (NW * i + w) * 1024), 16, 0, 0);
     }
 
-    // acc[i][jt] += (d - 1.5 * 2^23) * sx * sw for the MFMA result d of instruction tile (i, jt): nm = -1.5 * 2^23 * sx
-    __device__ __forceinline__ void rescale(int i, int jt, v4i d, v2f sx, v2f nm, const v2f (&sw)[2])
+    // the lane's operand of block b of a staged row
+    __device__ __forceinline__ typename I8Blk<BLK>::op_t read_op(const uint8_t* tile, int row, int b) const
     {
-        const v4f f = __builtin_bit_cast(v4f, d);
-        const v2f f01 = f.xy, f23 = f.zw;
-        const v2f u01 = __builtin_elementwise_fma(f01, sx, nm);
-        const v2f u23 = __builtin_elementwise_fma(f23, sx, nm);
-        acc[i][jt][0] = __builtin_elementwise_fma(u01, sw[0], acc[i][jt][0]);
-        acc[i][jt][1] = __builtin_elementwise_fma(u23, sw[1], acc[i][jt][1]);
+        if constexpr (BLK == 64) return read16(tile, row, b * 4 + q);
+        else return read8(tile, row, b * BLK + I8Blk<BLK>::lane(q));
     }
 
-    // epilogue: lane holds features n .. n + 3 of token t
+    // block b of the stage in buffer buf: the operands from LDS, one MFMA + rescale per instruction tile.  The block's exponents are
+    // the byte at bit sh of the rows' dwords ewd[i][j][e], exd[jt][e]
+    template <int ED>
+    __device__ __forceinline__ void block(const uint8_t* lds, int buf, int b, const uint32_t (&ewd)[TM][4][ED], const uint32_t (&exd)[TN][ED],
+                                          int e, int sh, int xm, int wm)
+    {
+        using Blk = I8Blk<BLK>;
+        const uint8_t* const sW = lds + buf * STAGE;
+        const uint8_t* const sX = sW + BN * BK;
+        typename Blk::op_t aF[TM], bF[TN];
+#pragma unroll
+        for (int i = 0; i < TM; i++) {
+            aF[i] = read_op(sW, rowW + 16 * i + r, b);
+            if (!Blk::a_live(q)) aF[i] = {};
+        }
+#pragma unroll
+        for (int jt = 0; jt < TN; jt++) bF[jt] = read_op(sX, rowX + 16 * jt + r, b);
+        v2f sx[TN], nm[TN];
+#pragma unroll
+        for (int jt = 0; jt < TN; jt++) token_scale(exp_byte(exd[jt][e], sh), xm, sx[jt], nm[jt]);
+        const v4i magic = {MAGIC_I, MAGIC_I, MAGIC_I, MAGIC_I};
+#pragma unroll
+        for (int i = 0; i < TM; i++) {
+            const v2f sw01 = v2f{pow2_scale(exp_byte(ewd[i][0][e], sh), wm), pow2_scale(exp_byte(ewd[i][1][e], sh), wm)};
+            const v2f sw23 = v2f{pow2_scale(exp_byte(ewd[i][2][e], sh), wm), pow2_scale(exp_byte(ewd[i][3][e], sh), wm)};
+#pragma unroll
+            for (int jt = 0; jt < TN; jt++)
+                rescale(Blk::mfma(aF[i], bF[jt], magic), sx[jt], nm[jt], sw01, sw23, acc[i][jt][0], acc[i][jt][1]);
+        }
+    }
+
+    // epilogue: lane holds features n .. n + 3 of token t.  (The biased store is written out here, not store4 + a bias: with the bias add
+    // in or in front of a shared function hipcc (ROCm 7.2) hoists bias + n instead of out + n and the register counts change)
     template <int OUT_DT>
     __device__ __forceinline__ void store(const void* bias, void* out, int T, int N) const
     {
@@ -178,10 +163,9 @@ struct I8Tile {
             for (int jt = 0; jt < TN; jt++) {
                 const int t = t0 + rowX + 16 * jt + r;
                 if (t >= T) continue;
-                const v2f a01 = acc[i][jt][0], a23 = acc[i][jt][1];
-                if constexpr (SPLIT) {
-                    *reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + ((size_t)part * T + t) * N + n) = make_float4(a01.x, a01.y, a23.x, a23.y);
-                } else {
+                if constexpr (SPLIT) store4<BFPQ_F32>(out, ((size_t)part * T + t) * N + n, acc[i][jt][0], acc[i][jt][1]);
+                else {
+                    const v2f a01 = acc[i][jt][0], a23 = acc[i][jt][1];
                     using raw_t = typename Traits<OUT_DT>::raw_t;
                     float v[4] = {a01.x, a01.y, a23.x, a23.y};
                     if (bias) {
@@ -209,51 +193,22 @@ __global__ void __launch_bounds__(64 * WM * WN) k_i8_gemm(const int8_t* __restri
                                                           int T, int N, int K, int tiles_t, int tiles, int trips_per_part, int xm, int wm)
 {
     using Tile = I8Tile<BLK, WM, WN, TM, TN, SPLIT>;
-    constexpr int BN = Tile::BN, STAGE = Tile::STAGE;
+    constexpr int STAGE = Tile::STAGE;
     __shared__ __attribute__((aligned(16))) uint8_t lds[2 * STAGE];
     Tile t(T, N, K, tiles_t, tiles, trips_per_part);
-    const int r = t.r, q = t.q, ta = t.ta, tb = t.tb;
+    const int ta = t.ta, tb = t.tb;
     const uint32_t* const we32 = reinterpret_cast<const uint32_t*>(we);
     const uint32_t* const xe32 = reinterpret_cast<const uint32_t*>(xe);
 
     if constexpr (BLK == 64) {
-        // one block of the stage in buffer buf: byte BB (0..3) of the trip's exponent dwords
-        auto block = [&](int buf, int b, int BB, const uint32_t (&ewd)[TM][4], const uint32_t (&exd)[TN]) __attribute__((always_inline)) {
-            const uint8_t* const sW = lds + buf * STAGE;
-            const uint8_t* const sX = sW + BN * BK;
-            const int c = b * 4 + q;
-            v4i aF[TM], bF[TN];
-#pragma unroll
-            for (int i = 0; i < TM; i++) aF[i] = read16(sW, t.rowW + 16 * i + r, c);
-#pragma unroll
-            for (int jt = 0; jt < TN; jt++) bF[jt] = read16(sX, t.rowX + 16 * jt + r, c);
-            v2f sx[TN], nm[TN];
-#pragma unroll
-            for (int jt = 0; jt < TN; jt++) {
-                const float s = block_scale((int)(int8_t)(exd[jt] >> (8 * BB)), xm);
-                sx[jt] = v2f{s, s};
-                nm[jt] = v2f{-MAGIC_F * s, -MAGIC_F * s};
-            }
-            const v4i magic = {MAGIC_I, MAGIC_I, MAGIC_I, MAGIC_I};
-#pragma unroll
-            for (int i = 0; i < TM; i++) {
-                v2f sw[2];
-#pragma unroll
-                for (int h = 0; h < 2; h++)
-                    sw[h] = v2f{block_scale((int)(int8_t)(ewd[i][2 * h] >> (8 * BB)), wm), block_scale((int)(int8_t)(ewd[i][2 * h + 1] >> (8 * BB)), wm)};
-#pragma unroll
-                for (int jt = 0; jt < TN; jt++) t.rescale(i, jt, I8Blk<64>::mfma(aF[i], bF[jt], magic), sx[jt], nm[jt], sw);
-            }
-        };
-
         if (ta < tb) {
-            uint32_t ewd[TM][4], exd[TN];
+            uint32_t ewd[TM][4][1], exd[TN][1];                          // block BB of a trip: byte BB of the trip's dwords
 #pragma unroll
             for (int i = 0; i < TM; i++)
 #pragma unroll
-                for (int j = 0; j < 4; j++) ewd[i][j] = we32[t.ewo[i][j] + ta];
+                for (int j = 0; j < 4; j++) ewd[i][j][0] = we32[t.ewo[i][j] + ta];
 #pragma unroll
-            for (int jt = 0; jt < TN; jt++) exd[jt] = xe32[t.exo[jt] + ta];
+            for (int jt = 0; jt < TN; jt++) exd[jt][0] = xe32[t.exo[jt] + ta];
             t.stage(lds, wc, xc, ta << 8, 0);
             landed();
             for (int tr = ta; tr < tb; tr++) {
@@ -266,19 +221,19 @@ __global__ void __launch_bounds__(64 * WM * WN) k_i8_gemm(const int8_t* __restri
 #pragma unroll
                 for (int jt = 0; jt < TN; jt++) exn[jt] = xe32[t.exo[jt] + trn];
                 t.stage(lds, wc, xc, (tr << 8) + BK, 1);
-                block(0, 0, 0, ewd, exd);
-                block(0, 1, 1, ewd, exd);
+                t.block(lds, 0, 0, ewd, exd, 0, 0, xm, wm);
+                t.block(lds, 0, 1, ewd, exd, 0, 8, xm, wm);
                 landed();
                 t.stage(lds, wc, xc, trn << 8, 0);
-                block(1, 0, 2, ewd, exd);
-                block(1, 1, 3, ewd, exd);
+                t.block(lds, 1, 0, ewd, exd, 0, 16, xm, wm);
+                t.block(lds, 1, 1, ewd, exd, 0, 24, xm, wm);
                 landed();
 #pragma unroll
                 for (int i = 0; i < TM; i++)
 #pragma unroll
-                    for (int j = 0; j < 4; j++) ewd[i][j] = ewn[i][j];
+                    for (int j = 0; j < 4; j++) ewd[i][j][0] = ewn[i][j];
 #pragma unroll
-                for (int jt = 0; jt < TN; jt++) exd[jt] = exn[jt];
+                for (int jt = 0; jt < TN; jt++) exd[jt][0] = exn[jt];
             }
         }
     } else {
@@ -296,40 +251,10 @@ __global__ void __launch_bounds__(64 * WM * WN) k_i8_gemm(const int8_t* __restri
 #pragma unroll
                 for (int e = 0; e < ED; e++) exd[jt][e] = xe32[t.exo[jt] + s * ED + e];
         };
-        const v4i magic = {MAGIC_I, MAGIC_I, MAGIC_I, MAGIC_I};
         // every block of the stage in buffer buf
         auto blocks = [&](int buf, const uint32_t (&ewd)[TM][4][ED], const uint32_t (&exd)[TN][ED]) __attribute__((always_inline)) {
-            const uint8_t* const sW = lds + buf * STAGE;
-            const uint8_t* const sX = sW + BN * BK;
-            const int o = I8Blk<BLK>::lane(q);
 #pragma unroll
-            for (int b = 0; b < NBS; b++) {
-                const int e = b >> 2, sh = 8 * (b & 3);
-                long aF[TM], bF[TN];
-#pragma unroll
-                for (int i = 0; i < TM; i++) {
-                    aF[i] = read8(sW, t.rowW + 16 * i + r, b * BLK + o);
-                    if (!I8Blk<BLK>::a_live(q)) aF[i] = 0;
-                }
-#pragma unroll
-                for (int jt = 0; jt < TN; jt++) bF[jt] = read8(sX, t.rowX + 16 * jt + r, b * BLK + o);
-                v2f sx[TN], nm[TN];
-#pragma unroll
-                for (int jt = 0; jt < TN; jt++) {
-                    const float s = block_scale((int)(int8_t)(exd[jt][e] >> sh), xm);
-                    sx[jt] = v2f{s, s};
-                    nm[jt] = v2f{-MAGIC_F * s, -MAGIC_F * s};
-                }
-#pragma unroll
-                for (int i = 0; i < TM; i++) {
-                    v2f sw[2];
-#pragma unroll
-                    for (int h = 0; h < 2; h++)
-                        sw[h] = v2f{block_scale((int)(int8_t)(ewd[i][2 * h][e] >> sh), wm), block_scale((int)(int8_t)(ewd[i][2 * h + 1][e] >> sh), wm)};
-#pragma unroll
-                    for (int jt = 0; jt < TN; jt++) t.rescale(i, jt, I8Blk<BLK>::mfma(aF[i], bF[jt], magic), sx[jt], nm[jt], sw);
-                }
-            }
+            for (int b = 0; b < NBS; b++) t.block(lds, buf, b, ewd, exd, b >> 2, 8 * (b & 3), xm, wm);
         };
 
         if (ta < tb) {
@@ -455,14 +380,6 @@ void launch_tile(dim3 grid, hipStream_t s, const int8_t* xc, const int8_t* xe, c
                        out, T, N, K, tiles_t, tiles, tpp, xm, wm);
 }
 
-// f(std::integral_constant<int, BLK>{}) for a block of 16, 32 or 64
-template <class F> void with_block(int block_size, F&& f)
-{
-    if (block_size == 32) f(std::integral_constant<int, 32>{});
-    else if (block_size == 16) f(std::integral_constant<int, 16>{});
-    else f(std::integral_constant<int, 64>{});
-}
-
 }  // namespace
 
 extern "C" __attribute__((visibility("hidden"))) int bfpq_g_i8_variant = -1;    // -1 = choose; 0..2 force (bfpq_tune, BFPQ_TUNE_I8_VARIANT)
@@ -470,7 +387,7 @@ extern "C" __attribute__((visibility("hidden"))) int bfpq_g_i8_parts = 0;       
 
 static bool i8_args_ok(int out_dtype, int w_mant_bits, int x_mant_bits)
 {
-    return dtype_ok(out_dtype) && w_mant_bits >= 1 && w_mant_bits <= 7 && x_mant_bits >= 1 && x_mant_bits <= 7;
+    return dtype_ok(out_dtype) && i8_mant_ok(w_mant_bits) && i8_mant_ok(x_mant_bits);
 }
 
 static bool small_block(int block_size) { return block_size == 16 || block_size == 32; }      // the blocks of the `b` entries

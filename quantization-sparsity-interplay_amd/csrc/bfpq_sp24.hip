@@ -10,7 +10,7 @@
 //   B (dense, 64 K x 16 columns): lane l = column l & 15, bytes k = 16 (l >> 4) .. +15, as v_mfma_i32_16x16x64_i8.
 //   D: lane l holds rows 4 (l >> 4) + j (j = 0..3) of column l & 15, as v_mfma_i32_16x16x64_i8.
 // K = 64 is one HBFP block, so every block's dot product is one instruction and an exact integer sum (|sum| <= 32 * 127^2 < 2^20);
-// the rescale is that of bfpq_i8gemm.hip (C operand 0x4B400000, two packed fp32 FMAs per pair of outputs, exponent -128 -> NaN).
+// the rescale is that of bfpq_i8mma.h (C operand 0x4B400000, two packed fp32 FMAs per pair of outputs, exponent -128 -> NaN).
 //
 // Layout (tiles of 16 rows; lane l = r + 16 q of tile rt holds row 16 rt + r, K 64 b + 16 q .. +15 of block b):
 //   per lane and block U bytes of values (4-bit codes: 8 nibbles, value j in nibble j, low first, U = 4; 8-bit codes: 8 bytes,
@@ -31,18 +31,12 @@
 #include <stdint.h>
 #include "bfpq.h"
 #include "bfpq_common.h"
+#include "bfpq_i8mma.h"
 
 using namespace bfpq;
 
 namespace {
 
-typedef int v2i __attribute__((ext_vector_type(2)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-constexpr int MAGIC_I = 0x4B400000;                       // bits of 1.5 * 2^23
-constexpr float MAGIC_F = 12582912.0f;
 constexpr int IDX_CH = 8;                                 // blocks per 16-byte chunk of positions (2 bytes per lane and block)
 constexpr int GROUP = 8;                                  // blocks per step of the decode kernel (one chunk of positions)
 
@@ -56,11 +50,6 @@ __device__ __forceinline__ size_t sp24_off(int rt, int nb, int b, int l, int CH,
 {
     const int c0 = b - b % CH, nbc = nb - c0 < CH ? nb - c0 : CH;
     return ((size_t)rt * nb + c0) * (size_t)(U * 64) + (size_t)l * (nbc * U) + (size_t)(b - c0) * U;
-}
-
-__device__ __forceinline__ float block_scale(int e, int m)   // 2^(e - m); NaN for the NaN block marker
-{
-    return e == -128 ? __builtin_nanf("") : ldexpf(1.0f, e - m);
 }
 
 // one group of 4 codes (c[0..3]) -> the two kept positions p0 < p1 (bfpq_int.hip's compact_group rule); *bad when more than 2 are non-zero
@@ -186,25 +175,17 @@ __device__ __forceinline__ v2i nibbles_to_i8(uint32_t w)
     return v2i{(int)__builtin_amdgcn_perm(hi, lo, 0x05010400u), (int)__builtin_amdgcn_perm(hi, lo, 0x07030602u)};
 }
 
-// 8 exponent bytes p[0..7] (two dword loads where the row allows it: EXP4 <=> nb % 4 == 0 and p 4-aligned)
-__device__ __forceinline__ uint2 exps8(const int8_t* p, bool dwords, int cnt)
+// 8 exponent bytes p[0..7] of a row as two exp4 dwords (cnt < 8: the bytes from cnt on are not read and give 0)
+__device__ __forceinline__ void exps8(const int8_t* p, bool dwords, int cnt, uint32_t (&d)[2])
 {
     if (dwords) {
-        const uint32_t a = *reinterpret_cast<const uint32_t*>(p);
-        const uint32_t b = cnt > 4 ? *reinterpret_cast<const uint32_t*>(p + 4) : 0u;
-        return make_uint2(a, b);
+        d[0] = exp4(p, 0, 4, true);
+        d[1] = cnt > 4 ? exp4(p, 4, 4, true) : 0u;
+    } else {
+        d[0] = exp4(p, 0, cnt, false);
+        d[1] = exp4(p, 4, cnt - 4, false);
     }
-    uint32_t a = 0, b = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++)
-        if (i < cnt) {
-            const uint32_t v = (uint8_t)p[i];
-            if (i < 4) a |= v << (8 * i); else b |= v << (8 * (i - 4));
-        }
-    return make_uint2(a, b);
 }
-
-__device__ __forceinline__ int exp_byte(uint2 e, int i) { return (int)(int8_t)(((i < 4 ? e.x : e.y) >> (8 * (i & 3))) & 255u); }
 
 // few tokens: wave = 16 features x 16 tokens (token group blockIdx.y) x `gps` groups of 8 blocks; fp32 slab [slice][T][N]
 template <int CB>
@@ -259,10 +240,10 @@ __global__ void __launch_bounds__(256) k_sp24_decode(const uint8_t* __restrict__
                 else { const uint2 v = *reinterpret_cast<const uint2*>(vp); vw[i][0] = v.x; vw[i][1] = v.y; }
             }
         }
-        const uint2 exx = exps8(xer + g0, dwords, cnt);
-        uint2 ew[4];
+        uint32_t exx[2], ew[4][2];
+        exps8(xer + g0, dwords, cnt, exx);
 #pragma unroll
-        for (int j = 0; j < 4; j++) ew[j] = exps8(wer + (size_t)j * nb + g0, dwords, cnt);
+        for (int j = 0; j < 4; j++) exps8(wer + (size_t)j * nb + g0, dwords, cnt, ew[j]);
 #pragma unroll
         for (int i = 0; i < GROUP; i++) {
             if (i >= cnt) break;
@@ -274,19 +255,15 @@ __global__ void __launch_bounds__(256) k_sp24_decode(const uint8_t* __restrict__
             asm volatile("" : "+v"(m0), "+v"(m1), "+v"(m2), "+v"(m3));
             const v4i c = {m0, m1, m2, m3};
             const v4i d = __builtin_amdgcn_smfmac_i32_16x16x64_i8(a, bx, c, (int)ixs[i], 0, 0);
-            const float s = block_scale(exp_byte(exx, i), xm);
-            const v2f sx = {s, s}, nm = {-MAGIC_F * s, -MAGIC_F * s};
-            const v2f sw01 = {block_scale(exp_byte(ew[0], i), wm), block_scale(exp_byte(ew[1], i), wm)};
-            const v2f sw23 = {block_scale(exp_byte(ew[2], i), wm), block_scale(exp_byte(ew[3], i), wm)};
-            const v4f f = __builtin_bit_cast(v4f, d);
-            const v2f u01 = __builtin_elementwise_fma(f.xy, sx, nm);
-            const v2f u23 = __builtin_elementwise_fma(f.zw, sx, nm);
-            acc01 = __builtin_elementwise_fma(u01, sw01, acc01);
-            acc23 = __builtin_elementwise_fma(u23, sw23, acc23);
+            const int e = i >> 2, sh = 8 * (i & 3);
+            v2f sx, nm;
+            token_scale(exp_byte(exx[e], sh), xm, sx, nm);
+            const v2f sw01 = {pow2_scale(exp_byte(ew[0][e], sh), wm), pow2_scale(exp_byte(ew[1][e], sh), wm)};
+            const v2f sw23 = {pow2_scale(exp_byte(ew[2][e], sh), wm), pow2_scale(exp_byte(ew[3][e], sh), wm)};
+            rescale(d, sx, nm, sw01, sw23, acc01, acc23);
         }
     }
-    if (tok < T)
-        *reinterpret_cast<float4*>(slabs + ((size_t)slice * T + tok) * N + n0 + 4 * q) = make_float4(acc01.x, acc01.y, acc23.x, acc23.y);
+    if (tok < T) store4<BFPQ_F32>(slabs, ((size_t)slice * T + tok) * N + n0 + 4 * q, acc01, acc23);
 }
 
 bool sp24_shape_ok(int64_t N, int64_t K) { return N >= 16 && N % 16 == 0 && K >= 64 && K % 64 == 0 && N * K < ((int64_t)1 << 32); }
@@ -355,8 +332,8 @@ int bfpq_hbfp_linear_sp24(const void* xcodes, const int8_t* xexp, const void* wv
                           void* out, float* slabs, int64_t T, int64_t N, int64_t K, int code_bits, int out_dtype, int w_mant_bits,
                           int x_mant_bits, void* stream)
 {
-    if (!dtype_ok(out_dtype) || (code_bits != 4 && code_bits != 8) || !codes_fit(code_bits, w_mant_bits) || w_mant_bits < 1 ||
-        w_mant_bits > 7 || x_mant_bits < 1 || x_mant_bits > 7 || T < 1 || N < 1 || K < 1)
+    if (!dtype_ok(out_dtype) || (code_bits != 4 && code_bits != 8) || !codes_fit(code_bits, w_mant_bits) || !i8_mant_ok(w_mant_bits) ||
+        !i8_mant_ok(x_mant_bits) || T < 1 || N < 1 || K < 1)
         return BFPQ_E_ARG;
     if (bfpq_hbfp_linear_sp24_ws(T, N, K) < 0) return BFPQ_E_UNSUPPORTED;
     if (!xcodes || !xexp || !wvals || !widx || !wexp || !out || !slabs) return BFPQ_E_ARG;

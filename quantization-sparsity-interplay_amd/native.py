@@ -857,6 +857,19 @@ def mfma_tiles(wcodes, wexps):
     return t, e
 
 
+def _linear_operands(x, T, N, K, x_mant_bits, epsilon, act, xq, bias, out_dtype, block_size=64):
+    """what the linears on int8 activation codes share, on x's device: the activation operand (xq as given, else act_codes of x pruned by
+    `act`), the [T, N] output and the bias in out_dtype (None stays None)"""
+    if xq is not None:
+        xc, xe = xq[0].contiguous(), xq[1].contiguous()
+    else:
+        xc, xe = act_codes(x.reshape(T, K), x_mant_bits, epsilon, act, block_size=block_size)
+    out = torch.empty((T, N), dtype=out_dtype, device=x.device)
+    if bias is not None:
+        bias = bias.to(out_dtype).contiguous()
+    return xc, xe, out, bias
+
+
 def hbfp_linear_decode_tiled(x, wtiles, wexpt, N, w_mant_bits, x_mant_bits=7, epsilon=1e-8, out_dtype=None, xq=None):
     """hbfp_linear_decode on the MFMA-tiled weight (see mfma_tiles).  xq: the activation operand made beforehand (act_codes: int8
     codes [T, K], int8 exponents [T, K/64]), e.g. pruned over more tokens than this call takes; x then only gives shape and dtype."""
@@ -869,14 +882,8 @@ def hbfp_linear_decode_tiled(x, wtiles, wexpt, N, w_mant_bits, x_mant_bits=7, ep
     dev = x.device
     out_dtype = out_dtype or x.dtype
     with torch.cuda.device(dev):
-        if xq is not None:
-            xc16, xe16 = xq[0].contiguous(), xq[1].contiguous()
-        else:
-            xc16 = torch.empty((T, K), dtype=torch.int8, device=dev)          # (token columns past T re-read row T-1: no padding rows)
-            xe16 = torch.empty((T, K // 64), dtype=torch.int8, device=dev)
-            quantize_nm(x.reshape(T, K), 64, x_mant_bits, epsilon, want_deq=False, code_bits=8, want_exp=True,
-                        codes_out=xc16, exps_out=xe16)
-        out = torch.empty((T, N), dtype=out_dtype, device=dev)
+        # (token columns past T re-read row T-1: no padding rows)
+        xc16, xe16, out, _ = _linear_operands(x, T, N, K, x_mant_bits, epsilon, None, xq, None, out_dtype)
         check(L.bfpq_hbfp_linear_decode_tiled(_ptr(wtiles), _ptr(wexpt), _ptr(xc16), _ptr(xe16), _ptr(out), T, N, K,
                                               DTYPE_CODE[out_dtype], int(w_mant_bits), int(x_mant_bits), _stream(x)),
               "bfpq_hbfp_linear_decode_tiled")
@@ -969,7 +976,8 @@ def _act_workspace(device):
     return _workspace(device)
 
 
-def _prune_count(t, frac):
+def prune_count(t, frac):
+    """the number of elements unstructured pruning zeroes in t: int(numel * frac), as the reference computes it (bfp_ops.py:66)"""
     k = int(t.numel() * frac)
     if k > t.numel():
         raise RuntimeError("selected index k out of range")      # what torch.topk raises in the reference
@@ -987,7 +995,7 @@ def act_codes(x, mant_bits, epsilon, act, codes_out=None, exps_out=None, block_s
         _, c, e = quantize_nm(x, block_size, mant_bits, epsilon, N=N, M=M, sparsify_first=(act is None or act.first == 's'), want_deq=False,
                               code_bits=8, want_exp=True, codes_out=codes_out, exps_out=exps_out)
         return c, e
-    k = _prune_count(x, act.frac)
+    k = prune_count(x, act.frac)
     ws = _act_workspace(dev)
     if act.first == 's':
         select_threshold(x, k, ws)
@@ -1022,7 +1030,7 @@ def stoc_codes(t, block_size, mant_bits, epsilon, seed, act=None):
         _, c, e = quantize_nm(t, block_size, mant_bits, epsilon, N=N, M=M, sparsify_first=(act is None or act.first == 's'),
                               want_deq=M > 0 and not is_fused(t, block_size, N, M), code_bits=8, want_exp=True, stoch_seed=seed)
         return c, e
-    k = _prune_count(t, act.frac)
+    k = prune_count(t, act.frac)
     ws = _act_workspace(t.device)
     if act.first == 's':
         select_threshold(t, k, ws)
@@ -1068,7 +1076,7 @@ def quantize_mx8(x, mant_bits, epsilon=1e-8, act=None):
                 rc = L.bfpq_quantize_mx8_nm(_ptr(x), _ptr(x8), _ptr(xs), T, K, DTYPE_CODE[x.dtype], int(mant_bits), float(epsilon),
                                             int(act.N), int(act.M), 1 if act.first == 's' else 0, win, _ptr(lut), _stream(x))
             else:
-                k = _prune_count(x, act.frac)
+                k = prune_count(x, act.frac)
                 ws = _act_workspace(dev)
                 select_threshold(x, k, ws)
                 rc = L.bfpq_quantize_threshold_mx8(_ptr(x), _ptr(x8), _ptr(xs), T, K, DTYPE_CODE[x.dtype], int(mant_bits), float(epsilon),
@@ -1237,16 +1245,9 @@ def hbfp_linear_i8(x, wcodes8, wexps, w_mant_bits, x_mant_bits, epsilon=1e-8, bi
     dev = x.device
     out_dtype = out_dtype or x.dtype
     with torch.cuda.device(dev):
-        if xq is not None:
-            xc, xe = xq[0].contiguous(), xq[1].contiguous()
-        else:
-            xc, xe = act_codes(x.reshape(T, K), x_mant_bits, epsilon, act, block_size=block_size)
+        xc, xe, out, bias = _linear_operands(x, T, N, K, x_mant_bits, epsilon, act, xq, bias, out_dtype, block_size)
         wc, we = wcodes8.contiguous(), wexps.contiguous()
-        out = torch.empty((T, N), dtype=out_dtype, device=dev)
-        if bias is not None:
-            bias = bias.to(out_dtype).contiguous()
-        bp = _ptr(bias) if bias is not None else None
-        ops = (_ptr(xc), _ptr(xe), _ptr(wc), _ptr(we), bp, _ptr(out))
+        ops = (_ptr(xc), _ptr(xe), _ptr(wc), _ptr(we), _ptr(bias), _ptr(out))
         # the C entry family of the block: block 64's take no block argument, the `b` entries take 16 or 32
         blk, sfx = ((), '') if block_size == 64 else ((int(block_size),), 'b')
         tail = blk + (DTYPE_CODE[out_dtype], int(w_mant_bits), int(x_mant_bits), _stream(x))
@@ -1416,16 +1417,10 @@ def hbfp_linear_sp24(x, wvals, widx, wexps, N, code_bits, w_mant_bits, x_mant_bi
     dev = x.device
     out_dtype = out_dtype or x.dtype
     with torch.cuda.device(dev):
-        if xq is not None:
-            xc, xe = xq[0].contiguous(), xq[1].contiguous()
-        else:
-            xc, xe = act_codes(x.reshape(T, K), x_mant_bits, epsilon, act)
-        out = torch.empty((T, N), dtype=out_dtype, device=dev)
-        if bias is not None:
-            bias = bias.to(out_dtype).contiguous()
+        xc, xe, out, bias = _linear_operands(x, T, N, K, x_mant_bits, epsilon, act, xq, bias, out_dtype)
         slabs = torch.empty(int(L.bfpq_hbfp_linear_sp24_ws(T, N, K)), dtype=torch.float32, device=dev)
         check(L.bfpq_hbfp_linear_sp24(_ptr(xc), _ptr(xe), _ptr(wvals.contiguous()), _ptr(widx.contiguous()), _ptr(wexps.contiguous()),
-                                      _ptr(bias) if bias is not None else None, _ptr(out), _ptr(slabs), T, N, K, int(code_bits),
+                                      _ptr(bias), _ptr(out), _ptr(slabs), T, N, K, int(code_bits),
                                       DTYPE_CODE[out_dtype], int(w_mant_bits), int(x_mant_bits), _stream(x)), "bfpq_hbfp_linear_sp24")
     return out.view(tuple(x.shape[:-1]) + (N,))
 
