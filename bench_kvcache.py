@@ -1,0 +1,129 @@
+#!/usr/bin/env python3
+"""bench_kvcache.py -- one autoregressive decode step of one attention layer (the new token's key / value joined to S - 1 past ones,
+scores, softmax, context; modeling_gpt2.py:345-348 with :207, 243) on one MI355X, three ways:
+  fake   F_matmul_bfp with torch.cat pasts: MxM_pre_processing + torch.matmul, all of K and V quantized again at every step;
+  int8   F_matmul_bfp(matrix_unit='int8') with torch.cat pasts: codes of all of K and V made at every step, the batched int8 GEMM;
+  cache  bfp_ops.HBFPKVCache: append of one token + scores + softmax + context from the held codes,
+and, for the cache alone, the append of a prefill chunk of S tokens.  Method of bench_matmul.py: hipGraph replay, the median of the
+replays, the legs alternating round by round in one process.  (A captured append writes at the captured position: every replay redoes the
+same step, which is what is timed.)  On a tree without the cache the cache columns are null and "cache" says "absent".
+
+--parent-json FILE: after the run (or alone, with --merge-only, on an existing --out file) every row gains parent_fake_us / parent_int8_us
+and their min / max from the row of the same shape, dtype and config in FILE, the output of this script on the parent commit.
+
+Without --case: a driver that runs every case as its own child process under `timeout`, chained with && (a case that faults, hangs or
+fails ends the run), each appending its rows to the --out file (default bench_out/kvcache.json)."""
+import argparse, json, os, subprocess, sys
+ROOT = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, ROOT)
+from bench_matmul import replay_times  # noqa: E402
+
+# name: (batch, heads, S, head_dim)
+SHAPES = {"gpt2s_b1_s128": (1, 12, 128, 64), "gpt2s_b1_s1024": (1, 12, 1024, 64), "gpt2s_b1_s4096": (1, 12, 4096, 64),
+          "gpt2s_b8_s128": (8, 12, 128, 64), "gpt2s_b8_s1024": (8, 12, 1024, 64), "gpt2s_b8_s4096": (8, 12, 4096, 64),
+          "d128_h32_s2048": (1, 32, 2048, 128)}
+CONFIGS = {"hbfp8_b64": dict(mant_bits=7, block_size=64), "hbfp4_b64": dict(mant_bits=3, block_size=64), "hbfp8_b16": dict(mant_bits=7, block_size=16)}
+DTYPES = ("bf16", "fp32")
+OUT = os.path.join(ROOT, "bench_out", "kvcache.json")
+
+
+def run_case(shape, iters, rounds, out, prefill_too=True):
+    import torch
+    import quantization_sparsity_interplay_amd as bfpq
+    from quantization_sparsity_interplay_amd.bfp import bfp_ops
+    dev = "cuda:0"
+    batch, heads, S, D = SHAPES[shape]
+    rows = []
+    for dname in DTYPES:
+        dt = dict(bf16=torch.bfloat16, fp32=torch.float32)[dname]
+        g = torch.Generator().manual_seed(1)
+        k, v = (torch.randn(batch, heads, S, D, generator=g).to(dt).to(dev) for _ in range(2))
+        q = torch.randn(batch, heads, 1, D, generator=g).to(dt).to(dev)
+        past_k, past_v, k_new, v_new = k[:, :, :S - 1].contiguous(), v[:, :, :S - 1].contiguous(), k[:, :, S - 1:].contiguous(), v[:, :, S - 1:].contiguous()
+        scale = 1.0 / D ** 0.5
+        for cname, c in CONFIGS.items():
+            kw = bfpq.BFPConfig.hbfp(c['mant_bits'] + 1, c['block_size']).to_kwargs()
+            fake = bfp_ops.F_matmul_bfp(**dict(kw))
+            i8 = bfp_ops.F_matmul_bfp(matrix_unit='int8', **dict(kw))
+            stats = getattr(i8, 'matmul_stats', None)
+            if stats is not None and hasattr(bfp_ops, 'MATMUL_I8_MIN'):
+                bfp_ops.MATMUL_I8_MIN = {key: 1 for key in bfp_ops.MATMUL_I8_MIN}     # time the route itself: every default floor off
+            cache = i8.kv_cache(batch, heads, D, S, dtype=dt, device=dev) if hasattr(i8, 'kv_cache') else None
+
+            def cat_step(mm):
+                k_all, v_all = torch.cat([past_k, k_new], dim=2), torch.cat([past_v, v_new], dim=2)
+                p = torch.softmax(mm(q, k_all.transpose(-1, -2)).float() * scale, dim=-1).to(dt)
+                return mm(p, v_all)
+
+            def cache_step():
+                cache.length = S - 1
+                cache.append(k_new, v_new)
+                p = torch.softmax(cache.scores(q).float() * scale, dim=-1).to(dt)
+                return cache.context(p)
+
+            def prefill():
+                cache.length = 0
+                cache.append(k, v)
+
+            with torch.no_grad():
+                fns = [lambda: cat_step(fake)] + ([lambda: cat_step(i8)] if stats is not None else [])
+                if cache is not None:
+                    cache.append(past_k, past_v)
+                    fns.append(cache_step)
+                med, spread = replay_times(fns, iters, rounds)
+                ran_i8 = stats is not None and stats.i8_calls > 0 and stats.fake_calls == 0
+                pre = replay_times([prefill], max(1, iters // 4), rounds) if cache is not None and prefill_too else None
+            row = dict(shape=shape, batch=batch, heads=heads, S=S, head_dim=D, dtype=dname, config=cname, iters=iters, rounds=rounds,
+                       fake_us=med[0], fake_min_max_us=spread[0], int8_route="ran" if ran_i8 else ("absent" if stats is None else "refused"),
+                       int8_us=med[1] if ran_i8 else None, int8_min_max_us=spread[1] if ran_i8 else None,
+                       cache="ran" if cache is not None else "absent", cache_us=med[-1] if cache is not None else None,
+                       cache_min_max_us=spread[-1] if cache is not None else None,
+                       prefill_append_us=pre[0][0] if pre else None, cache_bytes=cache.nbytes() if cache is not None else None,
+                       kv_bytes=2 * k.numel() * k.element_size())
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            cache = None
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    old = json.load(open(out)) if os.path.exists(out) else []
+    json.dump(old + rows, open(out, "w"), indent=1)
+
+
+def merge_parent(out, parent_json):
+    """add the parent commit's two legs (the rows of parent_json, this script's output there) to the rows of `out`"""
+    parent = {(r['shape'], r['dtype'], r['config']): r for r in json.load(open(parent_json))}
+    rows = json.load(open(out))
+    for r in rows:
+        p = parent[(r['shape'], r['dtype'], r['config'])]
+        r.update(parent_fake_us=p['fake_us'], parent_fake_min_max_us=p['fake_min_max_us'], parent_int8_us=p['int8_us'],
+                 parent_int8_min_max_us=p['int8_min_max_us'])
+    json.dump(rows, open(out, "w"), indent=1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--case", choices=sorted(SHAPES))
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--timeout", type=int, default=240, help="seconds per case (driver mode)")
+    ap.add_argument("--out", default=OUT, help="JSON file the rows are appended to")
+    ap.add_argument("--parent-json", help="this script's output on the parent commit: its two legs are added to every row of --out")
+    ap.add_argument("--skip-prefill", action="store_true", help="with --case: do not time the prefill append (a kernel trace of the decode step alone)")
+    ap.add_argument("--merge-only", action="store_true", help="run nothing: add --parent-json to an existing --out file")
+    a = ap.parse_args()
+    out = os.path.abspath(a.out)
+    if a.merge_only:
+        return merge_parent(out, a.parent_json)
+    if a.case:
+        return run_case(a.case, a.iters, a.rounds, out, not a.skip_prefill)
+    if os.path.exists(out):
+        os.remove(out)
+    steps = [f"timeout -k 10 {a.timeout} {sys.executable} {os.path.abspath(__file__)} --case {s} --iters {a.iters} --rounds {a.rounds} --out {out}"
+             for s in SHAPES]
+    rc = subprocess.call(" && ".join(steps), shell=True)
+    if rc == 0 and a.parent_json:
+        merge_parent(out, a.parent_json)
+    sys.exit(rc)
+
+
+if __name__ == "__main__":
+    main()

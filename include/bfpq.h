@@ -414,6 +414,14 @@ int bfpq_codes4_to_i8(const void* codes4_dev, void* codes8_dev, int64_t n_codes,
 int bfpq_hbfp_bmm_i8_ok(int64_t B, int64_t T, int64_t N, int64_t K, int64_t ldk, int block_size);
 int bfpq_hbfp_bmm_i8(const void* xcodes_dev, const int8_t* xexp_dev, const void* wcodes_dev, const int8_t* wexp_dev, void* out_dev, int64_t B,
                      int64_t T, int64_t N, int64_t K, int64_t ldk, int block_size, int out_dtype, int w_mant_bits, int x_mant_bits, void* stream);
+/* The same product with the second operand read in place from a larger array (the codes of a KV cache): w's code rows have the pitch
+ * w_ld (a multiple of 64, >= K rounded up to 64), its exponent rows the pitch w_exp_ld (>= K / block_size), batch b starts w_bstride
+ * rows after batch b - 1, and only the first w_rows <= N rows of a batch exist: the rows from w_rows to N are computed from row
+ * w_rows - 1 (never read past it) and are the caller's to drop.  x and out as above.  bfpq_hbfp_bmm_i8 is this entry with
+ * w_ld = ldk, w_exp_ld = K / block_size, w_bstride = w_rows = N.  A pitch or stride that does not fit: BFPQ_E_UNSUPPORTED. */
+int bfpq_hbfp_bmm_i8_strided(const void* xcodes_dev, const int8_t* xexp_dev, const void* wcodes_dev, const int8_t* wexp_dev, void* out_dev,
+                             int64_t B, int64_t T, int64_t N, int64_t K, int64_t ldk, int64_t w_ld, int64_t w_exp_ld, int64_t w_bstride,
+                             int64_t w_rows, int block_size, int out_dtype, int w_mant_bits, int x_mant_bits, void* stream);
 /* The second operand of that product when its blocks run along its second-to-last dimension (V of P V): in_dev [B, S, D] of dtype,
  * dense -> int8 codes [B, D, ldk] + int8 exponents [B, D, S/block_size] of float_to_bfp_blocked(in.transpose(-1, -2), identifier 'w')
  * (reference bfp_ops.py:153 with :29-59: the transposed copy, the quantizer and the transpose back), round-half-even, no pruning; one
@@ -423,6 +431,42 @@ int bfpq_hbfp_bmm_i8(const void* xcodes_dev, const int8_t* xexp_dev, const void*
  * exp_win_dev: bfpq_exp_window_host(dtype) on the device. */
 int bfpq_hbfp_codes_t(const void* in_dev, void* codes_dev, int8_t* exps_dev, int64_t B, int64_t S, int64_t D, int64_t ldk, int dtype,
                       int block_size, int mant_bits, double epsilon, const uint8_t* exp_win_dev, void* stream);
+/* ---- attention keys and values held as HBFP codes across decode steps (csrc/bfpq_kvcache.hip) ----------------------------------------
+ * Replaces, for decoding with layer_past (reference modeling_gpt2.py:345-348, 415-419), the torch.cat of the past keys / values and the
+ * quantization of all of K along D and of all of V^T along S at every step (bfp_ops.py:240-245 through :187-190 and :153).  Per head
+ * b < BH, capacity cap tokens (bfpq_kv_ok: block_size 16, 32 or 64, D % block_size == 0, D % 16 == 0, D <= 1024, cap % 64 == 0):
+ *   k_codes [BH, cap, ldd] int8 (ldd % 64 == 0, >= D), k_exps [BH, cap, D / block_size] int8: blocks along D;
+ *   v_codes [BH, D, cap] int8 (zeroed by the caller once), v_exps [BH, D, cap / block_size] int8: blocks along the tokens;
+ *   v_tail  [BH, block_size, D] of dtype: the original values of the token block that is still open.
+ * bfpq_kv_append: k_new, v_new [BH, t, D] of dtype become tokens pos .. pos + t - 1 (pos = tokens held so far, pos + t <= cap, any
+ * t >= 1 in one call).  Key rows are quantized once.  Every token block of V the chunk touches is quantized from original values --
+ * v_tail for the tokens before pos, v_new for the chunk, zeros for the tokens not yet there (the reference's zero pad of a ragged last
+ * block, bfp_ops.py:50-53) -- so after every call code * 2^(exp - mant_bits) equals float_to_bfp_blocked(K_all, identifier 'w') and
+ * float_to_bfp_blocked(V_all^T, identifier 'w') bit for bit (up to the sign of zero), and the codes from pos + t to the end of the
+ * open block are zero.  Unknown dtype / block_size, mant_bits outside 1..7, a negative size, a NULL or (float arrays, codes) not
+ * 16-byte aligned pointer: BFPQ_E_ARG; a shape bfpq_kv_ok refuses, a bad ldd or pos + t > cap: BFPQ_E_UNSUPPORTED; BH or t of 0
+ * returns 0.  Every check returns before anything is launched.  exp_win_dev: bfpq_exp_window_host(dtype) on the device. */
+int bfpq_kv_ok(int64_t D, int64_t cap, int block_size);
+int bfpq_kv_append(const void* k_new_dev, const void* v_new_dev, void* k_codes_dev, int8_t* k_exps_dev, void* v_codes_dev, int8_t* v_exps_dev,
+                   void* v_tail_dev, int64_t BH, int64_t D, int64_t pos, int64_t t, int64_t cap, int64_t ldd, int dtype, int block_size,
+                   int mant_bits, double epsilon, const uint8_t* exp_win_dev, void* stream);
+/* The decode product against one cached operand, the few-token operand quantized inside the kernel (reference bfp_ops.py:187-190 on
+ * (q, K_all^T) or (p, V_all) of modeling_gpt2.py:207, 243): out[b][t][n] = sum_k Q(x)[b][t][k] w[b][n][k] for t < Tq <=
+ * BFPQ_KV_DEC_MAX_TOKENS, x [B, Tq, ldx] of dtype (Kx elements per row, dense, unpruned), out [B, Tq, ldo] of dtype (Nout per row,
+ * ldo % 4 == 0: the entries from Nout to ldo may be written), w the codes (row pitch ldw, a multiple of 64), exponents (row pitch ldwe)
+ * and batch stride in rows (w_bstride) of
+ *   BFPQ_KV_QK: k_codes -- n the Nout = S cached keys, k the Kx = D elements of a key (Kx % block_size == 0);
+ *   BFPQ_KV_PV: v_codes -- n the Nout = D columns (Nout % 16 == 0), k the Kx = S cached tokens, any S >= 1: x's last block is quantized
+ *               with zeros past S, which is the reference's zero pad; the cache holds zero codes there.
+ * Arithmetic as bfpq_hbfp_bmm_i8 (an exact integer sum per block, one rescale, fp32 across blocks in block order, -128 = NaN block):
+ * on the same operands the same bits.  Rows of w at or past Nout are never read.  Errors as above; Tq > BFPQ_KV_DEC_MAX_TOKENS or a
+ * pitch that does not fit: BFPQ_E_UNSUPPORTED; B, Tq or Nout of 0 returns 0.  w's codes and out 16-byte aligned. */
+#define BFPQ_KV_QK 0
+#define BFPQ_KV_PV 1
+#define BFPQ_KV_DEC_MAX_TOKENS 16
+int bfpq_kv_bmm_dec(const void* x_dev, const void* wcodes_dev, const int8_t* wexp_dev, void* out_dev, int64_t B, int64_t Tq, int64_t Kx,
+                    int64_t Nout, int64_t ldx, int64_t ldw, int64_t ldwe, int64_t w_bstride, int64_t ldo, int family, int dtype,
+                    int block_size, int x_mant_bits, int w_mant_bits, double epsilon, const uint8_t* exp_win_dev, void* stream);
 /* ---- 2:4-compressed packed weights (format sp24) and their few-token product on v_smfmac_i32_16x16x64_i8 -------------------------
  * A weight pruned N:M with M = 4, N <= 2 along K (_structured_N_M_sparsity, reference bfp_ops.py:73-91) and quantized to HBFP block 64
  * holds at most 2 non-zero codes per group of 4.  sp24 keeps those two codes and their 2-bit positions, tiled for the decode kernel

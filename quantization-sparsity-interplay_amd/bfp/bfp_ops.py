@@ -1171,11 +1171,13 @@ def F_linear_bfp(**kwargs):
 
 
 class MatmulStats:
-    """what an F_matmul_bfp(matrix_unit='int8') op ran: i8_calls on the int8 matrix unit, fake_calls as the plain composition"""
+    """what an F_matmul_bfp(matrix_unit='int8') op ran: i8_calls on the int8 matrix unit, fake_calls as the plain composition,
+    cache_calls the scores / context products of the KV caches made by its kv_cache()"""
 
     def __init__(self):
         self.i8_calls = 0
         self.fake_calls = 0
+        self.cache_calls = 0
 
 
 # The batched int8 route by default: from this many rows of the first operand (T = x.shape[-2]) on, None: never.  Keyed by (operand
@@ -1257,9 +1259,170 @@ def _gen_matmul_i8_op(bfp_args, matrix_unit):
         stats.fake_calls += 1
         return fake(x, w, *args, **kwargs)
 
+    def kv_cache(batch, heads, head_dim, capacity, dtype=torch.bfloat16, device='cuda'):
+        """an HBFPKVCache under this op's bfp_args; its products count in matmul_stats.cache_calls"""
+        return HBFPKVCache(batch, heads, head_dim, capacity, dtype=dtype, stats=stats, **dict(bfp_args, device=device))
+
     bfp_op.__name__ = fake.__name__
     bfp_op.matmul_stats = stats
+    bfp_op.kv_cache = kv_cache
     return bfp_op
+
+
+def kv_cache_config_check(a, head_dim):
+    """raise ValueError unless HBFPKVCache holds keys and values of head_dim under the configuration `a` (unpacked bfp_args): 'bfp' in both
+    formats, round-half-even, block 16, 32 or 64, mant_bits 1..7, head_dim a multiple of the block and of 16, K and V dense.  Pruned K / V
+    (w_sparsity) is refused: N:M along the open token block and the whole-tensor threshold both change as tokens arrive.  in_sparsity (the
+    pruning of q and p) is taken as the batched int8 route takes it.  Host logic only."""
+    if a['num_format'] != 'bfp' or a['sparsity_num_format'] != 'bfp':
+        raise ValueError("HBFPKVCache holds HBFP codes: num_format and sparsity_num_format must be 'bfp' (got %r, %r)"
+                         % (a['num_format'], a['sparsity_num_format']))
+    if a['rounding_mode'] != rounding_modes.DETERM:
+        raise ValueError("HBFPKVCache: stochastic rounding is refused (appended codes must not depend on a draw): rounding_mode must be "
+                         "'determ' (got %r)" % (a['rounding_mode'],))
+    if a['block_size'] not in (64,) + native.I8_BLOCKS or isinstance(a['block_size'], bool):
+        raise ValueError("HBFPKVCache: block_size must be 16, 32 or 64 (got %r)" % (a['block_size'],))
+    if isinstance(a['mant_bits'], bool) or not 1 <= a['mant_bits'] <= 7:
+        raise ValueError("HBFPKVCache: mant_bits must be 1..7, codes are int8 (got %r)" % (a['mant_bits'],))
+    if head_dim < 16 or head_dim % a['block_size'] or head_dim % 16:
+        raise ValueError("HBFPKVCache: head_dim must be a multiple of block_size and of 16 (got head_dim=%r, block_size=%r)"
+                         % (head_dim, a['block_size']))
+    if a['w_sparsity'] == True:  # noqa: E712
+        raise ValueError("HBFPKVCache: pruned K / V (w_sparsity) is refused: pruning does not compose with appending tokens")
+    if not _pruning_ok(a, w_quantize_first=True):
+        raise ValueError("HBFPKVCache: in_sparsity configuration not taken (sparsity_mode=%r, N:M=%r:%r, sparsity_frac=%r)"
+                         % (a['sparsity_mode'], a['N'], a['M'], a['sparsity_frac']))
+
+
+class HBFPKVCache:
+    """Attention keys and values of B x H heads held as HBFP codes across decode steps (csrc/bfpq_kvcache.hip): what the
+    reference's GPT-2 keeps as layer_past (modeling_gpt2.py:345-348) and quantizes again in full at every step.
+
+        cache.append(k_new, v_new)   # each [B, H, t, D], any t >= 1; returns the new length
+        cache.scores(q)              # [B, H, Tq, S] == F_matmul_bfp(**bfp_args)(q, K_all.transpose(-1, -2))
+        cache.context(p)             # [B, H, Tq, D] == F_matmul_bfp(**bfp_args)(p, V_all), p [B, H, Tq, S]
+
+    with K_all / V_all everything appended so far and S = cache.length, on the int8 matrix unit (exact block sums, fp32 across blocks in
+    block order: the arithmetic of F_matmul_bfp(matrix_unit='int8')).  At every length the codes stand for
+    float_to_bfp_blocked(K_all, identifier='w') and float_to_bfp_blocked(V_all.transpose(-1, -2), identifier='w') bit for bit, up to the
+    sign of zero: V's blocks run along the tokens, so its open block is quantized again from the original values (v_tail) at every
+    append, never from codes.  Up to 16 dense rows of q / p are quantized inside the product kernel; more rows, or in_sparsity, go through
+    native.act_codes and the batched GEMM (there p is zero-padded to whole blocks first; with unstructured in_sparsity that needs
+    S % block_size == 0, the whole-tensor threshold would count the pad).
+
+    Inference only: every call raises ValueError while gradients are recorded.  The length lives on the host (a Python int), so a decode
+    step cannot be captured in a hipGraph: a replay would append at the captured position.  keys() / values() dequantize, for inspection
+    and tests."""
+
+    def __init__(self, batch, heads, head_dim, capacity, dtype=torch.bfloat16, device='cuda', stats=None, **bfp_args):
+        a = unpack_bfp_args(bfp_args)
+        if bfp_args:
+            raise TypeError(f"HBFPKVCache: unknown arguments {sorted(bfp_args)}")
+        kv_cache_config_check(a, head_dim)
+        if dtype not in native.DTYPE_CODE:
+            raise TypeError(f"HBFPKVCache: unsupported dtype {dtype}")
+        if batch < 1 or heads < 1 or capacity < 1:
+            raise ValueError(f"HBFPKVCache: batch, heads and capacity must be >= 1 (got {batch}, {heads}, {capacity})")
+        self.args, self.act = a, native.ActSparsity.from_bfp_args(a)
+        self.batch, self.heads, self.head_dim, self.capacity, self.dtype = batch, heads, head_dim, capacity, dtype
+        self.block, self.mant_bits, self.epsilon = a['block_size'], a['mant_bits'], a['epsilon']
+        self.cap = native.code_pitch(capacity)                   # tokens the buffers hold: a multiple of 64 and of the block
+        if not native.kv_ok(head_dim, self.cap, self.block):
+            raise ValueError(f"HBFPKVCache: head_dim {head_dim} x capacity {capacity} at block {self.block} is not taken")
+        self.stats = stats if stats is not None else MatmulStats()
+        self.length = 0
+        B, H, D, cap, blk = batch, heads, head_dim, self.cap, self.block
+        z = lambda *shape, dt=torch.int8: torch.zeros(shape, dtype=dt, device=device)
+        self.buffers = dict(k_codes=z(B, H, cap, native.code_pitch(D)), k_exps=z(B, H, cap, D // blk), v_codes=z(B, H, D, cap),
+                            v_exps=z(B, H, D, cap // blk), v_tail=z(B, H, blk, D, dt=dtype))
+        for name, t in self.buffers.items():
+            setattr(self, name, t)
+
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in self.buffers.values())
+
+    def reset(self):
+        self.length = 0
+        self.v_codes.zero_()
+
+    def _operand(self, x, what, last):
+        if torch.is_grad_enabled():
+            raise ValueError(f"HBFPKVCache.{what}: inference only, called while gradients are recorded (use torch.no_grad())")
+        want = (self.batch, self.heads, last)
+        if not isinstance(x, torch.Tensor) or x.dim() != 4 or (x.shape[0], x.shape[1], x.shape[3]) != want or x.shape[2] < 1:
+            raise ValueError(f"HBFPKVCache.{what} takes [{self.batch}, {self.heads}, t >= 1, {last}] (got {tuple(getattr(x, 'shape', ()))})")
+        if x.dtype != self.dtype or x.device != self.k_codes.device:
+            raise ValueError(f"HBFPKVCache.{what}: the cache holds {self.dtype} on {self.k_codes.device} (got {x.dtype} on {x.device})")
+        return x.reshape(self.batch * self.heads, x.shape[2], last)
+
+    def append(self, k_new, v_new):
+        """k_new, v_new [B, H, t, D] become tokens length .. length + t - 1 (one launch for a prefill chunk or one token)"""
+        k, v = self._operand(k_new, 'append', self.head_dim), self._operand(v_new, 'append', self.head_dim)
+        t = k.shape[1]
+        if v.shape[1] != t:
+            raise ValueError(f"HBFPKVCache.append: {t} keys and {v.shape[1]} values")
+        if self.length + t > self.capacity:
+            raise ValueError(f"HBFPKVCache.append: {self.length} + {t} tokens exceed the capacity {self.capacity}")
+        native.kv_append(k.contiguous(), v.contiguous(), self.k_codes, self.k_exps, self.v_codes, self.v_exps, self.v_tail, self.length,
+                         self.block, self.mant_bits, self.epsilon)
+        self.length += t
+        return self.length
+
+    def _in_kernel(self, Tq):
+        return self.act is None and Tq <= native.KV_DEC_MAX_TOKENS
+
+    def scores(self, q):
+        """q [B, H, Tq, D] -> [B, H, Tq, S]: Q_in(q) @ Q_w(K_all)^T"""
+        x = self._operand(q, 'scores', self.head_dim)
+        S, D, BH, Tq, m = self.length, self.head_dim, x.shape[0], x.shape[1], self.mant_bits
+        if S < 1:
+            raise ValueError("HBFPKVCache.scores: the cache is empty")
+        if self._in_kernel(Tq):
+            out = native.kv_bmm_dec(x, self.k_codes, self.k_exps, native.KV_QK, S, self.cap, self.block, m, self.epsilon)
+        else:
+            xq = native.act_codes(x.reshape(BH * Tq, D), m, self.epsilon, self.act, block_size=self.block)
+            N = (S + 15) // 16 * 16                               # rows S .. N - 1 repeat key S - 1 and are dropped
+            out = native.hbfp_bmm_i8_strided(xq, self.k_codes, self.k_exps, BH, Tq, N, D, self.cap, S, m, m, block_size=self.block,
+                                             out_dtype=self.dtype)[:, :, :S]
+        self.stats.cache_calls += 1
+        return out.unflatten(0, (self.batch, self.heads))
+
+    def context(self, p):
+        """p [B, H, Tq, S] -> [B, H, Tq, D]: Q_in(p) @ Q_w(V_all^T)^T, blocks along the S cached tokens (the last one zero-padded)"""
+        if not isinstance(p, torch.Tensor) or p.dim() != 4 or p.shape[-1] != self.length or self.length < 1:
+            raise ValueError(f"HBFPKVCache.context takes p [..., {self.length}], the cached length >= 1 (got {tuple(getattr(p, 'shape', ()))})")
+        x = self._operand(p, 'context', self.length)
+        S, D, BH, Tq, m, blk = self.length, self.head_dim, x.shape[0], x.shape[1], self.mant_bits, self.block
+        if self._in_kernel(Tq):
+            out = native.kv_bmm_dec(x, self.v_codes, self.v_exps, native.KV_PV, D, D, blk, m, self.epsilon)
+        else:
+            Sp = (S + blk - 1) // blk * blk
+            if Sp != S:
+                if self.act is not None and (self.act.mode != 'structured' or blk % self.act.M):
+                    raise ValueError(f"HBFPKVCache.context: in_sparsity {self.act.mode} on p needs S % block_size == 0 "
+                                     f"(or N:M with M dividing the block); S = {S}")
+                # the reference's zero pad of the last block (bfp_ops.py:50-53; for N:M its pad to M, :79-82, and all-zero groups); p is small
+                x = F.pad(x, (0, Sp - S))
+            xq = native.act_codes(x.reshape(BH * Tq, Sp), m, self.epsilon, self.act, block_size=blk)
+            out = native.hbfp_bmm_i8_strided(xq, self.v_codes, self.v_exps, BH, Tq, D, Sp, D, D, m, m, block_size=blk, out_dtype=self.dtype)
+        self.stats.cache_calls += 1
+        return out.unflatten(0, (self.batch, self.heads))
+
+    def keys(self):
+        """the cached keys dequantized, [B, H, S, D]"""
+        BH, S, D = self.batch * self.heads, self.length, self.head_dim
+        c = self.k_codes.view(BH, self.cap, -1)[:, :S, :D].reshape(BH * S, D)
+        e = self.k_exps.view(BH, self.cap, -1)[:, :S].reshape(BH * S, D // self.block)
+        return native.dequantize(c, e, D, self.dtype, self.block, self.mant_bits, 8).view(self.batch, self.heads, S, D)
+
+    def values(self):
+        """the cached values dequantized, [B, H, S, D]"""
+        BH, S, D, blk = self.batch * self.heads, self.length, self.head_dim, self.block
+        Sp = (S + blk - 1) // blk * blk
+        c = self.v_codes.view(BH * D, self.cap)[:, :Sp].contiguous()
+        e = self.v_exps.view(BH * D, -1)[:, :Sp // blk].contiguous()
+        v = native.dequantize(c, e, Sp, self.dtype, blk, self.mant_bits, 8)[:, :S]
+        return v.reshape(self.batch, self.heads, D, S).transpose(-1, -2)
 
 
 def F_matmul_bfp(matrix_unit=False, **kwargs):

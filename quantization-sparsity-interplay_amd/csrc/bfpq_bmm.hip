@@ -1,7 +1,9 @@
 // bfpq_bmm.hip -- the batched contraction of two activations, both HBFP: out[b][t][n] = sum_k x[b][t][k] w[b][n][k], b < B, with x and w
 // int8 codes + one int8 exponent per block of 64, 32 or 16, mantissa widths xm, wm in 1..7.  Replaces torch.matmul on the two
 // fake-quantised operands of F_matmul_bfp (reference bfp_ops.py:240-245 through :187-190), the attention matmuls of the reference's
-// GPT-2 (modeling_gpt2.py:207, 243, 297).  Neither operand is a weight: both sets of codes are made per call.
+// GPT-2 (modeling_gpt2.py:207, 243, 297).  Neither operand is a weight: both sets of codes are made per call -- or, decoding with
+// layer_past (modeling_gpt2.py:345-348), w's are the codes of a KV cache (bfpq_kvcache.hip): bfpq_hbfp_bmm_i8_strided gives w a row pitch,
+// an exponent pitch, a batch stride and a count of valid rows of its own.
 //
 // Arithmetic: the int8 block product of bfpq_i8mma.h (exactness argument, NaN marker and lane map are there).  One
 // v_mfma_i32_16x16x64_i8 per block of 64 (v_mfma_i32_16x16x32_i8 per block of 32 or 16), an exact integer block sum, one rescale by
@@ -41,7 +43,7 @@ constexpr int kWaves = 4;                                 // waves of a workgrou
 template <int BLK, int OUT_DT, int TM, int TN>
 __global__ void __launch_bounds__(64 * kWaves, TN == 4 ? 2 : 3) k_bmm_i8(const int8_t* __restrict__ xc, const int8_t* __restrict__ xe, const int8_t* __restrict__ wc,
                                                         const int8_t* __restrict__ we, void* __restrict__ out, int B, int T, int N, int K, int ldk,
-                                                        int tiles_t, int xm, int wm)
+                                                        int tiles_t, int xm, int wm, int ldw, int ldwe, int wbs, int nv)
 {
     using Blk = I8Blk<BLK>;
     using op_t = typename Blk::op_t;
@@ -52,18 +54,19 @@ __global__ void __launch_bounds__(64 * kWaves, TN == 4 ? 2 : 3) k_bmm_i8(const i
     const int t0 = (((int)blockIdx.x % tiles_t) * kWaves + w) * BT, n0 = ((int)blockIdx.x / tiles_t) * BN;
     if (t0 >= T) return;                                         // (wave-uniform; the kernel has no barrier)
     const int nb = K / BLK, nch = (K + 63) >> 6;
-    const bool dw = !(nb & 3) && !((reinterpret_cast<uintptr_t>(xe) | reinterpret_cast<uintptr_t>(we)) & 3u);
+    const bool dw = !((nb | ldwe) & 3) && !((reinterpret_cast<uintptr_t>(xe) | reinterpret_cast<uintptr_t>(we)) & 3u);
 
-    // rows past N / T repeat the last row (their results are not stored)
+    // w: code rows of pitch ldw, exponent rows of pitch ldwe, wbs rows from one batch to the next, nv of them valid (dense: ldk, K / BLK, N, N).
+    // rows past nv / T repeat the last row (their results are not stored, or are the caller's to drop)
     uint32_t offW[TM], offX[TN], ewo[TM][4], exo[TN];
 #pragma unroll
     for (int i = 0; i < TM; i++) {
         const int n = n0 + 16 * i + r;
-        offW[i] = (uint32_t)(n < N ? n : N - 1) * (uint32_t)ldk + Blk::lane(q);
+        offW[i] = (uint32_t)(n < nv ? n : nv - 1) * (uint32_t)ldw + Blk::lane(q);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const int ne = n0 + 16 * i + 4 * q + j;
-            ewo[i][j] = (uint32_t)(ne < N ? ne : N - 1) * (uint32_t)nb;
+            ewo[i][j] = (uint32_t)(ne < nv ? ne : nv - 1) * (uint32_t)ldwe;
         }
     }
 #pragma unroll
@@ -76,9 +79,9 @@ __global__ void __launch_bounds__(64 * kWaves, TN == 4 ? 2 : 3) k_bmm_i8(const i
 
     for (int b = blockIdx.y; b < B; b += gridDim.y) {
         const int8_t* const xcb = xc + (size_t)b * T * ldk;
-        const int8_t* const wcb = wc + (size_t)b * N * ldk;
+        const int8_t* const wcb = wc + (size_t)b * wbs * ldw;
         const int8_t* const xeb = xe + (size_t)b * T * nb;
-        const int8_t* const web = we + (size_t)b * N * nb;
+        const int8_t* const web = we + (size_t)b * wbs * ldwe;
 
         // the lane's operands of chunk c: NBS pieces per row (one 16-byte piece at block 64, 8-byte pieces at blocks 32 / 16)
         auto codes = [&](int c, op_t (&aF)[TM][NBS], op_t (&bF)[TN][NBS]) __attribute__((always_inline)) {
@@ -241,14 +244,19 @@ int bfpq_hbfp_bmm_i8_ok(int64_t B, int64_t T, int64_t N, int64_t K, int64_t ldk,
            ldk % 64 == 0 && T * ldk < lim && N * ldk < lim && T * N < lim && ((T + 15) / 16) * ((N + 63) / 64) < lim / 4;
 }
 
-int bfpq_hbfp_bmm_i8(const void* xcodes, const int8_t* xexp, const void* wcodes, const int8_t* wexp, void* out, int64_t B, int64_t T, int64_t N,
-                     int64_t K, int64_t ldk, int block_size, int out_dtype, int w_mant_bits, int x_mant_bits, void* stream)
+int bfpq_hbfp_bmm_i8_strided(const void* xcodes, const int8_t* xexp, const void* wcodes, const int8_t* wexp, void* out, int64_t B, int64_t T,
+                             int64_t N, int64_t K, int64_t ldk, int64_t w_ld, int64_t w_exp_ld, int64_t w_bstride, int64_t w_rows, int block_size,
+                             int out_dtype, int w_mant_bits, int x_mant_bits, void* stream)
 {
     if (!dtype_ok(out_dtype) || !i8_block_ok(block_size) || !i8_mant_ok(w_mant_bits) || !i8_mant_ok(x_mant_bits) || B < 0 ||
         T < 0 || N < 0)
         return BFPQ_E_ARG;
     if (B == 0 || T == 0 || N == 0) return 0;
     if (!bfpq_hbfp_bmm_i8_ok(B, T, N, K, ldk, block_size)) return BFPQ_E_UNSUPPORTED;
+    const int64_t lim = (int64_t)1 << 31;
+    if (w_ld % 64 != 0 || w_ld < (K + 63) / 64 * 64 || w_exp_ld < K / block_size || w_rows < 1 || w_rows > N || w_bstride < w_rows ||
+        w_bstride * w_ld >= lim || w_bstride * w_exp_ld >= lim)
+        return BFPQ_E_UNSUPPORTED;
     if (!xcodes || !xexp || !wcodes || !wexp || !out || !aligned16(xcodes, wcodes, out)) return BFPQ_E_ARG;
     const int tn = bmm_tn(B, T, N);
     const int tiles_t = (int)((T + 16 * tn * kWaves - 1) / (16 * tn * kWaves));
@@ -259,7 +267,7 @@ int bfpq_hbfp_bmm_i8(const void* xcodes, const int8_t* xexp, const void* wcodes,
             auto go = [&](auto tnc) {
                 hipLaunchKernelGGL((k_bmm_i8<decltype(blk)::value, decltype(dt)::value, 4, decltype(tnc)::value>), grid, dim3(64 * kWaves), 0, s,
                                    (const int8_t*)xcodes, xexp, (const int8_t*)wcodes, wexp, out, (int)B, (int)T, (int)N, (int)K, (int)ldk, tiles_t,
-                                   x_mant_bits, w_mant_bits);
+                                   x_mant_bits, w_mant_bits, (int)w_ld, (int)w_exp_ld, (int)w_bstride, (int)w_rows);
             };
             if (tn == 4) go(std::integral_constant<int, 4>{});
             else if (tn == 2) go(std::integral_constant<int, 2>{});
@@ -267,6 +275,14 @@ int bfpq_hbfp_bmm_i8(const void* xcodes, const int8_t* xexp, const void* wcodes,
         });
     });
     return (int)hipGetLastError();
+}
+
+int bfpq_hbfp_bmm_i8(const void* xcodes, const int8_t* xexp, const void* wcodes, const int8_t* wexp, void* out, int64_t B, int64_t T, int64_t N,
+                     int64_t K, int64_t ldk, int block_size, int out_dtype, int w_mant_bits, int x_mant_bits, void* stream)
+{
+    // w dense: the pitch of x, K / block exponents per row, N rows per batch, all of them valid
+    return bfpq_hbfp_bmm_i8_strided(xcodes, xexp, wcodes, wexp, out, B, T, N, K, ldk, ldk, i8_block_ok(block_size) ? K / block_size : 0, N, N,
+                                    block_size, out_dtype, w_mant_bits, x_mant_bits, stream);
 }
 
 int bfpq_hbfp_codes_t(const void* in, void* codes, int8_t* exps, int64_t B, int64_t S, int64_t D, int64_t ldk, int dtype, int block_size,

@@ -104,6 +104,10 @@ PROTOTYPES = {
     "bfpq_hbfp_bmm_i8_ok": (_i32, [_i64, _i64, _i64, _i64, _i64, _i32]),
     "bfpq_hbfp_bmm_i8": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
     "bfpq_hbfp_codes_t": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _dbl, _vp, _vp]),
+    "bfpq_hbfp_bmm_i8_strided": (_i32, [_vp, _vp, _vp, _vp, _vp] + [_i64] * 9 + [_i32, _i32, _i32, _i32, _vp]),
+    "bfpq_kv_ok": (_i32, [_i64, _i64, _i32]),
+    "bfpq_kv_append": (_i32, [_vp] * 7 + [_i64] * 6 + [_i32, _i32, _i32, _dbl, _vp, _vp]),
+    "bfpq_kv_bmm_dec": (_i32, [_vp, _vp, _vp, _vp] + [_i64] * 9 + [_i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp]),
 }
 
 
@@ -1337,6 +1341,103 @@ def codes_transposed(v, block_size, mant_bits, epsilon):
                                                int(mant_bits), float(epsilon), _ptr(exp_window_dev(src.dtype, dev)), _stream(src)),
               "bfpq_hbfp_codes_t")
     return codes, exps
+
+
+def hbfp_bmm_i8_strided(xq, wc, we, B, T, N, K, w_bstride, w_rows, w_mant_bits, x_mant_bits, block_size=64, out_dtype=torch.float32):
+    """hbfp_bmm_i8 with the second operand read in place from a larger array (a KV cache's codes): wc [..., w_ld] int8 codes and
+    we [..., w_exp_ld] int8 exponents, both contiguous, batch b starting w_bstride rows after batch b - 1, the first w_rows <= N rows of a
+    batch valid (rows w_rows .. N - 1 of the result repeat row w_rows - 1: the caller drops them).  xq as for hbfp_bmm_i8.  Returns
+    [B, T, N] (bfpq_hbfp_bmm_i8_strided)."""
+    if not hbfp_bmm_i8_ok(B, T, N, K, w_mant_bits, x_mant_bits, block_size):
+        raise ValueError(f"hbfp_bmm_i8_strided needs block 16, 32 or 64, N % 16 == 0, K % block_size == 0 and mantissas of 1..7 bits "
+                         f"(got B={B}, T={T}, N={N}, K={K}, w_mant_bits={w_mant_bits}, x_mant_bits={x_mant_bits}, block_size={block_size})")
+    if out_dtype not in DTYPE_CODE:
+        raise TypeError(f"unsupported dtype {out_dtype}")
+    xc, xe = xq
+    nb = K // block_size
+    if xe.numel() != B * T * nb or xe.dtype != torch.int8 or we.dtype != torch.int8 or wc.dtype != torch.int8:
+        raise ValueError(f"hbfp_bmm_i8_strided at block {block_size} takes int8 codes and int8 x exponents [{B * T}, {nb}] (got {tuple(xe.shape)})")
+    if not wc.is_contiguous() or not we.is_contiguous():
+        raise ValueError("hbfp_bmm_i8_strided takes contiguous w codes and exponents")
+    w_ld, w_exp_ld = wc.shape[-1], we.shape[-1]
+    if wc.numel() < B * w_bstride * w_ld or we.numel() < B * w_bstride * w_exp_ld:
+        raise ValueError(f"hbfp_bmm_i8_strided: w holds fewer than {B} x {w_bstride} rows (codes {tuple(wc.shape)}, exponents {tuple(we.shape)})")
+    xc = _pitched_codes(xc, B * T, K, "x")
+    require_device_tensor_any(xc)
+    dev = xc.device
+    with torch.cuda.device(dev):
+        xe = xe.contiguous()
+        out = torch.empty((B, T, N), dtype=out_dtype, device=dev)
+        check(load_library().bfpq_hbfp_bmm_i8_strided(_ptr(xc), _ptr(xe), _ptr(wc), _ptr(we), _ptr(out), B, T, N, K, code_pitch(K), int(w_ld),
+                                                      int(w_exp_ld), int(w_bstride), int(w_rows), int(block_size), DTYPE_CODE[out_dtype],
+                                                      int(w_mant_bits), int(x_mant_bits),
+                                                      ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "bfpq_hbfp_bmm_i8_strided")
+    return out
+
+
+# ---- attention keys and values held as HBFP codes (bfpq_kvcache.hip) -------------------------------------------
+KV_QK, KV_PV = 0, 1            # BFPQ_KV_QK, BFPQ_KV_PV
+KV_DEC_MAX_TOKENS = 16         # BFPQ_KV_DEC_MAX_TOKENS: kv_bmm_dec quantizes up to this many rows of x itself
+
+
+def kv_ok(D, cap, block_size):
+    """the KV cache takes this head size and capacity (bfpq_kv_ok)"""
+    return bool(load_library().bfpq_kv_ok(int(D), int(cap), int(block_size)))
+
+
+def kv_append(k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, pos, block_size, mant_bits, epsilon):
+    """k_new, v_new [BH, t, D] become tokens pos .. pos + t - 1 of the cache buffers (bfpq_kv_append: the layout is in include/bfpq.h);
+    one launch for any t >= 1"""
+    require_device_tensor(k_new, "k_new")
+    require_device_tensor(v_new, "v_new")
+    require_device_tensor(v_tail, "v_tail")
+    if k_new.dim() != 3 or v_new.shape != k_new.shape or v_new.dtype != k_new.dtype or v_tail.dtype != k_new.dtype:
+        raise ValueError(f"kv_append takes k_new and v_new [BH, t, D] of one dtype, the cache's (got {tuple(k_new.shape)} {k_new.dtype}, "
+                         f"{tuple(v_new.shape)} {v_new.dtype}, v_tail {v_tail.dtype})")
+    BH, t, D = k_new.shape
+    dev = k_new.device
+    if block_size not in (64,) + I8_BLOCKS:
+        raise ValueError(f"kv_append: block_size must be 16, 32 or 64 (got {block_size})")
+    if k_codes.dim() < 2 or v_codes.dim() < 2:
+        raise ValueError("kv_append takes k_codes [..., cap, ldd] and v_codes [..., D, cap]")
+    cap, ldd = k_codes.shape[-2], k_codes.shape[-1]
+    nbd, nbc = D // block_size, cap // block_size
+    sizes = dict(k_codes=(k_codes, BH * cap * ldd), k_exps=(k_exps, BH * cap * nbd), v_codes=(v_codes, BH * D * cap), v_exps=(v_exps, BH * D * nbc),
+                 v_tail=(v_tail, BH * block_size * D))
+    for name, (buf, numel) in sizes.items():
+        if buf.device != dev or not buf.is_contiguous() or buf.numel() != numel or (name != "v_tail" and buf.dtype != torch.int8):
+            raise ValueError(f"kv_append: {name} must be contiguous on {dev} with {numel} elements"
+                             f"{'' if name == 'v_tail' else ' of int8'} (got {tuple(buf.shape)}, {buf.dtype}, {buf.device})")
+    if v_codes.shape[-1] != cap or not k_new.is_contiguous() or not v_new.is_contiguous():
+        raise ValueError("kv_append takes contiguous k_new / v_new and v_codes [..., D, cap] with k_codes' capacity")
+    with torch.cuda.device(dev):
+        check(load_library().bfpq_kv_append(_ptr(k_new), _ptr(v_new), _ptr(k_codes), _ptr(k_exps), _ptr(v_codes), _ptr(v_exps), _ptr(v_tail), BH, D,
+                                            int(pos), t, cap, ldd, DTYPE_CODE[k_new.dtype], int(block_size), int(mant_bits), float(epsilon),
+                                            _ptr(exp_window_dev(k_new.dtype, dev)), _stream(k_new)), "bfpq_kv_append")
+
+
+def kv_bmm_dec(x, wc, we, family, Nout, w_bstride, block_size, mant_bits, epsilon):
+    """x [BH, Tq <= 16, Kx] (dense) against one cached operand, x quantized inside the kernel
+    (bfpq_kv_bmm_dec).  wc [..., ldw] / we [..., ldwe]: contiguous codes / exponents, w_bstride rows per head.  Returns [BH, Tq, Nout]:
+    a view of a buffer whose row pitch is Nout rounded up to 4."""
+    require_device_tensor(x, "x")
+    if x.dim() != 3:
+        raise ValueError(f"kv_bmm_dec takes x [BH, Tq, Kx] (got {tuple(x.shape)})")
+    BH, Tq, Kx = x.shape
+    x = x.contiguous()
+    dev = x.device
+    for name, buf in (("codes", wc), ("exponents", we)):
+        if buf.device != dev or buf.dtype != torch.int8 or not buf.is_contiguous() or buf.numel() < BH * int(w_bstride) * buf.shape[-1]:
+            raise ValueError(f"kv_bmm_dec: the cached {name} must be contiguous int8 on {dev} with {BH} x {w_bstride} rows "
+                             f"(got {tuple(buf.shape)}, {buf.dtype}, {buf.device})")
+    ldo = (int(Nout) + 3) // 4 * 4
+    with torch.cuda.device(dev):
+        out = torch.empty((BH, Tq, ldo), dtype=x.dtype, device=dev)
+        check(load_library().bfpq_kv_bmm_dec(_ptr(x), _ptr(wc), _ptr(we), _ptr(out), BH, Tq, Kx, int(Nout), Kx, wc.shape[-1], we.shape[-1],
+                                             int(w_bstride), ldo, int(family), DTYPE_CODE[x.dtype], int(block_size), int(mant_bits),
+                                             int(mant_bits), float(epsilon), _ptr(exp_window_dev(x.dtype, dev)), _stream(x)), "bfpq_kv_bmm_dec")
+    return out[:, :, :Nout] if ldo != Nout else out
+
 
 # ---- 2:4-compressed packed weights on the sparse int8 matrix unit (bfpq_sp24.hip) -----------------
 SP24_MAX_TOKENS = 64      # BFPQ_SP24_MAX_TOKENS: hbfp_linear_sp24 takes 1..64 tokens
