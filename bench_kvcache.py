@@ -4,6 +4,9 @@ scores, softmax, context; modeling_gpt2.py:345-348 with :207, 243) on one MI355X
   fake   F_matmul_bfp with torch.cat pasts: MxM_pre_processing + torch.matmul, all of K and V quantized again at every step;
   int8   F_matmul_bfp(matrix_unit='int8') with torch.cat pasts: codes of all of K and V made at every step, the batched int8 GEMM;
   cache  bfp_ops.HBFPKVCache: append of one token + scores + softmax + context from the held codes,
+  device the same step on HBFPKVCache(device_lengths=True): the lengths live on the device, so every replay of the captured step really
+         advances (from S - 1 tokens on; the capacity is S plus the iters x (rounds + 1) + 2 tokens the run appends, scores over the
+         whole capacity), context split over workgroups (--chunks-per-split, 0 = the library's choice),
 and, for the cache alone, the append of a prefill chunk of S tokens.  Method of bench_matmul.py: hipGraph replay, the median of the
 replays, the legs alternating round by round in one process.  (A captured append writes at the captured position: every replay redoes the
 same step, which is what is timed.)  On a tree without the cache the cache columns are null and "cache" says "absent".
@@ -12,7 +15,8 @@ same step, which is what is timed.)  On a tree without the cache the cache colum
 and their min / max from the row of the same shape, dtype and config in FILE, the output of this script on the parent commit.
 
 Without --case: a driver that runs every case as its own child process under `timeout`, chained with && (a case that faults, hangs or
-fails ends the run), each appending its rows to the --out file (default bench_out/kvcache.json)."""
+fails ends the run), each appending its rows to the --out file (default bench_out/kvcache.json).  --case ragged8: the device leg alone
+on batch 8 with lengths spread from 128 to 4096 (no other leg holds such a batch)."""
 import argparse, json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -27,7 +31,55 @@ DTYPES = ("bf16", "fp32")
 OUT = os.path.join(ROOT, "bench_out", "kvcache.json")
 
 
-def run_case(shape, iters, rounds, out, prefill_too=True):
+RAGGED = {"ragged8": (8, 12, (128, 695, 1262, 1829, 2396, 2963, 3530, 4096), 64)}
+
+
+def device_leg(i8, batch, heads, D, lens, k, v, q, dt, dev, iters, rounds, cps):
+    """(cache, step) of the device leg: sequence b prefilled to lens[b] - 1 tokens, room for every token the run appends"""
+    import torch
+    room = iters * (rounds + 1) + 2                                      # replay_times: two warm-up calls, the capture, rounds + 1 replays
+    cache = i8.kv_cache(batch, heads, D, max(lens) + room, dtype=dt, device=dev, device_lengths=True, chunks_per_split=cps, max_query_rows=1)
+    t = max(lens) - 1
+    cache.append(k[:, :, :t].contiguous(), v[:, :, :t].contiguous(), torch.tensor([n - 1 for n in lens], dtype=torch.int32, device=dev))
+    k_new, v_new, scale = k[:, :, -1:].contiguous(), v[:, :, -1:].contiguous(), 1.0 / D ** 0.5
+
+    def step():
+        cache.append(k_new, v_new)
+        p = torch.softmax(cache.scores(q).float() * scale, dim=-1).to(dt)
+        return cache.context(p)
+
+    return cache, step
+
+
+def run_ragged(name, iters, rounds, out, cps):
+    import torch
+    import quantization_sparsity_interplay_amd as bfpq
+    from quantization_sparsity_interplay_amd.bfp import bfp_ops
+    dev = "cuda:0"
+    batch, heads, lens, D = RAGGED[name]
+    rows = []
+    for dname in DTYPES:
+        dt = dict(bf16=torch.bfloat16, fp32=torch.float32)[dname]
+        g = torch.Generator().manual_seed(1)
+        k, v = (torch.randn(batch, heads, max(lens), D, generator=g).to(dt).to(dev) for _ in range(2))
+        q = torch.randn(batch, heads, 1, D, generator=g).to(dt).to(dev)
+        for cname, c in CONFIGS.items():
+            i8 = bfp_ops.F_matmul_bfp(matrix_unit='int8', **bfpq.BFPConfig.hbfp(c['mant_bits'] + 1, c['block_size']).to_kwargs())
+            with torch.no_grad():
+                cache, step = device_leg(i8, batch, heads, D, lens, k, v, q, dt, dev, iters, rounds, cps)
+                med, spread = replay_times([step], iters, rounds)
+                last = cache.lengths.tolist()
+            assert cache.overflow.item() == 0
+            row = dict(shape=name, batch=batch, heads=heads, lengths=list(lens), lengths_at_end=last, head_dim=D, dtype=dname, config=cname,
+                       iters=iters, rounds=rounds, chunks_per_split=cps, device_us=med[0], device_min_max_us=spread[0])
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    old = json.load(open(out)) if os.path.exists(out) else []
+    json.dump(old + rows, open(out, "w"), indent=1)
+
+
+def run_case(shape, iters, rounds, out, prefill_too=True, cps=0):
     import torch
     import quantization_sparsity_interplay_amd as bfpq
     from quantization_sparsity_interplay_amd.bfp import bfp_ops
@@ -67,10 +119,17 @@ def run_case(shape, iters, rounds, out, prefill_too=True):
 
             with torch.no_grad():
                 fns = [lambda: cat_step(fake)] + ([lambda: cat_step(i8)] if stats is not None else [])
+                dcache = None
                 if cache is not None:
                     cache.append(past_k, past_v)
                     fns.append(cache_step)
+                    if 'device_lengths' in (bfp_ops.HBFPKVCache.__init__.__code__.co_varnames):
+                        dcache, dstep = device_leg(i8, batch, heads, D, [S] * batch, k, v, q, dt, dev, iters, rounds, cps)
+                        fns.append(dstep)
                 med, spread = replay_times(fns, iters, rounds)
+                if dcache is not None:
+                    assert dcache.overflow.item() == 0
+                    dev_us, dev_spread, dev_end = med.pop(), spread.pop(), dcache.lengths.tolist()
                 ran_i8 = stats is not None and stats.i8_calls > 0 and stats.fake_calls == 0
                 pre = replay_times([prefill], max(1, iters // 4), rounds) if cache is not None and prefill_too else None
             row = dict(shape=shape, batch=batch, heads=heads, S=S, head_dim=D, dtype=dname, config=cname, iters=iters, rounds=rounds,
@@ -78,6 +137,9 @@ def run_case(shape, iters, rounds, out, prefill_too=True):
                        int8_us=med[1] if ran_i8 else None, int8_min_max_us=spread[1] if ran_i8 else None,
                        cache="ran" if cache is not None else "absent", cache_us=med[-1] if cache is not None else None,
                        cache_min_max_us=spread[-1] if cache is not None else None,
+                       device="ran" if dcache is not None else "absent", device_us=dev_us if dcache is not None else None,
+                       device_min_max_us=dev_spread if dcache is not None else None, device_lengths_at_end=dev_end if dcache is not None else None,
+                       chunks_per_split=cps if dcache is not None else None,
                        prefill_append_us=pre[0][0] if pre else None, cache_bytes=cache.nbytes() if cache is not None else None,
                        kv_bytes=2 * k.numel() * k.element_size())
             rows.append(row)
@@ -93,7 +155,9 @@ def merge_parent(out, parent_json):
     parent = {(r['shape'], r['dtype'], r['config']): r for r in json.load(open(parent_json))}
     rows = json.load(open(out))
     for r in rows:
-        p = parent[(r['shape'], r['dtype'], r['config'])]
+        p = parent.get((r['shape'], r['dtype'], r['config']))
+        if p is None:                                                     # (a case the parent cannot hold: the ragged batch)
+            continue
         r.update(parent_fake_us=p['fake_us'], parent_fake_min_max_us=p['fake_min_max_us'], parent_int8_us=p['int8_us'],
                  parent_int8_min_max_us=p['int8_min_max_us'])
     json.dump(rows, open(out, "w"), indent=1)
@@ -101,7 +165,8 @@ def merge_parent(out, parent_json):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--case", choices=sorted(SHAPES))
+    ap.add_argument("--case", choices=sorted(SHAPES) + sorted(RAGGED))
+    ap.add_argument("--chunks-per-split", type=int, default=0, help="64-token chunks per slice of the device leg's context (0: the library's choice)")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--timeout", type=int, default=240, help="seconds per case (driver mode)")
@@ -113,12 +178,14 @@ def main():
     out = os.path.abspath(a.out)
     if a.merge_only:
         return merge_parent(out, a.parent_json)
+    if a.case in RAGGED:
+        return run_ragged(a.case, a.iters, a.rounds, out, a.chunks_per_split)
     if a.case:
-        return run_case(a.case, a.iters, a.rounds, out, not a.skip_prefill)
+        return run_case(a.case, a.iters, a.rounds, out, not a.skip_prefill, a.chunks_per_split)
     if os.path.exists(out):
         os.remove(out)
-    steps = [f"timeout -k 10 {a.timeout} {sys.executable} {os.path.abspath(__file__)} --case {s} --iters {a.iters} --rounds {a.rounds} --out {out}"
-             for s in SHAPES]
+    steps = [f"timeout -k 10 {a.timeout} {sys.executable} {os.path.abspath(__file__)} --case {s} --iters {a.iters} --rounds {a.rounds} --chunks-per-split {a.chunks_per_split} --out {out}"
+             for s in list(SHAPES) + list(RAGGED)]
     rc = subprocess.call(" && ".join(steps), shell=True)
     if rc == 0 and a.parent_json:
         merge_parent(out, a.parent_json)

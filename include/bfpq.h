@@ -467,6 +467,41 @@ int bfpq_kv_append(const void* k_new_dev, const void* v_new_dev, void* k_codes_d
 int bfpq_kv_bmm_dec(const void* x_dev, const void* wcodes_dev, const int8_t* wexp_dev, void* out_dev, int64_t B, int64_t Tq, int64_t Kx,
                     int64_t Nout, int64_t ldx, int64_t ldw, int64_t ldwe, int64_t w_bstride, int64_t ldo, int family, int dtype,
                     int block_size, int x_mant_bits, int w_mant_bits, double epsilon, const uint8_t* exp_win_dev, void* stream);
+/* The same cache with the lengths in device memory, one per sequence: a ragged batch, and a decode step that a captured graph can
+ * replay (the reference's layer_past grows by torch.cat on the host, modeling_gpt2.py:345-348, 415-419; bfp_ops.py:240-245, :187-190,
+ * :153 as above).  Head b < BH belongs to sequence b / heads (heads >= 1, BH % heads == 0; else BFPQ_E_ARG); lens_dev [BH / heads]
+ * int32 holds the tokens of each sequence.  No entry reads anything back or synchronises.
+ * bfpq_kv_append_dev: bfpq_kv_append with pos = lens_dev[b / heads] and, of the t rows of k_new / v_new [BH, t, D], only the first
+ * counts_dev[b / heads] taken (counts_dev NULL: all t).  t is the row pitch and bounds the grid, which is sized for the worst position
+ * ((t + block_size - 2) / block_size + 1 token blocks of V); workgroups whose block a sequence does not have exit.  A sequence with a
+ * count outside 0..t, a length outside 0..limit or lens + count > limit (limit: the tokens a sequence may hold, 1..cap) is left
+ * untouched -- no codes, no v_tail -- and overflow_dev[0] (int32) is set to 1 by the kernel; nothing ever clears it but the caller.
+ * lens_dev is only read: bfpq_kv_lens_advance, a launch of its own after it in stream order (so no workgroup of the append can see a
+ * moved length), adds to lens_dev[b] what sequence b took by the same rule.  Errors as bfpq_kv_append; limit outside 1..cap or t > cap:
+ * BFPQ_E_UNSUPPORTED; the int32 arrays NULL (counts_dev may be) or not 4-byte aligned: BFPQ_E_ARG. */
+int bfpq_kv_append_dev(const void* k_new_dev, const void* v_new_dev, void* k_codes_dev, int8_t* k_exps_dev, void* v_codes_dev, int8_t* v_exps_dev,
+                       void* v_tail_dev, const int32_t* lens_dev, const int32_t* counts_dev, int32_t* overflow_dev, int64_t BH, int64_t heads,
+                       int64_t D, int64_t t, int64_t cap, int64_t limit, int64_t ldd, int dtype, int block_size, int mant_bits, double epsilon,
+                       const uint8_t* exp_win_dev, void* stream);
+int bfpq_kv_lens_advance(int32_t* lens_dev, const int32_t* counts_dev, int64_t B, int64_t t, int64_t limit, void* stream);
+/* bfpq_kv_bmm_dec with the cached length of head b read from lens_dev[b / heads] and a host bound that sizes the grid and the arrays:
+ *   BFPQ_KV_QK: Nout = max_len, 1 <= max_len <= w_bstride.  Column n < min(lens, max_len) of out [B, Tq, ldo] is the product, every
+ *               column from there to max_len is -inf (a softmax over the row ignores it).
+ *   BFPQ_KV_PV: Kx = L, the elements of a row of x, 1 <= L <= ldw; Nout = w_bstride = D <= 1024, B <= 65535.  Head b contracts over its
+ *               first min(lens, L) tokens; what x holds at or past that counts as zero, NaN and Inf included (the reference's zero pad,
+ *               bfp_ops.py:50-53); a sequence of length 0 gives zeros.  The contraction is split over workgroups: slices of
+ *               chunks_per_split 64-token chunks (1..16; 0: the library chooses) write each block's exact integer sum and x's block
+ *               exponents to ws_dev (16-byte aligned, ws_bytes >= bfpq_kv_dec_ws_bytes(B, Tq, D, L, block_size)), and a second launch
+ *               rescales and adds the blocks in block order: the fp32 additions of bfpq_kv_bmm_dec in its order, the same bits for
+ *               every chunks_per_split.
+ * Errors as bfpq_kv_bmm_dec; Nout or Kx of 0, a workspace too small or chunks_per_split > 16: BFPQ_E_UNSUPPORTED; lens_dev or (PV)
+ * ws_dev NULL or misaligned, a bad heads or a negative chunks_per_split: BFPQ_E_ARG; B or Tq of 0 returns 0.
+ * bfpq_kv_dec_ws_bytes: a negative error code for arguments the product refuses. */
+int64_t bfpq_kv_dec_ws_bytes(int64_t B, int64_t Tq, int64_t D, int64_t L, int block_size);
+int bfpq_kv_bmm_dec_dev(const void* x_dev, const void* wcodes_dev, const int8_t* wexp_dev, void* out_dev, const int32_t* lens_dev, int64_t B,
+                        int64_t heads, int64_t Tq, int64_t Kx, int64_t Nout, int64_t ldx, int64_t ldw, int64_t ldwe, int64_t w_bstride, int64_t ldo,
+                        int family, int dtype, int block_size, int x_mant_bits, int w_mant_bits, double epsilon, const uint8_t* exp_win_dev,
+                        void* ws_dev, int64_t ws_bytes, int64_t chunks_per_split, void* stream);
 /* ---- 2:4-compressed packed weights (format sp24) and their few-token product on v_smfmac_i32_16x16x64_i8 -------------------------
  * A weight pruned N:M with M = 4, N <= 2 along K (_structured_N_M_sparsity, reference bfp_ops.py:73-91) and quantized to HBFP block 64
  * holds at most 2 non-zero codes per group of 4.  sp24 keeps those two codes and their 2-bit positions, tiled for the decode kernel

@@ -1259,9 +1259,10 @@ def _gen_matmul_i8_op(bfp_args, matrix_unit):
         stats.fake_calls += 1
         return fake(x, w, *args, **kwargs)
 
-    def kv_cache(batch, heads, head_dim, capacity, dtype=torch.bfloat16, device='cuda'):
-        """an HBFPKVCache under this op's bfp_args; its products count in matmul_stats.cache_calls"""
-        return HBFPKVCache(batch, heads, head_dim, capacity, dtype=dtype, stats=stats, **dict(bfp_args, device=device))
+    def kv_cache(batch, heads, head_dim, capacity, dtype=torch.bfloat16, device='cuda', **mode):
+        """an HBFPKVCache under this op's bfp_args; its products count in matmul_stats.cache_calls.  mode: device_lengths=True (and
+        chunks_per_split) as HBFPKVCache takes them"""
+        return HBFPKVCache(batch, heads, head_dim, capacity, dtype=dtype, stats=stats, **mode, **dict(bfp_args, device=device))
 
     bfp_op.__name__ = fake.__name__
     bfp_op.matmul_stats = stats
@@ -1312,9 +1313,32 @@ class HBFPKVCache:
 
     Inference only: every call raises ValueError while gradients are recorded.  The length lives on the host (a Python int), so a decode
     step cannot be captured in a hipGraph: a replay would append at the captured position.  keys() / values() dequantize, for inspection
-    and tests."""
+    and tests.
 
-    def __init__(self, batch, heads, head_dim, capacity, dtype=torch.bfloat16, device='cuda', stats=None, **bfp_args):
+    device_lengths=True lifts that: the lengths live on the device, one per sequence, so the batch may be ragged and one
+    decode step -- append, scores, the caller's scale and softmax, context -- captured with torch.cuda.graph on one stream advances
+    correctly on every replay.  Then
+
+        cache.lengths                       # int32 [B] on the device, the only record of the lengths (cache.length raises)
+        cache.overflow                      # int32 [1]: set to 1, and left so until reset(), by an append that was refused
+        cache.append(k_new, v_new, counts)  # sequence b takes its first counts[b] (int32 [B] on the device, 0..t; None: all t) rows
+                                            # at lengths[b] ..; one that would pass `capacity`, or whose count is outside 0..t, is
+                                            # left untouched and raises `overflow`.  Returns None
+        cache.scores(q, max_len)            # [B, H, Tq, max_len], max_len a host int in 1..capacity (default: capacity): column
+                                            # n < lengths[b] is the product, every other column -inf.  A sequence longer than max_len
+                                            # is the caller's error: its columns past max_len are absent, nothing reports it
+        cache.context(p)                    # p [B, H, Tq, L], any 1 <= L <= capacity: sequence b contracts over its first
+                                            # min(lengths[b], L) tokens; p at or past lengths[b] counts as zero, NaN and Inf included
+
+    None of the three reads anything back, synchronises or allocates by a length: context()'s workspace is made once at construction
+    for max_query_rows rows of p (default 16: 4 B per row, cached token and column of V, i.e. a quarter of v_codes per row at block 64,
+    a sixteenth with max_query_rows=1, which is all a decode step needs; more rows than that raise ValueError).  Up to 16 dense rows of q / p only; more rows raise
+    ValueError, and so does in_sparsity at construction.  context() splits the tokens over workgroups (chunks_per_split 64-token chunks
+    per slice, 0: the library's choice) and adds the blocks in block order in a second launch: the same bits as the host-length cache
+    for any slice size.  keys(b) / values(b) read lengths[b] back, for inspection."""
+
+    def __init__(self, batch, heads, head_dim, capacity, dtype=torch.bfloat16, device='cuda', stats=None, device_lengths=False,
+                 chunks_per_split=0, max_query_rows=native.KV_DEC_MAX_TOKENS, **bfp_args):
         a = unpack_bfp_args(bfp_args)
         if bfp_args:
             raise TypeError(f"HBFPKVCache: unknown arguments {sorted(bfp_args)}")
@@ -1324,25 +1348,57 @@ class HBFPKVCache:
         if batch < 1 or heads < 1 or capacity < 1:
             raise ValueError(f"HBFPKVCache: batch, heads and capacity must be >= 1 (got {batch}, {heads}, {capacity})")
         self.args, self.act = a, native.ActSparsity.from_bfp_args(a)
+        self.device_lengths, self.chunks_per_split = bool(device_lengths), int(chunks_per_split)
+        if self.device_lengths and self.act is not None:
+            raise ValueError("HBFPKVCache(device_lengths=True): in_sparsity is not taken (q and p are quantized inside the product kernels)")
+        if not 0 <= self.chunks_per_split <= 16:
+            raise ValueError(f"HBFPKVCache: chunks_per_split must be 0..16 (got {chunks_per_split})")
+        if isinstance(max_query_rows, bool) or not isinstance(max_query_rows, int) or not 1 <= max_query_rows <= native.KV_DEC_MAX_TOKENS:
+            raise ValueError(f"HBFPKVCache: max_query_rows must be 1..{native.KV_DEC_MAX_TOKENS} (got {max_query_rows!r})")
+        self.max_query_rows = max_query_rows
         self.batch, self.heads, self.head_dim, self.capacity, self.dtype = batch, heads, head_dim, capacity, dtype
         self.block, self.mant_bits, self.epsilon = a['block_size'], a['mant_bits'], a['epsilon']
         self.cap = native.code_pitch(capacity)                   # tokens the buffers hold: a multiple of 64 and of the block
         if not native.kv_ok(head_dim, self.cap, self.block):
             raise ValueError(f"HBFPKVCache: head_dim {head_dim} x capacity {capacity} at block {self.block} is not taken")
         self.stats = stats if stats is not None else MatmulStats()
-        self.length = 0
+        self._length = 0
         B, H, D, cap, blk = batch, heads, head_dim, self.cap, self.block
         z = lambda *shape, dt=torch.int8: torch.zeros(shape, dtype=dt, device=device)
         self.buffers = dict(k_codes=z(B, H, cap, native.code_pitch(D)), k_exps=z(B, H, cap, D // blk), v_codes=z(B, H, D, cap),
                             v_exps=z(B, H, D, cap // blk), v_tail=z(B, H, blk, D, dt=dtype))
         for name, t in self.buffers.items():
             setattr(self, name, t)
+        if self.device_lengths:
+            self.lengths, self.overflow = z(B, dt=torch.int32), z(1, dt=torch.int32)
+            self._ws = self._workspace(max_query_rows)            # context()'s only workspace: made here, never grown
+
+    @property
+    def length(self):
+        if self.device_lengths:
+            raise AttributeError("HBFPKVCache(device_lengths=True) keeps no host length: read cache.lengths (int32 [B] on the device)")
+        return self._length
+
+    @length.setter
+    def length(self, value):
+        if self.device_lengths:
+            raise AttributeError("HBFPKVCache(device_lengths=True) keeps no host length: write cache.lengths (int32 [B] on the device)")
+        self._length = value
+
+    def _workspace(self, Tq):
+        """context()'s block sums for Tq query rows at any length up to the capacity"""
+        n = native.kv_dec_ws_bytes(self.batch * self.heads, Tq, self.head_dim, self.cap, self.block)
+        return torch.empty(n, dtype=torch.uint8, device=self.k_codes.device)
 
     def nbytes(self):
         return sum(t.numel() * t.element_size() for t in self.buffers.values())
 
     def reset(self):
-        self.length = 0
+        if self.device_lengths:
+            self.lengths.zero_()
+            self.overflow.zero_()
+        else:
+            self.length = 0
         self.v_codes.zero_()
 
     def _operand(self, x, what, last):
@@ -1355,12 +1411,28 @@ class HBFPKVCache:
             raise ValueError(f"HBFPKVCache.{what}: the cache holds {self.dtype} on {self.k_codes.device} (got {x.dtype} on {x.device})")
         return x.reshape(self.batch * self.heads, x.shape[2], last)
 
-    def append(self, k_new, v_new):
-        """k_new, v_new [B, H, t, D] become tokens length .. length + t - 1 (one launch for a prefill chunk or one token)"""
+    def _rows(self, what, Tq):
+        if Tq > native.KV_DEC_MAX_TOKENS:
+            raise ValueError(f"HBFPKVCache.{what}: device_lengths=True takes up to {native.KV_DEC_MAX_TOKENS} query rows (got {Tq})")
+
+    def append(self, k_new, v_new, counts=None):
+        """k_new, v_new [B, H, t, D] become tokens length .. length + t - 1 (one launch for a prefill chunk or one token).  With
+        device_lengths: per sequence, at lengths[b], the first counts[b] rows (the class docstring); two launches, returns None"""
         k, v = self._operand(k_new, 'append', self.head_dim), self._operand(v_new, 'append', self.head_dim)
         t = k.shape[1]
         if v.shape[1] != t:
             raise ValueError(f"HBFPKVCache.append: {t} keys and {v.shape[1]} values")
+        if not self.device_lengths and counts is not None:
+            raise ValueError("HBFPKVCache.append: counts needs device_lengths=True")
+        if self.device_lengths:
+            if t > self.cap:
+                raise ValueError(f"HBFPKVCache.append: a chunk of {t} tokens exceeds the buffers' {self.cap}")
+            if counts is not None and (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or counts.shape != (self.batch,)
+                                       or counts.device != self.k_codes.device or not counts.is_contiguous()):
+                raise ValueError(f"HBFPKVCache.append: counts must be a contiguous int32 tensor [{self.batch}] on {self.k_codes.device}")
+            native.kv_append_dev(k.contiguous(), v.contiguous(), self.k_codes, self.k_exps, self.v_codes, self.v_exps, self.v_tail, self.lengths,
+                                 counts, self.overflow, self.heads, self.capacity, self.block, self.mant_bits, self.epsilon)
+            return None
         if self.length + t > self.capacity:
             raise ValueError(f"HBFPKVCache.append: {self.length} + {t} tokens exceed the capacity {self.capacity}")
         native.kv_append(k.contiguous(), v.contiguous(), self.k_codes, self.k_exps, self.v_codes, self.v_exps, self.v_tail, self.length,
@@ -1371,9 +1443,20 @@ class HBFPKVCache:
     def _in_kernel(self, Tq):
         return self.act is None and Tq <= native.KV_DEC_MAX_TOKENS
 
-    def scores(self, q):
-        """q [B, H, Tq, D] -> [B, H, Tq, S]: Q_in(q) @ Q_w(K_all)^T"""
+    def scores(self, q, max_len=None):
+        """q [B, H, Tq, D] -> [B, H, Tq, S]: Q_in(q) @ Q_w(K_all)^T.  With device_lengths: [B, H, Tq, max_len], -inf from lengths[b] on"""
         x = self._operand(q, 'scores', self.head_dim)
+        if not self.device_lengths and max_len is not None:
+            raise ValueError("HBFPKVCache.scores: max_len needs device_lengths=True")
+        if self.device_lengths:
+            self._rows('scores', x.shape[1])
+            n = self.capacity if max_len is None else max_len
+            if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= self.capacity:
+                raise ValueError(f"HBFPKVCache.scores: max_len must be an int in 1..{self.capacity} (got {max_len!r})")
+            out = native.kv_bmm_dec_dev(x, self.k_codes, self.k_exps, native.KV_QK, n, self.cap, self.lengths, self.heads, self.block,
+                                        self.mant_bits, self.epsilon)
+            self.stats.cache_calls += 1
+            return out.unflatten(0, (self.batch, self.heads))
         S, D, BH, Tq, m = self.length, self.head_dim, x.shape[0], x.shape[1], self.mant_bits
         if S < 1:
             raise ValueError("HBFPKVCache.scores: the cache is empty")
@@ -1388,7 +1471,20 @@ class HBFPKVCache:
         return out.unflatten(0, (self.batch, self.heads))
 
     def context(self, p):
-        """p [B, H, Tq, S] -> [B, H, Tq, D]: Q_in(p) @ Q_w(V_all^T)^T, blocks along the S cached tokens (the last one zero-padded)"""
+        """p [B, H, Tq, S] -> [B, H, Tq, D]: Q_in(p) @ Q_w(V_all^T)^T, blocks along the S cached tokens (the last one zero-padded).  With
+        device_lengths: p [B, H, Tq, L], 1 <= L <= capacity, sequence b over its first min(lengths[b], L) tokens"""
+        if self.device_lengths:
+            if not isinstance(p, torch.Tensor) or p.dim() != 4 or not 1 <= p.shape[-1] <= self.capacity:
+                raise ValueError(f"HBFPKVCache.context takes p [..., L], 1 <= L <= {self.capacity} (got {tuple(getattr(p, 'shape', ()))})")
+            x = self._operand(p, 'context', p.shape[-1])
+            Tq = x.shape[1]
+            self._rows('context', Tq)
+            if Tq > self.max_query_rows:
+                raise ValueError(f"HBFPKVCache.context: {Tq} query rows, the workspace was made for max_query_rows={self.max_query_rows}")
+            out = native.kv_bmm_dec_dev(x, self.v_codes, self.v_exps, native.KV_PV, self.head_dim, self.head_dim, self.lengths, self.heads,
+                                        self.block, self.mant_bits, self.epsilon, ws=self._ws, chunks_per_split=self.chunks_per_split)
+            self.stats.cache_calls += 1
+            return out.unflatten(0, (self.batch, self.heads))
         if not isinstance(p, torch.Tensor) or p.dim() != 4 or p.shape[-1] != self.length or self.length < 1:
             raise ValueError(f"HBFPKVCache.context takes p [..., {self.length}], the cached length >= 1 (got {tuple(getattr(p, 'shape', ()))})")
         x = self._operand(p, 'context', self.length)
@@ -1408,21 +1504,33 @@ class HBFPKVCache:
         self.stats.cache_calls += 1
         return out.unflatten(0, (self.batch, self.heads))
 
-    def keys(self):
-        """the cached keys dequantized, [B, H, S, D]"""
-        BH, S, D = self.batch * self.heads, self.length, self.head_dim
-        c = self.k_codes.view(BH, self.cap, -1)[:, :S, :D].reshape(BH * S, D)
-        e = self.k_exps.view(BH, self.cap, -1)[:, :S].reshape(BH * S, D // self.block)
-        return native.dequantize(c, e, D, self.dtype, self.block, self.mant_bits, 8).view(self.batch, self.heads, S, D)
+    def _held(self, b):
+        """(first sequence, sequences, S) of keys() / values(): everything at the host length, or sequence b at lengths[b] (read back)"""
+        if not self.device_lengths:
+            if b is not None:
+                raise ValueError("HBFPKVCache.keys / values: a sequence index needs device_lengths=True")
+            return 0, self.batch, self.length
+        if isinstance(b, bool) or not isinstance(b, int) or not 0 <= b < self.batch:
+            raise ValueError(f"HBFPKVCache.keys / values: device_lengths=True takes a sequence index in 0..{self.batch - 1} (got {b!r})")
+        return b, 1, int(self.lengths[b].item())
 
-    def values(self):
-        """the cached values dequantized, [B, H, S, D]"""
-        BH, S, D, blk = self.batch * self.heads, self.length, self.head_dim, self.block
+    def keys(self, b=None):
+        """the cached keys dequantized, [B, H, S, D]; with device_lengths those of sequence b, [1, H, lengths[b], D]"""
+        b0, nb, S = self._held(b)
+        BH, D = nb * self.heads, self.head_dim
+        c = self.k_codes[b0:b0 + nb].view(BH, self.cap, -1)[:, :S, :D].reshape(BH * S, D)
+        e = self.k_exps[b0:b0 + nb].view(BH, self.cap, -1)[:, :S].reshape(BH * S, D // self.block)
+        return native.dequantize(c, e, D, self.dtype, self.block, self.mant_bits, 8).view(nb, self.heads, S, D)
+
+    def values(self, b=None):
+        """the cached values dequantized, [B, H, S, D]; with device_lengths those of sequence b, [1, H, lengths[b], D]"""
+        b0, nb, S = self._held(b)
+        BH, D, blk = nb * self.heads, self.head_dim, self.block
         Sp = (S + blk - 1) // blk * blk
-        c = self.v_codes.view(BH * D, self.cap)[:, :Sp].contiguous()
-        e = self.v_exps.view(BH * D, -1)[:, :Sp // blk].contiguous()
+        c = self.v_codes[b0:b0 + nb].view(BH * D, self.cap)[:, :Sp].contiguous()
+        e = self.v_exps[b0:b0 + nb].view(BH * D, -1)[:, :Sp // blk].contiguous()
         v = native.dequantize(c, e, Sp, self.dtype, blk, self.mant_bits, 8)[:, :S]
-        return v.reshape(self.batch, self.heads, D, S).transpose(-1, -2)
+        return v.reshape(nb, self.heads, D, S).transpose(-1, -2)
 
 
 def F_matmul_bfp(matrix_unit=False, **kwargs):

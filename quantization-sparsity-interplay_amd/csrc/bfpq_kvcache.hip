@@ -44,7 +44,7 @@ __device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b 
 template <int DT>
 __device__ __forceinline__ void v_block(const typename Traits<DT>::raw_t* __restrict__ vnew, typename Traits<DT>::raw_t* __restrict__ tail,
                                         int8_t* __restrict__ vcodes, int8_t* __restrict__ vexps, int bh, int tb, int d0, int D, int pos, int t,
-                                        int cap, int block, int mant_bits, float eps_dt, const uint8_t* s_win, uint32_t* s_val, uint32_t* s_max)
+                                        int tn, int cap, int block, int mant_bits, float eps_dt, const uint8_t* s_win, uint32_t* s_val, uint32_t* s_max)
 {
     using Tr = Traits<DT>;
     constexpr int VEC = Tr::VEC, LPR = kTD / VEC, RPP = 256 / LPR;
@@ -59,7 +59,7 @@ __device__ __forceinline__ void v_block(const typename Traits<DT>::raw_t* __rest
             const size_t to = ((size_t)bh * block + row) * D + d0 + col;
             if (s < pos) v = *reinterpret_cast<const uint4*>(tail + to);
             else if (s < pos + t) {
-                v = *reinterpret_cast<const uint4*>(vnew + ((size_t)bh * t + (s - pos)) * D + d0 + col);
+                v = *reinterpret_cast<const uint4*>(vnew + ((size_t)bh * tn + (s - pos)) * D + d0 + col);
                 if (open) *reinterpret_cast<uint4*>(tail + to) = v;
             }
         }
@@ -99,11 +99,24 @@ __device__ __forceinline__ void v_block(const typename Traits<DT>::raw_t* __rest
     }
 }
 
-template <int DT>
+// what sequence b of a device-length cache takes of a chunk of t rows: its position and count, or count -1 where it is refused (a count
+// outside 0..t, a length outside 0..limit, or tokens past limit): such a sequence is left as it is and the overflow flag is raised
+__device__ __forceinline__ int seq_take(const int32_t* __restrict__ lens, const int32_t* __restrict__ counts, int b, int t, int limit, int& pos)
+{
+    pos = lens[b];
+    const int n = counts ? counts[b] : t;
+    return (n < 0 || n > t || pos < 0 || pos > limit || n > limit - pos) ? -1 : n;
+}
+
+// DEV: the position and the count of head bh are those of its sequence bh / heads, read from device memory (lens, counts or null); t is
+// then the row pitch of k_new / v_new and the most a sequence can take, and the grid is sized for the worst position
+template <int DT, bool DEV>
 __global__ void __launch_bounds__(256) k_kv_append(const void* __restrict__ knew, const void* __restrict__ vnew, int8_t* __restrict__ kcodes,
                                                    int8_t* __restrict__ kexps, int8_t* __restrict__ vcodes, int8_t* __restrict__ vexps,
                                                    void* __restrict__ vtail, int BH, int D, int pos, int t, int cap, int ldd, int block,
-                                                   int mant_bits, float eps_dt, const uint8_t* __restrict__ exp_win, int nkb, int zc)
+                                                   int mant_bits, float eps_dt, const uint8_t* __restrict__ exp_win, int nkb, int zc,
+                                                   const int32_t* __restrict__ lens, const int32_t* __restrict__ counts,
+                                                   int32_t* __restrict__ overflow, int heads, int limit)
 {
     using Tr = Traits<DT>;
     using raw_t = typename Tr::raw_t;
@@ -123,6 +136,12 @@ __global__ void __launch_bounds__(256) k_kv_append(const void* __restrict__ knew
         const int seg = (int)(it % segs);
         const int64_t row = it / segs;                                    // bh * t + i
         const int bh = (int)(row / t), i = (int)(row % t);
+        bool live = valid;
+        if constexpr (DEV) {
+            const int n = seq_take(lens, counts, bh / heads, t, limit, pos);
+            if (n < 0 && valid && i == 0 && seg == 0) overflow[0] = 1;
+            live = valid && i < n;                                        // (one row: the lanes of a block are live together)
+        }
         const raw_t* const src = reinterpret_cast<const raw_t*>(knew) + (size_t)row * D + seg * 16;
         uint32_t raw[16], mx = 0;
 #pragma unroll
@@ -139,7 +158,7 @@ __global__ void __launch_bounds__(256) k_kv_append(const void* __restrict__ knew
             quant_elem<DT>(raw_to_f32<DT>(raw[e]), bs, false, 0.f, &c);
             pk[e >> 2] |= ((uint32_t)(int)c & 0xffu) << (8 * (e & 3));
         }
-        if (valid) {
+        if (live) {
             const size_t r = (size_t)bh * cap + pos + i;
             *reinterpret_cast<uint4*>(kcodes + r * ldd + seg * 16) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
             if (seg % per == 0) kexps[r * (D / block) + seg / per] = sat_exp(bs);
@@ -150,20 +169,28 @@ __global__ void __launch_bounds__(256) k_kv_append(const void* __restrict__ knew
     const int dtiles = (D + kTD - 1) / kTD;
     const int vb = (int)blockIdx.x - nkb;
     const int z = vb % zc, dt = (vb / zc) % dtiles, bh = vb / (zc * dtiles);
-    const int first = pos / block, last = (pos + t - 1) / block;
+    int cnt = t;
+    if constexpr (DEV) {
+        cnt = seq_take(lens, counts, bh / heads, t, limit, pos);
+        if (cnt <= 0) return;                                             // (the whole workgroup: nothing to take, or refused)
+    }
+    const int first = pos / block, last = (pos + cnt - 1) / block;
+    if (DEV && z > 0 && first + z >= last) return;                        // (a block the worst position has and this one has not)
     const int n = (z == 0 && last != first) ? 2 : 1;
     for (int it = 0; it < n; it++) {
         if (it) __syncthreads();                                          // (the first block's tile and tail rows have been read)
         v_block<DT>(reinterpret_cast<const raw_t*>(vnew), reinterpret_cast<raw_t*>(vtail), vcodes, vexps, bh, it ? last : first + z, dt * kTD, D,
-                    pos, t, cap, block, mant_bits, eps_dt, s_win, s_val, s_max);
+                    pos, cnt, t, cap, block, mant_bits, eps_dt, s_win, s_val, s_max);
     }
 }
 
 // ---- the decode product -----------------------------------------------------------------------------------------------------------
-template <int BLK, int DT, int TM>
+// DEV (family qk of a device-length cache): head b has min(lens[b / heads], Nout) keys, the rest of its row up to Nout is -inf
+template <int BLK, int DT, int TM, bool DEV>
 __global__ void __launch_bounds__(256) k_kv_bmm_dec(const void* __restrict__ x, const int8_t* __restrict__ wc, const int8_t* __restrict__ we,
                                                     void* __restrict__ out, int B, int Tq, int Kx, int Nout, int ldx, int ldw, int ldwe, int wbs,
-                                                    int ldo, int xm, int wm, float eps_dt, const uint8_t* __restrict__ exp_win)
+                                                    int ldo, int xm, int wm, float eps_dt, const uint8_t* __restrict__ exp_win,
+                                                    const int32_t* __restrict__ lens, int heads)
 {
     using Blk = I8Blk<BLK>;
     using op_t = typename Blk::op_t;
@@ -181,19 +208,39 @@ __global__ void __launch_bounds__(256) k_kv_bmm_dec(const void* __restrict__ x, 
     const bool tok = r < Tq;
 
     uint32_t offW[TM], ewo[TM][4];
+    auto rows = [&](int No) __attribute__((always_inline)) {
 #pragma unroll
-    for (int i = 0; i < TM; i++) {
-        const int n = n0 + 16 * i + r;
-        offW[i] = (uint32_t)(n < Nout ? n : Nout - 1) * (uint32_t)ldw + Blk::lane(q);
+        for (int i = 0; i < TM; i++) {
+            const int n = n0 + 16 * i + r;
+            offW[i] = (uint32_t)(n < No ? n : No - 1) * (uint32_t)ldw + Blk::lane(q);
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int ne = n0 + 16 * i + 4 * q + j;
-            ewo[i][j] = (uint32_t)(ne < Nout ? ne : Nout - 1) * (uint32_t)ldwe;
+            for (int j = 0; j < 4; j++) {
+                const int ne = n0 + 16 * i + 4 * q + j;
+                ewo[i][j] = (uint32_t)(ne < No ? ne : No - 1) * (uint32_t)ldwe;
+            }
         }
-    }
+    };
+    if constexpr (!DEV) rows(Nout);
     const v4i magic = {MAGIC_I, MAGIC_I, MAGIC_I, MAGIC_I};
+    const float ninf = -__builtin_inff();
 
     for (int b = blockIdx.y; b < B; b += gridDim.y) {
+        int No = Nout;
+        if constexpr (DEV) {
+            const int len = lens[b / heads];
+            No = len < Nout ? (len > 0 ? len : 0) : Nout;
+            if (n0 >= No) {                                      // (wave-uniform) none of this wave's keys exists
+                if (tok) {
+#pragma unroll
+                    for (int i = 0; i < TM; i++) {
+                        const int n = n0 + 16 * i + 4 * q;
+                        if (n < Nout) store4<DT>(out, ((size_t)b * Tq + r) * ldo + n, v2f{ninf, ninf}, v2f{ninf, ninf});
+                    }
+                }
+                continue;
+            }
+            rows(No);
+        }
         const int8_t* const wcb = wc + (size_t)b * wbs * ldw;
         const int8_t* const web = we + (size_t)b * wbs * ldwe;
         const raw_t* const xr = reinterpret_cast<const raw_t*>(x) + ((size_t)b * Tq + (tok ? r : 0)) * ldx;
@@ -288,10 +335,168 @@ __global__ void __launch_bounds__(256) k_kv_bmm_dec(const void* __restrict__ x, 
 #pragma unroll
             for (int i = 0; i < TM; i++) {
                 const int n = n0 + 16 * i + 4 * q;
+                if constexpr (DEV) {
+                    if (n + 0 >= No) acc[i][0].x = ninf;
+                    if (n + 1 >= No) acc[i][0].y = ninf;
+                    if (n + 2 >= No) acc[i][1].x = ninf;
+                    if (n + 3 >= No) acc[i][1].y = ninf;
+                }
                 if (n < Nout) store4<DT>(out, ((size_t)b * Tq + r) * ldo + n, acc[i][0], acc[i][1]);
             }
         }
     }
+}
+
+// ---- p v over a device-length cache, the contraction split over workgroups ------------------------------------------------------------
+// k_kv_pv_split: workgroup (64-column group of D, slice of kMaxCps or fewer 64-token chunks, head).  Head bh contracts over its first
+// Kx = min(lens[bh / heads], L) tokens; a workgroup whose slice starts at or past Kx returns at once.  Wave w first quantizes the chunks
+// w, w + 4, ... of the slice as k_kv_bmm_dec does (the lane map, the block maximum over a token's four lanes, block_scale / quant_elem;
+// elements at or past Kx are zeros whatever x holds there) into LDS, once for the four waves; then every wave multiplies the blocks of
+// the slice against its 16 columns of v_codes and writes the raw result of the block product -- the exact integer sum on top of the
+// MFMA's C operand MAGIC_I -- to sums [BH, Tq, nbw, D], and the first wave of a head x's block exponents to xexp [BH, Tq, nbw].
+// k_kv_pv_combine: a thread per four columns of one token runs rescale() of bfpq_i8mma.h over the blocks j < ceil(Kx / BLK) in block
+// order: the fp32 additions are those of k_kv_bmm_dec in the same order, so the result is the same bits whatever the slice size.
+constexpr int kMaxCps = 16;                               // chunks per slice (the LDS holds their codes)
+constexpr int64_t kSplitGrid = 2048;                      // workgroups the chosen slice size aims to stay within
+
+template <int BLK, int DT>
+__global__ void __launch_bounds__(256) k_kv_pv_split(const void* __restrict__ x, const int8_t* __restrict__ vc, int32_t* __restrict__ sums,
+                                                     int8_t* __restrict__ xexp, const int32_t* __restrict__ lens, int heads, int Tq, int L,
+                                                     int D, int ldx, int cap, int nbw, int cps, int xvec, int xm, float eps_dt,
+                                                     const uint8_t* __restrict__ exp_win)
+{
+    using Blk = I8Blk<BLK>;
+    using op_t = typename Blk::op_t;
+    using Tr = Traits<DT>;
+    using raw_t = typename Tr::raw_t;
+    constexpr int NBS = 64 / BLK, NE = BLK == 64 ? 16 : 8;
+    __shared__ uint8_t s_win[BFPQ_EXP_WIN_ENTRIES];
+    __shared__ op_t s_b[kMaxCps][NBS][64];
+    __shared__ int8_t s_e[kMaxCps][NBS][16];
+    const int bh = blockIdx.z, c0 = (int)blockIdx.y * cps;
+    const int len = lens[bh / heads];
+    const int Kx = len < L ? (len > 0 ? len : 0) : L;
+    if ((c0 << 6) >= Kx) return;                                 // (the whole workgroup, before any barrier)
+    for (int i = threadIdx.x; i < BFPQ_EXP_WIN_ENTRIES; i += 256) s_win[i] = exp_win[i];
+    __syncthreads();
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63, r = l & 15, q = l >> 4;
+    const int nb = (Kx + BLK - 1) / BLK, nch = (Kx + 63) >> 6, c1 = c0 + cps < nch ? c0 + cps : nch;
+    const bool tok = r < Tq;
+    const raw_t* const xr = reinterpret_cast<const raw_t*>(x) + ((size_t)bh * Tq + (tok ? r : 0)) * ldx;
+
+    for (int c = c0 + w; c < c1; c += 4) {
+#pragma unroll
+        for (int s = 0; s < NBS; s++) {
+            if (c * NBS + s >= nb) break;                        // (wave-uniform)
+            const int k0 = (c << 6) + s * BLK + Blk::lane(q);
+            uint32_t xv[NE], mx = 0;
+            if (xvec && k0 + NE <= L) {                          // rows 16-byte aligned: the lane's elements in 16-byte loads
+#pragma unroll
+                for (int v = 0; v < NE / Tr::VEC; v++) bfpq_dev::load_raw_vec<DT>(xr + k0, v, xv + v * Tr::VEC);
+            } else {
+#pragma unroll
+                for (int e = 0; e < NE; e++) xv[e] = k0 + e < L ? (uint32_t)xr[k0 + e] : 0u;
+            }
+#pragma unroll
+            for (int e = 0; e < NE; e++) {
+                if (!tok || k0 + e >= Kx) xv[e] = 0u;
+                mx = umax(mx, xv[e] & Tr::ABS);
+            }
+            mx = umax(mx, (uint32_t)__shfl_xor((int)mx, 16, 64));
+            mx = umax(mx, (uint32_t)__shfl_xor((int)mx, 32, 64));
+            const BlockScale bs = block_scale<DT>(mx, xm, eps_dt, s_win);
+            uint32_t pk[NE / 4];
+#pragma unroll
+            for (int e = 0; e < NE / 4; e++) pk[e] = 0u;
+#pragma unroll
+            for (int e = 0; e < NE; e++) {
+                float cd;
+                quant_elem<DT>(raw_to_f32<DT>(xv[e]), bs, false, 0.f, &cd);
+                pk[e >> 2] |= ((uint32_t)(int)cd & 0xffu) << (8 * (e & 3));
+            }
+            op_t bF;
+            if constexpr (BLK == 64) bF = v4i{(int)pk[0], (int)pk[1], (int)pk[2], (int)pk[3]};
+            else bF = (long)(((uint64_t)pk[1] << 32) | pk[0]);
+            s_b[c - c0][s][l] = bF;
+            if (q == 0) s_e[c - c0][s][r] = sat_exp(bs);
+        }
+    }
+    __syncthreads();
+
+    const int n0 = ((int)blockIdx.x * 4 + w) * 16;
+    if (n0 >= D) return;                                         // (wave-uniform; no barrier below.  D % 16 == 0: 16 whole columns)
+    const int8_t* const wrow = vc + ((size_t)bh * D + n0 + r) * cap + Blk::lane(q);
+    const v4i magic = {MAGIC_I, MAGIC_I, MAGIC_I, MAGIC_I};
+    const size_t o0 = ((size_t)bh * Tq + (tok ? r : 0)) * nbw;
+    for (int c = c0; c < c1; c++) {
+#pragma unroll
+        for (int s = 0; s < NBS; s++) {
+            const int j = c * NBS + s;
+            if (j >= nb) break;                                  // (wave-uniform)
+            op_t aF = *reinterpret_cast<const op_t*>(wrow + (c << 6) + s * BLK);
+            if (!Blk::a_live(q)) aF = op_t{};
+            const v4i d = Blk::mfma(aF, s_b[c - c0][s][l], magic);
+            if (tok) {
+                *reinterpret_cast<v4i*>(sums + (o0 + j) * D + n0 + 4 * q) = d;
+                if (n0 == 0 && q == 0) xexp[o0 + j] = s_e[c - c0][s][r];
+            }
+        }
+    }
+}
+
+template <int DT>
+__global__ void __launch_bounds__(256) k_kv_pv_combine(const int32_t* __restrict__ sums, const int8_t* __restrict__ xexp,
+                                                       const int8_t* __restrict__ ve, void* __restrict__ out, const int32_t* __restrict__ lens,
+                                                       int heads, int64_t total, int Tq, int L, int D, int ldve, int nbw, int ldo, int block,
+                                                       int xm, int wm)
+{
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int d4 = D >> 2, n = (int)(idx % d4) * 4;
+    const int64_t row = idx / d4;                                // bh * Tq + t
+    const int bh = (int)(row / Tq);
+    const int len = lens[bh / heads];
+    const int Kx = len < L ? (len > 0 ? len : 0) : L;
+    const int nb = (Kx + block - 1) / block;
+    const int32_t* const sr = sums + (size_t)row * nbw * D + n;
+    const int8_t* const xe = xexp + (size_t)row * nbw;
+    const int8_t* const we = ve + ((size_t)bh * D + n) * ldve;
+    v2f a01 = v2f{0.f, 0.f}, a23 = v2f{0.f, 0.f};
+    // the loads of kCU blocks are written ahead of their use; the additions stay in block order.  (Measured: no gain over the plain loop,
+    // 0.4-0.66 us per block and thread either way -- DESIGN 5k; this pass is what bounds context() now.)
+    constexpr int kCU = 8;
+    for (int j0 = 0; j0 < nb; j0 += kCU) {
+        v4i d[kCU];
+        int ex[kCU], ew[kCU][4];
+#pragma unroll
+        for (int u = 0; u < kCU; u++) {
+            const int j = j0 + u < nb ? j0 + u : nb - 1;
+            d[u] = *reinterpret_cast<const v4i*>(sr + (size_t)j * D);
+            ex[u] = (int)xe[j];
+#pragma unroll
+            for (int i = 0; i < 4; i++) ew[u][i] = (int)we[i * ldve + j];
+        }
+#pragma unroll
+        for (int u = 0; u < kCU; u++) {
+            if (j0 + u >= nb) break;
+            v2f sx, nm;
+            token_scale(ex[u], xm, sx, nm);
+            const v2f sw01 = v2f{pow2_scale(ew[u][0], wm), pow2_scale(ew[u][1], wm)};
+            const v2f sw23 = v2f{pow2_scale(ew[u][2], wm), pow2_scale(ew[u][3], wm)};
+            rescale(d[u], sx, nm, sw01, sw23, a01, a23);
+        }
+    }
+    store4<DT>(out, (size_t)row * ldo + n, a01, a23);
+}
+
+// lens[b] += what sequence b took of the chunk (seq_take: nothing where it was refused); after k_kv_append<.., true> in stream order
+__global__ void __launch_bounds__(256) k_kv_advance(int32_t* __restrict__ lens, const int32_t* __restrict__ counts, int B, int t, int limit)
+{
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    int pos;
+    const int n = seq_take(lens, counts, b, t, limit, pos);
+    if (n > 0) lens[b] = pos + n;
 }
 
 constexpr int64_t kLim = (int64_t)1 << 31;
@@ -322,9 +527,9 @@ int bfpq_kv_append(const void* k_new, const void* v_new, void* k_codes, int8_t* 
     if (nkb + nvb >= kLim) return BFPQ_E_UNSUPPORTED;
     const float eps_dt = bfpq_dev::h_round((float)epsilon, dtype);
     with_dtype(dtype, [&](auto dt) {
-        hipLaunchKernelGGL((k_kv_append<decltype(dt)::value>), dim3((unsigned)(nkb + nvb)), dim3(256), 0, (hipStream_t)stream, k_new, v_new,
+        hipLaunchKernelGGL((k_kv_append<decltype(dt)::value, false>), dim3((unsigned)(nkb + nvb)), dim3(256), 0, (hipStream_t)stream, k_new, v_new,
                            (int8_t*)k_codes, k_exps, (int8_t*)v_codes, v_exps, v_tail, (int)BH, (int)D, (int)pos, (int)t, (int)cap, (int)ldd,
-                           block_size, mant_bits, eps_dt, exp_win, (int)nkb, (int)zc);
+                           block_size, mant_bits, eps_dt, exp_win, (int)nkb, (int)zc, nullptr, nullptr, nullptr, 1, 0);
     });
     return (int)hipGetLastError();
 }
@@ -351,15 +556,125 @@ int bfpq_kv_bmm_dec(const void* x, const void* wcodes, const int8_t* wexp, void*
         with_dtype(dtype, [&](auto dt) {
             auto go = [&](auto tmc) {
                 constexpr int TM = decltype(tmc)::value;
-                hipLaunchKernelGGL((k_kv_bmm_dec<decltype(blk)::value, decltype(dt)::value, TM>), dim3((unsigned)((Nout + 64 * TM - 1) / (64 * TM)), gy),
-                                   dim3(256), 0, s, x, (const int8_t*)wcodes, wexp, out, (int)B, (int)Tq, (int)Kx, (int)Nout, (int)ldx, (int)ldw,
-                                   (int)ldwe, (int)w_bstride, (int)ldo, x_mant_bits, w_mant_bits, eps_dt, exp_win);
+                hipLaunchKernelGGL((k_kv_bmm_dec<decltype(blk)::value, decltype(dt)::value, TM, false>),
+                                   dim3((unsigned)((Nout + 64 * TM - 1) / (64 * TM)), gy), dim3(256), 0, s, x, (const int8_t*)wcodes, wexp, out, (int)B,
+                                   (int)Tq, (int)Kx, (int)Nout, (int)ldx, (int)ldw, (int)ldwe, (int)w_bstride, (int)ldo, x_mant_bits, w_mant_bits,
+                                   eps_dt, exp_win, nullptr, 1);
             };
             // rows per wave: 64 (32 at the small blocks) of the many cached keys, 16 of V's D columns
             if (family == BFPQ_KV_PV) go(std::integral_constant<int, 1>{});
             else if constexpr (decltype(blk)::value == 64) go(std::integral_constant<int, 4>{});
             else go(std::integral_constant<int, 2>{});
         });
+    });
+    return (int)hipGetLastError();
+}
+
+int bfpq_kv_append_dev(const void* k_new, const void* v_new, void* k_codes, int8_t* k_exps, void* v_codes, int8_t* v_exps, void* v_tail,
+                       const int32_t* lens, const int32_t* counts, int32_t* overflow, int64_t BH, int64_t heads, int64_t D, int64_t t,
+                       int64_t cap, int64_t limit, int64_t ldd, int dtype, int block_size, int mant_bits, double epsilon,
+                       const uint8_t* exp_win, void* stream)
+{
+    if (!dtype_ok(dtype) || !i8_block_ok(block_size) || !i8_mant_ok(mant_bits) || BH < 0 || t < 0 || heads < 1 || BH % heads != 0)
+        return BFPQ_E_ARG;
+    if (!bfpq_kv_ok(D, cap, block_size) || ldd < D || ldd % 64 != 0 || limit < 1 || limit > cap || t > cap || BH >= kLim)
+        return BFPQ_E_UNSUPPORTED;
+    if (BH == 0 || t == 0) return 0;
+    if (!k_new || !v_new || !k_codes || !k_exps || !v_codes || !v_exps || !v_tail || !lens || !overflow || !exp_win ||
+        !aligned16(k_new, v_new, k_codes, v_codes, v_tail) || ((reinterpret_cast<uintptr_t>(lens) | reinterpret_cast<uintptr_t>(counts) |
+                                                                 reinterpret_cast<uintptr_t>(overflow)) & 3u))
+        return BFPQ_E_ARG;
+    const int64_t nkb = (BH * t * (D / 16) + 255) / 256;
+    // the token blocks of V a chunk of t can touch at the worst position (its first token the last of a block)
+    const int64_t nblk = (t + block_size - 2) / block_size + 1, zc = nblk > 1 ? nblk - 1 : 1;
+    const int64_t nvb = BH * ((D + kTD - 1) / kTD) * zc;
+    if (nkb + nvb >= kLim) return BFPQ_E_UNSUPPORTED;
+    const float eps_dt = bfpq_dev::h_round((float)epsilon, dtype);
+    with_dtype(dtype, [&](auto dt) {
+        hipLaunchKernelGGL((k_kv_append<decltype(dt)::value, true>), dim3((unsigned)(nkb + nvb)), dim3(256), 0, (hipStream_t)stream, k_new, v_new,
+                           (int8_t*)k_codes, k_exps, (int8_t*)v_codes, v_exps, v_tail, (int)BH, (int)D, 0, (int)t, (int)cap, (int)ldd, block_size,
+                           mant_bits, eps_dt, exp_win, (int)nkb, (int)zc, lens, counts, overflow, (int)heads, (int)limit);
+    });
+    return (int)hipGetLastError();
+}
+
+int bfpq_kv_lens_advance(int32_t* lens, const int32_t* counts, int64_t B, int64_t t, int64_t limit, void* stream)
+{
+    if (B < 0 || t < 0 || limit < 1) return BFPQ_E_ARG;
+    if (B >= kLim || t >= kLim || limit >= kLim) return BFPQ_E_UNSUPPORTED;
+    if (B == 0 || t == 0) return 0;
+    if (!lens || ((reinterpret_cast<uintptr_t>(lens) | reinterpret_cast<uintptr_t>(counts)) & 3u)) return BFPQ_E_ARG;
+    hipLaunchKernelGGL(k_kv_advance, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, lens, counts, (int)B, (int)t, (int)limit);
+    return (int)hipGetLastError();
+}
+
+int64_t bfpq_kv_dec_ws_bytes(int64_t B, int64_t Tq, int64_t D, int64_t L, int block_size)
+{
+    if (!i8_block_ok(block_size) || B < 0 || Tq < 0 || D < 0 || L < 0) return BFPQ_E_ARG;
+    if (Tq > BFPQ_KV_DEC_MAX_TOKENS || D % 16 != 0 || D > 1024 || L >= kLim || B >= kLim) return BFPQ_E_UNSUPPORTED;
+    const int64_t nbw = (L + block_size - 1) / block_size;
+    return (B * Tq * nbw * (4 * D + 1) + 15) / 16 * 16;           // the int32 block sums, then x's block exponents
+}
+
+int bfpq_kv_bmm_dec_dev(const void* x, const void* wcodes, const int8_t* wexp, void* out, const int32_t* lens, int64_t B, int64_t heads,
+                        int64_t Tq, int64_t Kx, int64_t Nout, int64_t ldx, int64_t ldw, int64_t ldwe, int64_t w_bstride, int64_t ldo, int family,
+                        int dtype, int block_size, int x_mant_bits, int w_mant_bits, double epsilon, const uint8_t* exp_win, void* ws,
+                        int64_t ws_bytes, int64_t chunks_per_split, void* stream)
+{
+    if (!dtype_ok(dtype) || !i8_block_ok(block_size) || !i8_mant_ok(x_mant_bits) || !i8_mant_ok(w_mant_bits) ||
+        (family != BFPQ_KV_QK && family != BFPQ_KV_PV) || B < 0 || Tq < 0 || Nout < 0 || Kx < 0 || heads < 1 || B % heads != 0 ||
+        chunks_per_split < 0)
+        return BFPQ_E_ARG;
+    if (B == 0 || Tq == 0) return 0;
+    const int64_t nb = (Kx + block_size - 1) / block_size;
+    if (Tq > BFPQ_KV_DEC_MAX_TOKENS || Kx < 1 || Nout < 1 || (family == BFPQ_KV_QK ? Kx % block_size != 0 : (Nout % 16 != 0 || Nout > 1024)) ||
+        ldx < Kx || ldw % 64 != 0 || ldw < (Kx + 63) / 64 * 64 || ldwe < nb || w_bstride < Nout || ldo % 4 != 0 || ldo < Nout ||
+        w_bstride * ldw >= kLim || w_bstride * ldwe >= kLim || Tq * ldx >= kLim || Tq * ldo >= kLim || chunks_per_split > kMaxCps)
+        return BFPQ_E_UNSUPPORTED;
+    if (!x || !wcodes || !wexp || !out || !lens || !exp_win || !aligned16(wcodes, out) || (reinterpret_cast<uintptr_t>(lens) & 3u) ||
+        (reinterpret_cast<uintptr_t>(x) & (dtype == BFPQ_F32 ? 3u : 1u)))
+        return BFPQ_E_ARG;
+    const float eps_dt = bfpq_dev::h_round((float)epsilon, dtype);
+    hipStream_t s = (hipStream_t)stream;
+    if (family == BFPQ_KV_QK) {
+        const unsigned gy = (unsigned)(B < 65535 ? B : 65535);
+        with_block(block_size, [&](auto blk) {
+            with_dtype(dtype, [&](auto dt) {
+                constexpr int TM = decltype(blk)::value == 64 ? 4 : 2;
+                hipLaunchKernelGGL((k_kv_bmm_dec<decltype(blk)::value, decltype(dt)::value, TM, true>),
+                                   dim3((unsigned)((Nout + 64 * TM - 1) / (64 * TM)), gy), dim3(256), 0, s, x, (const int8_t*)wcodes, wexp, out, (int)B,
+                                   (int)Tq, (int)Kx, (int)Nout, (int)ldx, (int)ldw, (int)ldwe, (int)w_bstride, (int)ldo, x_mant_bits, w_mant_bits,
+                                   eps_dt, exp_win, lens, (int)heads);
+            });
+        });
+        return (int)hipGetLastError();
+    }
+    // p v: w_bstride == Nout == D rows per head (the sums are laid out by D)
+    const int64_t need = bfpq_kv_dec_ws_bytes(B, Tq, Nout, Kx, block_size);
+    if (w_bstride != Nout || B > 65535 || need < 0 || ws_bytes < need) return BFPQ_E_UNSUPPORTED;
+    if (!ws || !aligned16(ws)) return BFPQ_E_ARG;
+    const int64_t D = Nout, nch = (Kx + 63) / 64, dg = (D + 63) / 64;
+    int64_t cps = chunks_per_split;
+    if (cps == 0)                                                 // the shortest slices that keep the grid within kSplitGrid workgroups
+        for (cps = 1; cps < kMaxCps && (nch + cps - 1) / cps * dg * B > kSplitGrid; cps++) {}
+    const int64_t slices = (nch + cps - 1) / cps;
+    if (slices > 65535) return BFPQ_E_UNSUPPORTED;
+    int32_t* const sums = (int32_t*)ws;
+    int8_t* const xexp = (int8_t*)ws + B * Tq * nb * 4 * D;
+    const int xvec = (reinterpret_cast<uintptr_t>(x) & 15u) == 0 && (ldx * bfpq_dev::dtype_size(dtype)) % 16 == 0;
+    with_block(block_size, [&](auto blk) {
+        with_dtype(dtype, [&](auto dt) {
+            hipLaunchKernelGGL((k_kv_pv_split<decltype(blk)::value, decltype(dt)::value>), dim3((unsigned)dg, (unsigned)slices, (unsigned)B), dim3(256),
+                               0, s, x, (const int8_t*)wcodes, sums, xexp, lens, (int)heads, (int)Tq, (int)Kx, (int)D, (int)ldx, (int)ldw, (int)nb,
+                               (int)cps, xvec, x_mant_bits, eps_dt, exp_win);
+        });
+    });
+    int rc = (int)hipGetLastError();
+    if (rc) return rc;
+    const int64_t total = B * Tq * (D / 4);
+    with_dtype(dtype, [&](auto dt) {
+        hipLaunchKernelGGL((k_kv_pv_combine<decltype(dt)::value>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, sums, xexp, wexp, out, lens,
+                           (int)heads, total, (int)Tq, (int)Kx, (int)D, (int)ldwe, (int)nb, (int)ldo, block_size, x_mant_bits, w_mant_bits);
     });
     return (int)hipGetLastError();
 }

@@ -108,6 +108,10 @@ PROTOTYPES = {
     "bfpq_kv_ok": (_i32, [_i64, _i64, _i32]),
     "bfpq_kv_append": (_i32, [_vp] * 7 + [_i64] * 6 + [_i32, _i32, _i32, _dbl, _vp, _vp]),
     "bfpq_kv_bmm_dec": (_i32, [_vp, _vp, _vp, _vp] + [_i64] * 9 + [_i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp]),
+    "bfpq_kv_append_dev": (_i32, [_vp] * 10 + [_i64] * 7 + [_i32, _i32, _i32, _dbl, _vp, _vp]),
+    "bfpq_kv_lens_advance": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp]),
+    "bfpq_kv_dec_ws_bytes": (_i64, [_i64, _i64, _i64, _i64, _i32]),
+    "bfpq_kv_bmm_dec_dev": (_i32, [_vp] * 5 + [_i64] * 10 + [_i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _i64, _i64, _vp]),
 }
 
 
@@ -1385,6 +1389,31 @@ def kv_ok(D, cap, block_size):
     return bool(load_library().bfpq_kv_ok(int(D), int(cap), int(block_size)))
 
 
+def _kv_buffers(what, BH, D, block_size, k_codes, k_exps, v_codes, v_exps, v_tail, dev):
+    """the checks of kv_append on the five cache buffers; returns (cap, ldd)"""
+    if block_size not in (64,) + I8_BLOCKS:
+        raise ValueError(f"{what}: block_size must be 16, 32 or 64 (got {block_size})")
+    if k_codes.dim() < 2 or v_codes.dim() < 2:
+        raise ValueError(f"{what} takes k_codes [..., cap, ldd] and v_codes [..., D, cap]")
+    cap, ldd = k_codes.shape[-2], k_codes.shape[-1]
+    nbd, nbc = D // block_size, cap // block_size
+    sizes = dict(k_codes=(k_codes, BH * cap * ldd), k_exps=(k_exps, BH * cap * nbd), v_codes=(v_codes, BH * D * cap), v_exps=(v_exps, BH * D * nbc),
+                 v_tail=(v_tail, BH * block_size * D))
+    for name, (buf, numel) in sizes.items():
+        if buf.device != dev or not buf.is_contiguous() or buf.numel() != numel or (name != "v_tail" and buf.dtype != torch.int8):
+            raise ValueError(f"{what}: {name} must be contiguous on {dev} with {numel} elements"
+                             f"{'' if name == 'v_tail' else ' of int8'} (got {tuple(buf.shape)}, {buf.dtype}, {buf.device})")
+    if v_codes.shape[-1] != cap:
+        raise ValueError(f"{what} takes v_codes [..., D, cap] with k_codes' capacity")
+    return cap, ldd
+
+
+def _kv_int32(what, name, t, numel, dev):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != dev or not t.is_contiguous() or t.numel() != numel:
+        raise ValueError(f"{what}: {name} must be a contiguous int32 tensor of {numel} elements on {dev} "
+                         f"(got {tuple(getattr(t, 'shape', ()))}, {getattr(t, 'dtype', None)}, {getattr(t, 'device', None)})")
+
+
 def kv_append(k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, pos, block_size, mant_bits, epsilon):
     """k_new, v_new [BH, t, D] become tokens pos .. pos + t - 1 of the cache buffers (bfpq_kv_append: the layout is in include/bfpq.h);
     one launch for any t >= 1"""
@@ -1396,24 +1425,91 @@ def kv_append(k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, pos, block
                          f"{tuple(v_new.shape)} {v_new.dtype}, v_tail {v_tail.dtype})")
     BH, t, D = k_new.shape
     dev = k_new.device
-    if block_size not in (64,) + I8_BLOCKS:
-        raise ValueError(f"kv_append: block_size must be 16, 32 or 64 (got {block_size})")
-    if k_codes.dim() < 2 or v_codes.dim() < 2:
-        raise ValueError("kv_append takes k_codes [..., cap, ldd] and v_codes [..., D, cap]")
-    cap, ldd = k_codes.shape[-2], k_codes.shape[-1]
-    nbd, nbc = D // block_size, cap // block_size
-    sizes = dict(k_codes=(k_codes, BH * cap * ldd), k_exps=(k_exps, BH * cap * nbd), v_codes=(v_codes, BH * D * cap), v_exps=(v_exps, BH * D * nbc),
-                 v_tail=(v_tail, BH * block_size * D))
-    for name, (buf, numel) in sizes.items():
-        if buf.device != dev or not buf.is_contiguous() or buf.numel() != numel or (name != "v_tail" and buf.dtype != torch.int8):
-            raise ValueError(f"kv_append: {name} must be contiguous on {dev} with {numel} elements"
-                             f"{'' if name == 'v_tail' else ' of int8'} (got {tuple(buf.shape)}, {buf.dtype}, {buf.device})")
-    if v_codes.shape[-1] != cap or not k_new.is_contiguous() or not v_new.is_contiguous():
-        raise ValueError("kv_append takes contiguous k_new / v_new and v_codes [..., D, cap] with k_codes' capacity")
+    cap, ldd = _kv_buffers("kv_append", BH, D, block_size, k_codes, k_exps, v_codes, v_exps, v_tail, dev)
+    if not k_new.is_contiguous() or not v_new.is_contiguous():
+        raise ValueError("kv_append takes contiguous k_new / v_new")
     with torch.cuda.device(dev):
         check(load_library().bfpq_kv_append(_ptr(k_new), _ptr(v_new), _ptr(k_codes), _ptr(k_exps), _ptr(v_codes), _ptr(v_exps), _ptr(v_tail), BH, D,
                                             int(pos), t, cap, ldd, DTYPE_CODE[k_new.dtype], int(block_size), int(mant_bits), float(epsilon),
                                             _ptr(exp_window_dev(k_new.dtype, dev)), _stream(k_new)), "bfpq_kv_append")
+
+
+def kv_append_dev(k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, lengths, counts, overflow, heads, limit, block_size, mant_bits,
+                  epsilon):
+    """kv_append at the positions lengths [B] (int32, on the device) holds, sequence b = head // heads taking the first counts[b] of the t
+    rows (counts None: all), then lengths advanced by a second launch (bfpq_kv_append_dev, bfpq_kv_lens_advance).  A sequence that would
+    pass `limit` tokens is left untouched and overflow[0] set to 1.  Nothing is read back."""
+    require_device_tensor(k_new, "k_new")
+    require_device_tensor(v_new, "v_new")
+    require_device_tensor(v_tail, "v_tail")
+    if k_new.dim() != 3 or v_new.shape != k_new.shape or v_new.dtype != k_new.dtype or v_tail.dtype != k_new.dtype:
+        raise ValueError(f"kv_append_dev takes k_new and v_new [BH, t, D] of one dtype, the cache's (got {tuple(k_new.shape)} {k_new.dtype}, "
+                         f"{tuple(v_new.shape)} {v_new.dtype}, v_tail {v_tail.dtype})")
+    BH, t, D = k_new.shape
+    dev = k_new.device
+    heads = int(heads)
+    if heads < 1 or BH % heads:
+        raise ValueError(f"kv_append_dev: {BH} heads in all are no multiple of heads = {heads}")
+    cap, ldd = _kv_buffers("kv_append_dev", BH, D, block_size, k_codes, k_exps, v_codes, v_exps, v_tail, dev)
+    if not k_new.is_contiguous() or not v_new.is_contiguous():
+        raise ValueError("kv_append_dev takes contiguous k_new / v_new")
+    B = BH // heads
+    _kv_int32("kv_append_dev", "lengths", lengths, B, dev)
+    _kv_int32("kv_append_dev", "overflow", overflow, 1, dev)
+    if counts is not None:
+        _kv_int32("kv_append_dev", "counts", counts, B, dev)
+    with torch.cuda.device(dev):
+        L, stream = load_library(), _stream(k_new)
+        check(L.bfpq_kv_append_dev(_ptr(k_new), _ptr(v_new), _ptr(k_codes), _ptr(k_exps), _ptr(v_codes), _ptr(v_exps), _ptr(v_tail), _ptr(lengths),
+                                   _ptr(counts), _ptr(overflow), BH, heads, D, t, cap, int(limit), ldd, DTYPE_CODE[k_new.dtype], int(block_size),
+                                   int(mant_bits), float(epsilon), _ptr(exp_window_dev(k_new.dtype, dev)), stream), "bfpq_kv_append_dev")
+        check(L.bfpq_kv_lens_advance(_ptr(lengths), _ptr(counts), B, t, int(limit), stream), "bfpq_kv_lens_advance")
+
+
+def kv_dec_ws_bytes(BH, Tq, D, L, block_size):
+    """bytes of the workspace kv_bmm_dec_dev's KV_PV family needs (bfpq_kv_dec_ws_bytes; no device needed)"""
+    n = int(load_library().bfpq_kv_dec_ws_bytes(int(BH), int(Tq), int(D), int(L), int(block_size)))
+    if n < 0:
+        check(n, "bfpq_kv_dec_ws_bytes")
+    return n
+
+
+def kv_bmm_dec_dev(x, wc, we, family, bound, w_bstride, lengths, heads, block_size, mant_bits, epsilon, ws=None, chunks_per_split=0):
+    """kv_bmm_dec with head b's cached length read from lengths[b // heads] on the device (bfpq_kv_bmm_dec_dev).  KV_QK: x [BH, Tq, D],
+    bound = max_len; returns [BH, Tq, max_len], -inf from the length on.  KV_PV: x [BH, Tq, L], bound = D; returns [BH, Tq, D]; ws: a
+    uint8 tensor of at least kv_dec_ws_bytes(BH, Tq, D, L, block_size) bytes; chunks_per_split: 64-token chunks per slice of the
+    contraction, 0 = the library's choice (the result does not depend on it)."""
+    require_device_tensor(x, "x")
+    if x.dim() != 3:
+        raise ValueError(f"kv_bmm_dec_dev takes x [BH, Tq, Kx] (got {tuple(x.shape)})")
+    BH, Tq, Kx = x.shape
+    x = x.contiguous()
+    dev = x.device
+    heads = int(heads)
+    if heads < 1 or BH % heads:
+        raise ValueError(f"kv_bmm_dec_dev: {BH} heads in all are no multiple of heads = {heads}")
+    for name, buf in (("codes", wc), ("exponents", we)):
+        if buf.device != dev or buf.dtype != torch.int8 or not buf.is_contiguous() or buf.numel() < BH * int(w_bstride) * buf.shape[-1]:
+            raise ValueError(f"kv_bmm_dec_dev: the cached {name} must be contiguous int8 on {dev} with {BH} x {w_bstride} rows "
+                             f"(got {tuple(buf.shape)}, {buf.dtype}, {buf.device})")
+    _kv_int32("kv_bmm_dec_dev", "lengths", lengths, BH // heads, dev)
+    Nout = int(bound)
+    ws_bytes = 0
+    if family == KV_PV:
+        need = kv_dec_ws_bytes(BH, Tq, Nout, Kx, block_size)
+        if (not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or ws.device != dev or not ws.is_contiguous()
+                or ws.numel() < need):
+            raise ValueError(f"kv_bmm_dec_dev: ws must be a contiguous uint8 tensor of at least {need} bytes on {dev}")
+        ws_bytes = ws.numel()
+    ldo = (Nout + 3) // 4 * 4
+    with torch.cuda.device(dev):
+        out = torch.empty((BH, Tq, ldo), dtype=x.dtype, device=dev)
+        check(load_library().bfpq_kv_bmm_dec_dev(_ptr(x), _ptr(wc), _ptr(we), _ptr(out), _ptr(lengths), BH, heads, Tq, Kx, Nout, Kx, wc.shape[-1],
+                                                 we.shape[-1], int(w_bstride), ldo, int(family), DTYPE_CODE[x.dtype], int(block_size),
+                                                 int(mant_bits), int(mant_bits), float(epsilon), _ptr(exp_window_dev(x.dtype, dev)),
+                                                 _ptr(ws if family == KV_PV else None), ws_bytes, int(chunks_per_split), _stream(x)),
+              "bfpq_kv_bmm_dec_dev")
+    return out[:, :, :Nout] if ldo != Nout else out
 
 
 def kv_bmm_dec(x, wc, we, family, Nout, w_bstride, block_size, mant_bits, epsilon):
