@@ -7,6 +7,7 @@ scores, softmax, context; modeling_gpt2.py:345-348 with :207, 243) on one MI355X
   device the same step on HBFPKVCache(device_lengths=True): the lengths live on the device, so every replay of the captured step really
          advances (from S - 1 tokens on; the capacity is S plus the iters x (rounds + 1) + 2 tokens the run appends, scores over the
          whole capacity), context split over workgroups (--chunks-per-split, 0 = the library's choice),
+  attend the device leg's cache and replay with scores, scale, softmax and context as the one call cache.attend(q, scale),
 and, for the cache alone, the append of a prefill chunk of S tokens.  Method of bench_matmul.py: hipGraph replay, the median of the
 replays, the legs alternating round by round in one process.  (A captured append writes at the captured position: every replay redoes the
 same step, which is what is timed.)  On a tree without the cache the cache columns are null and "cache" says "absent".
@@ -34,8 +35,9 @@ OUT = os.path.join(ROOT, "bench_out", "kvcache.json")
 RAGGED = {"ragged8": (8, 12, (128, 695, 1262, 1829, 2396, 2963, 3530, 4096), 64)}
 
 
-def device_leg(i8, batch, heads, D, lens, k, v, q, dt, dev, iters, rounds, cps):
-    """(cache, step) of the device leg: sequence b prefilled to lens[b] - 1 tokens, room for every token the run appends"""
+def device_leg(i8, batch, heads, D, lens, k, v, q, dt, dev, iters, rounds, cps, attend=False):
+    """(cache, step) of the device leg: sequence b prefilled to lens[b] - 1 tokens, room for every token the run appends.  attend: the
+    same cache and step with cache.attend in place of scores, torch's scale and softmax, and context"""
     import torch
     room = iters * (rounds + 1) + 2                                      # replay_times: two warm-up calls, the capture, rounds + 1 replays
     cache = i8.kv_cache(batch, heads, D, max(lens) + room, dtype=dt, device=dev, device_lengths=True, chunks_per_split=cps, max_query_rows=1)
@@ -48,7 +50,17 @@ def device_leg(i8, batch, heads, D, lens, k, v, q, dt, dev, iters, rounds, cps):
         p = torch.softmax(cache.scores(q).float() * scale, dim=-1).to(dt)
         return cache.context(p)
 
-    return cache, step
+    def attend_step():
+        cache.append(k_new, v_new)
+        return cache.attend(q, scale)
+
+    if attend:
+        cache.prepare_attend()
+    return cache, (attend_step if attend else step)
+
+
+def has_attend(bfp_ops):
+    return hasattr(bfp_ops.HBFPKVCache, 'attend')
 
 
 def run_ragged(name, iters, rounds, out, cps):
@@ -67,16 +79,44 @@ def run_ragged(name, iters, rounds, out, cps):
             i8 = bfp_ops.F_matmul_bfp(matrix_unit='int8', **bfpq.BFPConfig.hbfp(c['mant_bits'] + 1, c['block_size']).to_kwargs())
             with torch.no_grad():
                 cache, step = device_leg(i8, batch, heads, D, lens, k, v, q, dt, dev, iters, rounds, cps)
-                med, spread = replay_times([step], iters, rounds)
+                fns, acache = [step], None
+                if has_attend(bfp_ops):
+                    acache, astep = device_leg(i8, batch, heads, D, lens, k, v, q, dt, dev, iters, rounds, cps, attend=True)
+                    fns.append(astep)
+                med, spread = replay_times(fns, iters, rounds)
                 last = cache.lengths.tolist()
-            assert cache.overflow.item() == 0
+            assert cache.overflow.item() == 0 and (acache is None or (acache.overflow.item() == 0 and acache.lengths.tolist() == last))
             row = dict(shape=name, batch=batch, heads=heads, lengths=list(lens), lengths_at_end=last, head_dim=D, dtype=dname, config=cname,
-                       iters=iters, rounds=rounds, chunks_per_split=cps, device_us=med[0], device_min_max_us=spread[0])
+                       iters=iters, rounds=rounds, chunks_per_split=cps, device_us=med[0], device_min_max_us=spread[0],
+                       attend_us=med[1] if acache is not None else None, attend_min_max_us=spread[1] if acache is not None else None)
             rows.append(row)
             print(json.dumps(row), flush=True)
     os.makedirs(os.path.dirname(out), exist_ok=True)
     old = json.load(open(out)) if os.path.exists(out) else []
     json.dump(old + rows, open(out, "w"), indent=1)
+
+
+def run_attend_only(shape, iters, rounds, out, cps):
+    """the attend leg alone, bf16 at block 64: what a kernel trace of one step is taken from (--attend-only)"""
+    import torch
+    import quantization_sparsity_interplay_amd as bfpq
+    from quantization_sparsity_interplay_amd.bfp import bfp_ops
+    dev, dt = "cuda:0", torch.bfloat16
+    batch, heads, S, D = SHAPES[shape]
+    g = torch.Generator().manual_seed(1)
+    k, v = (torch.randn(batch, heads, S, D, generator=g).to(dt).to(dev) for _ in range(2))
+    q = torch.randn(batch, heads, 1, D, generator=g).to(dt).to(dev)
+    c = CONFIGS["hbfp8_b64"]
+    i8 = bfp_ops.F_matmul_bfp(matrix_unit='int8', **bfpq.BFPConfig.hbfp(c['mant_bits'] + 1, c['block_size']).to_kwargs())
+    with torch.no_grad():
+        cache, step = device_leg(i8, batch, heads, D, [S] * batch, k, v, q, dt, dev, iters, rounds, cps, attend=True)
+        med, spread = replay_times([step], iters, rounds)
+    assert cache.overflow.item() == 0
+    row = dict(shape=shape, batch=batch, heads=heads, S=S, head_dim=D, dtype="bf16", config="hbfp8_b64", iters=iters, rounds=rounds,
+               chunks_per_split=cps, attend_us=med[0], attend_min_max_us=spread[0], lengths_at_end=cache.lengths.tolist())
+    print(json.dumps(row), flush=True)
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    json.dump((json.load(open(out)) if os.path.exists(out) else []) + [row], open(out, "w"), indent=1)
 
 
 def run_case(shape, iters, rounds, out, prefill_too=True, cps=0):
@@ -119,14 +159,21 @@ def run_case(shape, iters, rounds, out, prefill_too=True, cps=0):
 
             with torch.no_grad():
                 fns = [lambda: cat_step(fake)] + ([lambda: cat_step(i8)] if stats is not None else [])
-                dcache = None
+                dcache = acache = None
                 if cache is not None:
                     cache.append(past_k, past_v)
                     fns.append(cache_step)
                     if 'device_lengths' in (bfp_ops.HBFPKVCache.__init__.__code__.co_varnames):
                         dcache, dstep = device_leg(i8, batch, heads, D, [S] * batch, k, v, q, dt, dev, iters, rounds, cps)
                         fns.append(dstep)
+                        if has_attend(bfp_ops):
+                            acache, astep = device_leg(i8, batch, heads, D, [S] * batch, k, v, q, dt, dev, iters, rounds, cps, attend=True)
+                            fns.append(astep)
                 med, spread = replay_times(fns, iters, rounds)
+                att_us = att_spread = None
+                if acache is not None:
+                    assert acache.overflow.item() == 0 and acache.lengths.tolist() == dcache.lengths.tolist()
+                    att_us, att_spread = med.pop(), spread.pop()
                 if dcache is not None:
                     assert dcache.overflow.item() == 0
                     dev_us, dev_spread, dev_end = med.pop(), spread.pop(), dcache.lengths.tolist()
@@ -139,7 +186,7 @@ def run_case(shape, iters, rounds, out, prefill_too=True, cps=0):
                        cache_min_max_us=spread[-1] if cache is not None else None,
                        device="ran" if dcache is not None else "absent", device_us=dev_us if dcache is not None else None,
                        device_min_max_us=dev_spread if dcache is not None else None, device_lengths_at_end=dev_end if dcache is not None else None,
-                       chunks_per_split=cps if dcache is not None else None,
+                       chunks_per_split=cps if dcache is not None else None, attend_us=att_us, attend_min_max_us=att_spread,
                        prefill_append_us=pre[0][0] if pre else None, cache_bytes=cache.nbytes() if cache is not None else None,
                        kv_bytes=2 * k.numel() * k.element_size())
             rows.append(row)
@@ -173,6 +220,7 @@ def main():
     ap.add_argument("--out", default=OUT, help="JSON file the rows are appended to")
     ap.add_argument("--parent-json", help="this script's output on the parent commit: its two legs are added to every row of --out")
     ap.add_argument("--skip-prefill", action="store_true", help="with --case: do not time the prefill append (a kernel trace of the decode step alone)")
+    ap.add_argument("--attend-only", action="store_true", help="with --case: the attend leg alone, bf16 at block 64 (a kernel trace of one attend step)")
     ap.add_argument("--merge-only", action="store_true", help="run nothing: add --parent-json to an existing --out file")
     a = ap.parse_args()
     out = os.path.abspath(a.out)
@@ -180,6 +228,8 @@ def main():
         return merge_parent(out, a.parent_json)
     if a.case in RAGGED:
         return run_ragged(a.case, a.iters, a.rounds, out, a.chunks_per_split)
+    if a.case and a.attend_only:
+        return run_attend_only(a.case, a.iters, a.rounds, out, a.chunks_per_split)
     if a.case:
         return run_case(a.case, a.iters, a.rounds, out, not a.skip_prefill, a.chunks_per_split)
     if os.path.exists(out):

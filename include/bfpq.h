@@ -502,6 +502,29 @@ int bfpq_kv_bmm_dec_dev(const void* x_dev, const void* wcodes_dev, const int8_t*
                         int64_t heads, int64_t Tq, int64_t Kx, int64_t Nout, int64_t ldx, int64_t ldw, int64_t ldwe, int64_t w_bstride, int64_t ldo,
                         int family, int dtype, int block_size, int x_mant_bits, int w_mant_bits, double epsilon, const uint8_t* exp_win_dev,
                         void* ws_dev, int64_t ws_bytes, int64_t chunks_per_split, void* stream);
+/* One attention call on the device-length cache: scores, scale, softmax and context of a decode step (reference modeling_gpt2.py:207-243:
+ * the matmul of q and K^T, the scale, the causal mask, the softmax and the matmul with V) in three launches, no array of the dtype with
+ * a row per cached token in between.  q [BH, Tq, D] of dtype (dense), out [BH, Tq, ldo] of dtype (D per row, ldo % 4 == 0); the cache
+ * arrays, lens_dev and heads as above, max_len (1..cap) as bfpq_kv_bmm_dec_dev's BFPQ_KV_QK bound.  The result is that of
+ *   s = bfpq_kv_bmm_dec_dev(BFPQ_KV_QK, q), widened to fp32 and multiplied by (float)scale (scale finite; else BFPQ_E_ARG);
+ *   row t of head b sees the keys n < min(lens, max_len), with causal = 1 only n <= lens - Tq + t (the rows are the last Tq tokens held);
+ *   p = softmax over the keys the row sees, in fp32 -- the maximum (NaN propagates), expf(s - max), the sum in an order that depends on
+ *       the row alone, a division -- rounded once to dtype, +0 at every other key;
+ *   out = bfpq_kv_bmm_dec_dev(BFPQ_KV_PV, p) bit for bit, for every chunks_per_split.
+ * An empty sequence gives zeros; a row that sees no key of a sequence that holds some (causal with Tq > lens) has a p of zeros and
+ * gives what BFPQ_KV_PV gives for it.  p_dev, if not NULL: [BH, Tq, ldp] of dtype
+ * (ldp >= max_len) receives p, columns 0 .. max_len - 1 of every row.  score_ws_dev: the fp32 score rows, 16-byte aligned,
+ * score_ws_bytes >= bfpq_kv_attend_ws_bytes(BH, Tq, max_len) = 4 BH Tq (max_len rounded up to 4), rounded up to 16 (no device needed;
+ * a negative size: BFPQ_E_ARG, Tq > BFPQ_KV_DEC_MAX_TOKENS or a size of 2^31 or more: BFPQ_E_UNSUPPORTED); sum_ws_dev: the workspace of
+ * bfpq_kv_bmm_dec_dev's BFPQ_KV_PV family, sum_ws_bytes >= bfpq_kv_dec_ws_bytes(BH, Tq, D, max_len, block_size).  Errors as
+ * bfpq_kv_bmm_dec_dev; causal not 0 or 1: BFPQ_E_ARG; max_len outside 1..cap, BH > 65535, ldp < max_len or a workspace too small:
+ * BFPQ_E_UNSUPPORTED; BH or Tq of 0 returns 0.  Nothing is read back. */
+int64_t bfpq_kv_attend_ws_bytes(int64_t BH, int64_t Tq, int64_t max_len);
+int bfpq_kv_attend(const void* q_dev, const void* k_codes_dev, const int8_t* k_exps_dev, const void* v_codes_dev, const int8_t* v_exps_dev,
+                   void* out_dev, void* p_dev, const int32_t* lens_dev, int64_t BH, int64_t heads, int64_t Tq, int64_t D, int64_t max_len,
+                   int64_t cap, int64_t ldd, int64_t ldo, int64_t ldp, double scale, int causal, int dtype, int block_size, int x_mant_bits,
+                   int w_mant_bits, double epsilon, const uint8_t* exp_win_dev, void* score_ws_dev, int64_t score_ws_bytes, void* sum_ws_dev,
+                   int64_t sum_ws_bytes, int64_t chunks_per_split, void* stream);
 /* ---- 2:4-compressed packed weights (format sp24) and their few-token product on v_smfmac_i32_16x16x64_i8 -------------------------
  * A weight pruned N:M with M = 4, N <= 2 along K (_structured_N_M_sparsity, reference bfp_ops.py:73-91) and quantized to HBFP block 64
  * holds at most 2 non-zero codes per group of 4.  sp24 keeps those two codes and their 2-bit positions, tiled for the decode kernel

@@ -12,6 +12,8 @@ Differences from the reference, all documented in DESIGN.md:
 """
 import collections
 import contextlib
+import math
+import numbers
 import threading
 
 import torch
@@ -1335,7 +1337,20 @@ class HBFPKVCache:
     a sixteenth with max_query_rows=1, which is all a decode step needs; more rows than that raise ValueError).  Up to 16 dense rows of q / p only; more rows raise
     ValueError, and so does in_sparsity at construction.  context() splits the tokens over workgroups (chunks_per_split 64-token chunks
     per slice, 0: the library's choice) and adds the blocks in block order in a second launch: the same bits as the host-length cache
-    for any slice size.  keys(b) / values(b) read lengths[b] back, for inspection."""
+    for any slice size.  keys(b) / values(b) read lengths[b] back, for inspection.
+
+    The whole step after the append is one call there:
+
+        ctx = cache.attend(q, scale, max_len=None, causal=False)                     # [B, H, Tq, D]
+        ctx, p = cache.attend(q, scale, max_len=None, causal=False, return_probs=True)   # p [B, H, Tq, max_len]
+
+    equal to context(p) of p = softmax(scores(q, max_len).float() * scale, -1).to(dtype), in three launches and with no [.., S] array of
+    the dtype in between: the scores reach the softmax as scores() rounds them, times float(scale) in fp32; the softmax runs in fp32
+    (maximum, expf, a sum whose order depends on the row alone, a division) and is rounded once; from p on the bits are context(p)'s for
+    every chunks_per_split.  causal=True takes the Tq rows to be the last Tq tokens held: row t sees the keys n <= lengths[b] - Tq + t.
+    Keys a row does not see are exactly +0 in p; an empty sequence gives a zero context row, and a row that sees no key of a sequence
+    that holds some (causal with Tq > lengths[b]) what context() makes of a p of zeros.  The fp32 score rows [B H, max_query_rows, cap] are a workspace made by the first attend() or by prepare_attend() --
+    call either before capturing a graph -- and never grown; caches that never attend never hold it."""
 
     def __init__(self, batch, heads, head_dim, capacity, dtype=torch.bfloat16, device='cuda', stats=None, device_lengths=False,
                  chunks_per_split=0, max_query_rows=native.KV_DEC_MAX_TOKENS, **bfp_args):
@@ -1372,6 +1387,7 @@ class HBFPKVCache:
         if self.device_lengths:
             self.lengths, self.overflow = z(B, dt=torch.int32), z(1, dt=torch.int32)
             self._ws = self._workspace(max_query_rows)            # context()'s only workspace: made here, never grown
+            self._att_ws = None                                   # attend()'s fp32 score rows: made by its first call
 
     @property
     def length(self):
@@ -1503,6 +1519,37 @@ class HBFPKVCache:
             out = native.hbfp_bmm_i8_strided(xq, self.v_codes, self.v_exps, BH, Tq, D, Sp, D, D, m, m, block_size=blk, out_dtype=self.dtype)
         self.stats.cache_calls += 1
         return out.unflatten(0, (self.batch, self.heads))
+
+    def prepare_attend(self):
+        """make attend()'s workspace now (the fp32 score rows of max_query_rows rows over the whole capacity); it is never grown"""
+        if not self.device_lengths:
+            raise ValueError("HBFPKVCache.attend needs device_lengths=True")
+        if self._att_ws is None:
+            n = native.kv_attend_ws_bytes(self.batch * self.heads, self.max_query_rows, self.cap)
+            self._att_ws = torch.empty(n, dtype=torch.uint8, device=self.k_codes.device)
+
+    def attend(self, q, scale, max_len=None, causal=False, return_probs=False):
+        """q [B, H, Tq, D] -> the context [B, H, Tq, D] of softmax(scores(q, max_len) * scale) (the class docstring); with return_probs
+        also p [B, H, Tq, max_len].  device_lengths only; two products, three launches"""
+        if not self.device_lengths:
+            raise ValueError("HBFPKVCache.attend needs device_lengths=True")
+        x = self._operand(q, 'attend', self.head_dim)
+        Tq = x.shape[1]
+        self._rows('attend', Tq)
+        if Tq > self.max_query_rows:
+            raise ValueError(f"HBFPKVCache.attend: {Tq} query rows, the workspaces were made for max_query_rows={self.max_query_rows}")
+        if isinstance(scale, bool) or not isinstance(scale, numbers.Real) or not math.isfinite(scale) or abs(scale) > torch.finfo(torch.float32).max:
+            raise ValueError(f"HBFPKVCache.attend: scale must be a finite real number (in fp32; got {scale!r})")
+        n = self.capacity if max_len is None else max_len
+        if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= self.capacity:
+            raise ValueError(f"HBFPKVCache.attend: max_len must be an int in 1..{self.capacity} (got {max_len!r})")
+        self.prepare_attend()
+        out, p = native.kv_attend(x, self.k_codes, self.k_exps, self.v_codes, self.v_exps, self.lengths, self.heads, n, float(scale), bool(causal),
+                                  self.block, self.mant_bits, self.epsilon, self._att_ws, self._ws, chunks_per_split=self.chunks_per_split,
+                                  return_probs=bool(return_probs))
+        self.stats.cache_calls += 2
+        out = out.unflatten(0, (self.batch, self.heads))
+        return (out, p.unflatten(0, (self.batch, self.heads))) if return_probs else out
 
     def _held(self, b):
         """(first sequence, sequences, S) of keys() / values(): everything at the host length, or sequence b at lengths[b] (read back)"""

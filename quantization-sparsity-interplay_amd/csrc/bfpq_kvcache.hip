@@ -24,6 +24,11 @@
 // k_bmm_i8's bit for bit.  Rows past Nout repeat the last row (never stored); a lane stores four consecutive n of one token, so the
 // output has a pitch ldo (a multiple of 4).  The next 64-byte chunk of w, its exponents and x's elements are loaded before the current
 // one is multiplied.  No split of the contraction: pv at batch 1 runs B H D / 64 workgroups.
+//
+// bfpq_kv_attend: scores, scale, softmax and context of one decode step in three launches.  k_kv_bmm_dec<.., ATT> leaves the
+// scores -- rounded to the dtype, widened, times the scale -- as fp32 rows in a workspace; k_kv_pv_split<.., true> reads them, every
+// workgroup of a head reducing the head's rows to the same maximum and sum before it forms, rounds and quantizes the probabilities of
+// its own slice in registers; k_kv_pv_combine is the one context() runs.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "bfpq.h"
@@ -185,17 +190,31 @@ __global__ void __launch_bounds__(256) k_kv_append(const void* __restrict__ knew
 }
 
 // ---- the decode product -----------------------------------------------------------------------------------------------------------
-// DEV (family qk of a device-length cache): head b has min(lens[b / heads], Nout) keys, the rest of its row up to Nout is -inf
-template <int BLK, int DT, int TM, bool DEV>
+// MODE kDev (family qk of a device-length cache): head b has min(lens[b / heads], Nout) keys, the rest of its row up to Nout is -inf.
+// MODE kAtt: that, with out an fp32 array: what a softmax over the row takes -- the score rounded to the dtype, widened and multiplied
+// by `scale`, -inf from the row's visible length on (att_visible)
+constexpr int kHost = 0, kDev = 1, kAtt = 2;
+
+// keys that query row t of Tq sees of a head of `len` tokens, Kx = min(len, max_len) of them in reach: all, or (causal, the rows being
+// the last Tq tokens held) those up to its own
+__device__ __forceinline__ int att_visible(int len, int Kx, int Tq, int t, int causal)
+{
+    const int v = causal ? len - Tq + t + 1 : len;
+    return v < Kx ? (v > 0 ? v : 0) : Kx;
+}
+
+template <int BLK, int DT, int TM, int MODE>
 __global__ void __launch_bounds__(256) k_kv_bmm_dec(const void* __restrict__ x, const int8_t* __restrict__ wc, const int8_t* __restrict__ we,
                                                     void* __restrict__ out, int B, int Tq, int Kx, int Nout, int ldx, int ldw, int ldwe, int wbs,
                                                     int ldo, int xm, int wm, float eps_dt, const uint8_t* __restrict__ exp_win,
-                                                    const int32_t* __restrict__ lens, int heads)
+                                                    const int32_t* __restrict__ lens, int heads, float scale, int causal)
 {
     using Blk = I8Blk<BLK>;
     using op_t = typename Blk::op_t;
     using Tr = Traits<DT>;
     using raw_t = typename Tr::raw_t;
+    constexpr bool DEV = MODE != kHost;
+    constexpr int ODT = MODE == kAtt ? BFPQ_F32 : DT;            // the output's element type
     constexpr int NBS = 64 / BLK;                                // blocks per 64-byte chunk
     constexpr int NE = BLK == 64 ? 16 : 8;                       // a lane's bytes of a block
     __shared__ uint8_t s_win[BFPQ_EXP_WIN_ENTRIES];
@@ -225,16 +244,16 @@ __global__ void __launch_bounds__(256) k_kv_bmm_dec(const void* __restrict__ x, 
     const float ninf = -__builtin_inff();
 
     for (int b = blockIdx.y; b < B; b += gridDim.y) {
-        int No = Nout;
+        int No = Nout, len = 0;
         if constexpr (DEV) {
-            const int len = lens[b / heads];
+            len = lens[b / heads];
             No = len < Nout ? (len > 0 ? len : 0) : Nout;
             if (n0 >= No) {                                      // (wave-uniform) none of this wave's keys exists
                 if (tok) {
 #pragma unroll
                     for (int i = 0; i < TM; i++) {
                         const int n = n0 + 16 * i + 4 * q;
-                        if (n < Nout) store4<DT>(out, ((size_t)b * Tq + r) * ldo + n, v2f{ninf, ninf}, v2f{ninf, ninf});
+                        if (n < Nout) store4<ODT>(out, ((size_t)b * Tq + r) * ldo + n, v2f{ninf, ninf}, v2f{ninf, ninf});
                     }
                 }
                 continue;
@@ -335,13 +354,19 @@ __global__ void __launch_bounds__(256) k_kv_bmm_dec(const void* __restrict__ x, 
 #pragma unroll
             for (int i = 0; i < TM; i++) {
                 const int n = n0 + 16 * i + 4 * q;
-                if constexpr (DEV) {
+                if constexpr (MODE == kAtt) {
+                    const int vis = att_visible(len, No, Tq, r, causal);
+                    acc[i][0].x = n + 0 < vis ? rnd<DT>(acc[i][0].x) * scale : ninf;
+                    acc[i][0].y = n + 1 < vis ? rnd<DT>(acc[i][0].y) * scale : ninf;
+                    acc[i][1].x = n + 2 < vis ? rnd<DT>(acc[i][1].x) * scale : ninf;
+                    acc[i][1].y = n + 3 < vis ? rnd<DT>(acc[i][1].y) * scale : ninf;
+                } else if constexpr (DEV) {
                     if (n + 0 >= No) acc[i][0].x = ninf;
                     if (n + 1 >= No) acc[i][0].y = ninf;
                     if (n + 2 >= No) acc[i][1].x = ninf;
                     if (n + 3 >= No) acc[i][1].y = ninf;
                 }
-                if (n < Nout) store4<DT>(out, ((size_t)b * Tq + r) * ldo + n, acc[i][0], acc[i][1]);
+                if (n < Nout) store4<ODT>(out, ((size_t)b * Tq + r) * ldo + n, acc[i][0], acc[i][1]);
             }
         }
     }
@@ -356,14 +381,24 @@ __global__ void __launch_bounds__(256) k_kv_bmm_dec(const void* __restrict__ x, 
 // MFMA's C operand MAGIC_I -- to sums [BH, Tq, nbw, D], and the first wave of a head x's block exponents to xexp [BH, Tq, nbw].
 // k_kv_pv_combine: a thread per four columns of one token runs rescale() of bfpq_i8mma.h over the blocks j < ceil(Kx / BLK) in block
 // order: the fp32 additions are those of k_kv_bmm_dec in the same order, so the result is the same bits whatever the slice size.
+//
+// ATT (bfpq_kv_attend): x holds no probabilities but the fp32 score rows k_kv_bmm_dec<.., kAtt> left, pitch ldx.  Every workgroup first
+// reduces each row of its head over the row's visible columns (att_visible): the maximum (NaN propagates), then the sum of
+// expf(s - max) -- a thread over its columns 4 tid + 1024 i .. + 3 in ascending order, the 64 lanes of a wave by a butterfly, the four
+// waves as (w0 + w1) + (w2 + w3).  That order depends on the row alone, so all workgroups of a head hold the same two numbers per row,
+// whatever the slice size.  The quantization stage then forms p = expf(s - max) / sum for the lane's own elements, rounds it to the
+// dtype and goes on from those bits exactly as it does from a p it loaded; columns a row does not see are +0.  With pout the workgroups
+// of the first column group also store p [BH, Tq, ldp], zeros included (also those past the head's length, before they return).
 constexpr int kMaxCps = 16;                               // chunks per slice (the LDS holds their codes)
 constexpr int64_t kSplitGrid = 2048;                      // workgroups the chosen slice size aims to stay within
 
-template <int BLK, int DT>
+__device__ __forceinline__ float nan_max(float a, float b) { return a != a ? a : (b != b ? b : (a > b ? a : b)); }
+
+template <int BLK, int DT, bool ATT>
 __global__ void __launch_bounds__(256) k_kv_pv_split(const void* __restrict__ x, const int8_t* __restrict__ vc, int32_t* __restrict__ sums,
                                                      int8_t* __restrict__ xexp, const int32_t* __restrict__ lens, int heads, int Tq, int L,
                                                      int D, int ldx, int cap, int nbw, int cps, int xvec, int xm, float eps_dt,
-                                                     const uint8_t* __restrict__ exp_win)
+                                                     const uint8_t* __restrict__ exp_win, void* __restrict__ pout, int ldp, int causal)
 {
     using Blk = I8Blk<BLK>;
     using op_t = typename Blk::op_t;
@@ -373,15 +408,65 @@ __global__ void __launch_bounds__(256) k_kv_pv_split(const void* __restrict__ x,
     __shared__ uint8_t s_win[BFPQ_EXP_WIN_ENTRIES];
     __shared__ op_t s_b[kMaxCps][NBS][64];
     __shared__ int8_t s_e[kMaxCps][NBS][16];
+    __shared__ float s_red[ATT ? 2 * BFPQ_KV_DEC_MAX_TOKENS * 4 : 1];   // per row and wave: the maximum, then the sum
     const int bh = blockIdx.z, c0 = (int)blockIdx.y * cps;
     const int len = lens[bh / heads];
     const int Kx = len < L ? (len > 0 ? len : 0) : L;
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63, r = l & 15, q = l >> 4;
+    const bool tok = r < Tq;
+    raw_t* const prow = pout ? reinterpret_cast<raw_t*>(pout) + (size_t)bh * Tq * ldp : nullptr;
+    if constexpr (ATT) {
+        if (pout && blockIdx.x == 0) {                           // +0 at what the rows do not see of this slice's columns
+            const int k0 = c0 << 6, k1 = k0 + (cps << 6) < L ? k0 + (cps << 6) : L;
+            for (int i = threadIdx.x; i < Tq * (k1 - k0); i += 256) {
+                const int t = i / (k1 - k0), k = k0 + i % (k1 - k0);
+                if (k >= att_visible(len, Kx, Tq, t, causal)) prow[(size_t)t * ldp + k] = (raw_t)0;
+            }
+        }
+    }
     if ((c0 << 6) >= Kx) return;                                 // (the whole workgroup, before any barrier)
     for (int i = threadIdx.x; i < BFPQ_EXP_WIN_ENTRIES; i += 256) s_win[i] = exp_win[i];
-    __syncthreads();
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63, r = l & 15, q = l >> 4;
+    const float* const srow = reinterpret_cast<const float*>(x) + ((size_t)bh * Tq + (tok ? r : 0)) * ldx;   // (ATT) the lane's score row
+    float rmax = 0.f, rsum = 1.f;
+    int vis = 0;
+    if constexpr (ATT) {
+        const float* const sc = reinterpret_cast<const float*>(x) + (size_t)bh * Tq * ldx;
+        const float ninf = -__builtin_inff();
+        // f(v) over the visible elements of row t this thread owns, in ascending order
+        auto walk = [&](int t, int vt, auto&& f) __attribute__((always_inline)) {
+            for (int k = (int)threadIdx.x * 4; k < vt; k += 1024) {
+                const float4 v = *reinterpret_cast<const float4*>(sc + (size_t)t * ldx + k);
+                f(v.x);
+                if (k + 1 < vt) f(v.y);
+                if (k + 2 < vt) f(v.z);
+                if (k + 3 < vt) f(v.w);
+            }
+        };
+        for (int t = 0; t < Tq; t++) {
+            float m = ninf;
+            walk(t, att_visible(len, Kx, Tq, t, causal), [&](float v) { m = nan_max(m, v); });
+#pragma unroll
+            for (int o = 32; o; o >>= 1) m = nan_max(m, __shfl_xor(m, o, 64));
+            if (l == 0) s_red[t * 4 + w] = m;
+        }
+        __syncthreads();
+        for (int t = 0; t < Tq; t++) {
+            const float m = nan_max(nan_max(s_red[t * 4], s_red[t * 4 + 1]), nan_max(s_red[t * 4 + 2], s_red[t * 4 + 3]));
+            float a = 0.f;
+            walk(t, att_visible(len, Kx, Tq, t, causal), [&](float v) { a += expf(v - m); });
+#pragma unroll
+            for (int o = 32; o; o >>= 1) a += __shfl_xor(a, o, 64);
+            if (l == 0) s_red[(BFPQ_KV_DEC_MAX_TOKENS + t) * 4 + w] = a;
+        }
+        __syncthreads();
+        if (tok) {
+            const float* const sm = s_red + r * 4, * const ss = s_red + (BFPQ_KV_DEC_MAX_TOKENS + r) * 4;
+            rmax = nan_max(nan_max(sm[0], sm[1]), nan_max(sm[2], sm[3]));
+            rsum = (ss[0] + ss[1]) + (ss[2] + ss[3]);
+            vis = att_visible(len, Kx, Tq, r, causal);
+        }
+    } else __syncthreads();
     const int nb = (Kx + BLK - 1) / BLK, nch = (Kx + 63) >> 6, c1 = c0 + cps < nch ? c0 + cps : nch;
-    const bool tok = r < Tq;
     const raw_t* const xr = reinterpret_cast<const raw_t*>(x) + ((size_t)bh * Tq + (tok ? r : 0)) * ldx;
 
     for (int c = c0 + w; c < c1; c += 4) {
@@ -390,7 +475,20 @@ __global__ void __launch_bounds__(256) k_kv_pv_split(const void* __restrict__ x,
             if (c * NBS + s >= nb) break;                        // (wave-uniform)
             const int k0 = (c << 6) + s * BLK + Blk::lane(q);
             uint32_t xv[NE], mx = 0;
-            if (xvec && k0 + NE <= L) {                          // rows 16-byte aligned: the lane's elements in 16-byte loads
+            if constexpr (ATT) {                                 // p of the lane's elements, in the dtype's bits; the store for return_probs
+#pragma unroll
+                for (int v = 0; v < NE / 4; v++) {
+                    float4 sv = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (k0 + 4 * v < vis) sv = *reinterpret_cast<const float4*>(srow + k0 + 4 * v);
+                    const float se[4] = {sv.x, sv.y, sv.z, sv.w};
+#pragma unroll
+                    for (int e = 0; e < 4; e++) {
+                        const int k = k0 + 4 * v + e;
+                        xv[4 * v + e] = k < vis ? f32_to_raw<DT>(expf(se[e] - rmax) / rsum) : 0u;
+                        if (pout && blockIdx.x == 0 && k < vis) prow[(size_t)r * ldp + k] = (raw_t)xv[4 * v + e];
+                    }
+                }
+            } else if (xvec && k0 + NE <= L) {                   // rows 16-byte aligned: the lane's elements in 16-byte loads
 #pragma unroll
                 for (int v = 0; v < NE / Tr::VEC; v++) bfpq_dev::load_raw_vec<DT>(xr + k0, v, xv + v * Tr::VEC);
             } else {
@@ -399,7 +497,7 @@ __global__ void __launch_bounds__(256) k_kv_pv_split(const void* __restrict__ x,
             }
 #pragma unroll
             for (int e = 0; e < NE; e++) {
-                if (!tok || k0 + e >= Kx) xv[e] = 0u;
+                if (!ATT && (!tok || k0 + e >= Kx)) xv[e] = 0u;
                 mx = umax(mx, xv[e] & Tr::ABS);
             }
             mx = umax(mx, (uint32_t)__shfl_xor((int)mx, 16, 64));
@@ -501,6 +599,56 @@ __global__ void __launch_bounds__(256) k_kv_advance(int32_t* __restrict__ lens, 
 
 constexpr int64_t kLim = (int64_t)1 << 31;
 
+// the qk product of a device-length cache (arguments checked by the entries): MODE kDev writes the dtype, kAtt the fp32 softmax input
+template <int MODE>
+void qk_dev(const void* x, const void* wcodes, const int8_t* wexp, void* out, const int32_t* lens, int64_t B, int64_t heads, int64_t Tq, int64_t Kx,
+            int64_t Nout, int64_t ldx, int64_t ldw, int64_t ldwe, int64_t w_bstride, int64_t ldo, int dtype, int block_size, int xm, int wm,
+            float eps_dt, const uint8_t* exp_win, float scale, int causal, hipStream_t s)
+{
+    const unsigned gy = (unsigned)(B < 65535 ? B : 65535);
+    with_block(block_size, [&](auto blk) {
+        with_dtype(dtype, [&](auto dt) {
+            constexpr int TM = decltype(blk)::value == 64 ? 4 : 2;
+            hipLaunchKernelGGL((k_kv_bmm_dec<decltype(blk)::value, decltype(dt)::value, TM, MODE>),
+                               dim3((unsigned)((Nout + 64 * TM - 1) / (64 * TM)), gy), dim3(256), 0, s, x, (const int8_t*)wcodes, wexp, out, (int)B,
+                               (int)Tq, (int)Kx, (int)Nout, (int)ldx, (int)ldw, (int)ldwe, (int)w_bstride, (int)ldo, xm, wm, eps_dt, exp_win, lens,
+                               (int)heads, scale, causal);
+        });
+    });
+}
+
+// the split p v product and its combine pass (arguments checked by the entries).  ATT: x holds fp32 score rows (k_kv_pv_split)
+template <bool ATT>
+int pv_dev(const void* x, const void* wcodes, const int8_t* wexp, void* out, const int32_t* lens, int64_t B, int64_t heads, int64_t Tq, int64_t Kx,
+           int64_t D, int64_t ldx, int64_t ldw, int64_t ldwe, int64_t ldo, int dtype, int block_size, int xm, int wm, float eps_dt,
+           const uint8_t* exp_win, void* ws, int64_t chunks_per_split, void* pout, int64_t ldp, int causal, hipStream_t s)
+{
+    const int64_t nb = (Kx + block_size - 1) / block_size, nch = (Kx + 63) / 64, dg = (D + 63) / 64;
+    int64_t cps = chunks_per_split;
+    if (cps == 0)                                                 // the shortest slices that keep the grid within kSplitGrid workgroups
+        for (cps = 1; cps < kMaxCps && (nch + cps - 1) / cps * dg * B > kSplitGrid; cps++) {}
+    const int64_t slices = (nch + cps - 1) / cps;
+    if (slices > 65535) return BFPQ_E_UNSUPPORTED;
+    int32_t* const sums = (int32_t*)ws;
+    int8_t* const xexp = (int8_t*)ws + B * Tq * nb * 4 * D;
+    const int xvec = !ATT && (reinterpret_cast<uintptr_t>(x) & 15u) == 0 && (ldx * bfpq_dev::dtype_size(dtype)) % 16 == 0;
+    with_block(block_size, [&](auto blk) {
+        with_dtype(dtype, [&](auto dt) {
+            hipLaunchKernelGGL((k_kv_pv_split<decltype(blk)::value, decltype(dt)::value, ATT>), dim3((unsigned)dg, (unsigned)slices, (unsigned)B),
+                               dim3(256), 0, s, x, (const int8_t*)wcodes, sums, xexp, lens, (int)heads, (int)Tq, (int)Kx, (int)D, (int)ldx, (int)ldw,
+                               (int)nb, (int)cps, xvec, xm, eps_dt, exp_win, pout, (int)ldp, causal);
+        });
+    });
+    const int rc = (int)hipGetLastError();
+    if (rc) return rc;
+    const int64_t total = B * Tq * (D / 4);
+    with_dtype(dtype, [&](auto dt) {
+        hipLaunchKernelGGL((k_kv_pv_combine<decltype(dt)::value>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, sums, xexp, wexp, out, lens,
+                           (int)heads, total, (int)Tq, (int)Kx, (int)D, (int)ldwe, (int)nb, (int)ldo, block_size, xm, wm);
+    });
+    return (int)hipGetLastError();
+}
+
 }  // namespace
 
 extern "C" {
@@ -556,10 +704,10 @@ int bfpq_kv_bmm_dec(const void* x, const void* wcodes, const int8_t* wexp, void*
         with_dtype(dtype, [&](auto dt) {
             auto go = [&](auto tmc) {
                 constexpr int TM = decltype(tmc)::value;
-                hipLaunchKernelGGL((k_kv_bmm_dec<decltype(blk)::value, decltype(dt)::value, TM, false>),
+                hipLaunchKernelGGL((k_kv_bmm_dec<decltype(blk)::value, decltype(dt)::value, TM, kHost>),
                                    dim3((unsigned)((Nout + 64 * TM - 1) / (64 * TM)), gy), dim3(256), 0, s, x, (const int8_t*)wcodes, wexp, out, (int)B,
                                    (int)Tq, (int)Kx, (int)Nout, (int)ldx, (int)ldw, (int)ldwe, (int)w_bstride, (int)ldo, x_mant_bits, w_mant_bits,
-                                   eps_dt, exp_win, nullptr, 1);
+                                   eps_dt, exp_win, nullptr, 1, 1.f, 0);
             };
             // rows per wave: 64 (32 at the small blocks) of the many cached keys, 16 of V's D columns
             if (family == BFPQ_KV_PV) go(std::integral_constant<int, 1>{});
@@ -637,46 +785,55 @@ int bfpq_kv_bmm_dec_dev(const void* x, const void* wcodes, const int8_t* wexp, v
     const float eps_dt = bfpq_dev::h_round((float)epsilon, dtype);
     hipStream_t s = (hipStream_t)stream;
     if (family == BFPQ_KV_QK) {
-        const unsigned gy = (unsigned)(B < 65535 ? B : 65535);
-        with_block(block_size, [&](auto blk) {
-            with_dtype(dtype, [&](auto dt) {
-                constexpr int TM = decltype(blk)::value == 64 ? 4 : 2;
-                hipLaunchKernelGGL((k_kv_bmm_dec<decltype(blk)::value, decltype(dt)::value, TM, true>),
-                                   dim3((unsigned)((Nout + 64 * TM - 1) / (64 * TM)), gy), dim3(256), 0, s, x, (const int8_t*)wcodes, wexp, out, (int)B,
-                                   (int)Tq, (int)Kx, (int)Nout, (int)ldx, (int)ldw, (int)ldwe, (int)w_bstride, (int)ldo, x_mant_bits, w_mant_bits,
-                                   eps_dt, exp_win, lens, (int)heads);
-            });
-        });
+        qk_dev<kDev>(x, wcodes, wexp, out, lens, B, heads, Tq, Kx, Nout, ldx, ldw, ldwe, w_bstride, ldo, dtype, block_size, x_mant_bits, w_mant_bits,
+                     eps_dt, exp_win, 1.f, 0, s);
         return (int)hipGetLastError();
     }
     // p v: w_bstride == Nout == D rows per head (the sums are laid out by D)
     const int64_t need = bfpq_kv_dec_ws_bytes(B, Tq, Nout, Kx, block_size);
     if (w_bstride != Nout || B > 65535 || need < 0 || ws_bytes < need) return BFPQ_E_UNSUPPORTED;
     if (!ws || !aligned16(ws)) return BFPQ_E_ARG;
-    const int64_t D = Nout, nch = (Kx + 63) / 64, dg = (D + 63) / 64;
-    int64_t cps = chunks_per_split;
-    if (cps == 0)                                                 // the shortest slices that keep the grid within kSplitGrid workgroups
-        for (cps = 1; cps < kMaxCps && (nch + cps - 1) / cps * dg * B > kSplitGrid; cps++) {}
-    const int64_t slices = (nch + cps - 1) / cps;
-    if (slices > 65535) return BFPQ_E_UNSUPPORTED;
-    int32_t* const sums = (int32_t*)ws;
-    int8_t* const xexp = (int8_t*)ws + B * Tq * nb * 4 * D;
-    const int xvec = (reinterpret_cast<uintptr_t>(x) & 15u) == 0 && (ldx * bfpq_dev::dtype_size(dtype)) % 16 == 0;
-    with_block(block_size, [&](auto blk) {
-        with_dtype(dtype, [&](auto dt) {
-            hipLaunchKernelGGL((k_kv_pv_split<decltype(blk)::value, decltype(dt)::value>), dim3((unsigned)dg, (unsigned)slices, (unsigned)B), dim3(256),
-                               0, s, x, (const int8_t*)wcodes, sums, xexp, lens, (int)heads, (int)Tq, (int)Kx, (int)D, (int)ldx, (int)ldw, (int)nb,
-                               (int)cps, xvec, x_mant_bits, eps_dt, exp_win);
-        });
-    });
-    int rc = (int)hipGetLastError();
+    return pv_dev<false>(x, wcodes, wexp, out, lens, B, heads, Tq, Kx, Nout, ldx, ldw, ldwe, ldo, dtype, block_size, x_mant_bits, w_mant_bits, eps_dt,
+                         exp_win, ws, chunks_per_split, nullptr, 0, 0, s);
+}
+
+int64_t bfpq_kv_attend_ws_bytes(int64_t B, int64_t Tq, int64_t L)
+{
+    if (B < 0 || Tq < 0 || L < 0) return BFPQ_E_ARG;
+    if (Tq > BFPQ_KV_DEC_MAX_TOKENS || L >= kLim || B >= kLim) return BFPQ_E_UNSUPPORTED;
+    return (B * Tq * ((L + 3) / 4 * 4) * 4 + 15) / 16 * 16;       // the fp32 score rows, pitch L rounded up to 4
+}
+
+int bfpq_kv_attend(const void* q, const void* k_codes, const int8_t* k_exps, const void* v_codes, const int8_t* v_exps, void* out, void* p_out,
+                   const int32_t* lens, int64_t BH, int64_t heads, int64_t Tq, int64_t D, int64_t max_len, int64_t cap, int64_t ldd, int64_t ldo,
+                   int64_t ldp, double scale, int causal, int dtype, int block_size, int x_mant_bits, int w_mant_bits, double epsilon,
+                   const uint8_t* exp_win, void* score_ws, int64_t score_ws_bytes, void* sum_ws, int64_t sum_ws_bytes, int64_t chunks_per_split,
+                   void* stream)
+{
+    if (!dtype_ok(dtype) || !i8_block_ok(block_size) || !i8_mant_ok(x_mant_bits) || !i8_mant_ok(w_mant_bits) || BH < 0 || Tq < 0 || heads < 1 ||
+        BH % heads != 0 || chunks_per_split < 0 || (causal != 0 && causal != 1) || !(scale - scale == 0.0) || !((float)scale - (float)scale == 0.f))
+        return BFPQ_E_ARG;
+    if (BH == 0 || Tq == 0) return 0;
+    const int64_t pitch = (max_len + 3) / 4 * 4;
+    if (!bfpq_kv_ok(D, cap, block_size) || Tq > BFPQ_KV_DEC_MAX_TOKENS || max_len < 1 || max_len > cap || ldd < D || ldd % 64 != 0 || ldo % 4 != 0 ||
+        ldo < D || (p_out && ldp < max_len) || cap * ldd >= kLim || Tq * ldo >= kLim || Tq * pitch >= kLim || (p_out && Tq * ldp >= kLim) ||
+        BH > 65535 || chunks_per_split > kMaxCps)
+        return BFPQ_E_UNSUPPORTED;
+    const int64_t need_s = bfpq_kv_attend_ws_bytes(BH, Tq, max_len), need_p = bfpq_kv_dec_ws_bytes(BH, Tq, D, max_len, block_size);
+    if (need_s < 0 || need_p < 0 || score_ws_bytes < need_s || sum_ws_bytes < need_p) return BFPQ_E_UNSUPPORTED;
+    const uintptr_t emask = dtype == BFPQ_F32 ? 3u : 1u;
+    if (!q || !k_codes || !k_exps || !v_codes || !v_exps || !out || !lens || !exp_win || !score_ws || !sum_ws ||
+        !aligned16(k_codes, v_codes, out, score_ws, sum_ws) || (reinterpret_cast<uintptr_t>(lens) & 3u) ||
+        ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(p_out)) & emask))
+        return BFPQ_E_ARG;
+    const float eps_dt = bfpq_dev::h_round((float)epsilon, dtype);
+    hipStream_t s = (hipStream_t)stream;
+    qk_dev<kAtt>(q, k_codes, k_exps, score_ws, lens, BH, heads, Tq, D, max_len, D, ldd, D / block_size, cap, pitch, dtype, block_size, x_mant_bits,
+                 w_mant_bits, eps_dt, exp_win, (float)scale, causal, s);
+    const int rc = (int)hipGetLastError();
     if (rc) return rc;
-    const int64_t total = B * Tq * (D / 4);
-    with_dtype(dtype, [&](auto dt) {
-        hipLaunchKernelGGL((k_kv_pv_combine<decltype(dt)::value>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, sums, xexp, wexp, out, lens,
-                           (int)heads, total, (int)Tq, (int)Kx, (int)D, (int)ldwe, (int)nb, (int)ldo, block_size, x_mant_bits, w_mant_bits);
-    });
-    return (int)hipGetLastError();
+    return pv_dev<true>(score_ws, v_codes, v_exps, out, lens, BH, heads, Tq, max_len, D, pitch, cap, cap / block_size, ldo, dtype, block_size, x_mant_bits,
+                        w_mant_bits, eps_dt, exp_win, sum_ws, chunks_per_split, p_out, ldp, causal, s);
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@ library is missing, or a tensor is not on a ROCm device, the calls raise.
 """
 import collections
 import ctypes
+import math
 import os
 import subprocess
 import threading
@@ -112,6 +113,8 @@ PROTOTYPES = {
     "bfpq_kv_lens_advance": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp]),
     "bfpq_kv_dec_ws_bytes": (_i64, [_i64, _i64, _i64, _i64, _i32]),
     "bfpq_kv_bmm_dec_dev": (_i32, [_vp] * 5 + [_i64] * 10 + [_i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _i64, _i64, _vp]),
+    "bfpq_kv_attend_ws_bytes": (_i64, [_i64, _i64, _i64]),
+    "bfpq_kv_attend": (_i32, [_vp] * 8 + [_i64] * 9 + [_dbl, _i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _i64, _vp, _i64, _i64, _vp]),
 }
 
 
@@ -1510,6 +1513,56 @@ def kv_bmm_dec_dev(x, wc, we, family, bound, w_bstride, lengths, heads, block_si
                                                  _ptr(ws if family == KV_PV else None), ws_bytes, int(chunks_per_split), _stream(x)),
               "bfpq_kv_bmm_dec_dev")
     return out[:, :, :Nout] if ldo != Nout else out
+
+
+def kv_attend_ws_bytes(BH, Tq, max_len):
+    """bytes of kv_attend's fp32 score rows (bfpq_kv_attend_ws_bytes; no device needed)"""
+    n = int(load_library().bfpq_kv_attend_ws_bytes(int(BH), int(Tq), int(max_len)))
+    if n < 0:
+        check(n, "bfpq_kv_attend_ws_bytes")
+    return n
+
+
+def kv_attend(q, k_codes, k_exps, v_codes, v_exps, lengths, heads, max_len, scale, causal, block_size, mant_bits, epsilon, score_ws, sum_ws,
+              chunks_per_split=0, return_probs=False):
+    """scores, scale, softmax and context of q [BH, Tq, D] against a device-length cache in three launches (bfpq_kv_attend): returns
+    (context [BH, Tq, D], p [BH, Tq, max_len] or None).  score_ws / sum_ws: contiguous uint8 tensors of at least
+    kv_attend_ws_bytes(BH, Tq, max_len) / kv_dec_ws_bytes(BH, Tq, D, max_len, block_size) bytes.  Nothing is read back."""
+    require_device_tensor(q, "q")
+    if q.dim() != 3:
+        raise ValueError(f"kv_attend takes q [BH, Tq, D] (got {tuple(q.shape)})")
+    BH, Tq, D = q.shape
+    q = q.contiguous()
+    dev = q.device
+    heads = int(heads)
+    if heads < 1 or BH % heads:
+        raise ValueError(f"kv_attend: {BH} heads in all are no multiple of heads = {heads}")
+    if k_codes.dim() < 2 or v_codes.dim() < 2:
+        raise ValueError("kv_attend takes k_codes [..., cap, ldd] and v_codes [..., D, cap]")
+    cap, ldd = k_codes.shape[-2], k_codes.shape[-1]
+    nbd, nbc = D // int(block_size), cap // int(block_size)
+    for name, buf, numel in (("k_codes", k_codes, BH * cap * ldd), ("k_exps", k_exps, BH * cap * nbd), ("v_codes", v_codes, BH * D * cap),
+                             ("v_exps", v_exps, BH * D * nbc)):
+        if buf.device != dev or buf.dtype != torch.int8 or not buf.is_contiguous() or buf.numel() != numel:
+            raise ValueError(f"kv_attend: {name} must be contiguous int8 on {dev} with {numel} elements "
+                             f"(got {tuple(buf.shape)}, {buf.dtype}, {buf.device})")
+    _kv_int32("kv_attend", "lengths", lengths, BH // heads, dev)
+    max_len, scale = int(max_len), float(scale)
+    if not math.isfinite(scale) or abs(scale) > torch.finfo(torch.float32).max:
+        raise ValueError(f"kv_attend: scale must be finite in fp32 (got {scale})")
+    need = (kv_attend_ws_bytes(BH, Tq, max_len), kv_dec_ws_bytes(BH, Tq, D, max_len, block_size))
+    for name, ws, n in (("score_ws", score_ws, need[0]), ("sum_ws", sum_ws, need[1])):
+        if not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or ws.device != dev or not ws.is_contiguous() or ws.numel() < n:
+            raise ValueError(f"kv_attend: {name} must be a contiguous uint8 tensor of at least {n} bytes on {dev}")
+    with torch.cuda.device(dev):
+        out = torch.empty((BH, Tq, D), dtype=q.dtype, device=dev)
+        p = torch.empty((BH, Tq, max_len), dtype=q.dtype, device=dev) if return_probs else None
+        check(load_library().bfpq_kv_attend(_ptr(q), _ptr(k_codes), _ptr(k_exps), _ptr(v_codes), _ptr(v_exps), _ptr(out), _ptr(p), _ptr(lengths),
+                                            BH, heads, Tq, D, max_len, cap, ldd, D, max_len, scale, int(bool(causal)), DTYPE_CODE[q.dtype],
+                                            int(block_size), int(mant_bits), int(mant_bits), float(epsilon),
+                                            _ptr(exp_window_dev(q.dtype, dev)), _ptr(score_ws), score_ws.numel(), _ptr(sum_ws), sum_ws.numel(),
+                                            int(chunks_per_split), _stream(q)), "bfpq_kv_attend")
+    return out, p
 
 
 def kv_bmm_dec(x, wc, we, family, Nout, w_bstride, block_size, mant_bits, epsilon):
