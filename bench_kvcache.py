@@ -8,6 +8,8 @@ scores, softmax, context; modeling_gpt2.py:345-348 with :207, 243) on one MI355X
          advances (from S - 1 tokens on; the capacity is S plus the iters x (rounds + 1) + 2 tokens the run appends, scores over the
          whole capacity), context split over workgroups (--chunks-per-split, 0 = the library's choice),
   attend the device leg's cache and replay with scores, scale, softmax and context as the one call cache.attend(q, scale),
+  gqa    (--case gqa_*: grouped-query attention) the attend leg on HBFPKVCache(kv_heads=...) fed the kv_heads key / value
+         heads, against twin: the attend leg on the cache without kv_heads fed repeat_kv of them (both legs block 64, alternating),
 and, for the cache alone, the append of a prefill chunk of S tokens.  Method of bench_matmul.py: hipGraph replay, the median of the
 replays, the legs alternating round by round in one process.  (A captured append writes at the captured position: every replay redoes the
 same step, which is what is timed.)  On a tree without the cache the cache columns are null and "cache" says "absent".
@@ -17,7 +19,8 @@ and their min / max from the row of the same shape, dtype and config in FILE, th
 
 Without --case: a driver that runs every case as its own child process under `timeout`, chained with && (a case that faults, hangs or
 fails ends the run), each appending its rows to the --out file (default bench_out/kvcache.json).  --case ragged8: the device leg alone
-on batch 8 with lengths spread from 128 to 4096 (no other leg holds such a batch)."""
+on batch 8 with lengths spread from 128 to 4096 (no other leg holds such a batch).  --kv-heads N: the kv heads of a gqa case (default:
+the case's own)."""
 import argparse, json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -33,14 +36,18 @@ OUT = os.path.join(ROOT, "bench_out", "kvcache.json")
 
 
 RAGGED = {"ragged8": (8, 12, (128, 695, 1262, 1829, 2396, 2963, 3530, 4096), 64)}
+# name: (batch, heads, kv_heads, S, head_dim): the attention of LLaMA-2-70B / LLaMA-3 (modeling_llama.py:385-409), g = 4
+GQA = {"gqa_h32_kv8_b1_s2048": (1, 32, 8, 2048, 128), "gqa_h32_kv8_b8_s2048": (8, 32, 8, 2048, 128)}
 
 
-def device_leg(i8, batch, heads, D, lens, k, v, q, dt, dev, iters, rounds, cps, attend=False):
+def device_leg(i8, batch, heads, D, lens, k, v, q, dt, dev, iters, rounds, cps, attend=False, **mode):
     """(cache, step) of the device leg: sequence b prefilled to lens[b] - 1 tokens, room for every token the run appends.  attend: the
-    same cache and step with cache.attend in place of scores, torch's scale and softmax, and context"""
+    same cache and step with cache.attend in place of scores, torch's scale and softmax, and context.  mode: kv_heads (k and v then hold
+    that many heads)"""
     import torch
     room = iters * (rounds + 1) + 2                                      # replay_times: two warm-up calls, the capture, rounds + 1 replays
-    cache = i8.kv_cache(batch, heads, D, max(lens) + room, dtype=dt, device=dev, device_lengths=True, chunks_per_split=cps, max_query_rows=1)
+    cache = i8.kv_cache(batch, heads, D, max(lens) + room, dtype=dt, device=dev, device_lengths=True, chunks_per_split=cps, max_query_rows=1,
+                        **mode)
     t = max(lens) - 1
     cache.append(k[:, :, :t].contiguous(), v[:, :, :t].contiguous(), torch.tensor([n - 1 for n in lens], dtype=torch.int32, device=dev))
     k_new, v_new, scale = k[:, :, -1:].contiguous(), v[:, :, -1:].contiguous(), 1.0 / D ** 0.5
@@ -94,6 +101,44 @@ def run_ragged(name, iters, rounds, out, cps):
     os.makedirs(os.path.dirname(out), exist_ok=True)
     old = json.load(open(out)) if os.path.exists(out) else []
     json.dump(old + rows, open(out, "w"), indent=1)
+
+
+def run_gqa(name, iters, rounds, out, cps, kv_heads=None, only=None):
+    """the legs gqa and twin of a grouped-query case, bf16 and fp32 at block 64 (only: one leg alone, bf16: what a kernel trace is taken from)"""
+    import torch
+    import quantization_sparsity_interplay_amd as bfpq
+    from quantization_sparsity_interplay_amd.bfp import bfp_ops
+    dev = "cuda:0"
+    batch, heads, kvh, S, D = GQA[name]
+    kvh = kv_heads or kvh
+    g = heads // kvh
+    c = CONFIGS["hbfp8_b64"]
+    rows = []
+    for dname in DTYPES if only is None else ("bf16",):
+        dt = dict(bf16=torch.bfloat16, fp32=torch.float32)[dname]
+        gen = torch.Generator().manual_seed(1)
+        k, v = (torch.randn(batch, kvh, S, D, generator=gen).to(dt).to(dev) for _ in range(2))
+        q = torch.randn(batch, heads, 1, D, generator=gen).to(dt).to(dev)
+        i8 = bfp_ops.F_matmul_bfp(matrix_unit='int8', **bfpq.BFPConfig.hbfp(c['mant_bits'] + 1, c['block_size']).to_kwargs())
+        with torch.no_grad():
+            legs = {}
+            if only != "twin":
+                legs["gqa"] = device_leg(i8, batch, heads, D, [S] * batch, k, v, q, dt, dev, iters, rounds, cps, attend=True, kv_heads=kvh)
+            if only != "gqa":
+                kr, vr = (x.repeat_interleave(g, dim=1) for x in (k, v))                # repeat_kv (modeling_llama.py:264-273)
+                legs["twin"] = device_leg(i8, batch, heads, D, [S] * batch, kr, vr, q, dt, dev, iters, rounds, cps, attend=True)
+            med, spread = replay_times([step for _, step in legs.values()], iters, rounds)
+        row = dict(shape=name, batch=batch, heads=heads, kv_heads=kvh, S=S, head_dim=D, dtype=dname, config="hbfp8_b64", iters=iters, rounds=rounds,
+                   chunks_per_split=cps, kv_bytes_bf16=2 * batch * kvh * S * D * 2)
+        for (leg, (cache, _)), m, sp in zip(legs.items(), med, spread):
+            assert cache.overflow.item() == 0
+            row.update({f"{leg}_us": m, f"{leg}_min_max_us": sp, f"{leg}_cache_bytes": cache.nbytes(), f"{leg}_lengths_at_end": cache.lengths.tolist()})
+        if len(legs) == 2:
+            assert row["gqa_lengths_at_end"] == row["twin_lengths_at_end"] and row["gqa_cache_bytes"] * g == row["twin_cache_bytes"]
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    json.dump((json.load(open(out)) if os.path.exists(out) else []) + rows, open(out, "w"), indent=1)
 
 
 def run_attend_only(shape, iters, rounds, out, cps):
@@ -212,7 +257,9 @@ def merge_parent(out, parent_json):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--case", choices=sorted(SHAPES) + sorted(RAGGED))
+    ap.add_argument("--case", choices=sorted(SHAPES) + sorted(RAGGED) + sorted(GQA))
+    ap.add_argument("--kv-heads", type=int, help="with a gqa case: its kv heads (a divisor of the case's heads; default: the case's own)")
+    ap.add_argument("--leg", choices=("gqa", "twin"), help="with a gqa case: that leg alone, bf16 (a kernel trace of its step)")
     ap.add_argument("--chunks-per-split", type=int, default=0, help="64-token chunks per slice of the device leg's context (0: the library's choice)")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=7)
@@ -223,9 +270,15 @@ def main():
     ap.add_argument("--attend-only", action="store_true", help="with --case: the attend leg alone, bf16 at block 64 (a kernel trace of one attend step)")
     ap.add_argument("--merge-only", action="store_true", help="run nothing: add --parent-json to an existing --out file")
     a = ap.parse_args()
+    if (a.kv_heads is not None or a.leg) and a.case not in GQA:
+        ap.error("--kv-heads and --leg go with a gqa case (--case gqa_*)")
+    if a.kv_heads is not None and (a.kv_heads < 1 or GQA[a.case][1] % a.kv_heads):
+        ap.error(f"--kv-heads must be a divisor of the {GQA[a.case][1]} heads of {a.case} (got {a.kv_heads})")
     out = os.path.abspath(a.out)
     if a.merge_only:
         return merge_parent(out, a.parent_json)
+    if a.case in GQA:
+        return run_gqa(a.case, a.iters, a.rounds, out, a.chunks_per_split, a.kv_heads, a.leg)
     if a.case in RAGGED:
         return run_ragged(a.case, a.iters, a.rounds, out, a.chunks_per_split)
     if a.case and a.attend_only:
@@ -235,7 +288,7 @@ def main():
     if os.path.exists(out):
         os.remove(out)
     steps = [f"timeout -k 10 {a.timeout} {sys.executable} {os.path.abspath(__file__)} --case {s} --iters {a.iters} --rounds {a.rounds} --chunks-per-split {a.chunks_per_split} --out {out}"
-             for s in list(SHAPES) + list(RAGGED)]
+             for s in list(SHAPES) + list(RAGGED) + list(GQA)]
     rc = subprocess.call(" && ".join(steps), shell=True)
     if rc == 0 and a.parent_json:
         merge_parent(out, a.parent_json)

@@ -525,6 +525,27 @@ int bfpq_kv_attend(const void* q_dev, const void* k_codes_dev, const int8_t* k_e
                    int64_t cap, int64_t ldd, int64_t ldo, int64_t ldp, double scale, int causal, int dtype, int block_size, int x_mant_bits,
                    int w_mant_bits, double epsilon, const uint8_t* exp_win_dev, void* score_ws_dev, int64_t score_ws_bytes, void* sum_ws_dev,
                    int64_t sum_ws_bytes, int64_t chunks_per_split, void* stream);
+/* Grouped-query attention on the device-length cache (reference modeling_llama.py:397-409: repeat_kv of the key and value states --
+ * :264-273, kv head h serving the query heads h g .. h g + g - 1 -- and the two matmuls, the mask and the softmax between them).  The
+ * cache arrays hold B (resp. BH) kv heads, `heads` of them per sequence; every kv head serves `group` >= 1 query heads, and x / q, out
+ * and p are [B, group * Tq, .]: row r of kv head b is query head r / Tq of its group, token r % Tq (the contiguous view of
+ * [sequences, heads * group, Tq, .]).  Nothing is repeated: the rows are walked in tiles of 16, a tile's rows sharing every load of
+ * the codes (which are read again per tile).  The result is
+ * bit for bit that of the entry without _gqa on B * group heads whose cache arrays repeat every kv head group times: per row nothing
+ * depends on the other rows of its tile.  Tq <= BFPQ_KV_DEC_MAX_TOKENS stays a limit per query head; the workspaces are those of
+ * B * group heads: ws_bytes >= bfpq_kv_dec_ws_bytes(B * group, Tq, D, L, block_size), score_ws_bytes >=
+ * bfpq_kv_attend_ws_bytes(BH * group, Tq, max_len).  causal and max_len as bfpq_kv_attend, per token.  Errors as the entries without
+ * _gqa, which are these with group = 1; group < 1: BFPQ_E_ARG; more than 65535 (kv head, row tile) pairs where bfpq_kv_bmm_dec_dev
+ * refuses B > 65535, or group * Tq rows whose pitch does not fit: BFPQ_E_UNSUPPORTED. */
+int bfpq_kv_bmm_dec_gqa(const void* x_dev, const void* wcodes_dev, const int8_t* wexp_dev, void* out_dev, const int32_t* lens_dev, int64_t B,
+                        int64_t heads, int64_t Tq, int64_t group, int64_t Kx, int64_t Nout, int64_t ldx, int64_t ldw, int64_t ldwe,
+                        int64_t w_bstride, int64_t ldo, int family, int dtype, int block_size, int x_mant_bits, int w_mant_bits, double epsilon,
+                        const uint8_t* exp_win_dev, void* ws_dev, int64_t ws_bytes, int64_t chunks_per_split, void* stream);
+int bfpq_kv_attend_gqa(const void* q_dev, const void* k_codes_dev, const int8_t* k_exps_dev, const void* v_codes_dev, const int8_t* v_exps_dev,
+                       void* out_dev, void* p_dev, const int32_t* lens_dev, int64_t BH, int64_t heads, int64_t Tq, int64_t group, int64_t D,
+                       int64_t max_len, int64_t cap, int64_t ldd, int64_t ldo, int64_t ldp, double scale, int causal, int dtype, int block_size,
+                       int x_mant_bits, int w_mant_bits, double epsilon, const uint8_t* exp_win_dev, void* score_ws_dev, int64_t score_ws_bytes,
+                       void* sum_ws_dev, int64_t sum_ws_bytes, int64_t chunks_per_split, void* stream);
 /* ---- 2:4-compressed packed weights (format sp24) and their few-token product on v_smfmac_i32_16x16x64_i8 -------------------------
  * A weight pruned N:M with M = 4, N <= 2 along K (_structured_N_M_sparsity, reference bfp_ops.py:73-91) and quantized to HBFP block 64
  * holds at most 2 non-zero codes per group of 4.  sp24 keeps those two codes and their 2-bit positions, tiled for the decode kernel

@@ -1263,7 +1263,7 @@ def _gen_matmul_i8_op(bfp_args, matrix_unit):
 
     def kv_cache(batch, heads, head_dim, capacity, dtype=torch.bfloat16, device='cuda', **mode):
         """an HBFPKVCache under this op's bfp_args; its products count in matmul_stats.cache_calls.  mode: device_lengths=True (and
-        chunks_per_split) as HBFPKVCache takes them"""
+        chunks_per_split), kv_heads as HBFPKVCache takes them"""
         return HBFPKVCache(batch, heads, head_dim, capacity, dtype=dtype, stats=stats, **mode, **dict(bfp_args, device=device))
 
     bfp_op.__name__ = fake.__name__
@@ -1350,10 +1350,19 @@ class HBFPKVCache:
     every chunks_per_split.  causal=True takes the Tq rows to be the last Tq tokens held: row t sees the keys n <= lengths[b] - Tq + t.
     Keys a row does not see are exactly +0 in p; an empty sequence gives a zero context row, and a row that sees no key of a sequence
     that holds some (causal with Tq > lengths[b]) what context() makes of a p of zeros.  The fp32 score rows [B H, max_query_rows, cap] are a workspace made by the first attend() or by prepare_attend() --
-    call either before capturing a graph -- and never grown; caches that never attend never hold it."""
+    call either before capturing a graph -- and never grown; caches that never attend never hold it.
+
+    kv_heads (grouped-query attention; the reference's LLaMA, modeling_llama.py:385-409): an int in 1..heads that divides
+    heads; None or heads is the cache above.  The buffers, append(), keys() and values() then hold kv_heads heads per sequence -- nbytes()
+    is 1 / g of the above, g = heads // kv_heads -- while scores(), context() and attend() take and return [B, heads, Tq, .] as before:
+    query head h reads kv head h // g, the reference's repeat_kv order (:264-273), and nothing is repeated.  Every result is bit for
+    bit that of an HBFPKVCache(batch, heads, ...) fed k.repeat_interleave(g, 1), v.repeat_interleave(g, 1).  The row limits (16,
+    max_query_rows) stay limits per query head, and the workspaces hold the same bytes.  The g Tq rows of a kv head go through the
+    kernels in tiles of 16: the rows of a tile share every load of the codes, which are read again per tile; on the host-length cache
+    more than 16 rows take the act_codes route."""
 
     def __init__(self, batch, heads, head_dim, capacity, dtype=torch.bfloat16, device='cuda', stats=None, device_lengths=False,
-                 chunks_per_split=0, max_query_rows=native.KV_DEC_MAX_TOKENS, **bfp_args):
+                 chunks_per_split=0, max_query_rows=native.KV_DEC_MAX_TOKENS, kv_heads=None, **bfp_args):
         a = unpack_bfp_args(bfp_args)
         if bfp_args:
             raise TypeError(f"HBFPKVCache: unknown arguments {sorted(bfp_args)}")
@@ -1362,6 +1371,12 @@ class HBFPKVCache:
             raise TypeError(f"HBFPKVCache: unsupported dtype {dtype}")
         if batch < 1 or heads < 1 or capacity < 1:
             raise ValueError(f"HBFPKVCache: batch, heads and capacity must be >= 1 (got {batch}, {heads}, {capacity})")
+        if kv_heads is None:
+            kv_heads = heads
+        if isinstance(kv_heads, bool) or not isinstance(kv_heads, int):
+            raise TypeError(f"HBFPKVCache: kv_heads must be an int or None (got {kv_heads!r})")
+        if not 1 <= kv_heads <= heads or heads % kv_heads:
+            raise ValueError(f"HBFPKVCache: kv_heads must be in 1..heads and divide heads (got kv_heads={kv_heads}, heads={heads})")
         self.args, self.act = a, native.ActSparsity.from_bfp_args(a)
         self.device_lengths, self.chunks_per_split = bool(device_lengths), int(chunks_per_split)
         if self.device_lengths and self.act is not None:
@@ -1372,13 +1387,14 @@ class HBFPKVCache:
             raise ValueError(f"HBFPKVCache: max_query_rows must be 1..{native.KV_DEC_MAX_TOKENS} (got {max_query_rows!r})")
         self.max_query_rows = max_query_rows
         self.batch, self.heads, self.head_dim, self.capacity, self.dtype = batch, heads, head_dim, capacity, dtype
+        self.kv_heads, self.group = kv_heads, heads // kv_heads  # query head h reads kv head h // group
         self.block, self.mant_bits, self.epsilon = a['block_size'], a['mant_bits'], a['epsilon']
         self.cap = native.code_pitch(capacity)                   # tokens the buffers hold: a multiple of 64 and of the block
         if not native.kv_ok(head_dim, self.cap, self.block):
             raise ValueError(f"HBFPKVCache: head_dim {head_dim} x capacity {capacity} at block {self.block} is not taken")
         self.stats = stats if stats is not None else MatmulStats()
         self._length = 0
-        B, H, D, cap, blk = batch, heads, head_dim, self.cap, self.block
+        B, H, D, cap, blk = batch, kv_heads, head_dim, self.cap, self.block
         z = lambda *shape, dt=torch.int8: torch.zeros(shape, dtype=dt, device=device)
         self.buffers = dict(k_codes=z(B, H, cap, native.code_pitch(D)), k_exps=z(B, H, cap, D // blk), v_codes=z(B, H, D, cap),
                             v_exps=z(B, H, D, cap // blk), v_tail=z(B, H, blk, D, dt=dtype))
@@ -1402,7 +1418,7 @@ class HBFPKVCache:
         self._length = value
 
     def _workspace(self, Tq):
-        """context()'s block sums for Tq query rows at any length up to the capacity"""
+        """context()'s block sums for Tq query rows (of every query head) at any length up to the capacity"""
         n = native.kv_dec_ws_bytes(self.batch * self.heads, Tq, self.head_dim, self.cap, self.block)
         return torch.empty(n, dtype=torch.uint8, device=self.k_codes.device)
 
@@ -1417,24 +1433,36 @@ class HBFPKVCache:
             self.length = 0
         self.v_codes.zero_()
 
-    def _operand(self, x, what, last):
+    def _operand(self, x, what, last, heads=None):
+        """x [B, heads, t, last] (heads: the query heads unless given) as the rows of the kv heads, [B kv_heads, heads // kv_heads * t, last]"""
+        heads = self.heads if heads is None else heads
         if torch.is_grad_enabled():
             raise ValueError(f"HBFPKVCache.{what}: inference only, called while gradients are recorded (use torch.no_grad())")
-        want = (self.batch, self.heads, last)
+        want = (self.batch, heads, last)
         if not isinstance(x, torch.Tensor) or x.dim() != 4 or (x.shape[0], x.shape[1], x.shape[3]) != want or x.shape[2] < 1:
-            raise ValueError(f"HBFPKVCache.{what} takes [{self.batch}, {self.heads}, t >= 1, {last}] (got {tuple(getattr(x, 'shape', ()))})")
+            raise ValueError(f"HBFPKVCache.{what} takes [{self.batch}, {heads}, t >= 1, {last}] (got {tuple(getattr(x, 'shape', ()))})")
         if x.dtype != self.dtype or x.device != self.k_codes.device:
             raise ValueError(f"HBFPKVCache.{what}: the cache holds {self.dtype} on {self.k_codes.device} (got {x.dtype} on {x.device})")
-        return x.reshape(self.batch * self.heads, x.shape[2], last)
+        return x.reshape(self.batch * self.kv_heads, heads // self.kv_heads * x.shape[2], last)
 
-    def _rows(self, what, Tq):
+    def _result(self, out, Tq):
+        """[B kv_heads, group Tq, n] as [B, heads, Tq, n] (a view)"""
+        return out.unflatten(1, (self.group, Tq)).reshape(self.batch, self.heads, Tq, out.shape[-1])
+
+    def _rows(self, what, Tq, tiles_on_grid=False):
+        """tiles_on_grid: the launch carries a workgroup per (kv head, tile of 16 rows) on a grid dimension of 65535 (k_kv_pv_split:
+        context and attend; the qk kernel strides over the pairs).  A cache without groups leaves that limit to the C entry, as before"""
         if Tq > native.KV_DEC_MAX_TOKENS:
             raise ValueError(f"HBFPKVCache.{what}: device_lengths=True takes up to {native.KV_DEC_MAX_TOKENS} query rows (got {Tq})")
+        tiles = self.batch * self.kv_heads * ((self.group * Tq + 15) // 16)
+        if tiles_on_grid and self.group > 1 and tiles > 65535:
+            raise ValueError(f"HBFPKVCache.{what}: {self.batch} x {self.kv_heads} kv heads of {self.group} x {Tq} query rows are {tiles} "
+                             "tiles of 16 rows, the grid takes 65535")
 
     def append(self, k_new, v_new, counts=None):
-        """k_new, v_new [B, H, t, D] become tokens length .. length + t - 1 (one launch for a prefill chunk or one token).  With
+        """k_new, v_new [B, kv_heads, t, D] become tokens length .. length + t - 1 (one launch for a prefill chunk or one token).  With
         device_lengths: per sequence, at lengths[b], the first counts[b] rows (the class docstring); two launches, returns None"""
-        k, v = self._operand(k_new, 'append', self.head_dim), self._operand(v_new, 'append', self.head_dim)
+        k, v = (self._operand(x, 'append', self.head_dim, self.kv_heads) for x in (k_new, v_new))
         t = k.shape[1]
         if v.shape[1] != t:
             raise ValueError(f"HBFPKVCache.append: {t} keys and {v.shape[1]} values")
@@ -1447,7 +1475,7 @@ class HBFPKVCache:
                                        or counts.device != self.k_codes.device or not counts.is_contiguous()):
                 raise ValueError(f"HBFPKVCache.append: counts must be a contiguous int32 tensor [{self.batch}] on {self.k_codes.device}")
             native.kv_append_dev(k.contiguous(), v.contiguous(), self.k_codes, self.k_exps, self.v_codes, self.v_exps, self.v_tail, self.lengths,
-                                 counts, self.overflow, self.heads, self.capacity, self.block, self.mant_bits, self.epsilon)
+                                 counts, self.overflow, self.kv_heads, self.capacity, self.block, self.mant_bits, self.epsilon)
             return None
         if self.length + t > self.capacity:
             raise ValueError(f"HBFPKVCache.append: {self.length} + {t} tokens exceed the capacity {self.capacity}")
@@ -1456,35 +1484,37 @@ class HBFPKVCache:
         self.length += t
         return self.length
 
-    def _in_kernel(self, Tq):
-        return self.act is None and Tq <= native.KV_DEC_MAX_TOKENS
+    def _in_kernel(self, rows):
+        """the host-length cache quantizes up to 16 dense rows per (kv) head inside the product kernel"""
+        return self.act is None and rows <= native.KV_DEC_MAX_TOKENS
 
     def scores(self, q, max_len=None):
         """q [B, H, Tq, D] -> [B, H, Tq, S]: Q_in(q) @ Q_w(K_all)^T.  With device_lengths: [B, H, Tq, max_len], -inf from lengths[b] on"""
         x = self._operand(q, 'scores', self.head_dim)
+        Tq = q.shape[2]
         if not self.device_lengths and max_len is not None:
             raise ValueError("HBFPKVCache.scores: max_len needs device_lengths=True")
         if self.device_lengths:
-            self._rows('scores', x.shape[1])
+            self._rows('scores', Tq)
             n = self.capacity if max_len is None else max_len
             if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= self.capacity:
                 raise ValueError(f"HBFPKVCache.scores: max_len must be an int in 1..{self.capacity} (got {max_len!r})")
-            out = native.kv_bmm_dec_dev(x, self.k_codes, self.k_exps, native.KV_QK, n, self.cap, self.lengths, self.heads, self.block,
-                                        self.mant_bits, self.epsilon)
+            out = native.kv_bmm_dec_dev(x, self.k_codes, self.k_exps, native.KV_QK, n, self.cap, self.lengths, self.kv_heads, self.block,
+                                        self.mant_bits, self.epsilon, group=self.group)
             self.stats.cache_calls += 1
-            return out.unflatten(0, (self.batch, self.heads))
-        S, D, BH, Tq, m = self.length, self.head_dim, x.shape[0], x.shape[1], self.mant_bits
+            return self._result(out, Tq)
+        S, D, BH, R, m = self.length, self.head_dim, x.shape[0], x.shape[1], self.mant_bits   # R = group * Tq rows per kv head
         if S < 1:
             raise ValueError("HBFPKVCache.scores: the cache is empty")
-        if self._in_kernel(Tq):
+        if self._in_kernel(R):
             out = native.kv_bmm_dec(x, self.k_codes, self.k_exps, native.KV_QK, S, self.cap, self.block, m, self.epsilon)
         else:
-            xq = native.act_codes(x.reshape(BH * Tq, D), m, self.epsilon, self.act, block_size=self.block)
+            xq = native.act_codes(x.reshape(BH * R, D), m, self.epsilon, self.act, block_size=self.block)
             N = (S + 15) // 16 * 16                               # rows S .. N - 1 repeat key S - 1 and are dropped
-            out = native.hbfp_bmm_i8_strided(xq, self.k_codes, self.k_exps, BH, Tq, N, D, self.cap, S, m, m, block_size=self.block,
+            out = native.hbfp_bmm_i8_strided(xq, self.k_codes, self.k_exps, BH, R, N, D, self.cap, S, m, m, block_size=self.block,
                                              out_dtype=self.dtype)[:, :, :S]
         self.stats.cache_calls += 1
-        return out.unflatten(0, (self.batch, self.heads))
+        return self._result(out, Tq)
 
     def context(self, p):
         """p [B, H, Tq, S] -> [B, H, Tq, D]: Q_in(p) @ Q_w(V_all^T)^T, blocks along the S cached tokens (the last one zero-padded).  With
@@ -1493,19 +1523,20 @@ class HBFPKVCache:
             if not isinstance(p, torch.Tensor) or p.dim() != 4 or not 1 <= p.shape[-1] <= self.capacity:
                 raise ValueError(f"HBFPKVCache.context takes p [..., L], 1 <= L <= {self.capacity} (got {tuple(getattr(p, 'shape', ()))})")
             x = self._operand(p, 'context', p.shape[-1])
-            Tq = x.shape[1]
-            self._rows('context', Tq)
+            Tq = p.shape[2]
+            self._rows('context', Tq, tiles_on_grid=True)
             if Tq > self.max_query_rows:
                 raise ValueError(f"HBFPKVCache.context: {Tq} query rows, the workspace was made for max_query_rows={self.max_query_rows}")
-            out = native.kv_bmm_dec_dev(x, self.v_codes, self.v_exps, native.KV_PV, self.head_dim, self.head_dim, self.lengths, self.heads,
-                                        self.block, self.mant_bits, self.epsilon, ws=self._ws, chunks_per_split=self.chunks_per_split)
+            out = native.kv_bmm_dec_dev(x, self.v_codes, self.v_exps, native.KV_PV, self.head_dim, self.head_dim, self.lengths, self.kv_heads,
+                                        self.block, self.mant_bits, self.epsilon, ws=self._ws, chunks_per_split=self.chunks_per_split,
+                                        group=self.group)
             self.stats.cache_calls += 1
-            return out.unflatten(0, (self.batch, self.heads))
+            return self._result(out, Tq)
         if not isinstance(p, torch.Tensor) or p.dim() != 4 or p.shape[-1] != self.length or self.length < 1:
             raise ValueError(f"HBFPKVCache.context takes p [..., {self.length}], the cached length >= 1 (got {tuple(getattr(p, 'shape', ()))})")
         x = self._operand(p, 'context', self.length)
-        S, D, BH, Tq, m, blk = self.length, self.head_dim, x.shape[0], x.shape[1], self.mant_bits, self.block
-        if self._in_kernel(Tq):
+        S, D, BH, R, m, blk = self.length, self.head_dim, x.shape[0], x.shape[1], self.mant_bits, self.block
+        if self._in_kernel(R):
             out = native.kv_bmm_dec(x, self.v_codes, self.v_exps, native.KV_PV, D, D, blk, m, self.epsilon)
         else:
             Sp = (S + blk - 1) // blk * blk
@@ -1515,10 +1546,10 @@ class HBFPKVCache:
                                      f"(or N:M with M dividing the block); S = {S}")
                 # the reference's zero pad of the last block (bfp_ops.py:50-53; for N:M its pad to M, :79-82, and all-zero groups); p is small
                 x = F.pad(x, (0, Sp - S))
-            xq = native.act_codes(x.reshape(BH * Tq, Sp), m, self.epsilon, self.act, block_size=blk)
-            out = native.hbfp_bmm_i8_strided(xq, self.v_codes, self.v_exps, BH, Tq, D, Sp, D, D, m, m, block_size=blk, out_dtype=self.dtype)
+            xq = native.act_codes(x.reshape(BH * R, Sp), m, self.epsilon, self.act, block_size=blk)
+            out = native.hbfp_bmm_i8_strided(xq, self.v_codes, self.v_exps, BH, R, D, Sp, D, D, m, m, block_size=blk, out_dtype=self.dtype)
         self.stats.cache_calls += 1
-        return out.unflatten(0, (self.batch, self.heads))
+        return self._result(out, p.shape[2])
 
     def prepare_attend(self):
         """make attend()'s workspace now (the fp32 score rows of max_query_rows rows over the whole capacity); it is never grown"""
@@ -1534,8 +1565,8 @@ class HBFPKVCache:
         if not self.device_lengths:
             raise ValueError("HBFPKVCache.attend needs device_lengths=True")
         x = self._operand(q, 'attend', self.head_dim)
-        Tq = x.shape[1]
-        self._rows('attend', Tq)
+        Tq = q.shape[2]
+        self._rows('attend', Tq, tiles_on_grid=True)
         if Tq > self.max_query_rows:
             raise ValueError(f"HBFPKVCache.attend: {Tq} query rows, the workspaces were made for max_query_rows={self.max_query_rows}")
         if isinstance(scale, bool) or not isinstance(scale, numbers.Real) or not math.isfinite(scale) or abs(scale) > torch.finfo(torch.float32).max:
@@ -1544,12 +1575,12 @@ class HBFPKVCache:
         if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= self.capacity:
             raise ValueError(f"HBFPKVCache.attend: max_len must be an int in 1..{self.capacity} (got {max_len!r})")
         self.prepare_attend()
-        out, p = native.kv_attend(x, self.k_codes, self.k_exps, self.v_codes, self.v_exps, self.lengths, self.heads, n, float(scale), bool(causal),
-                                  self.block, self.mant_bits, self.epsilon, self._att_ws, self._ws, chunks_per_split=self.chunks_per_split,
-                                  return_probs=bool(return_probs))
+        out, p = native.kv_attend(x, self.k_codes, self.k_exps, self.v_codes, self.v_exps, self.lengths, self.kv_heads, n, float(scale),
+                                  bool(causal), self.block, self.mant_bits, self.epsilon, self._att_ws, self._ws,
+                                  chunks_per_split=self.chunks_per_split, return_probs=bool(return_probs), group=self.group)
         self.stats.cache_calls += 2
-        out = out.unflatten(0, (self.batch, self.heads))
-        return (out, p.unflatten(0, (self.batch, self.heads))) if return_probs else out
+        out = self._result(out, Tq)
+        return (out, self._result(p, Tq)) if return_probs else out
 
     def _held(self, b):
         """(first sequence, sequences, S) of keys() / values(): everything at the host length, or sequence b at lengths[b] (read back)"""
@@ -1562,22 +1593,22 @@ class HBFPKVCache:
         return b, 1, int(self.lengths[b].item())
 
     def keys(self, b=None):
-        """the cached keys dequantized, [B, H, S, D]; with device_lengths those of sequence b, [1, H, lengths[b], D]"""
+        """the cached keys dequantized, [B, kv_heads, S, D]; with device_lengths those of sequence b, [1, kv_heads, lengths[b], D]"""
         b0, nb, S = self._held(b)
-        BH, D = nb * self.heads, self.head_dim
+        BH, D = nb * self.kv_heads, self.head_dim
         c = self.k_codes[b0:b0 + nb].view(BH, self.cap, -1)[:, :S, :D].reshape(BH * S, D)
         e = self.k_exps[b0:b0 + nb].view(BH, self.cap, -1)[:, :S].reshape(BH * S, D // self.block)
-        return native.dequantize(c, e, D, self.dtype, self.block, self.mant_bits, 8).view(nb, self.heads, S, D)
+        return native.dequantize(c, e, D, self.dtype, self.block, self.mant_bits, 8).view(nb, self.kv_heads, S, D)
 
     def values(self, b=None):
-        """the cached values dequantized, [B, H, S, D]; with device_lengths those of sequence b, [1, H, lengths[b], D]"""
+        """the cached values dequantized, [B, kv_heads, S, D]; with device_lengths those of sequence b, [1, kv_heads, lengths[b], D]"""
         b0, nb, S = self._held(b)
-        BH, D, blk = nb * self.heads, self.head_dim, self.block
+        BH, D, blk = nb * self.kv_heads, self.head_dim, self.block
         Sp = (S + blk - 1) // blk * blk
         c = self.v_codes[b0:b0 + nb].view(BH * D, self.cap)[:, :Sp].contiguous()
         e = self.v_exps[b0:b0 + nb].view(BH * D, -1)[:, :Sp // blk].contiguous()
         v = native.dequantize(c, e, Sp, self.dtype, blk, self.mant_bits, 8)[:, :S]
-        return v.reshape(nb, self.heads, D, S).transpose(-1, -2)
+        return v.reshape(nb, self.kv_heads, D, S).transpose(-1, -2)
 
 
 def F_matmul_bfp(matrix_unit=False, **kwargs):

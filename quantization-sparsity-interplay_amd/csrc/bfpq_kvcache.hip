@@ -29,6 +29,18 @@
 // scores -- rounded to the dtype, widened, times the scale -- as fp32 rows in a workspace; k_kv_pv_split<.., true> reads them, every
 // workgroup of a head reducing the head's rows to the same maximum and sum before it forms, rounds and quantizes the probabilities of
 // its own slice in registers; k_kv_pv_combine is the one context() runs.
+//
+// Grouped-query attention (the reference's LLaMA, modeling_llama.py:385-409): the cache holds B x kv_heads heads and query
+// head h reads kv head h / g (repeat_kv, :264-273).  Nothing is repeated: the rows of a kv head are the contiguous view
+// [B kv_heads, R = g Tq, .] of q / p / the outputs, row r being query head r / Tq of the group and its token t = r % Tq, and the GRP
+// instances of k_kv_bmm_dec and k_kv_pv_split walk them in tiles of 16 consecutive rows (the tile index shares a grid dimension with
+// the head).  The rows of a tile share every load of the K / V codes and exponents -- for R <= 16, the decode step of every real
+// model, the whole group reads them once -- and each further tile is an iteration of k_kv_bmm_dec's y loop or a workgroup of
+// k_kv_pv_split of its own, which reads them again.  The result is, bit for bit, that of a cache of B x heads heads fed repeat_kv(k),
+// repeat_kv(v), by construction: K and V are quantized per head, so repeated heads hold identical codes; a row's x block maximum is
+// taken over that token's four lanes only; block sums are exact integers; the fp32 additions run across blocks in block order per
+// row; the softmax's summation order depends on the row alone -- nothing a row computes depends on which rows share its tile.  Only
+// att_visible needs the token: it is called with t = r % Tq.  The instances without GRP are the code as it was (g = 1).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "bfpq.h"
@@ -203,11 +215,14 @@ __device__ __forceinline__ int att_visible(int len, int Kx, int Tq, int t, int c
     return v < Kx ? (v > 0 ? v : 0) : Kx;
 }
 
-template <int BLK, int DT, int TM, int MODE>
+// GRP: head b has R = group * Tq rows of x and out (row = query head of the group * Tq + token), walked in tiles of 16: blockIdx.y runs
+// over (head, tile).  Without GRP the argument `group` is passed and never read (the compiler drops it: the register figures of those
+// instances are the ones they had without it): one tile, the row is the token
+template <int BLK, int DT, int TM, int MODE, bool GRP = false>
 __global__ void __launch_bounds__(256) k_kv_bmm_dec(const void* __restrict__ x, const int8_t* __restrict__ wc, const int8_t* __restrict__ we,
                                                     void* __restrict__ out, int B, int Tq, int Kx, int Nout, int ldx, int ldw, int ldwe, int wbs,
                                                     int ldo, int xm, int wm, float eps_dt, const uint8_t* __restrict__ exp_win,
-                                                    const int32_t* __restrict__ lens, int heads, float scale, int causal)
+                                                    const int32_t* __restrict__ lens, int heads, float scale, int causal, int group)
 {
     using Blk = I8Blk<BLK>;
     using op_t = typename Blk::op_t;
@@ -224,7 +239,7 @@ __global__ void __launch_bounds__(256) k_kv_bmm_dec(const void* __restrict__ x, 
     const int n0 = ((int)blockIdx.x * 4 + w) * 16 * TM;
     if (n0 >= Nout) return;                                      // (wave-uniform; no barrier below)
     const int nb = (Kx + BLK - 1) / BLK, nch = (Kx + 63) >> 6;
-    const bool tok = r < Tq;
+    const int R = GRP ? Tq * group : Tq, ntiles = GRP ? (R + 15) >> 4 : 1;
 
     uint32_t offW[TM], ewo[TM][4];
     auto rows = [&](int No) __attribute__((always_inline)) {
@@ -243,7 +258,9 @@ __global__ void __launch_bounds__(256) k_kv_bmm_dec(const void* __restrict__ x, 
     const v4i magic = {MAGIC_I, MAGIC_I, MAGIC_I, MAGIC_I};
     const float ninf = -__builtin_inff();
 
-    for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    for (int y = blockIdx.y; y < B * ntiles; y += gridDim.y) {
+        const int b = GRP ? y / ntiles : y, row = GRP ? (y % ntiles) * 16 + r : r;   // the head, and the lane's row of it
+        const bool tok = row < R;
         int No = Nout, len = 0;
         if constexpr (DEV) {
             len = lens[b / heads];
@@ -253,7 +270,7 @@ __global__ void __launch_bounds__(256) k_kv_bmm_dec(const void* __restrict__ x, 
 #pragma unroll
                     for (int i = 0; i < TM; i++) {
                         const int n = n0 + 16 * i + 4 * q;
-                        if (n < Nout) store4<ODT>(out, ((size_t)b * Tq + r) * ldo + n, v2f{ninf, ninf}, v2f{ninf, ninf});
+                        if (n < Nout) store4<ODT>(out, ((size_t)b * R + row) * ldo + n, v2f{ninf, ninf}, v2f{ninf, ninf});
                     }
                 }
                 continue;
@@ -262,7 +279,7 @@ __global__ void __launch_bounds__(256) k_kv_bmm_dec(const void* __restrict__ x, 
         }
         const int8_t* const wcb = wc + (size_t)b * wbs * ldw;
         const int8_t* const web = we + (size_t)b * wbs * ldwe;
-        const raw_t* const xr = reinterpret_cast<const raw_t*>(x) + ((size_t)b * Tq + (tok ? r : 0)) * ldx;
+        const raw_t* const xr = reinterpret_cast<const raw_t*>(x) + ((size_t)b * R + (tok ? row : 0)) * ldx;
 
         // chunk c: the lane's w codes, the exponents of its four output rows (byte s of a word = block s of the chunk) and its x elements
         auto load = [&](int c, op_t (&aF)[TM][NBS], uint32_t (&ew)[TM][4], uint32_t (&xv)[NBS][NE]) __attribute__((always_inline)) {
@@ -349,13 +366,13 @@ __global__ void __launch_bounds__(256) k_kv_bmm_dec(const void* __restrict__ x, 
             }
         }
 
-        // the lane holds rows n .. n + 3 of token r (the pitch ldo takes the ones past Nout)
+        // the lane holds rows n .. n + 3 of row `row` (the pitch ldo takes the ones past Nout)
         if (tok) {
 #pragma unroll
             for (int i = 0; i < TM; i++) {
                 const int n = n0 + 16 * i + 4 * q;
                 if constexpr (MODE == kAtt) {
-                    const int vis = att_visible(len, No, Tq, r, causal);
+                    const int vis = att_visible(len, No, Tq, GRP ? row % Tq : r, causal);
                     acc[i][0].x = n + 0 < vis ? rnd<DT>(acc[i][0].x) * scale : ninf;
                     acc[i][0].y = n + 1 < vis ? rnd<DT>(acc[i][0].y) * scale : ninf;
                     acc[i][1].x = n + 2 < vis ? rnd<DT>(acc[i][1].x) * scale : ninf;
@@ -366,7 +383,7 @@ __global__ void __launch_bounds__(256) k_kv_bmm_dec(const void* __restrict__ x, 
                     if (n + 2 >= No) acc[i][1].x = ninf;
                     if (n + 3 >= No) acc[i][1].y = ninf;
                 }
-                if (n < Nout) store4<ODT>(out, ((size_t)b * Tq + r) * ldo + n, acc[i][0], acc[i][1]);
+                if (n < Nout) store4<ODT>(out, ((size_t)b * R + row) * ldo + n, acc[i][0], acc[i][1]);
             }
         }
     }
@@ -389,16 +406,21 @@ __global__ void __launch_bounds__(256) k_kv_bmm_dec(const void* __restrict__ x, 
 // whatever the slice size.  The quantization stage then forms p = expf(s - max) / sum for the lane's own elements, rounds it to the
 // dtype and goes on from those bits exactly as it does from a p it loaded; columns a row does not see are +0.  With pout the workgroups
 // of the first column group also store p [BH, Tq, ldp], zeros included (also those past the head's length, before they return).
+//
+// GRP: head bh has R = group * Tq rows (k_kv_bmm_dec), blockIdx.z runs over (head, tile of 16 rows) and a workgroup reduces, quantizes
+// and multiplies the rows of its own tile; sums, xexp, the score rows and p are indexed by (head, row).  A row's visible length is that
+// of its token, row % Tq.  Without GRP `group` is unused here too.
 constexpr int kMaxCps = 16;                               // chunks per slice (the LDS holds their codes)
 constexpr int64_t kSplitGrid = 2048;                      // workgroups the chosen slice size aims to stay within
 
 __device__ __forceinline__ float nan_max(float a, float b) { return a != a ? a : (b != b ? b : (a > b ? a : b)); }
 
-template <int BLK, int DT, bool ATT>
+template <int BLK, int DT, bool ATT, bool GRP = false>
 __global__ void __launch_bounds__(256) k_kv_pv_split(const void* __restrict__ x, const int8_t* __restrict__ vc, int32_t* __restrict__ sums,
                                                      int8_t* __restrict__ xexp, const int32_t* __restrict__ lens, int heads, int Tq, int L,
                                                      int D, int ldx, int cap, int nbw, int cps, int xvec, int xm, float eps_dt,
-                                                     const uint8_t* __restrict__ exp_win, void* __restrict__ pout, int ldp, int causal)
+                                                     const uint8_t* __restrict__ exp_win, void* __restrict__ pout, int ldp, int causal,
+                                                     int group)
 {
     using Blk = I8Blk<BLK>;
     using op_t = typename Blk::op_t;
@@ -409,30 +431,33 @@ __global__ void __launch_bounds__(256) k_kv_pv_split(const void* __restrict__ x,
     __shared__ op_t s_b[kMaxCps][NBS][64];
     __shared__ int8_t s_e[kMaxCps][NBS][16];
     __shared__ float s_red[ATT ? 2 * BFPQ_KV_DEC_MAX_TOKENS * 4 : 1];   // per row and wave: the maximum, then the sum
-    const int bh = blockIdx.z, c0 = (int)blockIdx.y * cps;
+    const int R = GRP ? Tq * group : Tq, ntiles = GRP ? (R + 15) >> 4 : 1;
+    const int bh = GRP ? (int)blockIdx.z / ntiles : (int)blockIdx.z, c0 = (int)blockIdx.y * cps;
+    const int r0 = GRP ? ((int)blockIdx.z % ntiles) * 16 : 0, nr = GRP ? (R - r0 < 16 ? R - r0 : 16) : Tq;   // the tile's first row, its rows
+    auto token = [&](int i) __attribute__((always_inline)) { return GRP ? (r0 + i) % Tq : i; };               // of the tile's row i
     const int len = lens[bh / heads];
     const int Kx = len < L ? (len > 0 ? len : 0) : L;
     const int w = threadIdx.x >> 6, l = threadIdx.x & 63, r = l & 15, q = l >> 4;
-    const bool tok = r < Tq;
-    raw_t* const prow = pout ? reinterpret_cast<raw_t*>(pout) + (size_t)bh * Tq * ldp : nullptr;
+    const bool tok = r < nr;
+    raw_t* const prow = pout ? reinterpret_cast<raw_t*>(pout) + ((size_t)bh * R + r0) * ldp : nullptr;   // the tile's rows of p
     if constexpr (ATT) {
         if (pout && blockIdx.x == 0) {                           // +0 at what the rows do not see of this slice's columns
             const int k0 = c0 << 6, k1 = k0 + (cps << 6) < L ? k0 + (cps << 6) : L;
-            for (int i = threadIdx.x; i < Tq * (k1 - k0); i += 256) {
+            for (int i = threadIdx.x; i < nr * (k1 - k0); i += 256) {
                 const int t = i / (k1 - k0), k = k0 + i % (k1 - k0);
-                if (k >= att_visible(len, Kx, Tq, t, causal)) prow[(size_t)t * ldp + k] = (raw_t)0;
+                if (k >= att_visible(len, Kx, Tq, token(t), causal)) prow[(size_t)t * ldp + k] = (raw_t)0;
             }
         }
     }
     if ((c0 << 6) >= Kx) return;                                 // (the whole workgroup, before any barrier)
     for (int i = threadIdx.x; i < BFPQ_EXP_WIN_ENTRIES; i += 256) s_win[i] = exp_win[i];
-    const float* const srow = reinterpret_cast<const float*>(x) + ((size_t)bh * Tq + (tok ? r : 0)) * ldx;   // (ATT) the lane's score row
+    const float* const srow = reinterpret_cast<const float*>(x) + ((size_t)bh * R + r0 + (tok ? r : 0)) * ldx;   // (ATT) the lane's score row
     float rmax = 0.f, rsum = 1.f;
     int vis = 0;
     if constexpr (ATT) {
-        const float* const sc = reinterpret_cast<const float*>(x) + (size_t)bh * Tq * ldx;
+        const float* const sc = reinterpret_cast<const float*>(x) + ((size_t)bh * R + r0) * ldx;
         const float ninf = -__builtin_inff();
-        // f(v) over the visible elements of row t this thread owns, in ascending order
+        // f(v) over the visible elements of the tile's row t this thread owns, in ascending order
         auto walk = [&](int t, int vt, auto&& f) __attribute__((always_inline)) {
             for (int k = (int)threadIdx.x * 4; k < vt; k += 1024) {
                 const float4 v = *reinterpret_cast<const float4*>(sc + (size_t)t * ldx + k);
@@ -442,18 +467,18 @@ __global__ void __launch_bounds__(256) k_kv_pv_split(const void* __restrict__ x,
                 if (k + 3 < vt) f(v.w);
             }
         };
-        for (int t = 0; t < Tq; t++) {
+        for (int t = 0; t < nr; t++) {
             float m = ninf;
-            walk(t, att_visible(len, Kx, Tq, t, causal), [&](float v) { m = nan_max(m, v); });
+            walk(t, att_visible(len, Kx, Tq, token(t), causal), [&](float v) { m = nan_max(m, v); });
 #pragma unroll
             for (int o = 32; o; o >>= 1) m = nan_max(m, __shfl_xor(m, o, 64));
             if (l == 0) s_red[t * 4 + w] = m;
         }
         __syncthreads();
-        for (int t = 0; t < Tq; t++) {
+        for (int t = 0; t < nr; t++) {
             const float m = nan_max(nan_max(s_red[t * 4], s_red[t * 4 + 1]), nan_max(s_red[t * 4 + 2], s_red[t * 4 + 3]));
             float a = 0.f;
-            walk(t, att_visible(len, Kx, Tq, t, causal), [&](float v) { a += expf(v - m); });
+            walk(t, att_visible(len, Kx, Tq, token(t), causal), [&](float v) { a += expf(v - m); });
 #pragma unroll
             for (int o = 32; o; o >>= 1) a += __shfl_xor(a, o, 64);
             if (l == 0) s_red[(BFPQ_KV_DEC_MAX_TOKENS + t) * 4 + w] = a;
@@ -463,11 +488,11 @@ __global__ void __launch_bounds__(256) k_kv_pv_split(const void* __restrict__ x,
             const float* const sm = s_red + r * 4, * const ss = s_red + (BFPQ_KV_DEC_MAX_TOKENS + r) * 4;
             rmax = nan_max(nan_max(sm[0], sm[1]), nan_max(sm[2], sm[3]));
             rsum = (ss[0] + ss[1]) + (ss[2] + ss[3]);
-            vis = att_visible(len, Kx, Tq, r, causal);
+            vis = att_visible(len, Kx, Tq, token(r), causal);
         }
     } else __syncthreads();
     const int nb = (Kx + BLK - 1) / BLK, nch = (Kx + 63) >> 6, c1 = c0 + cps < nch ? c0 + cps : nch;
-    const raw_t* const xr = reinterpret_cast<const raw_t*>(x) + ((size_t)bh * Tq + (tok ? r : 0)) * ldx;
+    const raw_t* const xr = reinterpret_cast<const raw_t*>(x) + ((size_t)bh * R + r0 + (tok ? r : 0)) * ldx;
 
     for (int c = c0 + w; c < c1; c += 4) {
 #pragma unroll
@@ -525,7 +550,7 @@ __global__ void __launch_bounds__(256) k_kv_pv_split(const void* __restrict__ x,
     if (n0 >= D) return;                                         // (wave-uniform; no barrier below.  D % 16 == 0: 16 whole columns)
     const int8_t* const wrow = vc + ((size_t)bh * D + n0 + r) * cap + Blk::lane(q);
     const v4i magic = {MAGIC_I, MAGIC_I, MAGIC_I, MAGIC_I};
-    const size_t o0 = ((size_t)bh * Tq + (tok ? r : 0)) * nbw;
+    const size_t o0 = ((size_t)bh * R + r0 + (tok ? r : 0)) * nbw;
     for (int c = c0; c < c1; c++) {
 #pragma unroll
         for (int s = 0; s < NBS; s++) {
@@ -599,52 +624,68 @@ __global__ void __launch_bounds__(256) k_kv_advance(int32_t* __restrict__ lens, 
 
 constexpr int64_t kLim = (int64_t)1 << 31;
 
-// the qk product of a device-length cache (arguments checked by the entries): MODE kDev writes the dtype, kAtt the fp32 softmax input
+// the tiles of 16 rows a head's group * Tq rows make
+inline int64_t row_tiles(int64_t Tq, int64_t group) { return (Tq * group + 15) / 16; }
+
+// the qk product of a device-length cache (arguments checked by the entries): MODE kDev writes the dtype, kAtt the fp32 softmax input.
+// x [B, group * Tq, ldx]; group > 1 runs the GRP instances
 template <int MODE>
-void qk_dev(const void* x, const void* wcodes, const int8_t* wexp, void* out, const int32_t* lens, int64_t B, int64_t heads, int64_t Tq, int64_t Kx,
-            int64_t Nout, int64_t ldx, int64_t ldw, int64_t ldwe, int64_t w_bstride, int64_t ldo, int dtype, int block_size, int xm, int wm,
+void qk_dev(const void* x, const void* wcodes, const int8_t* wexp, void* out, const int32_t* lens, int64_t B, int64_t heads, int64_t Tq,
+            int64_t group, int64_t Kx, int64_t Nout, int64_t ldx, int64_t ldw, int64_t ldwe, int64_t w_bstride, int64_t ldo, int dtype, int block_size, int xm, int wm,
             float eps_dt, const uint8_t* exp_win, float scale, int causal, hipStream_t s)
 {
-    const unsigned gy = (unsigned)(B < 65535 ? B : 65535);
+    const int64_t ny = B * row_tiles(Tq, group);
+    const unsigned gy = (unsigned)(ny < 65535 ? ny : 65535);
     with_block(block_size, [&](auto blk) {
         with_dtype(dtype, [&](auto dt) {
-            constexpr int TM = decltype(blk)::value == 64 ? 4 : 2;
-            hipLaunchKernelGGL((k_kv_bmm_dec<decltype(blk)::value, decltype(dt)::value, TM, MODE>),
-                               dim3((unsigned)((Nout + 64 * TM - 1) / (64 * TM)), gy), dim3(256), 0, s, x, (const int8_t*)wcodes, wexp, out, (int)B,
-                               (int)Tq, (int)Kx, (int)Nout, (int)ldx, (int)ldw, (int)ldwe, (int)w_bstride, (int)ldo, xm, wm, eps_dt, exp_win, lens,
-                               (int)heads, scale, causal);
+            auto go = [&](auto grp) {
+                constexpr int TM = decltype(blk)::value == 64 ? 4 : 2;
+                hipLaunchKernelGGL((k_kv_bmm_dec<decltype(blk)::value, decltype(dt)::value, TM, MODE, decltype(grp)::value>),
+                                   dim3((unsigned)((Nout + 64 * TM - 1) / (64 * TM)), gy), dim3(256), 0, s, x, (const int8_t*)wcodes, wexp, out, (int)B,
+                                   (int)Tq, (int)Kx, (int)Nout, (int)ldx, (int)ldw, (int)ldwe, (int)w_bstride, (int)ldo, xm, wm, eps_dt, exp_win, lens,
+                                   (int)heads, scale, causal, (int)group);
+            };
+            if (group > 1) go(std::true_type{});
+            else go(std::false_type{});
         });
     });
 }
 
-// the split p v product and its combine pass (arguments checked by the entries).  ATT: x holds fp32 score rows (k_kv_pv_split)
+// the split p v product and its combine pass (arguments checked by the entries).  ATT: x holds fp32 score rows (k_kv_pv_split).
+// x and out hold R = group * Tq rows per head; the combine pass works per row and takes R for its Tq
 template <bool ATT>
-int pv_dev(const void* x, const void* wcodes, const int8_t* wexp, void* out, const int32_t* lens, int64_t B, int64_t heads, int64_t Tq, int64_t Kx,
-           int64_t D, int64_t ldx, int64_t ldw, int64_t ldwe, int64_t ldo, int dtype, int block_size, int xm, int wm, float eps_dt,
+int pv_dev(const void* x, const void* wcodes, const int8_t* wexp, void* out, const int32_t* lens, int64_t B, int64_t heads, int64_t Tq,
+           int64_t group, int64_t Kx, int64_t D, int64_t ldx, int64_t ldw, int64_t ldwe, int64_t ldo, int dtype, int block_size, int xm, int wm, float eps_dt,
            const uint8_t* exp_win, void* ws, int64_t chunks_per_split, void* pout, int64_t ldp, int causal, hipStream_t s)
 {
     const int64_t nb = (Kx + block_size - 1) / block_size, nch = (Kx + 63) / 64, dg = (D + 63) / 64;
+    const int64_t R = group * Tq, gz = B * row_tiles(Tq, group);  // a workgroup per (head, row tile) on the grid's z
     int64_t cps = chunks_per_split;
     if (cps == 0)                                                 // the shortest slices that keep the grid within kSplitGrid workgroups
-        for (cps = 1; cps < kMaxCps && (nch + cps - 1) / cps * dg * B > kSplitGrid; cps++) {}
+        for (cps = 1; cps < kMaxCps && (nch + cps - 1) / cps * dg * gz > kSplitGrid; cps++) {}
     const int64_t slices = (nch + cps - 1) / cps;
-    if (slices > 65535) return BFPQ_E_UNSUPPORTED;
+    if (slices > 65535 || gz > 65535) return BFPQ_E_UNSUPPORTED;
     int32_t* const sums = (int32_t*)ws;
-    int8_t* const xexp = (int8_t*)ws + B * Tq * nb * 4 * D;
+    int8_t* const xexp = (int8_t*)ws + B * R * nb * 4 * D;
     const int xvec = !ATT && (reinterpret_cast<uintptr_t>(x) & 15u) == 0 && (ldx * bfpq_dev::dtype_size(dtype)) % 16 == 0;
     with_block(block_size, [&](auto blk) {
         with_dtype(dtype, [&](auto dt) {
-            hipLaunchKernelGGL((k_kv_pv_split<decltype(blk)::value, decltype(dt)::value, ATT>), dim3((unsigned)dg, (unsigned)slices, (unsigned)B),
-                               dim3(256), 0, s, x, (const int8_t*)wcodes, sums, xexp, lens, (int)heads, (int)Tq, (int)Kx, (int)D, (int)ldx, (int)ldw,
-                               (int)nb, (int)cps, xvec, xm, eps_dt, exp_win, pout, (int)ldp, causal);
+            auto go = [&](auto grp) {
+                hipLaunchKernelGGL((k_kv_pv_split<decltype(blk)::value, decltype(dt)::value, ATT, decltype(grp)::value>),
+                                   dim3((unsigned)dg, (unsigned)slices, (unsigned)gz), dim3(256), 0, s, x, (const int8_t*)wcodes, sums, xexp, lens,
+                                   (int)heads, (int)Tq, (int)Kx, (int)D, (int)ldx, (int)ldw, (int)nb, (int)cps, xvec, xm, eps_dt, exp_win, pout,
+                                   (int)ldp, causal, (int)group);
+            };
+            if (group > 1) go(std::true_type{});
+            else go(std::false_type{});
         });
     });
     const int rc = (int)hipGetLastError();
     if (rc) return rc;
-    const int64_t total = B * Tq * (D / 4);
+    const int64_t total = B * R * (D / 4);
     with_dtype(dtype, [&](auto dt) {
         hipLaunchKernelGGL((k_kv_pv_combine<decltype(dt)::value>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, sums, xexp, wexp, out, lens,
-                           (int)heads, total, (int)Tq, (int)Kx, (int)D, (int)ldwe, (int)nb, (int)ldo, block_size, xm, wm);
+                           (int)heads, total, (int)R, (int)Kx, (int)D, (int)ldwe, (int)nb, (int)ldo, block_size, xm, wm);
     });
     return (int)hipGetLastError();
 }
@@ -707,7 +748,7 @@ int bfpq_kv_bmm_dec(const void* x, const void* wcodes, const int8_t* wexp, void*
                 hipLaunchKernelGGL((k_kv_bmm_dec<decltype(blk)::value, decltype(dt)::value, TM, kHost>),
                                    dim3((unsigned)((Nout + 64 * TM - 1) / (64 * TM)), gy), dim3(256), 0, s, x, (const int8_t*)wcodes, wexp, out, (int)B,
                                    (int)Tq, (int)Kx, (int)Nout, (int)ldx, (int)ldw, (int)ldwe, (int)w_bstride, (int)ldo, x_mant_bits, w_mant_bits,
-                                   eps_dt, exp_win, nullptr, 1, 1.f, 0);
+                                   eps_dt, exp_win, nullptr, 1, 1.f, 0, 1);
             };
             // rows per wave: 64 (32 at the small blocks) of the many cached keys, 16 of V's D columns
             if (family == BFPQ_KV_PV) go(std::integral_constant<int, 1>{});
@@ -764,20 +805,22 @@ int64_t bfpq_kv_dec_ws_bytes(int64_t B, int64_t Tq, int64_t D, int64_t L, int bl
     return (B * Tq * nbw * (4 * D + 1) + 15) / 16 * 16;           // the int32 block sums, then x's block exponents
 }
 
-int bfpq_kv_bmm_dec_dev(const void* x, const void* wcodes, const int8_t* wexp, void* out, const int32_t* lens, int64_t B, int64_t heads,
-                        int64_t Tq, int64_t Kx, int64_t Nout, int64_t ldx, int64_t ldw, int64_t ldwe, int64_t w_bstride, int64_t ldo, int family,
-                        int dtype, int block_size, int x_mant_bits, int w_mant_bits, double epsilon, const uint8_t* exp_win, void* ws,
-                        int64_t ws_bytes, int64_t chunks_per_split, void* stream)
+int bfpq_kv_bmm_dec_gqa(const void* x, const void* wcodes, const int8_t* wexp, void* out, const int32_t* lens, int64_t B, int64_t heads,
+                        int64_t Tq, int64_t group, int64_t Kx, int64_t Nout, int64_t ldx, int64_t ldw, int64_t ldwe, int64_t w_bstride,
+                        int64_t ldo, int family, int dtype, int block_size, int x_mant_bits, int w_mant_bits, double epsilon,
+                        const uint8_t* exp_win, void* ws, int64_t ws_bytes, int64_t chunks_per_split, void* stream)
 {
     if (!dtype_ok(dtype) || !i8_block_ok(block_size) || !i8_mant_ok(x_mant_bits) || !i8_mant_ok(w_mant_bits) ||
-        (family != BFPQ_KV_QK && family != BFPQ_KV_PV) || B < 0 || Tq < 0 || Nout < 0 || Kx < 0 || heads < 1 || B % heads != 0 ||
+        (family != BFPQ_KV_QK && family != BFPQ_KV_PV) || B < 0 || Tq < 0 || Nout < 0 || Kx < 0 || heads < 1 || B % heads != 0 || group < 1 ||
         chunks_per_split < 0)
         return BFPQ_E_ARG;
     if (B == 0 || Tq == 0) return 0;
-    const int64_t nb = (Kx + block_size - 1) / block_size;
-    if (Tq > BFPQ_KV_DEC_MAX_TOKENS || Kx < 1 || Nout < 1 || (family == BFPQ_KV_QK ? Kx % block_size != 0 : (Nout % 16 != 0 || Nout > 1024)) ||
+    const int64_t nb = (Kx + block_size - 1) / block_size, R = Tq * group;
+    if (Tq > BFPQ_KV_DEC_MAX_TOKENS || group >= kLim || Kx < 1 || Nout < 1 ||
+        (family == BFPQ_KV_QK ? Kx % block_size != 0 : (Nout % 16 != 0 || Nout > 1024)) ||
         ldx < Kx || ldw % 64 != 0 || ldw < (Kx + 63) / 64 * 64 || ldwe < nb || w_bstride < Nout || ldo % 4 != 0 || ldo < Nout ||
-        w_bstride * ldw >= kLim || w_bstride * ldwe >= kLim || Tq * ldx >= kLim || Tq * ldo >= kLim || chunks_per_split > kMaxCps)
+        w_bstride * ldw >= kLim || w_bstride * ldwe >= kLim || R * ldx >= kLim || R * ldo >= kLim ||
+        B * row_tiles(Tq, group) >= kLim || chunks_per_split > kMaxCps)
         return BFPQ_E_UNSUPPORTED;
     if (!x || !wcodes || !wexp || !out || !lens || !exp_win || !aligned16(wcodes, out) || (reinterpret_cast<uintptr_t>(lens) & 3u) ||
         (reinterpret_cast<uintptr_t>(x) & (dtype == BFPQ_F32 ? 3u : 1u)))
@@ -785,16 +828,25 @@ int bfpq_kv_bmm_dec_dev(const void* x, const void* wcodes, const int8_t* wexp, v
     const float eps_dt = bfpq_dev::h_round((float)epsilon, dtype);
     hipStream_t s = (hipStream_t)stream;
     if (family == BFPQ_KV_QK) {
-        qk_dev<kDev>(x, wcodes, wexp, out, lens, B, heads, Tq, Kx, Nout, ldx, ldw, ldwe, w_bstride, ldo, dtype, block_size, x_mant_bits, w_mant_bits,
+        qk_dev<kDev>(x, wcodes, wexp, out, lens, B, heads, Tq, group, Kx, Nout, ldx, ldw, ldwe, w_bstride, ldo, dtype, block_size, x_mant_bits, w_mant_bits,
                      eps_dt, exp_win, 1.f, 0, s);
         return (int)hipGetLastError();
     }
-    // p v: w_bstride == Nout == D rows per head (the sums are laid out by D)
-    const int64_t need = bfpq_kv_dec_ws_bytes(B, Tq, Nout, Kx, block_size);
-    if (w_bstride != Nout || B > 65535 || need < 0 || ws_bytes < need) return BFPQ_E_UNSUPPORTED;
+    // p v: w_bstride == Nout == D rows per head (the sums are laid out by D); a workgroup per (head, row tile) on the grid's z
+    const int64_t need = bfpq_kv_dec_ws_bytes(B * group, Tq, Nout, Kx, block_size);
+    if (w_bstride != Nout || B * row_tiles(Tq, group) > 65535 || need < 0 || ws_bytes < need) return BFPQ_E_UNSUPPORTED;
     if (!ws || !aligned16(ws)) return BFPQ_E_ARG;
-    return pv_dev<false>(x, wcodes, wexp, out, lens, B, heads, Tq, Kx, Nout, ldx, ldw, ldwe, ldo, dtype, block_size, x_mant_bits, w_mant_bits, eps_dt,
-                         exp_win, ws, chunks_per_split, nullptr, 0, 0, s);
+    return pv_dev<false>(x, wcodes, wexp, out, lens, B, heads, Tq, group, Kx, Nout, ldx, ldw, ldwe, ldo, dtype, block_size, x_mant_bits, w_mant_bits,
+                         eps_dt, exp_win, ws, chunks_per_split, nullptr, 0, 0, s);
+}
+
+int bfpq_kv_bmm_dec_dev(const void* x, const void* wcodes, const int8_t* wexp, void* out, const int32_t* lens, int64_t B, int64_t heads,
+                        int64_t Tq, int64_t Kx, int64_t Nout, int64_t ldx, int64_t ldw, int64_t ldwe, int64_t w_bstride, int64_t ldo, int family,
+                        int dtype, int block_size, int x_mant_bits, int w_mant_bits, double epsilon, const uint8_t* exp_win, void* ws,
+                        int64_t ws_bytes, int64_t chunks_per_split, void* stream)
+{
+    return bfpq_kv_bmm_dec_gqa(x, wcodes, wexp, out, lens, B, heads, Tq, 1, Kx, Nout, ldx, ldw, ldwe, w_bstride, ldo, family, dtype, block_size,
+                               x_mant_bits, w_mant_bits, epsilon, exp_win, ws, ws_bytes, chunks_per_split, stream);
 }
 
 int64_t bfpq_kv_attend_ws_bytes(int64_t B, int64_t Tq, int64_t L)
@@ -804,22 +856,23 @@ int64_t bfpq_kv_attend_ws_bytes(int64_t B, int64_t Tq, int64_t L)
     return (B * Tq * ((L + 3) / 4 * 4) * 4 + 15) / 16 * 16;       // the fp32 score rows, pitch L rounded up to 4
 }
 
-int bfpq_kv_attend(const void* q, const void* k_codes, const int8_t* k_exps, const void* v_codes, const int8_t* v_exps, void* out, void* p_out,
-                   const int32_t* lens, int64_t BH, int64_t heads, int64_t Tq, int64_t D, int64_t max_len, int64_t cap, int64_t ldd, int64_t ldo,
-                   int64_t ldp, double scale, int causal, int dtype, int block_size, int x_mant_bits, int w_mant_bits, double epsilon,
-                   const uint8_t* exp_win, void* score_ws, int64_t score_ws_bytes, void* sum_ws, int64_t sum_ws_bytes, int64_t chunks_per_split,
-                   void* stream)
+int bfpq_kv_attend_gqa(const void* q, const void* k_codes, const int8_t* k_exps, const void* v_codes, const int8_t* v_exps, void* out, void* p_out,
+                       const int32_t* lens, int64_t BH, int64_t heads, int64_t Tq, int64_t group, int64_t D, int64_t max_len, int64_t cap,
+                       int64_t ldd, int64_t ldo, int64_t ldp, double scale, int causal, int dtype, int block_size, int x_mant_bits,
+                       int w_mant_bits, double epsilon, const uint8_t* exp_win, void* score_ws, int64_t score_ws_bytes, void* sum_ws,
+                       int64_t sum_ws_bytes, int64_t chunks_per_split, void* stream)
 {
     if (!dtype_ok(dtype) || !i8_block_ok(block_size) || !i8_mant_ok(x_mant_bits) || !i8_mant_ok(w_mant_bits) || BH < 0 || Tq < 0 || heads < 1 ||
-        BH % heads != 0 || chunks_per_split < 0 || (causal != 0 && causal != 1) || !(scale - scale == 0.0) || !((float)scale - (float)scale == 0.f))
+        BH % heads != 0 || group < 1 || chunks_per_split < 0 || (causal != 0 && causal != 1) || !(scale - scale == 0.0) || !((float)scale - (float)scale == 0.f))
         return BFPQ_E_ARG;
     if (BH == 0 || Tq == 0) return 0;
-    const int64_t pitch = (max_len + 3) / 4 * 4;
-    if (!bfpq_kv_ok(D, cap, block_size) || Tq > BFPQ_KV_DEC_MAX_TOKENS || max_len < 1 || max_len > cap || ldd < D || ldd % 64 != 0 || ldo % 4 != 0 ||
-        ldo < D || (p_out && ldp < max_len) || cap * ldd >= kLim || Tq * ldo >= kLim || Tq * pitch >= kLim || (p_out && Tq * ldp >= kLim) ||
-        BH > 65535 || chunks_per_split > kMaxCps)
+    const int64_t pitch = (max_len + 3) / 4 * 4, R = Tq * group;
+    if (!bfpq_kv_ok(D, cap, block_size) || Tq > BFPQ_KV_DEC_MAX_TOKENS || group >= kLim || max_len < 1 || max_len > cap || ldd < D ||
+        ldd % 64 != 0 || ldo % 4 != 0 || ldo < D || (p_out && ldp < max_len) || cap * ldd >= kLim || R * ldo >= kLim ||
+        R * pitch >= kLim || (p_out && R * ldp >= kLim) || BH * row_tiles(Tq, group) > 65535 ||
+        chunks_per_split > kMaxCps)
         return BFPQ_E_UNSUPPORTED;
-    const int64_t need_s = bfpq_kv_attend_ws_bytes(BH, Tq, max_len), need_p = bfpq_kv_dec_ws_bytes(BH, Tq, D, max_len, block_size);
+    const int64_t need_s = bfpq_kv_attend_ws_bytes(BH * group, Tq, max_len), need_p = bfpq_kv_dec_ws_bytes(BH * group, Tq, D, max_len, block_size);
     if (need_s < 0 || need_p < 0 || score_ws_bytes < need_s || sum_ws_bytes < need_p) return BFPQ_E_UNSUPPORTED;
     const uintptr_t emask = dtype == BFPQ_F32 ? 3u : 1u;
     if (!q || !k_codes || !k_exps || !v_codes || !v_exps || !out || !lens || !exp_win || !score_ws || !sum_ws ||
@@ -828,12 +881,23 @@ int bfpq_kv_attend(const void* q, const void* k_codes, const int8_t* k_exps, con
         return BFPQ_E_ARG;
     const float eps_dt = bfpq_dev::h_round((float)epsilon, dtype);
     hipStream_t s = (hipStream_t)stream;
-    qk_dev<kAtt>(q, k_codes, k_exps, score_ws, lens, BH, heads, Tq, D, max_len, D, ldd, D / block_size, cap, pitch, dtype, block_size, x_mant_bits,
+    qk_dev<kAtt>(q, k_codes, k_exps, score_ws, lens, BH, heads, Tq, group, D, max_len, D, ldd, D / block_size, cap, pitch, dtype, block_size, x_mant_bits,
                  w_mant_bits, eps_dt, exp_win, (float)scale, causal, s);
     const int rc = (int)hipGetLastError();
     if (rc) return rc;
-    return pv_dev<true>(score_ws, v_codes, v_exps, out, lens, BH, heads, Tq, max_len, D, pitch, cap, cap / block_size, ldo, dtype, block_size, x_mant_bits,
-                        w_mant_bits, eps_dt, exp_win, sum_ws, chunks_per_split, p_out, ldp, causal, s);
+    return pv_dev<true>(score_ws, v_codes, v_exps, out, lens, BH, heads, Tq, group, max_len, D, pitch, cap, cap / block_size, ldo, dtype, block_size,
+                        x_mant_bits, w_mant_bits, eps_dt, exp_win, sum_ws, chunks_per_split, p_out, ldp, causal, s);
+}
+
+int bfpq_kv_attend(const void* q, const void* k_codes, const int8_t* k_exps, const void* v_codes, const int8_t* v_exps, void* out, void* p_out,
+                   const int32_t* lens, int64_t BH, int64_t heads, int64_t Tq, int64_t D, int64_t max_len, int64_t cap, int64_t ldd, int64_t ldo,
+                   int64_t ldp, double scale, int causal, int dtype, int block_size, int x_mant_bits, int w_mant_bits, double epsilon,
+                   const uint8_t* exp_win, void* score_ws, int64_t score_ws_bytes, void* sum_ws, int64_t sum_ws_bytes, int64_t chunks_per_split,
+                   void* stream)
+{
+    return bfpq_kv_attend_gqa(q, k_codes, k_exps, v_codes, v_exps, out, p_out, lens, BH, heads, Tq, 1, D, max_len, cap, ldd, ldo, ldp, scale, causal,
+                              dtype, block_size, x_mant_bits, w_mant_bits, epsilon, exp_win, score_ws, score_ws_bytes, sum_ws, sum_ws_bytes,
+                              chunks_per_split, stream);
 }
 
 }  // extern "C"

@@ -115,6 +115,8 @@ PROTOTYPES = {
     "bfpq_kv_bmm_dec_dev": (_i32, [_vp] * 5 + [_i64] * 10 + [_i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _i64, _i64, _vp]),
     "bfpq_kv_attend_ws_bytes": (_i64, [_i64, _i64, _i64]),
     "bfpq_kv_attend": (_i32, [_vp] * 8 + [_i64] * 9 + [_dbl, _i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _i64, _vp, _i64, _i64, _vp]),
+    "bfpq_kv_bmm_dec_gqa": (_i32, [_vp] * 5 + [_i64] * 11 + [_i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _i64, _i64, _vp]),
+    "bfpq_kv_attend_gqa": (_i32, [_vp] * 8 + [_i64] * 10 + [_dbl, _i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _i64, _vp, _i64, _i64, _vp]),
 }
 
 
@@ -1477,15 +1479,27 @@ def kv_dec_ws_bytes(BH, Tq, D, L, block_size):
     return n
 
 
-def kv_bmm_dec_dev(x, wc, we, family, bound, w_bstride, lengths, heads, block_size, mant_bits, epsilon, ws=None, chunks_per_split=0):
-    """kv_bmm_dec with head b's cached length read from lengths[b // heads] on the device (bfpq_kv_bmm_dec_dev).  KV_QK: x [BH, Tq, D],
+def _kv_group(what, rows, group):
+    """the query rows per head of `rows` = group * Tq rows of a kv head serving `group` query heads"""
+    if isinstance(group, bool) or not isinstance(group, int) or group < 1:
+        raise ValueError(f"{what}: group must be an int >= 1 (got {group!r})")
+    if rows % group:
+        raise ValueError(f"{what}: {rows} rows per kv head are no multiple of group = {group}")
+    return rows // group
+
+
+def kv_bmm_dec_dev(x, wc, we, family, bound, w_bstride, lengths, heads, block_size, mant_bits, epsilon, ws=None, chunks_per_split=0, group=1):
+    """kv_bmm_dec with head b's cached length read from lengths[b // heads] on the device (bfpq_kv_bmm_dec_gqa).  KV_QK: x [BH, Tq, D],
     bound = max_len; returns [BH, Tq, max_len], -inf from the length on.  KV_PV: x [BH, Tq, L], bound = D; returns [BH, Tq, D]; ws: a
     uint8 tensor of at least kv_dec_ws_bytes(BH, Tq, D, L, block_size) bytes; chunks_per_split: 64-token chunks per slice of the
-    contraction, 0 = the library's choice (the result does not depend on it)."""
+    contraction, 0 = the library's choice (the result does not depend on it).  group > 1 (grouped-query attention): the BH cached heads
+    serve `group` query heads each, x and the result hold group * Tq rows per cached head -- query head r // Tq of the group, token
+    r % Tq -- and the workspace is that of BH * group heads."""
     require_device_tensor(x, "x")
     if x.dim() != 3:
         raise ValueError(f"kv_bmm_dec_dev takes x [BH, Tq, Kx] (got {tuple(x.shape)})")
-    BH, Tq, Kx = x.shape
+    BH, R, Kx = x.shape
+    Tq = _kv_group("kv_bmm_dec_dev", R, group)
     x = x.contiguous()
     dev = x.device
     heads = int(heads)
@@ -1499,19 +1513,19 @@ def kv_bmm_dec_dev(x, wc, we, family, bound, w_bstride, lengths, heads, block_si
     Nout = int(bound)
     ws_bytes = 0
     if family == KV_PV:
-        need = kv_dec_ws_bytes(BH, Tq, Nout, Kx, block_size)
+        need = kv_dec_ws_bytes(BH * group, Tq, Nout, Kx, block_size)
         if (not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or ws.device != dev or not ws.is_contiguous()
                 or ws.numel() < need):
             raise ValueError(f"kv_bmm_dec_dev: ws must be a contiguous uint8 tensor of at least {need} bytes on {dev}")
         ws_bytes = ws.numel()
     ldo = (Nout + 3) // 4 * 4
     with torch.cuda.device(dev):
-        out = torch.empty((BH, Tq, ldo), dtype=x.dtype, device=dev)
-        check(load_library().bfpq_kv_bmm_dec_dev(_ptr(x), _ptr(wc), _ptr(we), _ptr(out), _ptr(lengths), BH, heads, Tq, Kx, Nout, Kx, wc.shape[-1],
-                                                 we.shape[-1], int(w_bstride), ldo, int(family), DTYPE_CODE[x.dtype], int(block_size),
-                                                 int(mant_bits), int(mant_bits), float(epsilon), _ptr(exp_window_dev(x.dtype, dev)),
-                                                 _ptr(ws if family == KV_PV else None), ws_bytes, int(chunks_per_split), _stream(x)),
-              "bfpq_kv_bmm_dec_dev")
+        out = torch.empty((BH, R, ldo), dtype=x.dtype, device=dev)
+        check(load_library().bfpq_kv_bmm_dec_gqa(_ptr(x), _ptr(wc), _ptr(we), _ptr(out), _ptr(lengths), BH, heads, Tq, group, Kx, Nout, Kx,
+                                                 wc.shape[-1], we.shape[-1], int(w_bstride), ldo, int(family), DTYPE_CODE[x.dtype],
+                                                 int(block_size), int(mant_bits), int(mant_bits), float(epsilon),
+                                                 _ptr(exp_window_dev(x.dtype, dev)), _ptr(ws if family == KV_PV else None), ws_bytes,
+                                                 int(chunks_per_split), _stream(x)), "bfpq_kv_bmm_dec_gqa")
     return out[:, :, :Nout] if ldo != Nout else out
 
 
@@ -1524,14 +1538,16 @@ def kv_attend_ws_bytes(BH, Tq, max_len):
 
 
 def kv_attend(q, k_codes, k_exps, v_codes, v_exps, lengths, heads, max_len, scale, causal, block_size, mant_bits, epsilon, score_ws, sum_ws,
-              chunks_per_split=0, return_probs=False):
-    """scores, scale, softmax and context of q [BH, Tq, D] against a device-length cache in three launches (bfpq_kv_attend): returns
+              chunks_per_split=0, return_probs=False, group=1):
+    """scores, scale, softmax and context of q [BH, Tq, D] against a device-length cache in three launches (bfpq_kv_attend_gqa): returns
     (context [BH, Tq, D], p [BH, Tq, max_len] or None).  score_ws / sum_ws: contiguous uint8 tensors of at least
-    kv_attend_ws_bytes(BH, Tq, max_len) / kv_dec_ws_bytes(BH, Tq, D, max_len, block_size) bytes.  Nothing is read back."""
+    kv_attend_ws_bytes(BH, Tq, max_len) / kv_dec_ws_bytes(BH, Tq, D, max_len, block_size) bytes.  Nothing is read back.  group > 1: rows
+    and workspaces as kv_bmm_dec_dev takes them (q, the context and p hold group * Tq rows per cached head; causal goes by the token)."""
     require_device_tensor(q, "q")
     if q.dim() != 3:
         raise ValueError(f"kv_attend takes q [BH, Tq, D] (got {tuple(q.shape)})")
-    BH, Tq, D = q.shape
+    BH, R, D = q.shape
+    Tq = _kv_group("kv_attend", R, group)
     q = q.contiguous()
     dev = q.device
     heads = int(heads)
@@ -1550,18 +1566,18 @@ def kv_attend(q, k_codes, k_exps, v_codes, v_exps, lengths, heads, max_len, scal
     max_len, scale = int(max_len), float(scale)
     if not math.isfinite(scale) or abs(scale) > torch.finfo(torch.float32).max:
         raise ValueError(f"kv_attend: scale must be finite in fp32 (got {scale})")
-    need = (kv_attend_ws_bytes(BH, Tq, max_len), kv_dec_ws_bytes(BH, Tq, D, max_len, block_size))
+    need = (kv_attend_ws_bytes(BH * group, Tq, max_len), kv_dec_ws_bytes(BH * group, Tq, D, max_len, block_size))
     for name, ws, n in (("score_ws", score_ws, need[0]), ("sum_ws", sum_ws, need[1])):
         if not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or ws.device != dev or not ws.is_contiguous() or ws.numel() < n:
             raise ValueError(f"kv_attend: {name} must be a contiguous uint8 tensor of at least {n} bytes on {dev}")
     with torch.cuda.device(dev):
-        out = torch.empty((BH, Tq, D), dtype=q.dtype, device=dev)
-        p = torch.empty((BH, Tq, max_len), dtype=q.dtype, device=dev) if return_probs else None
-        check(load_library().bfpq_kv_attend(_ptr(q), _ptr(k_codes), _ptr(k_exps), _ptr(v_codes), _ptr(v_exps), _ptr(out), _ptr(p), _ptr(lengths),
-                                            BH, heads, Tq, D, max_len, cap, ldd, D, max_len, scale, int(bool(causal)), DTYPE_CODE[q.dtype],
-                                            int(block_size), int(mant_bits), int(mant_bits), float(epsilon),
-                                            _ptr(exp_window_dev(q.dtype, dev)), _ptr(score_ws), score_ws.numel(), _ptr(sum_ws), sum_ws.numel(),
-                                            int(chunks_per_split), _stream(q)), "bfpq_kv_attend")
+        out = torch.empty((BH, R, D), dtype=q.dtype, device=dev)
+        p = torch.empty((BH, R, max_len), dtype=q.dtype, device=dev) if return_probs else None
+        check(load_library().bfpq_kv_attend_gqa(_ptr(q), _ptr(k_codes), _ptr(k_exps), _ptr(v_codes), _ptr(v_exps), _ptr(out), _ptr(p),
+                                                _ptr(lengths), BH, heads, Tq, group, D, max_len, cap, ldd, D, max_len, scale, int(bool(causal)),
+                                                DTYPE_CODE[q.dtype], int(block_size), int(mant_bits), int(mant_bits), float(epsilon),
+                                                _ptr(exp_window_dev(q.dtype, dev)), _ptr(score_ws), score_ws.numel(), _ptr(sum_ws),
+                                                sum_ws.numel(), int(chunks_per_split), _stream(q)), "bfpq_kv_attend_gqa")
     return out, p
 
 
