@@ -10,6 +10,10 @@ scores, softmax, context; modeling_gpt2.py:345-348 with :207, 243) on one MI355X
   attend the device leg's cache and replay with scores, scale, softmax and context as the one call cache.attend(q, scale),
   gqa    (--case gqa_*: grouped-query attention) the attend leg on HBFPKVCache(kv_heads=...) fed the kv_heads key / value
          heads, against twin: the attend leg on the cache without kv_heads fed repeat_kv of them (both legs block 64, alternating),
+  prompt (--case prompt_*: prompt attention) one step = append(prompt) + attend(q, causal=True) of a whole prompt of T tokens
+         on an empty HBFPKVCache(prompt_rows=P), against loop16: what the cache can do without prompt_rows on the same tokens, ceil(T / 16)
+         non-causal 16-row attend calls (a cost yardstick only), and matmul: the prompt route without it, mm(q, k^T), torch's softmax
+         with a causal mask and mm(p, v) on F_matmul_bfp(matrix_unit='int8'), plus the append the cache still needs (all block 64),
 and, for the cache alone, the append of a prefill chunk of S tokens.  Method of bench_matmul.py: hipGraph replay, the median of the
 replays, the legs alternating round by round in one process.  (A captured append writes at the captured position: every replay redoes the
 same step, which is what is timed.)  On a tree without the cache the cache columns are null and "cache" says "absent".
@@ -141,6 +145,76 @@ def run_gqa(name, iters, rounds, out, cps, kv_heads=None, only=None):
     json.dump((json.load(open(out)) if os.path.exists(out) else []) + rows, open(out, "w"), indent=1)
 
 
+# name: (batch, heads, kv_heads, T, head_dim, prompt_rows)
+PROMPT = {"prompt_gpt2s_b8_t1024": (8, 12, 12, 1024, 64, 256), "prompt_h32_d128_b1_t2048": (1, 32, 32, 2048, 128, 512),
+          "prompt_h32_kv8_b1_t2048": (1, 32, 8, 2048, 128, 512)}
+
+
+def run_prompt(name, iters, rounds, out, prompt_rows=None, only=None):
+    """the legs prompt, loop16 and matmul of a prompt case, bf16 and fp32 at block 64 (only: one leg alone, bf16: what a kernel trace is
+    taken from).  Every step starts from an empty cache: it zeroes the lengths, appends the T tokens and attends"""
+    import torch
+    import quantization_sparsity_interplay_amd as bfpq
+    from quantization_sparsity_interplay_amd.bfp import bfp_ops
+    dev = "cuda:0"
+    batch, heads, kvh, T, D, P = PROMPT[name]
+    P = prompt_rows or P
+    g = heads // kvh
+    c = CONFIGS["hbfp8_b64"]
+    scale = 1.0 / D ** 0.5
+    rows = []
+    for dname in DTYPES if only is None else ("bf16",):
+        dt = dict(bf16=torch.bfloat16, fp32=torch.float32)[dname]
+        gen = torch.Generator().manual_seed(1)
+        k, v = (torch.randn(batch, kvh, T, D, generator=gen).to(dt).to(dev) for _ in range(2))
+        q = torch.randn(batch, heads, T, D, generator=gen).to(dt).to(dev)
+        i8 = bfp_ops.F_matmul_bfp(matrix_unit='int8', **bfpq.BFPConfig.hbfp(c['mant_bits'] + 1, c['block_size']).to_kwargs())
+        if hasattr(bfp_ops, 'MATMUL_I8_MIN'):
+            bfp_ops.MATMUL_I8_MIN = {key: 1 for key in bfp_ops.MATMUL_I8_MIN}          # time the route itself: every default floor off
+        mk = lambda **mode: i8.kv_cache(batch, heads, D, T, dtype=dt, device=dev, device_lengths=True, kv_heads=kvh, **mode)
+        caches = dict(prompt=mk(prompt_rows=P), loop16=mk(), matmul=mk())
+        mask = ~torch.ones(T, T, dtype=torch.bool, device=dev).tril()
+        q16 = [q[:, :, i:i + 16].contiguous() for i in range(0, T, 16)]
+
+        def fill(cache):
+            cache.lengths.zero_()
+            cache.append(k, v)
+
+        def prompt_step():
+            fill(caches['prompt'])
+            return caches['prompt'].attend(q, scale, causal=True)
+
+        def loop16_step():
+            fill(caches['loop16'])
+            return [caches['loop16'].attend(x, scale) for x in q16]
+
+        def matmul_step():
+            fill(caches['matmul'])
+            kr, vr = (x.repeat_interleave(g, dim=1) for x in (k, v)) if g > 1 else (k, v)   # repeat_kv (modeling_llama.py:264-273)
+            s = i8(q, kr.transpose(-1, -2)).float() * scale
+            return i8(torch.softmax(s.masked_fill(mask, float('-inf')), dim=-1).to(dt), vr)
+
+        steps = dict(prompt=prompt_step, loop16=loop16_step, matmul=matmul_step)
+        legs = [leg for leg in steps if only in (None, leg)]
+        with torch.no_grad():
+            for leg in legs:
+                if leg != 'matmul':
+                    caches[leg].prepare_attend()
+            calls = i8.matmul_stats.i8_calls, i8.matmul_stats.fake_calls
+            med, spread = replay_times([steps[leg] for leg in legs], iters, rounds)
+        row = dict(shape=name, batch=batch, heads=heads, kv_heads=kvh, T=T, head_dim=D, dtype=dname, config="hbfp8_b64", iters=iters, rounds=rounds,
+                   prompt_rows=P, panel_ws_bytes=caches['prompt']._rows_ws.numel() if caches['prompt']._rows_ws is not None else None)
+        for leg, m, sp in zip(legs, med, spread):
+            assert caches[leg].overflow.item() == 0 and caches[leg].lengths.tolist() == [T] * batch
+            row.update({f"{leg}_us": m, f"{leg}_min_max_us": sp})
+        if 'matmul' in legs:
+            assert i8.matmul_stats.i8_calls > calls[0] and i8.matmul_stats.fake_calls == calls[1]    # both products on the int8 route
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    json.dump((json.load(open(out)) if os.path.exists(out) else []) + rows, open(out, "w"), indent=1)
+
+
 def run_attend_only(shape, iters, rounds, out, cps):
     """the attend leg alone, bf16 at block 64: what a kernel trace of one step is taken from (--attend-only)"""
     import torch
@@ -257,7 +331,9 @@ def merge_parent(out, parent_json):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--case", choices=sorted(SHAPES) + sorted(RAGGED) + sorted(GQA))
+    ap.add_argument("--case", choices=sorted(SHAPES) + sorted(RAGGED) + sorted(GQA) + sorted(PROMPT))
+    ap.add_argument("--prompt-rows", type=int, help="with a prompt case: the panel size (default: the case's own)")
+    ap.add_argument("--prompt-leg", choices=("prompt", "loop16", "matmul"), help="with a prompt case: that leg alone, bf16 (a kernel trace)")
     ap.add_argument("--kv-heads", type=int, help="with a gqa case: its kv heads (a divisor of the case's heads; default: the case's own)")
     ap.add_argument("--leg", choices=("gqa", "twin"), help="with a gqa case: that leg alone, bf16 (a kernel trace of its step)")
     ap.add_argument("--chunks-per-split", type=int, default=0, help="64-token chunks per slice of the device leg's context (0: the library's choice)")
@@ -277,6 +353,8 @@ def main():
     out = os.path.abspath(a.out)
     if a.merge_only:
         return merge_parent(out, a.parent_json)
+    if a.case in PROMPT:
+        return run_prompt(a.case, min(a.iters, 4), a.rounds, out, a.prompt_rows, a.prompt_leg)
     if a.case in GQA:
         return run_gqa(a.case, a.iters, a.rounds, out, a.chunks_per_split, a.kv_heads, a.leg)
     if a.case in RAGGED:
@@ -288,7 +366,7 @@ def main():
     if os.path.exists(out):
         os.remove(out)
     steps = [f"timeout -k 10 {a.timeout} {sys.executable} {os.path.abspath(__file__)} --case {s} --iters {a.iters} --rounds {a.rounds} --chunks-per-split {a.chunks_per_split} --out {out}"
-             for s in list(SHAPES) + list(RAGGED) + list(GQA)]
+             for s in list(SHAPES) + list(RAGGED) + list(GQA) + list(PROMPT)]
     rc = subprocess.call(" && ".join(steps), shell=True)
     if rc == 0 and a.parent_json:
         merge_parent(out, a.parent_json)

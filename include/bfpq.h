@@ -546,6 +546,25 @@ int bfpq_kv_attend_gqa(const void* q_dev, const void* k_codes_dev, const int8_t*
                        int64_t max_len, int64_t cap, int64_t ldd, int64_t ldo, int64_t ldp, double scale, int causal, int dtype, int block_size,
                        int x_mant_bits, int w_mant_bits, double epsilon, const uint8_t* exp_win_dev, void* score_ws_dev, int64_t score_ws_bytes,
                        void* sum_ws_dev, int64_t sum_ws_bytes, int64_t chunks_per_split, void* stream);
+/* Prompt attention on the device-length cache: bfpq_kv_attend_gqa for any number of query tokens, walked in panels (the same reference
+ * lines -- modeling_gpt2.py:207-243, the matmul of q and K^T, the scale, the causal mask, the softmax and the matmul with V, and
+ * modeling_llama.py:397-409 with repeat_kv, :264-273 -- for the Tq tokens of a prompt or of one chunk of it, where the reference makes
+ * the [.., Tq, S] scores and probabilities in the dtype).  Every argument as bfpq_kv_attend_gqa, except: Tq is any count >= 0 and one
+ * call covers the query tokens row0 .. row0 + rows - 1 of every query head (0 <= row0, row0 + rows <= Tq), reading those rows of q
+ * [BH, group * Tq, D] and writing those rows of out and p; causal sight goes by the token's index in the whole Tq, row t seeing the keys
+ * n <= lens - Tq + t.  Two launches per call: q k^T of the panel into score_ws_dev (16-byte aligned, score_ws_bytes >=
+ * bfpq_kv_attend_rows_ws_bytes(BH * group, rows, max_len) = 4 BH group rows (max_len rounded up to 4), rounded up to 16; no device
+ * needed; a size of 2^31 or more: BFPQ_E_UNSUPPORTED), then softmax and p v with the fp32 accumulators in registers.  There are no
+ * block sums: sum_ws_dev, sum_ws_bytes and chunks_per_split (0..16) are taken and not used, sum_ws_dev may be NULL.  Row for row the
+ * result is bit for bit bfpq_kv_attend_gqa's for that row -- nothing a row computes depends on Tq, on the panel or on the rows beside
+ * it -- with the row's visible length that of its token.  D <= 256 and q 16-byte aligned here; else errors as bfpq_kv_attend_gqa; row0
+ * or rows negative or past Tq: BFPQ_E_ARG; rows of 0 returns 0.  Nothing is read back. */
+int64_t bfpq_kv_attend_rows_ws_bytes(int64_t BH, int64_t P, int64_t max_len);
+int bfpq_kv_attend_rows(const void* q_dev, const void* k_codes_dev, const int8_t* k_exps_dev, const void* v_codes_dev, const int8_t* v_exps_dev,
+                        void* out_dev, void* p_dev, const int32_t* lens_dev, int64_t BH, int64_t heads, int64_t Tq, int64_t group, int64_t D,
+                        int64_t max_len, int64_t cap, int64_t ldd, int64_t ldo, int64_t ldp, double scale, int causal, int dtype, int block_size,
+                        int x_mant_bits, int w_mant_bits, double epsilon, const uint8_t* exp_win_dev, void* score_ws_dev, int64_t score_ws_bytes,
+                        void* sum_ws_dev, int64_t sum_ws_bytes, int64_t chunks_per_split, int64_t row0, int64_t rows, void* stream);
 /* ---- 2:4-compressed packed weights (format sp24) and their few-token product on v_smfmac_i32_16x16x64_i8 -------------------------
  * A weight pruned N:M with M = 4, N <= 2 along K (_structured_N_M_sparsity, reference bfp_ops.py:73-91) and quantized to HBFP block 64
  * holds at most 2 non-zero codes per group of 4.  sp24 keeps those two codes and their 2-bit positions, tiled for the decode kernel

@@ -1263,7 +1263,7 @@ def _gen_matmul_i8_op(bfp_args, matrix_unit):
 
     def kv_cache(batch, heads, head_dim, capacity, dtype=torch.bfloat16, device='cuda', **mode):
         """an HBFPKVCache under this op's bfp_args; its products count in matmul_stats.cache_calls.  mode: device_lengths=True (and
-        chunks_per_split), kv_heads as HBFPKVCache takes them"""
+        chunks_per_split), kv_heads, prompt_rows as HBFPKVCache takes them"""
         return HBFPKVCache(batch, heads, head_dim, capacity, dtype=dtype, stats=stats, **mode, **dict(bfp_args, device=device))
 
     bfp_op.__name__ = fake.__name__
@@ -1359,10 +1359,29 @@ class HBFPKVCache:
     bit that of an HBFPKVCache(batch, heads, ...) fed k.repeat_interleave(g, 1), v.repeat_interleave(g, 1).  The row limits (16,
     max_query_rows) stay limits per query head, and the workspaces hold the same bytes.  The g Tq rows of a kv head go through the
     kernels in tiles of 16: the rows of a tile share every load of the codes, which are read again per tile; on the host-length cache
-    more than 16 rows take the act_codes route."""
+    more than 16 rows take the act_codes route.
+
+    prompt_rows=P (prompt attention; needs device_lengths=True): attend() then takes any Tq >= 1, so the prompt -- in one
+    piece or in chunks, append(chunk); attend(q_chunk, scale, causal=True) -- runs on the codes append() has just made, with no second
+    quantization of K and V and no [B, H, Tq, S] array of the dtype.  Tq <= 16 goes exactly where it goes without P.  More rows are
+    walked in panels of P query tokens per query head, two launches per panel (q k^T of the panel into fp32 score rows; softmax and
+    p v with the accumulators in registers: no block sums, no combine pass), with no read-back and no allocation but the results;
+    cache_calls counts 2 per call.  causal, max_len, return_probs and kv_heads mean what they mean above, row t of Tq seeing the keys
+    n <= lengths[b] - Tq + t.  Nothing a row computes depends on Tq, on P or on the rows beside it: every row is, bit for bit, the
+    row attend() gives for it among up to 16, and context(p[:, :, i:i + 16]) gives ctx[:, :, i:i + 16].  P is an int, a multiple of
+    16 in 16 .. prompt_rows_max(batch, heads, capacity) -- the most for which the panel workspace, the fp32 score rows
+    [B heads, P, cap] made by prepare_attend() or the first long attend(), stays below 2^31 bytes -- and head_dim is at most 256.
+    Small panels bound the workspace, large ones fill the device: a panel launches B heads P / 64 workgroups.  0, the default, is the
+    cache above in every respect: nothing more is allocated and no new kernel is launched.  scores() and context() keep their 16-row
+    limit, and the host-length cache stays as it is: both are outside this route."""
+
+    @staticmethod
+    def prompt_rows_max(batch, heads, capacity):
+        """the largest prompt_rows: a multiple of 16 whose fp32 score rows [batch heads, P, cap] stay below 2^31 bytes (0: none does)"""
+        return ((1 << 31) - 16) // (4 * batch * heads * native.code_pitch(capacity)) // 16 * 16
 
     def __init__(self, batch, heads, head_dim, capacity, dtype=torch.bfloat16, device='cuda', stats=None, device_lengths=False,
-                 chunks_per_split=0, max_query_rows=native.KV_DEC_MAX_TOKENS, kv_heads=None, **bfp_args):
+                 chunks_per_split=0, max_query_rows=native.KV_DEC_MAX_TOKENS, kv_heads=None, prompt_rows=0, **bfp_args):
         a = unpack_bfp_args(bfp_args)
         if bfp_args:
             raise TypeError(f"HBFPKVCache: unknown arguments {sorted(bfp_args)}")
@@ -1386,6 +1405,19 @@ class HBFPKVCache:
         if isinstance(max_query_rows, bool) or not isinstance(max_query_rows, int) or not 1 <= max_query_rows <= native.KV_DEC_MAX_TOKENS:
             raise ValueError(f"HBFPKVCache: max_query_rows must be 1..{native.KV_DEC_MAX_TOKENS} (got {max_query_rows!r})")
         self.max_query_rows = max_query_rows
+        if isinstance(prompt_rows, bool) or not isinstance(prompt_rows, int):
+            raise TypeError(f"HBFPKVCache: prompt_rows must be an int (got {prompt_rows!r})")
+        if prompt_rows:
+            if prompt_rows < 16 or prompt_rows % 16:
+                raise ValueError(f"HBFPKVCache: prompt_rows must be 0 or a multiple of 16, at least 16 (got {prompt_rows})")
+            if not self.device_lengths:
+                raise ValueError("HBFPKVCache: prompt_rows needs device_lengths=True")
+            if head_dim > native.KV_ROWS_MAX_HEAD_DIM:
+                raise ValueError(f"HBFPKVCache: prompt_rows takes head_dim up to {native.KV_ROWS_MAX_HEAD_DIM} (got {head_dim})")
+            if batch >= 1 and heads >= 1 and capacity >= 1 and prompt_rows > self.prompt_rows_max(batch, heads, capacity):
+                raise ValueError(f"HBFPKVCache: prompt_rows={prompt_rows} makes a panel workspace of 2^31 bytes or more; the most here is "
+                                 f"{self.prompt_rows_max(batch, heads, capacity)}")
+        self.prompt_rows = prompt_rows
         self.batch, self.heads, self.head_dim, self.capacity, self.dtype = batch, heads, head_dim, capacity, dtype
         self.kv_heads, self.group = kv_heads, heads // kv_heads  # query head h reads kv head h // group
         self.block, self.mant_bits, self.epsilon = a['block_size'], a['mant_bits'], a['epsilon']
@@ -1404,6 +1436,7 @@ class HBFPKVCache:
             self.lengths, self.overflow = z(B, dt=torch.int32), z(1, dt=torch.int32)
             self._ws = self._workspace(max_query_rows)            # context()'s only workspace: made here, never grown
             self._att_ws = None                                   # attend()'s fp32 score rows: made by its first call
+            self._rows_ws = None                                  # the panel's fp32 score rows (prompt_rows): likewise
 
     @property
     def length(self):
@@ -1552,29 +1585,43 @@ class HBFPKVCache:
         return self._result(out, p.shape[2])
 
     def prepare_attend(self):
-        """make attend()'s workspace now (the fp32 score rows of max_query_rows rows over the whole capacity); it is never grown"""
+        """make attend()'s workspaces now (the fp32 score rows of max_query_rows rows over the whole capacity and, with prompt_rows, of
+        a panel); they are never grown"""
         if not self.device_lengths:
             raise ValueError("HBFPKVCache.attend needs device_lengths=True")
         if self._att_ws is None:
             n = native.kv_attend_ws_bytes(self.batch * self.heads, self.max_query_rows, self.cap)
             self._att_ws = torch.empty(n, dtype=torch.uint8, device=self.k_codes.device)
+        if self.prompt_rows and self._rows_ws is None:
+            n = native.kv_attend_rows_ws_bytes(self.batch * self.heads, self.prompt_rows, self.cap)
+            self._rows_ws = torch.empty(n, dtype=torch.uint8, device=self.k_codes.device)
 
     def attend(self, q, scale, max_len=None, causal=False, return_probs=False):
         """q [B, H, Tq, D] -> the context [B, H, Tq, D] of softmax(scores(q, max_len) * scale) (the class docstring); with return_probs
-        also p [B, H, Tq, max_len].  device_lengths only; two products, three launches"""
+        also p [B, H, Tq, max_len].  device_lengths only; two products, three launches.  More than 16 rows need prompt_rows (the
+        class docstring): two launches per panel"""
         if not self.device_lengths:
             raise ValueError("HBFPKVCache.attend needs device_lengths=True")
         x = self._operand(q, 'attend', self.head_dim)
         Tq = q.shape[2]
-        self._rows('attend', Tq, tiles_on_grid=True)
-        if Tq > self.max_query_rows:
-            raise ValueError(f"HBFPKVCache.attend: {Tq} query rows, the workspaces were made for max_query_rows={self.max_query_rows}")
+        panels = self.prompt_rows > 0 and Tq > native.KV_DEC_MAX_TOKENS
+        if not panels:
+            self._rows('attend', Tq, tiles_on_grid=True)
+            if Tq > self.max_query_rows:
+                raise ValueError(f"HBFPKVCache.attend: {Tq} query rows, the workspaces were made for max_query_rows={self.max_query_rows}")
         if isinstance(scale, bool) or not isinstance(scale, numbers.Real) or not math.isfinite(scale) or abs(scale) > torch.finfo(torch.float32).max:
             raise ValueError(f"HBFPKVCache.attend: scale must be a finite real number (in fp32; got {scale!r})")
         n = self.capacity if max_len is None else max_len
         if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= self.capacity:
             raise ValueError(f"HBFPKVCache.attend: max_len must be an int in 1..{self.capacity} (got {max_len!r})")
         self.prepare_attend()
+        if panels:
+            out, p = native.kv_attend_rows(x, self.k_codes, self.k_exps, self.v_codes, self.v_exps, self.lengths, self.kv_heads, n, float(scale),
+                                           bool(causal), self.block, self.mant_bits, self.epsilon, self._rows_ws, self.prompt_rows,
+                                           return_probs=bool(return_probs), group=self.group)
+            self.stats.cache_calls += 2
+            out = self._result(out, Tq)
+            return (out, self._result(p, Tq)) if return_probs else out
         out, p = native.kv_attend(x, self.k_codes, self.k_exps, self.v_codes, self.v_exps, self.lengths, self.kv_heads, n, float(scale),
                                   bool(causal), self.block, self.mant_bits, self.epsilon, self._att_ws, self._ws,
                                   chunks_per_split=self.chunks_per_split, return_probs=bool(return_probs), group=self.group)

@@ -41,6 +41,14 @@
 // taken over that token's four lanes only; block sums are exact integers; the fp32 additions run across blocks in block order per
 // row; the softmax's summation order depends on the row alone -- nothing a row computes depends on which rows share its tile.  Only
 // att_visible needs the token: it is called with t = r % Tq.  The instances without GRP are the code as it was (g = 1).
+//
+// Prompt attention (the same lines of modeling_gpt2.py:207-243 / modeling_llama.py:397-409 for the Tq tokens of a prompt or a
+// chunk of one): bfpq_kv_attend_rows walks `rows` query tokens from row0 on in two launches, k_kv_qk_rows and k_kv_pv_rows.  The rows of
+// a kv head in a panel are its group segments of `rows` tokens, panel row pr = query head pr / rows of the group, token row0 + pr % rows;
+// a workgroup owns 64 consecutive panel rows, a 16-row tile per wave.  k_kv_qk_rows quantizes its rows of q once, into LDS, and loops
+// over tiles of 64 keys that go through LDS once for the four waves; k_kv_pv_rows reduces each row of the fp32 panel to its maximum and
+// sum in k_kv_pv_split's order, forms and quantizes p in registers and adds the token blocks in block order into fp32 accumulators that
+// hold all D columns, the V codes of a 64-token chunk going through LDS once for the four waves.  No block sums, no combine pass.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "bfpq.h"
@@ -622,6 +630,342 @@ __global__ void __launch_bounds__(256) k_kv_advance(int32_t* __restrict__ lens, 
     if (n > 0) lens[b] = pos + n;
 }
 
+// ---- attention over a panel of query rows (bfpq_kv_attend_rows) ------------------------------------------------------------------------
+// Shared by the two kernels.  The panel holds PR = group * rows rows per kv head; rows [a, e] of it (e < PR) see at most what their
+// latest token sees: the last row's token, or the panel's last token where the range runs over the end of a query head's segment.
+constexpr int kRowsWg = 64;                               // panel rows per workgroup: a tile of 16 per wave
+constexpr int kMaxDT = 16;                                // 16-column tiles of D a wave of k_kv_pv_rows accumulates: D <= 256
+
+__device__ __forceinline__ int range_visible(int a, int e, int rows, int row0, int len, int Kx, int Tq, int causal)
+{
+    const int t = a / rows != e / rows ? row0 + rows - 1 : row0 + e % rows;
+    return att_visible(len, Kx, Tq, t, causal);
+}
+
+// An operand of block BLK as it lies in LDS: 64 lanes of 16 bytes, of 8 bytes, or (block 16, whose lanes 32..63 carry no k) 32 lanes
+template <int BLK> struct LdsOp {
+    static constexpr int LN = BLK == 16 ? 32 : 64;
+    __device__ __forceinline__ static int slot(int l) { return l & (LN - 1); }
+};
+
+// q k^T of panel rows: workgroup (kv head b, 64 panel rows).  Its rows of q are quantized once -- k_kv_bmm_dec's code: the block maximum
+// over the four lanes of a token, block_scale / quant_elem -- and kept as MFMA operands s_q [wave][block][lane] with their exponents
+// s_qe; then it loops over the tiles of 64 keys some row of it sees: the tile's codes s_k [16-key tile][block][lane] and exponents s_ke
+// [block][key] are loaded once for the four waves, and a wave whose own rows see none of the tile sits it out.  Blocks are added in
+// block order, the epilogue is kAtt's; only the columns below the wave's visible length are written, which is all the softmax reads.
+template <int BLK, int DT>
+__global__ void __launch_bounds__(256) k_kv_qk_rows(const void* __restrict__ x, const int8_t* __restrict__ kc, const int8_t* __restrict__ ke,
+                                                    float* __restrict__ ws, int Tq, int D, int Nout, int ldd, int cap, int pitch, int xm, int wm,
+                                                    float eps_dt, const uint8_t* __restrict__ exp_win, const int32_t* __restrict__ lens, int heads,
+                                                    float scale, int causal, int group, int row0, int rows)
+{
+    using Blk = I8Blk<BLK>;
+    using op_t = typename Blk::op_t;
+    using Tr = Traits<DT>;
+    using raw_t = typename Tr::raw_t;
+    constexpr int NE = BLK == 64 ? 16 : 8, LN = LdsOp<BLK>::LN;
+    extern __shared__ uint4 s_dyn[];
+    __shared__ uint8_t s_win[BFPQ_EXP_WIN_ENTRIES];
+    const int nbd = D / BLK;
+    op_t* const s_q = reinterpret_cast<op_t*>(s_dyn);             // [4][nbd][LN]
+    op_t* const s_k = s_q + 4 * nbd * LN;                         // [4][nbd][LN]
+    int8_t* const s_ke = reinterpret_cast<int8_t*>(s_k + 4 * nbd * LN);   // [nbd][64]
+    int8_t* const s_qe = s_ke + nbd * 64;                         // [4][nbd][16]
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, r = l & 15, q = l >> 4;
+    const int PR = group * rows, nwg = (PR + kRowsWg - 1) / kRowsWg;
+    const int b = (int)blockIdx.x / nwg, pr0 = ((int)blockIdx.x % nwg) * kRowsWg;
+    const int len = lens[b / heads];
+    const int No = len < Nout ? (len > 0 ? len : 0) : Nout;
+    const int prl = pr0 + kRowsWg - 1 < PR ? pr0 + kRowsWg - 1 : PR - 1;
+    const int vwg = range_visible(pr0, prl, rows, row0, len, No, Tq, causal);
+    if (vwg <= 0) return;                                        // (the whole workgroup, before any barrier) no row sees a key
+    for (int i = tid; i < BFPQ_EXP_WIN_ENTRIES; i += 256) s_win[i] = exp_win[i];
+    __syncthreads();
+    const int pw0 = pr0 + 16 * w, pwl = pw0 + 15 < PR ? pw0 + 15 : PR - 1;
+    const int vw = pw0 < PR ? range_visible(pw0, pwl, rows, row0, len, No, Tq, causal) : 0;   // what the wave's rows see at most
+    const int pr = pw0 + r;
+    const bool tok = pr < PR;
+    const int hq = tok ? pr / rows : 0, t = tok ? row0 + pr % rows : row0;
+    {
+        const raw_t* const xr = reinterpret_cast<const raw_t*>(x) + ((size_t)b * group * Tq + (size_t)hq * Tq + t) * D;
+        for (int j = 0; j < nbd; j++) {
+            uint32_t xv[NE], mx = 0;
+#pragma unroll
+            for (int v = 0; v < NE / Tr::VEC; v++) bfpq_dev::load_raw_vec<DT>(xr + j * BLK + Blk::lane(q), v, xv + v * Tr::VEC);
+#pragma unroll
+            for (int e = 0; e < NE; e++) {
+                if (!tok) xv[e] = 0u;
+                mx = umax(mx, xv[e] & Tr::ABS);
+            }
+            mx = umax(mx, (uint32_t)__shfl_xor((int)mx, 16, 64));
+            mx = umax(mx, (uint32_t)__shfl_xor((int)mx, 32, 64));
+            const BlockScale bs = block_scale<DT>(mx, xm, eps_dt, s_win);
+            uint32_t pk[NE / 4];
+#pragma unroll
+            for (int e = 0; e < NE / 4; e++) pk[e] = 0u;
+#pragma unroll
+            for (int e = 0; e < NE; e++) {
+                float cd;
+                quant_elem<DT>(raw_to_f32<DT>(xv[e]), bs, false, 0.f, &cd);
+                pk[e >> 2] |= ((uint32_t)(int)cd & 0xffu) << (8 * (e & 3));
+            }
+            op_t bF;
+            if constexpr (BLK == 64) bF = v4i{(int)pk[0], (int)pk[1], (int)pk[2], (int)pk[3]};
+            else bF = (long)(((uint64_t)pk[1] << 32) | pk[0]);
+            if (l < LN) s_q[(w * nbd + j) * LN + l] = bF;
+            if (q == 0) s_qe[(w * nbd + j) * 16 + r] = sat_exp(bs);
+        }
+    }
+    const v4i magic = {MAGIC_I, MAGIC_I, MAGIC_I, MAGIC_I};
+    const float ninf = -__builtin_inff();
+    const int vis = tok ? att_visible(len, No, Tq, t, causal) : 0;
+    float* const orow = ws + ((size_t)b * PR + (tok ? pr : pr0)) * pitch;
+    const int nkt = (vwg + 63) >> 6;
+    for (int kt = 0; kt < nkt; kt++) {
+        __syncthreads();                                         // (s_q, s_qe written; the tile before this one read)
+        const int8_t* const kcb = kc + ((size_t)b * cap + (kt << 6)) * ldd;
+        const int8_t* const keb = ke + ((size_t)b * cap + (kt << 6)) * nbd;
+        for (int idx = tid; idx < 4 * nbd * LN; idx += 256) {    // idx = (16-key tile i, block j, lane slot)
+            const int ls = idx % LN, j = (idx / LN) % nbd, i = idx / (LN * nbd);
+            s_k[idx] = *reinterpret_cast<const op_t*>(kcb + (size_t)(16 * i + (ls & 15)) * ldd + j * BLK + Blk::lane(ls >> 4));
+        }
+        for (int idx = tid; idx < 64 * nbd; idx += 256) s_ke[(idx % nbd) * 64 + idx / nbd] = keb[idx];
+        __syncthreads();
+        if ((kt << 6) >= vw) continue;                           // (wave-uniform) none of the wave's rows sees this tile
+        v2f acc[4][2];
+#pragma unroll
+        for (int i = 0; i < 4; i++) acc[i][0] = acc[i][1] = v2f{0.f, 0.f};
+        for (int j = 0; j < nbd; j++) {
+            const op_t bF = s_q[(w * nbd + j) * LN + LdsOp<BLK>::slot(l)];
+            v2f sx, nm;
+            token_scale((int)s_qe[(w * nbd + j) * 16 + r], xm, sx, nm);
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                op_t aF = s_k[(i * nbd + j) * LN + LdsOp<BLK>::slot(l)];
+                if (!Blk::a_live(q)) aF = op_t{};
+                const uint32_t ew = *reinterpret_cast<const uint32_t*>(s_ke + j * 64 + 16 * i + 4 * q);
+                const v2f sw01 = v2f{pow2_scale(exp_byte(ew, 0), wm), pow2_scale(exp_byte(ew, 8), wm)};
+                const v2f sw23 = v2f{pow2_scale(exp_byte(ew, 16), wm), pow2_scale(exp_byte(ew, 24), wm)};
+                rescale(Blk::mfma(aF, bF, magic), sx, nm, sw01, sw23, acc[i][0], acc[i][1]);
+            }
+        }
+        if (tok) {
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int n = (kt << 6) + 16 * i + 4 * q;
+                acc[i][0].x = n + 0 < vis ? rnd<DT>(acc[i][0].x) * scale : ninf;
+                acc[i][0].y = n + 1 < vis ? rnd<DT>(acc[i][0].y) * scale : ninf;
+                acc[i][1].x = n + 2 < vis ? rnd<DT>(acc[i][1].x) * scale : ninf;
+                acc[i][1].y = n + 3 < vis ? rnd<DT>(acc[i][1].y) * scale : ninf;
+                if (n < Nout) store4<BFPQ_F32>(orow, n, acc[i][0], acc[i][1]);
+            }
+        }
+    }
+}
+
+// softmax and p v of panel rows: workgroup (kv head bh, 64 panel rows), wave w the 16-row tile w and all D <= 256 columns.  First every
+// row's maximum and sum, all 256 threads per row in k_kv_pv_split<.., true>'s order (four rows' loads in flight at a time; a row's
+// operations and their order are unchanged): the same two numbers, bit for bit.  Then the walk over 64-token chunks: the chunk's V codes
+// s_v [16-column tile][block][lane] and exponents s_ve [block][column] go through LDS once for the four waves; a wave forms p of its rows
+// for a block, rounds, stores (pout) and quantizes it as k_kv_pv_split does, and adds the block's term for every column tile with
+// rescale() -- k_kv_pv_combine's additions in its order.  A wave stops forming p after the last block any of its rows sees (jstop); for
+// every block j in jstop .. nb - 1 the combine pass would still add the term of an all-zero p block -- its scale from block_scale(0),
+// NaN where the dtype's epsilon is zero; the block sum zero; V's scale, NaN for a NaN block -- so the wave adds exactly that term,
+// rescale() of the bare MAGIC_I, from V's exponent bytes alone.  With pout, p is zero from a row's visible length on.
+template <int BLK, int DT>
+__global__ void __launch_bounds__(256) k_kv_pv_rows(const float* __restrict__ ws, const int8_t* __restrict__ vc, const int8_t* __restrict__ ve,
+                                                    void* __restrict__ out, void* __restrict__ pout, const int32_t* __restrict__ lens, int heads,
+                                                    int Tq, int L, int D, int pitch, int cap, int ldve, int ldo, int ldp, int xm, int wm,
+                                                    float eps_dt, const uint8_t* __restrict__ exp_win, int causal, int group, int row0, int rows)
+{
+    using Blk = I8Blk<BLK>;
+    using op_t = typename Blk::op_t;
+    using Tr = Traits<DT>;
+    using raw_t = typename Tr::raw_t;
+    constexpr int NBS = 64 / BLK, NE = BLK == 64 ? 16 : 8, LN = LdsOp<BLK>::LN;
+    extern __shared__ uint4 s_dyn[];
+    __shared__ uint8_t s_win[BFPQ_EXP_WIN_ENTRIES];
+    __shared__ float s_red[2 * kRowsWg * 4];                     // per row and wave: the maximum, then the sum
+    const int ndt = D >> 4;
+    op_t* const s_v = reinterpret_cast<op_t*>(s_dyn);             // [ndt][NBS][LN]
+    int8_t* const s_ve = reinterpret_cast<int8_t*>(s_v + ndt * NBS * LN);   // [NBS][D]
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, r = l & 15, q = l >> 4;
+    const int PR = group * rows, nwg = (PR + kRowsWg - 1) / kRowsWg;
+    const int bh = (int)blockIdx.x / nwg, pr0 = ((int)blockIdx.x % nwg) * kRowsWg;
+    const int nrw = PR - pr0 < kRowsWg ? PR - pr0 : kRowsWg;      // the workgroup's rows
+    const int len = lens[bh / heads];
+    const int Kx = len < L ? (len > 0 ? len : 0) : L;
+    auto row_vis = [&](int i) __attribute__((always_inline)) { return att_visible(len, Kx, Tq, row0 + (pr0 + i) % rows, causal); };
+    for (int i = tid; i < BFPQ_EXP_WIN_ENTRIES; i += 256) s_win[i] = exp_win[i];
+    const float* const sc = ws + ((size_t)bh * PR + pr0) * pitch;
+    {
+        const float ninf = -__builtin_inff();
+        // f(u, v) over the visible elements this thread owns of rows t0 + u, u < 4, each row's in ascending order
+        auto walk4 = [&](int t0, auto&& f) __attribute__((always_inline)) {
+            int vt[4], vm = 0;
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                vt[u] = t0 + u < nrw ? row_vis(t0 + u) : 0;
+                vm = vt[u] > vm ? vt[u] : vm;
+            }
+            for (int k = tid * 4; k < vm; k += 1024) {
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    if (k < vt[u]) {
+                        const float4 v = *reinterpret_cast<const float4*>(sc + (size_t)(t0 + u) * pitch + k);
+                        f(u, v.x);
+                        if (k + 1 < vt[u]) f(u, v.y);
+                        if (k + 2 < vt[u]) f(u, v.z);
+                        if (k + 3 < vt[u]) f(u, v.w);
+                    }
+                }
+            }
+        };
+        for (int t0 = 0; t0 < nrw; t0 += 4) {
+            float m[4] = {ninf, ninf, ninf, ninf};
+            walk4(t0, [&](int u, float v) { m[u] = nan_max(m[u], v); });
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+#pragma unroll
+                for (int o = 32; o; o >>= 1) m[u] = nan_max(m[u], __shfl_xor(m[u], o, 64));
+                if (l == 0 && t0 + u < nrw) s_red[(t0 + u) * 4 + w] = m[u];
+            }
+        }
+        __syncthreads();
+        for (int t0 = 0; t0 < nrw; t0 += 4) {
+            float m[4], a[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const float* const sm = s_red + (t0 + u < nrw ? t0 + u : 0) * 4;
+                m[u] = nan_max(nan_max(sm[0], sm[1]), nan_max(sm[2], sm[3]));
+            }
+            walk4(t0, [&](int u, float v) { a[u] += expf(v - m[u]); });
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+#pragma unroll
+                for (int o = 32; o; o >>= 1) a[u] += __shfl_xor(a[u], o, 64);
+                if (l == 0 && t0 + u < nrw) s_red[(kRowsWg + t0 + u) * 4 + w] = a[u];
+            }
+        }
+        __syncthreads();
+    }
+    const int pw0 = pr0 + 16 * w, pr = pw0 + r;
+    const bool tok = pr < PR;
+    float rmax = 0.f, rsum = 1.f;
+    int vis = 0;
+    if (tok) {
+        const float* const sm = s_red + (16 * w + r) * 4, * const ss = s_red + (kRowsWg + 16 * w + r) * 4;
+        rmax = nan_max(nan_max(sm[0], sm[1]), nan_max(sm[2], sm[3]));
+        rsum = (ss[0] + ss[1]) + (ss[2] + ss[3]);
+        vis = row_vis(16 * w + r);
+    }
+    const int hq = tok ? pr / rows : 0, t = tok ? row0 + pr % rows : row0;
+    const size_t grow = (size_t)bh * group * Tq + (size_t)hq * Tq + t;   // the lane's row of q, out and p
+    const float* const srow = ws + ((size_t)bh * PR + (tok ? pr : pr0)) * pitch;
+    raw_t* const prow = pout ? reinterpret_cast<raw_t*>(pout) + grow * ldp : nullptr;
+    const int nb = (Kx + BLK - 1) / BLK;
+    const int prl = pr0 + nrw - 1, pwl = pw0 + 15 < PR ? pw0 + 15 : PR - 1;
+    const int vwg = range_visible(pr0, prl, rows, row0, len, Kx, Tq, causal);
+    const int vw = pw0 < PR ? range_visible(pw0, pwl, rows, row0, len, Kx, Tq, causal) : 0;
+    const int jstop = (vw + BLK - 1) / BLK;                       // (<= nb) blocks some row of the wave sees
+    const v4i magic = {MAGIC_I, MAGIC_I, MAGIC_I, MAGIC_I};
+    v2f acc[kMaxDT][2];
+#pragma unroll
+    for (int i = 0; i < kMaxDT; i++) acc[i][0] = acc[i][1] = v2f{0.f, 0.f};
+
+    const int nchw = (vwg + 63) >> 6;
+    for (int c = 0; c < nchw; c++) {
+        __syncthreads();                                         // (the chunk before this one read)
+        for (int idx = tid; idx < ndt * NBS * LN; idx += 256) {  // idx = (16-column tile i, block s of the chunk, lane slot)
+            const int ls = idx % LN, s = (idx / LN) % NBS, i = idx / (LN * NBS);
+            s_v[idx] = *reinterpret_cast<const op_t*>(vc + ((size_t)bh * D + 16 * i + (ls & 15)) * cap + (c << 6) + s * BLK + Blk::lane(ls >> 4));
+        }
+        for (int idx = tid; idx < NBS * D; idx += 256) {
+            const int j = c * NBS + idx / D;
+            s_ve[idx] = j < nb ? ve[((size_t)bh * D + idx % D) * ldve + j] : (int8_t)0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < NBS; s++) {
+            const int j = c * NBS + s;
+            if (j >= jstop) break;                               // (wave-uniform)
+            const int k0 = (c << 6) + s * BLK + Blk::lane(q);
+            uint32_t xv[NE], mx = 0;
+#pragma unroll
+            for (int v = 0; v < NE / 4; v++) {                   // p of the lane's elements, in the dtype's bits; the store for return_probs
+                float4 sv = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (k0 + 4 * v < vis) sv = *reinterpret_cast<const float4*>(srow + k0 + 4 * v);
+                const float se[4] = {sv.x, sv.y, sv.z, sv.w};
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    const int k = k0 + 4 * v + e;
+                    xv[4 * v + e] = k < vis ? f32_to_raw<DT>(expf(se[e] - rmax) / rsum) : 0u;
+                    if (prow && k < vis) prow[k] = (raw_t)xv[4 * v + e];
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < NE; e++) mx = umax(mx, xv[e] & Tr::ABS);
+            mx = umax(mx, (uint32_t)__shfl_xor((int)mx, 16, 64));
+            mx = umax(mx, (uint32_t)__shfl_xor((int)mx, 32, 64));
+            const BlockScale bs = block_scale<DT>(mx, xm, eps_dt, s_win);
+            uint32_t pk[NE / 4];
+#pragma unroll
+            for (int e = 0; e < NE / 4; e++) pk[e] = 0u;
+#pragma unroll
+            for (int e = 0; e < NE; e++) {
+                float cd;
+                quant_elem<DT>(raw_to_f32<DT>(xv[e]), bs, false, 0.f, &cd);
+                pk[e >> 2] |= ((uint32_t)(int)cd & 0xffu) << (8 * (e & 3));
+            }
+            op_t bF;
+            if constexpr (BLK == 64) bF = v4i{(int)pk[0], (int)pk[1], (int)pk[2], (int)pk[3]};
+            else bF = (long)(((uint64_t)pk[1] << 32) | pk[0]);
+            v2f sx, nm;
+            token_scale((int)sat_exp(bs), xm, sx, nm);
+#pragma unroll
+            for (int i = 0; i < kMaxDT; i++) {
+                if (i < ndt) {                                   // (uniform)
+                    op_t aF = s_v[(i * NBS + s) * LN + LdsOp<BLK>::slot(l)];
+                    if (!Blk::a_live(q)) aF = op_t{};
+                    const uint32_t ew = *reinterpret_cast<const uint32_t*>(s_ve + s * D + 16 * i + 4 * q);
+                    const v2f sw01 = v2f{pow2_scale(exp_byte(ew, 0), wm), pow2_scale(exp_byte(ew, 8), wm)};
+                    const v2f sw23 = v2f{pow2_scale(exp_byte(ew, 16), wm), pow2_scale(exp_byte(ew, 24), wm)};
+                    rescale(Blk::mfma(aF, bF, magic), sx, nm, sw01, sw23, acc[i][0], acc[i][1]);
+                }
+            }
+        }
+    }
+    if (pw0 >= PR) return;                                       // (wave-uniform; no barrier below) a wave without rows
+    if (jstop < nb) {                                            // the blocks no row of the wave sees: the term of a zero p block
+        const BlockScale bs = block_scale<DT>(0u, xm, eps_dt, s_win);
+        v2f sx, nm;
+        token_scale((int)sat_exp(bs), xm, sx, nm);
+        for (int j = jstop; j < nb; j++) {
+#pragma unroll
+            for (int i = 0; i < kMaxDT; i++) {
+                if (i < ndt) {
+                    const int8_t* const we = ve + ((size_t)bh * D + 16 * i + 4 * q) * ldve + j;
+                    const v2f sw01 = v2f{pow2_scale((int)we[0], wm), pow2_scale((int)we[ldve], wm)};
+                    const v2f sw23 = v2f{pow2_scale((int)we[2 * ldve], wm), pow2_scale((int)we[3 * ldve], wm)};
+                    rescale(magic, sx, nm, sw01, sw23, acc[i][0], acc[i][1]);
+                }
+            }
+        }
+    }
+    if (tok) {
+#pragma unroll
+        for (int i = 0; i < kMaxDT; i++)
+            if (i < ndt) store4<DT>(out, grow * ldo + 16 * i + 4 * q, acc[i][0], acc[i][1]);
+    }
+    if (pout) {                                                  // +0 at what the wave's rows do not see
+        for (int i = 0; i < 16 && pw0 + i < PR; i++) {
+            const int p = pw0 + i;
+            raw_t* const pr_i = reinterpret_cast<raw_t*>(pout) + ((size_t)bh * group * Tq + (size_t)(p / rows) * Tq + row0 + p % rows) * ldp;
+            for (int k = row_vis(16 * w + i) + l; k < L; k += 64) pr_i[k] = (raw_t)0;
+        }
+    }
+}
+
 constexpr int64_t kLim = (int64_t)1 << 31;
 
 // the tiles of 16 rows a head's group * Tq rows make
@@ -898,6 +1242,62 @@ int bfpq_kv_attend(const void* q, const void* k_codes, const int8_t* k_exps, con
     return bfpq_kv_attend_gqa(q, k_codes, k_exps, v_codes, v_exps, out, p_out, lens, BH, heads, Tq, 1, D, max_len, cap, ldd, ldo, ldp, scale, causal,
                               dtype, block_size, x_mant_bits, w_mant_bits, epsilon, exp_win, score_ws, score_ws_bytes, sum_ws, sum_ws_bytes,
                               chunks_per_split, stream);
+}
+
+int64_t bfpq_kv_attend_rows_ws_bytes(int64_t BH, int64_t P, int64_t max_len)
+{
+    if (BH < 0 || P < 0 || max_len < 0) return BFPQ_E_ARG;
+    if (max_len >= kLim || BH >= kLim || P >= kLim) return BFPQ_E_UNSUPPORTED;
+    const int64_t n = BH * P * ((max_len + 3) / 4 * 4);           // the fp32 score rows of a panel, pitch max_len rounded up to 4
+    if (n >= kLim / 4 - 4) return BFPQ_E_UNSUPPORTED;
+    return (n * 4 + 15) / 16 * 16;
+}
+
+int bfpq_kv_attend_rows(const void* q, const void* k_codes, const int8_t* k_exps, const void* v_codes, const int8_t* v_exps, void* out, void* p_out,
+                        const int32_t* lens, int64_t BH, int64_t heads, int64_t Tq, int64_t group, int64_t D, int64_t max_len, int64_t cap,
+                        int64_t ldd, int64_t ldo, int64_t ldp, double scale, int causal, int dtype, int block_size, int x_mant_bits,
+                        int w_mant_bits, double epsilon, const uint8_t* exp_win, void* score_ws, int64_t score_ws_bytes, void* sum_ws,
+                        int64_t sum_ws_bytes, int64_t chunks_per_split, int64_t row0, int64_t rows, void* stream)
+{
+    (void)sum_ws; (void)sum_ws_bytes;                             // no block sums on this route
+    if (!dtype_ok(dtype) || !i8_block_ok(block_size) || !i8_mant_ok(x_mant_bits) || !i8_mant_ok(w_mant_bits) || BH < 0 || Tq < 0 || heads < 1 ||
+        BH % heads != 0 || group < 1 || chunks_per_split < 0 || (causal != 0 && causal != 1) || !(scale - scale == 0.0) ||
+        !((float)scale - (float)scale == 0.f) || row0 < 0 || rows < 0 || row0 > Tq || rows > Tq - row0)
+        return BFPQ_E_ARG;
+    if (BH == 0 || Tq == 0 || rows == 0) return 0;
+    const int64_t pitch = (max_len + 3) / 4 * 4, R = Tq * group, PR = rows * group, nwg = (PR + kRowsWg - 1) / kRowsWg;
+    if (!bfpq_kv_ok(D, cap, block_size) || D > 16 * kMaxDT || group >= kLim || Tq >= kLim || max_len < 1 || max_len > cap || ldd < D ||
+        ldd % 64 != 0 || ldo % 4 != 0 || ldo < D || (p_out && ldp < max_len) || cap * ldd >= kLim || R >= kLim || BH * nwg >= kLim ||
+        chunks_per_split > kMaxCps)
+        return BFPQ_E_UNSUPPORTED;
+    const int64_t need = bfpq_kv_attend_rows_ws_bytes(BH * group, rows, max_len);
+    if (need < 0 || score_ws_bytes < need) return BFPQ_E_UNSUPPORTED;
+    const uintptr_t emask = dtype == BFPQ_F32 ? 3u : 1u;
+    if (!q || !k_codes || !k_exps || !v_codes || !v_exps || !out || !lens || !exp_win || !score_ws ||
+        !aligned16(q, k_codes, v_codes, out, score_ws) || (reinterpret_cast<uintptr_t>(lens) & 3u) || (reinterpret_cast<uintptr_t>(p_out) & emask))
+        return BFPQ_E_ARG;
+    const float eps_dt = bfpq_dev::h_round((float)epsilon, dtype);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t nbd = D / block_size;
+    const size_t lds_qk = (size_t)(2 * 64 * D + 128 * nbd), lds_pv = (size_t)(64 * D + 64 / block_size * D);   // <= 36 KiB at D = 256
+    with_block(block_size, [&](auto blk) {
+        with_dtype(dtype, [&](auto dt) {
+            hipLaunchKernelGGL((k_kv_qk_rows<decltype(blk)::value, decltype(dt)::value>), dim3((unsigned)(BH * nwg)), dim3(256), lds_qk, s, q,
+                               (const int8_t*)k_codes, k_exps, (float*)score_ws, (int)Tq, (int)D, (int)max_len, (int)ldd, (int)cap, (int)pitch,
+                               x_mant_bits, w_mant_bits, eps_dt, exp_win, lens, (int)heads, (float)scale, causal, (int)group, (int)row0, (int)rows);
+        });
+    });
+    const int rc = (int)hipGetLastError();
+    if (rc) return rc;
+    with_block(block_size, [&](auto blk) {
+        with_dtype(dtype, [&](auto dt) {
+            hipLaunchKernelGGL((k_kv_pv_rows<decltype(blk)::value, decltype(dt)::value>), dim3((unsigned)(BH * nwg)), dim3(256), lds_pv, s,
+                               (const float*)score_ws, (const int8_t*)v_codes, v_exps, out, p_out, lens, (int)heads, (int)Tq, (int)max_len, (int)D,
+                               (int)pitch, (int)cap, (int)(cap / block_size), (int)ldo, (int)ldp, x_mant_bits, w_mant_bits, eps_dt, exp_win, causal,
+                               (int)group, (int)row0, (int)rows);
+        });
+    });
+    return (int)hipGetLastError();
 }
 
 }  // extern "C"

@@ -117,6 +117,9 @@ PROTOTYPES = {
     "bfpq_kv_attend": (_i32, [_vp] * 8 + [_i64] * 9 + [_dbl, _i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _i64, _vp, _i64, _i64, _vp]),
     "bfpq_kv_bmm_dec_gqa": (_i32, [_vp] * 5 + [_i64] * 11 + [_i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _i64, _i64, _vp]),
     "bfpq_kv_attend_gqa": (_i32, [_vp] * 8 + [_i64] * 10 + [_dbl, _i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _i64, _vp, _i64, _i64, _vp]),
+    "bfpq_kv_attend_rows_ws_bytes": (_i64, [_i64, _i64, _i64]),
+    "bfpq_kv_attend_rows": (_i32, [_vp] * 8 + [_i64] * 10 + [_dbl, _i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64,
+                                   _vp]),
 }
 
 
@@ -1578,6 +1581,65 @@ def kv_attend(q, k_codes, k_exps, v_codes, v_exps, lengths, heads, max_len, scal
                                                 DTYPE_CODE[q.dtype], int(block_size), int(mant_bits), int(mant_bits), float(epsilon),
                                                 _ptr(exp_window_dev(q.dtype, dev)), _ptr(score_ws), score_ws.numel(), _ptr(sum_ws),
                                                 sum_ws.numel(), int(chunks_per_split), _stream(q)), "bfpq_kv_attend_gqa")
+    return out, p
+
+
+KV_ROWS_MAX_HEAD_DIM = 256     # bfpq_kv_attend_rows keeps a row's accumulators for all of D in registers
+
+
+def kv_attend_rows_ws_bytes(BH, P, max_len):
+    """bytes of kv_attend_rows' fp32 score rows for panels of P rows of BH query heads (bfpq_kv_attend_rows_ws_bytes; no device needed)"""
+    n = int(load_library().bfpq_kv_attend_rows_ws_bytes(int(BH), int(P), int(max_len)))
+    if n < 0:
+        check(n, "bfpq_kv_attend_rows_ws_bytes")
+    return n
+
+
+def kv_attend_rows(q, k_codes, k_exps, v_codes, v_exps, lengths, heads, max_len, scale, causal, block_size, mant_bits, epsilon, score_ws,
+                   panel_rows, return_probs=False, group=1):
+    """kv_attend for any number of query rows (bfpq_kv_attend_rows): q [BH, group * Tq, D] is walked in panels of panel_rows tokens per
+    query head, two launches per panel, the panel's fp32 score rows in score_ws (a contiguous uint8 tensor of at least
+    kv_attend_rows_ws_bytes(BH * group, min(panel_rows, Tq), max_len) bytes).  Returns (context [BH, group * Tq, D], p
+    [BH, group * Tq, max_len] or None); row for row kv_attend's bits.  Nothing is read back."""
+    require_device_tensor(q, "q")
+    if q.dim() != 3:
+        raise ValueError(f"kv_attend_rows takes q [BH, Tq, D] (got {tuple(q.shape)})")
+    BH, R, D = q.shape
+    Tq = _kv_group("kv_attend_rows", R, group)
+    panel_rows = int(panel_rows)
+    if panel_rows < 1:
+        raise ValueError(f"kv_attend_rows: panel_rows must be >= 1 (got {panel_rows})")
+    q = q.contiguous()
+    dev = q.device
+    heads = int(heads)
+    if heads < 1 or BH % heads:
+        raise ValueError(f"kv_attend_rows: {BH} heads in all are no multiple of heads = {heads}")
+    if k_codes.dim() < 2 or v_codes.dim() < 2:
+        raise ValueError("kv_attend_rows takes k_codes [..., cap, ldd] and v_codes [..., D, cap]")
+    cap, ldd = k_codes.shape[-2], k_codes.shape[-1]
+    nbd, nbc = D // int(block_size), cap // int(block_size)
+    for name, buf, numel in (("k_codes", k_codes, BH * cap * ldd), ("k_exps", k_exps, BH * cap * nbd), ("v_codes", v_codes, BH * D * cap),
+                             ("v_exps", v_exps, BH * D * nbc)):
+        if buf.device != dev or buf.dtype != torch.int8 or not buf.is_contiguous() or buf.numel() != numel:
+            raise ValueError(f"kv_attend_rows: {name} must be contiguous int8 on {dev} with {numel} elements "
+                             f"(got {tuple(buf.shape)}, {buf.dtype}, {buf.device})")
+    _kv_int32("kv_attend_rows", "lengths", lengths, BH // heads, dev)
+    max_len, scale = int(max_len), float(scale)
+    if not math.isfinite(scale) or abs(scale) > torch.finfo(torch.float32).max:
+        raise ValueError(f"kv_attend_rows: scale must be finite in fp32 (got {scale})")
+    need = kv_attend_rows_ws_bytes(BH * group, min(panel_rows, Tq), max_len)
+    if (not isinstance(score_ws, torch.Tensor) or score_ws.dtype != torch.uint8 or score_ws.device != dev or not score_ws.is_contiguous()
+            or score_ws.numel() < need):
+        raise ValueError(f"kv_attend_rows: score_ws must be a contiguous uint8 tensor of at least {need} bytes on {dev}")
+    with torch.cuda.device(dev):
+        out = torch.empty((BH, R, D), dtype=q.dtype, device=dev)
+        p = torch.empty((BH, R, max_len), dtype=q.dtype, device=dev) if return_probs else None
+        L, win, stream = load_library(), _ptr(exp_window_dev(q.dtype, dev)), _stream(q)
+        for row0 in range(0, Tq, panel_rows):
+            check(L.bfpq_kv_attend_rows(_ptr(q), _ptr(k_codes), _ptr(k_exps), _ptr(v_codes), _ptr(v_exps), _ptr(out), _ptr(p), _ptr(lengths), BH,
+                                        heads, Tq, group, D, max_len, cap, ldd, D, max_len, scale, int(bool(causal)), DTYPE_CODE[q.dtype],
+                                        int(block_size), int(mant_bits), int(mant_bits), float(epsilon), win, _ptr(score_ws), score_ws.numel(),
+                                        None, 0, 0, row0, min(panel_rows, Tq - row0), stream), "bfpq_kv_attend_rows")
     return out, p
 
 
