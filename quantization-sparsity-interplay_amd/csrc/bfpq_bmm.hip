@@ -205,13 +205,8 @@ __global__ void __launch_bounds__(256) k_codes_t(const void* __restrict__ in, in
         const int first = sq & ~(per - 1);                                // first wave of this thread's block
         for (int o = 0; o < per; o++) { const uint32_t k = s_max[(first + o) * kTD + d]; mx = k > mx ? k : mx; }
         const BlockScale bs = block_scale<DT>(mx, mant_bits, eps_dt, s_win);
-        uint32_t pk[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int i = 0; i < 16; i++) {
-            float c;
-            quant_elem<DT>(raw_to_f32<DT>(raw[i]), bs, false, 0.f, &c);
-            pk[i >> 2] |= ((uint32_t)(int)c & 0xffu) << (8 * (i & 3));
-        }
+        uint32_t pk[4];
+        pack_codes<DT>(raw, 16, bs, pk);
         *reinterpret_cast<uint4*>(s_code + d * kTS + sq * 16) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
         const int s = s0 + sq * 16;
         if (sq == first && s < S && d0 + d < D) exps[((size_t)b * D + d0 + d) * nb + s / block] = sat_exp(bs);

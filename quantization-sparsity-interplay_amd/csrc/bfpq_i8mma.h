@@ -80,6 +80,18 @@ __device__ __forceinline__ void token_scale(int e, int m, v2f& sx, v2f& nm)
     nm = v2f{-MAGIC_F * s, -MAGIC_F * s};
 }
 
+// the weight side: sw01 / sw23 = 2^(e - m) of the lane's features 0, 1 / 2, 3 from their block exponents, or from the four bytes of an
+// exp4 dword
+__device__ __forceinline__ void weight_scales(int e0, int e1, int e2, int e3, int m, v2f& sw01, v2f& sw23)
+{
+    sw01 = v2f{pow2_scale(e0, m), pow2_scale(e1, m)};
+    sw23 = v2f{pow2_scale(e2, m), pow2_scale(e3, m)};
+}
+__device__ __forceinline__ void weight_scales(uint32_t ew, int m, v2f& sw01, v2f& sw23)
+{
+    weight_scales(exp_byte(ew, 0), exp_byte(ew, 8), exp_byte(ew, 16), exp_byte(ew, 24), m, sw01, sw23);
+}
+
 // a01, a23 += (d - 1.5 * 2^23) * sx * sw for the MFMA result d (C = MAGIC_I): sw01 / sw23 the weight scales of the lane's features 0, 1 / 2, 3
 __device__ __forceinline__ void rescale(v4i d, v2f sx, v2f nm, v2f sw01, v2f sw23, v2f& a01, v2f& a23)
 {
@@ -102,6 +114,21 @@ __device__ __forceinline__ void store4(void* out, size_t o, v2f a01, v2f a23)
         const uint32_t lo = f32_to_raw<OUT_DT>(a01.x) | (f32_to_raw<OUT_DT>(a01.y) << 16);
         const uint32_t hi = f32_to_raw<OUT_DT>(a23.x) | (f32_to_raw<OUT_DT>(a23.y) << 16);
         *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(out) + o) = make_uint2(lo, hi);
+    }
+}
+
+// the int8 codes of NE elements (raw bits of the dtype) under their block's scale, four to a word in element order: quant_elem for the
+// first n, zero codes for the rest
+template <int DT, int NE>
+__device__ __forceinline__ void pack_codes(const uint32_t (&raw)[NE], int n, const BlockScale& bs, uint32_t (&pk)[NE / 4])
+{
+#pragma unroll
+    for (int e = 0; e < NE / 4; e++) pk[e] = 0u;
+#pragma unroll
+    for (int e = 0; e < NE; e++) {
+        float c = 0.f;
+        if (e < n) quant_elem<DT>(raw_to_f32<DT>(raw[e]), bs, false, 0.f, &c);
+        pk[e >> 2] |= ((uint32_t)(int)c & 0xffu) << (8 * (e & 3));
     }
 }
 

@@ -10,45 +10,43 @@
 // already rounded is a double rounding, so that block is quantized again FROM v_tail at every append, absent tokens as zeros -- which
 // is the reference's zero pad of a ragged last block (bfp_ops.py:50-53).  A closed block is never touched again.
 //
+// Every kernel quantizes with the same steps, each written once below: quant_operand (a token's block of x -> its int8 MFMA operand:
+// the block maximum over the token's four lanes, block_scale, pack_codes of bfpq_i8mma.h) and, for the softmax, row_stats (a row's
+// maximum and sum, in an order that depends on the row alone), form_p (p of a lane's elements, rounded once) and att_scores (what the
+// softmax reads of a score).  The bit-for-bit laws of DESIGN 5k-5n are these helpers being the only copy.
+//
 // k_kv_append: one launch for any t >= 1.  Its first workgroups quantize the t key rows (a thread per 16 elements, the block maximum
-// over 1, 2 or 4 neighbour lanes); the others own one 64-column slice of V and one token block each: rows below pos come from v_tail,
-// rows of the chunk from v_new (and go to v_tail where the block stays open), the rest are zeros; the block x 64 tile goes through
-// LDS as in k_codes_t (bfpq_bmm.hip), the scale and the codes are block_scale / quant_elem of bfpq_common.h.  The workgroup of the
-// chunk's first block also does its last one, after a barrier: those are the only two that touch v_tail (read, then write).
+// over 1, 2 or 4 neighbour lanes); the others own one 64-column slice of V and one token block each (v_block): rows below pos come from
+// v_tail, rows of the chunk from v_new (and go to v_tail where the block stays open), the rest are zeros; the block x 64 tile goes
+// through LDS as in k_codes_t (bfpq_bmm.hip).  The workgroup of the chunk's first block also does its last one, after a barrier: those
+// are the only two that touch v_tail (read, then write).
 //
-// k_kv_bmm_dec: out[b][t][n] = sum_k x[b][t][k] w[b][n][k] for t < Tq <= 16, x in its float dtype and quantized in the kernel block by
-// block as the walk reaches it (a lane holds the 16 or 8 elements of its MFMA operand; the block maximum over the four lanes of a
-// token; elements past Kx count as zeros), w a cached operand.  Family qk: w = k_codes, n the S cached keys, k = D.  Family pv:
-// w = v_codes, n = D, k the S cached tokens (the last block ragged: zero codes on the cache side, zeros on x's).  The block product,
-// the rescale, the NaN marker and the lane map are bfpq_i8mma.h; blocks are added in block order, so on the same codes the result is
-// k_bmm_i8's bit for bit.  Rows past Nout repeat the last row (never stored); a lane stores four consecutive n of one token, so the
-// output has a pitch ldo (a multiple of 4).  The next 64-byte chunk of w, its exponents and x's elements are loaded before the current
-// one is multiplied.  No split of the contraction: pv at batch 1 runs B H D / 64 workgroups.
+// k_kv_bmm_dec: out[b][t][n] = sum_k x[b][t][k] w[b][n][k] for t < Tq <= 16, x in its float dtype and quantized block by block as the
+// walk reaches it (quant_operand; elements past Kx count as zeros), w a cached operand.  Family qk: w = k_codes, n the S cached keys,
+// k = D.  Family pv: w = v_codes, n = D, k the S cached tokens (the last block ragged: zero codes on the cache side, zeros on x's).
+// The block product, the rescale, the NaN marker and the lane map are bfpq_i8mma.h; blocks are added in block order, so on the same
+// codes the result is k_bmm_i8's bit for bit.  Rows past Nout repeat the last row (never stored); a lane stores four consecutive n of
+// one token, so the output has a pitch ldo (a multiple of 4).  The next 64-byte chunk of w, its exponents and x's elements are loaded
+// before the current one is multiplied.  No split of the contraction: pv at batch 1 runs B H D / 64 workgroups.
 //
-// bfpq_kv_attend: scores, scale, softmax and context of one decode step in three launches.  k_kv_bmm_dec<.., ATT> leaves the
-// scores -- rounded to the dtype, widened, times the scale -- as fp32 rows in a workspace; k_kv_pv_split<.., true> reads them, every
-// workgroup of a head reducing the head's rows to the same maximum and sum before it forms, rounds and quantizes the probabilities of
-// its own slice in registers; k_kv_pv_combine is the one context() runs.
+// bfpq_kv_attend: scores, scale, softmax and context of one decode step in three launches.  k_kv_bmm_dec<.., kAtt> leaves
+// att_scores as fp32 rows in a workspace; k_kv_pv_split<.., true> runs row_stats on the head's rows in every workgroup of the head, then
+// form_p and quant_operand on its own slice, in registers; k_kv_pv_combine is the one context() runs.
 //
 // Grouped-query attention (the reference's LLaMA, modeling_llama.py:385-409): the cache holds B x kv_heads heads and query
 // head h reads kv head h / g (repeat_kv, :264-273).  Nothing is repeated: the rows of a kv head are the contiguous view
 // [B kv_heads, R = g Tq, .] of q / p / the outputs, row r being query head r / Tq of the group and its token t = r % Tq, and the GRP
-// instances of k_kv_bmm_dec and k_kv_pv_split walk them in tiles of 16 consecutive rows (the tile index shares a grid dimension with
-// the head).  The rows of a tile share every load of the K / V codes and exponents -- for R <= 16, the decode step of every real
-// model, the whole group reads them once -- and each further tile is an iteration of k_kv_bmm_dec's y loop or a workgroup of
-// k_kv_pv_split of its own, which reads them again.  The result is, bit for bit, that of a cache of B x heads heads fed repeat_kv(k),
-// repeat_kv(v), by construction: K and V are quantized per head, so repeated heads hold identical codes; a row's x block maximum is
-// taken over that token's four lanes only; block sums are exact integers; the fp32 additions run across blocks in block order per
-// row; the softmax's summation order depends on the row alone -- nothing a row computes depends on which rows share its tile.  Only
-// att_visible needs the token: it is called with t = r % Tq.  The instances without GRP are the code as it was (g = 1).
+// instances of k_kv_bmm_dec and k_kv_pv_split walk them in tiles of 16 consecutive rows that share every load of the K / V codes and
+// exponents (a further tile is an iteration of k_kv_bmm_dec's y loop or a workgroup of k_kv_pv_split, and reads them again).  The
+// result is, bit for bit, that of a cache of B x heads heads fed repeat_kv(k), repeat_kv(v): repeated heads hold identical codes, and
+// nothing the helpers compute for a row depends on which rows share its tile.  Only att_visible needs the token, t = r % Tq.
 //
-// Prompt attention (the same lines of modeling_gpt2.py:207-243 / modeling_llama.py:397-409 for the Tq tokens of a prompt or a
-// chunk of one): bfpq_kv_attend_rows walks `rows` query tokens from row0 on in two launches, k_kv_qk_rows and k_kv_pv_rows.  The rows of
-// a kv head in a panel are its group segments of `rows` tokens, panel row pr = query head pr / rows of the group, token row0 + pr % rows;
-// a workgroup owns 64 consecutive panel rows, a 16-row tile per wave.  k_kv_qk_rows quantizes its rows of q once, into LDS, and loops
-// over tiles of 64 keys that go through LDS once for the four waves; k_kv_pv_rows reduces each row of the fp32 panel to its maximum and
-// sum in k_kv_pv_split's order, forms and quantizes p in registers and adds the token blocks in block order into fp32 accumulators that
-// hold all D columns, the V codes of a 64-token chunk going through LDS once for the four waves.  No block sums, no combine pass.
+// Prompt attention (modeling_gpt2.py:207-243 / modeling_llama.py:397-409 for the Tq tokens of a prompt or a chunk of one):
+// bfpq_kv_attend_rows walks `rows` query tokens from row0 on in two launches.  The rows of a kv head in a panel are its group segments
+// of `rows` tokens, panel row pr = query head pr / rows of the group, token row0 + pr % rows; a workgroup owns 64 consecutive panel
+// rows, a 16-row tile per wave.  k_kv_qk_rows: quant_operand on its rows of q once, into LDS, then tiles of 64 keys that go through LDS
+// once for the four waves, att_scores into the fp32 panel.  k_kv_pv_rows: row_stats, then form_p, quant_operand and the rescale of
+// every token block in block order into fp32 accumulators that hold all D columns.  No block sums, no combine pass.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "bfpq.h"
@@ -64,6 +62,42 @@ constexpr int kTD = 64;                                   // columns of V per wo
 constexpr int kPitch = kTD + 1;                           // words per token row of the value tile
 
 __device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
+
+// ---- the steps every kernel below shares: each is written here once ----------------------------------------------------------------------
+// the exponent window table into LDS, by the 256 threads of a workgroup (no barrier)
+__device__ __forceinline__ void load_exp_win(uint8_t* s_win, const uint8_t* __restrict__ exp_win)
+{
+    for (int i = threadIdx.x; i < BFPQ_EXP_WIN_ENTRIES; i += 256) s_win[i] = exp_win[i];
+}
+
+// the tokens a head of `len` contracts over, or the keys it has, where the caller reaches L of them
+__device__ __forceinline__ int clamp_len(int len, int L) { return len < L ? (len > 0 ? len : 0) : L; }
+
+// the magnitude maximum of a lane's raw elements
+template <int DT, int NE> __device__ __forceinline__ uint32_t abs_max(const uint32_t (&xv)[NE])
+{
+    uint32_t mx = 0;
+#pragma unroll
+    for (int e = 0; e < NE; e++) mx = umax(mx, xv[e] & Traits<DT>::ABS);
+    return mx;
+}
+
+// quant_operand: a token's block as the B operand of I8Blk<BLK>::mfma.  xv: the lane's NE elements of the block (I8Blk::lane), mx their
+// abs_max.  The block maximum is taken over the token's four lanes (l & 15 alike), the scale is block_scale's, the codes quant_elem's
+// (pack_codes).  bs is the block's scale: its sat_exp is the exponent byte, token_scale makes the rescale's factors of it
+template <int BLK, int DT, int NE>
+__device__ __forceinline__ typename I8Blk<BLK>::op_t quant_operand(const uint32_t (&xv)[NE], uint32_t mx, int xm, float eps_dt, const uint8_t* s_win,
+                                                                   BlockScale& bs)
+{
+    static_assert(NE == (BLK == 64 ? 16 : 8), "a lane's bytes of a block");
+    mx = umax(mx, (uint32_t)__shfl_xor((int)mx, 16, 64));
+    mx = umax(mx, (uint32_t)__shfl_xor((int)mx, 32, 64));
+    bs = block_scale<DT>(mx, xm, eps_dt, s_win);
+    uint32_t pk[NE / 4];
+    pack_codes<DT>(xv, NE, bs, pk);
+    if constexpr (BLK == 64) return v4i{(int)pk[0], (int)pk[1], (int)pk[2], (int)pk[3]};
+    else return (long)(((uint64_t)pk[1] << 32) | pk[0]);
+}
 
 // one token block tb of one 64-column slice of V
 template <int DT>
@@ -108,13 +142,8 @@ __device__ __forceinline__ void v_block(const typename Traits<DT>::raw_t* __rest
     __syncthreads();
     for (int o = 0; o < 4; o++) mx = umax(mx, s_max[o * kTD + d]);
     const BlockScale bs = block_scale<DT>(mx, mant_bits, eps_dt, s_win);
-    uint32_t pk[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-        float c = 0.f;
-        if (i < per) quant_elem<DT>(raw_to_f32<DT>(raw[i]), bs, false, 0.f, &c);
-        pk[i >> 2] |= ((uint32_t)(int)c & 0xffu) << (8 * (i & 3));
-    }
+    uint32_t pk[4];
+    pack_codes<DT>(raw, per, bs, pk);
     if (d0 + d < D) {
         int8_t* const dst = vcodes + ((size_t)bh * D + d0 + d) * cap + tb * block + sq * per;
         if (per == 16) *reinterpret_cast<uint4*>(dst) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
@@ -149,7 +178,7 @@ __global__ void __launch_bounds__(256) k_kv_append(const void* __restrict__ knew
     __shared__ uint32_t s_val[64 * kPitch];
     __shared__ uint32_t s_max[4 * kTD];
     const int tid = threadIdx.x;
-    for (int i = tid; i < BFPQ_EXP_WIN_ENTRIES; i += 256) s_win[i] = exp_win[i];
+    load_exp_win(s_win, exp_win);
     __syncthreads();
     if ((int)blockIdx.x < nkb) {
         // keys: a thread per 16 elements of a row, blocks along D
@@ -168,21 +197,15 @@ __global__ void __launch_bounds__(256) k_kv_append(const void* __restrict__ knew
             live = valid && i < n;                                        // (one row: the lanes of a block are live together)
         }
         const raw_t* const src = reinterpret_cast<const raw_t*>(knew) + (size_t)row * D + seg * 16;
-        uint32_t raw[16], mx = 0;
+        uint32_t raw[16];
 #pragma unroll
         for (int v = 0; v < 16 / Tr::VEC; v++) bfpq_dev::load_raw_vec<DT>(src, v, raw + v * Tr::VEC);
-#pragma unroll
-        for (int e = 0; e < 16; e++) mx = umax(mx, raw[e] & Tr::ABS);
+        uint32_t mx = abs_max<DT>(raw);
         if (per >= 2) mx = umax(mx, (uint32_t)__shfl_xor((int)mx, 1, 64));
         if (per >= 4) mx = umax(mx, (uint32_t)__shfl_xor((int)mx, 2, 64));
         const BlockScale bs = block_scale<DT>(mx, mant_bits, eps_dt, s_win);
-        uint32_t pk[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int e = 0; e < 16; e++) {
-            float c;
-            quant_elem<DT>(raw_to_f32<DT>(raw[e]), bs, false, 0.f, &c);
-            pk[e >> 2] |= ((uint32_t)(int)c & 0xffu) << (8 * (e & 3));
-        }
+        uint32_t pk[4];
+        pack_codes<DT>(raw, 16, bs, pk);
         if (live) {
             const size_t r = (size_t)bh * cap + pos + i;
             *reinterpret_cast<uint4*>(kcodes + r * ldd + seg * 16) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
@@ -223,6 +246,16 @@ __device__ __forceinline__ int att_visible(int len, int Kx, int Tq, int t, int c
     return v < Kx ? (v > 0 ? v : 0) : Kx;
 }
 
+// att_scores: MODE kAtt's epilogue on a lane's four scores of keys n .. n + 3 of a row that sees `vis` keys
+template <int DT> __device__ __forceinline__ void att_scores(v2f& a01, v2f& a23, int n, int vis, float scale)
+{
+    const float ninf = -__builtin_inff();
+    a01.x = n + 0 < vis ? rnd<DT>(a01.x) * scale : ninf;
+    a01.y = n + 1 < vis ? rnd<DT>(a01.y) * scale : ninf;
+    a23.x = n + 2 < vis ? rnd<DT>(a23.x) * scale : ninf;
+    a23.y = n + 3 < vis ? rnd<DT>(a23.y) * scale : ninf;
+}
+
 // GRP: head b has R = group * Tq rows of x and out (row = query head of the group * Tq + token), walked in tiles of 16: blockIdx.y runs
 // over (head, tile).  Without GRP the argument `group` is passed and never read (the compiler drops it: the register figures of those
 // instances are the ones they had without it): one tile, the row is the token
@@ -241,7 +274,7 @@ __global__ void __launch_bounds__(256) k_kv_bmm_dec(const void* __restrict__ x, 
     constexpr int NBS = 64 / BLK;                                // blocks per 64-byte chunk
     constexpr int NE = BLK == 64 ? 16 : 8;                       // a lane's bytes of a block
     __shared__ uint8_t s_win[BFPQ_EXP_WIN_ENTRIES];
-    for (int i = threadIdx.x; i < BFPQ_EXP_WIN_ENTRIES; i += 256) s_win[i] = exp_win[i];
+    load_exp_win(s_win, exp_win);
     __syncthreads();
     const int w = threadIdx.x >> 6, l = threadIdx.x & 63, r = l & 15, q = l >> 4;
     const int n0 = ((int)blockIdx.x * 4 + w) * 16 * TM;
@@ -272,7 +305,7 @@ __global__ void __launch_bounds__(256) k_kv_bmm_dec(const void* __restrict__ x, 
         int No = Nout, len = 0;
         if constexpr (DEV) {
             len = lens[b / heads];
-            No = len < Nout ? (len > 0 ? len : 0) : Nout;
+            No = clamp_len(len, Nout);
             if (n0 >= No) {                                      // (wave-uniform) none of this wave's keys exists
                 if (tok) {
 #pragma unroll
@@ -329,32 +362,15 @@ __global__ void __launch_bounds__(256) k_kv_bmm_dec(const void* __restrict__ x, 
 #pragma unroll
             for (int s = 0; s < NBS; s++) {
                 if (c * NBS + s < nb) {                          // (wave-uniform)
-                    // x's block: the maximum over the four lanes of the token, the dtype-exact scale, the lane's codes
-                    uint32_t mx = 0;
-#pragma unroll
-                    for (int e = 0; e < NE; e++) mx = umax(mx, xv[s][e] & Tr::ABS);
-                    mx = umax(mx, (uint32_t)__shfl_xor((int)mx, 16, 64));
-                    mx = umax(mx, (uint32_t)__shfl_xor((int)mx, 32, 64));
-                    const BlockScale bs = block_scale<DT>(mx, xm, eps_dt, s_win);
-                    uint32_t pk[NE / 4];
-#pragma unroll
-                    for (int e = 0; e < NE / 4; e++) pk[e] = 0u;
-#pragma unroll
-                    for (int e = 0; e < NE; e++) {
-                        float cd;
-                        quant_elem<DT>(raw_to_f32<DT>(xv[s][e]), bs, false, 0.f, &cd);
-                        pk[e >> 2] |= ((uint32_t)(int)cd & 0xffu) << (8 * (e & 3));
-                    }
-                    op_t bF;
-                    if constexpr (BLK == 64) bF = v4i{(int)pk[0], (int)pk[1], (int)pk[2], (int)pk[3]};
-                    else bF = (long)(((uint64_t)pk[1] << 32) | pk[0]);
+                    BlockScale bs;                                // x's block
+                    const op_t bF = quant_operand<BLK, DT>(xv[s], abs_max<DT>(xv[s]), xm, eps_dt, s_win, bs);
                     v2f sx, nm;
                     token_scale((int)sat_exp(bs), xm, sx, nm);
                     const int sh = 8 * s;
 #pragma unroll
                     for (int i = 0; i < TM; i++) {
-                        const v2f sw01 = v2f{pow2_scale(exp_byte(ew[i][0], sh), wm), pow2_scale(exp_byte(ew[i][1], sh), wm)};
-                        const v2f sw23 = v2f{pow2_scale(exp_byte(ew[i][2], sh), wm), pow2_scale(exp_byte(ew[i][3], sh), wm)};
+                        v2f sw01, sw23;
+                        weight_scales(exp_byte(ew[i][0], sh), exp_byte(ew[i][1], sh), exp_byte(ew[i][2], sh), exp_byte(ew[i][3], sh), wm, sw01, sw23);
                         rescale(Blk::mfma(aF[i][s], bF, magic), sx, nm, sw01, sw23, acc[i][0], acc[i][1]);
                     }
                 }
@@ -380,11 +396,7 @@ __global__ void __launch_bounds__(256) k_kv_bmm_dec(const void* __restrict__ x, 
             for (int i = 0; i < TM; i++) {
                 const int n = n0 + 16 * i + 4 * q;
                 if constexpr (MODE == kAtt) {
-                    const int vis = att_visible(len, No, Tq, GRP ? row % Tq : r, causal);
-                    acc[i][0].x = n + 0 < vis ? rnd<DT>(acc[i][0].x) * scale : ninf;
-                    acc[i][0].y = n + 1 < vis ? rnd<DT>(acc[i][0].y) * scale : ninf;
-                    acc[i][1].x = n + 2 < vis ? rnd<DT>(acc[i][1].x) * scale : ninf;
-                    acc[i][1].y = n + 3 < vis ? rnd<DT>(acc[i][1].y) * scale : ninf;
+                    att_scores<DT>(acc[i][0], acc[i][1], n, att_visible(len, No, Tq, GRP ? row % Tq : r, causal), scale);
                 } else if constexpr (DEV) {
                     if (n + 0 >= No) acc[i][0].x = ninf;
                     if (n + 1 >= No) acc[i][0].y = ninf;
@@ -400,20 +412,18 @@ __global__ void __launch_bounds__(256) k_kv_bmm_dec(const void* __restrict__ x, 
 // ---- p v over a device-length cache, the contraction split over workgroups ------------------------------------------------------------
 // k_kv_pv_split: workgroup (64-column group of D, slice of kMaxCps or fewer 64-token chunks, head).  Head bh contracts over its first
 // Kx = min(lens[bh / heads], L) tokens; a workgroup whose slice starts at or past Kx returns at once.  Wave w first quantizes the chunks
-// w, w + 4, ... of the slice as k_kv_bmm_dec does (the lane map, the block maximum over a token's four lanes, block_scale / quant_elem;
-// elements at or past Kx are zeros whatever x holds there) into LDS, once for the four waves; then every wave multiplies the blocks of
+// w, w + 4, ... of the slice (quant_operand; elements at or past Kx are zeros whatever x holds there) into LDS, once for the four
+// waves; then every wave multiplies the blocks of
 // the slice against its 16 columns of v_codes and writes the raw result of the block product -- the exact integer sum on top of the
 // MFMA's C operand MAGIC_I -- to sums [BH, Tq, nbw, D], and the first wave of a head x's block exponents to xexp [BH, Tq, nbw].
 // k_kv_pv_combine: a thread per four columns of one token runs rescale() of bfpq_i8mma.h over the blocks j < ceil(Kx / BLK) in block
 // order: the fp32 additions are those of k_kv_bmm_dec in the same order, so the result is the same bits whatever the slice size.
 //
 // ATT (bfpq_kv_attend): x holds no probabilities but the fp32 score rows k_kv_bmm_dec<.., kAtt> left, pitch ldx.  Every workgroup first
-// reduces each row of its head over the row's visible columns (att_visible): the maximum (NaN propagates), then the sum of
-// expf(s - max) -- a thread over its columns 4 tid + 1024 i .. + 3 in ascending order, the 64 lanes of a wave by a butterfly, the four
-// waves as (w0 + w1) + (w2 + w3).  That order depends on the row alone, so all workgroups of a head hold the same two numbers per row,
-// whatever the slice size.  The quantization stage then forms p = expf(s - max) / sum for the lane's own elements, rounds it to the
-// dtype and goes on from those bits exactly as it does from a p it loaded; columns a row does not see are +0.  With pout the workgroups
-// of the first column group also store p [BH, Tq, ldp], zeros included (also those past the head's length, before they return).
+// reduces each row of its head over the row's visible columns (att_visible) with row_stats, so all workgroups of a head hold the same
+// two numbers per row, whatever the slice size.  The quantization stage then takes form_p's bits exactly as it takes a p it loaded.
+// With pout the workgroups of the first column group also store p [BH, Tq, ldp], zeros included (also those past the head's length,
+// before they return).
 //
 // GRP: head bh has R = group * Tq rows (k_kv_bmm_dec), blockIdx.z runs over (head, tile of 16 rows) and a workgroup reduces, quantizes
 // and multiplies the rows of its own tile; sums, xexp, the score rows and p are indexed by (head, row).  A row's visible length is that
@@ -422,6 +432,111 @@ constexpr int kMaxCps = 16;                               // chunks per slice (t
 constexpr int64_t kSplitGrid = 2048;                      // workgroups the chosen slice size aims to stay within
 
 __device__ __forceinline__ float nan_max(float a, float b) { return a != a ? a : (b != b ? b : (a > b ? a : b)); }
+
+// ---- the softmax row law: one order of operations per row, whatever kernel, slice or panel the row is in ---------------------------------
+__device__ __forceinline__ float wave_nan_max(float m)
+{
+#pragma unroll
+    for (int o = 32; o; o >>= 1) m = nan_max(m, __shfl_xor(m, o, 64));
+    return m;
+}
+__device__ __forceinline__ float wave_add(float a)
+{
+#pragma unroll
+    for (int o = 32; o; o >>= 1) a += __shfl_xor(a, o, 64);
+    return a;
+}
+
+// s_red [2][NR rows][4 waves]: the four waves' partial maxima of every row, then their partial sums; combined as (w0, w1), (w2, w3)
+__device__ __forceinline__ float row_max(const float* s_red, int row)
+{
+    const float* const sm = s_red + row * 4;
+    return nan_max(nan_max(sm[0], sm[1]), nan_max(sm[2], sm[3]));
+}
+template <int NR> __device__ __forceinline__ float row_sum(const float* s_red, int row)
+{
+    const float* const ss = s_red + (NR + row) * 4;
+    return (ss[0] + ss[1]) + (ss[2] + ss[3]);
+}
+
+// row_stats: rows t < nr of the fp32 score rows sc (pitch ld) reduced over their first vis(t) columns to s_red, by all 256 threads: the
+// maximum (NaN propagates), then the sum of expf(s - max) -- a thread over its columns 4 tid + 1024 i .. + 3 in ascending order, the 64
+// lanes of a wave by a butterfly, the waves' partials left for row_max / row_sum.  U rows' loads are in flight at a time; a row's
+// operations and their order do not depend on U, nr or the rows beside it.  Both passes end with a barrier; whatever the caller wrote
+// to LDS before the call is visible after it
+template <int U, int NR, class V>
+__device__ __forceinline__ void row_stats(const float* __restrict__ sc, int ld, int nr, V&& vis, float* s_red)
+{
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
+    // f(u, v) over the visible elements this thread owns of rows t0 + u, u < U, each row's in ascending order
+    auto walk = [&](int t0, auto&& f) __attribute__((always_inline)) {
+        int vt[U], vm = 0;
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            vt[u] = t0 + u < nr ? vis(t0 + u) : 0;
+            vm = vt[u] > vm ? vt[u] : vm;
+        }
+        for (int k = tid * 4; k < vm; k += 1024) {
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                if (k < vt[u]) {
+                    const float4 v = *reinterpret_cast<const float4*>(sc + (size_t)(t0 + u) * ld + k);
+                    f(u, v.x);
+                    if (k + 1 < vt[u]) f(u, v.y);
+                    if (k + 2 < vt[u]) f(u, v.z);
+                    if (k + 3 < vt[u]) f(u, v.w);
+                }
+            }
+        }
+    };
+    for (int t0 = 0; t0 < nr; t0 += U) {
+        float m[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) m[u] = -__builtin_inff();
+        walk(t0, [&](int u, float v) { m[u] = nan_max(m[u], v); });
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            m[u] = wave_nan_max(m[u]);
+            if (l == 0 && t0 + u < nr) s_red[(t0 + u) * 4 + w] = m[u];
+        }
+    }
+    __syncthreads();
+    for (int t0 = 0; t0 < nr; t0 += U) {
+        float m[U], a[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            m[u] = row_max(s_red, t0 + u < nr ? t0 + u : 0);
+            a[u] = 0.f;
+        }
+        walk(t0, [&](int u, float v) { a[u] += expf(v - m[u]); });
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            a[u] = wave_add(a[u]);
+            if (l == 0 && t0 + u < nr) s_red[(NR + t0 + u) * 4 + w] = a[u];
+        }
+    }
+    __syncthreads();
+}
+
+// form_p: p of the lane's NE elements k0 .. of its fp32 score row, in the dtype's bits: expf(s - rmax) / rsum rounded once, +0 from the
+// row's visible length on.  prow (or null): the lane's row of the p the caller returns; the visible elements are stored there
+template <int DT, int NE>
+__device__ __forceinline__ void form_p(const float* __restrict__ srow, int k0, int vis, float rmax, float rsum, typename Traits<DT>::raw_t* prow,
+                                       uint32_t (&xv)[NE])
+{
+#pragma unroll
+    for (int v = 0; v < NE / 4; v++) {
+        float4 sv = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (k0 + 4 * v < vis) sv = *reinterpret_cast<const float4*>(srow + k0 + 4 * v);
+        const float se[4] = {sv.x, sv.y, sv.z, sv.w};
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const int k = k0 + 4 * v + e;
+            xv[4 * v + e] = k < vis ? f32_to_raw<DT>(expf(se[e] - rmax) / rsum) : 0u;
+            if (prow && k < vis) prow[k] = (typename Traits<DT>::raw_t)xv[4 * v + e];
+        }
+    }
+}
 
 template <int BLK, int DT, bool ATT, bool GRP = false>
 __global__ void __launch_bounds__(256) k_kv_pv_split(const void* __restrict__ x, const int8_t* __restrict__ vc, int32_t* __restrict__ sums,
@@ -444,7 +559,7 @@ __global__ void __launch_bounds__(256) k_kv_pv_split(const void* __restrict__ x,
     const int r0 = GRP ? ((int)blockIdx.z % ntiles) * 16 : 0, nr = GRP ? (R - r0 < 16 ? R - r0 : 16) : Tq;   // the tile's first row, its rows
     auto token = [&](int i) __attribute__((always_inline)) { return GRP ? (r0 + i) % Tq : i; };               // of the tile's row i
     const int len = lens[bh / heads];
-    const int Kx = len < L ? (len > 0 ? len : 0) : L;
+    const int Kx = clamp_len(len, L);
     const int w = threadIdx.x >> 6, l = threadIdx.x & 63, r = l & 15, q = l >> 4;
     const bool tok = r < nr;
     raw_t* const prow = pout ? reinterpret_cast<raw_t*>(pout) + ((size_t)bh * R + r0) * ldp : nullptr;   // the tile's rows of p
@@ -458,44 +573,17 @@ __global__ void __launch_bounds__(256) k_kv_pv_split(const void* __restrict__ x,
         }
     }
     if ((c0 << 6) >= Kx) return;                                 // (the whole workgroup, before any barrier)
-    for (int i = threadIdx.x; i < BFPQ_EXP_WIN_ENTRIES; i += 256) s_win[i] = exp_win[i];
+    load_exp_win(s_win, exp_win);
     const float* const srow = reinterpret_cast<const float*>(x) + ((size_t)bh * R + r0 + (tok ? r : 0)) * ldx;   // (ATT) the lane's score row
+    raw_t* const plane = (prow && blockIdx.x == 0) ? prow + (size_t)r * ldp : nullptr;                            // (ATT) and its row of p
     float rmax = 0.f, rsum = 1.f;
     int vis = 0;
     if constexpr (ATT) {
-        const float* const sc = reinterpret_cast<const float*>(x) + ((size_t)bh * R + r0) * ldx;
-        const float ninf = -__builtin_inff();
-        // f(v) over the visible elements of the tile's row t this thread owns, in ascending order
-        auto walk = [&](int t, int vt, auto&& f) __attribute__((always_inline)) {
-            for (int k = (int)threadIdx.x * 4; k < vt; k += 1024) {
-                const float4 v = *reinterpret_cast<const float4*>(sc + (size_t)t * ldx + k);
-                f(v.x);
-                if (k + 1 < vt) f(v.y);
-                if (k + 2 < vt) f(v.z);
-                if (k + 3 < vt) f(v.w);
-            }
-        };
-        for (int t = 0; t < nr; t++) {
-            float m = ninf;
-            walk(t, att_visible(len, Kx, Tq, token(t), causal), [&](float v) { m = nan_max(m, v); });
-#pragma unroll
-            for (int o = 32; o; o >>= 1) m = nan_max(m, __shfl_xor(m, o, 64));
-            if (l == 0) s_red[t * 4 + w] = m;
-        }
-        __syncthreads();
-        for (int t = 0; t < nr; t++) {
-            const float m = nan_max(nan_max(s_red[t * 4], s_red[t * 4 + 1]), nan_max(s_red[t * 4 + 2], s_red[t * 4 + 3]));
-            float a = 0.f;
-            walk(t, att_visible(len, Kx, Tq, token(t), causal), [&](float v) { a += expf(v - m); });
-#pragma unroll
-            for (int o = 32; o; o >>= 1) a += __shfl_xor(a, o, 64);
-            if (l == 0) s_red[(BFPQ_KV_DEC_MAX_TOKENS + t) * 4 + w] = a;
-        }
-        __syncthreads();
+        row_stats<1, BFPQ_KV_DEC_MAX_TOKENS>(reinterpret_cast<const float*>(x) + ((size_t)bh * R + r0) * ldx, ldx, nr,
+                                             [&](int t) { return att_visible(len, Kx, Tq, token(t), causal); }, s_red);
         if (tok) {
-            const float* const sm = s_red + r * 4, * const ss = s_red + (BFPQ_KV_DEC_MAX_TOKENS + r) * 4;
-            rmax = nan_max(nan_max(sm[0], sm[1]), nan_max(sm[2], sm[3]));
-            rsum = (ss[0] + ss[1]) + (ss[2] + ss[3]);
+            rmax = row_max(s_red, r);
+            rsum = row_sum<BFPQ_KV_DEC_MAX_TOKENS>(s_red, r);
             vis = att_visible(len, Kx, Tq, token(r), causal);
         }
     } else __syncthreads();
@@ -507,20 +595,9 @@ __global__ void __launch_bounds__(256) k_kv_pv_split(const void* __restrict__ x,
         for (int s = 0; s < NBS; s++) {
             if (c * NBS + s >= nb) break;                        // (wave-uniform)
             const int k0 = (c << 6) + s * BLK + Blk::lane(q);
-            uint32_t xv[NE], mx = 0;
-            if constexpr (ATT) {                                 // p of the lane's elements, in the dtype's bits; the store for return_probs
-#pragma unroll
-                for (int v = 0; v < NE / 4; v++) {
-                    float4 sv = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (k0 + 4 * v < vis) sv = *reinterpret_cast<const float4*>(srow + k0 + 4 * v);
-                    const float se[4] = {sv.x, sv.y, sv.z, sv.w};
-#pragma unroll
-                    for (int e = 0; e < 4; e++) {
-                        const int k = k0 + 4 * v + e;
-                        xv[4 * v + e] = k < vis ? f32_to_raw<DT>(expf(se[e] - rmax) / rsum) : 0u;
-                        if (pout && blockIdx.x == 0 && k < vis) prow[(size_t)r * ldp + k] = (raw_t)xv[4 * v + e];
-                    }
-                }
+            uint32_t xv[NE];
+            if constexpr (ATT) {
+                form_p<DT>(srow, k0, vis, rmax, rsum, plane, xv);
             } else if (xvec && k0 + NE <= L) {                   // rows 16-byte aligned: the lane's elements in 16-byte loads
 #pragma unroll
                 for (int v = 0; v < NE / Tr::VEC; v++) bfpq_dev::load_raw_vec<DT>(xr + k0, v, xv + v * Tr::VEC);
@@ -528,27 +605,13 @@ __global__ void __launch_bounds__(256) k_kv_pv_split(const void* __restrict__ x,
 #pragma unroll
                 for (int e = 0; e < NE; e++) xv[e] = k0 + e < L ? (uint32_t)xr[k0 + e] : 0u;
             }
+            if constexpr (!ATT) {
 #pragma unroll
-            for (int e = 0; e < NE; e++) {
-                if (!ATT && (!tok || k0 + e >= Kx)) xv[e] = 0u;
-                mx = umax(mx, xv[e] & Tr::ABS);
+                for (int e = 0; e < NE; e++)
+                    if (!tok || k0 + e >= Kx) xv[e] = 0u;
             }
-            mx = umax(mx, (uint32_t)__shfl_xor((int)mx, 16, 64));
-            mx = umax(mx, (uint32_t)__shfl_xor((int)mx, 32, 64));
-            const BlockScale bs = block_scale<DT>(mx, xm, eps_dt, s_win);
-            uint32_t pk[NE / 4];
-#pragma unroll
-            for (int e = 0; e < NE / 4; e++) pk[e] = 0u;
-#pragma unroll
-            for (int e = 0; e < NE; e++) {
-                float cd;
-                quant_elem<DT>(raw_to_f32<DT>(xv[e]), bs, false, 0.f, &cd);
-                pk[e >> 2] |= ((uint32_t)(int)cd & 0xffu) << (8 * (e & 3));
-            }
-            op_t bF;
-            if constexpr (BLK == 64) bF = v4i{(int)pk[0], (int)pk[1], (int)pk[2], (int)pk[3]};
-            else bF = (long)(((uint64_t)pk[1] << 32) | pk[0]);
-            s_b[c - c0][s][l] = bF;
+            BlockScale bs;
+            s_b[c - c0][s][l] = quant_operand<BLK, DT>(xv, abs_max<DT>(xv), xm, eps_dt, s_win, bs);
             if (q == 0) s_e[c - c0][s][r] = sat_exp(bs);
         }
     }
@@ -586,9 +649,7 @@ __global__ void __launch_bounds__(256) k_kv_pv_combine(const int32_t* __restrict
     const int d4 = D >> 2, n = (int)(idx % d4) * 4;
     const int64_t row = idx / d4;                                // bh * Tq + t
     const int bh = (int)(row / Tq);
-    const int len = lens[bh / heads];
-    const int Kx = len < L ? (len > 0 ? len : 0) : L;
-    const int nb = (Kx + block - 1) / block;
+    const int nb = (clamp_len(lens[bh / heads], L) + block - 1) / block;
     const int32_t* const sr = sums + (size_t)row * nbw * D + n;
     const int8_t* const xe = xexp + (size_t)row * nbw;
     const int8_t* const we = ve + ((size_t)bh * D + n) * ldve;
@@ -612,8 +673,8 @@ __global__ void __launch_bounds__(256) k_kv_pv_combine(const int32_t* __restrict
             if (j0 + u >= nb) break;
             v2f sx, nm;
             token_scale(ex[u], xm, sx, nm);
-            const v2f sw01 = v2f{pow2_scale(ew[u][0], wm), pow2_scale(ew[u][1], wm)};
-            const v2f sw23 = v2f{pow2_scale(ew[u][2], wm), pow2_scale(ew[u][3], wm)};
+            v2f sw01, sw23;
+            weight_scales(ew[u][0], ew[u][1], ew[u][2], ew[u][3], wm, sw01, sw23);
             rescale(d[u], sx, nm, sw01, sw23, a01, a23);
         }
     }
@@ -648,11 +709,10 @@ template <int BLK> struct LdsOp {
     __device__ __forceinline__ static int slot(int l) { return l & (LN - 1); }
 };
 
-// q k^T of panel rows: workgroup (kv head b, 64 panel rows).  Its rows of q are quantized once -- k_kv_bmm_dec's code: the block maximum
-// over the four lanes of a token, block_scale / quant_elem -- and kept as MFMA operands s_q [wave][block][lane] with their exponents
-// s_qe; then it loops over the tiles of 64 keys some row of it sees: the tile's codes s_k [16-key tile][block][lane] and exponents s_ke
+// q k^T of panel rows: workgroup (kv head b, 64 panel rows).  Its rows of q are quantized once (quant_operand) and kept as MFMA
+// operands s_q [wave][block][lane] with their exponents s_qe; then it loops over the tiles of 64 keys some row of it sees: the tile's codes s_k [16-key tile][block][lane] and exponents s_ke
 // [block][key] are loaded once for the four waves, and a wave whose own rows see none of the tile sits it out.  Blocks are added in
-// block order, the epilogue is kAtt's; only the columns below the wave's visible length are written, which is all the softmax reads.
+// block order, the epilogue is att_scores; only the columns below the wave's visible length are written, which is all the softmax reads.
 template <int BLK, int DT>
 __global__ void __launch_bounds__(256) k_kv_qk_rows(const void* __restrict__ x, const int8_t* __restrict__ kc, const int8_t* __restrict__ ke,
                                                     float* __restrict__ ws, int Tq, int D, int Nout, int ldd, int cap, int pitch, int xm, int wm,
@@ -675,11 +735,11 @@ __global__ void __launch_bounds__(256) k_kv_qk_rows(const void* __restrict__ x, 
     const int PR = group * rows, nwg = (PR + kRowsWg - 1) / kRowsWg;
     const int b = (int)blockIdx.x / nwg, pr0 = ((int)blockIdx.x % nwg) * kRowsWg;
     const int len = lens[b / heads];
-    const int No = len < Nout ? (len > 0 ? len : 0) : Nout;
+    const int No = clamp_len(len, Nout);
     const int prl = pr0 + kRowsWg - 1 < PR ? pr0 + kRowsWg - 1 : PR - 1;
     const int vwg = range_visible(pr0, prl, rows, row0, len, No, Tq, causal);
     if (vwg <= 0) return;                                        // (the whole workgroup, before any barrier) no row sees a key
-    for (int i = tid; i < BFPQ_EXP_WIN_ENTRIES; i += 256) s_win[i] = exp_win[i];
+    load_exp_win(s_win, exp_win);
     __syncthreads();
     const int pw0 = pr0 + 16 * w, pwl = pw0 + 15 < PR ? pw0 + 15 : PR - 1;
     const int vw = pw0 < PR ? range_visible(pw0, pwl, rows, row0, len, No, Tq, causal) : 0;   // what the wave's rows see at most
@@ -689,35 +749,19 @@ __global__ void __launch_bounds__(256) k_kv_qk_rows(const void* __restrict__ x, 
     {
         const raw_t* const xr = reinterpret_cast<const raw_t*>(x) + ((size_t)b * group * Tq + (size_t)hq * Tq + t) * D;
         for (int j = 0; j < nbd; j++) {
-            uint32_t xv[NE], mx = 0;
+            uint32_t xv[NE];
 #pragma unroll
             for (int v = 0; v < NE / Tr::VEC; v++) bfpq_dev::load_raw_vec<DT>(xr + j * BLK + Blk::lane(q), v, xv + v * Tr::VEC);
 #pragma unroll
-            for (int e = 0; e < NE; e++) {
+            for (int e = 0; e < NE; e++)
                 if (!tok) xv[e] = 0u;
-                mx = umax(mx, xv[e] & Tr::ABS);
-            }
-            mx = umax(mx, (uint32_t)__shfl_xor((int)mx, 16, 64));
-            mx = umax(mx, (uint32_t)__shfl_xor((int)mx, 32, 64));
-            const BlockScale bs = block_scale<DT>(mx, xm, eps_dt, s_win);
-            uint32_t pk[NE / 4];
-#pragma unroll
-            for (int e = 0; e < NE / 4; e++) pk[e] = 0u;
-#pragma unroll
-            for (int e = 0; e < NE; e++) {
-                float cd;
-                quant_elem<DT>(raw_to_f32<DT>(xv[e]), bs, false, 0.f, &cd);
-                pk[e >> 2] |= ((uint32_t)(int)cd & 0xffu) << (8 * (e & 3));
-            }
-            op_t bF;
-            if constexpr (BLK == 64) bF = v4i{(int)pk[0], (int)pk[1], (int)pk[2], (int)pk[3]};
-            else bF = (long)(((uint64_t)pk[1] << 32) | pk[0]);
+            BlockScale bs;
+            const op_t bF = quant_operand<BLK, DT>(xv, abs_max<DT>(xv), xm, eps_dt, s_win, bs);
             if (l < LN) s_q[(w * nbd + j) * LN + l] = bF;
             if (q == 0) s_qe[(w * nbd + j) * 16 + r] = sat_exp(bs);
         }
     }
     const v4i magic = {MAGIC_I, MAGIC_I, MAGIC_I, MAGIC_I};
-    const float ninf = -__builtin_inff();
     const int vis = tok ? att_visible(len, No, Tq, t, causal) : 0;
     float* const orow = ws + ((size_t)b * PR + (tok ? pr : pr0)) * pitch;
     const int nkt = (vwg + 63) >> 6;
@@ -743,9 +787,8 @@ __global__ void __launch_bounds__(256) k_kv_qk_rows(const void* __restrict__ x, 
             for (int i = 0; i < 4; i++) {
                 op_t aF = s_k[(i * nbd + j) * LN + LdsOp<BLK>::slot(l)];
                 if (!Blk::a_live(q)) aF = op_t{};
-                const uint32_t ew = *reinterpret_cast<const uint32_t*>(s_ke + j * 64 + 16 * i + 4 * q);
-                const v2f sw01 = v2f{pow2_scale(exp_byte(ew, 0), wm), pow2_scale(exp_byte(ew, 8), wm)};
-                const v2f sw23 = v2f{pow2_scale(exp_byte(ew, 16), wm), pow2_scale(exp_byte(ew, 24), wm)};
+                v2f sw01, sw23;
+                weight_scales(*reinterpret_cast<const uint32_t*>(s_ke + j * 64 + 16 * i + 4 * q), wm, sw01, sw23);
                 rescale(Blk::mfma(aF, bF, magic), sx, nm, sw01, sw23, acc[i][0], acc[i][1]);
             }
         }
@@ -753,10 +796,7 @@ __global__ void __launch_bounds__(256) k_kv_qk_rows(const void* __restrict__ x, 
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 const int n = (kt << 6) + 16 * i + 4 * q;
-                acc[i][0].x = n + 0 < vis ? rnd<DT>(acc[i][0].x) * scale : ninf;
-                acc[i][0].y = n + 1 < vis ? rnd<DT>(acc[i][0].y) * scale : ninf;
-                acc[i][1].x = n + 2 < vis ? rnd<DT>(acc[i][1].x) * scale : ninf;
-                acc[i][1].y = n + 3 < vis ? rnd<DT>(acc[i][1].y) * scale : ninf;
+                att_scores<DT>(acc[i][0], acc[i][1], n, vis, scale);
                 if (n < Nout) store4<BFPQ_F32>(orow, n, acc[i][0], acc[i][1]);
             }
         }
@@ -764,11 +804,10 @@ __global__ void __launch_bounds__(256) k_kv_qk_rows(const void* __restrict__ x, 
 }
 
 // softmax and p v of panel rows: workgroup (kv head bh, 64 panel rows), wave w the 16-row tile w and all D <= 256 columns.  First every
-// row's maximum and sum, all 256 threads per row in k_kv_pv_split<.., true>'s order (four rows' loads in flight at a time; a row's
-// operations and their order are unchanged): the same two numbers, bit for bit.  Then the walk over 64-token chunks: the chunk's V codes
-// s_v [16-column tile][block][lane] and exponents s_ve [block][column] go through LDS once for the four waves; a wave forms p of its rows
-// for a block, rounds, stores (pout) and quantizes it as k_kv_pv_split does, and adds the block's term for every column tile with
-// rescale() -- k_kv_pv_combine's additions in its order.  A wave stops forming p after the last block any of its rows sees (jstop); for
+// row's maximum and sum (row_stats, four rows' loads in flight at a time).  Then the walk over 64-token chunks: the chunk's V codes
+// s_v [16-column tile][block][lane] and exponents s_ve [block][column] go through LDS once for the four waves; a wave runs form_p and
+// quant_operand on its rows for a block and adds the block's term for every column tile with rescale() -- k_kv_pv_combine's additions
+// in its order.  A wave stops forming p after the last block any of its rows sees (jstop); for
 // every block j in jstop .. nb - 1 the combine pass would still add the term of an all-zero p block -- its scale from block_scale(0),
 // NaN where the dtype's epsilon is zero; the block sum zero; V's scale, NaN for a NaN block -- so the wave adds exactly that term,
 // rescale() of the bare MAGIC_I, from V's exponent bytes alone.  With pout, p is zero from a row's visible length on.
@@ -794,69 +833,17 @@ __global__ void __launch_bounds__(256) k_kv_pv_rows(const float* __restrict__ ws
     const int bh = (int)blockIdx.x / nwg, pr0 = ((int)blockIdx.x % nwg) * kRowsWg;
     const int nrw = PR - pr0 < kRowsWg ? PR - pr0 : kRowsWg;      // the workgroup's rows
     const int len = lens[bh / heads];
-    const int Kx = len < L ? (len > 0 ? len : 0) : L;
+    const int Kx = clamp_len(len, L);
     auto row_vis = [&](int i) __attribute__((always_inline)) { return att_visible(len, Kx, Tq, row0 + (pr0 + i) % rows, causal); };
-    for (int i = tid; i < BFPQ_EXP_WIN_ENTRIES; i += 256) s_win[i] = exp_win[i];
-    const float* const sc = ws + ((size_t)bh * PR + pr0) * pitch;
-    {
-        const float ninf = -__builtin_inff();
-        // f(u, v) over the visible elements this thread owns of rows t0 + u, u < 4, each row's in ascending order
-        auto walk4 = [&](int t0, auto&& f) __attribute__((always_inline)) {
-            int vt[4], vm = 0;
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                vt[u] = t0 + u < nrw ? row_vis(t0 + u) : 0;
-                vm = vt[u] > vm ? vt[u] : vm;
-            }
-            for (int k = tid * 4; k < vm; k += 1024) {
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    if (k < vt[u]) {
-                        const float4 v = *reinterpret_cast<const float4*>(sc + (size_t)(t0 + u) * pitch + k);
-                        f(u, v.x);
-                        if (k + 1 < vt[u]) f(u, v.y);
-                        if (k + 2 < vt[u]) f(u, v.z);
-                        if (k + 3 < vt[u]) f(u, v.w);
-                    }
-                }
-            }
-        };
-        for (int t0 = 0; t0 < nrw; t0 += 4) {
-            float m[4] = {ninf, ninf, ninf, ninf};
-            walk4(t0, [&](int u, float v) { m[u] = nan_max(m[u], v); });
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-#pragma unroll
-                for (int o = 32; o; o >>= 1) m[u] = nan_max(m[u], __shfl_xor(m[u], o, 64));
-                if (l == 0 && t0 + u < nrw) s_red[(t0 + u) * 4 + w] = m[u];
-            }
-        }
-        __syncthreads();
-        for (int t0 = 0; t0 < nrw; t0 += 4) {
-            float m[4], a[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const float* const sm = s_red + (t0 + u < nrw ? t0 + u : 0) * 4;
-                m[u] = nan_max(nan_max(sm[0], sm[1]), nan_max(sm[2], sm[3]));
-            }
-            walk4(t0, [&](int u, float v) { a[u] += expf(v - m[u]); });
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-#pragma unroll
-                for (int o = 32; o; o >>= 1) a[u] += __shfl_xor(a[u], o, 64);
-                if (l == 0 && t0 + u < nrw) s_red[(kRowsWg + t0 + u) * 4 + w] = a[u];
-            }
-        }
-        __syncthreads();
-    }
+    load_exp_win(s_win, exp_win);
+    row_stats<4, kRowsWg>(ws + ((size_t)bh * PR + pr0) * pitch, pitch, nrw, row_vis, s_red);
     const int pw0 = pr0 + 16 * w, pr = pw0 + r;
     const bool tok = pr < PR;
     float rmax = 0.f, rsum = 1.f;
     int vis = 0;
     if (tok) {
-        const float* const sm = s_red + (16 * w + r) * 4, * const ss = s_red + (kRowsWg + 16 * w + r) * 4;
-        rmax = nan_max(nan_max(sm[0], sm[1]), nan_max(sm[2], sm[3]));
-        rsum = (ss[0] + ss[1]) + (ss[2] + ss[3]);
+        rmax = row_max(s_red, 16 * w + r);
+        rsum = row_sum<kRowsWg>(s_red, 16 * w + r);
         vis = row_vis(16 * w + r);
     }
     const int hq = tok ? pr / rows : 0, t = tok ? row0 + pr % rows : row0;
@@ -890,36 +877,10 @@ __global__ void __launch_bounds__(256) k_kv_pv_rows(const float* __restrict__ ws
             const int j = c * NBS + s;
             if (j >= jstop) break;                               // (wave-uniform)
             const int k0 = (c << 6) + s * BLK + Blk::lane(q);
-            uint32_t xv[NE], mx = 0;
-#pragma unroll
-            for (int v = 0; v < NE / 4; v++) {                   // p of the lane's elements, in the dtype's bits; the store for return_probs
-                float4 sv = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (k0 + 4 * v < vis) sv = *reinterpret_cast<const float4*>(srow + k0 + 4 * v);
-                const float se[4] = {sv.x, sv.y, sv.z, sv.w};
-#pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    const int k = k0 + 4 * v + e;
-                    xv[4 * v + e] = k < vis ? f32_to_raw<DT>(expf(se[e] - rmax) / rsum) : 0u;
-                    if (prow && k < vis) prow[k] = (raw_t)xv[4 * v + e];
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < NE; e++) mx = umax(mx, xv[e] & Tr::ABS);
-            mx = umax(mx, (uint32_t)__shfl_xor((int)mx, 16, 64));
-            mx = umax(mx, (uint32_t)__shfl_xor((int)mx, 32, 64));
-            const BlockScale bs = block_scale<DT>(mx, xm, eps_dt, s_win);
-            uint32_t pk[NE / 4];
-#pragma unroll
-            for (int e = 0; e < NE / 4; e++) pk[e] = 0u;
-#pragma unroll
-            for (int e = 0; e < NE; e++) {
-                float cd;
-                quant_elem<DT>(raw_to_f32<DT>(xv[e]), bs, false, 0.f, &cd);
-                pk[e >> 2] |= ((uint32_t)(int)cd & 0xffu) << (8 * (e & 3));
-            }
-            op_t bF;
-            if constexpr (BLK == 64) bF = v4i{(int)pk[0], (int)pk[1], (int)pk[2], (int)pk[3]};
-            else bF = (long)(((uint64_t)pk[1] << 32) | pk[0]);
+            uint32_t xv[NE];
+            form_p<DT>(srow, k0, vis, rmax, rsum, prow, xv);
+            BlockScale bs;
+            const op_t bF = quant_operand<BLK, DT>(xv, abs_max<DT>(xv), xm, eps_dt, s_win, bs);
             v2f sx, nm;
             token_scale((int)sat_exp(bs), xm, sx, nm);
 #pragma unroll
@@ -927,9 +888,8 @@ __global__ void __launch_bounds__(256) k_kv_pv_rows(const float* __restrict__ ws
                 if (i < ndt) {                                   // (uniform)
                     op_t aF = s_v[(i * NBS + s) * LN + LdsOp<BLK>::slot(l)];
                     if (!Blk::a_live(q)) aF = op_t{};
-                    const uint32_t ew = *reinterpret_cast<const uint32_t*>(s_ve + s * D + 16 * i + 4 * q);
-                    const v2f sw01 = v2f{pow2_scale(exp_byte(ew, 0), wm), pow2_scale(exp_byte(ew, 8), wm)};
-                    const v2f sw23 = v2f{pow2_scale(exp_byte(ew, 16), wm), pow2_scale(exp_byte(ew, 24), wm)};
+                    v2f sw01, sw23;
+                    weight_scales(*reinterpret_cast<const uint32_t*>(s_ve + s * D + 16 * i + 4 * q), wm, sw01, sw23);
                     rescale(Blk::mfma(aF, bF, magic), sx, nm, sw01, sw23, acc[i][0], acc[i][1]);
                 }
             }
@@ -945,8 +905,8 @@ __global__ void __launch_bounds__(256) k_kv_pv_rows(const float* __restrict__ ws
             for (int i = 0; i < kMaxDT; i++) {
                 if (i < ndt) {
                     const int8_t* const we = ve + ((size_t)bh * D + 16 * i + 4 * q) * ldve + j;
-                    const v2f sw01 = v2f{pow2_scale((int)we[0], wm), pow2_scale((int)we[ldve], wm)};
-                    const v2f sw23 = v2f{pow2_scale((int)we[2 * ldve], wm), pow2_scale((int)we[3 * ldve], wm)};
+                    v2f sw01, sw23;
+                    weight_scales((int)we[0], (int)we[ldve], (int)we[2 * ldve], (int)we[3 * ldve], wm, sw01, sw23);
                     rescale(magic, sx, nm, sw01, sw23, acc[i][0], acc[i][1]);
                 }
             }
@@ -1034,6 +994,47 @@ int pv_dev(const void* x, const void* wcodes, const int8_t* wexp, void* out, con
     return (int)hipGetLastError();
 }
 
+// ---- what the entries check alike.  Each entry runs the three steps in this order -- values (BFPQ_E_ARG), "nothing to do", shapes
+// (BFPQ_E_UNSUPPORTED), pointers (BFPQ_E_ARG) -- with its own conditions beside the shared ones of the same step ----------------------------
+// bfpq_kv_bmm_dec and bfpq_kv_bmm_dec_gqa; x and out hold R rows per head
+inline bool dec_values_ok(int dtype, int block_size, int xm, int wm, int family, int64_t B, int64_t Tq, int64_t Nout, int64_t Kx)
+{
+    return dtype_ok(dtype) && i8_block_ok(block_size) && i8_mant_ok(xm) && i8_mant_ok(wm) && (family == BFPQ_KV_QK || family == BFPQ_KV_PV) &&
+           B >= 0 && Tq >= 0 && Nout >= 0 && Kx >= 0;
+}
+inline bool dec_shapes_ok(int family, int block_size, int64_t Tq, int64_t R, int64_t Kx, int64_t Nout, int64_t ldx, int64_t ldw, int64_t ldwe,
+                          int64_t w_bstride, int64_t ldo)
+{
+    const int64_t nb = (Kx + block_size - 1) / block_size;
+    return Tq <= BFPQ_KV_DEC_MAX_TOKENS && Kx >= 1 && (family == BFPQ_KV_QK ? Kx % block_size == 0 : Nout % 16 == 0) && ldx >= Kx &&
+           ldw % 64 == 0 && ldw >= (Kx + 63) / 64 * 64 && ldwe >= nb && w_bstride >= Nout && ldo % 4 == 0 && ldo >= Nout &&
+           w_bstride * ldw < kLim && w_bstride * ldwe < kLim && R * ldx < kLim && R * ldo < kLim;
+}
+inline bool dec_ptrs_ok(const void* x, const void* wcodes, const void* wexp, const void* out, const void* exp_win, int dtype)
+{
+    return x && wcodes && wexp && out && exp_win && aligned16(wcodes, out) && !(reinterpret_cast<uintptr_t>(x) & (dtype == BFPQ_F32 ? 3u : 1u));
+}
+
+// bfpq_kv_attend_gqa and bfpq_kv_attend_rows
+inline bool att_values_ok(int dtype, int block_size, int xm, int wm, int64_t BH, int64_t heads, int64_t Tq, int64_t group, int64_t chunks_per_split,
+                          int causal, double scale)
+{
+    return dtype_ok(dtype) && i8_block_ok(block_size) && i8_mant_ok(xm) && i8_mant_ok(wm) && BH >= 0 && Tq >= 0 && heads >= 1 && BH % heads == 0 &&
+           group >= 1 && chunks_per_split >= 0 && (causal == 0 || causal == 1) && scale - scale == 0.0 && (float)scale - (float)scale == 0.f;
+}
+inline bool att_shapes_ok(int block_size, int64_t group, int64_t D, int64_t max_len, int64_t cap, int64_t ldd, int64_t ldo, int64_t ldp,
+                          const void* p_out, int64_t chunks_per_split)
+{
+    return bfpq_kv_ok(D, cap, block_size) && group < kLim && max_len >= 1 && max_len <= cap && ldd >= D && ldd % 64 == 0 && ldo % 4 == 0 &&
+           ldo >= D && !(p_out && ldp < max_len) && cap * ldd < kLim && chunks_per_split <= kMaxCps;
+}
+inline bool att_ptrs_ok(const void* q, const void* k_codes, const void* k_exps, const void* v_codes, const void* v_exps, const void* out,
+                        const void* p_out, const void* lens, const void* exp_win, const void* score_ws, int dtype)
+{
+    return q && k_codes && k_exps && v_codes && v_exps && out && lens && exp_win && score_ws && aligned16(k_codes, v_codes, out, score_ws) &&
+           !(reinterpret_cast<uintptr_t>(lens) & 3u) && !(reinterpret_cast<uintptr_t>(p_out) & (dtype == BFPQ_F32 ? 3u : 1u));
+}
+
 }  // namespace
 
 extern "C" {
@@ -1071,17 +1072,10 @@ int bfpq_kv_bmm_dec(const void* x, const void* wcodes, const int8_t* wexp, void*
                     int64_t ldx, int64_t ldw, int64_t ldwe, int64_t w_bstride, int64_t ldo, int family, int dtype, int block_size,
                     int x_mant_bits, int w_mant_bits, double epsilon, const uint8_t* exp_win, void* stream)
 {
-    if (!dtype_ok(dtype) || !i8_block_ok(block_size) || !i8_mant_ok(x_mant_bits) || !i8_mant_ok(w_mant_bits) ||
-        (family != BFPQ_KV_QK && family != BFPQ_KV_PV) || B < 0 || Tq < 0 || Nout < 0 || Kx < 0)
-        return BFPQ_E_ARG;
+    if (!dec_values_ok(dtype, block_size, x_mant_bits, w_mant_bits, family, B, Tq, Nout, Kx)) return BFPQ_E_ARG;
     if (B == 0 || Tq == 0 || Nout == 0) return 0;
-    const int64_t nb = (Kx + block_size - 1) / block_size;
-    if (Tq > BFPQ_KV_DEC_MAX_TOKENS || Kx < 1 || (family == BFPQ_KV_QK ? Kx % block_size != 0 : Nout % 16 != 0) || ldx < Kx || ldw % 64 != 0 ||
-        ldw < (Kx + 63) / 64 * 64 || ldwe < nb || w_bstride < Nout || ldo % 4 != 0 || ldo < Nout || w_bstride * ldw >= kLim ||
-        w_bstride * ldwe >= kLim || Tq * ldx >= kLim || Tq * ldo >= kLim)
-        return BFPQ_E_UNSUPPORTED;
-    if (!x || !wcodes || !wexp || !out || !exp_win || !aligned16(wcodes, out) || (reinterpret_cast<uintptr_t>(x) & (dtype == BFPQ_F32 ? 3u : 1u)))
-        return BFPQ_E_ARG;
+    if (!dec_shapes_ok(family, block_size, Tq, Tq, Kx, Nout, ldx, ldw, ldwe, w_bstride, ldo)) return BFPQ_E_UNSUPPORTED;
+    if (!dec_ptrs_ok(x, wcodes, wexp, out, exp_win, dtype)) return BFPQ_E_ARG;
     const float eps_dt = bfpq_dev::h_round((float)epsilon, dtype);
     hipStream_t s = (hipStream_t)stream;
     const unsigned gy = (unsigned)(B < 65535 ? B : 65535);
@@ -1154,21 +1148,14 @@ int bfpq_kv_bmm_dec_gqa(const void* x, const void* wcodes, const int8_t* wexp, v
                         int64_t ldo, int family, int dtype, int block_size, int x_mant_bits, int w_mant_bits, double epsilon,
                         const uint8_t* exp_win, void* ws, int64_t ws_bytes, int64_t chunks_per_split, void* stream)
 {
-    if (!dtype_ok(dtype) || !i8_block_ok(block_size) || !i8_mant_ok(x_mant_bits) || !i8_mant_ok(w_mant_bits) ||
-        (family != BFPQ_KV_QK && family != BFPQ_KV_PV) || B < 0 || Tq < 0 || Nout < 0 || Kx < 0 || heads < 1 || B % heads != 0 || group < 1 ||
+    if (!dec_values_ok(dtype, block_size, x_mant_bits, w_mant_bits, family, B, Tq, Nout, Kx) || heads < 1 || B % heads != 0 || group < 1 ||
         chunks_per_split < 0)
         return BFPQ_E_ARG;
     if (B == 0 || Tq == 0) return 0;
-    const int64_t nb = (Kx + block_size - 1) / block_size, R = Tq * group;
-    if (Tq > BFPQ_KV_DEC_MAX_TOKENS || group >= kLim || Kx < 1 || Nout < 1 ||
-        (family == BFPQ_KV_QK ? Kx % block_size != 0 : (Nout % 16 != 0 || Nout > 1024)) ||
-        ldx < Kx || ldw % 64 != 0 || ldw < (Kx + 63) / 64 * 64 || ldwe < nb || w_bstride < Nout || ldo % 4 != 0 || ldo < Nout ||
-        w_bstride * ldw >= kLim || w_bstride * ldwe >= kLim || R * ldx >= kLim || R * ldo >= kLim ||
-        B * row_tiles(Tq, group) >= kLim || chunks_per_split > kMaxCps)
+    if (Tq > BFPQ_KV_DEC_MAX_TOKENS || group >= kLim || !dec_shapes_ok(family, block_size, Tq, Tq * group, Kx, Nout, ldx, ldw, ldwe, w_bstride, ldo) ||
+        Nout < 1 || (family == BFPQ_KV_PV && Nout > 1024) || B * row_tiles(Tq, group) >= kLim || chunks_per_split > kMaxCps)
         return BFPQ_E_UNSUPPORTED;
-    if (!x || !wcodes || !wexp || !out || !lens || !exp_win || !aligned16(wcodes, out) || (reinterpret_cast<uintptr_t>(lens) & 3u) ||
-        (reinterpret_cast<uintptr_t>(x) & (dtype == BFPQ_F32 ? 3u : 1u)))
-        return BFPQ_E_ARG;
+    if (!dec_ptrs_ok(x, wcodes, wexp, out, exp_win, dtype) || !lens || (reinterpret_cast<uintptr_t>(lens) & 3u)) return BFPQ_E_ARG;
     const float eps_dt = bfpq_dev::h_round((float)epsilon, dtype);
     hipStream_t s = (hipStream_t)stream;
     if (family == BFPQ_KV_QK) {
@@ -1206,22 +1193,16 @@ int bfpq_kv_attend_gqa(const void* q, const void* k_codes, const int8_t* k_exps,
                        int w_mant_bits, double epsilon, const uint8_t* exp_win, void* score_ws, int64_t score_ws_bytes, void* sum_ws,
                        int64_t sum_ws_bytes, int64_t chunks_per_split, void* stream)
 {
-    if (!dtype_ok(dtype) || !i8_block_ok(block_size) || !i8_mant_ok(x_mant_bits) || !i8_mant_ok(w_mant_bits) || BH < 0 || Tq < 0 || heads < 1 ||
-        BH % heads != 0 || group < 1 || chunks_per_split < 0 || (causal != 0 && causal != 1) || !(scale - scale == 0.0) || !((float)scale - (float)scale == 0.f))
-        return BFPQ_E_ARG;
+    if (!att_values_ok(dtype, block_size, x_mant_bits, w_mant_bits, BH, heads, Tq, group, chunks_per_split, causal, scale)) return BFPQ_E_ARG;
     if (BH == 0 || Tq == 0) return 0;
     const int64_t pitch = (max_len + 3) / 4 * 4, R = Tq * group;
-    if (!bfpq_kv_ok(D, cap, block_size) || Tq > BFPQ_KV_DEC_MAX_TOKENS || group >= kLim || max_len < 1 || max_len > cap || ldd < D ||
-        ldd % 64 != 0 || ldo % 4 != 0 || ldo < D || (p_out && ldp < max_len) || cap * ldd >= kLim || R * ldo >= kLim ||
-        R * pitch >= kLim || (p_out && R * ldp >= kLim) || BH * row_tiles(Tq, group) > 65535 ||
-        chunks_per_split > kMaxCps)
+    if (!att_shapes_ok(block_size, group, D, max_len, cap, ldd, ldo, ldp, p_out, chunks_per_split) || Tq > BFPQ_KV_DEC_MAX_TOKENS ||
+        R * ldo >= kLim || R * pitch >= kLim || (p_out && R * ldp >= kLim) || BH * row_tiles(Tq, group) > 65535)
         return BFPQ_E_UNSUPPORTED;
     const int64_t need_s = bfpq_kv_attend_ws_bytes(BH * group, Tq, max_len), need_p = bfpq_kv_dec_ws_bytes(BH * group, Tq, D, max_len, block_size);
     if (need_s < 0 || need_p < 0 || score_ws_bytes < need_s || sum_ws_bytes < need_p) return BFPQ_E_UNSUPPORTED;
-    const uintptr_t emask = dtype == BFPQ_F32 ? 3u : 1u;
-    if (!q || !k_codes || !k_exps || !v_codes || !v_exps || !out || !lens || !exp_win || !score_ws || !sum_ws ||
-        !aligned16(k_codes, v_codes, out, score_ws, sum_ws) || (reinterpret_cast<uintptr_t>(lens) & 3u) ||
-        ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(p_out)) & emask))
+    if (!att_ptrs_ok(q, k_codes, k_exps, v_codes, v_exps, out, p_out, lens, exp_win, score_ws, dtype) || !sum_ws || !aligned16(sum_ws) ||
+        (reinterpret_cast<uintptr_t>(q) & (dtype == BFPQ_F32 ? 3u : 1u)))
         return BFPQ_E_ARG;
     const float eps_dt = bfpq_dev::h_round((float)epsilon, dtype);
     hipStream_t s = (hipStream_t)stream;
@@ -1260,22 +1241,17 @@ int bfpq_kv_attend_rows(const void* q, const void* k_codes, const int8_t* k_exps
                         int64_t sum_ws_bytes, int64_t chunks_per_split, int64_t row0, int64_t rows, void* stream)
 {
     (void)sum_ws; (void)sum_ws_bytes;                             // no block sums on this route
-    if (!dtype_ok(dtype) || !i8_block_ok(block_size) || !i8_mant_ok(x_mant_bits) || !i8_mant_ok(w_mant_bits) || BH < 0 || Tq < 0 || heads < 1 ||
-        BH % heads != 0 || group < 1 || chunks_per_split < 0 || (causal != 0 && causal != 1) || !(scale - scale == 0.0) ||
-        !((float)scale - (float)scale == 0.f) || row0 < 0 || rows < 0 || row0 > Tq || rows > Tq - row0)
+    if (!att_values_ok(dtype, block_size, x_mant_bits, w_mant_bits, BH, heads, Tq, group, chunks_per_split, causal, scale) || row0 < 0 || rows < 0 ||
+        row0 > Tq || rows > Tq - row0)
         return BFPQ_E_ARG;
     if (BH == 0 || Tq == 0 || rows == 0) return 0;
     const int64_t pitch = (max_len + 3) / 4 * 4, R = Tq * group, PR = rows * group, nwg = (PR + kRowsWg - 1) / kRowsWg;
-    if (!bfpq_kv_ok(D, cap, block_size) || D > 16 * kMaxDT || group >= kLim || Tq >= kLim || max_len < 1 || max_len > cap || ldd < D ||
-        ldd % 64 != 0 || ldo % 4 != 0 || ldo < D || (p_out && ldp < max_len) || cap * ldd >= kLim || R >= kLim || BH * nwg >= kLim ||
-        chunks_per_split > kMaxCps)
+    if (!att_shapes_ok(block_size, group, D, max_len, cap, ldd, ldo, ldp, p_out, chunks_per_split) || D > 16 * kMaxDT || Tq >= kLim || R >= kLim ||
+        BH * nwg >= kLim)
         return BFPQ_E_UNSUPPORTED;
     const int64_t need = bfpq_kv_attend_rows_ws_bytes(BH * group, rows, max_len);
     if (need < 0 || score_ws_bytes < need) return BFPQ_E_UNSUPPORTED;
-    const uintptr_t emask = dtype == BFPQ_F32 ? 3u : 1u;
-    if (!q || !k_codes || !k_exps || !v_codes || !v_exps || !out || !lens || !exp_win || !score_ws ||
-        !aligned16(q, k_codes, v_codes, out, score_ws) || (reinterpret_cast<uintptr_t>(lens) & 3u) || (reinterpret_cast<uintptr_t>(p_out) & emask))
-        return BFPQ_E_ARG;
+    if (!att_ptrs_ok(q, k_codes, k_exps, v_codes, v_exps, out, p_out, lens, exp_win, score_ws, dtype) || !aligned16(q)) return BFPQ_E_ARG;
     const float eps_dt = bfpq_dev::h_round((float)epsilon, dtype);
     hipStream_t s = (hipStream_t)stream;
     const int64_t nbd = D / block_size;

@@ -1422,20 +1422,28 @@ def _kv_int32(what, name, t, numel, dev):
                          f"(got {tuple(getattr(t, 'shape', ()))}, {getattr(t, 'dtype', None)}, {getattr(t, 'device', None)})")
 
 
-def kv_append(k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, pos, block_size, mant_bits, epsilon):
-    """k_new, v_new [BH, t, D] become tokens pos .. pos + t - 1 of the cache buffers (bfpq_kv_append: the layout is in include/bfpq.h);
-    one launch for any t >= 1"""
+def _kv_new(what, k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, block_size, heads=None):
+    """the checks kv_append and kv_append_dev share on the new rows and the cache buffers; returns (BH, t, D, cap, ldd)"""
     require_device_tensor(k_new, "k_new")
     require_device_tensor(v_new, "v_new")
     require_device_tensor(v_tail, "v_tail")
     if k_new.dim() != 3 or v_new.shape != k_new.shape or v_new.dtype != k_new.dtype or v_tail.dtype != k_new.dtype:
-        raise ValueError(f"kv_append takes k_new and v_new [BH, t, D] of one dtype, the cache's (got {tuple(k_new.shape)} {k_new.dtype}, "
+        raise ValueError(f"{what} takes k_new and v_new [BH, t, D] of one dtype, the cache's (got {tuple(k_new.shape)} {k_new.dtype}, "
                          f"{tuple(v_new.shape)} {v_new.dtype}, v_tail {v_tail.dtype})")
     BH, t, D = k_new.shape
-    dev = k_new.device
-    cap, ldd = _kv_buffers("kv_append", BH, D, block_size, k_codes, k_exps, v_codes, v_exps, v_tail, dev)
+    if heads is not None and (heads < 1 or BH % heads):
+        raise ValueError(f"{what}: {BH} heads in all are no multiple of heads = {heads}")
+    cap, ldd = _kv_buffers(what, BH, D, block_size, k_codes, k_exps, v_codes, v_exps, v_tail, k_new.device)
     if not k_new.is_contiguous() or not v_new.is_contiguous():
-        raise ValueError("kv_append takes contiguous k_new / v_new")
+        raise ValueError(f"{what} takes contiguous k_new / v_new")
+    return BH, t, D, cap, ldd
+
+
+def kv_append(k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, pos, block_size, mant_bits, epsilon):
+    """k_new, v_new [BH, t, D] become tokens pos .. pos + t - 1 of the cache buffers (bfpq_kv_append: the layout is in include/bfpq.h);
+    one launch for any t >= 1"""
+    BH, t, D, cap, ldd = _kv_new("kv_append", k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, block_size)
+    dev = k_new.device
     with torch.cuda.device(dev):
         check(load_library().bfpq_kv_append(_ptr(k_new), _ptr(v_new), _ptr(k_codes), _ptr(k_exps), _ptr(v_codes), _ptr(v_exps), _ptr(v_tail), BH, D,
                                             int(pos), t, cap, ldd, DTYPE_CODE[k_new.dtype], int(block_size), int(mant_bits), float(epsilon),
@@ -1447,21 +1455,9 @@ def kv_append_dev(k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, length
     """kv_append at the positions lengths [B] (int32, on the device) holds, sequence b = head // heads taking the first counts[b] of the t
     rows (counts None: all), then lengths advanced by a second launch (bfpq_kv_append_dev, bfpq_kv_lens_advance).  A sequence that would
     pass `limit` tokens is left untouched and overflow[0] set to 1.  Nothing is read back."""
-    require_device_tensor(k_new, "k_new")
-    require_device_tensor(v_new, "v_new")
-    require_device_tensor(v_tail, "v_tail")
-    if k_new.dim() != 3 or v_new.shape != k_new.shape or v_new.dtype != k_new.dtype or v_tail.dtype != k_new.dtype:
-        raise ValueError(f"kv_append_dev takes k_new and v_new [BH, t, D] of one dtype, the cache's (got {tuple(k_new.shape)} {k_new.dtype}, "
-                         f"{tuple(v_new.shape)} {v_new.dtype}, v_tail {v_tail.dtype})")
-    BH, t, D = k_new.shape
-    dev = k_new.device
     heads = int(heads)
-    if heads < 1 or BH % heads:
-        raise ValueError(f"kv_append_dev: {BH} heads in all are no multiple of heads = {heads}")
-    cap, ldd = _kv_buffers("kv_append_dev", BH, D, block_size, k_codes, k_exps, v_codes, v_exps, v_tail, dev)
-    if not k_new.is_contiguous() or not v_new.is_contiguous():
-        raise ValueError("kv_append_dev takes contiguous k_new / v_new")
-    B = BH // heads
+    BH, t, D, cap, ldd = _kv_new("kv_append_dev", k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, block_size, heads)
+    dev, B = k_new.device, BH // heads
     _kv_int32("kv_append_dev", "lengths", lengths, B, dev)
     _kv_int32("kv_append_dev", "overflow", overflow, 1, dev)
     if counts is not None:
@@ -1491,6 +1487,56 @@ def _kv_group(what, rows, group):
     return rows // group
 
 
+def _kv_rows(what, x, form, group=1, heads=1):
+    """the query-side tensor x [BH, group * Tq, last] of an entry (`form`: how its message spells it); returns (x contiguous, BH, R, Tq,
+    last, heads)"""
+    require_device_tensor(x, form.split()[0])
+    if x.dim() != 3:
+        raise ValueError(f"{what} takes {form} (got {tuple(x.shape)})")
+    BH, R, last = x.shape
+    Tq = _kv_group(what, R, group)
+    heads = int(heads)
+    if heads < 1 or BH % heads:
+        raise ValueError(f"{what}: {BH} heads in all are no multiple of heads = {heads}")
+    return x.contiguous(), BH, R, Tq, last, heads
+
+
+def _kv_operand(what, BH, w_bstride, wc, we, dev):
+    """one cached operand of kv_bmm_dec / kv_bmm_dec_dev: contiguous codes and exponents of BH x w_bstride rows"""
+    for name, buf in (("codes", wc), ("exponents", we)):
+        if buf.device != dev or buf.dtype != torch.int8 or not buf.is_contiguous() or buf.numel() < BH * int(w_bstride) * buf.shape[-1]:
+            raise ValueError(f"{what}: the cached {name} must be contiguous int8 on {dev} with {BH} x {w_bstride} rows "
+                             f"(got {tuple(buf.shape)}, {buf.dtype}, {buf.device})")
+
+
+def _kv_cached(what, BH, D, block_size, k_codes, k_exps, v_codes, v_exps, dev):
+    """the four code and exponent buffers of BH cached heads as the attend entries take them; returns (cap, ldd)"""
+    if k_codes.dim() < 2 or v_codes.dim() < 2:
+        raise ValueError(f"{what} takes k_codes [..., cap, ldd] and v_codes [..., D, cap]")
+    cap, ldd = k_codes.shape[-2], k_codes.shape[-1]
+    nbd, nbc = D // int(block_size), cap // int(block_size)
+    for name, buf, numel in (("k_codes", k_codes, BH * cap * ldd), ("k_exps", k_exps, BH * cap * nbd), ("v_codes", v_codes, BH * D * cap),
+                             ("v_exps", v_exps, BH * D * nbc)):
+        if buf.device != dev or buf.dtype != torch.int8 or not buf.is_contiguous() or buf.numel() != numel:
+            raise ValueError(f"{what}: {name} must be contiguous int8 on {dev} with {numel} elements "
+                             f"(got {tuple(buf.shape)}, {buf.dtype}, {buf.device})")
+    return cap, ldd
+
+
+def _kv_ws(what, name, ws, need, dev):
+    """a workspace: a contiguous uint8 tensor of at least `need` bytes; returns its bytes"""
+    if not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or ws.device != dev or not ws.is_contiguous() or ws.numel() < need:
+        raise ValueError(f"{what}: {name} must be a contiguous uint8 tensor of at least {need} bytes on {dev}")
+    return ws.numel()
+
+
+def _kv_scale(what, scale):
+    scale = float(scale)
+    if not math.isfinite(scale) or abs(scale) > torch.finfo(torch.float32).max:
+        raise ValueError(f"{what}: scale must be finite in fp32 (got {scale})")
+    return scale
+
+
 def kv_bmm_dec_dev(x, wc, we, family, bound, w_bstride, lengths, heads, block_size, mant_bits, epsilon, ws=None, chunks_per_split=0, group=1):
     """kv_bmm_dec with head b's cached length read from lengths[b // heads] on the device (bfpq_kv_bmm_dec_gqa).  KV_QK: x [BH, Tq, D],
     bound = max_len; returns [BH, Tq, max_len], -inf from the length on.  KV_PV: x [BH, Tq, L], bound = D; returns [BH, Tq, D]; ws: a
@@ -1498,29 +1544,14 @@ def kv_bmm_dec_dev(x, wc, we, family, bound, w_bstride, lengths, heads, block_si
     contraction, 0 = the library's choice (the result does not depend on it).  group > 1 (grouped-query attention): the BH cached heads
     serve `group` query heads each, x and the result hold group * Tq rows per cached head -- query head r // Tq of the group, token
     r % Tq -- and the workspace is that of BH * group heads."""
-    require_device_tensor(x, "x")
-    if x.dim() != 3:
-        raise ValueError(f"kv_bmm_dec_dev takes x [BH, Tq, Kx] (got {tuple(x.shape)})")
-    BH, R, Kx = x.shape
-    Tq = _kv_group("kv_bmm_dec_dev", R, group)
-    x = x.contiguous()
+    x, BH, R, Tq, Kx, heads = _kv_rows("kv_bmm_dec_dev", x, "x [BH, Tq, Kx]", group, heads)
     dev = x.device
-    heads = int(heads)
-    if heads < 1 or BH % heads:
-        raise ValueError(f"kv_bmm_dec_dev: {BH} heads in all are no multiple of heads = {heads}")
-    for name, buf in (("codes", wc), ("exponents", we)):
-        if buf.device != dev or buf.dtype != torch.int8 or not buf.is_contiguous() or buf.numel() < BH * int(w_bstride) * buf.shape[-1]:
-            raise ValueError(f"kv_bmm_dec_dev: the cached {name} must be contiguous int8 on {dev} with {BH} x {w_bstride} rows "
-                             f"(got {tuple(buf.shape)}, {buf.dtype}, {buf.device})")
+    _kv_operand("kv_bmm_dec_dev", BH, w_bstride, wc, we, dev)
     _kv_int32("kv_bmm_dec_dev", "lengths", lengths, BH // heads, dev)
     Nout = int(bound)
     ws_bytes = 0
     if family == KV_PV:
-        need = kv_dec_ws_bytes(BH * group, Tq, Nout, Kx, block_size)
-        if (not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or ws.device != dev or not ws.is_contiguous()
-                or ws.numel() < need):
-            raise ValueError(f"kv_bmm_dec_dev: ws must be a contiguous uint8 tensor of at least {need} bytes on {dev}")
-        ws_bytes = ws.numel()
+        ws_bytes = _kv_ws("kv_bmm_dec_dev", "ws", ws, kv_dec_ws_bytes(BH * group, Tq, Nout, Kx, block_size), dev)
     ldo = (Nout + 3) // 4 * 4
     with torch.cuda.device(dev):
         out = torch.empty((BH, R, ldo), dtype=x.dtype, device=dev)
@@ -1546,41 +1577,21 @@ def kv_attend(q, k_codes, k_exps, v_codes, v_exps, lengths, heads, max_len, scal
     (context [BH, Tq, D], p [BH, Tq, max_len] or None).  score_ws / sum_ws: contiguous uint8 tensors of at least
     kv_attend_ws_bytes(BH, Tq, max_len) / kv_dec_ws_bytes(BH, Tq, D, max_len, block_size) bytes.  Nothing is read back.  group > 1: rows
     and workspaces as kv_bmm_dec_dev takes them (q, the context and p hold group * Tq rows per cached head; causal goes by the token)."""
-    require_device_tensor(q, "q")
-    if q.dim() != 3:
-        raise ValueError(f"kv_attend takes q [BH, Tq, D] (got {tuple(q.shape)})")
-    BH, R, D = q.shape
-    Tq = _kv_group("kv_attend", R, group)
-    q = q.contiguous()
+    q, BH, R, Tq, D, heads = _kv_rows("kv_attend", q, "q [BH, Tq, D]", group, heads)
     dev = q.device
-    heads = int(heads)
-    if heads < 1 or BH % heads:
-        raise ValueError(f"kv_attend: {BH} heads in all are no multiple of heads = {heads}")
-    if k_codes.dim() < 2 or v_codes.dim() < 2:
-        raise ValueError("kv_attend takes k_codes [..., cap, ldd] and v_codes [..., D, cap]")
-    cap, ldd = k_codes.shape[-2], k_codes.shape[-1]
-    nbd, nbc = D // int(block_size), cap // int(block_size)
-    for name, buf, numel in (("k_codes", k_codes, BH * cap * ldd), ("k_exps", k_exps, BH * cap * nbd), ("v_codes", v_codes, BH * D * cap),
-                             ("v_exps", v_exps, BH * D * nbc)):
-        if buf.device != dev or buf.dtype != torch.int8 or not buf.is_contiguous() or buf.numel() != numel:
-            raise ValueError(f"kv_attend: {name} must be contiguous int8 on {dev} with {numel} elements "
-                             f"(got {tuple(buf.shape)}, {buf.dtype}, {buf.device})")
+    cap, ldd = _kv_cached("kv_attend", BH, D, block_size, k_codes, k_exps, v_codes, v_exps, dev)
     _kv_int32("kv_attend", "lengths", lengths, BH // heads, dev)
-    max_len, scale = int(max_len), float(scale)
-    if not math.isfinite(scale) or abs(scale) > torch.finfo(torch.float32).max:
-        raise ValueError(f"kv_attend: scale must be finite in fp32 (got {scale})")
-    need = (kv_attend_ws_bytes(BH * group, Tq, max_len), kv_dec_ws_bytes(BH * group, Tq, D, max_len, block_size))
-    for name, ws, n in (("score_ws", score_ws, need[0]), ("sum_ws", sum_ws, need[1])):
-        if not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or ws.device != dev or not ws.is_contiguous() or ws.numel() < n:
-            raise ValueError(f"kv_attend: {name} must be a contiguous uint8 tensor of at least {n} bytes on {dev}")
+    max_len, scale = int(max_len), _kv_scale("kv_attend", scale)
+    score_bytes = _kv_ws("kv_attend", "score_ws", score_ws, kv_attend_ws_bytes(BH * group, Tq, max_len), dev)
+    sum_bytes = _kv_ws("kv_attend", "sum_ws", sum_ws, kv_dec_ws_bytes(BH * group, Tq, D, max_len, block_size), dev)
     with torch.cuda.device(dev):
         out = torch.empty((BH, R, D), dtype=q.dtype, device=dev)
         p = torch.empty((BH, R, max_len), dtype=q.dtype, device=dev) if return_probs else None
         check(load_library().bfpq_kv_attend_gqa(_ptr(q), _ptr(k_codes), _ptr(k_exps), _ptr(v_codes), _ptr(v_exps), _ptr(out), _ptr(p),
                                                 _ptr(lengths), BH, heads, Tq, group, D, max_len, cap, ldd, D, max_len, scale, int(bool(causal)),
                                                 DTYPE_CODE[q.dtype], int(block_size), int(mant_bits), int(mant_bits), float(epsilon),
-                                                _ptr(exp_window_dev(q.dtype, dev)), _ptr(score_ws), score_ws.numel(), _ptr(sum_ws),
-                                                sum_ws.numel(), int(chunks_per_split), _stream(q)), "bfpq_kv_attend_gqa")
+                                                _ptr(exp_window_dev(q.dtype, dev)), _ptr(score_ws), score_bytes, _ptr(sum_ws), sum_bytes,
+                                                int(chunks_per_split), _stream(q)), "bfpq_kv_attend_gqa")
     return out, p
 
 
@@ -1601,36 +1612,15 @@ def kv_attend_rows(q, k_codes, k_exps, v_codes, v_exps, lengths, heads, max_len,
     query head, two launches per panel, the panel's fp32 score rows in score_ws (a contiguous uint8 tensor of at least
     kv_attend_rows_ws_bytes(BH * group, min(panel_rows, Tq), max_len) bytes).  Returns (context [BH, group * Tq, D], p
     [BH, group * Tq, max_len] or None); row for row kv_attend's bits.  Nothing is read back."""
-    require_device_tensor(q, "q")
-    if q.dim() != 3:
-        raise ValueError(f"kv_attend_rows takes q [BH, Tq, D] (got {tuple(q.shape)})")
-    BH, R, D = q.shape
-    Tq = _kv_group("kv_attend_rows", R, group)
+    q, BH, R, Tq, D, heads = _kv_rows("kv_attend_rows", q, "q [BH, Tq, D]", group, heads)
     panel_rows = int(panel_rows)
     if panel_rows < 1:
         raise ValueError(f"kv_attend_rows: panel_rows must be >= 1 (got {panel_rows})")
-    q = q.contiguous()
     dev = q.device
-    heads = int(heads)
-    if heads < 1 or BH % heads:
-        raise ValueError(f"kv_attend_rows: {BH} heads in all are no multiple of heads = {heads}")
-    if k_codes.dim() < 2 or v_codes.dim() < 2:
-        raise ValueError("kv_attend_rows takes k_codes [..., cap, ldd] and v_codes [..., D, cap]")
-    cap, ldd = k_codes.shape[-2], k_codes.shape[-1]
-    nbd, nbc = D // int(block_size), cap // int(block_size)
-    for name, buf, numel in (("k_codes", k_codes, BH * cap * ldd), ("k_exps", k_exps, BH * cap * nbd), ("v_codes", v_codes, BH * D * cap),
-                             ("v_exps", v_exps, BH * D * nbc)):
-        if buf.device != dev or buf.dtype != torch.int8 or not buf.is_contiguous() or buf.numel() != numel:
-            raise ValueError(f"kv_attend_rows: {name} must be contiguous int8 on {dev} with {numel} elements "
-                             f"(got {tuple(buf.shape)}, {buf.dtype}, {buf.device})")
+    cap, ldd = _kv_cached("kv_attend_rows", BH, D, block_size, k_codes, k_exps, v_codes, v_exps, dev)
     _kv_int32("kv_attend_rows", "lengths", lengths, BH // heads, dev)
-    max_len, scale = int(max_len), float(scale)
-    if not math.isfinite(scale) or abs(scale) > torch.finfo(torch.float32).max:
-        raise ValueError(f"kv_attend_rows: scale must be finite in fp32 (got {scale})")
-    need = kv_attend_rows_ws_bytes(BH * group, min(panel_rows, Tq), max_len)
-    if (not isinstance(score_ws, torch.Tensor) or score_ws.dtype != torch.uint8 or score_ws.device != dev or not score_ws.is_contiguous()
-            or score_ws.numel() < need):
-        raise ValueError(f"kv_attend_rows: score_ws must be a contiguous uint8 tensor of at least {need} bytes on {dev}")
+    max_len, scale = int(max_len), _kv_scale("kv_attend_rows", scale)
+    score_bytes = _kv_ws("kv_attend_rows", "score_ws", score_ws, kv_attend_rows_ws_bytes(BH * group, min(panel_rows, Tq), max_len), dev)
     with torch.cuda.device(dev):
         out = torch.empty((BH, R, D), dtype=q.dtype, device=dev)
         p = torch.empty((BH, R, max_len), dtype=q.dtype, device=dev) if return_probs else None
@@ -1638,7 +1628,7 @@ def kv_attend_rows(q, k_codes, k_exps, v_codes, v_exps, lengths, heads, max_len,
         for row0 in range(0, Tq, panel_rows):
             check(L.bfpq_kv_attend_rows(_ptr(q), _ptr(k_codes), _ptr(k_exps), _ptr(v_codes), _ptr(v_exps), _ptr(out), _ptr(p), _ptr(lengths), BH,
                                         heads, Tq, group, D, max_len, cap, ldd, D, max_len, scale, int(bool(causal)), DTYPE_CODE[q.dtype],
-                                        int(block_size), int(mant_bits), int(mant_bits), float(epsilon), win, _ptr(score_ws), score_ws.numel(),
+                                        int(block_size), int(mant_bits), int(mant_bits), float(epsilon), win, _ptr(score_ws), score_bytes,
                                         None, 0, 0, row0, min(panel_rows, Tq - row0), stream), "bfpq_kv_attend_rows")
     return out, p
 
@@ -1647,16 +1637,9 @@ def kv_bmm_dec(x, wc, we, family, Nout, w_bstride, block_size, mant_bits, epsilo
     """x [BH, Tq <= 16, Kx] (dense) against one cached operand, x quantized inside the kernel
     (bfpq_kv_bmm_dec).  wc [..., ldw] / we [..., ldwe]: contiguous codes / exponents, w_bstride rows per head.  Returns [BH, Tq, Nout]:
     a view of a buffer whose row pitch is Nout rounded up to 4."""
-    require_device_tensor(x, "x")
-    if x.dim() != 3:
-        raise ValueError(f"kv_bmm_dec takes x [BH, Tq, Kx] (got {tuple(x.shape)})")
-    BH, Tq, Kx = x.shape
-    x = x.contiguous()
+    x, BH, _, Tq, Kx, _ = _kv_rows("kv_bmm_dec", x, "x [BH, Tq, Kx]")
     dev = x.device
-    for name, buf in (("codes", wc), ("exponents", we)):
-        if buf.device != dev or buf.dtype != torch.int8 or not buf.is_contiguous() or buf.numel() < BH * int(w_bstride) * buf.shape[-1]:
-            raise ValueError(f"kv_bmm_dec: the cached {name} must be contiguous int8 on {dev} with {BH} x {w_bstride} rows "
-                             f"(got {tuple(buf.shape)}, {buf.dtype}, {buf.device})")
+    _kv_operand("kv_bmm_dec", BH, w_bstride, wc, we, dev)
     ldo = (int(Nout) + 3) // 4 * 4
     with torch.cuda.device(dev):
         out = torch.empty((BH, Tq, ldo), dtype=x.dtype, device=dev)
