@@ -14,6 +14,11 @@ scores, softmax, context; modeling_gpt2.py:345-348 with :207, 243) on one MI355X
          on an empty HBFPKVCache(prompt_rows=P), against loop16: what the cache can do without prompt_rows on the same tokens, ceil(T / 16)
          non-causal 16-row attend calls (a cost yardstick only), and matmul: the prompt route without it, mm(q, k^T), torch's softmax
          with a causal mask and mm(p, v) on F_matmul_bfp(matrix_unit='int8'), plus the append the cache still needs (all block 64),
+  window (--case window_*: a first visible key per row) the attend leg (decode) or the prompt leg (window_prompt_*) on
+         HBFPKVCache(window=W), against full: the same cache and length without a window, i.e. the path before window existed, and
+         masked: what a user did before, scores() + torch's mask and softmax + context() (the prompt case: the matmul leg with a windowed
+         mask); --case starts_ragged8: the attend leg on the ragged batch with a quarter of each sequence as left padding
+         (HBFPKVCache(starts=True)) against full (all block 64),
 and, for the cache alone, the append of a prefill chunk of S tokens.  Method of bench_matmul.py: hipGraph replay, the median of the
 replays, the legs alternating round by round in one process.  (A captured append writes at the captured position: every replay redoes the
 same step, which is what is timed.)  On a tree without the cache the cache columns are null and "cache" says "absent".
@@ -44,10 +49,10 @@ RAGGED = {"ragged8": (8, 12, (128, 695, 1262, 1829, 2396, 2963, 3530, 4096), 64)
 GQA = {"gqa_h32_kv8_b1_s2048": (1, 32, 8, 2048, 128), "gqa_h32_kv8_b8_s2048": (8, 32, 8, 2048, 128)}
 
 
-def device_leg(i8, batch, heads, D, lens, k, v, q, dt, dev, iters, rounds, cps, attend=False, **mode):
+def device_leg(i8, batch, heads, D, lens, k, v, q, dt, dev, iters, rounds, cps, attend=False, hide=None, **mode):
     """(cache, step) of the device leg: sequence b prefilled to lens[b] - 1 tokens, room for every token the run appends.  attend: the
     same cache and step with cache.attend in place of scores, torch's scale and softmax, and context.  mode: kv_heads (k and v then hold
-    that many heads)"""
+    that many heads), window, starts.  hide (the composition only): cache -> the bool mask [B, 1, 1, capacity] of the keys torch hides"""
     import torch
     room = iters * (rounds + 1) + 2                                      # replay_times: two warm-up calls, the capture, rounds + 1 replays
     cache = i8.kv_cache(batch, heads, D, max(lens) + room, dtype=dt, device=dev, device_lengths=True, chunks_per_split=cps, max_query_rows=1,
@@ -58,7 +63,10 @@ def device_leg(i8, batch, heads, D, lens, k, v, q, dt, dev, iters, rounds, cps, 
 
     def step():
         cache.append(k_new, v_new)
-        p = torch.softmax(cache.scores(q).float() * scale, dim=-1).to(dt)
+        s = cache.scores(q).float() * scale
+        if hide is not None:
+            s = s.masked_fill(hide(cache), float('-inf'))
+        p = torch.softmax(s, dim=-1).to(dt)
         return cache.context(p)
 
     def attend_step():
@@ -215,6 +223,124 @@ def run_prompt(name, iters, rounds, out, prompt_rows=None, only=None):
     json.dump((json.load(open(out)) if os.path.exists(out) else []) + rows, open(out, "w"), indent=1)
 
 
+# name: (batch, heads, kv_heads, S, head_dim, window): sliding-window decode (sliding_window of Mistral / Mixtral / Qwen2 / Starcoder2)
+WINDOW = {"window_gpt2s_b1_s4096_w1024": (1, 12, 12, 4096, 64, 1024), "window_h32_kv8_b1_s4096_w1024": (1, 32, 8, 4096, 128, 1024)}
+# name: (batch, heads, kv_heads, T, head_dim, prompt_rows, window)
+WINDOW_PROMPT = {"window_prompt_h32_d128_b1_t2048_w512": (1, 32, 32, 2048, 128, 512, 512)}
+STARTS = {"starts_ragged8": "ragged8"}                               # a quarter of each sequence of the ragged batch is left padding
+
+
+def _append_rows(out, rows):
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    json.dump((json.load(open(out)) if os.path.exists(out) else []) + rows, open(out, "w"), indent=1)
+
+
+def run_window(name, iters, rounds, out, cps, only=None):
+    """the legs window, full and masked of a sliding-window decode case, or starts and full of the left-padded ragged batch; bf16 and
+    fp32 at block 64 (only: one leg alone, bf16: what a kernel trace is taken from)"""
+    import torch
+    import quantization_sparsity_interplay_amd as bfpq
+    from quantization_sparsity_interplay_amd.bfp import bfp_ops
+    dev = "cuda:0"
+    if name in STARTS:
+        batch, heads, lens, D = RAGGED[STARTS[name]]
+        kvh, W, pads, new = heads, None, [n // 4 for n in lens], "starts"
+    else:
+        batch, heads, kvh, S, D, W = WINDOW[name]
+        lens, pads, new = [S] * batch, None, "window"
+    c = CONFIGS["hbfp8_b64"]
+    rows = []
+    for dname in DTYPES if only is None else ("bf16",):
+        dt = dict(bf16=torch.bfloat16, fp32=torch.float32)[dname]
+        gen = torch.Generator().manual_seed(1)
+        k, v = (torch.randn(batch, kvh, max(lens), D, generator=gen).to(dt).to(dev) for _ in range(2))
+        q = torch.randn(batch, heads, 1, D, generator=gen).to(dt).to(dev)
+        i8 = bfp_ops.F_matmul_bfp(matrix_unit='int8', **bfpq.BFPConfig.hbfp(c['mant_bits'] + 1, c['block_size']).to_kwargs())
+        mode = dict(kv_heads=kvh)
+        leg = lambda **kw: device_leg(i8, batch, heads, D, lens, k, v, q, dt, dev, iters, rounds, cps, **mode, **kw)
+
+        def hide(cache):                                             # the keys below the window of the row that was just appended
+            n = torch.arange(cache.capacity, device=dev).view(1, 1, 1, -1)
+            return n < (cache.lengths - W).view(-1, 1, 1, 1)
+
+        with torch.no_grad():
+            legs = {}
+            if only in (None, new):
+                legs[new] = leg(attend=True, window=W) if pads is None else leg(attend=True, starts=True)
+                if pads is not None:
+                    legs[new][0].starts.copy_(torch.tensor(pads, dtype=torch.int32, device=dev))
+            if only in (None, "full"):
+                legs["full"] = leg(attend=True)
+            if pads is None and only in (None, "masked"):
+                legs["masked"] = leg(hide=hide)
+            med, spread = replay_times([step for _, step in legs.values()], iters, rounds)
+        row = dict(shape=name, batch=batch, heads=heads, kv_heads=kvh, lengths=list(lens), head_dim=D, window=W, starts=pads, dtype=dname,
+                   config="hbfp8_b64", iters=iters, rounds=rounds, chunks_per_split=cps)
+        ends = set()
+        for (lname, (cache, _)), m, sp in zip(legs.items(), med, spread):
+            assert cache.overflow.item() == 0
+            ends.add(tuple(cache.lengths.tolist()))
+            row.update({f"{lname}_us": m, f"{lname}_min_max_us": sp})
+        assert len(ends) == 1
+        row["lengths_at_end"] = list(ends.pop())
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    _append_rows(out, rows)
+
+
+def run_window_prompt(name, iters, rounds, out, only=None):
+    """the legs window, full and masked of a sliding-window prompt, bf16 and fp32 at block 64: one step = append(prompt) +
+    attend(q, causal=True) on an empty cache, as run_prompt; masked is its matmul leg with the windowed causal mask"""
+    import torch
+    import quantization_sparsity_interplay_amd as bfpq
+    from quantization_sparsity_interplay_amd.bfp import bfp_ops
+    dev = "cuda:0"
+    batch, heads, kvh, T, D, P, W = WINDOW_PROMPT[name]
+    g = heads // kvh
+    c = CONFIGS["hbfp8_b64"]
+    scale = 1.0 / D ** 0.5
+    rows = []
+    for dname in DTYPES if only is None else ("bf16",):
+        dt = dict(bf16=torch.bfloat16, fp32=torch.float32)[dname]
+        gen = torch.Generator().manual_seed(1)
+        k, v = (torch.randn(batch, kvh, T, D, generator=gen).to(dt).to(dev) for _ in range(2))
+        q = torch.randn(batch, heads, T, D, generator=gen).to(dt).to(dev)
+        i8 = bfp_ops.F_matmul_bfp(matrix_unit='int8', **bfpq.BFPConfig.hbfp(c['mant_bits'] + 1, c['block_size']).to_kwargs())
+        bfp_ops.MATMUL_I8_MIN = {key: 1 for key in bfp_ops.MATMUL_I8_MIN}              # time the route itself: every default floor off
+        mk = lambda **mode: i8.kv_cache(batch, heads, D, T, dtype=dt, device=dev, device_lengths=True, kv_heads=kvh, **mode)
+        caches = dict(window=mk(prompt_rows=P, window=W), full=mk(prompt_rows=P), masked=mk())
+        ones = torch.ones(T, T, dtype=torch.bool, device=dev)
+        mask = ~(ones.tril() & ones.triu(1 - W))                     # row i sees the keys i - W + 1 .. i
+
+        def attend_step(cache):
+            cache.lengths.zero_()
+            cache.append(k, v)
+            return cache.attend(q, scale, causal=True)
+
+        def masked_step():
+            caches['masked'].lengths.zero_()
+            caches['masked'].append(k, v)
+            kr, vr = (x.repeat_interleave(g, dim=1) for x in (k, v)) if g > 1 else (k, v)
+            s = i8(q, kr.transpose(-1, -2)).float() * scale
+            return i8(torch.softmax(s.masked_fill(mask, float('-inf')), dim=-1).to(dt), vr)
+
+        steps = dict(window=lambda: attend_step(caches['window']), full=lambda: attend_step(caches['full']), masked=masked_step)
+        legs = [leg for leg in steps if only in (None, leg)]
+        with torch.no_grad():
+            for leg in legs:
+                if leg != 'masked':
+                    caches[leg].prepare_attend()
+            med, spread = replay_times([steps[leg] for leg in legs], iters, rounds)
+        row = dict(shape=name, batch=batch, heads=heads, kv_heads=kvh, T=T, head_dim=D, window=W, dtype=dname, config="hbfp8_b64", iters=iters,
+                   rounds=rounds, prompt_rows=P)
+        for leg, m, sp in zip(legs, med, spread):
+            assert caches[leg].overflow.item() == 0 and caches[leg].lengths.tolist() == [T] * batch
+            row.update({f"{leg}_us": m, f"{leg}_min_max_us": sp})
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    _append_rows(out, rows)
+
+
 def run_attend_only(shape, iters, rounds, out, cps):
     """the attend leg alone, bf16 at block 64: what a kernel trace of one step is taken from (--attend-only)"""
     import torch
@@ -331,7 +457,8 @@ def merge_parent(out, parent_json):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--case", choices=sorted(SHAPES) + sorted(RAGGED) + sorted(GQA) + sorted(PROMPT))
+    ap.add_argument("--case", choices=sorted(SHAPES) + sorted(RAGGED) + sorted(GQA) + sorted(PROMPT) + sorted(WINDOW) + sorted(WINDOW_PROMPT) + sorted(STARTS))
+    ap.add_argument("--window-leg", choices=("window", "starts", "full", "masked"), help="with a window_* / starts_* case: that leg alone, bf16 (a kernel trace)")
     ap.add_argument("--prompt-rows", type=int, help="with a prompt case: the panel size (default: the case's own)")
     ap.add_argument("--prompt-leg", choices=("prompt", "loop16", "matmul"), help="with a prompt case: that leg alone, bf16 (a kernel trace)")
     ap.add_argument("--kv-heads", type=int, help="with a gqa case: its kv heads (a divisor of the case's heads; default: the case's own)")
@@ -346,6 +473,10 @@ def main():
     ap.add_argument("--attend-only", action="store_true", help="with --case: the attend leg alone, bf16 at block 64 (a kernel trace of one attend step)")
     ap.add_argument("--merge-only", action="store_true", help="run nothing: add --parent-json to an existing --out file")
     a = ap.parse_args()
+    if a.window_leg:
+        legs = ("starts", "full") if a.case in STARTS else ("window", "full", "masked") if a.case in WINDOW or a.case in WINDOW_PROMPT else ()
+        if a.window_leg not in legs:
+            ap.error(f"--window-leg {a.window_leg} does not go with --case {a.case}: its legs are {', '.join(legs) or 'none'}")
     if (a.kv_heads is not None or a.leg) and a.case not in GQA:
         ap.error("--kv-heads and --leg go with a gqa case (--case gqa_*)")
     if a.kv_heads is not None and (a.kv_heads < 1 or GQA[a.case][1] % a.kv_heads):
@@ -353,6 +484,10 @@ def main():
     out = os.path.abspath(a.out)
     if a.merge_only:
         return merge_parent(out, a.parent_json)
+    if a.case in WINDOW or a.case in STARTS:
+        return run_window(a.case, a.iters, a.rounds, out, a.chunks_per_split, a.window_leg)
+    if a.case in WINDOW_PROMPT:
+        return run_window_prompt(a.case, min(a.iters, 4), a.rounds, out, a.window_leg)
     if a.case in PROMPT:
         return run_prompt(a.case, min(a.iters, 4), a.rounds, out, a.prompt_rows, a.prompt_leg)
     if a.case in GQA:
@@ -366,7 +501,7 @@ def main():
     if os.path.exists(out):
         os.remove(out)
     steps = [f"timeout -k 10 {a.timeout} {sys.executable} {os.path.abspath(__file__)} --case {s} --iters {a.iters} --rounds {a.rounds} --chunks-per-split {a.chunks_per_split} --out {out}"
-             for s in list(SHAPES) + list(RAGGED) + list(GQA) + list(PROMPT)]
+             for s in list(SHAPES) + list(RAGGED) + list(GQA) + list(PROMPT) + list(WINDOW) + list(WINDOW_PROMPT) + list(STARTS)]
     rc = subprocess.call(" && ".join(steps), shell=True)
     if rc == 0 and a.parent_json:
         merge_parent(out, a.parent_json)

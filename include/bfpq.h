@@ -565,6 +565,29 @@ int bfpq_kv_attend_rows(const void* q_dev, const void* k_codes_dev, const int8_t
                         int64_t max_len, int64_t cap, int64_t ldd, int64_t ldo, int64_t ldp, double scale, int causal, int dtype, int block_size,
                         int x_mant_bits, int w_mant_bits, double epsilon, const uint8_t* exp_win_dev, void* score_ws_dev, int64_t score_ws_bytes,
                         void* sum_ws_dev, int64_t sum_ws_bytes, int64_t chunks_per_split, int64_t row0, int64_t rows, void* stream);
+/* A first visible key per query row: left-padded batches and sliding-window attention on the device-length cache (the reference's
+ * transformers tree: batched generate() pads on the left and the additive attention_mask hides the pad tokens, modeling_gpt2.py:228-230,
+ * modeling_llama.py:402-404; the sliding_window of modeling_attn_mask_utils.py, row i seeing the keys i - W + 1 .. i).  The two entries
+ * are bfpq_kv_attend_gqa and bfpq_kv_attend_rows with two more arguments in front of the stream: starts_dev, int32 [sequences] on the
+ * device or NULL, read at launch and never on the host (a negative start counts as 0), and window (0: none).  With len = lens,
+ * v = causal ? len - Tq + t + 1 : len and hi = clamp(v, 0, min(len, max_len)) as before, row t sees the keys lo <= n < hi,
+ * lo = max(0, starts[sequence], v - window); where lo >= hi it sees none and is the row that sees no key of the entries above.  Keys
+ * below lo are +0 in p.  Everything a row computes is, bit for bit, what the entry without _win computes for it with -inf scores
+ * below lo; tiles, slices and blocks below every row's lo are skipped (the combine pass still walks every block).  The same
+ * workspaces.  Pad tokens are cached tokens like any other: nothing is evicted.  Errors as the entry each extends; window < 0 or
+ * starts_dev not 4-byte aligned: BFPQ_E_ARG.  starts_dev NULL and window 0 launch the kernels of the entry without _win. */
+int bfpq_kv_attend_gqa_win(const void* q_dev, const void* k_codes_dev, const int8_t* k_exps_dev, const void* v_codes_dev, const int8_t* v_exps_dev,
+                           void* out_dev, void* p_dev, const int32_t* lens_dev, int64_t BH, int64_t heads, int64_t Tq, int64_t group, int64_t D,
+                           int64_t max_len, int64_t cap, int64_t ldd, int64_t ldo, int64_t ldp, double scale, int causal, int dtype,
+                           int block_size, int x_mant_bits, int w_mant_bits, double epsilon, const uint8_t* exp_win_dev, void* score_ws_dev,
+                           int64_t score_ws_bytes, void* sum_ws_dev, int64_t sum_ws_bytes, int64_t chunks_per_split, const int32_t* starts_dev,
+                           int64_t window, void* stream);
+int bfpq_kv_attend_rows_win(const void* q_dev, const void* k_codes_dev, const int8_t* k_exps_dev, const void* v_codes_dev, const int8_t* v_exps_dev,
+                            void* out_dev, void* p_dev, const int32_t* lens_dev, int64_t BH, int64_t heads, int64_t Tq, int64_t group, int64_t D,
+                            int64_t max_len, int64_t cap, int64_t ldd, int64_t ldo, int64_t ldp, double scale, int causal, int dtype,
+                            int block_size, int x_mant_bits, int w_mant_bits, double epsilon, const uint8_t* exp_win_dev, void* score_ws_dev,
+                            int64_t score_ws_bytes, void* sum_ws_dev, int64_t sum_ws_bytes, int64_t chunks_per_split, int64_t row0, int64_t rows,
+                            const int32_t* starts_dev, int64_t window, void* stream);
 /* ---- 2:4-compressed packed weights (format sp24) and their few-token product on v_smfmac_i32_16x16x64_i8 -------------------------
  * A weight pruned N:M with M = 4, N <= 2 along K (_structured_N_M_sparsity, reference bfp_ops.py:73-91) and quantized to HBFP block 64
  * holds at most 2 non-zero codes per group of 4.  sp24 keeps those two codes and their 2-bit positions, tiled for the decode kernel

@@ -1263,7 +1263,7 @@ def _gen_matmul_i8_op(bfp_args, matrix_unit):
 
     def kv_cache(batch, heads, head_dim, capacity, dtype=torch.bfloat16, device='cuda', **mode):
         """an HBFPKVCache under this op's bfp_args; its products count in matmul_stats.cache_calls.  mode: device_lengths=True (and
-        chunks_per_split), kv_heads, prompt_rows as HBFPKVCache takes them"""
+        chunks_per_split), kv_heads, prompt_rows, window, starts as HBFPKVCache takes them"""
         return HBFPKVCache(batch, heads, head_dim, capacity, dtype=dtype, stats=stats, **mode, **dict(bfp_args, device=device))
 
     bfp_op.__name__ = fake.__name__
@@ -1373,7 +1373,31 @@ class HBFPKVCache:
     [B heads, P, cap] made by prepare_attend() or the first long attend(), stays below 2^31 bytes -- and head_dim is at most 256.
     Small panels bound the workspace, large ones fill the device: a panel launches B heads P / 64 workgroups.  0, the default, is the
     cache above in every respect: nothing more is allocated and no new kernel is launched.  scores() and context() keep their 16-row
-    limit, and the host-length cache stays as it is: both are outside this route."""
+    limit, and the host-length cache stays as it is: both are outside this route.
+
+    window=W and starts=True (a first visible key per row; both need device_lengths=True): what a row of attend() sees is a
+    range of keys, not a prefix.  With len = lengths[b], v(t) = len - Tq + t + 1 (causal) or len, and hi(t) = clamp(v(t), 0,
+    min(len, max_len)) as above, row t sees the keys lo(t) <= n < hi(t),
+
+        lo(t) = max(0, starts[b] if starts, v(t) - W if window)
+
+    starts=True gives the cache `cache.starts`, int32 [B] on the device, zero at construction and after reset(): the number of pad
+    tokens at the front of sequence b of a left-padded batch (the reference's batched generate(); modeling_gpt2.py:228-230 and
+    modeling_llama.py:402-404 hide them with the additive attention_mask).  The caller appends the pad tokens like any others and writes
+    their count, cache.starts.copy_(pad_counts); the kernels read it at launch and never on the host, so a captured step follows a
+    change between replays.  A negative start counts as 0.  window=W, an int >= 1, is sliding-window attention (sliding_window in
+    modeling_attn_mask_utils.py: Mistral, Mixtral, Qwen2, Starcoder2): causal row i sees the W keys i - W + 1 .. i; without causal
+    every row sees the last W keys of its sequence.  Nothing is evicted: a windowed cache still holds `capacity` tokens.  Keys below
+    lo are exactly +0 in p; a row with lo >= hi sees nothing and is the row above that sees no key (p all +0, the context what
+    context() makes of a p of zeros).  Every row is, bit for bit, the row the cache without them computes from scores that are -inf
+    below lo, so ctx == context(p) still holds and nothing depends on Tq, prompt_rows, chunks_per_split or the rows beside it; key
+    tiles, slices and token blocks below every row's lo are skipped.  Both compose with kv_heads, prompt_rows, max_len, causal,
+    return_probs, chunks_per_split and max_query_rows, on both routes of attend().  Only attend() honours them: scores() and
+    context() are products, not attention, and stay exactly as they are.  With neither (None, False: the defaults) the cache is the
+    one above in every respect: the same entries, kernels, workspaces and bytes."""
+
+    window = None                  # no window, and ...
+    starts = None                  # ... no starts, unless the constructor is given them
 
     @staticmethod
     def prompt_rows_max(batch, heads, capacity):
@@ -1381,7 +1405,7 @@ class HBFPKVCache:
         return ((1 << 31) - 16) // (4 * batch * heads * native.code_pitch(capacity)) // 16 * 16
 
     def __init__(self, batch, heads, head_dim, capacity, dtype=torch.bfloat16, device='cuda', stats=None, device_lengths=False,
-                 chunks_per_split=0, max_query_rows=native.KV_DEC_MAX_TOKENS, kv_heads=None, prompt_rows=0, **bfp_args):
+                 chunks_per_split=0, max_query_rows=native.KV_DEC_MAX_TOKENS, kv_heads=None, prompt_rows=0, window=None, starts=False, **bfp_args):
         a = unpack_bfp_args(bfp_args)
         if bfp_args:
             raise TypeError(f"HBFPKVCache: unknown arguments {sorted(bfp_args)}")
@@ -1418,6 +1442,18 @@ class HBFPKVCache:
                 raise ValueError(f"HBFPKVCache: prompt_rows={prompt_rows} makes a panel workspace of 2^31 bytes or more; the most here is "
                                  f"{self.prompt_rows_max(batch, heads, capacity)}")
         self.prompt_rows = prompt_rows
+        if window is not None:
+            if isinstance(window, bool) or not isinstance(window, int):
+                raise TypeError(f"HBFPKVCache: window must be None or an int (got {window!r})")
+            if window < 1:
+                raise ValueError(f"HBFPKVCache: window must be >= 1 (got {window})")
+            if not self.device_lengths:
+                raise ValueError("HBFPKVCache: window needs device_lengths=True")
+            self.window = window
+        if not isinstance(starts, bool):
+            raise TypeError(f"HBFPKVCache: starts must be False or True (got {starts!r}); the counts go into cache.starts")
+        if starts and not self.device_lengths:
+            raise ValueError("HBFPKVCache: starts needs device_lengths=True")
         self.batch, self.heads, self.head_dim, self.capacity, self.dtype = batch, heads, head_dim, capacity, dtype
         self.kv_heads, self.group = kv_heads, heads // kv_heads  # query head h reads kv head h // group
         self.block, self.mant_bits, self.epsilon = a['block_size'], a['mant_bits'], a['epsilon']
@@ -1437,6 +1473,8 @@ class HBFPKVCache:
             self._ws = self._workspace(max_query_rows)            # context()'s only workspace: made here, never grown
             self._att_ws = None                                   # attend()'s fp32 score rows: made by its first call
             self._rows_ws = None                                  # the panel's fp32 score rows (prompt_rows): likewise
+            if starts:
+                self.starts = z(B, dt=torch.int32)                # the first visible key of every sequence: written by the caller
 
     @property
     def length(self):
@@ -1462,6 +1500,8 @@ class HBFPKVCache:
         if self.device_lengths:
             self.lengths.zero_()
             self.overflow.zero_()
+            if self.starts is not None:
+                self.starts.zero_()
         else:
             self.length = 0
         self.v_codes.zero_()
@@ -1522,7 +1562,8 @@ class HBFPKVCache:
         return self.act is None and rows <= native.KV_DEC_MAX_TOKENS
 
     def scores(self, q, max_len=None):
-        """q [B, H, Tq, D] -> [B, H, Tq, S]: Q_in(q) @ Q_w(K_all)^T.  With device_lengths: [B, H, Tq, max_len], -inf from lengths[b] on"""
+        """q [B, H, Tq, D] -> [B, H, Tq, S]: Q_in(q) @ Q_w(K_all)^T.  With device_lengths: [B, H, Tq, max_len], -inf from lengths[b] on.
+        A product, not attention: window and starts do not act here"""
         x = self._operand(q, 'scores', self.head_dim)
         Tq = q.shape[2]
         if not self.device_lengths and max_len is not None:
@@ -1551,7 +1592,8 @@ class HBFPKVCache:
 
     def context(self, p):
         """p [B, H, Tq, S] -> [B, H, Tq, D]: Q_in(p) @ Q_w(V_all^T)^T, blocks along the S cached tokens (the last one zero-padded).  With
-        device_lengths: p [B, H, Tq, L], 1 <= L <= capacity, sequence b over its first min(lengths[b], L) tokens"""
+        device_lengths: p [B, H, Tq, L], 1 <= L <= capacity, sequence b over its first min(lengths[b], L) tokens.  A product, not
+        attention: window and starts do not act here"""
         if self.device_lengths:
             if not isinstance(p, torch.Tensor) or p.dim() != 4 or not 1 <= p.shape[-1] <= self.capacity:
                 raise ValueError(f"HBFPKVCache.context takes p [..., L], 1 <= L <= {self.capacity} (got {tuple(getattr(p, 'shape', ()))})")
@@ -1599,7 +1641,7 @@ class HBFPKVCache:
     def attend(self, q, scale, max_len=None, causal=False, return_probs=False):
         """q [B, H, Tq, D] -> the context [B, H, Tq, D] of softmax(scores(q, max_len) * scale) (the class docstring); with return_probs
         also p [B, H, Tq, max_len].  device_lengths only; two products, three launches.  More than 16 rows need prompt_rows (the
-        class docstring): two launches per panel"""
+        class docstring): two launches per panel.  A cache with window / starts takes the rows' first keys from them"""
         if not self.device_lengths:
             raise ValueError("HBFPKVCache.attend needs device_lengths=True")
         x = self._operand(q, 'attend', self.head_dim)
@@ -1618,13 +1660,14 @@ class HBFPKVCache:
         if panels:
             out, p = native.kv_attend_rows(x, self.k_codes, self.k_exps, self.v_codes, self.v_exps, self.lengths, self.kv_heads, n, float(scale),
                                            bool(causal), self.block, self.mant_bits, self.epsilon, self._rows_ws, self.prompt_rows,
-                                           return_probs=bool(return_probs), group=self.group)
+                                           return_probs=bool(return_probs), group=self.group, starts=self.starts, window=self.window)
             self.stats.cache_calls += 2
             out = self._result(out, Tq)
             return (out, self._result(p, Tq)) if return_probs else out
         out, p = native.kv_attend(x, self.k_codes, self.k_exps, self.v_codes, self.v_exps, self.lengths, self.kv_heads, n, float(scale),
                                   bool(causal), self.block, self.mant_bits, self.epsilon, self._att_ws, self._ws,
-                                  chunks_per_split=self.chunks_per_split, return_probs=bool(return_probs), group=self.group)
+                                  chunks_per_split=self.chunks_per_split, return_probs=bool(return_probs), group=self.group,
+                                  starts=self.starts, window=self.window)
         self.stats.cache_calls += 2
         out = self._result(out, Tq)
         return (out, self._result(p, Tq)) if return_probs else out

@@ -47,6 +47,13 @@
 // rows, a 16-row tile per wave.  k_kv_qk_rows: quant_operand on its rows of q once, into LDS, then tiles of 64 keys that go through LDS
 // once for the four waves, att_scores into the fp32 panel.  k_kv_pv_rows: row_stats, then form_p, quant_operand and the rescale of
 // every token block in block order into fp32 accumulators that hold all D columns.  No block sums, no combine pass.
+//
+// A first visible key per row (left-padded batches, modeling_gpt2.py:228-230 / modeling_llama.py:402-404, and the
+// sliding_window of modeling_attn_mask_utils.py): the WIN instances of the four attend kernels, behind bfpq_kv_attend_gqa_win and
+// bfpq_kv_attend_rows_win.  A row sees the keys att_first <= n < att_visible.  att_scores, row_stats and form_p leave out what lies below
+// the first key -- the bits of the row with -inf there -- and the kernels skip the key tiles, slices and token blocks below every first
+// key of a tile, a wave or a workgroup, a skipped block of p leaving the term of a zero block.  The instances without WIN never read
+// `starts` and `window` and are the code they were.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "bfpq.h"
@@ -246,29 +253,68 @@ __device__ __forceinline__ int att_visible(int len, int Kx, int Tq, int t, int c
     return v < Kx ? (v > 0 ? v : 0) : Kx;
 }
 
-// att_scores: MODE kAtt's epilogue on a lane's four scores of keys n .. n + 3 of a row that sees `vis` keys
-template <int DT> __device__ __forceinline__ void att_scores(v2f& a01, v2f& a23, int n, int vis, float scale)
+// the first key that row sees (WIN instances): its sequence's `start` (left padding; negative counts as 0) or, with a window,
+// the key `window` below the end of what it sees, whichever is later.  The row sees the keys lo <= n < att_visible, none where lo is
+// not below that; lo does not decrease with t.  window 0: none
+__device__ __forceinline__ int att_first(int len, int Tq, int t, int causal, int start, int window)
+{
+    const int lo = start > 0 ? start : 0;
+    if (window <= 0) return lo;
+    const int v = causal ? len - Tq + t + 1 : len;
+    const int w = v > window ? v - window : 0;
+    return w > lo ? w : lo;
+}
+
+// sequence b's start, or 0 without starts
+__device__ __forceinline__ int seq_start(const int32_t* __restrict__ starts, int b) { return starts ? starts[b] : 0; }
+
+// the least of a wave's values
+__device__ __forceinline__ int wave_min(int v)
+{
+#pragma unroll
+    for (int o = 32; o; o >>= 1) {
+        const int u = __shfl_xor(v, o, 64);
+        v = u < v ? u : v;
+    }
+    return __builtin_amdgcn_readfirstlane(v);                    // (the same in every lane: a scalar, so a branch on it is uniform)
+}
+
+// key k of a row that sees [lo, vis): WIN instances have a first key, the others see a prefix and never read lo
+template <bool WIN> __device__ __forceinline__ bool sees(int k, int lo, int vis)
+{
+    if constexpr (WIN) return k >= lo && k < vis;
+    else return k < vis;
+}
+
+// att_scores: MODE kAtt's epilogue on a lane's four scores of keys n .. n + 3 of a row that sees the keys lo .. vis - 1
+template <int DT, bool WIN = false> __device__ __forceinline__ void att_scores(v2f& a01, v2f& a23, int n, int lo, int vis, float scale)
 {
     const float ninf = -__builtin_inff();
-    a01.x = n + 0 < vis ? rnd<DT>(a01.x) * scale : ninf;
-    a01.y = n + 1 < vis ? rnd<DT>(a01.y) * scale : ninf;
-    a23.x = n + 2 < vis ? rnd<DT>(a23.x) * scale : ninf;
-    a23.y = n + 3 < vis ? rnd<DT>(a23.y) * scale : ninf;
+    a01.x = sees<WIN>(n + 0, lo, vis) ? rnd<DT>(a01.x) * scale : ninf;
+    a01.y = sees<WIN>(n + 1, lo, vis) ? rnd<DT>(a01.y) * scale : ninf;
+    a23.x = sees<WIN>(n + 2, lo, vis) ? rnd<DT>(a23.x) * scale : ninf;
+    a23.y = sees<WIN>(n + 3, lo, vis) ? rnd<DT>(a23.y) * scale : ninf;
 }
 
 // GRP: head b has R = group * Tq rows of x and out (row = query head of the group * Tq + token), walked in tiles of 16: blockIdx.y runs
 // over (head, tile).  Without GRP the argument `group` is passed and never read (the compiler drops it: the register figures of those
-// instances are the ones they had without it): one tile, the row is the token
-template <int BLK, int DT, int TM, int MODE, bool GRP = false>
-__global__ void __launch_bounds__(256) k_kv_bmm_dec(const void* __restrict__ x, const int8_t* __restrict__ wc, const int8_t* __restrict__ we,
+// instances are the ones they had without it): one tile, the row is the token.
+// WIN (kAtt only): rows have a first key (att_first; starts per sequence or null, window or 0 -- both unread without WIN).  A wave whose
+// 16 TM keys lie below the first key of all 16 rows of the tile skips the product and stores nothing: the softmax never reads there.
+// The WIN instances of block 64 are held to the 2 waves per SIMD of their plain twins (without the bound they take 241-243 VGPRs + 16
+// AGPRs and run 1)
+template <int BLK, int DT, int TM, int MODE, bool GRP = false, bool WIN = false>
+__global__ void __launch_bounds__(256, WIN && BLK == 64 ? 2 : 1) k_kv_bmm_dec(const void* __restrict__ x, const int8_t* __restrict__ wc, const int8_t* __restrict__ we,
                                                     void* __restrict__ out, int B, int Tq, int Kx, int Nout, int ldx, int ldw, int ldwe, int wbs,
                                                     int ldo, int xm, int wm, float eps_dt, const uint8_t* __restrict__ exp_win,
-                                                    const int32_t* __restrict__ lens, int heads, float scale, int causal, int group)
+                                                    const int32_t* __restrict__ lens, int heads, float scale, int causal, int group,
+                                                    const int32_t* __restrict__ starts, int window)
 {
     using Blk = I8Blk<BLK>;
     using op_t = typename Blk::op_t;
     using Tr = Traits<DT>;
     using raw_t = typename Tr::raw_t;
+    static_assert(!WIN || MODE == kAtt, "a first key is attention's");
     constexpr bool DEV = MODE != kHost;
     constexpr int ODT = MODE == kAtt ? BFPQ_F32 : DT;            // the output's element type
     constexpr int NBS = 64 / BLK;                                // blocks per 64-byte chunk
@@ -317,6 +363,11 @@ __global__ void __launch_bounds__(256) k_kv_bmm_dec(const void* __restrict__ x, 
                 continue;
             }
             rows(No);
+        }
+        // (WIN) the first key the lane's row sees
+        auto first = [&]() __attribute__((always_inline)) { return att_first(len, Tq, GRP ? row % Tq : r, causal, seq_start(starts, b / heads), window); };
+        if constexpr (WIN) {
+            if (n0 + 16 * TM <= wave_min(tok ? first() : 0x7fffffff)) continue;   // (wave-uniform) no row of the tile sees a key of this wave
         }
         const int8_t* const wcb = wc + (size_t)b * wbs * ldw;
         const int8_t* const web = we + (size_t)b * wbs * ldwe;
@@ -392,11 +443,12 @@ __global__ void __launch_bounds__(256) k_kv_bmm_dec(const void* __restrict__ x, 
 
         // the lane holds rows n .. n + 3 of row `row` (the pitch ldo takes the ones past Nout)
         if (tok) {
+            const int lo = WIN ? first() : 0;
 #pragma unroll
             for (int i = 0; i < TM; i++) {
                 const int n = n0 + 16 * i + 4 * q;
                 if constexpr (MODE == kAtt) {
-                    att_scores<DT>(acc[i][0], acc[i][1], n, att_visible(len, No, Tq, GRP ? row % Tq : r, causal), scale);
+                    att_scores<DT, WIN>(acc[i][0], acc[i][1], n, lo, att_visible(len, No, Tq, GRP ? row % Tq : r, causal), scale);
                 } else if constexpr (DEV) {
                     if (n + 0 >= No) acc[i][0].x = ninf;
                     if (n + 1 >= No) acc[i][0].y = ninf;
@@ -428,6 +480,10 @@ __global__ void __launch_bounds__(256) k_kv_bmm_dec(const void* __restrict__ x, 
 // GRP: head bh has R = group * Tq rows (k_kv_bmm_dec), blockIdx.z runs over (head, tile of 16 rows) and a workgroup reduces, quantizes
 // and multiplies the rows of its own tile; sums, xexp, the score rows and p are indexed by (head, row).  A row's visible length is that
 // of its token, row % Tq.  Without GRP `group` is unused here too.
+//
+// WIN (ATT only): rows have a first key (att_first).  A slice whose tokens lie below the first key of every row of the tile leaves what
+// a zero p block leaves the combine pass -- the bare MAGIC_I, exact for zero codes whatever V holds, and block_scale(0)'s exponent --
+// and reads neither score rows nor V codes.  Without WIN starts and window are unread.
 constexpr int kMaxCps = 16;                               // chunks per slice (the LDS holds their codes)
 constexpr int64_t kSplitGrid = 2048;                      // workgroups the chosen slice size aims to stay within
 
@@ -459,13 +515,15 @@ template <int NR> __device__ __forceinline__ float row_sum(const float* s_red, i
     return (ss[0] + ss[1]) + (ss[2] + ss[3]);
 }
 
-// row_stats: rows t < nr of the fp32 score rows sc (pitch ld) reduced over their first vis(t) columns to s_red, by all 256 threads: the
+// row_stats: rows t < nr of the fp32 score rows sc (pitch ld) reduced over their columns lo(t) .. vis(t) - 1 to s_red, by all 256 threads: the
 // maximum (NaN propagates), then the sum of expf(s - max) -- a thread over its columns 4 tid + 1024 i .. + 3 in ascending order, the 64
 // lanes of a wave by a butterfly, the waves' partials left for row_max / row_sum.  U rows' loads are in flight at a time; a row's
 // operations and their order do not depend on U, nr or the rows beside it.  Both passes end with a barrier; whatever the caller wrote
-// to LDS before the call is visible after it
-template <int U, int NR, class V>
-__device__ __forceinline__ void row_stats(const float* __restrict__ sc, int ld, int nr, V&& vis, float* s_red)
+// to LDS before the call is visible after it.  WIN: a thread keeps the columns it owns and leaves out those below lo(t) -- the bits of the
+// row with -inf there, nan_max(m, -inf) == m and a + expf(-inf - m) == a -- starting at its first stride that reaches some row's first
+// key; it loads a float4 only where the row sees one of the four.  Without WIN lo is never called
+template <int U, int NR, bool WIN, class V, class F>
+__device__ __forceinline__ void row_stats(const float* __restrict__ sc, int ld, int nr, V&& vis, F&& lo, float* s_red)
 {
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
     // f(u, v) over the visible elements this thread owns of rows t0 + u, u < U, each row's in ascending order
@@ -475,6 +533,29 @@ __device__ __forceinline__ void row_stats(const float* __restrict__ sc, int ld, 
         for (int u = 0; u < U; u++) {
             vt[u] = t0 + u < nr ? vis(t0 + u) : 0;
             vm = vt[u] > vm ? vt[u] : vm;
+        }
+        if constexpr (WIN) {
+            int lt[U], lm = 0x7fffffff;
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                lt[u] = t0 + u < nr ? lo(t0 + u) : 0x7fffffff;
+                lm = lt[u] < lm ? lt[u] : lm;
+            }
+            if (lm >= vm) return;                                // no row of these sees a key
+            const int own = tid * 4 + 3;                         // the thread's first stride with a column at or past lm
+            for (int k = tid * 4 + (lm > own ? (lm - own + 1023) / 1024 * 1024 : 0); k < vm; k += 1024) {
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    if (k < vt[u] && k + 3 >= lt[u] && lt[u] < vt[u]) {   // (a row that sees nothing loads nothing)
+                        const float4 v = *reinterpret_cast<const float4*>(sc + (size_t)(t0 + u) * ld + k);
+                        if (k >= lt[u]) f(u, v.x);
+                        if (k + 1 >= lt[u] && k + 1 < vt[u]) f(u, v.y);
+                        if (k + 2 >= lt[u] && k + 2 < vt[u]) f(u, v.z);
+                        if (k + 3 < vt[u]) f(u, v.w);
+                    }
+                }
+            }
+            return;
         }
         for (int k = tid * 4; k < vm; k += 1024) {
 #pragma unroll
@@ -519,32 +600,38 @@ __device__ __forceinline__ void row_stats(const float* __restrict__ sc, int ld, 
 }
 
 // form_p: p of the lane's NE elements k0 .. of its fp32 score row, in the dtype's bits: expf(s - rmax) / rsum rounded once, +0 from the
-// row's visible length on.  prow (or null): the lane's row of the p the caller returns; the visible elements are stored there
-template <int DT, int NE>
-__device__ __forceinline__ void form_p(const float* __restrict__ srow, int k0, int vis, float rmax, float rsum, typename Traits<DT>::raw_t* prow,
-                                       uint32_t (&xv)[NE])
+// row's visible length on (WIN: and below its first key lo, with the same guard on the loads).  prow (or null): the lane's row of the p
+// the caller returns; the visible elements are stored there
+template <int DT, bool WIN, int NE>
+__device__ __forceinline__ void form_p(const float* __restrict__ srow, int k0, int lo, int vis, float rmax, float rsum,
+                                       typename Traits<DT>::raw_t* prow, uint32_t (&xv)[NE])
 {
 #pragma unroll
     for (int v = 0; v < NE / 4; v++) {
         float4 sv = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (k0 + 4 * v < vis) sv = *reinterpret_cast<const float4*>(srow + k0 + 4 * v);
+        if constexpr (WIN) {
+            if (k0 + 4 * v < vis && k0 + 4 * v + 3 >= lo) sv = *reinterpret_cast<const float4*>(srow + k0 + 4 * v);
+        } else {
+            if (k0 + 4 * v < vis) sv = *reinterpret_cast<const float4*>(srow + k0 + 4 * v);
+        }
         const float se[4] = {sv.x, sv.y, sv.z, sv.w};
 #pragma unroll
         for (int e = 0; e < 4; e++) {
             const int k = k0 + 4 * v + e;
-            xv[4 * v + e] = k < vis ? f32_to_raw<DT>(expf(se[e] - rmax) / rsum) : 0u;
-            if (prow && k < vis) prow[k] = (typename Traits<DT>::raw_t)xv[4 * v + e];
+            xv[4 * v + e] = sees<WIN>(k, lo, vis) ? f32_to_raw<DT>(expf(se[e] - rmax) / rsum) : 0u;
+            if (prow && sees<WIN>(k, lo, vis)) prow[k] = (typename Traits<DT>::raw_t)xv[4 * v + e];
         }
     }
 }
 
-template <int BLK, int DT, bool ATT, bool GRP = false>
+template <int BLK, int DT, bool ATT, bool GRP = false, bool WIN = false>
 __global__ void __launch_bounds__(256) k_kv_pv_split(const void* __restrict__ x, const int8_t* __restrict__ vc, int32_t* __restrict__ sums,
                                                      int8_t* __restrict__ xexp, const int32_t* __restrict__ lens, int heads, int Tq, int L,
                                                      int D, int ldx, int cap, int nbw, int cps, int xvec, int xm, float eps_dt,
                                                      const uint8_t* __restrict__ exp_win, void* __restrict__ pout, int ldp, int causal,
-                                                     int group)
+                                                     int group, const int32_t* __restrict__ starts, int window)
 {
+    static_assert(!WIN || ATT, "a first key is attention's");
     using Blk = I8Blk<BLK>;
     using op_t = typename Blk::op_t;
     using Tr = Traits<DT>;
@@ -563,28 +650,46 @@ __global__ void __launch_bounds__(256) k_kv_pv_split(const void* __restrict__ x,
     const int w = threadIdx.x >> 6, l = threadIdx.x & 63, r = l & 15, q = l >> 4;
     const bool tok = r < nr;
     raw_t* const prow = pout ? reinterpret_cast<raw_t*>(pout) + ((size_t)bh * R + r0) * ldp : nullptr;   // the tile's rows of p
+    const int start = WIN ? seq_start(starts, bh / heads) : 0;
+    auto first = [&](int i) __attribute__((always_inline)) { return att_first(len, Tq, token(i), causal, start, window); };   // (WIN) of row i
     if constexpr (ATT) {
         if (pout && blockIdx.x == 0) {                           // +0 at what the rows do not see of this slice's columns
             const int k0 = c0 << 6, k1 = k0 + (cps << 6) < L ? k0 + (cps << 6) : L;
             for (int i = threadIdx.x; i < nr * (k1 - k0); i += 256) {
                 const int t = i / (k1 - k0), k = k0 + i % (k1 - k0);
-                if (k >= att_visible(len, Kx, Tq, token(t), causal)) prow[(size_t)t * ldp + k] = (raw_t)0;
+                if (!sees<WIN>(k, WIN ? first(t) : 0, att_visible(len, Kx, Tq, token(t), causal))) prow[(size_t)t * ldp + k] = (raw_t)0;
             }
         }
     }
     if ((c0 << 6) >= Kx) return;                                 // (the whole workgroup, before any barrier)
     load_exp_win(s_win, exp_win);
+    if constexpr (WIN) {
+        const int c1 = c0 + cps < (Kx + 63) >> 6 ? c0 + cps : (Kx + 63) >> 6;
+        if ((c1 << 6) <= wave_min(tok ? first(r) : 0x7fffffff)) {  // (the whole workgroup) no row of the tile sees a token of the slice
+            __syncthreads();
+            const int n0 = ((int)blockIdx.x * 4 + w) * 16, nb = (Kx + BLK - 1) / BLK;
+            if (n0 >= D || !tok) return;
+            const int8_t e0 = sat_exp(block_scale<DT>(0u, xm, eps_dt, s_win));
+            const size_t o0 = ((size_t)bh * R + r0 + r) * nbw;
+            for (int j = c0 * NBS; j < c1 * NBS && j < nb; j++) {
+                *reinterpret_cast<v4i*>(sums + (o0 + j) * D + n0 + 4 * q) = v4i{MAGIC_I, MAGIC_I, MAGIC_I, MAGIC_I};
+                if (n0 == 0 && q == 0) xexp[o0 + j] = e0;
+            }
+            return;
+        }
+    }
     const float* const srow = reinterpret_cast<const float*>(x) + ((size_t)bh * R + r0 + (tok ? r : 0)) * ldx;   // (ATT) the lane's score row
     raw_t* const plane = (prow && blockIdx.x == 0) ? prow + (size_t)r * ldp : nullptr;                            // (ATT) and its row of p
     float rmax = 0.f, rsum = 1.f;
-    int vis = 0;
+    int vis = 0, lo = 0;
     if constexpr (ATT) {
-        row_stats<1, BFPQ_KV_DEC_MAX_TOKENS>(reinterpret_cast<const float*>(x) + ((size_t)bh * R + r0) * ldx, ldx, nr,
-                                             [&](int t) { return att_visible(len, Kx, Tq, token(t), causal); }, s_red);
+        row_stats<1, BFPQ_KV_DEC_MAX_TOKENS, WIN>(reinterpret_cast<const float*>(x) + ((size_t)bh * R + r0) * ldx, ldx, nr,
+                                                  [&](int t) { return att_visible(len, Kx, Tq, token(t), causal); }, first, s_red);
         if (tok) {
             rmax = row_max(s_red, r);
             rsum = row_sum<BFPQ_KV_DEC_MAX_TOKENS>(s_red, r);
             vis = att_visible(len, Kx, Tq, token(r), causal);
+            if constexpr (WIN) lo = first(r);
         }
     } else __syncthreads();
     const int nb = (Kx + BLK - 1) / BLK, nch = (Kx + 63) >> 6, c1 = c0 + cps < nch ? c0 + cps : nch;
@@ -597,7 +702,7 @@ __global__ void __launch_bounds__(256) k_kv_pv_split(const void* __restrict__ x,
             const int k0 = (c << 6) + s * BLK + Blk::lane(q);
             uint32_t xv[NE];
             if constexpr (ATT) {
-                form_p<DT>(srow, k0, vis, rmax, rsum, plane, xv);
+                form_p<DT, WIN>(srow, k0, lo, vis, rmax, rsum, plane, xv);
             } else if (xvec && k0 + NE <= L) {                   // rows 16-byte aligned: the lane's elements in 16-byte loads
 #pragma unroll
                 for (int v = 0; v < NE / Tr::VEC; v++) bfpq_dev::load_raw_vec<DT>(xr + k0, v, xv + v * Tr::VEC);
@@ -703,6 +808,14 @@ __device__ __forceinline__ int range_visible(int a, int e, int rows, int row0, i
     return att_visible(len, Kx, Tq, t, causal);
 }
 
+// ... and see no key below what their earliest token sees first (att_first does not decrease with the token): the first row's token,
+// or the panel's first token where the range runs over the end of a query head's segment
+__device__ __forceinline__ int range_first(int a, int e, int rows, int row0, int len, int Tq, int causal, int start, int window)
+{
+    const int t = a / rows != e / rows ? row0 : row0 + a % rows;
+    return att_first(len, Tq, t, causal, start, window);
+}
+
 // An operand of block BLK as it lies in LDS: 64 lanes of 16 bytes, of 8 bytes, or (block 16, whose lanes 32..63 carry no k) 32 lanes
 template <int BLK> struct LdsOp {
     static constexpr int LN = BLK == 16 ? 32 : 64;
@@ -713,11 +826,14 @@ template <int BLK> struct LdsOp {
 // operands s_q [wave][block][lane] with their exponents s_qe; then it loops over the tiles of 64 keys some row of it sees: the tile's codes s_k [16-key tile][block][lane] and exponents s_ke
 // [block][key] are loaded once for the four waves, and a wave whose own rows see none of the tile sits it out.  Blocks are added in
 // block order, the epilogue is att_scores; only the columns below the wave's visible length are written, which is all the softmax reads.
-template <int BLK, int DT>
+// WIN: rows have a first key (att_first).  The loop starts at the tile of the workgroup's least first key (range_first) and a wave sits
+// out the tiles below its own rows' least; those columns are not written and the softmax does not read them.
+template <int BLK, int DT, bool WIN = false>
 __global__ void __launch_bounds__(256) k_kv_qk_rows(const void* __restrict__ x, const int8_t* __restrict__ kc, const int8_t* __restrict__ ke,
                                                     float* __restrict__ ws, int Tq, int D, int Nout, int ldd, int cap, int pitch, int xm, int wm,
                                                     float eps_dt, const uint8_t* __restrict__ exp_win, const int32_t* __restrict__ lens, int heads,
-                                                    float scale, int causal, int group, int row0, int rows)
+                                                    float scale, int causal, int group, int row0, int rows, const int32_t* __restrict__ starts,
+                                                    int window)
 {
     using Blk = I8Blk<BLK>;
     using op_t = typename Blk::op_t;
@@ -739,10 +855,14 @@ __global__ void __launch_bounds__(256) k_kv_qk_rows(const void* __restrict__ x, 
     const int prl = pr0 + kRowsWg - 1 < PR ? pr0 + kRowsWg - 1 : PR - 1;
     const int vwg = range_visible(pr0, prl, rows, row0, len, No, Tq, causal);
     if (vwg <= 0) return;                                        // (the whole workgroup, before any barrier) no row sees a key
+    const int start = WIN ? seq_start(starts, b / heads) : 0;
+    const int lwg = WIN ? range_first(pr0, prl, rows, row0, len, Tq, causal, start, window) : 0;   // the workgroup's least first key
+    if (WIN && lwg >= vwg) return;                               // (likewise)
     load_exp_win(s_win, exp_win);
     __syncthreads();
     const int pw0 = pr0 + 16 * w, pwl = pw0 + 15 < PR ? pw0 + 15 : PR - 1;
     const int vw = pw0 < PR ? range_visible(pw0, pwl, rows, row0, len, No, Tq, causal) : 0;   // what the wave's rows see at most
+    const int lw = WIN && pw0 < PR ? range_first(pw0, pwl, rows, row0, len, Tq, causal, start, window) : 0;   // and where at the earliest
     const int pr = pw0 + r;
     const bool tok = pr < PR;
     const int hq = tok ? pr / rows : 0, t = tok ? row0 + pr % rows : row0;
@@ -763,9 +883,10 @@ __global__ void __launch_bounds__(256) k_kv_qk_rows(const void* __restrict__ x, 
     }
     const v4i magic = {MAGIC_I, MAGIC_I, MAGIC_I, MAGIC_I};
     const int vis = tok ? att_visible(len, No, Tq, t, causal) : 0;
+    const int lo = WIN ? att_first(len, Tq, t, causal, start, window) : 0;
     float* const orow = ws + ((size_t)b * PR + (tok ? pr : pr0)) * pitch;
     const int nkt = (vwg + 63) >> 6;
-    for (int kt = 0; kt < nkt; kt++) {
+    for (int kt = WIN ? lwg >> 6 : 0; kt < nkt; kt++) {
         __syncthreads();                                         // (s_q, s_qe written; the tile before this one read)
         const int8_t* const kcb = kc + ((size_t)b * cap + (kt << 6)) * ldd;
         const int8_t* const keb = ke + ((size_t)b * cap + (kt << 6)) * nbd;
@@ -776,6 +897,7 @@ __global__ void __launch_bounds__(256) k_kv_qk_rows(const void* __restrict__ x, 
         for (int idx = tid; idx < 64 * nbd; idx += 256) s_ke[(idx % nbd) * 64 + idx / nbd] = keb[idx];
         __syncthreads();
         if ((kt << 6) >= vw) continue;                           // (wave-uniform) none of the wave's rows sees this tile
+        if (WIN && ((kt + 1) << 6) <= lw) continue;              // (likewise) it lies below their first keys
         v2f acc[4][2];
 #pragma unroll
         for (int i = 0; i < 4; i++) acc[i][0] = acc[i][1] = v2f{0.f, 0.f};
@@ -796,7 +918,7 @@ __global__ void __launch_bounds__(256) k_kv_qk_rows(const void* __restrict__ x, 
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 const int n = (kt << 6) + 16 * i + 4 * q;
-                att_scores<DT>(acc[i][0], acc[i][1], n, vis, scale);
+                att_scores<DT, WIN>(acc[i][0], acc[i][1], n, lo, vis, scale);
                 if (n < Nout) store4<BFPQ_F32>(orow, n, acc[i][0], acc[i][1]);
             }
         }
@@ -811,11 +933,15 @@ __global__ void __launch_bounds__(256) k_kv_qk_rows(const void* __restrict__ x, 
 // every block j in jstop .. nb - 1 the combine pass would still add the term of an all-zero p block -- its scale from block_scale(0),
 // NaN where the dtype's epsilon is zero; the block sum zero; V's scale, NaN for a NaN block -- so the wave adds exactly that term,
 // rescale() of the bare MAGIC_I, from V's exponent bytes alone.  With pout, p is zero from a row's visible length on.
-template <int BLK, int DT>
+// WIN: rows have a first key (att_first).  The blocks below the least first key of the wave's rows (j < jstart) get the same zero-block
+// term, in block order before the first block the wave forms p for, and the chunks start at the workgroup's first seen one; p is zero
+// below a row's first key too.
+template <int BLK, int DT, bool WIN = false>
 __global__ void __launch_bounds__(256) k_kv_pv_rows(const float* __restrict__ ws, const int8_t* __restrict__ vc, const int8_t* __restrict__ ve,
                                                     void* __restrict__ out, void* __restrict__ pout, const int32_t* __restrict__ lens, int heads,
                                                     int Tq, int L, int D, int pitch, int cap, int ldve, int ldo, int ldp, int xm, int wm,
-                                                    float eps_dt, const uint8_t* __restrict__ exp_win, int causal, int group, int row0, int rows)
+                                                    float eps_dt, const uint8_t* __restrict__ exp_win, int causal, int group, int row0, int rows,
+                                                    const int32_t* __restrict__ starts, int window)
 {
     using Blk = I8Blk<BLK>;
     using op_t = typename Blk::op_t;
@@ -835,16 +961,19 @@ __global__ void __launch_bounds__(256) k_kv_pv_rows(const float* __restrict__ ws
     const int len = lens[bh / heads];
     const int Kx = clamp_len(len, L);
     auto row_vis = [&](int i) __attribute__((always_inline)) { return att_visible(len, Kx, Tq, row0 + (pr0 + i) % rows, causal); };
+    const int start = WIN ? seq_start(starts, bh / heads) : 0;
+    auto row_lo = [&](int i) __attribute__((always_inline)) { return att_first(len, Tq, row0 + (pr0 + i) % rows, causal, start, window); };   // (WIN)
     load_exp_win(s_win, exp_win);
-    row_stats<4, kRowsWg>(ws + ((size_t)bh * PR + pr0) * pitch, pitch, nrw, row_vis, s_red);
+    row_stats<4, kRowsWg, WIN>(ws + ((size_t)bh * PR + pr0) * pitch, pitch, nrw, row_vis, row_lo, s_red);
     const int pw0 = pr0 + 16 * w, pr = pw0 + r;
     const bool tok = pr < PR;
     float rmax = 0.f, rsum = 1.f;
-    int vis = 0;
+    int vis = 0, lo = 0;
     if (tok) {
         rmax = row_max(s_red, 16 * w + r);
         rsum = row_sum<kRowsWg>(s_red, 16 * w + r);
         vis = row_vis(16 * w + r);
+        if constexpr (WIN) lo = row_lo(16 * w + r);
     }
     const int hq = tok ? pr / rows : 0, t = tok ? row0 + pr % rows : row0;
     const size_t grow = (size_t)bh * group * Tq + (size_t)hq * Tq + t;   // the lane's row of q, out and p
@@ -861,7 +990,30 @@ __global__ void __launch_bounds__(256) k_kv_pv_rows(const float* __restrict__ ws
     for (int i = 0; i < kMaxDT; i++) acc[i][0] = acc[i][1] = v2f{0.f, 0.f};
 
     const int nchw = (vwg + 63) >> 6;
-    for (int c = 0; c < nchw; c++) {
+    int jstart = 0, cfirst = 0;                                  // (WIN) the first block some row of the wave sees, the workgroup's first chunk
+    if constexpr (WIN) {
+        const int lwg = range_first(pr0, prl, rows, row0, len, Tq, causal, start, window);
+        const int lw = pw0 < PR ? range_first(pw0, pwl, rows, row0, len, Tq, causal, start, window) : 0;
+        jstart = lw / BLK < jstop ? lw / BLK : jstop;
+        cfirst = lwg >> 6 < nchw ? lwg >> 6 : nchw;
+        if (jstart > 0) {                                        // the blocks below every first key of the wave: the term of a zero p block
+            const BlockScale bs = block_scale<DT>(0u, xm, eps_dt, s_win);
+            v2f sx, nm;
+            token_scale((int)sat_exp(bs), xm, sx, nm);
+            for (int j = 0; j < jstart; j++) {
+#pragma unroll
+                for (int i = 0; i < kMaxDT; i++) {
+                    if (i < ndt) {
+                        const int8_t* const we = ve + ((size_t)bh * D + 16 * i + 4 * q) * ldve + j;
+                        v2f sw01, sw23;
+                        weight_scales((int)we[0], (int)we[ldve], (int)we[2 * ldve], (int)we[3 * ldve], wm, sw01, sw23);
+                        rescale(magic, sx, nm, sw01, sw23, acc[i][0], acc[i][1]);
+                    }
+                }
+            }
+        }
+    }
+    for (int c = WIN ? cfirst : 0; c < nchw; c++) {
         __syncthreads();                                         // (the chunk before this one read)
         for (int idx = tid; idx < ndt * NBS * LN; idx += 256) {  // idx = (16-column tile i, block s of the chunk, lane slot)
             const int ls = idx % LN, s = (idx / LN) % NBS, i = idx / (LN * NBS);
@@ -876,9 +1028,10 @@ __global__ void __launch_bounds__(256) k_kv_pv_rows(const float* __restrict__ ws
         for (int s = 0; s < NBS; s++) {
             const int j = c * NBS + s;
             if (j >= jstop) break;                               // (wave-uniform)
+            if (WIN && j < jstart) continue;                     // (likewise)
             const int k0 = (c << 6) + s * BLK + Blk::lane(q);
             uint32_t xv[NE];
-            form_p<DT>(srow, k0, vis, rmax, rsum, prow, xv);
+            form_p<DT, WIN>(srow, k0, lo, vis, rmax, rsum, prow, xv);
             BlockScale bs;
             const op_t bF = quant_operand<BLK, DT>(xv, abs_max<DT>(xv), xm, eps_dt, s_win, bs);
             v2f sx, nm;
@@ -922,6 +1075,10 @@ __global__ void __launch_bounds__(256) k_kv_pv_rows(const float* __restrict__ ws
             const int p = pw0 + i;
             raw_t* const pr_i = reinterpret_cast<raw_t*>(pout) + ((size_t)bh * group * Tq + (size_t)(p / rows) * Tq + row0 + p % rows) * ldp;
             for (int k = row_vis(16 * w + i) + l; k < L; k += 64) pr_i[k] = (raw_t)0;
+            if constexpr (WIN) {
+                const int e = row_lo(16 * w + i) < L ? row_lo(16 * w + i) : L;
+                for (int k = l; k < e; k += 64) pr_i[k] = (raw_t)0;
+            }
         }
     }
 }
@@ -932,11 +1089,11 @@ constexpr int64_t kLim = (int64_t)1 << 31;
 inline int64_t row_tiles(int64_t Tq, int64_t group) { return (Tq * group + 15) / 16; }
 
 // the qk product of a device-length cache (arguments checked by the entries): MODE kDev writes the dtype, kAtt the fp32 softmax input.
-// x [B, group * Tq, ldx]; group > 1 runs the GRP instances
-template <int MODE>
+// x [B, group * Tq, ldx]; group > 1 runs the GRP instances, WIN (kAtt) those with a first key per row (starts or null, window or 0)
+template <int MODE, bool WIN = false>
 void qk_dev(const void* x, const void* wcodes, const int8_t* wexp, void* out, const int32_t* lens, int64_t B, int64_t heads, int64_t Tq,
             int64_t group, int64_t Kx, int64_t Nout, int64_t ldx, int64_t ldw, int64_t ldwe, int64_t w_bstride, int64_t ldo, int dtype, int block_size, int xm, int wm,
-            float eps_dt, const uint8_t* exp_win, float scale, int causal, hipStream_t s)
+            float eps_dt, const uint8_t* exp_win, float scale, int causal, hipStream_t s, const int32_t* starts = nullptr, int window = 0)
 {
     const int64_t ny = B * row_tiles(Tq, group);
     const unsigned gy = (unsigned)(ny < 65535 ? ny : 65535);
@@ -944,10 +1101,10 @@ void qk_dev(const void* x, const void* wcodes, const int8_t* wexp, void* out, co
         with_dtype(dtype, [&](auto dt) {
             auto go = [&](auto grp) {
                 constexpr int TM = decltype(blk)::value == 64 ? 4 : 2;
-                hipLaunchKernelGGL((k_kv_bmm_dec<decltype(blk)::value, decltype(dt)::value, TM, MODE, decltype(grp)::value>),
+                hipLaunchKernelGGL((k_kv_bmm_dec<decltype(blk)::value, decltype(dt)::value, TM, MODE, decltype(grp)::value, WIN>),
                                    dim3((unsigned)((Nout + 64 * TM - 1) / (64 * TM)), gy), dim3(256), 0, s, x, (const int8_t*)wcodes, wexp, out, (int)B,
                                    (int)Tq, (int)Kx, (int)Nout, (int)ldx, (int)ldw, (int)ldwe, (int)w_bstride, (int)ldo, xm, wm, eps_dt, exp_win, lens,
-                                   (int)heads, scale, causal, (int)group);
+                                   (int)heads, scale, causal, (int)group, starts, window);
             };
             if (group > 1) go(std::true_type{});
             else go(std::false_type{});
@@ -956,11 +1113,12 @@ void qk_dev(const void* x, const void* wcodes, const int8_t* wexp, void* out, co
 }
 
 // the split p v product and its combine pass (arguments checked by the entries).  ATT: x holds fp32 score rows (k_kv_pv_split).
-// x and out hold R = group * Tq rows per head; the combine pass works per row and takes R for its Tq
-template <bool ATT>
+// x and out hold R = group * Tq rows per head; the combine pass works per row and takes R for its Tq.  WIN (ATT): as qk_dev
+template <bool ATT, bool WIN = false>
 int pv_dev(const void* x, const void* wcodes, const int8_t* wexp, void* out, const int32_t* lens, int64_t B, int64_t heads, int64_t Tq,
            int64_t group, int64_t Kx, int64_t D, int64_t ldx, int64_t ldw, int64_t ldwe, int64_t ldo, int dtype, int block_size, int xm, int wm, float eps_dt,
-           const uint8_t* exp_win, void* ws, int64_t chunks_per_split, void* pout, int64_t ldp, int causal, hipStream_t s)
+           const uint8_t* exp_win, void* ws, int64_t chunks_per_split, void* pout, int64_t ldp, int causal, hipStream_t s,
+           const int32_t* starts = nullptr, int window = 0)
 {
     const int64_t nb = (Kx + block_size - 1) / block_size, nch = (Kx + 63) / 64, dg = (D + 63) / 64;
     const int64_t R = group * Tq, gz = B * row_tiles(Tq, group);  // a workgroup per (head, row tile) on the grid's z
@@ -975,10 +1133,10 @@ int pv_dev(const void* x, const void* wcodes, const int8_t* wexp, void* out, con
     with_block(block_size, [&](auto blk) {
         with_dtype(dtype, [&](auto dt) {
             auto go = [&](auto grp) {
-                hipLaunchKernelGGL((k_kv_pv_split<decltype(blk)::value, decltype(dt)::value, ATT, decltype(grp)::value>),
+                hipLaunchKernelGGL((k_kv_pv_split<decltype(blk)::value, decltype(dt)::value, ATT, decltype(grp)::value, WIN>),
                                    dim3((unsigned)dg, (unsigned)slices, (unsigned)gz), dim3(256), 0, s, x, (const int8_t*)wcodes, sums, xexp, lens,
                                    (int)heads, (int)Tq, (int)Kx, (int)D, (int)ldx, (int)ldw, (int)nb, (int)cps, xvec, xm, eps_dt, exp_win, pout,
-                                   (int)ldp, causal, (int)group);
+                                   (int)ldp, causal, (int)group, starts, window);
             };
             if (group > 1) go(std::true_type{});
             else go(std::false_type{});
@@ -1035,6 +1193,92 @@ inline bool att_ptrs_ok(const void* q, const void* k_codes, const void* k_exps, 
            !(reinterpret_cast<uintptr_t>(lens) & 3u) && !(reinterpret_cast<uintptr_t>(p_out) & (dtype == BFPQ_F32 ? 3u : 1u));
 }
 
+// the _win entries: a window of 0 is none, and so is one no length reaches
+inline bool win_values_ok(const int32_t* starts, int64_t window) { return window >= 0 && !(reinterpret_cast<uintptr_t>(starts) & 3u); }
+inline int win_arg(int64_t window) { return window < kLim ? (int)window : 0; }
+
+// bfpq_kv_attend_gqa (win false: starts and window are unread) and bfpq_kv_attend_gqa_win
+int attend_gqa(const void* q, const void* k_codes, const int8_t* k_exps, const void* v_codes, const int8_t* v_exps, void* out, void* p_out,
+               const int32_t* lens, int64_t BH, int64_t heads, int64_t Tq, int64_t group, int64_t D, int64_t max_len, int64_t cap, int64_t ldd,
+               int64_t ldo, int64_t ldp, double scale, int causal, int dtype, int block_size, int x_mant_bits, int w_mant_bits, double epsilon,
+               const uint8_t* exp_win, void* score_ws, int64_t score_ws_bytes, void* sum_ws, int64_t sum_ws_bytes, int64_t chunks_per_split,
+               bool win, const int32_t* starts, int64_t window, void* stream)
+{
+    if (!att_values_ok(dtype, block_size, x_mant_bits, w_mant_bits, BH, heads, Tq, group, chunks_per_split, causal, scale) ||
+        (win && !win_values_ok(starts, window)))
+        return BFPQ_E_ARG;
+    if (BH == 0 || Tq == 0) return 0;
+    const int64_t pitch = (max_len + 3) / 4 * 4, R = Tq * group;
+    if (!att_shapes_ok(block_size, group, D, max_len, cap, ldd, ldo, ldp, p_out, chunks_per_split) || Tq > BFPQ_KV_DEC_MAX_TOKENS ||
+        R * ldo >= kLim || R * pitch >= kLim || (p_out && R * ldp >= kLim) || BH * row_tiles(Tq, group) > 65535)
+        return BFPQ_E_UNSUPPORTED;
+    const int64_t need_s = bfpq_kv_attend_ws_bytes(BH * group, Tq, max_len), need_p = bfpq_kv_dec_ws_bytes(BH * group, Tq, D, max_len, block_size);
+    if (need_s < 0 || need_p < 0 || score_ws_bytes < need_s || sum_ws_bytes < need_p) return BFPQ_E_UNSUPPORTED;
+    if (!att_ptrs_ok(q, k_codes, k_exps, v_codes, v_exps, out, p_out, lens, exp_win, score_ws, dtype) || !sum_ws || !aligned16(sum_ws) ||
+        (reinterpret_cast<uintptr_t>(q) & (dtype == BFPQ_F32 ? 3u : 1u)))
+        return BFPQ_E_ARG;
+    const float eps_dt = bfpq_dev::h_round((float)epsilon, dtype);
+    hipStream_t s = (hipStream_t)stream;
+    auto go = [&](auto w) {
+        constexpr bool WIN = decltype(w)::value;
+        qk_dev<kAtt, WIN>(q, k_codes, k_exps, score_ws, lens, BH, heads, Tq, group, D, max_len, D, ldd, D / block_size, cap, pitch, dtype, block_size,
+                          x_mant_bits, w_mant_bits, eps_dt, exp_win, (float)scale, causal, s, starts, win_arg(window));
+        const int rc = (int)hipGetLastError();
+        if (rc) return rc;
+        return pv_dev<true, WIN>(score_ws, v_codes, v_exps, out, lens, BH, heads, Tq, group, max_len, D, pitch, cap, cap / block_size, ldo, dtype,
+                                 block_size, x_mant_bits, w_mant_bits, eps_dt, exp_win, sum_ws, chunks_per_split, p_out, ldp, causal, s, starts,
+                                 win_arg(window));
+    };
+    return win && (starts || win_arg(window)) ? go(std::true_type{}) : go(std::false_type{});
+}
+
+// bfpq_kv_attend_rows and bfpq_kv_attend_rows_win, likewise
+int attend_rows(const void* q, const void* k_codes, const int8_t* k_exps, const void* v_codes, const int8_t* v_exps, void* out, void* p_out,
+                const int32_t* lens, int64_t BH, int64_t heads, int64_t Tq, int64_t group, int64_t D, int64_t max_len, int64_t cap, int64_t ldd,
+                int64_t ldo, int64_t ldp, double scale, int causal, int dtype, int block_size, int x_mant_bits, int w_mant_bits, double epsilon,
+                const uint8_t* exp_win, void* score_ws, int64_t score_ws_bytes, int64_t chunks_per_split, int64_t row0, int64_t rows, bool win,
+                const int32_t* starts, int64_t window, void* stream)
+{
+    if (!att_values_ok(dtype, block_size, x_mant_bits, w_mant_bits, BH, heads, Tq, group, chunks_per_split, causal, scale) || row0 < 0 || rows < 0 ||
+        row0 > Tq || rows > Tq - row0 || (win && !win_values_ok(starts, window)))
+        return BFPQ_E_ARG;
+    if (BH == 0 || Tq == 0 || rows == 0) return 0;
+    const int64_t pitch = (max_len + 3) / 4 * 4, R = Tq * group, PR = rows * group, nwg = (PR + kRowsWg - 1) / kRowsWg;
+    if (!att_shapes_ok(block_size, group, D, max_len, cap, ldd, ldo, ldp, p_out, chunks_per_split) || D > 16 * kMaxDT || Tq >= kLim || R >= kLim ||
+        BH * nwg >= kLim)
+        return BFPQ_E_UNSUPPORTED;
+    const int64_t need = bfpq_kv_attend_rows_ws_bytes(BH * group, rows, max_len);
+    if (need < 0 || score_ws_bytes < need) return BFPQ_E_UNSUPPORTED;
+    if (!att_ptrs_ok(q, k_codes, k_exps, v_codes, v_exps, out, p_out, lens, exp_win, score_ws, dtype) || !aligned16(q)) return BFPQ_E_ARG;
+    const float eps_dt = bfpq_dev::h_round((float)epsilon, dtype);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t nbd = D / block_size;
+    const size_t lds_qk = (size_t)(2 * 64 * D + 128 * nbd), lds_pv = (size_t)(64 * D + 64 / block_size * D);   // <= 36 KiB at D = 256
+    auto go = [&](auto w) {
+        constexpr bool WIN = decltype(w)::value;
+        with_block(block_size, [&](auto blk) {
+            with_dtype(dtype, [&](auto dt) {
+                hipLaunchKernelGGL((k_kv_qk_rows<decltype(blk)::value, decltype(dt)::value, WIN>), dim3((unsigned)(BH * nwg)), dim3(256), lds_qk, s, q,
+                                   (const int8_t*)k_codes, k_exps, (float*)score_ws, (int)Tq, (int)D, (int)max_len, (int)ldd, (int)cap, (int)pitch,
+                                   x_mant_bits, w_mant_bits, eps_dt, exp_win, lens, (int)heads, (float)scale, causal, (int)group, (int)row0, (int)rows,
+                                   starts, win_arg(window));
+            });
+        });
+        const int rc = (int)hipGetLastError();
+        if (rc) return rc;
+        with_block(block_size, [&](auto blk) {
+            with_dtype(dtype, [&](auto dt) {
+                hipLaunchKernelGGL((k_kv_pv_rows<decltype(blk)::value, decltype(dt)::value, WIN>), dim3((unsigned)(BH * nwg)), dim3(256), lds_pv, s,
+                                   (const float*)score_ws, (const int8_t*)v_codes, v_exps, out, p_out, lens, (int)heads, (int)Tq, (int)max_len, (int)D,
+                                   (int)pitch, (int)cap, (int)(cap / block_size), (int)ldo, (int)ldp, x_mant_bits, w_mant_bits, eps_dt, exp_win, causal,
+                                   (int)group, (int)row0, (int)rows, starts, win_arg(window));
+            });
+        });
+        return (int)hipGetLastError();
+    };
+    return win && (starts || win_arg(window)) ? go(std::true_type{}) : go(std::false_type{});
+}
+
 }  // namespace
 
 extern "C" {
@@ -1086,7 +1330,7 @@ int bfpq_kv_bmm_dec(const void* x, const void* wcodes, const int8_t* wexp, void*
                 hipLaunchKernelGGL((k_kv_bmm_dec<decltype(blk)::value, decltype(dt)::value, TM, kHost>),
                                    dim3((unsigned)((Nout + 64 * TM - 1) / (64 * TM)), gy), dim3(256), 0, s, x, (const int8_t*)wcodes, wexp, out, (int)B,
                                    (int)Tq, (int)Kx, (int)Nout, (int)ldx, (int)ldw, (int)ldwe, (int)w_bstride, (int)ldo, x_mant_bits, w_mant_bits,
-                                   eps_dt, exp_win, nullptr, 1, 1.f, 0, 1);
+                                   eps_dt, exp_win, nullptr, 1, 1.f, 0, 1, nullptr, 0);
             };
             // rows per wave: 64 (32 at the small blocks) of the many cached keys, 16 of V's D columns
             if (family == BFPQ_KV_PV) go(std::integral_constant<int, 1>{});
@@ -1193,25 +1437,20 @@ int bfpq_kv_attend_gqa(const void* q, const void* k_codes, const int8_t* k_exps,
                        int w_mant_bits, double epsilon, const uint8_t* exp_win, void* score_ws, int64_t score_ws_bytes, void* sum_ws,
                        int64_t sum_ws_bytes, int64_t chunks_per_split, void* stream)
 {
-    if (!att_values_ok(dtype, block_size, x_mant_bits, w_mant_bits, BH, heads, Tq, group, chunks_per_split, causal, scale)) return BFPQ_E_ARG;
-    if (BH == 0 || Tq == 0) return 0;
-    const int64_t pitch = (max_len + 3) / 4 * 4, R = Tq * group;
-    if (!att_shapes_ok(block_size, group, D, max_len, cap, ldd, ldo, ldp, p_out, chunks_per_split) || Tq > BFPQ_KV_DEC_MAX_TOKENS ||
-        R * ldo >= kLim || R * pitch >= kLim || (p_out && R * ldp >= kLim) || BH * row_tiles(Tq, group) > 65535)
-        return BFPQ_E_UNSUPPORTED;
-    const int64_t need_s = bfpq_kv_attend_ws_bytes(BH * group, Tq, max_len), need_p = bfpq_kv_dec_ws_bytes(BH * group, Tq, D, max_len, block_size);
-    if (need_s < 0 || need_p < 0 || score_ws_bytes < need_s || sum_ws_bytes < need_p) return BFPQ_E_UNSUPPORTED;
-    if (!att_ptrs_ok(q, k_codes, k_exps, v_codes, v_exps, out, p_out, lens, exp_win, score_ws, dtype) || !sum_ws || !aligned16(sum_ws) ||
-        (reinterpret_cast<uintptr_t>(q) & (dtype == BFPQ_F32 ? 3u : 1u)))
-        return BFPQ_E_ARG;
-    const float eps_dt = bfpq_dev::h_round((float)epsilon, dtype);
-    hipStream_t s = (hipStream_t)stream;
-    qk_dev<kAtt>(q, k_codes, k_exps, score_ws, lens, BH, heads, Tq, group, D, max_len, D, ldd, D / block_size, cap, pitch, dtype, block_size, x_mant_bits,
-                 w_mant_bits, eps_dt, exp_win, (float)scale, causal, s);
-    const int rc = (int)hipGetLastError();
-    if (rc) return rc;
-    return pv_dev<true>(score_ws, v_codes, v_exps, out, lens, BH, heads, Tq, group, max_len, D, pitch, cap, cap / block_size, ldo, dtype, block_size,
-                        x_mant_bits, w_mant_bits, eps_dt, exp_win, sum_ws, chunks_per_split, p_out, ldp, causal, s);
+    return attend_gqa(q, k_codes, k_exps, v_codes, v_exps, out, p_out, lens, BH, heads, Tq, group, D, max_len, cap, ldd, ldo, ldp, scale, causal, dtype,
+                      block_size, x_mant_bits, w_mant_bits, epsilon, exp_win, score_ws, score_ws_bytes, sum_ws, sum_ws_bytes, chunks_per_split,
+                      false, nullptr, 0, stream);
+}
+
+int bfpq_kv_attend_gqa_win(const void* q, const void* k_codes, const int8_t* k_exps, const void* v_codes, const int8_t* v_exps, void* out,
+                           void* p_out, const int32_t* lens, int64_t BH, int64_t heads, int64_t Tq, int64_t group, int64_t D, int64_t max_len,
+                           int64_t cap, int64_t ldd, int64_t ldo, int64_t ldp, double scale, int causal, int dtype, int block_size,
+                           int x_mant_bits, int w_mant_bits, double epsilon, const uint8_t* exp_win, void* score_ws, int64_t score_ws_bytes,
+                           void* sum_ws, int64_t sum_ws_bytes, int64_t chunks_per_split, const int32_t* starts, int64_t window, void* stream)
+{
+    return attend_gqa(q, k_codes, k_exps, v_codes, v_exps, out, p_out, lens, BH, heads, Tq, group, D, max_len, cap, ldd, ldo, ldp, scale, causal, dtype,
+                      block_size, x_mant_bits, w_mant_bits, epsilon, exp_win, score_ws, score_ws_bytes, sum_ws, sum_ws_bytes, chunks_per_split,
+                      true, starts, window, stream);
 }
 
 int bfpq_kv_attend(const void* q, const void* k_codes, const int8_t* k_exps, const void* v_codes, const int8_t* v_exps, void* out, void* p_out,
@@ -1241,39 +1480,22 @@ int bfpq_kv_attend_rows(const void* q, const void* k_codes, const int8_t* k_exps
                         int64_t sum_ws_bytes, int64_t chunks_per_split, int64_t row0, int64_t rows, void* stream)
 {
     (void)sum_ws; (void)sum_ws_bytes;                             // no block sums on this route
-    if (!att_values_ok(dtype, block_size, x_mant_bits, w_mant_bits, BH, heads, Tq, group, chunks_per_split, causal, scale) || row0 < 0 || rows < 0 ||
-        row0 > Tq || rows > Tq - row0)
-        return BFPQ_E_ARG;
-    if (BH == 0 || Tq == 0 || rows == 0) return 0;
-    const int64_t pitch = (max_len + 3) / 4 * 4, R = Tq * group, PR = rows * group, nwg = (PR + kRowsWg - 1) / kRowsWg;
-    if (!att_shapes_ok(block_size, group, D, max_len, cap, ldd, ldo, ldp, p_out, chunks_per_split) || D > 16 * kMaxDT || Tq >= kLim || R >= kLim ||
-        BH * nwg >= kLim)
-        return BFPQ_E_UNSUPPORTED;
-    const int64_t need = bfpq_kv_attend_rows_ws_bytes(BH * group, rows, max_len);
-    if (need < 0 || score_ws_bytes < need) return BFPQ_E_UNSUPPORTED;
-    if (!att_ptrs_ok(q, k_codes, k_exps, v_codes, v_exps, out, p_out, lens, exp_win, score_ws, dtype) || !aligned16(q)) return BFPQ_E_ARG;
-    const float eps_dt = bfpq_dev::h_round((float)epsilon, dtype);
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t nbd = D / block_size;
-    const size_t lds_qk = (size_t)(2 * 64 * D + 128 * nbd), lds_pv = (size_t)(64 * D + 64 / block_size * D);   // <= 36 KiB at D = 256
-    with_block(block_size, [&](auto blk) {
-        with_dtype(dtype, [&](auto dt) {
-            hipLaunchKernelGGL((k_kv_qk_rows<decltype(blk)::value, decltype(dt)::value>), dim3((unsigned)(BH * nwg)), dim3(256), lds_qk, s, q,
-                               (const int8_t*)k_codes, k_exps, (float*)score_ws, (int)Tq, (int)D, (int)max_len, (int)ldd, (int)cap, (int)pitch,
-                               x_mant_bits, w_mant_bits, eps_dt, exp_win, lens, (int)heads, (float)scale, causal, (int)group, (int)row0, (int)rows);
-        });
-    });
-    const int rc = (int)hipGetLastError();
-    if (rc) return rc;
-    with_block(block_size, [&](auto blk) {
-        with_dtype(dtype, [&](auto dt) {
-            hipLaunchKernelGGL((k_kv_pv_rows<decltype(blk)::value, decltype(dt)::value>), dim3((unsigned)(BH * nwg)), dim3(256), lds_pv, s,
-                               (const float*)score_ws, (const int8_t*)v_codes, v_exps, out, p_out, lens, (int)heads, (int)Tq, (int)max_len, (int)D,
-                               (int)pitch, (int)cap, (int)(cap / block_size), (int)ldo, (int)ldp, x_mant_bits, w_mant_bits, eps_dt, exp_win, causal,
-                               (int)group, (int)row0, (int)rows);
-        });
-    });
-    return (int)hipGetLastError();
+    return attend_rows(q, k_codes, k_exps, v_codes, v_exps, out, p_out, lens, BH, heads, Tq, group, D, max_len, cap, ldd, ldo, ldp, scale, causal,
+                       dtype, block_size, x_mant_bits, w_mant_bits, epsilon, exp_win, score_ws, score_ws_bytes, chunks_per_split, row0, rows, false,
+                       nullptr, 0, stream);
+}
+
+int bfpq_kv_attend_rows_win(const void* q, const void* k_codes, const int8_t* k_exps, const void* v_codes, const int8_t* v_exps, void* out,
+                            void* p_out, const int32_t* lens, int64_t BH, int64_t heads, int64_t Tq, int64_t group, int64_t D, int64_t max_len,
+                            int64_t cap, int64_t ldd, int64_t ldo, int64_t ldp, double scale, int causal, int dtype, int block_size,
+                            int x_mant_bits, int w_mant_bits, double epsilon, const uint8_t* exp_win, void* score_ws, int64_t score_ws_bytes,
+                            void* sum_ws, int64_t sum_ws_bytes, int64_t chunks_per_split, int64_t row0, int64_t rows, const int32_t* starts,
+                            int64_t window, void* stream)
+{
+    (void)sum_ws; (void)sum_ws_bytes;
+    return attend_rows(q, k_codes, k_exps, v_codes, v_exps, out, p_out, lens, BH, heads, Tq, group, D, max_len, cap, ldd, ldo, ldp, scale, causal,
+                       dtype, block_size, x_mant_bits, w_mant_bits, epsilon, exp_win, score_ws, score_ws_bytes, chunks_per_split, row0, rows, true,
+                       starts, window, stream);
 }
 
 }  // extern "C"

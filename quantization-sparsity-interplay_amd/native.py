@@ -120,6 +120,10 @@ PROTOTYPES = {
     "bfpq_kv_attend_rows_ws_bytes": (_i64, [_i64, _i64, _i64]),
     "bfpq_kv_attend_rows": (_i32, [_vp] * 8 + [_i64] * 10 + [_dbl, _i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64,
                                    _vp]),
+    "bfpq_kv_attend_gqa_win": (_i32, [_vp] * 8 + [_i64] * 10 + [_dbl, _i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64,
+                                      _vp]),
+    "bfpq_kv_attend_rows_win": (_i32, [_vp] * 8 + [_i64] * 10 + [_dbl, _i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64,
+                                       _vp, _i64, _vp]),
 }
 
 
@@ -1571,14 +1575,28 @@ def kv_attend_ws_bytes(BH, Tq, max_len):
     return n
 
 
+def _kv_window(what, BH, heads, starts, window, dev):
+    """the first-key arguments of the _win entries: (starts or None, window as an int, 0 for none); both absent means the plain entry"""
+    if starts is not None:
+        _kv_int32(what, "starts", starts, BH // heads, dev)
+    if window is None:
+        window = 0
+    elif isinstance(window, bool) or not isinstance(window, int) or window < 1:
+        raise ValueError(f"{what}: window must be None or an int >= 1 (got {window!r})")
+    return starts, window
+
+
 def kv_attend(q, k_codes, k_exps, v_codes, v_exps, lengths, heads, max_len, scale, causal, block_size, mant_bits, epsilon, score_ws, sum_ws,
-              chunks_per_split=0, return_probs=False, group=1):
+              chunks_per_split=0, return_probs=False, group=1, starts=None, window=None):
     """scores, scale, softmax and context of q [BH, Tq, D] against a device-length cache in three launches (bfpq_kv_attend_gqa): returns
     (context [BH, Tq, D], p [BH, Tq, max_len] or None).  score_ws / sum_ws: contiguous uint8 tensors of at least
     kv_attend_ws_bytes(BH, Tq, max_len) / kv_dec_ws_bytes(BH, Tq, D, max_len, block_size) bytes.  Nothing is read back.  group > 1: rows
-    and workspaces as kv_bmm_dec_dev takes them (q, the context and p hold group * Tq rows per cached head; causal goes by the token)."""
+    and workspaces as kv_bmm_dec_dev takes them (q, the context and p hold group * Tq rows per cached head; causal goes by the token).
+    starts (int32 [BH // heads] on the device) and / or window (an int >= 1): the rows see the keys from max(starts[b], what they see
+    minus window) on (bfpq_kv_attend_gqa_win); with neither, the call and its kernels are the ones without."""
     q, BH, R, Tq, D, heads = _kv_rows("kv_attend", q, "q [BH, Tq, D]", group, heads)
     dev = q.device
+    starts, window = _kv_window("kv_attend", BH, heads, starts, window, dev)
     cap, ldd = _kv_cached("kv_attend", BH, D, block_size, k_codes, k_exps, v_codes, v_exps, dev)
     _kv_int32("kv_attend", "lengths", lengths, BH // heads, dev)
     max_len, scale = int(max_len), _kv_scale("kv_attend", scale)
@@ -1587,11 +1605,13 @@ def kv_attend(q, k_codes, k_exps, v_codes, v_exps, lengths, heads, max_len, scal
     with torch.cuda.device(dev):
         out = torch.empty((BH, R, D), dtype=q.dtype, device=dev)
         p = torch.empty((BH, R, max_len), dtype=q.dtype, device=dev) if return_probs else None
-        check(load_library().bfpq_kv_attend_gqa(_ptr(q), _ptr(k_codes), _ptr(k_exps), _ptr(v_codes), _ptr(v_exps), _ptr(out), _ptr(p),
-                                                _ptr(lengths), BH, heads, Tq, group, D, max_len, cap, ldd, D, max_len, scale, int(bool(causal)),
-                                                DTYPE_CODE[q.dtype], int(block_size), int(mant_bits), int(mant_bits), float(epsilon),
-                                                _ptr(exp_window_dev(q.dtype, dev)), _ptr(score_ws), score_bytes, _ptr(sum_ws), sum_bytes,
-                                                int(chunks_per_split), _stream(q)), "bfpq_kv_attend_gqa")
+        args = (_ptr(q), _ptr(k_codes), _ptr(k_exps), _ptr(v_codes), _ptr(v_exps), _ptr(out), _ptr(p), _ptr(lengths), BH, heads, Tq, group, D,
+                max_len, cap, ldd, D, max_len, scale, int(bool(causal)), DTYPE_CODE[q.dtype], int(block_size), int(mant_bits), int(mant_bits),
+                float(epsilon), _ptr(exp_window_dev(q.dtype, dev)), _ptr(score_ws), score_bytes, _ptr(sum_ws), sum_bytes, int(chunks_per_split))
+        if starts is None and not window:
+            check(load_library().bfpq_kv_attend_gqa(*args, _stream(q)), "bfpq_kv_attend_gqa")
+        else:
+            check(load_library().bfpq_kv_attend_gqa_win(*args, _ptr(starts), window, _stream(q)), "bfpq_kv_attend_gqa_win")
     return out, p
 
 
@@ -1607,16 +1627,18 @@ def kv_attend_rows_ws_bytes(BH, P, max_len):
 
 
 def kv_attend_rows(q, k_codes, k_exps, v_codes, v_exps, lengths, heads, max_len, scale, causal, block_size, mant_bits, epsilon, score_ws,
-                   panel_rows, return_probs=False, group=1):
+                   panel_rows, return_probs=False, group=1, starts=None, window=None):
     """kv_attend for any number of query rows (bfpq_kv_attend_rows): q [BH, group * Tq, D] is walked in panels of panel_rows tokens per
     query head, two launches per panel, the panel's fp32 score rows in score_ws (a contiguous uint8 tensor of at least
     kv_attend_rows_ws_bytes(BH * group, min(panel_rows, Tq), max_len) bytes).  Returns (context [BH, group * Tq, D], p
-    [BH, group * Tq, max_len] or None); row for row kv_attend's bits.  Nothing is read back."""
+    [BH, group * Tq, max_len] or None); row for row kv_attend's bits.  Nothing is read back.  starts, window: as kv_attend
+    (bfpq_kv_attend_rows_win)."""
     q, BH, R, Tq, D, heads = _kv_rows("kv_attend_rows", q, "q [BH, Tq, D]", group, heads)
     panel_rows = int(panel_rows)
     if panel_rows < 1:
         raise ValueError(f"kv_attend_rows: panel_rows must be >= 1 (got {panel_rows})")
     dev = q.device
+    starts, window = _kv_window("kv_attend_rows", BH, heads, starts, window, dev)
     cap, ldd = _kv_cached("kv_attend_rows", BH, D, block_size, k_codes, k_exps, v_codes, v_exps, dev)
     _kv_int32("kv_attend_rows", "lengths", lengths, BH // heads, dev)
     max_len, scale = int(max_len), _kv_scale("kv_attend_rows", scale)
@@ -1626,10 +1648,13 @@ def kv_attend_rows(q, k_codes, k_exps, v_codes, v_exps, lengths, heads, max_len,
         p = torch.empty((BH, R, max_len), dtype=q.dtype, device=dev) if return_probs else None
         L, win, stream = load_library(), _ptr(exp_window_dev(q.dtype, dev)), _stream(q)
         for row0 in range(0, Tq, panel_rows):
-            check(L.bfpq_kv_attend_rows(_ptr(q), _ptr(k_codes), _ptr(k_exps), _ptr(v_codes), _ptr(v_exps), _ptr(out), _ptr(p), _ptr(lengths), BH,
-                                        heads, Tq, group, D, max_len, cap, ldd, D, max_len, scale, int(bool(causal)), DTYPE_CODE[q.dtype],
-                                        int(block_size), int(mant_bits), int(mant_bits), float(epsilon), win, _ptr(score_ws), score_bytes,
-                                        None, 0, 0, row0, min(panel_rows, Tq - row0), stream), "bfpq_kv_attend_rows")
+            args = (_ptr(q), _ptr(k_codes), _ptr(k_exps), _ptr(v_codes), _ptr(v_exps), _ptr(out), _ptr(p), _ptr(lengths), BH, heads, Tq, group, D,
+                    max_len, cap, ldd, D, max_len, scale, int(bool(causal)), DTYPE_CODE[q.dtype], int(block_size), int(mant_bits), int(mant_bits),
+                    float(epsilon), win, _ptr(score_ws), score_bytes, None, 0, 0, row0, min(panel_rows, Tq - row0))
+            if starts is None and not window:
+                check(L.bfpq_kv_attend_rows(*args, stream), "bfpq_kv_attend_rows")
+            else:
+                check(L.bfpq_kv_attend_rows_win(*args, _ptr(starts), window, stream), "bfpq_kv_attend_rows_win")
     return out, p
 
 
