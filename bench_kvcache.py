@@ -19,6 +19,9 @@ scores, softmax, context; modeling_gpt2.py:345-348 with :207, 243) on one MI355X
          masked: what a user did before, scores() + torch's mask and softmax + context() (the prompt case: the matmul leg with a windowed
          mask); --case starts_ragged8: the attend leg on the ragged batch with a quarter of each sequence as left padding
          (HBFPKVCache(starts=True)) against full (all block 64),
+  paged  (--case paged_*: a paged cache) the attend leg (paged_gpt2s_b8_s1024, paged_ragged8) or the prompt leg
+         (paged_prompt_*) on HBFPKVCache(page_tokens=P, pages=N) -- P from --page-tokens, N what the batch needs, the sequences' pages
+         interleaved in the pool -- against full: the same step on the cache without pages; the rows also hold both caches' nbytes(),
 and, for the cache alone, the append of a prefill chunk of S tokens.  Method of bench_matmul.py: hipGraph replay, the median of the
 replays, the legs alternating round by round in one process.  (A captured append writes at the captured position: every replay redoes the
 same step, which is what is timed.)  On a tree without the cache the cache columns are null and "cache" says "absent".
@@ -55,8 +58,13 @@ def device_leg(i8, batch, heads, D, lens, k, v, q, dt, dev, iters, rounds, cps, 
     that many heads), window, starts.  hide (the composition only): cache -> the bool mask [B, 1, 1, capacity] of the keys torch hides"""
     import torch
     room = iters * (rounds + 1) + 2                                      # replay_times: two warm-up calls, the capture, rounds + 1 replays
-    cache = i8.kv_cache(batch, heads, D, max(lens) + room, dtype=dt, device=dev, device_lengths=True, chunks_per_split=cps, max_query_rows=1,
-                        **mode)
+    cap = max(lens) + room
+    if mode.get('page_tokens'):                                          # a pool of just the pages the run needs
+        P = mode['page_tokens']
+        cap, mode = -(-cap // P) * P, dict(mode, pages=sum(-(-(n + room) // P) for n in lens))
+    cache = i8.kv_cache(batch, heads, D, cap, dtype=dt, device=dev, device_lengths=True, chunks_per_split=cps, max_query_rows=1, **mode)
+    if mode.get('page_tokens'):
+        reserve_interleaved(cache, [n + room for n in lens])
     t = max(lens) - 1
     cache.append(k[:, :, :t].contiguous(), v[:, :, :t].contiguous(), torch.tensor([n - 1 for n in lens], dtype=torch.int32, device=dev))
     k_new, v_new, scale = k[:, :, -1:].contiguous(), v[:, :, -1:].contiguous(), 1.0 / D ** 0.5
@@ -76,6 +84,13 @@ def device_leg(i8, batch, heads, D, lens, k, v, q, dt, dev, iters, rounds, cps, 
     if attend:
         cache.prepare_attend()
     return cache, (attend_step if attend else step)
+
+
+def reserve_interleaved(cache, tokens):
+    """pages for tokens[b] tokens of every sequence b, a page per sequence at a time: neighbours in a sequence are not neighbours in the pool"""
+    P = cache.page_tokens
+    for n in range(P, max(tokens) + P, P):
+        cache.reserve([min(n, t) for t in tokens])
 
 
 def has_attend(bfp_ops):
@@ -341,6 +356,77 @@ def run_window_prompt(name, iters, rounds, out, only=None):
     _append_rows(out, rows)
 
 
+# name: the decode shape, the ragged batch or the prompt case it pages
+PAGED = {"paged_gpt2s_b8_s1024": "gpt2s_b8_s1024", "paged_ragged8": "ragged8", "paged_prompt_h32_d128_b1_t2048": "prompt_h32_d128_b1_t2048"}
+
+
+def run_paged(name, iters, rounds, out, cps, page_tokens, only=None):
+    """the legs paged and full of a paged case, bf16 and fp32 at block 64 (only: one leg alone, bf16: what a kernel trace is taken from).
+    A decode case: the attend leg of device_leg.  A prompt case: one step = append(prompt) + attend(q, causal=True) on a cache whose
+    lengths the step zeroes first, as run_prompt; the pages stay reserved"""
+    import torch
+    import quantization_sparsity_interplay_amd as bfpq
+    from quantization_sparsity_interplay_amd.bfp import bfp_ops
+    dev = "cuda:0"
+    base = PAGED[name]
+    prompt = base in PROMPT
+    if prompt:
+        batch, heads, kvh, T, D, PR = PROMPT[base]
+        lens, Tq = [T] * batch, T
+    elif base in RAGGED:
+        batch, heads, lens, D = RAGGED[base]
+        kvh, Tq = heads, 1
+    else:
+        batch, heads, S, D = SHAPES[base]
+        lens, kvh, Tq = [S] * batch, heads, 1
+    c = CONFIGS["hbfp8_b64"]
+    scale = 1.0 / D ** 0.5
+    rows = []
+    for dname in DTYPES if only is None else ("bf16",):
+        dt = dict(bf16=torch.bfloat16, fp32=torch.float32)[dname]
+        gen = torch.Generator().manual_seed(1)
+        k, v = (torch.randn(batch, kvh, max(lens), D, generator=gen).to(dt).to(dev) for _ in range(2))
+        q = torch.randn(batch, heads, Tq, D, generator=gen).to(dt).to(dev)
+        i8 = bfp_ops.F_matmul_bfp(matrix_unit='int8', **bfpq.BFPConfig.hbfp(c['mant_bits'] + 1, c['block_size']).to_kwargs())
+        modes = dict(paged=dict(page_tokens=page_tokens), full={})
+        legs = {}
+        with torch.no_grad():
+            for leg, mode in modes.items():
+                if only not in (None, leg):
+                    continue
+                if not prompt:
+                    legs[leg] = device_leg(i8, batch, heads, D, lens, k, v, q, dt, dev, iters, rounds, cps, attend=True, kv_heads=kvh, **mode)
+                    continue
+                if mode:
+                    mode = dict(mode, pages=batch * (T // page_tokens))
+                cache = i8.kv_cache(batch, heads, D, T, dtype=dt, device=dev, device_lengths=True, kv_heads=kvh, prompt_rows=PR, **mode)
+                if mode:
+                    reserve_interleaved(cache, lens)
+                cache.prepare_attend()
+
+                def step(cache=cache):
+                    cache.lengths.zero_()
+                    cache.append(k, v)
+                    return cache.attend(q, scale, causal=True)
+
+                legs[leg] = (cache, step)
+            med, spread = replay_times([step for _, step in legs.values()], iters, rounds)
+        row = dict(shape=name, batch=batch, heads=heads, kv_heads=kvh, lengths=list(lens), head_dim=D, dtype=dname, config="hbfp8_b64", iters=iters,
+                   rounds=rounds, chunks_per_split=cps, page_tokens=page_tokens)
+        ends = set()
+        for (leg, (cache, _)), m, sp in zip(legs.items(), med, spread):
+            assert cache.overflow.item() == 0
+            ends.add(tuple(cache.lengths.tolist()))
+            row.update({f"{leg}_us": m, f"{leg}_min_max_us": sp, f"{leg}_cache_bytes": cache.nbytes()})
+            if cache.pages is not None:
+                row.update(pages=cache.page_count, capacity=cache.capacity)
+        assert len(ends) == 1
+        row["lengths_at_end"] = list(ends.pop())
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    _append_rows(out, rows)
+
+
 def run_attend_only(shape, iters, rounds, out, cps):
     """the attend leg alone, bf16 at block 64: what a kernel trace of one step is taken from (--attend-only)"""
     import torch
@@ -457,7 +543,9 @@ def merge_parent(out, parent_json):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--case", choices=sorted(SHAPES) + sorted(RAGGED) + sorted(GQA) + sorted(PROMPT) + sorted(WINDOW) + sorted(WINDOW_PROMPT) + sorted(STARTS))
+    ap.add_argument("--case", choices=sorted(SHAPES) + sorted(RAGGED) + sorted(GQA) + sorted(PROMPT) + sorted(WINDOW) + sorted(WINDOW_PROMPT) + sorted(STARTS) + sorted(PAGED))
+    ap.add_argument("--page-tokens", type=int, default=64, help="with a paged_* case: tokens per page (a multiple of 64)")
+    ap.add_argument("--paged-leg", choices=("paged", "full"), help="with a paged_* case: that leg alone, bf16 (a kernel trace)")
     ap.add_argument("--window-leg", choices=("window", "starts", "full", "masked"), help="with a window_* / starts_* case: that leg alone, bf16 (a kernel trace)")
     ap.add_argument("--prompt-rows", type=int, help="with a prompt case: the panel size (default: the case's own)")
     ap.add_argument("--prompt-leg", choices=("prompt", "loop16", "matmul"), help="with a prompt case: that leg alone, bf16 (a kernel trace)")
@@ -484,6 +572,8 @@ def main():
     out = os.path.abspath(a.out)
     if a.merge_only:
         return merge_parent(out, a.parent_json)
+    if a.case in PAGED:
+        return run_paged(a.case, min(a.iters, 4) if PAGED[a.case] in PROMPT else a.iters, a.rounds, out, a.chunks_per_split, a.page_tokens, a.paged_leg)
     if a.case in WINDOW or a.case in STARTS:
         return run_window(a.case, a.iters, a.rounds, out, a.chunks_per_split, a.window_leg)
     if a.case in WINDOW_PROMPT:
@@ -501,7 +591,7 @@ def main():
     if os.path.exists(out):
         os.remove(out)
     steps = [f"timeout -k 10 {a.timeout} {sys.executable} {os.path.abspath(__file__)} --case {s} --iters {a.iters} --rounds {a.rounds} --chunks-per-split {a.chunks_per_split} --out {out}"
-             for s in list(SHAPES) + list(RAGGED) + list(GQA) + list(PROMPT) + list(WINDOW) + list(WINDOW_PROMPT) + list(STARTS)]
+             for s in list(SHAPES) + list(RAGGED) + list(GQA) + list(PROMPT) + list(WINDOW) + list(WINDOW_PROMPT) + list(STARTS) + list(PAGED)]
     rc = subprocess.call(" && ".join(steps), shell=True)
     if rc == 0 and a.parent_json:
         merge_parent(out, a.parent_json)

@@ -588,6 +588,50 @@ int bfpq_kv_attend_rows_win(const void* q_dev, const void* k_codes_dev, const in
                             int block_size, int x_mant_bits, int w_mant_bits, double epsilon, const uint8_t* exp_win_dev, void* score_ws_dev,
                             int64_t score_ws_bytes, void* sum_ws_dev, int64_t sum_ws_bytes, int64_t chunks_per_split, int64_t row0, int64_t rows,
                             const int32_t* starts_dev, int64_t window, void* stream);
+/* A paged device-length cache: sequences draw pages of page_tokens tokens from one pool instead of reserving cap tokens each.  The five
+ * entries are bfpq_kv_append_dev, bfpq_kv_lens_advance, bfpq_kv_bmm_dec_gqa, bfpq_kv_attend_gqa and bfpq_kv_attend_rows with, in front of
+ * the stream, page_table_dev -- int32 [sequences, cap / page_tokens] on the device, read at launch and never on the host, entry
+ * [b][s / page_tokens] the page of sequence b's token s, -1 for none -- then page_tokens (a multiple of 64, so a page holds whole token
+ * blocks at every block size and whole 64-key tiles) and pages, the number of pages in the pool.  cap becomes the most tokens one sequence
+ * may hold (cap % page_tokens == 0; bfpq_kv_lens_advance_paged and bfpq_kv_bmm_dec_paged take it as one more argument in front of the
+ * table), and the cache arrays hold pages, a page being page_tokens tokens of all `heads` heads of one sequence:
+ *   k_codes [pages, heads, page_tokens, ldd]   k_exps [pages, heads, page_tokens, D / block_size]
+ *   v_codes [pages, heads, D, page_tokens]     v_exps [pages, heads, D, page_tokens / block_size]
+ * so a page seen through one head is a contiguous head of capacity page_tokens; v_tail stays [BH, block_size, D], per sequence.  On the
+ * same appended tokens every result is, bit for bit, that of the entry each extends on a contiguous cache: only where the bytes lie
+ * changes.  bfpq_kv_append_paged refuses a sequence, as bfpq_kv_append_dev refuses one that would pass `limit`, where a token it would
+ * take has an entry outside 0 .. pages - 1: it is left untouched and overflow_dev[0] set to 1; bfpq_kv_lens_advance_paged leaves its
+ * length by the same rule.  Nothing allocates: the table is the caller's.  The products read the pages of tokens below lens_dev only,
+ * which an append has checked; an entry outside 0 .. pages - 1 met there all the same is clamped into the pool, never dereferenced as
+ * it is.  bfpq_kv_bmm_dec_paged: BFPQ_KV_QK takes w_bstride = page_tokens and Nout = max_len <= cap, BFPQ_KV_PV ldw = page_tokens, ldwe
+ * = page_tokens / block_size and L <= cap.  No first visible key per row here (no starts, no window).  Errors as the entry each
+ * extends; page_tokens not a multiple of 64, cap not a multiple of page_tokens or pages < 1: BFPQ_E_ARG; page_table_dev NULL or not
+ * 4-byte aligned: BFPQ_E_ARG; pages * heads or page_tokens * ldd of 2^31 or more: BFPQ_E_UNSUPPORTED. */
+int bfpq_kv_append_paged(const void* k_new_dev, const void* v_new_dev, void* k_codes_dev, int8_t* k_exps_dev, void* v_codes_dev,
+                         int8_t* v_exps_dev, void* v_tail_dev, const int32_t* lens_dev, const int32_t* counts_dev, int32_t* overflow_dev,
+                         int64_t BH, int64_t heads, int64_t D, int64_t t, int64_t cap, int64_t limit, int64_t ldd, int dtype, int block_size,
+                         int mant_bits, double epsilon, const uint8_t* exp_win_dev, const int32_t* page_table_dev, int64_t page_tokens,
+                         int64_t pages, void* stream);
+int bfpq_kv_lens_advance_paged(int32_t* lens_dev, const int32_t* counts_dev, int64_t B, int64_t t, int64_t limit, int64_t cap,
+                               const int32_t* page_table_dev, int64_t page_tokens, int64_t pages, void* stream);
+int bfpq_kv_bmm_dec_paged(const void* x_dev, const void* wcodes_dev, const int8_t* wexp_dev, void* out_dev, const int32_t* lens_dev, int64_t B,
+                          int64_t heads, int64_t Tq, int64_t group, int64_t Kx, int64_t Nout, int64_t ldx, int64_t ldw, int64_t ldwe,
+                          int64_t w_bstride, int64_t ldo, int family, int dtype, int block_size, int x_mant_bits, int w_mant_bits,
+                          double epsilon, const uint8_t* exp_win_dev, void* ws_dev, int64_t ws_bytes, int64_t chunks_per_split, int64_t cap,
+                          const int32_t* page_table_dev, int64_t page_tokens, int64_t pages, void* stream);
+int bfpq_kv_attend_paged(const void* q_dev, const void* k_codes_dev, const int8_t* k_exps_dev, const void* v_codes_dev, const int8_t* v_exps_dev,
+                         void* out_dev, void* p_dev, const int32_t* lens_dev, int64_t BH, int64_t heads, int64_t Tq, int64_t group, int64_t D,
+                         int64_t max_len, int64_t cap, int64_t ldd, int64_t ldo, int64_t ldp, double scale, int causal, int dtype,
+                         int block_size, int x_mant_bits, int w_mant_bits, double epsilon, const uint8_t* exp_win_dev, void* score_ws_dev,
+                         int64_t score_ws_bytes, void* sum_ws_dev, int64_t sum_ws_bytes, int64_t chunks_per_split,
+                         const int32_t* page_table_dev, int64_t page_tokens, int64_t pages, void* stream);
+int bfpq_kv_attend_rows_paged(const void* q_dev, const void* k_codes_dev, const int8_t* k_exps_dev, const void* v_codes_dev,
+                              const int8_t* v_exps_dev, void* out_dev, void* p_dev, const int32_t* lens_dev, int64_t BH, int64_t heads,
+                              int64_t Tq, int64_t group, int64_t D, int64_t max_len, int64_t cap, int64_t ldd, int64_t ldo, int64_t ldp,
+                              double scale, int causal, int dtype, int block_size, int x_mant_bits, int w_mant_bits, double epsilon,
+                              const uint8_t* exp_win_dev, void* score_ws_dev, int64_t score_ws_bytes, void* sum_ws_dev, int64_t sum_ws_bytes,
+                              int64_t chunks_per_split, int64_t row0, int64_t rows, const int32_t* page_table_dev, int64_t page_tokens,
+                              int64_t pages, void* stream);
 /* ---- 2:4-compressed packed weights (format sp24) and their few-token product on v_smfmac_i32_16x16x64_i8 -------------------------
  * A weight pruned N:M with M = 4, N <= 2 along K (_structured_N_M_sparsity, reference bfp_ops.py:73-91) and quantized to HBFP block 64
  * holds at most 2 non-zero codes per group of 4.  sp24 keeps those two codes and their 2-bit positions, tiled for the decode kernel

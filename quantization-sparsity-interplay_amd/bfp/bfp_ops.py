@@ -1263,7 +1263,7 @@ def _gen_matmul_i8_op(bfp_args, matrix_unit):
 
     def kv_cache(batch, heads, head_dim, capacity, dtype=torch.bfloat16, device='cuda', **mode):
         """an HBFPKVCache under this op's bfp_args; its products count in matmul_stats.cache_calls.  mode: device_lengths=True (and
-        chunks_per_split), kv_heads, prompt_rows, window, starts as HBFPKVCache takes them"""
+        chunks_per_split), kv_heads, prompt_rows, window, starts, page_tokens and pages as HBFPKVCache takes them"""
         return HBFPKVCache(batch, heads, head_dim, capacity, dtype=dtype, stats=stats, **mode, **dict(bfp_args, device=device))
 
     bfp_op.__name__ = fake.__name__
@@ -1394,10 +1394,32 @@ class HBFPKVCache:
     tiles, slices and token blocks below every row's lo are skipped.  Both compose with kv_heads, prompt_rows, max_len, causal,
     return_probs, chunks_per_split and max_query_rows, on both routes of attend().  Only attend() honours them: scores() and
     context() are products, not attention, and stay exactly as they are.  With neither (None, False: the defaults) the cache is the
-    one above in every respect: the same entries, kernels, workspaces and bytes."""
+    one above in every respect: the same entries, kernels, workspaces and bytes.
+
+    page_tokens=P, pages=N (a paged cache; needs device_lengths=True): the sequences draw pages of P tokens (a multiple of
+    64) from one pool of N pages instead of reserving `capacity` tokens each.  `capacity` (a multiple of P) is then the most tokens one
+    sequence may hold, and the buffers hold pages, a page being P tokens of all kv heads of one sequence: k_codes [N, kv_heads, P, ldd],
+    k_exps [N, kv_heads, P, D / block], v_codes [N, kv_heads, D, P], v_exps [N, kv_heads, D, P / block]; v_tail, the one open token
+    block per head, stays per sequence.
+
+        cache.page_table        # int32 [B, capacity / P] on the device, -1: no page; the kernels read it at launch, so a captured step
+                                # follows what is written between replays
+        cache.reserve(tokens)   # an int or B ints: every sequence gets the pages for that many tokens (never fewer than it has).  Host
+                                # lists only -- no read-back -- and one small copy of the changed table rows; RuntimeError, with nothing
+                                # changed, where the pool has too few free pages
+        cache.assign(b, pages)  # reserve() with the caller's choice: these free pages, in this order, become sequence b's next ones
+        cache.release(b)        # sequence b's pages go back to the pool, its table row to -1 and its length to 0; reset() releases all
+        cache.pages_free        # free pages; nbytes() counts the pool, v_tail, the table and the lengths
+
+    append() never allocates: a sequence whose chunk would reach a token without a page is refused as one that would pass `capacity`
+    is -- left untouched, `overflow` raised -- so a captured append stays a captured append.  append(), scores(), context(), attend()
+    on both routes, keys() and values() keep their signatures, and every result is, bit for bit, that of the cache without pages given
+    the same calls: paging changes where the bytes lie, not what they are.  Composes with kv_heads, prompt_rows, max_len, causal and
+    return_probs; with starts or window the constructor raises NotImplementedError (paging under a first visible key is not built)."""
 
     window = None                  # no window, and ...
     starts = None                  # ... no starts, unless the constructor is given them
+    pages = None                   # no pages either: native.KVPages(page_table, P, N, capacity) of a paged cache
 
     @staticmethod
     def prompt_rows_max(batch, heads, capacity):
@@ -1405,7 +1427,8 @@ class HBFPKVCache:
         return ((1 << 31) - 16) // (4 * batch * heads * native.code_pitch(capacity)) // 16 * 16
 
     def __init__(self, batch, heads, head_dim, capacity, dtype=torch.bfloat16, device='cuda', stats=None, device_lengths=False,
-                 chunks_per_split=0, max_query_rows=native.KV_DEC_MAX_TOKENS, kv_heads=None, prompt_rows=0, window=None, starts=False, **bfp_args):
+                 chunks_per_split=0, max_query_rows=native.KV_DEC_MAX_TOKENS, kv_heads=None, prompt_rows=0, window=None, starts=False,
+                 page_tokens=None, pages=None, **bfp_args):
         a = unpack_bfp_args(bfp_args)
         if bfp_args:
             raise TypeError(f"HBFPKVCache: unknown arguments {sorted(bfp_args)}")
@@ -1454,18 +1477,37 @@ class HBFPKVCache:
             raise TypeError(f"HBFPKVCache: starts must be False or True (got {starts!r}); the counts go into cache.starts")
         if starts and not self.device_lengths:
             raise ValueError("HBFPKVCache: starts needs device_lengths=True")
+        if page_tokens is None and pages is not None:
+            raise ValueError("HBFPKVCache: pages needs page_tokens")
+        if page_tokens is not None:
+            for name, v in (("page_tokens", page_tokens), ("pages", pages)):
+                if isinstance(v, bool) or not isinstance(v, int):
+                    raise TypeError(f"HBFPKVCache: {name} must be an int (got {v!r}); a paged cache takes page_tokens=P, pages=N")
+            if page_tokens < 64 or page_tokens % 64:
+                raise ValueError(f"HBFPKVCache: page_tokens must be a multiple of 64 (got {page_tokens})")
+            if pages < 1:
+                raise ValueError(f"HBFPKVCache: pages must be >= 1 (got {pages})")
+            if not self.device_lengths:
+                raise ValueError("HBFPKVCache: page_tokens needs device_lengths=True")
+            if starts or window is not None:
+                raise NotImplementedError("HBFPKVCache: page_tokens with starts=True or window=W is not built: paging under a first "
+                                          "visible key is a later change")
+            if capacity % page_tokens:
+                raise ValueError(f"HBFPKVCache: capacity must be a multiple of page_tokens (got {capacity}, {page_tokens}): the page "
+                                 "table is capacity / page_tokens entries wide")
         self.batch, self.heads, self.head_dim, self.capacity, self.dtype = batch, heads, head_dim, capacity, dtype
         self.kv_heads, self.group = kv_heads, heads // kv_heads  # query head h reads kv head h // group
         self.block, self.mant_bits, self.epsilon = a['block_size'], a['mant_bits'], a['epsilon']
         self.cap = native.code_pitch(capacity)                   # tokens the buffers hold: a multiple of 64 and of the block
-        if not native.kv_ok(head_dim, self.cap, self.block):
+        if not native.kv_ok(head_dim, self.cap, self.block) or (page_tokens and not native.kv_ok(head_dim, page_tokens, self.block)):
             raise ValueError(f"HBFPKVCache: head_dim {head_dim} x capacity {capacity} at block {self.block} is not taken")
         self.stats = stats if stats is not None else MatmulStats()
         self._length = 0
         B, H, D, cap, blk = batch, kv_heads, head_dim, self.cap, self.block
         z = lambda *shape, dt=torch.int8: torch.zeros(shape, dtype=dt, device=device)
-        self.buffers = dict(k_codes=z(B, H, cap, native.code_pitch(D)), k_exps=z(B, H, cap, D // blk), v_codes=z(B, H, D, cap),
-                            v_exps=z(B, H, D, cap // blk), v_tail=z(B, H, blk, D, dt=dtype))
+        HB, hc = (pages, page_tokens) if page_tokens else (B, cap)   # the buffers' leading dimension: the pool's pages, or the sequences
+        self.buffers = dict(k_codes=z(HB, H, hc, native.code_pitch(D)), k_exps=z(HB, H, hc, D // blk), v_codes=z(HB, H, D, hc),
+                            v_exps=z(HB, H, D, hc // blk), v_tail=z(B, H, blk, D, dt=dtype))
         for name, t in self.buffers.items():
             setattr(self, name, t)
         if self.device_lengths:
@@ -1475,6 +1517,88 @@ class HBFPKVCache:
             self._rows_ws = None                                  # the panel's fp32 score rows (prompt_rows): likewise
             if starts:
                 self.starts = z(B, dt=torch.int32)                # the first visible key of every sequence: written by the caller
+            if page_tokens:
+                self.page_tokens, self.page_count = page_tokens, pages
+                self.page_table = torch.full((B, capacity // page_tokens), -1, dtype=torch.int32, device=device)
+                self.pages = native.KVPages(self.page_table, page_tokens, pages, capacity)
+                self._table_host = torch.full((B, capacity // page_tokens), -1, dtype=torch.int32)   # the table as reserve() last wrote it
+                self._owned = [[] for _ in range(B)]              # every sequence's pages, in token order
+                self._free = collections.deque(range(pages))      # taken from the left, returned to the right
+
+    # ---- the pages of a paged cache: host lists, nothing read back ---------------------------------------------------------------
+    def _paged(self, what):
+        if self.pages is None:
+            raise ValueError(f"HBFPKVCache.{what} needs a paged cache (page_tokens=P, pages=N)")
+
+    def _seq(self, what, b):
+        if isinstance(b, bool) or not isinstance(b, int) or not 0 <= b < self.batch:
+            raise ValueError(f"HBFPKVCache.{what}: a sequence index in 0..{self.batch - 1} (got {b!r})")
+
+    def _give(self, grants):
+        """grants {b: pages}: they leave the free list and become the next pages of sequence b; the changed table rows go to the device in
+        one copy.  The caller has checked that every page is free and every row has room"""
+        grants = {b: list(pg) for b, pg in grants.items() if len(pg)}
+        if not grants:
+            return
+        taken = {p for pg in grants.values() for p in pg}
+        self._free = collections.deque(p for p in self._free if p not in taken)
+        for b, pg in grants.items():
+            n = len(self._owned[b])
+            self._table_host[b, n:n + len(pg)] = torch.tensor(pg, dtype=torch.int32)
+            self._owned[b].extend(pg)
+        lo, hi = min(grants), max(grants) + 1
+        self.page_table[lo:hi].copy_(self._table_host[lo:hi])
+
+    @property
+    def pages_free(self):
+        self._paged('pages_free')
+        return len(self._free)
+
+    def reserve(self, tokens):
+        """every sequence gets pages for `tokens` tokens (an int, or one int per sequence); one that has as many keeps what it has.
+        RuntimeError, with the table and the free list as they were, where the pool has too few free pages"""
+        self._paged('reserve')
+        want = list(tokens) if isinstance(tokens, (list, tuple)) else [tokens] * self.batch
+        if len(want) != self.batch or any(isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= self.capacity for n in want):
+            raise ValueError(f"HBFPKVCache.reserve takes an int or {self.batch} ints in 0..{self.capacity} (got {tokens!r})")
+        P = self.page_tokens
+        more = [max(0, (n + P - 1) // P - len(self._owned[b])) for b, n in enumerate(want)]
+        if sum(more) > len(self._free):
+            raise RuntimeError(f"HBFPKVCache.reserve: the pool is exhausted: {sum(more)} pages wanted, {len(self._free)} of "
+                               f"{self.page_count} free")
+        free = list(self._free)
+        grants, at = {}, 0
+        for b, n in enumerate(more):
+            grants[b], at = free[at:at + n], at + n
+        self._give(grants)
+
+    def assign(self, b, pages):
+        """reserve() with the caller's choice of pages: `pages`, distinct free pages of the pool, become sequence b's next ones in this
+        order.  ValueError, with nothing changed, for a page that is not free or a row that has no room"""
+        self._paged('assign')
+        self._seq('assign', b)
+        pages = list(pages)
+        free = set(self._free)
+        if any(isinstance(p, bool) or not isinstance(p, int) for p in pages) or len(set(pages)) != len(pages) or not set(pages) <= free:
+            raise ValueError(f"HBFPKVCache.assign takes distinct free pages of the pool (got {pages!r})")
+        if len(self._owned[b]) + len(pages) > self._table_host.shape[1]:
+            raise ValueError(f"HBFPKVCache.assign: sequence {b} holds {len(self._owned[b])} pages of at most {self._table_host.shape[1]}")
+        self._give({b: pages})
+
+    def release(self, b):
+        """sequence b's pages go back to the pool; its table row becomes -1 and its length 0"""
+        self._paged('release')
+        self._seq('release', b)
+        self._free.extend(self._owned[b])
+        self._owned[b] = []
+        self._table_host[b] = -1
+        self.page_table[b:b + 1].copy_(self._table_host[b:b + 1])
+        self.lengths[b:b + 1].zero_()
+
+    @property
+    def head_cap(self):
+        """tokens of a head of the code buffers: a page's, or all the buffers hold"""
+        return self.cap if self.pages is None else self.page_tokens
 
     @property
     def length(self):
@@ -1494,9 +1618,15 @@ class HBFPKVCache:
         return torch.empty(n, dtype=torch.uint8, device=self.k_codes.device)
 
     def nbytes(self):
-        return sum(t.numel() * t.element_size() for t in self.buffers.values())
+        held = list(self.buffers.values()) + ([self.page_table, self.lengths] if self.pages is not None else [])
+        return sum(t.numel() * t.element_size() for t in held)
 
     def reset(self):
+        if self.pages is not None:
+            self._free.extend(p for own in self._owned for p in own)
+            self._owned = [[] for _ in range(self.batch)]
+            self._table_host.fill_(-1)
+            self.page_table.fill_(-1)
         if self.device_lengths:
             self.lengths.zero_()
             self.overflow.zero_()
@@ -1548,7 +1678,7 @@ class HBFPKVCache:
                                        or counts.device != self.k_codes.device or not counts.is_contiguous()):
                 raise ValueError(f"HBFPKVCache.append: counts must be a contiguous int32 tensor [{self.batch}] on {self.k_codes.device}")
             native.kv_append_dev(k.contiguous(), v.contiguous(), self.k_codes, self.k_exps, self.v_codes, self.v_exps, self.v_tail, self.lengths,
-                                 counts, self.overflow, self.kv_heads, self.capacity, self.block, self.mant_bits, self.epsilon)
+                                 counts, self.overflow, self.kv_heads, self.capacity, self.block, self.mant_bits, self.epsilon, pages=self.pages)
             return None
         if self.length + t > self.capacity:
             raise ValueError(f"HBFPKVCache.append: {self.length} + {t} tokens exceed the capacity {self.capacity}")
@@ -1573,8 +1703,8 @@ class HBFPKVCache:
             n = self.capacity if max_len is None else max_len
             if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= self.capacity:
                 raise ValueError(f"HBFPKVCache.scores: max_len must be an int in 1..{self.capacity} (got {max_len!r})")
-            out = native.kv_bmm_dec_dev(x, self.k_codes, self.k_exps, native.KV_QK, n, self.cap, self.lengths, self.kv_heads, self.block,
-                                        self.mant_bits, self.epsilon, group=self.group)
+            out = native.kv_bmm_dec_dev(x, self.k_codes, self.k_exps, native.KV_QK, n, self.head_cap, self.lengths, self.kv_heads, self.block,
+                                        self.mant_bits, self.epsilon, group=self.group, pages=self.pages)
             self.stats.cache_calls += 1
             return self._result(out, Tq)
         S, D, BH, R, m = self.length, self.head_dim, x.shape[0], x.shape[1], self.mant_bits   # R = group * Tq rows per kv head
@@ -1604,7 +1734,7 @@ class HBFPKVCache:
                 raise ValueError(f"HBFPKVCache.context: {Tq} query rows, the workspace was made for max_query_rows={self.max_query_rows}")
             out = native.kv_bmm_dec_dev(x, self.v_codes, self.v_exps, native.KV_PV, self.head_dim, self.head_dim, self.lengths, self.kv_heads,
                                         self.block, self.mant_bits, self.epsilon, ws=self._ws, chunks_per_split=self.chunks_per_split,
-                                        group=self.group)
+                                        group=self.group, pages=self.pages)
             self.stats.cache_calls += 1
             return self._result(out, Tq)
         if not isinstance(p, torch.Tensor) or p.dim() != 4 or p.shape[-1] != self.length or self.length < 1:
@@ -1660,14 +1790,15 @@ class HBFPKVCache:
         if panels:
             out, p = native.kv_attend_rows(x, self.k_codes, self.k_exps, self.v_codes, self.v_exps, self.lengths, self.kv_heads, n, float(scale),
                                            bool(causal), self.block, self.mant_bits, self.epsilon, self._rows_ws, self.prompt_rows,
-                                           return_probs=bool(return_probs), group=self.group, starts=self.starts, window=self.window)
+                                           return_probs=bool(return_probs), group=self.group, starts=self.starts, window=self.window,
+                                           pages=self.pages)
             self.stats.cache_calls += 2
             out = self._result(out, Tq)
             return (out, self._result(p, Tq)) if return_probs else out
         out, p = native.kv_attend(x, self.k_codes, self.k_exps, self.v_codes, self.v_exps, self.lengths, self.kv_heads, n, float(scale),
                                   bool(causal), self.block, self.mant_bits, self.epsilon, self._att_ws, self._ws,
                                   chunks_per_split=self.chunks_per_split, return_probs=bool(return_probs), group=self.group,
-                                  starts=self.starts, window=self.window)
+                                  starts=self.starts, window=self.window, pages=self.pages)
         self.stats.cache_calls += 2
         out = self._result(out, Tq)
         return (out, self._result(p, Tq)) if return_probs else out
@@ -1682,10 +1813,24 @@ class HBFPKVCache:
             raise ValueError(f"HBFPKVCache.keys / values: device_lengths=True takes a sequence index in 0..{self.batch - 1} (got {b!r})")
         return b, 1, int(self.lengths[b].item())
 
+    def _gathered(self, buf, b, S, axis):
+        """a paged buffer [N, kv_heads, .., ..] as sequence b's contiguous heads [kv_heads, .., ..], the pages of its first S tokens
+        (the table row read back, as lengths[b] was) side by side along `axis`, the one the tokens run along"""
+        n = (S + self.page_tokens - 1) // self.page_tokens
+        idx = self.page_table[b, :n].to(torch.int64).clamp_(0, self.page_count - 1)
+        t = buf[idx]                                              # [n, kv_heads, a, b]
+        if axis == 2:
+            return t.permute(1, 0, 2, 3).reshape(self.kv_heads, n * t.shape[2], t.shape[3])
+        return t.permute(1, 2, 0, 3).reshape(self.kv_heads, t.shape[2], n * t.shape[3])
+
     def keys(self, b=None):
         """the cached keys dequantized, [B, kv_heads, S, D]; with device_lengths those of sequence b, [1, kv_heads, lengths[b], D]"""
         b0, nb, S = self._held(b)
         BH, D = nb * self.kv_heads, self.head_dim
+        if self.pages is not None:
+            kc, ke = (self._gathered(t, b, S, 2) for t in (self.k_codes, self.k_exps))   # [kv_heads, tokens, .]
+            c, e = kc[:, :S, :D].reshape(BH * S, D), ke[:, :S].reshape(BH * S, D // self.block)
+            return native.dequantize(c, e, D, self.dtype, self.block, self.mant_bits, 8).view(nb, self.kv_heads, S, D)
         c = self.k_codes[b0:b0 + nb].view(BH, self.cap, -1)[:, :S, :D].reshape(BH * S, D)
         e = self.k_exps[b0:b0 + nb].view(BH, self.cap, -1)[:, :S].reshape(BH * S, D // self.block)
         return native.dequantize(c, e, D, self.dtype, self.block, self.mant_bits, 8).view(nb, self.kv_heads, S, D)
@@ -1695,8 +1840,12 @@ class HBFPKVCache:
         b0, nb, S = self._held(b)
         BH, D, blk = nb * self.kv_heads, self.head_dim, self.block
         Sp = (S + blk - 1) // blk * blk
-        c = self.v_codes[b0:b0 + nb].view(BH * D, self.cap)[:, :Sp].contiguous()
-        e = self.v_exps[b0:b0 + nb].view(BH * D, -1)[:, :Sp // blk].contiguous()
+        if self.pages is not None:
+            c = self._gathered(self.v_codes, b, S, 3).reshape(BH * D, -1)[:, :Sp].contiguous()
+            e = self._gathered(self.v_exps, b, S, 3).reshape(BH * D, -1)[:, :Sp // blk].contiguous()
+        else:
+            c = self.v_codes[b0:b0 + nb].view(BH * D, self.cap)[:, :Sp].contiguous()
+            e = self.v_exps[b0:b0 + nb].view(BH * D, -1)[:, :Sp // blk].contiguous()
         v = native.dequantize(c, e, Sp, self.dtype, blk, self.mant_bits, 8)[:, :S]
         return v.reshape(nb, self.kv_heads, D, S).transpose(-1, -2)
 

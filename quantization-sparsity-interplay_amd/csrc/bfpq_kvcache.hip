@@ -54,6 +54,14 @@
 // the first key -- the bits of the row with -inf there -- and the kernels skip the key tiles, slices and token blocks below every first
 // key of a tile, a wave or a workgroup, a skipped block of p leaving the term of a zero block.  The instances without WIN never read
 // `starts` and `window` and are the code they were.
+//
+// A paged cache: the PG instances behind the bfpq_kv_*_paged entries.  The four code and exponent tensors are a pool of
+// pages -- a page: P tokens (a multiple of 64) of all kv heads of one sequence, so seen through one kv head a contiguous head of
+// capacity P -- and sequence b's token s lies in page page_table[b][s / P].  The kernels get P for `cap` and take the head's base from
+// head_at, the one copy of the lookup; tiles, chunks and token blocks never straddle a page, so the entry is fetched once per unit
+// (head_tile: as a scalar) and the next unit's ahead of this unit's loads.  v_tail stays per sequence.  An entry outside the pool is
+// refused by the append (seq_take_at) and clamped by head_at; it is never dereferenced.  The instances without PG never read the
+// descriptor and are the code they were.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "bfpq.h"
@@ -79,6 +87,46 @@ __device__ __forceinline__ void load_exp_win(uint8_t* s_win, const uint8_t* __re
 
 // the tokens a head of `len` contracts over, or the keys it has, where the caller reaches L of them
 __device__ __forceinline__ int clamp_len(int len, int L) { return len < L ? (len > 0 ? len : 0) : L; }
+
+// ---- a paged cache: the cache tensors are a pool of pages, a page being `tokens` consecutive tokens of all `heads` kv heads
+// of one sequence, and sequence b's token s lies in page table[b][s / tokens].  The PG instances take the head's base from head_at; the
+// others never read the descriptor and are the code they were
+struct Pages {
+    const int32_t* table;                                     // page_table [sequences, width] int32, read at launch; -1: no page
+    int width, tokens, count;                                 // entries per sequence, tokens per page (a multiple of 64), pages in the pool
+};
+
+// sequence b's table entry e as it stands (e clamped into the row)
+__device__ __forceinline__ int page_entry(const Pages& pg, int b, int e)
+{
+    return pg.table[(size_t)b * pg.width + (e < pg.width ? (e > 0 ? e : 0) : pg.width - 1)];
+}
+__device__ __forceinline__ bool page_ok(const Pages& pg, int p) { return p >= 0 && p < pg.count; }
+
+// head_at: where token s of head bh (kv head bh % heads of sequence bh / heads) lies -- the head of capacity `tokens` that holds it (a
+// page seen through one kv head) and, in sl, its token there.  Without PG: the head itself and s.  The only copy of the lookup: an entry
+// outside 0 .. count - 1 is clamped into the pool before use (append refuses such a token and the products walk tokens below the
+// length only, so this guards a table the caller corrupted)
+template <bool PG> __device__ __forceinline__ int head_at(const Pages& pg, int bh, int heads, int s, int& sl)
+{
+    if constexpr (!PG) {
+        sl = s;
+        return bh;
+    } else {
+        const int b = bh / heads, e = s / pg.tokens;             // (one division each: the remainders by a multiplication)
+        const int p = page_entry(pg, b, e);
+        sl = s - e * pg.tokens;
+        return (p < 0 ? 0 : (p < pg.count ? p : pg.count - 1)) * heads + (bh - b * heads);
+    }
+}
+
+// head_at for a wave whose lanes ask for one (head, token): a 64-key tile, a slice's chunk, a token block -- none straddles a page.  The
+// entry is fetched once, as a scalar
+template <bool PG> __device__ __forceinline__ int head_tile(const Pages& pg, int bh, int heads, int s, int& sl)
+{
+    if constexpr (!PG) return head_at<false>(pg, bh, heads, s, sl);
+    else return head_at<true>(pg, __builtin_amdgcn_readfirstlane(bh), heads, __builtin_amdgcn_readfirstlane(s), sl);
+}
 
 // the magnitude maximum of a lane's raw elements
 template <int DT, int NE> __device__ __forceinline__ uint32_t abs_max(const uint32_t (&xv)[NE])
@@ -107,10 +155,11 @@ __device__ __forceinline__ typename I8Blk<BLK>::op_t quant_operand(const uint32_
 }
 
 // one token block tb of one 64-column slice of V
-template <int DT>
+template <int DT, bool PG>
 __device__ __forceinline__ void v_block(const typename Traits<DT>::raw_t* __restrict__ vnew, typename Traits<DT>::raw_t* __restrict__ tail,
                                         int8_t* __restrict__ vcodes, int8_t* __restrict__ vexps, int bh, int tb, int d0, int D, int pos, int t,
-                                        int tn, int cap, int block, int mant_bits, float eps_dt, const uint8_t* s_win, uint32_t* s_val, uint32_t* s_max)
+                                        int tn, int cap, int block, int mant_bits, float eps_dt, const uint8_t* s_win, uint32_t* s_val, uint32_t* s_max,
+                                        const Pages& pg, int heads)
 {
     using Tr = Traits<DT>;
     constexpr int VEC = Tr::VEC, LPR = kTD / VEC, RPP = 256 / LPR;
@@ -151,12 +200,19 @@ __device__ __forceinline__ void v_block(const typename Traits<DT>::raw_t* __rest
     const BlockScale bs = block_scale<DT>(mx, mant_bits, eps_dt, s_win);
     uint32_t pk[4];
     pack_codes<DT>(raw, per, bs, pk);
+    size_t hb = bh;                                                       // the head the block's codes lie in, and the block there
+    int tbl = tb;
+    if constexpr (PG) {                                                   // (the block's page: cap is the page's tokens)
+        int sl;
+        hb = head_tile<true>(pg, bh, heads, tb * block, sl);
+        tbl = sl / block;
+    }
     if (d0 + d < D) {
-        int8_t* const dst = vcodes + ((size_t)bh * D + d0 + d) * cap + tb * block + sq * per;
+        int8_t* const dst = vcodes + (hb * D + d0 + d) * cap + tbl * block + sq * per;
         if (per == 16) *reinterpret_cast<uint4*>(dst) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
         else if (per == 8) *reinterpret_cast<uint2*>(dst) = make_uint2(pk[0], pk[1]);
         else *reinterpret_cast<uint32_t*>(dst) = pk[0];
-        if (sq == 0) vexps[((size_t)bh * D + d0 + d) * (cap / block) + tb] = sat_exp(bs);
+        if (sq == 0) vexps[(hb * D + d0 + d) * (cap / block) + tbl] = sat_exp(bs);
     }
 }
 
@@ -169,16 +225,32 @@ __device__ __forceinline__ int seq_take(const int32_t* __restrict__ lens, const 
     return (n < 0 || n > t || pos < 0 || pos > limit || n > limit - pos) ? -1 : n;
 }
 
+// seq_take on a paged cache: a sequence is refused as well where one of the tokens it would take has no page
+template <bool PG>
+__device__ __forceinline__ int seq_take_at(const Pages& pg, const int32_t* __restrict__ lens, const int32_t* __restrict__ counts, int b, int t,
+                                           int limit, int& pos)
+{
+    int n = seq_take(lens, counts, b, t, limit, pos);
+    if constexpr (PG) {
+        if (n > 0)
+            for (int e = pos / pg.tokens, last = (pos + n - 1) / pg.tokens; e <= last; e++)
+                if (!page_ok(pg, page_entry(pg, b, e))) n = -1;
+    }
+    return n;
+}
+
 // DEV: the position and the count of head bh are those of its sequence bh / heads, read from device memory (lens, counts or null); t is
 // then the row pitch of k_new / v_new and the most a sequence can take, and the grid is sized for the worst position
-template <int DT, bool DEV>
+// PG (DEV only): cap is a page's tokens and a token's rows lie where head_at says
+template <int DT, bool DEV, bool PG = false>
 __global__ void __launch_bounds__(256) k_kv_append(const void* __restrict__ knew, const void* __restrict__ vnew, int8_t* __restrict__ kcodes,
                                                    int8_t* __restrict__ kexps, int8_t* __restrict__ vcodes, int8_t* __restrict__ vexps,
                                                    void* __restrict__ vtail, int BH, int D, int pos, int t, int cap, int ldd, int block,
                                                    int mant_bits, float eps_dt, const uint8_t* __restrict__ exp_win, int nkb, int zc,
                                                    const int32_t* __restrict__ lens, const int32_t* __restrict__ counts,
-                                                   int32_t* __restrict__ overflow, int heads, int limit)
+                                                   int32_t* __restrict__ overflow, int heads, int limit, Pages pg)
 {
+    static_assert(!PG || DEV, "a paged cache keeps its lengths on the device");
     using Tr = Traits<DT>;
     using raw_t = typename Tr::raw_t;
     __shared__ uint8_t s_win[BFPQ_EXP_WIN_ENTRIES];
@@ -199,7 +271,7 @@ __global__ void __launch_bounds__(256) k_kv_append(const void* __restrict__ knew
         const int bh = (int)(row / t), i = (int)(row % t);
         bool live = valid;
         if constexpr (DEV) {
-            const int n = seq_take(lens, counts, bh / heads, t, limit, pos);
+            const int n = seq_take_at<PG>(pg, lens, counts, bh / heads, t, limit, pos);
             if (n < 0 && valid && i == 0 && seg == 0) overflow[0] = 1;
             live = valid && i < n;                                        // (one row: the lanes of a block are live together)
         }
@@ -214,7 +286,11 @@ __global__ void __launch_bounds__(256) k_kv_append(const void* __restrict__ knew
         uint32_t pk[4];
         pack_codes<DT>(raw, 16, bs, pk);
         if (live) {
-            const size_t r = (size_t)bh * cap + pos + i;
+            size_t r = (size_t)bh * cap + pos + i;
+            if constexpr (PG) {
+                int sl;
+                r = (size_t)head_at<true>(pg, bh, heads, pos + i, sl) * cap + sl;
+            }
             *reinterpret_cast<uint4*>(kcodes + r * ldd + seg * 16) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
             if (seg % per == 0) kexps[r * (D / block) + seg / per] = sat_exp(bs);
         }
@@ -226,7 +302,7 @@ __global__ void __launch_bounds__(256) k_kv_append(const void* __restrict__ knew
     const int z = vb % zc, dt = (vb / zc) % dtiles, bh = vb / (zc * dtiles);
     int cnt = t;
     if constexpr (DEV) {
-        cnt = seq_take(lens, counts, bh / heads, t, limit, pos);
+        cnt = seq_take_at<PG>(pg, lens, counts, bh / heads, t, limit, pos);
         if (cnt <= 0) return;                                             // (the whole workgroup: nothing to take, or refused)
     }
     const int first = pos / block, last = (pos + cnt - 1) / block;
@@ -234,8 +310,8 @@ __global__ void __launch_bounds__(256) k_kv_append(const void* __restrict__ knew
     const int n = (z == 0 && last != first) ? 2 : 1;
     for (int it = 0; it < n; it++) {
         if (it) __syncthreads();                                          // (the first block's tile and tail rows have been read)
-        v_block<DT>(reinterpret_cast<const raw_t*>(vnew), reinterpret_cast<raw_t*>(vtail), vcodes, vexps, bh, it ? last : first + z, dt * kTD, D,
-                    pos, cnt, t, cap, block, mant_bits, eps_dt, s_win, s_val, s_max);
+        v_block<DT, PG>(reinterpret_cast<const raw_t*>(vnew), reinterpret_cast<raw_t*>(vtail), vcodes, vexps, bh, it ? last : first + z, dt * kTD, D,
+                        pos, cnt, t, cap, block, mant_bits, eps_dt, s_win, s_val, s_max, pg, heads);
     }
 }
 
@@ -303,18 +379,21 @@ template <int DT, bool WIN = false> __device__ __forceinline__ void att_scores(v
 // 16 TM keys lie below the first key of all 16 rows of the tile skips the product and stores nothing: the softmax never reads there.
 // The WIN instances of block 64 are held to the 2 waves per SIMD of their plain twins (without the bound they take 241-243 VGPRs + 16
 // AGPRs and run 1)
-template <int BLK, int DT, int TM, int MODE, bool GRP = false, bool WIN = false>
+// PG (family qk of a paged cache; not with WIN): wbs is a page's tokens; the 16 TM <= 64 keys of a wave lie in one page, whose head
+// (head_tile) gives the base of the wave's codes and exponents, its rows counted from the page's first token
+template <int BLK, int DT, int TM, int MODE, bool GRP = false, bool WIN = false, bool PG = false>
 __global__ void __launch_bounds__(256, WIN && BLK == 64 ? 2 : 1) k_kv_bmm_dec(const void* __restrict__ x, const int8_t* __restrict__ wc, const int8_t* __restrict__ we,
                                                     void* __restrict__ out, int B, int Tq, int Kx, int Nout, int ldx, int ldw, int ldwe, int wbs,
                                                     int ldo, int xm, int wm, float eps_dt, const uint8_t* __restrict__ exp_win,
                                                     const int32_t* __restrict__ lens, int heads, float scale, int causal, int group,
-                                                    const int32_t* __restrict__ starts, int window)
+                                                    const int32_t* __restrict__ starts, int window, Pages pg)
 {
     using Blk = I8Blk<BLK>;
     using op_t = typename Blk::op_t;
     using Tr = Traits<DT>;
     using raw_t = typename Tr::raw_t;
     static_assert(!WIN || MODE == kAtt, "a first key is attention's");
+    static_assert(!PG || (MODE != kHost && !WIN), "a paged cache keeps its lengths on the device and has no first key");
     constexpr bool DEV = MODE != kHost;
     constexpr int ODT = MODE == kAtt ? BFPQ_F32 : DT;            // the output's element type
     constexpr int NBS = 64 / BLK;                                // blocks per 64-byte chunk
@@ -327,17 +406,18 @@ __global__ void __launch_bounds__(256, WIN && BLK == 64 ? 2 : 1) k_kv_bmm_dec(co
     if (n0 >= Nout) return;                                      // (wave-uniform; no barrier below)
     const int nb = (Kx + BLK - 1) / BLK, nch = (Kx + 63) >> 6;
     const int R = GRP ? Tq * group : Tq, ntiles = GRP ? (R + 15) >> 4 : 1;
+    const int pt0 = PG ? n0 - n0 % pg.tokens : 0;                // (PG) the first token of the page of the wave's keys
 
     uint32_t offW[TM], ewo[TM][4];
     auto rows = [&](int No) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < TM; i++) {
             const int n = n0 + 16 * i + r;
-            offW[i] = (uint32_t)(n < No ? n : No - 1) * (uint32_t)ldw + Blk::lane(q);
+            offW[i] = (uint32_t)((n < No ? n : No - 1) - pt0) * (uint32_t)ldw + Blk::lane(q);
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const int ne = n0 + 16 * i + 4 * q + j;
-                ewo[i][j] = (uint32_t)(ne < No ? ne : No - 1) * (uint32_t)ldwe;
+                ewo[i][j] = (uint32_t)((ne < No ? ne : No - 1) - pt0) * (uint32_t)ldwe;
             }
         }
     };
@@ -348,6 +428,11 @@ __global__ void __launch_bounds__(256, WIN && BLK == 64 ? 2 : 1) k_kv_bmm_dec(co
     for (int y = blockIdx.y; y < B * ntiles; y += gridDim.y) {
         const int b = GRP ? y / ntiles : y, row = GRP ? (y % ntiles) * 16 + r : r;   // the head, and the lane's row of it
         const bool tok = row < R;
+        size_t hb = b;                                            // the head the wave's codes lie in
+        if constexpr (PG) {                                      // (the page of the wave's keys: fetched beside the length)
+            int sl;
+            hb = head_tile<true>(pg, b, heads, n0, sl);
+        }
         int No = Nout, len = 0;
         if constexpr (DEV) {
             len = lens[b / heads];
@@ -369,8 +454,8 @@ __global__ void __launch_bounds__(256, WIN && BLK == 64 ? 2 : 1) k_kv_bmm_dec(co
         if constexpr (WIN) {
             if (n0 + 16 * TM <= wave_min(tok ? first() : 0x7fffffff)) continue;   // (wave-uniform) no row of the tile sees a key of this wave
         }
-        const int8_t* const wcb = wc + (size_t)b * wbs * ldw;
-        const int8_t* const web = we + (size_t)b * wbs * ldwe;
+        const int8_t* const wcb = wc + hb * wbs * ldw;
+        const int8_t* const web = we + hb * wbs * ldwe;
         const raw_t* const xr = reinterpret_cast<const raw_t*>(x) + ((size_t)b * R + (tok ? row : 0)) * ldx;
 
         // chunk c: the lane's w codes, the exponents of its four output rows (byte s of a word = block s of the chunk) and its x elements
@@ -624,14 +709,18 @@ __device__ __forceinline__ void form_p(const float* __restrict__ srow, int k0, i
     }
 }
 
-template <int BLK, int DT, bool ATT, bool GRP = false, bool WIN = false>
+//
+// PG (not with WIN): cap is a page's tokens; a 64-token chunk lies in one page, whose head is fetched once per chunk (head_tile), the
+// next chunk's ahead of this chunk's loads.
+template <int BLK, int DT, bool ATT, bool GRP = false, bool WIN = false, bool PG = false>
 __global__ void __launch_bounds__(256) k_kv_pv_split(const void* __restrict__ x, const int8_t* __restrict__ vc, int32_t* __restrict__ sums,
                                                      int8_t* __restrict__ xexp, const int32_t* __restrict__ lens, int heads, int Tq, int L,
                                                      int D, int ldx, int cap, int nbw, int cps, int xvec, int xm, float eps_dt,
                                                      const uint8_t* __restrict__ exp_win, void* __restrict__ pout, int ldp, int causal,
-                                                     int group, const int32_t* __restrict__ starts, int window)
+                                                     int group, const int32_t* __restrict__ starts, int window, Pages pg)
 {
     static_assert(!WIN || ATT, "a first key is attention's");
+    static_assert(!PG || !WIN, "a paged cache has no first key");
     using Blk = I8Blk<BLK>;
     using op_t = typename Blk::op_t;
     using Tr = Traits<DT>;
@@ -645,6 +734,8 @@ __global__ void __launch_bounds__(256) k_kv_pv_split(const void* __restrict__ x,
     const int bh = GRP ? (int)blockIdx.z / ntiles : (int)blockIdx.z, c0 = (int)blockIdx.y * cps;
     const int r0 = GRP ? ((int)blockIdx.z % ntiles) * 16 : 0, nr = GRP ? (R - r0 < 16 ? R - r0 : 16) : Tq;   // the tile's first row, its rows
     auto token = [&](int i) __attribute__((always_inline)) { return GRP ? (r0 + i) % Tq : i; };               // of the tile's row i
+    int hbN = 0, slN = 0;                                        // (PG) the head and the first token of the chunk to come: the slice's first,
+    if constexpr (PG) hbN = head_tile<true>(pg, bh, heads, c0 << 6, slN);   // fetched beside the length
     const int len = lens[bh / heads];
     const int Kx = clamp_len(len, L);
     const int w = threadIdx.x >> 6, l = threadIdx.x & 63, r = l & 15, q = l >> 4;
@@ -728,11 +819,16 @@ __global__ void __launch_bounds__(256) k_kv_pv_split(const void* __restrict__ x,
     const v4i magic = {MAGIC_I, MAGIC_I, MAGIC_I, MAGIC_I};
     const size_t o0 = ((size_t)bh * R + r0 + (tok ? r : 0)) * nbw;
     for (int c = c0; c < c1; c++) {
+        const int8_t* wch = wrow + (c << 6);                     // the lane's codes of the chunk
+        if constexpr (PG) {
+            wch = vc + ((size_t)hbN * D + n0 + r) * cap + slN + Blk::lane(q);
+            if (c + 1 < c1) hbN = head_tile<true>(pg, bh, heads, (c + 1) << 6, slN);
+        }
 #pragma unroll
         for (int s = 0; s < NBS; s++) {
             const int j = c * NBS + s;
             if (j >= nb) break;                                  // (wave-uniform)
-            op_t aF = *reinterpret_cast<const op_t*>(wrow + (c << 6) + s * BLK);
+            op_t aF = *reinterpret_cast<const op_t*>(wch + s * BLK);
             if (!Blk::a_live(q)) aF = op_t{};
             const v4i d = Blk::mfma(aF, s_b[c - c0][s][l], magic);
             if (tok) {
@@ -743,11 +839,12 @@ __global__ void __launch_bounds__(256) k_kv_pv_split(const void* __restrict__ x,
     }
 }
 
-template <int DT>
+// PG: V's exponents of block j lie in the page of its tokens (head_at: per thread, a thread being a row of a head), ldve a page's blocks
+template <int DT, bool PG = false>
 __global__ void __launch_bounds__(256) k_kv_pv_combine(const int32_t* __restrict__ sums, const int8_t* __restrict__ xexp,
                                                        const int8_t* __restrict__ ve, void* __restrict__ out, const int32_t* __restrict__ lens,
                                                        int heads, int64_t total, int Tq, int L, int D, int ldve, int nbw, int ldo, int block,
-                                                       int xm, int wm)
+                                                       int xm, int wm, Pages pg)
 {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= total) return;
@@ -770,8 +867,16 @@ __global__ void __launch_bounds__(256) k_kv_pv_combine(const int32_t* __restrict
             const int j = j0 + u < nb ? j0 + u : nb - 1;
             d[u] = *reinterpret_cast<const v4i*>(sr + (size_t)j * D);
             ex[u] = (int)xe[j];
+            if constexpr (PG) {
+                int sl;
+                const int hb = head_at<true>(pg, bh, heads, j * block, sl);
+                const int8_t* const wej = ve + ((size_t)hb * D + n) * ldve + (sl >> (__ffs(block) - 1));   // (block: a power of two)
 #pragma unroll
-            for (int i = 0; i < 4; i++) ew[u][i] = (int)we[i * ldve + j];
+                for (int i = 0; i < 4; i++) ew[u][i] = (int)wej[i * ldve];
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; i++) ew[u][i] = (int)we[i * ldve + j];
+            }
         }
 #pragma unroll
         for (int u = 0; u < kCU; u++) {
@@ -787,12 +892,14 @@ __global__ void __launch_bounds__(256) k_kv_pv_combine(const int32_t* __restrict
 }
 
 // lens[b] += what sequence b took of the chunk (seq_take: nothing where it was refused); after k_kv_append<.., true> in stream order
-__global__ void __launch_bounds__(256) k_kv_advance(int32_t* __restrict__ lens, const int32_t* __restrict__ counts, int B, int t, int limit)
+// (PG: seq_take_at, so a sequence refused for a missing page stays where it is)
+template <bool PG = false>
+__global__ void __launch_bounds__(256) k_kv_advance(int32_t* __restrict__ lens, const int32_t* __restrict__ counts, int B, int t, int limit, Pages pg)
 {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
     int pos;
-    const int n = seq_take(lens, counts, b, t, limit, pos);
+    const int n = seq_take_at<PG>(pg, lens, counts, b, t, limit, pos);
     if (n > 0) lens[b] = pos + n;
 }
 
@@ -828,13 +935,16 @@ template <int BLK> struct LdsOp {
 // block order, the epilogue is att_scores; only the columns below the wave's visible length are written, which is all the softmax reads.
 // WIN: rows have a first key (att_first).  The loop starts at the tile of the workgroup's least first key (range_first) and a wave sits
 // out the tiles below its own rows' least; those columns are not written and the softmax does not read them.
-template <int BLK, int DT, bool WIN = false>
+// PG (not with WIN): cap is a page's tokens; a tile of 64 keys lies in one page, whose head is fetched once per tile (head_tile), the
+// next tile's ahead of this tile's loads.
+template <int BLK, int DT, bool WIN = false, bool PG = false>
 __global__ void __launch_bounds__(256) k_kv_qk_rows(const void* __restrict__ x, const int8_t* __restrict__ kc, const int8_t* __restrict__ ke,
                                                     float* __restrict__ ws, int Tq, int D, int Nout, int ldd, int cap, int pitch, int xm, int wm,
                                                     float eps_dt, const uint8_t* __restrict__ exp_win, const int32_t* __restrict__ lens, int heads,
                                                     float scale, int causal, int group, int row0, int rows, const int32_t* __restrict__ starts,
-                                                    int window)
+                                                    int window, Pages pg)
 {
+    static_assert(!PG || !WIN, "a paged cache has no first key");
     using Blk = I8Blk<BLK>;
     using op_t = typename Blk::op_t;
     using Tr = Traits<DT>;
@@ -886,10 +996,16 @@ __global__ void __launch_bounds__(256) k_kv_qk_rows(const void* __restrict__ x, 
     const int lo = WIN ? att_first(len, Tq, t, causal, start, window) : 0;
     float* const orow = ws + ((size_t)b * PR + (tok ? pr : pr0)) * pitch;
     const int nkt = (vwg + 63) >> 6;
+    int hbN = 0, slN = 0;                                        // (PG) the head and the first key of the tile to come
+    if constexpr (PG) hbN = head_tile<true>(pg, b, heads, 0, slN);
     for (int kt = WIN ? lwg >> 6 : 0; kt < nkt; kt++) {
         __syncthreads();                                         // (s_q, s_qe written; the tile before this one read)
-        const int8_t* const kcb = kc + ((size_t)b * cap + (kt << 6)) * ldd;
-        const int8_t* const keb = ke + ((size_t)b * cap + (kt << 6)) * nbd;
+        const size_t k0 = PG ? (size_t)hbN * cap + slN : (size_t)b * cap + (kt << 6);   // the tile's first row of the codes and exponents
+        if constexpr (PG) {
+            if (kt + 1 < nkt) hbN = head_tile<true>(pg, b, heads, (kt + 1) << 6, slN);
+        }
+        const int8_t* const kcb = kc + k0 * ldd;
+        const int8_t* const keb = ke + k0 * nbd;
         for (int idx = tid; idx < 4 * nbd * LN; idx += 256) {    // idx = (16-key tile i, block j, lane slot)
             const int ls = idx % LN, j = (idx / LN) % nbd, i = idx / (LN * nbd);
             s_k[idx] = *reinterpret_cast<const op_t*>(kcb + (size_t)(16 * i + (ls & 15)) * ldd + j * BLK + Blk::lane(ls >> 4));
@@ -936,13 +1052,16 @@ __global__ void __launch_bounds__(256) k_kv_qk_rows(const void* __restrict__ x, 
 // WIN: rows have a first key (att_first).  The blocks below the least first key of the wave's rows (j < jstart) get the same zero-block
 // term, in block order before the first block the wave forms p for, and the chunks start at the workgroup's first seen one; p is zero
 // below a row's first key too.
-template <int BLK, int DT, bool WIN = false>
+// PG (not with WIN): cap is a page's tokens and ldve its blocks; a 64-token chunk lies in one page, whose head is fetched once per chunk
+// (head_tile), the next chunk's ahead of this chunk's loads; the zero-block terms look up the page of their block.
+template <int BLK, int DT, bool WIN = false, bool PG = false>
 __global__ void __launch_bounds__(256) k_kv_pv_rows(const float* __restrict__ ws, const int8_t* __restrict__ vc, const int8_t* __restrict__ ve,
                                                     void* __restrict__ out, void* __restrict__ pout, const int32_t* __restrict__ lens, int heads,
                                                     int Tq, int L, int D, int pitch, int cap, int ldve, int ldo, int ldp, int xm, int wm,
                                                     float eps_dt, const uint8_t* __restrict__ exp_win, int causal, int group, int row0, int rows,
-                                                    const int32_t* __restrict__ starts, int window)
+                                                    const int32_t* __restrict__ starts, int window, Pages pg)
 {
+    static_assert(!PG || !WIN, "a paged cache has no first key");
     using Blk = I8Blk<BLK>;
     using op_t = typename Blk::op_t;
     using Tr = Traits<DT>;
@@ -958,6 +1077,8 @@ __global__ void __launch_bounds__(256) k_kv_pv_rows(const float* __restrict__ ws
     const int PR = group * rows, nwg = (PR + kRowsWg - 1) / kRowsWg;
     const int bh = (int)blockIdx.x / nwg, pr0 = ((int)blockIdx.x % nwg) * kRowsWg;
     const int nrw = PR - pr0 < kRowsWg ? PR - pr0 : kRowsWg;      // the workgroup's rows
+    int hbN = 0, slN = 0;                                        // (PG) the head and the first token of the chunk to come: the first,
+    if constexpr (PG) hbN = head_tile<true>(pg, bh, heads, 0, slN);   // fetched beside the length
     const int len = lens[bh / heads];
     const int Kx = clamp_len(len, L);
     auto row_vis = [&](int i) __attribute__((always_inline)) { return att_visible(len, Kx, Tq, row0 + (pr0 + i) % rows, causal); };
@@ -1015,13 +1136,24 @@ __global__ void __launch_bounds__(256) k_kv_pv_rows(const float* __restrict__ ws
     }
     for (int c = WIN ? cfirst : 0; c < nchw; c++) {
         __syncthreads();                                         // (the chunk before this one read)
-        for (int idx = tid; idx < ndt * NBS * LN; idx += 256) {  // idx = (16-column tile i, block s of the chunk, lane slot)
-            const int ls = idx % LN, s = (idx / LN) % NBS, i = idx / (LN * NBS);
-            s_v[idx] = *reinterpret_cast<const op_t*>(vc + ((size_t)bh * D + 16 * i + (ls & 15)) * cap + (c << 6) + s * BLK + Blk::lane(ls >> 4));
-        }
-        for (int idx = tid; idx < NBS * D; idx += 256) {
-            const int j = c * NBS + idx / D;
-            s_ve[idx] = j < nb ? ve[((size_t)bh * D + idx % D) * ldve + j] : (int8_t)0;
+        if constexpr (PG) {
+            const int hb = hbN, t0 = slN;                        // the chunk's head and its first token there
+            if (c + 1 < nchw) hbN = head_tile<true>(pg, bh, heads, (c + 1) << 6, slN);
+            for (int idx = tid; idx < ndt * NBS * LN; idx += 256) {
+                const int ls = idx % LN, s = (idx / LN) % NBS, i = idx / (LN * NBS);
+                s_v[idx] = *reinterpret_cast<const op_t*>(vc + ((size_t)hb * D + 16 * i + (ls & 15)) * cap + t0 + s * BLK + Blk::lane(ls >> 4));
+            }
+            for (int idx = tid; idx < NBS * D; idx += 256)
+                s_ve[idx] = c * NBS + idx / D < nb ? ve[((size_t)hb * D + idx % D) * ldve + t0 / BLK + idx / D] : (int8_t)0;
+        } else {
+            for (int idx = tid; idx < ndt * NBS * LN; idx += 256) {  // idx = (16-column tile i, block s of the chunk, lane slot)
+                const int ls = idx % LN, s = (idx / LN) % NBS, i = idx / (LN * NBS);
+                s_v[idx] = *reinterpret_cast<const op_t*>(vc + ((size_t)bh * D + 16 * i + (ls & 15)) * cap + (c << 6) + s * BLK + Blk::lane(ls >> 4));
+            }
+            for (int idx = tid; idx < NBS * D; idx += 256) {
+                const int j = c * NBS + idx / D;
+                s_ve[idx] = j < nb ? ve[((size_t)bh * D + idx % D) * ldve + j] : (int8_t)0;
+            }
         }
         __syncthreads();
 #pragma unroll
@@ -1054,10 +1186,17 @@ __global__ void __launch_bounds__(256) k_kv_pv_rows(const float* __restrict__ ws
         v2f sx, nm;
         token_scale((int)sat_exp(bs), xm, sx, nm);
         for (int j = jstop; j < nb; j++) {
+            size_t hb = bh;                                      // the head the block's exponents lie in, and the block there
+            int jl = j;
+            if constexpr (PG) {
+                int sl;
+                hb = head_tile<true>(pg, bh, heads, j * BLK, sl);
+                jl = sl / BLK;
+            }
 #pragma unroll
             for (int i = 0; i < kMaxDT; i++) {
                 if (i < ndt) {
-                    const int8_t* const we = ve + ((size_t)bh * D + 16 * i + 4 * q) * ldve + j;
+                    const int8_t* const we = ve + (hb * D + 16 * i + 4 * q) * ldve + jl;
                     v2f sw01, sw23;
                     weight_scales((int)we[0], (int)we[ldve], (int)we[2 * ldve], (int)we[3 * ldve], wm, sw01, sw23);
                     rescale(magic, sx, nm, sw01, sw23, acc[i][0], acc[i][1]);
@@ -1090,35 +1229,40 @@ inline int64_t row_tiles(int64_t Tq, int64_t group) { return (Tq * group + 15) /
 
 // the qk product of a device-length cache (arguments checked by the entries): MODE kDev writes the dtype, kAtt the fp32 softmax input.
 // x [B, group * Tq, ldx]; group > 1 runs the GRP instances, WIN (kAtt) those with a first key per row (starts or null, window or 0)
+// pages (or null; not with WIN): the PG instances, w_bstride then a page's tokens
 template <int MODE, bool WIN = false>
 void qk_dev(const void* x, const void* wcodes, const int8_t* wexp, void* out, const int32_t* lens, int64_t B, int64_t heads, int64_t Tq,
             int64_t group, int64_t Kx, int64_t Nout, int64_t ldx, int64_t ldw, int64_t ldwe, int64_t w_bstride, int64_t ldo, int dtype, int block_size, int xm, int wm,
-            float eps_dt, const uint8_t* exp_win, float scale, int causal, hipStream_t s, const int32_t* starts = nullptr, int window = 0)
+            float eps_dt, const uint8_t* exp_win, float scale, int causal, hipStream_t s, const int32_t* starts = nullptr, int window = 0,
+            const Pages* pages = nullptr)
 {
     const int64_t ny = B * row_tiles(Tq, group);
     const unsigned gy = (unsigned)(ny < 65535 ? ny : 65535);
     with_block(block_size, [&](auto blk) {
         with_dtype(dtype, [&](auto dt) {
-            auto go = [&](auto grp) {
+            auto go = [&](auto grp, auto paged) {
                 constexpr int TM = decltype(blk)::value == 64 ? 4 : 2;
-                hipLaunchKernelGGL((k_kv_bmm_dec<decltype(blk)::value, decltype(dt)::value, TM, MODE, decltype(grp)::value, WIN>),
+                constexpr bool PG = decltype(paged)::value;
+                hipLaunchKernelGGL((k_kv_bmm_dec<decltype(blk)::value, decltype(dt)::value, TM, MODE, decltype(grp)::value, WIN && !PG, PG>),
                                    dim3((unsigned)((Nout + 64 * TM - 1) / (64 * TM)), gy), dim3(256), 0, s, x, (const int8_t*)wcodes, wexp, out, (int)B,
                                    (int)Tq, (int)Kx, (int)Nout, (int)ldx, (int)ldw, (int)ldwe, (int)w_bstride, (int)ldo, xm, wm, eps_dt, exp_win, lens,
-                                   (int)heads, scale, causal, (int)group, starts, window);
+                                   (int)heads, scale, causal, (int)group, starts, window, PG ? *pages : Pages{});
             };
-            if (group > 1) go(std::true_type{});
-            else go(std::false_type{});
+            if (pages) group > 1 ? go(std::true_type{}, std::true_type{}) : go(std::false_type{}, std::true_type{});
+            else if (group > 1) go(std::true_type{}, std::false_type{});
+            else go(std::false_type{}, std::false_type{});
         });
     });
 }
 
 // the split p v product and its combine pass (arguments checked by the entries).  ATT: x holds fp32 score rows (k_kv_pv_split).
 // x and out hold R = group * Tq rows per head; the combine pass works per row and takes R for its Tq.  WIN (ATT): as qk_dev
+// pages (or null; not with WIN): the PG instances, ldw then a page's tokens and ldwe its blocks
 template <bool ATT, bool WIN = false>
 int pv_dev(const void* x, const void* wcodes, const int8_t* wexp, void* out, const int32_t* lens, int64_t B, int64_t heads, int64_t Tq,
            int64_t group, int64_t Kx, int64_t D, int64_t ldx, int64_t ldw, int64_t ldwe, int64_t ldo, int dtype, int block_size, int xm, int wm, float eps_dt,
            const uint8_t* exp_win, void* ws, int64_t chunks_per_split, void* pout, int64_t ldp, int causal, hipStream_t s,
-           const int32_t* starts = nullptr, int window = 0)
+           const int32_t* starts = nullptr, int window = 0, const Pages* pages = nullptr)
 {
     const int64_t nb = (Kx + block_size - 1) / block_size, nch = (Kx + 63) / 64, dg = (D + 63) / 64;
     const int64_t R = group * Tq, gz = B * row_tiles(Tq, group);  // a workgroup per (head, row tile) on the grid's z
@@ -1132,22 +1276,29 @@ int pv_dev(const void* x, const void* wcodes, const int8_t* wexp, void* out, con
     const int xvec = !ATT && (reinterpret_cast<uintptr_t>(x) & 15u) == 0 && (ldx * bfpq_dev::dtype_size(dtype)) % 16 == 0;
     with_block(block_size, [&](auto blk) {
         with_dtype(dtype, [&](auto dt) {
-            auto go = [&](auto grp) {
-                hipLaunchKernelGGL((k_kv_pv_split<decltype(blk)::value, decltype(dt)::value, ATT, decltype(grp)::value, WIN>),
+            auto go = [&](auto grp, auto paged) {
+                constexpr bool PG = decltype(paged)::value;
+                hipLaunchKernelGGL((k_kv_pv_split<decltype(blk)::value, decltype(dt)::value, ATT, decltype(grp)::value, WIN && !PG, PG>),
                                    dim3((unsigned)dg, (unsigned)slices, (unsigned)gz), dim3(256), 0, s, x, (const int8_t*)wcodes, sums, xexp, lens,
                                    (int)heads, (int)Tq, (int)Kx, (int)D, (int)ldx, (int)ldw, (int)nb, (int)cps, xvec, xm, eps_dt, exp_win, pout,
-                                   (int)ldp, causal, (int)group, starts, window);
+                                   (int)ldp, causal, (int)group, starts, window, PG ? *pages : Pages{});
             };
-            if (group > 1) go(std::true_type{});
-            else go(std::false_type{});
+            if (pages) group > 1 ? go(std::true_type{}, std::true_type{}) : go(std::false_type{}, std::true_type{});
+            else if (group > 1) go(std::true_type{}, std::false_type{});
+            else go(std::false_type{}, std::false_type{});
         });
     });
     const int rc = (int)hipGetLastError();
     if (rc) return rc;
     const int64_t total = B * R * (D / 4);
     with_dtype(dtype, [&](auto dt) {
-        hipLaunchKernelGGL((k_kv_pv_combine<decltype(dt)::value>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, sums, xexp, wexp, out, lens,
-                           (int)heads, total, (int)R, (int)Kx, (int)D, (int)ldwe, (int)nb, (int)ldo, block_size, xm, wm);
+        auto go = [&](auto paged) {
+            constexpr bool PG = decltype(paged)::value;
+            hipLaunchKernelGGL((k_kv_pv_combine<decltype(dt)::value, PG>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, sums, xexp, wexp, out,
+                               lens, (int)heads, total, (int)R, (int)Kx, (int)D, (int)ldwe, (int)nb, (int)ldo, block_size, xm, wm, PG ? *pages : Pages{});
+        };
+        if (pages) go(std::true_type{});
+        else go(std::false_type{});
     });
     return (int)hipGetLastError();
 }
@@ -1197,37 +1348,55 @@ inline bool att_ptrs_ok(const void* q, const void* k_codes, const void* k_exps, 
 inline bool win_values_ok(const int32_t* starts, int64_t window) { return window >= 0 && !(reinterpret_cast<uintptr_t>(starts) & 3u); }
 inline int win_arg(int64_t window) { return window < kLim ? (int)window : 0; }
 
+// the _paged entries: cap is the most tokens of a sequence, the table cap / page_tokens entries wide; the cache tensors hold
+// `pages` pages of `heads` heads of page_tokens tokens.  The values (BFPQ_E_ARG), the sizes (BFPQ_E_UNSUPPORTED), the table (BFPQ_E_ARG)
+inline bool pages_values_ok(int64_t page_tokens, int64_t pages, int64_t cap)
+{
+    return page_tokens >= 64 && page_tokens % 64 == 0 && pages >= 1 && cap >= page_tokens && cap % page_tokens == 0;
+}
+inline bool pages_shapes_ok(int64_t page_tokens, int64_t pages, int64_t heads, int64_t D, int64_t ldd, int block_size)
+{
+    return bfpq_kv_ok(D, page_tokens, block_size) && page_tokens * ldd < kLim && pages * heads < kLim;
+}
+inline bool pages_ptr_ok(const int32_t* table) { return table && !(reinterpret_cast<uintptr_t>(table) & 3u); }
+inline Pages pages_arg(const int32_t* table, int64_t page_tokens, int64_t pages, int64_t cap)
+{
+    return Pages{table, (int)(cap / page_tokens), (int)page_tokens, (int)pages};
+}
+
 // bfpq_kv_attend_gqa (win false: starts and window are unread) and bfpq_kv_attend_gqa_win
 int attend_gqa(const void* q, const void* k_codes, const int8_t* k_exps, const void* v_codes, const int8_t* v_exps, void* out, void* p_out,
                const int32_t* lens, int64_t BH, int64_t heads, int64_t Tq, int64_t group, int64_t D, int64_t max_len, int64_t cap, int64_t ldd,
                int64_t ldo, int64_t ldp, double scale, int causal, int dtype, int block_size, int x_mant_bits, int w_mant_bits, double epsilon,
                const uint8_t* exp_win, void* score_ws, int64_t score_ws_bytes, void* sum_ws, int64_t sum_ws_bytes, int64_t chunks_per_split,
-               bool win, const int32_t* starts, int64_t window, void* stream)
+               bool win, const int32_t* starts, int64_t window, void* stream, const Pages* pages = nullptr)
 {
     if (!att_values_ok(dtype, block_size, x_mant_bits, w_mant_bits, BH, heads, Tq, group, chunks_per_split, causal, scale) ||
-        (win && !win_values_ok(starts, window)))
+        (win && !win_values_ok(starts, window)) || (pages && !pages_values_ok(pages->tokens, pages->count, cap)))
         return BFPQ_E_ARG;
     if (BH == 0 || Tq == 0) return 0;
     const int64_t pitch = (max_len + 3) / 4 * 4, R = Tq * group;
+    const int64_t hcap = pages ? pages->tokens : cap;             // tokens of a head of the cache tensors
     if (!att_shapes_ok(block_size, group, D, max_len, cap, ldd, ldo, ldp, p_out, chunks_per_split) || Tq > BFPQ_KV_DEC_MAX_TOKENS ||
-        R * ldo >= kLim || R * pitch >= kLim || (p_out && R * ldp >= kLim) || BH * row_tiles(Tq, group) > 65535)
+        R * ldo >= kLim || R * pitch >= kLim || (p_out && R * ldp >= kLim) || BH * row_tiles(Tq, group) > 65535 ||
+        (pages && !pages_shapes_ok(pages->tokens, pages->count, heads, D, ldd, block_size)))
         return BFPQ_E_UNSUPPORTED;
     const int64_t need_s = bfpq_kv_attend_ws_bytes(BH * group, Tq, max_len), need_p = bfpq_kv_dec_ws_bytes(BH * group, Tq, D, max_len, block_size);
     if (need_s < 0 || need_p < 0 || score_ws_bytes < need_s || sum_ws_bytes < need_p) return BFPQ_E_UNSUPPORTED;
     if (!att_ptrs_ok(q, k_codes, k_exps, v_codes, v_exps, out, p_out, lens, exp_win, score_ws, dtype) || !sum_ws || !aligned16(sum_ws) ||
-        (reinterpret_cast<uintptr_t>(q) & (dtype == BFPQ_F32 ? 3u : 1u)))
+        (reinterpret_cast<uintptr_t>(q) & (dtype == BFPQ_F32 ? 3u : 1u)) || (pages && !pages_ptr_ok(pages->table)))
         return BFPQ_E_ARG;
     const float eps_dt = bfpq_dev::h_round((float)epsilon, dtype);
     hipStream_t s = (hipStream_t)stream;
     auto go = [&](auto w) {
         constexpr bool WIN = decltype(w)::value;
-        qk_dev<kAtt, WIN>(q, k_codes, k_exps, score_ws, lens, BH, heads, Tq, group, D, max_len, D, ldd, D / block_size, cap, pitch, dtype, block_size,
-                          x_mant_bits, w_mant_bits, eps_dt, exp_win, (float)scale, causal, s, starts, win_arg(window));
+        qk_dev<kAtt, WIN>(q, k_codes, k_exps, score_ws, lens, BH, heads, Tq, group, D, max_len, D, ldd, D / block_size, hcap, pitch, dtype, block_size,
+                          x_mant_bits, w_mant_bits, eps_dt, exp_win, (float)scale, causal, s, starts, win_arg(window), pages);
         const int rc = (int)hipGetLastError();
         if (rc) return rc;
-        return pv_dev<true, WIN>(score_ws, v_codes, v_exps, out, lens, BH, heads, Tq, group, max_len, D, pitch, cap, cap / block_size, ldo, dtype,
+        return pv_dev<true, WIN>(score_ws, v_codes, v_exps, out, lens, BH, heads, Tq, group, max_len, D, pitch, hcap, hcap / block_size, ldo, dtype,
                                  block_size, x_mant_bits, w_mant_bits, eps_dt, exp_win, sum_ws, chunks_per_split, p_out, ldp, causal, s, starts,
-                                 win_arg(window));
+                                 win_arg(window), pages);
     };
     return win && (starts || win_arg(window)) ? go(std::true_type{}) : go(std::false_type{});
 }
@@ -1237,46 +1406,49 @@ int attend_rows(const void* q, const void* k_codes, const int8_t* k_exps, const 
                 const int32_t* lens, int64_t BH, int64_t heads, int64_t Tq, int64_t group, int64_t D, int64_t max_len, int64_t cap, int64_t ldd,
                 int64_t ldo, int64_t ldp, double scale, int causal, int dtype, int block_size, int x_mant_bits, int w_mant_bits, double epsilon,
                 const uint8_t* exp_win, void* score_ws, int64_t score_ws_bytes, int64_t chunks_per_split, int64_t row0, int64_t rows, bool win,
-                const int32_t* starts, int64_t window, void* stream)
+                const int32_t* starts, int64_t window, void* stream, const Pages* pages = nullptr)
 {
     if (!att_values_ok(dtype, block_size, x_mant_bits, w_mant_bits, BH, heads, Tq, group, chunks_per_split, causal, scale) || row0 < 0 || rows < 0 ||
-        row0 > Tq || rows > Tq - row0 || (win && !win_values_ok(starts, window)))
+        row0 > Tq || rows > Tq - row0 || (win && !win_values_ok(starts, window)) || (pages && !pages_values_ok(pages->tokens, pages->count, cap)))
         return BFPQ_E_ARG;
     if (BH == 0 || Tq == 0 || rows == 0) return 0;
     const int64_t pitch = (max_len + 3) / 4 * 4, R = Tq * group, PR = rows * group, nwg = (PR + kRowsWg - 1) / kRowsWg;
     if (!att_shapes_ok(block_size, group, D, max_len, cap, ldd, ldo, ldp, p_out, chunks_per_split) || D > 16 * kMaxDT || Tq >= kLim || R >= kLim ||
-        BH * nwg >= kLim)
+        BH * nwg >= kLim || (pages && !pages_shapes_ok(pages->tokens, pages->count, heads, D, ldd, block_size)))
         return BFPQ_E_UNSUPPORTED;
     const int64_t need = bfpq_kv_attend_rows_ws_bytes(BH * group, rows, max_len);
     if (need < 0 || score_ws_bytes < need) return BFPQ_E_UNSUPPORTED;
-    if (!att_ptrs_ok(q, k_codes, k_exps, v_codes, v_exps, out, p_out, lens, exp_win, score_ws, dtype) || !aligned16(q)) return BFPQ_E_ARG;
+    if (!att_ptrs_ok(q, k_codes, k_exps, v_codes, v_exps, out, p_out, lens, exp_win, score_ws, dtype) || !aligned16(q) ||
+        (pages && !pages_ptr_ok(pages->table)))
+        return BFPQ_E_ARG;
     const float eps_dt = bfpq_dev::h_round((float)epsilon, dtype);
     hipStream_t s = (hipStream_t)stream;
-    const int64_t nbd = D / block_size;
+    const int64_t nbd = D / block_size, hcap = pages ? pages->tokens : cap;   // (hcap: tokens of a head of the cache tensors)
     const size_t lds_qk = (size_t)(2 * 64 * D + 128 * nbd), lds_pv = (size_t)(64 * D + 64 / block_size * D);   // <= 36 KiB at D = 256
-    auto go = [&](auto w) {
-        constexpr bool WIN = decltype(w)::value;
+    auto go = [&](auto w, auto paged) {
+        constexpr bool WIN = decltype(w)::value, PG = decltype(paged)::value;
         with_block(block_size, [&](auto blk) {
             with_dtype(dtype, [&](auto dt) {
-                hipLaunchKernelGGL((k_kv_qk_rows<decltype(blk)::value, decltype(dt)::value, WIN>), dim3((unsigned)(BH * nwg)), dim3(256), lds_qk, s, q,
-                                   (const int8_t*)k_codes, k_exps, (float*)score_ws, (int)Tq, (int)D, (int)max_len, (int)ldd, (int)cap, (int)pitch,
+                hipLaunchKernelGGL((k_kv_qk_rows<decltype(blk)::value, decltype(dt)::value, WIN, PG>), dim3((unsigned)(BH * nwg)), dim3(256), lds_qk, s,
+                                   q, (const int8_t*)k_codes, k_exps, (float*)score_ws, (int)Tq, (int)D, (int)max_len, (int)ldd, (int)hcap, (int)pitch,
                                    x_mant_bits, w_mant_bits, eps_dt, exp_win, lens, (int)heads, (float)scale, causal, (int)group, (int)row0, (int)rows,
-                                   starts, win_arg(window));
+                                   starts, win_arg(window), PG ? *pages : Pages{});
             });
         });
         const int rc = (int)hipGetLastError();
         if (rc) return rc;
         with_block(block_size, [&](auto blk) {
             with_dtype(dtype, [&](auto dt) {
-                hipLaunchKernelGGL((k_kv_pv_rows<decltype(blk)::value, decltype(dt)::value, WIN>), dim3((unsigned)(BH * nwg)), dim3(256), lds_pv, s,
+                hipLaunchKernelGGL((k_kv_pv_rows<decltype(blk)::value, decltype(dt)::value, WIN, PG>), dim3((unsigned)(BH * nwg)), dim3(256), lds_pv, s,
                                    (const float*)score_ws, (const int8_t*)v_codes, v_exps, out, p_out, lens, (int)heads, (int)Tq, (int)max_len, (int)D,
-                                   (int)pitch, (int)cap, (int)(cap / block_size), (int)ldo, (int)ldp, x_mant_bits, w_mant_bits, eps_dt, exp_win, causal,
-                                   (int)group, (int)row0, (int)rows, starts, win_arg(window));
+                                   (int)pitch, (int)hcap, (int)(hcap / block_size), (int)ldo, (int)ldp, x_mant_bits, w_mant_bits, eps_dt, exp_win,
+                                   causal, (int)group, (int)row0, (int)rows, starts, win_arg(window), PG ? *pages : Pages{});
             });
         });
         return (int)hipGetLastError();
     };
-    return win && (starts || win_arg(window)) ? go(std::true_type{}) : go(std::false_type{});
+    if (pages) return go(std::false_type{}, std::true_type{});
+    return win && (starts || win_arg(window)) ? go(std::true_type{}, std::false_type{}) : go(std::false_type{}, std::false_type{});
 }
 
 }  // namespace
@@ -1307,7 +1479,7 @@ int bfpq_kv_append(const void* k_new, const void* v_new, void* k_codes, int8_t* 
     with_dtype(dtype, [&](auto dt) {
         hipLaunchKernelGGL((k_kv_append<decltype(dt)::value, false>), dim3((unsigned)(nkb + nvb)), dim3(256), 0, (hipStream_t)stream, k_new, v_new,
                            (int8_t*)k_codes, k_exps, (int8_t*)v_codes, v_exps, v_tail, (int)BH, (int)D, (int)pos, (int)t, (int)cap, (int)ldd,
-                           block_size, mant_bits, eps_dt, exp_win, (int)nkb, (int)zc, nullptr, nullptr, nullptr, 1, 0);
+                           block_size, mant_bits, eps_dt, exp_win, (int)nkb, (int)zc, nullptr, nullptr, nullptr, 1, 0, Pages{});
     });
     return (int)hipGetLastError();
 }
@@ -1330,7 +1502,7 @@ int bfpq_kv_bmm_dec(const void* x, const void* wcodes, const int8_t* wexp, void*
                 hipLaunchKernelGGL((k_kv_bmm_dec<decltype(blk)::value, decltype(dt)::value, TM, kHost>),
                                    dim3((unsigned)((Nout + 64 * TM - 1) / (64 * TM)), gy), dim3(256), 0, s, x, (const int8_t*)wcodes, wexp, out, (int)B,
                                    (int)Tq, (int)Kx, (int)Nout, (int)ldx, (int)ldw, (int)ldwe, (int)w_bstride, (int)ldo, x_mant_bits, w_mant_bits,
-                                   eps_dt, exp_win, nullptr, 1, 1.f, 0, 1, nullptr, 0);
+                                   eps_dt, exp_win, nullptr, 1, 1.f, 0, 1, nullptr, 0, Pages{});
             };
             // rows per wave: 64 (32 at the small blocks) of the many cached keys, 16 of V's D columns
             if (family == BFPQ_KV_PV) go(std::integral_constant<int, 1>{});
@@ -1341,19 +1513,23 @@ int bfpq_kv_bmm_dec(const void* x, const void* wcodes, const int8_t* wexp, void*
     return (int)hipGetLastError();
 }
 
-int bfpq_kv_append_dev(const void* k_new, const void* v_new, void* k_codes, int8_t* k_exps, void* v_codes, int8_t* v_exps, void* v_tail,
-                       const int32_t* lens, const int32_t* counts, int32_t* overflow, int64_t BH, int64_t heads, int64_t D, int64_t t,
-                       int64_t cap, int64_t limit, int64_t ldd, int dtype, int block_size, int mant_bits, double epsilon,
-                       const uint8_t* exp_win, void* stream)
+// bfpq_kv_append_dev (pages null) and bfpq_kv_append_paged
+static int append_dev(const void* k_new, const void* v_new, void* k_codes, int8_t* k_exps, void* v_codes, int8_t* v_exps, void* v_tail,
+                      const int32_t* lens, const int32_t* counts, int32_t* overflow, int64_t BH, int64_t heads, int64_t D, int64_t t,
+                      int64_t cap, int64_t limit, int64_t ldd, int dtype, int block_size, int mant_bits, double epsilon,
+                      const uint8_t* exp_win, void* stream, const Pages* pages)
 {
-    if (!dtype_ok(dtype) || !i8_block_ok(block_size) || !i8_mant_ok(mant_bits) || BH < 0 || t < 0 || heads < 1 || BH % heads != 0)
+    if (!dtype_ok(dtype) || !i8_block_ok(block_size) || !i8_mant_ok(mant_bits) || BH < 0 || t < 0 || heads < 1 || BH % heads != 0 ||
+        (pages && !pages_values_ok(pages->tokens, pages->count, cap)))
         return BFPQ_E_ARG;
-    if (!bfpq_kv_ok(D, cap, block_size) || ldd < D || ldd % 64 != 0 || limit < 1 || limit > cap || t > cap || BH >= kLim)
+    if (!bfpq_kv_ok(D, cap, block_size) || ldd < D || ldd % 64 != 0 || limit < 1 || limit > cap || t > cap || BH >= kLim ||
+        (pages && !pages_shapes_ok(pages->tokens, pages->count, heads, D, ldd, block_size)))
         return BFPQ_E_UNSUPPORTED;
     if (BH == 0 || t == 0) return 0;
     if (!k_new || !v_new || !k_codes || !k_exps || !v_codes || !v_exps || !v_tail || !lens || !overflow || !exp_win ||
         !aligned16(k_new, v_new, k_codes, v_codes, v_tail) || ((reinterpret_cast<uintptr_t>(lens) | reinterpret_cast<uintptr_t>(counts) |
-                                                                 reinterpret_cast<uintptr_t>(overflow)) & 3u))
+                                                                 reinterpret_cast<uintptr_t>(overflow)) & 3u) ||
+        (pages && !pages_ptr_ok(pages->table)))
         return BFPQ_E_ARG;
     const int64_t nkb = (BH * t * (D / 16) + 255) / 256;
     // the token blocks of V a chunk of t can touch at the worst position (its first token the last of a block)
@@ -1362,21 +1538,49 @@ int bfpq_kv_append_dev(const void* k_new, const void* v_new, void* k_codes, int8
     if (nkb + nvb >= kLim) return BFPQ_E_UNSUPPORTED;
     const float eps_dt = bfpq_dev::h_round((float)epsilon, dtype);
     with_dtype(dtype, [&](auto dt) {
-        hipLaunchKernelGGL((k_kv_append<decltype(dt)::value, true>), dim3((unsigned)(nkb + nvb)), dim3(256), 0, (hipStream_t)stream, k_new, v_new,
-                           (int8_t*)k_codes, k_exps, (int8_t*)v_codes, v_exps, v_tail, (int)BH, (int)D, 0, (int)t, (int)cap, (int)ldd, block_size,
-                           mant_bits, eps_dt, exp_win, (int)nkb, (int)zc, lens, counts, overflow, (int)heads, (int)limit);
+        auto go = [&](auto paged) {
+            constexpr bool PG = decltype(paged)::value;           // (PG: the kernel's cap is a page's tokens)
+            hipLaunchKernelGGL((k_kv_append<decltype(dt)::value, true, PG>), dim3((unsigned)(nkb + nvb)), dim3(256), 0, (hipStream_t)stream, k_new,
+                               v_new, (int8_t*)k_codes, k_exps, (int8_t*)v_codes, v_exps, v_tail, (int)BH, (int)D, 0, (int)t,
+                               (int)(PG ? pages->tokens : cap), (int)ldd, block_size, mant_bits, eps_dt, exp_win, (int)nkb, (int)zc, lens, counts,
+                               overflow, (int)heads, (int)limit, PG ? *pages : Pages{});
+        };
+        if (pages) go(std::true_type{});
+        else go(std::false_type{});
     });
+    return (int)hipGetLastError();
+}
+
+int bfpq_kv_append_dev(const void* k_new, const void* v_new, void* k_codes, int8_t* k_exps, void* v_codes, int8_t* v_exps, void* v_tail,
+                       const int32_t* lens, const int32_t* counts, int32_t* overflow, int64_t BH, int64_t heads, int64_t D, int64_t t,
+                       int64_t cap, int64_t limit, int64_t ldd, int dtype, int block_size, int mant_bits, double epsilon,
+                       const uint8_t* exp_win, void* stream)
+{
+    return append_dev(k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, lens, counts, overflow, BH, heads, D, t, cap, limit, ldd, dtype,
+                      block_size, mant_bits, epsilon, exp_win, stream, nullptr);
+}
+
+// bfpq_kv_lens_advance (pages null) and bfpq_kv_lens_advance_paged
+static int lens_advance(int32_t* lens, const int32_t* counts, int64_t B, int64_t t, int64_t limit, void* stream, const Pages* pages)
+{
+    if (B < 0 || t < 0 || limit < 1 || (pages && !pages_values_ok(pages->tokens, pages->count, (int64_t)pages->width * pages->tokens)))
+        return BFPQ_E_ARG;
+    if (B >= kLim || t >= kLim || limit >= kLim || (pages && limit > (int64_t)pages->width * pages->tokens)) return BFPQ_E_UNSUPPORTED;
+    if (B == 0 || t == 0) return 0;
+    if (!lens || ((reinterpret_cast<uintptr_t>(lens) | reinterpret_cast<uintptr_t>(counts)) & 3u) || (pages && !pages_ptr_ok(pages->table)))
+        return BFPQ_E_ARG;
+    if (pages)
+        hipLaunchKernelGGL(k_kv_advance<true>, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, lens, counts, (int)B, (int)t,
+                           (int)limit, *pages);
+    else
+        hipLaunchKernelGGL(k_kv_advance<false>, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, lens, counts, (int)B, (int)t,
+                           (int)limit, Pages{});
     return (int)hipGetLastError();
 }
 
 int bfpq_kv_lens_advance(int32_t* lens, const int32_t* counts, int64_t B, int64_t t, int64_t limit, void* stream)
 {
-    if (B < 0 || t < 0 || limit < 1) return BFPQ_E_ARG;
-    if (B >= kLim || t >= kLim || limit >= kLim) return BFPQ_E_UNSUPPORTED;
-    if (B == 0 || t == 0) return 0;
-    if (!lens || ((reinterpret_cast<uintptr_t>(lens) | reinterpret_cast<uintptr_t>(counts)) & 3u)) return BFPQ_E_ARG;
-    hipLaunchKernelGGL(k_kv_advance, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, lens, counts, (int)B, (int)t, (int)limit);
-    return (int)hipGetLastError();
+    return lens_advance(lens, counts, B, t, limit, stream, nullptr);
 }
 
 int64_t bfpq_kv_dec_ws_bytes(int64_t B, int64_t Tq, int64_t D, int64_t L, int block_size)
@@ -1387,24 +1591,39 @@ int64_t bfpq_kv_dec_ws_bytes(int64_t B, int64_t Tq, int64_t D, int64_t L, int bl
     return (B * Tq * nbw * (4 * D + 1) + 15) / 16 * 16;           // the int32 block sums, then x's block exponents
 }
 
-int bfpq_kv_bmm_dec_gqa(const void* x, const void* wcodes, const int8_t* wexp, void* out, const int32_t* lens, int64_t B, int64_t heads,
-                        int64_t Tq, int64_t group, int64_t Kx, int64_t Nout, int64_t ldx, int64_t ldw, int64_t ldwe, int64_t w_bstride,
-                        int64_t ldo, int family, int dtype, int block_size, int x_mant_bits, int w_mant_bits, double epsilon,
-                        const uint8_t* exp_win, void* ws, int64_t ws_bytes, int64_t chunks_per_split, void* stream)
+// bfpq_kv_bmm_dec_gqa (pages null) and bfpq_kv_bmm_dec_paged: there the rows of a head are those of one page (ldw, ldwe and w_bstride as
+// the entry documents them) and `cap` the most tokens of a sequence
+static int bmm_dec_gqa(const void* x, const void* wcodes, const int8_t* wexp, void* out, const int32_t* lens, int64_t B, int64_t heads,
+                       int64_t Tq, int64_t group, int64_t Kx, int64_t Nout, int64_t ldx, int64_t ldw, int64_t ldwe, int64_t w_bstride,
+                       int64_t ldo, int family, int dtype, int block_size, int x_mant_bits, int w_mant_bits, double epsilon,
+                       const uint8_t* exp_win, void* ws, int64_t ws_bytes, int64_t chunks_per_split, void* stream, const Pages* pages, int64_t cap)
 {
     if (!dec_values_ok(dtype, block_size, x_mant_bits, w_mant_bits, family, B, Tq, Nout, Kx) || heads < 1 || B % heads != 0 || group < 1 ||
-        chunks_per_split < 0)
+        chunks_per_split < 0 || (pages && !pages_values_ok(pages->tokens, pages->count, cap)))
         return BFPQ_E_ARG;
     if (B == 0 || Tq == 0) return 0;
-    if (Tq > BFPQ_KV_DEC_MAX_TOKENS || group >= kLim || !dec_shapes_ok(family, block_size, Tq, Tq * group, Kx, Nout, ldx, ldw, ldwe, w_bstride, ldo) ||
-        Nout < 1 || (family == BFPQ_KV_PV && Nout > 1024) || B * row_tiles(Tq, group) >= kLim || chunks_per_split > kMaxCps)
+    if (pages) {                                                  // the bounds of a whole sequence, then a page's as the head's
+        const int64_t P = pages->tokens;
+        if ((family == BFPQ_KV_QK ? Nout : Kx) > cap || pages->count * heads >= kLim ||
+            (family == BFPQ_KV_QK ? w_bstride != P || ldw < Kx || ldwe < Kx / block_size
+                                  : ldw != P || ldwe != P / block_size || w_bstride != Nout))
+            return BFPQ_E_UNSUPPORTED;
+        if (Tq > BFPQ_KV_DEC_MAX_TOKENS || group >= kLim || Kx < 1 || Nout < 1 || (family == BFPQ_KV_QK ? Kx % block_size != 0 : Nout % 16 != 0) ||
+            ldx < Kx || ldw % 64 != 0 || ldo % 4 != 0 || ldo < Nout || w_bstride * ldw >= kLim || Tq * group * ldx >= kLim ||
+            Tq * group * ldo >= kLim || (family == BFPQ_KV_PV && Nout > 1024) || B * row_tiles(Tq, group) >= kLim || chunks_per_split > kMaxCps)
+            return BFPQ_E_UNSUPPORTED;
+    } else if (Tq > BFPQ_KV_DEC_MAX_TOKENS || group >= kLim ||
+               !dec_shapes_ok(family, block_size, Tq, Tq * group, Kx, Nout, ldx, ldw, ldwe, w_bstride, ldo) || Nout < 1 ||
+               (family == BFPQ_KV_PV && Nout > 1024) || B * row_tiles(Tq, group) >= kLim || chunks_per_split > kMaxCps)
         return BFPQ_E_UNSUPPORTED;
-    if (!dec_ptrs_ok(x, wcodes, wexp, out, exp_win, dtype) || !lens || (reinterpret_cast<uintptr_t>(lens) & 3u)) return BFPQ_E_ARG;
+    if (!dec_ptrs_ok(x, wcodes, wexp, out, exp_win, dtype) || !lens || (reinterpret_cast<uintptr_t>(lens) & 3u) ||
+        (pages && !pages_ptr_ok(pages->table)))
+        return BFPQ_E_ARG;
     const float eps_dt = bfpq_dev::h_round((float)epsilon, dtype);
     hipStream_t s = (hipStream_t)stream;
     if (family == BFPQ_KV_QK) {
         qk_dev<kDev>(x, wcodes, wexp, out, lens, B, heads, Tq, group, Kx, Nout, ldx, ldw, ldwe, w_bstride, ldo, dtype, block_size, x_mant_bits, w_mant_bits,
-                     eps_dt, exp_win, 1.f, 0, s);
+                     eps_dt, exp_win, 1.f, 0, s, nullptr, 0, pages);
         return (int)hipGetLastError();
     }
     // p v: w_bstride == Nout == D rows per head (the sums are laid out by D); a workgroup per (head, row tile) on the grid's z
@@ -1412,7 +1631,16 @@ int bfpq_kv_bmm_dec_gqa(const void* x, const void* wcodes, const int8_t* wexp, v
     if (w_bstride != Nout || B * row_tiles(Tq, group) > 65535 || need < 0 || ws_bytes < need) return BFPQ_E_UNSUPPORTED;
     if (!ws || !aligned16(ws)) return BFPQ_E_ARG;
     return pv_dev<false>(x, wcodes, wexp, out, lens, B, heads, Tq, group, Kx, Nout, ldx, ldw, ldwe, ldo, dtype, block_size, x_mant_bits, w_mant_bits,
-                         eps_dt, exp_win, ws, chunks_per_split, nullptr, 0, 0, s);
+                         eps_dt, exp_win, ws, chunks_per_split, nullptr, 0, 0, s, nullptr, 0, pages);
+}
+
+int bfpq_kv_bmm_dec_gqa(const void* x, const void* wcodes, const int8_t* wexp, void* out, const int32_t* lens, int64_t B, int64_t heads,
+                        int64_t Tq, int64_t group, int64_t Kx, int64_t Nout, int64_t ldx, int64_t ldw, int64_t ldwe, int64_t w_bstride,
+                        int64_t ldo, int family, int dtype, int block_size, int x_mant_bits, int w_mant_bits, double epsilon,
+                        const uint8_t* exp_win, void* ws, int64_t ws_bytes, int64_t chunks_per_split, void* stream)
+{
+    return bmm_dec_gqa(x, wcodes, wexp, out, lens, B, heads, Tq, group, Kx, Nout, ldx, ldw, ldwe, w_bstride, ldo, family, dtype, block_size,
+                       x_mant_bits, w_mant_bits, epsilon, exp_win, ws, ws_bytes, chunks_per_split, stream, nullptr, 0);
 }
 
 int bfpq_kv_bmm_dec_dev(const void* x, const void* wcodes, const int8_t* wexp, void* out, const int32_t* lens, int64_t B, int64_t heads,
@@ -1497,5 +1725,67 @@ int bfpq_kv_attend_rows_win(const void* q, const void* k_codes, const int8_t* k_
                        dtype, block_size, x_mant_bits, w_mant_bits, epsilon, exp_win, score_ws, score_ws_bytes, chunks_per_split, row0, rows, true,
                        starts, window, stream);
 }
+
+// ---- the paged entries: the entry each extends with page_table, page_tokens and pages in front of the stream ------------------
+#define BFPQ_PAGES_OR_RETURN(cap)                                                                          \
+    if (!pages_values_ok(page_tokens, pages, cap)) return BFPQ_E_ARG;                                      \
+    if (page_tokens >= kLim || pages >= kLim || (cap) >= kLim) return BFPQ_E_UNSUPPORTED;                  \
+    const Pages pg = pages_arg(page_table, page_tokens, pages, cap)
+
+int bfpq_kv_append_paged(const void* k_new, const void* v_new, void* k_codes, int8_t* k_exps, void* v_codes, int8_t* v_exps, void* v_tail,
+                         const int32_t* lens, const int32_t* counts, int32_t* overflow, int64_t BH, int64_t heads, int64_t D, int64_t t,
+                         int64_t cap, int64_t limit, int64_t ldd, int dtype, int block_size, int mant_bits, double epsilon,
+                         const uint8_t* exp_win, const int32_t* page_table, int64_t page_tokens, int64_t pages, void* stream)
+{
+    BFPQ_PAGES_OR_RETURN(cap);
+    return append_dev(k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, lens, counts, overflow, BH, heads, D, t, cap, limit, ldd, dtype,
+                      block_size, mant_bits, epsilon, exp_win, stream, &pg);
+}
+
+int bfpq_kv_lens_advance_paged(int32_t* lens, const int32_t* counts, int64_t B, int64_t t, int64_t limit, int64_t cap,
+                               const int32_t* page_table, int64_t page_tokens, int64_t pages, void* stream)
+{
+    BFPQ_PAGES_OR_RETURN(cap);
+    return lens_advance(lens, counts, B, t, limit, stream, &pg);
+}
+
+int bfpq_kv_bmm_dec_paged(const void* x, const void* wcodes, const int8_t* wexp, void* out, const int32_t* lens, int64_t B, int64_t heads,
+                          int64_t Tq, int64_t group, int64_t Kx, int64_t Nout, int64_t ldx, int64_t ldw, int64_t ldwe, int64_t w_bstride,
+                          int64_t ldo, int family, int dtype, int block_size, int x_mant_bits, int w_mant_bits, double epsilon,
+                          const uint8_t* exp_win, void* ws, int64_t ws_bytes, int64_t chunks_per_split, int64_t cap,
+                          const int32_t* page_table, int64_t page_tokens, int64_t pages, void* stream)
+{
+    BFPQ_PAGES_OR_RETURN(cap);
+    return bmm_dec_gqa(x, wcodes, wexp, out, lens, B, heads, Tq, group, Kx, Nout, ldx, ldw, ldwe, w_bstride, ldo, family, dtype, block_size,
+                       x_mant_bits, w_mant_bits, epsilon, exp_win, ws, ws_bytes, chunks_per_split, stream, &pg, cap);
+}
+
+int bfpq_kv_attend_paged(const void* q, const void* k_codes, const int8_t* k_exps, const void* v_codes, const int8_t* v_exps, void* out,
+                         void* p_out, const int32_t* lens, int64_t BH, int64_t heads, int64_t Tq, int64_t group, int64_t D, int64_t max_len,
+                         int64_t cap, int64_t ldd, int64_t ldo, int64_t ldp, double scale, int causal, int dtype, int block_size,
+                         int x_mant_bits, int w_mant_bits, double epsilon, const uint8_t* exp_win, void* score_ws, int64_t score_ws_bytes,
+                         void* sum_ws, int64_t sum_ws_bytes, int64_t chunks_per_split, const int32_t* page_table, int64_t page_tokens,
+                         int64_t pages, void* stream)
+{
+    BFPQ_PAGES_OR_RETURN(cap);
+    return attend_gqa(q, k_codes, k_exps, v_codes, v_exps, out, p_out, lens, BH, heads, Tq, group, D, max_len, cap, ldd, ldo, ldp, scale, causal, dtype,
+                      block_size, x_mant_bits, w_mant_bits, epsilon, exp_win, score_ws, score_ws_bytes, sum_ws, sum_ws_bytes, chunks_per_split,
+                      false, nullptr, 0, stream, &pg);
+}
+
+int bfpq_kv_attend_rows_paged(const void* q, const void* k_codes, const int8_t* k_exps, const void* v_codes, const int8_t* v_exps, void* out,
+                              void* p_out, const int32_t* lens, int64_t BH, int64_t heads, int64_t Tq, int64_t group, int64_t D, int64_t max_len,
+                              int64_t cap, int64_t ldd, int64_t ldo, int64_t ldp, double scale, int causal, int dtype, int block_size,
+                              int x_mant_bits, int w_mant_bits, double epsilon, const uint8_t* exp_win, void* score_ws, int64_t score_ws_bytes,
+                              void* sum_ws, int64_t sum_ws_bytes, int64_t chunks_per_split, int64_t row0, int64_t rows,
+                              const int32_t* page_table, int64_t page_tokens, int64_t pages, void* stream)
+{
+    (void)sum_ws; (void)sum_ws_bytes;
+    BFPQ_PAGES_OR_RETURN(cap);
+    return attend_rows(q, k_codes, k_exps, v_codes, v_exps, out, p_out, lens, BH, heads, Tq, group, D, max_len, cap, ldd, ldo, ldp, scale, causal,
+                       dtype, block_size, x_mant_bits, w_mant_bits, epsilon, exp_win, score_ws, score_ws_bytes, chunks_per_split, row0, rows, false,
+                       nullptr, 0, stream, &pg);
+}
+#undef BFPQ_PAGES_OR_RETURN
 
 }  // extern "C"

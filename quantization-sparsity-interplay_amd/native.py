@@ -124,6 +124,14 @@ PROTOTYPES = {
                                       _vp]),
     "bfpq_kv_attend_rows_win": (_i32, [_vp] * 8 + [_i64] * 10 + [_dbl, _i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64,
                                        _vp, _i64, _vp]),
+    "bfpq_kv_append_paged": (_i32, [_vp] * 10 + [_i64] * 7 + [_i32, _i32, _i32, _dbl, _vp, _vp, _i64, _i64, _vp]),
+    "bfpq_kv_lens_advance_paged": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp]),
+    "bfpq_kv_bmm_dec_paged": (_i32, [_vp] * 5 + [_i64] * 11 + [_i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64,
+                                     _vp]),
+    "bfpq_kv_attend_paged": (_i32, [_vp] * 8 + [_i64] * 10 + [_dbl, _i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64,
+                                    _i64, _vp]),
+    "bfpq_kv_attend_rows_paged": (_i32, [_vp] * 8 + [_i64] * 10 + [_dbl, _i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _i64, _vp, _i64, _i64, _i64,
+                                         _i64, _vp, _i64, _i64, _vp]),
 }
 
 
@@ -1401,15 +1409,39 @@ def kv_ok(D, cap, block_size):
     return bool(load_library().bfpq_kv_ok(int(D), int(cap), int(block_size)))
 
 
-def _kv_buffers(what, BH, D, block_size, k_codes, k_exps, v_codes, v_exps, v_tail, dev):
-    """the checks of kv_append on the five cache buffers; returns (cap, ldd)"""
+class KVPages(collections.namedtuple("KVPages", "table tokens count capacity")):
+    """a paged cache as the _paged entries take it (include/bfpq.h): table int32 [sequences, capacity // tokens] on the device (-1: no
+    page), `tokens` per page (a multiple of 64), `count` pages in the pool, `capacity` the most tokens of one sequence.  The code and
+    exponent buffers then hold count x heads heads of `tokens` tokens"""
+    __slots__ = ()
+
+    def args(self):
+        """(page_table, page_tokens, pages) as they stand in front of the stream"""
+        return _ptr(self.table), int(self.tokens), int(self.count)
+
+
+def _kv_pages(what, pages, B, heads, dev):
+    """the checks on a KVPages of B sequences; returns the heads the code buffers hold"""
+    if not isinstance(pages, KVPages):
+        raise ValueError(f"{what}: pages must be a native.KVPages (got {type(pages).__name__})")
+    P, N, cap = int(pages.tokens), int(pages.count), int(pages.capacity)
+    if P < 64 or P % 64 or N < 1 or cap < P or cap % P:
+        raise ValueError(f"{what}: page_tokens must be a multiple of 64 that divides the capacity, pages >= 1 (got {P}, {cap}, {N})")
+    _kv_int32(what, "page_table", pages.table, B * (cap // P), dev)
+    return N * heads
+
+
+def _kv_buffers(what, BH, D, block_size, k_codes, k_exps, v_codes, v_exps, v_tail, dev, held=None):
+    """the checks of kv_append on the five cache buffers (held: the heads the code and exponent buffers hold, where not BH: a paged
+    cache); returns (cap, ldd)"""
     if block_size not in (64,) + I8_BLOCKS:
         raise ValueError(f"{what}: block_size must be 16, 32 or 64 (got {block_size})")
     if k_codes.dim() < 2 or v_codes.dim() < 2:
         raise ValueError(f"{what} takes k_codes [..., cap, ldd] and v_codes [..., D, cap]")
     cap, ldd = k_codes.shape[-2], k_codes.shape[-1]
     nbd, nbc = D // block_size, cap // block_size
-    sizes = dict(k_codes=(k_codes, BH * cap * ldd), k_exps=(k_exps, BH * cap * nbd), v_codes=(v_codes, BH * D * cap), v_exps=(v_exps, BH * D * nbc),
+    HB = BH if held is None else held
+    sizes = dict(k_codes=(k_codes, HB * cap * ldd), k_exps=(k_exps, HB * cap * nbd), v_codes=(v_codes, HB * D * cap), v_exps=(v_exps, HB * D * nbc),
                  v_tail=(v_tail, BH * block_size * D))
     for name, (buf, numel) in sizes.items():
         if buf.device != dev or not buf.is_contiguous() or buf.numel() != numel or (name != "v_tail" and buf.dtype != torch.int8):
@@ -1426,7 +1458,7 @@ def _kv_int32(what, name, t, numel, dev):
                          f"(got {tuple(getattr(t, 'shape', ()))}, {getattr(t, 'dtype', None)}, {getattr(t, 'device', None)})")
 
 
-def _kv_new(what, k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, block_size, heads=None):
+def _kv_new(what, k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, block_size, heads=None, pages=None):
     """the checks kv_append and kv_append_dev share on the new rows and the cache buffers; returns (BH, t, D, cap, ldd)"""
     require_device_tensor(k_new, "k_new")
     require_device_tensor(v_new, "v_new")
@@ -1437,7 +1469,8 @@ def _kv_new(what, k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, block_
     BH, t, D = k_new.shape
     if heads is not None and (heads < 1 or BH % heads):
         raise ValueError(f"{what}: {BH} heads in all are no multiple of heads = {heads}")
-    cap, ldd = _kv_buffers(what, BH, D, block_size, k_codes, k_exps, v_codes, v_exps, v_tail, k_new.device)
+    held = None if pages is None else _kv_pages(what, pages, BH // heads, heads, k_new.device)
+    cap, ldd = _kv_buffers(what, BH, D, block_size, k_codes, k_exps, v_codes, v_exps, v_tail, k_new.device, held)
     if not k_new.is_contiguous() or not v_new.is_contiguous():
         raise ValueError(f"{what} takes contiguous k_new / v_new")
     return BH, t, D, cap, ldd
@@ -1455,12 +1488,13 @@ def kv_append(k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, pos, block
 
 
 def kv_append_dev(k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, lengths, counts, overflow, heads, limit, block_size, mant_bits,
-                  epsilon):
+                  epsilon, pages=None):
     """kv_append at the positions lengths [B] (int32, on the device) holds, sequence b = head // heads taking the first counts[b] of the t
     rows (counts None: all), then lengths advanced by a second launch (bfpq_kv_append_dev, bfpq_kv_lens_advance).  A sequence that would
-    pass `limit` tokens is left untouched and overflow[0] set to 1.  Nothing is read back."""
+    pass `limit` tokens is left untouched and overflow[0] set to 1.  Nothing is read back.  pages (a KVPages): the buffers are a pool of
+    pages (bfpq_kv_append_paged, bfpq_kv_lens_advance_paged), and a sequence one of whose tokens has no page is refused likewise."""
     heads = int(heads)
-    BH, t, D, cap, ldd = _kv_new("kv_append_dev", k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, block_size, heads)
+    BH, t, D, cap, ldd = _kv_new("kv_append_dev", k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, block_size, heads, pages)
     dev, B = k_new.device, BH // heads
     _kv_int32("kv_append_dev", "lengths", lengths, B, dev)
     _kv_int32("kv_append_dev", "overflow", overflow, 1, dev)
@@ -1468,6 +1502,14 @@ def kv_append_dev(k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, length
         _kv_int32("kv_append_dev", "counts", counts, B, dev)
     with torch.cuda.device(dev):
         L, stream = load_library(), _stream(k_new)
+        if pages is not None:
+            check(L.bfpq_kv_append_paged(_ptr(k_new), _ptr(v_new), _ptr(k_codes), _ptr(k_exps), _ptr(v_codes), _ptr(v_exps), _ptr(v_tail),
+                                         _ptr(lengths), _ptr(counts), _ptr(overflow), BH, heads, D, t, int(pages.capacity), int(limit), ldd,
+                                         DTYPE_CODE[k_new.dtype], int(block_size), int(mant_bits), float(epsilon),
+                                         _ptr(exp_window_dev(k_new.dtype, dev)), *pages.args(), stream), "bfpq_kv_append_paged")
+            check(L.bfpq_kv_lens_advance_paged(_ptr(lengths), _ptr(counts), B, t, int(limit), int(pages.capacity), *pages.args(), stream),
+                  "bfpq_kv_lens_advance_paged")
+            return
         check(L.bfpq_kv_append_dev(_ptr(k_new), _ptr(v_new), _ptr(k_codes), _ptr(k_exps), _ptr(v_codes), _ptr(v_exps), _ptr(v_tail), _ptr(lengths),
                                    _ptr(counts), _ptr(overflow), BH, heads, D, t, cap, int(limit), ldd, DTYPE_CODE[k_new.dtype], int(block_size),
                                    int(mant_bits), float(epsilon), _ptr(exp_window_dev(k_new.dtype, dev)), stream), "bfpq_kv_append_dev")
@@ -1505,7 +1547,7 @@ def _kv_rows(what, x, form, group=1, heads=1):
     return x.contiguous(), BH, R, Tq, last, heads
 
 
-def _kv_operand(what, BH, w_bstride, wc, we, dev):
+def _kv_operand(what, BH, w_bstride, wc, we, dev):   # (a paged cache: BH the heads the pool holds)
     """one cached operand of kv_bmm_dec / kv_bmm_dec_dev: contiguous codes and exponents of BH x w_bstride rows"""
     for name, buf in (("codes", wc), ("exponents", we)):
         if buf.device != dev or buf.dtype != torch.int8 or not buf.is_contiguous() or buf.numel() < BH * int(w_bstride) * buf.shape[-1]:
@@ -1514,7 +1556,8 @@ def _kv_operand(what, BH, w_bstride, wc, we, dev):
 
 
 def _kv_cached(what, BH, D, block_size, k_codes, k_exps, v_codes, v_exps, dev):
-    """the four code and exponent buffers of BH cached heads as the attend entries take them; returns (cap, ldd)"""
+    """the four code and exponent buffers of BH cached heads (a paged cache: the heads the pool holds, of a page's tokens each) as the
+    attend entries take them; returns (cap, ldd)"""
     if k_codes.dim() < 2 or v_codes.dim() < 2:
         raise ValueError(f"{what} takes k_codes [..., cap, ldd] and v_codes [..., D, cap]")
     cap, ldd = k_codes.shape[-2], k_codes.shape[-1]
@@ -1541,16 +1584,18 @@ def _kv_scale(what, scale):
     return scale
 
 
-def kv_bmm_dec_dev(x, wc, we, family, bound, w_bstride, lengths, heads, block_size, mant_bits, epsilon, ws=None, chunks_per_split=0, group=1):
+def kv_bmm_dec_dev(x, wc, we, family, bound, w_bstride, lengths, heads, block_size, mant_bits, epsilon, ws=None, chunks_per_split=0, group=1,
+                   pages=None):
     """kv_bmm_dec with head b's cached length read from lengths[b // heads] on the device (bfpq_kv_bmm_dec_gqa).  KV_QK: x [BH, Tq, D],
     bound = max_len; returns [BH, Tq, max_len], -inf from the length on.  KV_PV: x [BH, Tq, L], bound = D; returns [BH, Tq, D]; ws: a
     uint8 tensor of at least kv_dec_ws_bytes(BH, Tq, D, L, block_size) bytes; chunks_per_split: 64-token chunks per slice of the
     contraction, 0 = the library's choice (the result does not depend on it).  group > 1 (grouped-query attention): the BH cached heads
     serve `group` query heads each, x and the result hold group * Tq rows per cached head -- query head r // Tq of the group, token
-    r % Tq -- and the workspace is that of BH * group heads."""
+    r % Tq -- and the workspace is that of BH * group heads.  pages (a KVPages): wc / we are a pool of pages (bfpq_kv_bmm_dec_paged),
+    w_bstride for KV_QK a page's tokens."""
     x, BH, R, Tq, Kx, heads = _kv_rows("kv_bmm_dec_dev", x, "x [BH, Tq, Kx]", group, heads)
     dev = x.device
-    _kv_operand("kv_bmm_dec_dev", BH, w_bstride, wc, we, dev)
+    _kv_operand("kv_bmm_dec_dev", BH if pages is None else _kv_pages("kv_bmm_dec_dev", pages, BH // heads, heads, dev), w_bstride, wc, we, dev)
     _kv_int32("kv_bmm_dec_dev", "lengths", lengths, BH // heads, dev)
     Nout = int(bound)
     ws_bytes = 0
@@ -1559,11 +1604,13 @@ def kv_bmm_dec_dev(x, wc, we, family, bound, w_bstride, lengths, heads, block_si
     ldo = (Nout + 3) // 4 * 4
     with torch.cuda.device(dev):
         out = torch.empty((BH, R, ldo), dtype=x.dtype, device=dev)
-        check(load_library().bfpq_kv_bmm_dec_gqa(_ptr(x), _ptr(wc), _ptr(we), _ptr(out), _ptr(lengths), BH, heads, Tq, group, Kx, Nout, Kx,
-                                                 wc.shape[-1], we.shape[-1], int(w_bstride), ldo, int(family), DTYPE_CODE[x.dtype],
-                                                 int(block_size), int(mant_bits), int(mant_bits), float(epsilon),
-                                                 _ptr(exp_window_dev(x.dtype, dev)), _ptr(ws if family == KV_PV else None), ws_bytes,
-                                                 int(chunks_per_split), _stream(x)), "bfpq_kv_bmm_dec_gqa")
+        args = (_ptr(x), _ptr(wc), _ptr(we), _ptr(out), _ptr(lengths), BH, heads, Tq, group, Kx, Nout, Kx, wc.shape[-1], we.shape[-1],
+                int(w_bstride), ldo, int(family), DTYPE_CODE[x.dtype], int(block_size), int(mant_bits), int(mant_bits), float(epsilon),
+                _ptr(exp_window_dev(x.dtype, dev)), _ptr(ws if family == KV_PV else None), ws_bytes, int(chunks_per_split))
+        if pages is None:
+            check(load_library().bfpq_kv_bmm_dec_gqa(*args, _stream(x)), "bfpq_kv_bmm_dec_gqa")
+        else:
+            check(load_library().bfpq_kv_bmm_dec_paged(*args, int(pages.capacity), *pages.args(), _stream(x)), "bfpq_kv_bmm_dec_paged")
     return out[:, :, :Nout] if ldo != Nout else out
 
 
@@ -1586,18 +1633,32 @@ def _kv_window(what, BH, heads, starts, window, dev):
     return starts, window
 
 
+def _kv_paged_cached(what, pages, starts, window, BH, heads, D, block_size, k_codes, k_exps, v_codes, v_exps, dev):
+    """_kv_cached for the attend entries, on a pool of pages where `pages` is given; returns (the cap the entry takes, ldd)"""
+    if pages is None:
+        return _kv_cached(what, BH, D, block_size, k_codes, k_exps, v_codes, v_exps, dev)
+    if starts is not None or window:
+        raise NotImplementedError(f"{what}: a paged cache takes no starts and no window")
+    held = _kv_pages(what, pages, BH // heads, heads, dev)
+    P, ldd = _kv_cached(what, held, D, block_size, k_codes, k_exps, v_codes, v_exps, dev)
+    if P != int(pages.tokens):
+        raise ValueError(f"{what}: the buffers hold heads of {P} tokens, a page has {pages.tokens}")
+    return int(pages.capacity), ldd
+
+
 def kv_attend(q, k_codes, k_exps, v_codes, v_exps, lengths, heads, max_len, scale, causal, block_size, mant_bits, epsilon, score_ws, sum_ws,
-              chunks_per_split=0, return_probs=False, group=1, starts=None, window=None):
+              chunks_per_split=0, return_probs=False, group=1, starts=None, window=None, pages=None):
     """scores, scale, softmax and context of q [BH, Tq, D] against a device-length cache in three launches (bfpq_kv_attend_gqa): returns
     (context [BH, Tq, D], p [BH, Tq, max_len] or None).  score_ws / sum_ws: contiguous uint8 tensors of at least
     kv_attend_ws_bytes(BH, Tq, max_len) / kv_dec_ws_bytes(BH, Tq, D, max_len, block_size) bytes.  Nothing is read back.  group > 1: rows
     and workspaces as kv_bmm_dec_dev takes them (q, the context and p hold group * Tq rows per cached head; causal goes by the token).
     starts (int32 [BH // heads] on the device) and / or window (an int >= 1): the rows see the keys from max(starts[b], what they see
-    minus window) on (bfpq_kv_attend_gqa_win); with neither, the call and its kernels are the ones without."""
+    minus window) on (bfpq_kv_attend_gqa_win); with neither, the call and its kernels are the ones without.  pages (a KVPages; with neither
+    starts nor window): the buffers are a pool of pages (bfpq_kv_attend_paged)."""
     q, BH, R, Tq, D, heads = _kv_rows("kv_attend", q, "q [BH, Tq, D]", group, heads)
     dev = q.device
     starts, window = _kv_window("kv_attend", BH, heads, starts, window, dev)
-    cap, ldd = _kv_cached("kv_attend", BH, D, block_size, k_codes, k_exps, v_codes, v_exps, dev)
+    cap, ldd = _kv_paged_cached("kv_attend", pages, starts, window, BH, heads, D, block_size, k_codes, k_exps, v_codes, v_exps, dev)
     _kv_int32("kv_attend", "lengths", lengths, BH // heads, dev)
     max_len, scale = int(max_len), _kv_scale("kv_attend", scale)
     score_bytes = _kv_ws("kv_attend", "score_ws", score_ws, kv_attend_ws_bytes(BH * group, Tq, max_len), dev)
@@ -1608,7 +1669,9 @@ def kv_attend(q, k_codes, k_exps, v_codes, v_exps, lengths, heads, max_len, scal
         args = (_ptr(q), _ptr(k_codes), _ptr(k_exps), _ptr(v_codes), _ptr(v_exps), _ptr(out), _ptr(p), _ptr(lengths), BH, heads, Tq, group, D,
                 max_len, cap, ldd, D, max_len, scale, int(bool(causal)), DTYPE_CODE[q.dtype], int(block_size), int(mant_bits), int(mant_bits),
                 float(epsilon), _ptr(exp_window_dev(q.dtype, dev)), _ptr(score_ws), score_bytes, _ptr(sum_ws), sum_bytes, int(chunks_per_split))
-        if starts is None and not window:
+        if pages is not None:
+            check(load_library().bfpq_kv_attend_paged(*args, *pages.args(), _stream(q)), "bfpq_kv_attend_paged")
+        elif starts is None and not window:
             check(load_library().bfpq_kv_attend_gqa(*args, _stream(q)), "bfpq_kv_attend_gqa")
         else:
             check(load_library().bfpq_kv_attend_gqa_win(*args, _ptr(starts), window, _stream(q)), "bfpq_kv_attend_gqa_win")
@@ -1627,19 +1690,19 @@ def kv_attend_rows_ws_bytes(BH, P, max_len):
 
 
 def kv_attend_rows(q, k_codes, k_exps, v_codes, v_exps, lengths, heads, max_len, scale, causal, block_size, mant_bits, epsilon, score_ws,
-                   panel_rows, return_probs=False, group=1, starts=None, window=None):
+                   panel_rows, return_probs=False, group=1, starts=None, window=None, pages=None):
     """kv_attend for any number of query rows (bfpq_kv_attend_rows): q [BH, group * Tq, D] is walked in panels of panel_rows tokens per
     query head, two launches per panel, the panel's fp32 score rows in score_ws (a contiguous uint8 tensor of at least
     kv_attend_rows_ws_bytes(BH * group, min(panel_rows, Tq), max_len) bytes).  Returns (context [BH, group * Tq, D], p
     [BH, group * Tq, max_len] or None); row for row kv_attend's bits.  Nothing is read back.  starts, window: as kv_attend
-    (bfpq_kv_attend_rows_win)."""
+    (bfpq_kv_attend_rows_win); pages: as kv_attend (bfpq_kv_attend_rows_paged)."""
     q, BH, R, Tq, D, heads = _kv_rows("kv_attend_rows", q, "q [BH, Tq, D]", group, heads)
     panel_rows = int(panel_rows)
     if panel_rows < 1:
         raise ValueError(f"kv_attend_rows: panel_rows must be >= 1 (got {panel_rows})")
     dev = q.device
     starts, window = _kv_window("kv_attend_rows", BH, heads, starts, window, dev)
-    cap, ldd = _kv_cached("kv_attend_rows", BH, D, block_size, k_codes, k_exps, v_codes, v_exps, dev)
+    cap, ldd = _kv_paged_cached("kv_attend_rows", pages, starts, window, BH, heads, D, block_size, k_codes, k_exps, v_codes, v_exps, dev)
     _kv_int32("kv_attend_rows", "lengths", lengths, BH // heads, dev)
     max_len, scale = int(max_len), _kv_scale("kv_attend_rows", scale)
     score_bytes = _kv_ws("kv_attend_rows", "score_ws", score_ws, kv_attend_rows_ws_bytes(BH * group, min(panel_rows, Tq), max_len), dev)
@@ -1651,7 +1714,9 @@ def kv_attend_rows(q, k_codes, k_exps, v_codes, v_exps, lengths, heads, max_len,
             args = (_ptr(q), _ptr(k_codes), _ptr(k_exps), _ptr(v_codes), _ptr(v_exps), _ptr(out), _ptr(p), _ptr(lengths), BH, heads, Tq, group, D,
                     max_len, cap, ldd, D, max_len, scale, int(bool(causal)), DTYPE_CODE[q.dtype], int(block_size), int(mant_bits), int(mant_bits),
                     float(epsilon), win, _ptr(score_ws), score_bytes, None, 0, 0, row0, min(panel_rows, Tq - row0))
-            if starts is None and not window:
+            if pages is not None:
+                check(L.bfpq_kv_attend_rows_paged(*args, *pages.args(), stream), "bfpq_kv_attend_rows_paged")
+            elif starts is None and not window:
                 check(L.bfpq_kv_attend_rows(*args, stream), "bfpq_kv_attend_rows")
             else:
                 check(L.bfpq_kv_attend_rows_win(*args, _ptr(starts), window, stream), "bfpq_kv_attend_rows_win")
