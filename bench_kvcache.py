@@ -22,6 +22,12 @@ scores, softmax, context; modeling_gpt2.py:345-348 with :207, 243) on one MI355X
   paged  (--case paged_*: a paged cache) the attend leg (paged_gpt2s_b8_s1024, paged_ragged8) or the prompt leg
          (paged_prompt_*) on HBFPKVCache(page_tokens=P, pages=N) -- P from --page-tokens, N what the batch needs, the sequences' pages
          interleaved in the pool -- against full: the same step on the cache without pages; the rows also hold both caches' nbytes(),
+  fork   (--case fork_*: pages shared between sequences; both legs eager, since reorder plans on the host; HIP-event and
+         wall time) fork_beam8_gpt2s_s1024: one beam-search step of 8 beams, reorder(beam_idx, tokens) + reserve + append of one token +
+         attend on the paged cache (fork_beam8_h32_d128_s4096: the same at 32 heads of 128 and 4096 tokens), against select: the same step on the contiguous device-length cache with the reference's own
+         reorder, index_select(0, beam_idx) of its five buffers and the lengths, copied back; fork_prompt8_s1024: 8 sequences behind a
+         1024-token prompt with 64 own tokens each, the prompt appended and attended once and forked (once) against appended and
+         attended by all 8 (each), with the pages in use and shared,
 and, for the cache alone, the append of a prefill chunk of S tokens.  Method of bench_matmul.py: hipGraph replay, the median of the
 replays, the legs alternating round by round in one process.  (A captured append writes at the captured position: every replay redoes the
 same step, which is what is timed.)  On a tree without the cache the cache columns are null and "cache" says "absent".
@@ -427,6 +433,154 @@ def run_paged(name, iters, rounds, out, cps, page_tokens, only=None):
     _append_rows(out, rows)
 
 
+# name: (batch, heads, head_dim, S): a beam search's step; (batch, heads, head_dim, prompt tokens, own tokens, prompt_rows): a shared prompt
+FORK = {"fork_beam8_gpt2s_s1024": (8, 12, 64, 1024), "fork_beam8_h32_d128_s4096": (8, 32, 128, 4096),
+        "fork_prompt8_s1024": (8, 12, 64, 1024, 64, 256)}
+BEAM_IDX = [0, 0, 1, 3, 3, 3, 6, 7]
+
+
+def eager_times(fns, iters, rounds, before=None):
+    """per call of each fn, eager: (median HIP-event us, its (min, max), median wall us, its (min, max)) over `rounds` runs of `iters`
+    calls, the fns alternating round by round; before(): run ahead of every timed run, outside the timing"""
+    import statistics, time, torch
+    for fn in fns:
+        if before:
+            before()
+        fn(); fn(); torch.cuda.synchronize()
+    ev, wall = [[] for _ in fns], [[] for _ in fns]
+    for _ in range(rounds):
+        for i, fn in enumerate(fns):
+            if before:
+                before()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record(); torch.cuda.synchronize()
+            wall[i].append((time.perf_counter() - t0) * 1e6 / iters)
+            ev[i].append(e0.elapsed_time(e1) * 1e3 / iters)
+    return [(statistics.median(e), (min(e), max(e)), statistics.median(w), (min(w), max(w))) for e, w in zip(ev, wall)]
+
+
+def run_fork_beam(name, iters, rounds, out, only=None):
+    """the legs paged and select of a beam-search step, bf16 at block 64, pages of 64 tokens (only: one leg alone: a kernel trace)"""
+    import torch
+    import quantization_sparsity_interplay_amd as bfpq
+    from quantization_sparsity_interplay_amd.bfp import bfp_ops
+    dev, dt, P = "cuda:0", torch.bfloat16, 64
+    batch, heads, D, S = FORK[name]
+    c = CONFIGS["hbfp8_b64"]
+    scale = 1.0 / D ** 0.5
+    steps = 2 + iters * rounds
+    cap = -(-(S + steps) // P) * P
+    gen = torch.Generator().manual_seed(1)
+    k, v = (torch.randn(batch, heads, S, D, generator=gen).to(dt).to(dev) for _ in range(2))
+    q = torch.randn(batch, heads, 1, D, generator=gen).to(dt).to(dev)
+    k_new, v_new = k[:, :, -1:].contiguous(), v[:, :, -1:].contiguous()
+    i8 = bfp_ops.F_matmul_bfp(matrix_unit='int8', **bfpq.BFPConfig.hbfp(c['mant_bits'] + 1, c['block_size']).to_kwargs())
+    mk = lambda **mode: i8.kv_cache(batch, heads, D, cap, dtype=dt, device=dev, device_lengths=True, max_query_rows=1, **mode)
+    idx = torch.tensor(BEAM_IDX, device=dev)
+    legs, held = {}, {}
+    with torch.no_grad():
+        if only in (None, "paged"):
+            cache = mk(page_tokens=P, pages=batch * (cap // P))
+            reserve_interleaved(cache, [S - 1] * batch)
+            held["paged"] = [S - 1]                                  # the beams' common length, kept on the host as a generate() loop has it
+
+            def paged_step(cache=cache, n=held["paged"]):
+                cache.reorder(BEAM_IDX, [n[0]] * batch)
+                cache.reserve(n[0] + 1)
+                cache.append(k_new, v_new)
+                n[0] += 1
+                return cache.attend(q, scale)
+
+            legs["paged"] = (cache, paged_step)
+        if only in (None, "select"):
+            cache = mk()
+
+            def select_step(cache=cache):                            # _reorder_cache: index_select(0, beam_idx) of everything the cache holds
+                for t in list(cache.buffers.values()) + [cache.lengths]:
+                    t.copy_(t.index_select(0, idx))
+                cache.append(k_new, v_new)
+                return cache.attend(q, scale)
+
+            legs["select"] = (cache, select_step)
+        for cache, _ in legs.values():
+            cache.append(k[:, :, :S - 1].contiguous(), v[:, :, :S - 1].contiguous())
+            cache.prepare_attend()
+        times = eager_times([step for _, step in legs.values()], iters, rounds)
+    row = dict(shape=name, batch=batch, heads=heads, S=S, head_dim=D, dtype="bf16", config="hbfp8_b64", iters=iters, rounds=rounds, page_tokens=P,
+               beam_idx=BEAM_IDX, capacity=cap)
+    for (leg, (cache, _)), (ev, ev_mm, wall, wall_mm) in zip(legs.items(), times):
+        assert cache.overflow.item() == 0 and cache.lengths.tolist() == [S - 1 + steps] * batch, (leg, cache.lengths.tolist())
+        row.update({f"{leg}_us": ev, f"{leg}_min_max_us": ev_mm, f"{leg}_wall_us": wall, f"{leg}_wall_min_max_us": wall_mm,
+                    f"{leg}_cache_bytes": cache.nbytes()})
+        if cache.pages is not None:
+            row.update(pages=cache.page_count, pages_in_use=cache.page_count - cache.pages_free, pages_shared=cache.pages_shared)
+    print(json.dumps(row), flush=True)
+    _append_rows(out, [row])
+
+
+def run_fork_prompt(name, iters, rounds, out, only=None):
+    """the legs once and each of a shared prompt, bf16 at block 64, pages of 64 tokens: every step starts from reset()"""
+    import torch
+    import quantization_sparsity_interplay_amd as bfpq
+    from quantization_sparsity_interplay_amd.bfp import bfp_ops
+    dev, dt, P = "cuda:0", torch.bfloat16, 64
+    batch, heads, D, T, own, PR = FORK[name]
+    c = CONFIGS["hbfp8_b64"]
+    scale = 1.0 / D ** 0.5
+    gen = torch.Generator().manual_seed(1)
+    k, v = (torch.randn(batch, heads, T + own, D, generator=gen).to(dt).to(dev) for _ in range(2))
+    k[:, :, :T], v[:, :, :T] = k[:1, :, :T], v[:1, :, :T]             # one prompt, then every sequence's own tokens
+    q = torch.randn(batch, heads, T + own, D, generator=gen).to(dt).to(dev)
+    kp, vp, qp = (x[:, :, :T].contiguous() for x in (k, v, q))
+    ko, vo, qo = (x[:, :, T:].contiguous() for x in (k, v, q))
+    first = torch.tensor([T] + [0] * (batch - 1), dtype=torch.int32, device=dev)
+    i8 = bfp_ops.F_matmul_bfp(matrix_unit='int8', **bfpq.BFPConfig.hbfp(c['mant_bits'] + 1, c['block_size']).to_kwargs())
+    per = (T + own) // P
+    mk = lambda: i8.kv_cache(batch, heads, D, T + own, dtype=dt, device=dev, device_lengths=True, prompt_rows=PR, page_tokens=P, pages=batch * per)
+
+    def once_step(cache):
+        cache.reset()
+        cache.reserve([T] + [0] * (batch - 1))
+        cache.append(kp, vp, first)                                   # the prompt on row 0 alone
+        cache.attend(qp, scale, causal=True)
+        cache.fork(0, range(1, batch), T)
+        cache.reserve(T + own)
+        cache.append(ko, vo)
+        return cache.attend(qo, scale, causal=True)
+
+    def each_step(cache):
+        cache.reset()
+        cache.reserve(T + own)
+        cache.append(kp, vp)
+        cache.attend(qp, scale, causal=True)
+        cache.append(ko, vo)
+        return cache.attend(qo, scale, causal=True)
+
+    legs = {}
+    with torch.no_grad():
+        for leg, fn in (("once", once_step), ("each", each_step)):
+            if only in (None, leg):
+                cache = mk()
+                cache.prepare_attend()
+                legs[leg] = (cache, lambda cache=cache, fn=fn: fn(cache))
+        times = eager_times([step for _, step in legs.values()], iters, rounds)
+    row = dict(shape=name, batch=batch, heads=heads, prompt=T, own=own, head_dim=D, dtype="bf16", config="hbfp8_b64", iters=iters, rounds=rounds,
+               page_tokens=P, prompt_rows=PR)
+    for (leg, (cache, _)), (ev, ev_mm, wall, wall_mm) in zip(legs.items(), times):
+        assert cache.overflow.item() == 0 and cache.lengths.tolist() == [T + own] * batch
+        used, shared = cache.page_count - cache.pages_free, cache.pages_shared
+        assert (used, shared) == ((T // P + batch * (own // P), T // P) if leg == "once" else (batch * per, 0)), (leg, used, shared)
+        row.update({f"{leg}_us": ev, f"{leg}_min_max_us": ev_mm, f"{leg}_wall_us": wall, f"{leg}_wall_min_max_us": wall_mm,
+                    f"{leg}_pages_in_use": used, f"{leg}_pages_shared": shared})
+    print(json.dumps(row), flush=True)
+    _append_rows(out, [row])
+
+
 def run_attend_only(shape, iters, rounds, out, cps):
     """the attend leg alone, bf16 at block 64: what a kernel trace of one step is taken from (--attend-only)"""
     import torch
@@ -543,7 +697,8 @@ def merge_parent(out, parent_json):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--case", choices=sorted(SHAPES) + sorted(RAGGED) + sorted(GQA) + sorted(PROMPT) + sorted(WINDOW) + sorted(WINDOW_PROMPT) + sorted(STARTS) + sorted(PAGED))
+    ap.add_argument("--case", choices=sorted(SHAPES) + sorted(RAGGED) + sorted(GQA) + sorted(PROMPT) + sorted(WINDOW) + sorted(WINDOW_PROMPT) + sorted(STARTS) + sorted(PAGED) + sorted(FORK))
+    ap.add_argument("--fork-leg", choices=("paged", "select", "once", "each"), help="with a fork_* case: that leg alone (a kernel trace)")
     ap.add_argument("--page-tokens", type=int, default=64, help="with a paged_* case: tokens per page (a multiple of 64)")
     ap.add_argument("--paged-leg", choices=("paged", "full"), help="with a paged_* case: that leg alone, bf16 (a kernel trace)")
     ap.add_argument("--window-leg", choices=("window", "starts", "full", "masked"), help="with a window_* / starts_* case: that leg alone, bf16 (a kernel trace)")
@@ -572,6 +727,10 @@ def main():
     out = os.path.abspath(a.out)
     if a.merge_only:
         return merge_parent(out, a.parent_json)
+    if a.case in FORK and len(FORK[a.case]) == 4:
+        return run_fork_beam(a.case, a.iters, a.rounds, out, a.fork_leg)
+    if a.case in FORK:
+        return run_fork_prompt(a.case, min(a.iters, 4), a.rounds, out, a.fork_leg)
     if a.case in PAGED:
         return run_paged(a.case, min(a.iters, 4) if PAGED[a.case] in PROMPT else a.iters, a.rounds, out, a.chunks_per_split, a.page_tokens, a.paged_leg)
     if a.case in WINDOW or a.case in STARTS:
@@ -591,7 +750,7 @@ def main():
     if os.path.exists(out):
         os.remove(out)
     steps = [f"timeout -k 10 {a.timeout} {sys.executable} {os.path.abspath(__file__)} --case {s} --iters {a.iters} --rounds {a.rounds} --chunks-per-split {a.chunks_per_split} --out {out}"
-             for s in list(SHAPES) + list(RAGGED) + list(GQA) + list(PROMPT) + list(WINDOW) + list(WINDOW_PROMPT) + list(STARTS) + list(PAGED)]
+             for s in list(SHAPES) + list(RAGGED) + list(GQA) + list(PROMPT) + list(WINDOW) + list(WINDOW_PROMPT) + list(STARTS) + list(PAGED) + list(FORK)]
     rc = subprocess.call(" && ".join(steps), shell=True)
     if rc == 0 and a.parent_json:
         merge_parent(out, a.parent_json)

@@ -632,6 +632,31 @@ int bfpq_kv_attend_rows_paged(const void* q_dev, const void* k_codes_dev, const 
                               const uint8_t* exp_win_dev, void* score_ws_dev, int64_t score_ws_bytes, void* sum_ws_dev, int64_t sum_ws_bytes,
                               int64_t chunks_per_split, int64_t row0, int64_t rows, const int32_t* page_table_dev, int64_t page_tokens,
                               int64_t pages, void* stream);
+/* Pages shared between the sequences of a paged cache (csrc/bfpq_kvpages.hip).  Replaces the reference's _reorder_cache
+ * (modeling_gpt2.py:1370-1379, and the same in LLaMA and OPT): past_state.index_select(0, beam_idx) of every layer's keys and values at
+ * every step of a beam search.  A full page is immutable (key rows are final once appended, token blocks of V once closed, and pages hold
+ * whole blocks), so the caller reorders by editing page_table rows, which may then name one page more than once; what is left for the
+ * device is one job per new row that does not simply stay what it was, jobs_dev int32 [n_jobs, 5] on the device:
+ *   src_row, dst_row   sequences in 0 .. B - 1: dst_row becomes what src_row is
+ *   src_page, dst_page pages in 0 .. pages - 1: the open page of src_row copied into a page no job reads (all kv_heads heads of the
+ *                      four pool arrays; their layout as above, ldd = D rounded up to 64), or both -1: no page to copy
+ *   tokens             the length of src_row the caller planned the pages with
+ * Two launches, so that rows may be each other's source (a cycle).  The first copies the pages (16-byte vector loads and stores; every
+ * piece is a multiple of 16 bytes) and stages v_tail[src_row] and lens_dev[src_row] of every job in stage_dev; it stages the length only
+ * where it equals `tokens`, else 0, setting overflow_dev[0] to 1 (left so, as by a refused append): a wrong count gives an empty row,
+ * never one that reads pages it was not given.  The second writes v_tail[dst_row] and lens_dev[dst_row] from stage_dev.  A job with a row
+ * or a page outside its range (or one page of -1 only) does nothing in either launch and sets overflow_dev[0]: a bad list cannot fault.
+ * Two jobs with one dst_row, or a dst_page that another job reads, are the caller's error and leave either's bytes.  Nothing is read
+ * back.  stage_dev: bfpq_kv_rows_move_ws_bytes(n_jobs, ...) bytes -- n_jobs * kv_heads * block_size * D elements of dtype, then n_jobs
+ * int32 rounded up to 16 bytes -- 16-byte aligned; that function returns a negative BFPQ_E_* for arguments it does not take.
+ * Unknown dtype / block_size, n_jobs < 0, B or kv_heads < 1, page_tokens not a multiple of 64 or pages < 1: BFPQ_E_ARG; a shape
+ * bfpq_kv_ok(D, page_tokens, block_size) refuses or a size of 2^31 or more: BFPQ_E_UNSUPPORTED; n_jobs of 0 returns 0; a NULL or
+ * misaligned pointer (the pool arrays, v_tail and stage_dev 16 bytes, the int32 arrays 4) or stage_bytes too small: BFPQ_E_ARG.  Every
+ * check returns before anything is launched. */
+int64_t bfpq_kv_rows_move_ws_bytes(int64_t n_jobs, int64_t kv_heads, int64_t D, int block_size, int dtype);
+int bfpq_kv_rows_move(void* k_codes_dev, int8_t* k_exps_dev, void* v_codes_dev, int8_t* v_exps_dev, void* v_tail_dev, int32_t* lens_dev,
+                      int32_t* overflow_dev, const int32_t* jobs_dev, int64_t n_jobs, void* stage_dev, int64_t stage_bytes, int64_t B,
+                      int64_t kv_heads, int64_t D, int block_size, int dtype, int64_t page_tokens, int64_t pages, void* stream);
 /* ---- 2:4-compressed packed weights (format sp24) and their few-token product on v_smfmac_i32_16x16x64_i8 -------------------------
  * A weight pruned N:M with M = 4, N <= 2 along K (_structured_N_M_sparsity, reference bfp_ops.py:73-91) and quantized to HBFP block 64
  * holds at most 2 non-zero codes per group of 4.  sp24 keeps those two codes and their 2-bit positions, tiled for the decode kernel

@@ -10,6 +10,7 @@ Differences from the reference, all documented in DESIGN.md:
   * _unstructured_sparsity: which of the elements EQUAL to the threshold are pruned is "lowest flat
     index first"; the reference's choice is an artefact of a sequential introselect.
 """
+import array
 import collections
 import contextlib
 import math
@@ -1415,7 +1416,21 @@ class HBFPKVCache:
     is -- left untouched, `overflow` raised -- so a captured append stays a captured append.  append(), scores(), context(), attend()
     on both routes, keys() and values() keep their signatures, and every result is, bit for bit, that of the cache without pages given
     the same calls: paging changes where the bytes lie, not what they are.  Composes with kv_heads, prompt_rows, max_len, causal and
-    return_probs; with starts or window the constructor raises NotImplementedError (paging under a first visible key is not built)."""
+    return_probs; with starts or window the constructor raises NotImplementedError (paging under a first visible key is not built).
+
+    Sequences of a paged cache may share pages (csrc/bfpq_kvpages.hip): a page below a sequence's last one holds finished
+    key rows and closed token blocks only and is never written again, so any number of table rows may name it.  Every page has a
+    reference count, and is free exactly when it is 0:
+
+        cache.reorder(index, tokens=None)   # new sequence b becomes old sequence index[b]: the reference's _reorder_cache, a beam
+                                            # search's index_select(0, beam_idx), as a table edit, a copy of at most one page (the
+                                            # open one) per duplicate and a move of v_tail and the lengths; then reserve(), append()
+        cache.fork(src, dst, tokens=None)   # dst (an int or ints) become copies of src: a prompt appended and attended once
+        cache.pages_shared                  # pages that more than one sequence names
+        cache.page_refs                     # the counts, a host list (a copy)
+
+    release(b) and reset() return a shared page to the pool when its last owner lets go.  No kernel of the cache changes: they read
+    the table at launch.  What is not protected is said at reorder()."""
 
     window = None                  # no window, and ...
     starts = None                  # ... no starts, unless the constructor is given them
@@ -1519,11 +1534,17 @@ class HBFPKVCache:
                 self.starts = z(B, dt=torch.int32)                # the first visible key of every sequence: written by the caller
             if page_tokens:
                 self.page_tokens, self.page_count = page_tokens, pages
-                self.page_table = torch.full((B, capacity // page_tokens), -1, dtype=torch.int32, device=device)
+                width = capacity // page_tokens
+                # the table and, behind it, the job list of a reorder(): one small copy brings both
+                self._table_dev = torch.full((B * (width + native.KV_JOB_WORDS),), -1, dtype=torch.int32, device=device)
+                self.page_table = self._table_dev[:B * width].view(B, width)
                 self.pages = native.KVPages(self.page_table, page_tokens, pages, capacity)
                 self._table_host = torch.full((B, capacity // page_tokens), -1, dtype=torch.int32)   # the table as reserve() last wrote it
                 self._owned = [[] for _ in range(B)]              # every sequence's pages, in token order
                 self._free = collections.deque(range(pages))      # taken from the left, returned to the right
+                self._refs = [0] * pages                          # table rows that name each page: free exactly when 0
+                self._move_ws = None                              # reorder()'s staging buffer: made by its first call, kept
+                self._uploads, self._upload_at = None, 0          # reorder()'s pinned host buffers, used in turn, each with an event
 
     # ---- the pages of a paged cache: host lists, nothing read back ---------------------------------------------------------------
     def _paged(self, what):
@@ -1546,6 +1567,8 @@ class HBFPKVCache:
             n = len(self._owned[b])
             self._table_host[b, n:n + len(pg)] = torch.tensor(pg, dtype=torch.int32)
             self._owned[b].extend(pg)
+            for p in pg:
+                self._refs[p] = 1
         lo, hi = min(grants), max(grants) + 1
         self.page_table[lo:hi].copy_(self._table_host[lo:hi])
 
@@ -1585,15 +1608,177 @@ class HBFPKVCache:
             raise ValueError(f"HBFPKVCache.assign: sequence {b} holds {len(self._owned[b])} pages of at most {self._table_host.shape[1]}")
         self._give({b: pages})
 
+    def _drop(self, pages):
+        """one table row lets go of these pages: those no other row names go to the right of the free queue, in this order"""
+        for p in pages:
+            self._refs[p] -= 1
+            if self._refs[p] == 0:
+                self._free.append(p)
+
     def release(self, b):
-        """sequence b's pages go back to the pool; its table row becomes -1 and its length 0"""
+        """sequence b's pages go back to the pool -- those it shares with another sequence (fork, reorder) once the last of them lets
+        go; its table row becomes -1 and its length 0"""
         self._paged('release')
         self._seq('release', b)
-        self._free.extend(self._owned[b])
+        self._drop(self._owned[b])
         self._owned[b] = []
         self._table_host[b] = -1
         self.page_table[b:b + 1].copy_(self._table_host[b:b + 1])
         self.lengths[b:b + 1].zero_()
+
+    # ---- pages shared between sequences (DESIGN 5r): a full page is immutable, so any number of table rows may name it ---------------
+    @property
+    def pages_shared(self):
+        """pages that more than one sequence names"""
+        self._paged('pages_shared')
+        return sum(1 for n in self._refs if n > 1)
+
+    @property
+    def page_refs(self):
+        """how many sequences name each page of the pool (a copy); a page is free exactly when its count is 0"""
+        self._paged('page_refs')
+        return list(self._refs)
+
+    def _plan_reorder(self, index, tokens):
+        """reorder() as a pure function of the host state: (the sequences' new page lists, the new counts, the new free queue, the
+        jobs of native.kv_rows_move).  Raises with nothing changed; ValueError for bad arguments, RuntimeError where the pool has too
+        few pages for the copies"""
+        B, P = self.batch, self.page_tokens
+        if len(index) != B or any(isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < B for i in index):
+            raise ValueError(f"HBFPKVCache.reorder takes {B} sequence indices in 0..{B - 1} (got {index!r})")
+        if len(tokens) != B or any(isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= self.capacity for n in tokens):
+            raise ValueError(f"HBFPKVCache.reorder: tokens must be {B} ints in 0..{self.capacity}, the sequences' lengths (got {tokens!r})")
+        heirs = {}                                                # source -> the new rows it becomes, ascending
+        for b, s in enumerate(index):
+            heirs.setdefault(s, []).append(b)
+        for s in heirs:
+            if tokens[s] > len(self._owned[s]) * P:
+                raise ValueError(f"HBFPKVCache.reorder: sequence {s} has pages for {len(self._owned[s]) * P} tokens, tokens says {tokens[s]}")
+        owned, refs, copies = [None] * B, list(self._refs), {}    # copies: the rows that get a fresh page -> its slot
+        for s, rows in heirs.items():
+            own = self._owned[s]
+            if len(rows) == 1:
+                owned[rows[0]] = own                              # the only heir: the list moves with the table row
+                continue
+            full, open_page = tokens[s] // P, tokens[s] % P != 0
+            heir = s if index[s] == s else rows[0]                # keeps s's open page and whatever s had reserved beyond it
+            shared = own[:full]
+            for p in shared:
+                refs[p] += len(rows) - 1
+            for b in rows:
+                if b == heir:
+                    owned[b] = own
+                elif open_page:
+                    owned[b], copies[b] = shared + [-1], full
+                else:
+                    owned[b] = list(shared)
+        free = list(self._free)
+        for s in range(B):                                        # what no new row names is released, in row order, and may serve below
+            if s not in heirs:
+                for p in self._owned[s]:
+                    refs[p] -= 1
+                    if refs[p] == 0:
+                        free.append(p)
+        if len(copies) > len(free):
+            raise RuntimeError(f"HBFPKVCache.reorder: the pool is exhausted: {len(copies)} pages wanted for the open pages of duplicated "
+                               f"sequences, {len(free)} of {self.page_count} free or released by this call")
+        jobs, taken = [], 0
+        for b, s in enumerate(index):
+            if b == s:
+                continue                                          # its own heir: nothing moves
+            src_page = dst_page = -1
+            if b in copies:
+                at = copies[b]
+                src_page, dst_page, taken = self._owned[s][at], free[taken], taken + 1
+                owned[b][at], refs[dst_page] = dst_page, 1
+            jobs.append((s, b, src_page, dst_page, tokens[s]))
+        return owned, refs, collections.deque(free[taken:]), jobs
+
+    def reorder(self, index, tokens=None):
+        """new sequence b becomes old sequence index[b] (the reference's _reorder_cache, index_select(0, beam_idx)): B ints in
+        0..B-1 as a list or an integer tensor -- a tensor is read back to the host, one synchronisation.  tokens: the B old lengths
+        as host ints; None reads cache.lengths back in that same synchronisation.  Full pages are shared, not copied: with L =
+        tokens[s] and old sequence s named by k new rows, the L // P full pages are named by all k; if L % P != 0 one heir -- row s
+        itself if index[s] == s, else the lowest such row -- keeps s's open page and what s had reserved beyond it, and each of
+        the other k - 1 rows gets a fresh page from the left of the free queue, into which the device copies the open page, and
+        nothing beyond it: call reserve() afterwards, as before any append.  Old sequences nobody names are released, and their
+        pages may serve as fresh ones in the same call.  RuntimeError, with nothing changed, where the pool is short of the
+        sum over s of (k_s - 1) * (L_s % P != 0) pages.  On the device (native.kv_rows_move, two launches, one small copy of the job
+        list): v_tail and the length of every row that is not its own heir follow; rows with index[b] == b cost nothing.  A
+        length travels only if it equals tokens[s]: a wrong count leaves the new row empty and sets `overflow` -- release() such a
+        row -- and never gives a row that attends over pages it was not given.  Plans on the host, so it is not for a captured
+        graph; captured steps replayed afterwards follow the new table.
+
+        Not protected: a caller who writes cache.lengths[b] downwards on a row that shares pages and then appends overwrites pages
+        other sequences read; release(b) is the way to reuse a row.  Speculative rollback is not part of this."""
+        self._paged('reorder')
+        on_host = not isinstance(index, torch.Tensor)
+        if not on_host and (index.dim() != 1 or index.dtype.is_floating_point or index.dtype.is_complex or index.dtype == torch.bool):
+            raise ValueError(f"HBFPKVCache.reorder: index must be a list or an integer tensor [{self.batch}] (got {index.dtype}, "
+                             f"{tuple(index.shape)})")
+        if tokens is None:
+            if not on_host and index.device == self.lengths.device and index.numel() == self.batch:
+                both = torch.cat([index.to(torch.int64), self.lengths.to(torch.int64)]).tolist()      # the one synchronisation
+                index, tokens = both[:self.batch], both[self.batch:]
+            else:
+                tokens = self.lengths.tolist()
+        if isinstance(index, torch.Tensor):
+            index = index.tolist()
+        if not isinstance(index, (list, tuple, range)) or not isinstance(tokens, (list, tuple)):
+            raise ValueError(f"HBFPKVCache.reorder takes {self.batch} indices (a list or an integer tensor) and tokens=None or "
+                             f"{self.batch} ints (got {index!r}, {tokens!r})")
+        index, tokens = list(index), list(tokens)
+        self._commit_reorder(*self._plan_reorder(index, tokens))
+
+    def _commit_reorder(self, owned, refs, free, jobs):
+        """the plan becomes the state: the lists, the counts, the queue; the table and the jobs go to the device in one copy that does
+        not wait for the stream (a pinned buffer, four used in turn, each reused only once its last copy has run), then two launches"""
+        self._owned, self._refs, self._free = owned, refs, free
+        B, width = self._table_host.shape
+        flat = [p for own in owned for p in own + [-1] * (width - len(own))] + [w for job in jobs for w in job]
+        host = torch.frombuffer(array.array('i', flat), dtype=torch.int32)
+        self._table_host.copy_(host[:B * width].view(B, width))
+        dev, n = self.k_codes.device, len(flat)
+        if jobs and self._move_ws is None:                        # the staging buffer, kept: at most B jobs, one v_tail's worth and B ints
+            ws = native.kv_rows_move_ws_bytes(B, self.kv_heads, self.head_dim, self.block, self.dtype)
+            self._move_ws = torch.empty(ws, dtype=torch.uint8, device=dev)
+        if dev.type != 'cuda':
+            self._table_dev[:n].copy_(host)                       # (device='meta': no memory behind the buffers, the plan is all there is)
+            return
+        with torch.cuda.device(dev):
+            if self._uploads is None:
+                self._uploads = [(torch.empty(self._table_dev.numel(), dtype=torch.int32).pin_memory(), torch.cuda.Event()) for _ in range(4)]
+            pinned, event = self._uploads[self._upload_at]
+            self._upload_at = (self._upload_at + 1) % len(self._uploads)
+            event.synchronize()
+            pinned[:n].copy_(host)
+            self._table_dev[:n].copy_(pinned[:n], non_blocking=True)
+            event.record()
+        if not jobs:
+            return
+        native.kv_rows_move(self.k_codes, self.k_exps, self.v_codes, self.v_exps, self.v_tail, self.lengths, self.overflow,
+                            self._table_dev[B * width:n].view(len(jobs), native.KV_JOB_WORDS), self._move_ws, self.kv_heads, self.block,
+                            self.pages)
+
+    def fork(self, src, dst, tokens=None):
+        """sequence(s) dst -- an int or distinct ints, none of them src -- become copies of sequence src that share its full pages
+        (a prompt appended and attended once, then fork(0, range(1, B))): reorder() with the identity except index[d] = src.  tokens:
+        src's length as a host int; None reads it back.  What the dst rows held is released"""
+        self._paged('fork')
+        self._seq('fork', src)
+        if isinstance(dst, (bool, str)) or not isinstance(dst, (int, list, tuple, range)):
+            raise ValueError(f"HBFPKVCache.fork: dst must be a sequence index or a list of them (got {dst!r})")
+        dst = [dst] if isinstance(dst, int) else list(dst)
+        for d in dst:
+            self._seq('fork', d)
+        if src in dst or len(set(dst)) != len(dst):
+            raise ValueError(f"HBFPKVCache.fork takes distinct destinations, none the source {src} (got {dst!r})")
+        if tokens is None:
+            tokens = int(self.lengths[src].item())
+        if isinstance(tokens, bool) or not isinstance(tokens, int) or not 0 <= tokens <= self.capacity:
+            raise ValueError(f"HBFPKVCache.fork: tokens must be an int in 0..{self.capacity}, the length of sequence {src} (got {tokens!r})")
+        index = [src if b in dst else b for b in range(self.batch)]
+        self._commit_reorder(*self._plan_reorder(index, [tokens if b == src else 0 for b in range(self.batch)]))
 
     @property
     def head_cap(self):
@@ -1623,7 +1808,8 @@ class HBFPKVCache:
 
     def reset(self):
         if self.pages is not None:
-            self._free.extend(p for own in self._owned for p in own)
+            for own in self._owned:
+                self._drop(own)
             self._owned = [[] for _ in range(self.batch)]
             self._table_host.fill_(-1)
             self.page_table.fill_(-1)

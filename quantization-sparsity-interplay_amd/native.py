@@ -132,6 +132,8 @@ PROTOTYPES = {
                                     _i64, _vp]),
     "bfpq_kv_attend_rows_paged": (_i32, [_vp] * 8 + [_i64] * 10 + [_dbl, _i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _i64, _vp, _i64, _i64, _i64,
                                          _i64, _vp, _i64, _i64, _vp]),
+    "bfpq_kv_rows_move_ws_bytes": (_i64, [_i64, _i64, _i64, _i32, _i32]),
+    "bfpq_kv_rows_move": (_i32, [_vp] * 8 + [_i64, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _i64, _i64, _vp]),
 }
 
 
@@ -1514,6 +1516,42 @@ def kv_append_dev(k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, length
                                    _ptr(counts), _ptr(overflow), BH, heads, D, t, cap, int(limit), ldd, DTYPE_CODE[k_new.dtype], int(block_size),
                                    int(mant_bits), float(epsilon), _ptr(exp_window_dev(k_new.dtype, dev)), stream), "bfpq_kv_append_dev")
         check(L.bfpq_kv_lens_advance(_ptr(lengths), _ptr(counts), B, t, int(limit), stream), "bfpq_kv_lens_advance")
+
+
+KV_JOB_WORDS = 5                     # a job of kv_rows_move: src_row, dst_row, src_page, dst_page, tokens
+
+
+def kv_rows_move_ws_bytes(n_jobs, kv_heads, D, block_size, dtype):
+    """bytes of the staging buffer kv_rows_move needs for n_jobs jobs (bfpq_kv_rows_move_ws_bytes; no device needed)"""
+    n = int(load_library().bfpq_kv_rows_move_ws_bytes(int(n_jobs), int(kv_heads), int(D), int(block_size), DTYPE_CODE[dtype]))
+    if n < 0:
+        check(n, "bfpq_kv_rows_move_ws_bytes")
+    return n
+
+
+def kv_rows_move(k_codes, k_exps, v_codes, v_exps, v_tail, lengths, overflow, jobs, stage, kv_heads, block_size, pages):
+    """the device side of a reorder of a paged cache's sequences (bfpq_kv_rows_move, include/bfpq.h): jobs int32 [n, 5] on the device
+    (src_row, dst_row, src_page, dst_page, tokens); per job the open page copied into a fresh one, and v_tail and the length of src_row
+    moved to dst_row through `stage` (uint8, kv_rows_move_ws_bytes(n, ...)), the length only where it equals `tokens` (else 0, and
+    overflow[0] set).  Two launches; nothing is read back.  pages: the cache's KVPages"""
+    require_device_tensor(v_tail, "v_tail")
+    dev, B = v_tail.device, lengths.numel()
+    D = v_tail.shape[-1]
+    held = _kv_pages("kv_rows_move", pages, B, kv_heads, dev)
+    _kv_buffers("kv_rows_move", B * kv_heads, D, block_size, k_codes, k_exps, v_codes, v_exps, v_tail, dev, held)
+    _kv_int32("kv_rows_move", "lengths", lengths, B, dev)
+    _kv_int32("kv_rows_move", "overflow", overflow, 1, dev)
+    if not isinstance(jobs, torch.Tensor) or jobs.dim() != 2 or jobs.shape[1] != KV_JOB_WORDS:
+        raise ValueError(f"kv_rows_move: jobs must be int32 [n, {KV_JOB_WORDS}] (got {tuple(getattr(jobs, 'shape', ()))})")
+    n = jobs.shape[0]
+    _kv_int32("kv_rows_move", "jobs", jobs, n * KV_JOB_WORDS, dev)
+    if not isinstance(stage, torch.Tensor) or stage.dtype != torch.uint8 or stage.device != dev or not stage.is_contiguous():
+        raise ValueError(f"kv_rows_move: stage must be a contiguous uint8 tensor on {dev}")
+    with torch.cuda.device(dev):
+        check(load_library().bfpq_kv_rows_move(_ptr(k_codes), _ptr(k_exps), _ptr(v_codes), _ptr(v_exps), _ptr(v_tail), _ptr(lengths),
+                                               _ptr(overflow), _ptr(jobs), n, _ptr(stage), stage.numel(), B, int(kv_heads), D, int(block_size),
+                                               DTYPE_CODE[v_tail.dtype], int(pages.tokens), int(pages.count), _stream(v_tail)),
+              "bfpq_kv_rows_move")
 
 
 def kv_dec_ws_bytes(BH, Tq, D, L, block_size):
