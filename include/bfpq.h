@@ -39,7 +39,7 @@ enum {
 };
 
 /* sizes of the small constant tables the kernels read (built on the host, uploaded by the caller
- * once per device; keeping them caller-owned keeps the library stateless) */
+ * once per device; keeping them caller-owned keeps the library stateless -- but for the pointer pairs of bfpq_nm4_lut_bind) */
 #define BFPQ_EXP_WIN_ENTRIES 320   /* uint8 per unbiased exponent k in [-160, 160)              */
 #define BFPQ_NM4_LUT_ENTRIES 729   /* uint8 keep-mask per 3^6 pairwise-comparison signature     */
 #define BFPQ_NM8_LUT_ENTRIES (1 << 24) /* uint8 prune-mask per (number of smaller keys)^8 vector, 3 bits each */
@@ -65,6 +65,15 @@ const char* bfpq_error_string(int code);
  * used by _structured_N_M_sparsity (bfp_ops.py:85). */
 int bfpq_exp_window_host(int dtype, uint8_t* table_host /* [BFPQ_EXP_WIN_ENTRIES] */);
 int bfpq_nm4_lut_host(int N, uint8_t* lut_host /* [BFPQ_NM4_LUT_ENTRIES] */);
+/* bfpq_nm4_masks_host: the same table expanded for the 16-bit dtypes -- per signature the two AND masks (elements 0,1 | 2,3 as
+ * 0xffff halves) of a group of 4, padded with keep-everything entries to BFPQ_NM4_MASK_BYTES.  Optional: a caller that uploads it
+ * (16-byte aligned) and names it with bfpq_nm4_lut_bind(lut_dev, masks_dev) spares the packed-output kernels the expansion of the byte
+ * table in every workgroup; a LUT pointer that was never bound works as before.  Both device buffers stay the caller's and must
+ * outlive the binding (masks_dev == NULL removes it); at most BFPQ_NM4_BIND_MAX bindings, BFPQ_E_ARG beyond. */
+#define BFPQ_NM4_MASK_BYTES 5888   /* 736 x 2 x uint32 */
+#define BFPQ_NM4_BIND_MAX 64
+int bfpq_nm4_masks_host(int N, uint32_t* masks_host /* [BFPQ_NM4_MASK_BYTES / 4] */);
+int bfpq_nm4_lut_bind(const uint8_t* nm4_lut_dev, const void* masks_dev);
 /* bfpq_nm8_lut_host: PRUNE mask (bit i set = element i zeroed) of one group of 8 for "keep N of 8", indexed by
  * sum_i less_i << (3 i) with less_i = number of keys strictly smaller than key i (this vector identifies the weak
  * ordering of the group, which is all std::nth_element's behaviour depends on).  16 MiB, optional: pass it as nm4_lut_dev

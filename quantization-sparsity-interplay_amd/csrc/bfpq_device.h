@@ -124,7 +124,9 @@ struct FusedArgs {
     int kb_lo, kb_span;       // hot16 path: dtype exponent fields of the block max it takes (kb_span < 0: never)
     uint32_t maxv_c;          //   (2^m - 1) * 2^(e - m) in dtype bits = (fp32-biased e << MBITS) + maxv_c
     SelWs* selws;             // NM == -1 (global magnitude threshold): the select workspace (threshold + tie bookkeeping)
+    const uint2* nm_mask;     // global, kNm4MaskEntries: nm_lut expanded to the AND masks of a 16-bit group (bfpq_nm4_masks_host), or nullptr
 };
+constexpr int kNm4MaskEntries = (BFPQ_NM4_MASK_BYTES) / 8;   // 736: the 729 signatures padded to whole 16-byte loads
 
 // A list of tensors in one launch (bfpq_fake_quantize_batched): up to kMaxBatch descriptors travel in the kernel arguments
 // (no device memory, graph-capturable).  The tensors share dtype / block / mantissa width; each is a flat array of lane
@@ -530,10 +532,11 @@ inline int grid_for_cap(int64_t work_threads, int64_t cap)
     return (int)((g + sweeps - 1) / sweeps);
 }
 inline int grid_for(int64_t work_threads) { return grid_for_cap(work_threads, kMaxGrid); }
-// The packed-output instantiations write a quarter (4-bit codes) or half (e4m3 image) of the bytes they read.  After the r03 diet
-// (83 vector instructions per item instead of 148) and with two sweeps of loads in flight they are bound by bytes in flight, and fit
-// 64 VGPRs: the cap is two workgroups per SIMD slot pair = 2048, one full round of the chip at 8 waves per SIMD (interleaved sweep on
-// [4096,11008] bf16 2:4 packed, tools_dev/ab_packed.py: 1024 workgroups 24.1 us, 1536 24.1, 2048 23.1, 2752 23.4).
-inline int grid_for_packed(int64_t work_threads) { return grid_for_cap(work_threads, (int64_t)kMaxGrid * 2); }
+// The packed-output instantiations write a quarter (4-bit codes) or half (e4m3 image) of the bytes they read, run two sweeps of loads
+// ahead and fit 64 VGPRs (8 waves per SIMD).  With 83 vector instructions per item and 2 of 11 sweeps in the guarded body the cap was
+// 2048 (1536 24.1 us, 2048 23.1, 2752 23.4); with the tail peeled, the mask table copied and 78 per item, fewer and longer sweeps no
+// longer pay for themselves and the e4m3 image's cap wins here too (interleaved on [4096,11008] bf16 2:4 packed, tools_dev/ab_packed.py,
+// fastest-slowest of 7 rounds: 1536 22.82-23.70 us, 2048 22.51-22.78, 2752 21.77-22.15; profiles/packed_sweep.md).
+inline int grid_for_packed(int64_t work_threads) { return grid_for_cap(work_threads, (int64_t)kMaxGrid * 43 / 16); }
 
 }  // namespace bfpq_dev

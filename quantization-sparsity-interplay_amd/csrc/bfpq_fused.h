@@ -25,13 +25,16 @@ __device__ __forceinline__ void fused_flat_body(const FusedArgs& a, [[maybe_unus
     constexpr bool PACK4 = PACK != 0;                            // packed-only output: 4-bit codes + int8 exponents (PACK == 4) or
     constexpr bool MX8 = PACK == 8;                              // e4m3 mantissas + E8M0 block scales (PACK == 8: the matrix unit's image)
     __shared__ __attribute__((aligned(16))) uint8_t s_win[512];
-    __shared__ uint2 s_mask[NM == 4 && VEC == 8 ? 736 : 1];      // 16-bit dtypes: AND masks for the two dwords of a group
+    __shared__ __attribute__((aligned(16))) uint2 s_mask[NM == 4 && VEC == 8 ? kNm4MaskEntries : 1];   // 16-bit dtypes: AND masks for the two dwords of a group
     __shared__ uint8_t s_keep[NM == 4 && VEC == 4 ? 736 : 1];    // fp32: 4-bit keep mask
     __shared__ uint64_t s_kv[NM == 8 ? 8 * kThreads : 1];        // N:8: column per thread for the nth_element replay (rare)
     __shared__ uint4 s_f32t[F32IMG ? kThreads / 64 : 1][F32IMG ? 128 : 1];   // fp32 image: a wave's 2 KB on their way to hole-free stores
     // (the tables are filled further down, behind the first tile's load: one memory round trip for everything)
 
     const bool do_quant = a.lpb > 0;
+    constexpr bool IDX32 = PACK4 && !BATCHED;                     // the packed-output sweep (32-bit indices, two sweeps of loads ahead)
+    // host-expanded N:4 masks (a.nm_mask) instead of the expansion below: both flat sweeps (the list kernel keeps the expansion)
+    constexpr bool MASK_TAB = NM == 4 && VEC == 8 && !BATCHED;
     constexpr int kLead = NM == -1 ? kCutWGs : 0;                 // threshold mode: the first workgroups of the grid own the cut segment
     const int64_t stride = (int64_t)(gridDim.x - kLead) * kThreads;
     const int64_t n_round = (a.n_items + kThreads - 1) / kThreads * kThreads;   // uniform trip count per block
@@ -312,7 +315,7 @@ __device__ __forceinline__ void fused_flat_body(const FusedArgs& a, [[maybe_unus
                         // clamp: two v_med3_f32 per dword (bf16, after the unpack) or v_pk_max/min_f16 on the packed halves (fp16).
                         typedef float float2v __attribute__((ext_vector_type(2)));
                         const float2v C2 = {h16.C, h16.C};
-                        uint32_t g[4];
+                        uint32_t se[4], so[4];                                     // float images of the sums: even / odd elements
 #pragma unroll
                         for (int x = 0; x < 4; x++) {
                             float2v v;
@@ -325,12 +328,15 @@ __device__ __forceinline__ void fused_flat_body(const FusedArgs& a, [[maybe_unus
                                 asm("v_pk_max_f16 %0, %1, %2" : "=v"(cl) : "v"(cl), "v"(h16.maxv2 | 0x80008000u));
                                 v = (float2v){fma_mix_f16<false>(cl, h16.C), fma_mix_f16<true>(cl, h16.C)};
                             }
-                            g[x] = __builtin_amdgcn_perm(f2u(v.y), f2u(v.x), 0x0c0c0400u);        // [lo.byte0, hi.byte0, 0, 0]
+                            se[x] = f2u(v.x); so[x] = f2u(v.y);
                         }
-                        uint32_t p0 = __builtin_amdgcn_perm(g[1], g[0], 0x05040100u) & 0x0f0f0f0fu;    // the low nibbles of elements 0..3 / 4..7, one per byte
-                        uint32_t p1 = __builtin_amdgcn_perm(g[3], g[2], 0x05040100u) & 0x0f0f0f0fu;
-                        p0 |= p0 >> 4; p1 |= p1 >> 4;                                                  // bytes 0 and 2 now hold two nibbles each
-                        pack_w = __builtin_amdgcn_perm(p1, p0, 0x06040200u);
+                        // eight low nibbles -> one dword in 8 instructions (13 before: a v_perm per dword, two to join them, two masks, two
+                        // shift-or pairs and a last v_perm).  Byte k of the result is element 2k | element 2k+1 << 4, so the low bytes of
+                        // the EVEN elements' sums go side by side into one dword and those of the odd ones into another, and one
+                        // v_bfi_b32 takes the low nibble of every byte from the first and the high nibble from the second << 4.
+                        const uint32_t ev = __builtin_amdgcn_perm(se[1], se[0], 0x0c0c0400u) | __builtin_amdgcn_perm(se[3], se[2], 0x04000c0cu);
+                        const uint32_t od = __builtin_amdgcn_perm(so[1], so[0], 0x0c0c0400u) | __builtin_amdgcn_perm(so[3], so[2], 0x04000c0cu);
+                        pack_w = bfi_b32(0x0f0f0f0fu, ev, od << 4);
                         pack_e = h16.e;
                     } else {
                     uint32_t q[4];
@@ -365,10 +371,11 @@ __device__ __forceinline__ void fused_flat_body(const FusedArgs& a, [[maybe_unus
                         c[x] = pk_sub_i16(q[x] ^ m, m);                                            // two's complement per half
                     }
                     // eight low nibbles -> one dword: low bytes of the halves side by side, then nibbles of adjacent bytes together
-                    uint32_t p0 = __builtin_amdgcn_perm(c[1], c[0], 0x06040200u) & 0x0f0f0f0fu;   // [c0.lo, c0.hi, c1.lo, c1.hi]
-                    uint32_t p1 = __builtin_amdgcn_perm(c[3], c[2], 0x06040200u) & 0x0f0f0f0fu;
-                    p0 |= p0 >> 4; p1 |= p1 >> 4;                                                  // bytes 0 and 2 now hold two nibbles each
-                    pack_w = __builtin_amdgcn_perm(p1, p0, 0x06040200u);
+                    // (even elements' bytes into one dword, odd ones' into another, one v_bfi_b32: see the signed branch above)
+                    const uint32_t x01 = __builtin_amdgcn_perm(c[1], c[0], 0x06020400u);           // [c0.lo, c1.lo, c0.hi, c1.hi]
+                    const uint32_t x23 = __builtin_amdgcn_perm(c[3], c[2], 0x06020400u);
+                    const uint32_t ev = __builtin_amdgcn_perm(x23, x01, 0x05040100u), od = __builtin_amdgcn_perm(x23, x01, 0x07060302u);
+                    pack_w = bfi_b32(0x0f0f0f0fu, ev, od << 4);
                     pack_e = h16.e;
                     }
                     }
@@ -772,7 +779,6 @@ __device__ __forceinline__ void fused_flat_body(const FusedArgs& a, [[maybe_unus
     // (the packed-output instantiations are bound by vector-instruction issue, not by memory: they index with 32 bits -- byte
     // offsets from a uniform base, one shift per address instead of 64-bit compare / select / shift-add chains; the launcher
     // cuts a tensor beyond 2^28 lane items into pieces)
-    constexpr bool IDX32 = PACK4 && !BATCHED;
     using idx_t = std::conditional_t<IDX32, uint32_t, int64_t>;
     const idx_t last = (idx_t)(a.n_items - 1);
     auto fetch = [&](idx_t i) __attribute__((always_inline)) {
@@ -799,17 +805,38 @@ __device__ __forceinline__ void fused_flat_body(const FusedArgs& a, [[maybe_unus
         };
         const bool win_al = a.exp_win && (reinterpret_cast<uintptr_t>(a.exp_win) & 3u) == 0;
         const bool lut_al = NM == 4 && (reinterpret_cast<uintptr_t>(a.nm_lut) & 3u) == 0;
+        // The masks as the host expanded them (bfpq_nm4_masks_host, bound to the caller's LUT): 368 x 16 bytes, copied by one wide
+        // load per thread and a second one in the first 112 -- no select / or chains per workgroup.  A LUT that nobody bound
+        // (nm_mask == nullptr) is expanded here as before.
+        bool mask_tab = false;
+        if constexpr (MASK_TAB) mask_tab = a.nm_mask != nullptr;
+        constexpr int kMask16 = kNm4MaskEntries / 2;               // 16-byte pieces
+        static_assert(kNm4MaskEntries % 2 == 0 && kMask16 > kThreads && kMask16 <= 2 * kThreads, "two pieces per thread at most");
         uint32_t w = 0, k4 = 0;
+        [[maybe_unused]] uint4 mk0 = make_uint4(0, 0, 0, 0), mk1 = make_uint4(0, 0, 0, 0);
         if (win_al && t < BFPQ_EXP_WIN_ENTRIES / 4) w = reinterpret_cast<const uint32_t*>(a.exp_win)[t];
         if constexpr (NM == 4) {
-            if (lut_al && t < BFPQ_NM4_LUT_ENTRIES / 4) k4 = reinterpret_cast<const uint32_t*>(a.nm_lut)[t];
+            if (mask_tab) {
+                if constexpr (MASK_TAB) {
+                    const uint4* m4 = reinterpret_cast<const uint4*>(a.nm_mask);
+                    mk0 = m4[t];
+                    if (t < kMask16 - kThreads) mk1 = m4[kThreads + t];
+                }
+            }
+            else if (lut_al && t < BFPQ_NM4_LUT_ENTRIES / 4) k4 = reinterpret_cast<const uint32_t*>(a.nm_lut)[t];
             else if (lut_al && t == BFPQ_NM4_LUT_ENTRIES / 4) k4 = a.nm_lut[BFPQ_NM4_LUT_ENTRIES - 1];    // 729 = 4 * 182 + 1
         }
         if (win_al) { if (t < 128) reinterpret_cast<uint32_t*>(s_win)[t] = w; }
         else
             for (int i = t; i < 512; i += kThreads) s_win[i] = (a.exp_win && i < BFPQ_EXP_WIN_ENTRIES) ? a.exp_win[i] : 0;
         if constexpr (NM == 4) {
-            if (lut_al) {
+            if (mask_tab) {
+                if constexpr (MASK_TAB) {
+                    uint4* s4 = reinterpret_cast<uint4*>(s_mask);
+                    s4[t] = mk0;
+                    if (t < kMask16 - kThreads) s4[kThreads + t] = mk1;
+                }
+            } else if (lut_al) {
 #pragma unroll
                 for (int j = 0; j < 4; j++)
                     if (4 * t + j < BFPQ_NM4_LUT_ENTRIES) put(4 * t + j, (k4 >> (8 * j)) & 0xffu);
@@ -859,10 +886,26 @@ __device__ __forceinline__ void fused_flat_body(const FusedArgs& a, [[maybe_unus
             c1 = fetch(item + 4 * strd);
             body(std::false_type{}, (int64_t)(item + 2 * strd), u4(c2));
         }
-        for (; item < n_rnd; item += strd) {
+        // The 0..2 full sweeps the loop above left: unguarded like every full sweep, peeled -- the register sets keep their names
+        // (c0, c1 are loaded or in flight; the third set takes the tile behind them, index clamped as ever).  Rolled through the
+        // guarded body, as they were, 2 of the flagship tensor's 11 items per wave paid its 64-bit compare, branchy stores and two
+        // register-set copies for a guard that 6 workgroups in 2002 need.
+        const idx_t left = full - sweep;                                   // block-uniform
+        u4v ct = c0;                                                       // the ragged sweep's tile: whichever set holds it
+        if (left != 0) {
             const u4v c2 = fetch(item + 2 * strd);
-            body(std::true_type{}, (int64_t)item, u4(c0));
-            c0 = c1; c1 = c2;
+            body(std::false_type{}, (int64_t)item, u4(c0));
+            if (left == 2) {
+                body(std::false_type{}, (int64_t)(item + strd), u4(c1));
+                ct = c2; item += 2 * strd;
+            } else { ct = c1; item += strd; }
+        }
+        // The ragged last sweep (block-uniform: the workgroup's chunk starts inside the tensor).  A wave whose 64 items all
+        // exist runs the unguarded body there too; only the wave that straddles the end, and those behind it, take the guard.
+        if (item < n_rnd) {
+            const uint32_t wave0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)item);     // lane 0's item: the wave's first
+            if (wave0 + 63u < (uint32_t)a.n_items) body(std::false_type{}, (int64_t)item, u4(ct));
+            else body(std::true_type{}, (int64_t)item, u4(ct));
         }
         asm volatile("" : : "v"(dummy));
         return;
@@ -876,11 +919,21 @@ __device__ __forceinline__ void fused_flat_body(const FusedArgs& a, [[maybe_unus
         c0 = fetch(item + 2 * strd);
         body(std::false_type{}, (int64_t)(item + strd), u4(c1));
     }
-    // remaining full sweep (0..1) and the ragged last one: guarded, rolled (block-uniform trip count)
-    for (; item < n_rnd; item += strd) {
-        const u4v c1 = fetch(item + strd);
-        body(std::true_type{}, (int64_t)item, u4(c0));
-        c0 = c1;
+    // The full sweep the loop above left (0..1) and the ragged last one, as in the packed sweep: the full one unguarded and peeled, the
+    // guard only in a wave that holds an item past the end.  (Rolled through the guarded body, as both were, 2 of the headline tensor's
+    // 22 items per wave took it: interleaved A/B with the host-expanded masks, tools_dev/ab.py, 31.40-32.19 -> 30.76-31.12 us.)
+    {
+        u4v ct = c0;
+        if (sweep < full) {
+            const u4v c1 = fetch(item + strd);
+            body(std::false_type{}, (int64_t)item, u4(c0));
+            ct = c1; item += strd;
+        }
+        if (item < n_rnd) {
+            const int64_t wave0 = uniform64((int64_t)item - (threadIdx.x & 63));
+            if (wave0 + 63 < a.n_items) body(std::false_type{}, (int64_t)item, u4(ct));
+            else body(std::true_type{}, (int64_t)item, u4(ct));
+        }
     }
     asm volatile("" : : "v"(dummy));                                       // the dummy's only "use": after all the work
 }

@@ -18,6 +18,7 @@
 #include <math.h>
 #include <string.h>
 #include <type_traits>
+#include <mutex>
 #include "bfpq.h"
 #include "bfpq_common.h"
 #include "nm_select.h"
@@ -608,6 +609,49 @@ uint64_t bfpq_nm_prune_mask_host(const uint32_t* keys, int N, int M)
     return nm_prune_mask(v, N, M);
 }
 
+// LUT pointer -> its expanded masks (bfpq_nm4_lut_bind).  A handful of entries, written once per (N, device) by the caller's set-up
+// and read by every N:4 launch of the packed-output kernels: a fixed array under one mutex.
+static std::mutex g_nm4_bind_mu;
+static struct { const uint8_t* lut; const void* masks; } g_nm4_bind[BFPQ_NM4_BIND_MAX];
+
+static const uint2* nm4_masks_of(const uint8_t* lut)
+{
+    if (!lut) return nullptr;
+    std::lock_guard<std::mutex> lk(g_nm4_bind_mu);
+    for (int i = 0; i < BFPQ_NM4_BIND_MAX; i++)
+        if (g_nm4_bind[i].lut == lut) return reinterpret_cast<const uint2*>(g_nm4_bind[i].masks);
+    return nullptr;
+}
+
+int bfpq_nm4_lut_bind(const uint8_t* lut_dev, const void* masks_dev)
+{
+    if (!lut_dev || (reinterpret_cast<uintptr_t>(masks_dev) & 15u)) return BFPQ_E_ARG;
+    std::lock_guard<std::mutex> lk(g_nm4_bind_mu);
+    int slot = -1;
+    for (int i = 0; i < BFPQ_NM4_BIND_MAX; i++) {
+        if (g_nm4_bind[i].lut == lut_dev) { slot = i; break; }
+        if (slot < 0 && !g_nm4_bind[i].lut) slot = i;
+    }
+    if (!masks_dev) { if (slot >= 0 && g_nm4_bind[slot].lut == lut_dev) g_nm4_bind[slot] = {nullptr, nullptr}; return 0; }
+    if (slot < 0) return BFPQ_E_ARG;
+    g_nm4_bind[slot] = {lut_dev, masks_dev};
+    return 0;
+}
+
+int bfpq_nm4_masks_host(int N, uint32_t* masks)
+{
+    uint8_t lut[BFPQ_NM4_LUT_ENTRIES];
+    if (!masks) return BFPQ_E_ARG;
+    const int rc = bfpq_nm4_lut_host(N, lut);
+    if (rc) return rc;
+    for (int i = 0; i < kNm4MaskEntries; i++) {            // (the kernel's own expansion, once: see the table set-up of fused_flat_body)
+        const uint32_t k = i < BFPQ_NM4_LUT_ENTRIES ? lut[i] : 0x0fu;
+        masks[2 * i] = ((k & 1u) ? 0xffffu : 0u) | ((k & 2u) ? 0xffff0000u : 0u);
+        masks[2 * i + 1] = ((k & 4u) ? 0xffffu : 0u) | ((k & 8u) ? 0xffff0000u : 0u);
+    }
+    return 0;
+}
+
 int bfpq_nm4_lut_host(int N, uint8_t* lut)
 {
     if (!lut || N < 1 || N > 4) return BFPQ_E_ARG;
@@ -677,6 +721,7 @@ int bfpq_quantize_nm(const void* in, void* out_deq, void* out_codes, int8_t* out
         a.in = src; a.out_deq = deq; a.out_codes = out_codes; a.out_exp = out_exp;
         a.n_items = rows * cols / dtype_vec(dtype);
         a.seed = stoch_seed; a.N = n; a.nm_lut = lut; a.code_bits = code_bits;
+        if (M == 4 && dtype != BFPQ_F32) a.nm_mask = nm4_masks_of(lut);
         return a;
     };
 
@@ -741,6 +786,7 @@ int bfpq_quantize_mx8_nm(const void* in, void* out8, void* out_scale, int64_t ro
     if (!aligned16(in) || (reinterpret_cast<uintptr_t>(out8) & 7u) || (reinterpret_cast<uintptr_t>(out_scale) & 7u)) return BFPQ_E_UNSUPPORTED;
     FusedArgs a = mx8_args(in, out8, out_scale, rows * cols / dtype_vec(dtype), dtype, mant_bits, epsilon, exp_win);
     a.nm_lut = nm_lut; a.N = N;
+    if (M == 4 && dtype != BFPQ_F32) a.nm_mask = nm4_masks_of(nm_lut);
     if (dtype == BFPQ_F32) {                                                            // fp32: the general kernel, image bytes in its store epilogue
         a.code_bits = kCodeBitsE4M3;
         return fused_launch(dtype, a, M, sparsify_first != 0, (hipStream_t)stream);

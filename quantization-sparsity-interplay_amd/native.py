@@ -24,6 +24,7 @@ BFPQ_E_UNSUPPORTED = -2
 
 EXP_WIN_ENTRIES = 320
 NM4_LUT_ENTRIES = 729
+NM4_MASK_BYTES = 5888
 NM8_LUT_ENTRIES = 1 << 24
 USE_NM8_TABLE = True               # False: N:8 groups with straddling ties replay nth_element in the kernel (tests)
 SELECT_STATE_BYTES = 80
@@ -39,6 +40,8 @@ PROTOTYPES = {
     "bfpq_error_string": (ctypes.c_char_p, [_i32]),
     "bfpq_exp_window_host": (_i32, [_i32, _vp]),
     "bfpq_nm4_lut_host": (_i32, [_i32, _vp]),
+    "bfpq_nm4_masks_host": (_i32, [_i32, _vp]),
+    "bfpq_nm4_lut_bind": (_i32, [_vp, _vp]),
     "bfpq_nm8_lut_host": (_i32, [_i32, _vp]),
     "bfpq_compact24": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "bfpq_expand24": (_i32, [_vp, _vp, _vp, _i64, _vp]),
@@ -218,8 +221,21 @@ def exp_window_dev(dtype, device):
     return _device_table("win", dtype, device, lambda: exp_window_host(dtype))
 
 
+def nm4_masks_host(N):
+    buf = (ctypes.c_uint8 * NM4_MASK_BYTES)()
+    check(load_library().bfpq_nm4_masks_host(int(N), ctypes.addressof(buf)), "bfpq_nm4_masks_host")
+    return bytes(buf)
+
+
 def nm4_lut_dev(N, device):
-    return _device_table("lut", int(N), device, lambda: nm4_lut_host(N))
+    """the 729-byte table, and behind it (from byte 736 on, 16-byte aligned) its expansion to AND masks, bound to it in the
+    library: the packed-output kernels copy the masks instead of expanding the bytes in every workgroup"""
+    pad = (-NM4_LUT_ENTRIES) % 16
+    first = ("lut", int(N), device.index if device.index is not None else torch.cuda.current_device()) not in _table_cache
+    t = _device_table("lut", int(N), device, lambda: nm4_lut_host(N) + bytes(pad) + nm4_masks_host(N))
+    if first:
+        check(load_library().bfpq_nm4_lut_bind(t.data_ptr(), t.data_ptr() + NM4_LUT_ENTRIES + pad), "bfpq_nm4_lut_bind")
+    return t
 
 
 def nm8_lut_host(N):

@@ -17,6 +17,11 @@ for a in sys.argv[1:]:
 ins = [(torch.randn(rows, cols, generator=torch.Generator().manual_seed(r)) * 0.02).to(torch.bfloat16).to(dev) for r in range(R)]
 outs = [torch.empty_like(x) for x in ins]
 win = native.exp_window_dev(torch.bfloat16, dev); lut = None if MM == 0 else (native.nm4_lut_dev(NN, dev) if MM == 4 else native.nm8_lut_dev(NN, dev))
+if MM == 4:
+    for lib in libs.values():                      # every build that knows the expanded mask table gets the binding the product's loader made
+        if hasattr(lib, "bfpq_nm4_lut_bind"):
+            lib.bfpq_nm4_lut_bind.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+            assert lib.bfpq_nm4_lut_bind(lut.data_ptr(), lut.data_ptr() + 736) == 0
 graphs = {}
 for n, lib in libs.items():
     def run():
@@ -40,4 +45,5 @@ for r in range(ROUNDS):
 bytes_ = rows * cols * 4
 for n, t in times.items():
     med, mn = statistics.median(t), min(t)
-    print(f"{n:10s} median {med:6.2f} us  min {mn:6.2f} us  -> {bytes_/med/1e3:7.1f} GB/s median ({bytes_/med/1e3/8000*100:4.1f}% of 8 TB/s)")
+    print(f"{'':10s} runs, in order: " + " ".join(f"{v:.2f}" for v in t))
+    print(f"{n:10s} median {med:6.2f} us  min {mn:6.2f} us  max {max(t):6.2f} us  -> {bytes_/med/1e3:7.1f} GB/s median ({bytes_/med/1e3/8000*100:4.1f}% of 8 TB/s)")

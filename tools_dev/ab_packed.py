@@ -1,10 +1,11 @@
 """A/B harness for the packed-output kernel: several builds of libbfpq.so in ONE process, interleaved rounds, hipGraph of L
 launches each ([4096,11008] bf16, 2:4 -> HBFP4, 4-bit codes + int8 exponents only).
 usage: python tools_dev/ab_packed.py name=path.so ..."""
-import ctypes, sys, statistics, torch
+import ctypes, os, sys, statistics, torch
 sys.path.insert(0, '.')
 from quantization_sparsity_interplay_amd import native
-rows, cols, L, R, ROUNDS = 4096, 11008, 100, 8, 10
+rows, cols, L, R, ROUNDS = 4096, 11008, 100, 8, int(os.environ.get("ROUNDS", "10"))
+WARM = int(os.environ.get("WARM", "0"))          # untimed interleaved rounds first (the clocks ramp over the first few replays)
 dev = torch.device('cuda:0')
 libs = {}
 for a in sys.argv[1:]:
@@ -25,6 +26,10 @@ ins = [(torch.randn(rows, cols, generator=torch.Generator().manual_seed(r)) * 0.
 codes = [torch.empty(rows, cols // 2, dtype=torch.uint8, device=dev) for _ in range(R)]
 exps = [torch.empty(rows, cols // 64, dtype=torch.int8, device=dev) for _ in range(R)]
 win = native.exp_window_dev(torch.bfloat16, dev); lut = native.nm4_lut_dev(2, dev)
+for lib in libs.values():                          # every build that knows the expanded mask table gets the binding the product's loader made
+    if hasattr(lib, "bfpq_nm4_lut_bind"):
+        lib.bfpq_nm4_lut_bind.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        assert lib.bfpq_nm4_lut_bind(lut.data_ptr(), lut.data_ptr() + 736) == 0
 graphs = {}
 for n, lib in libs.items():
     def run():
@@ -40,12 +45,14 @@ for n, lib in libs.items():
     g.replay(); torch.cuda.synchronize()
     graphs[n] = g
 times = {n: [] for n in libs}
-for r in range(ROUNDS):
+for r in range(-WARM, ROUNDS):
     for n, g in graphs.items():
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(); g.replay(); e1.record(); torch.cuda.synchronize()
-        times[n].append(e0.elapsed_time(e1) * 1e3 / L)
+        if r >= 0:
+            times[n].append(e0.elapsed_time(e1) * 1e3 / L)
 bytes_ = rows * cols * (2 + 0.5 + 1 / 64)
 for n, t in times.items():
     med, mn = statistics.median(t), min(t)
-    print(f"{n:12s} median {med:6.2f} us  min {mn:6.2f} us  -> {bytes_/med/1e3:7.1f} GB/s median ({bytes_/med/1e3/8000*100:4.1f}% of 8 TB/s)")
+    print(f"{n:12s} median {med:6.2f} us  min {mn:6.2f} us  max {max(t):6.2f} us  -> {bytes_/med/1e3:7.1f} GB/s median ({bytes_/med/1e3/8000*100:4.1f}% of 8 TB/s)")
+    print(f"{'':12s} runs, in order: " + " ".join(f"{v:.2f}" for v in t))
