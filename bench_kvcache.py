@@ -28,6 +28,10 @@ scores, softmax, context; modeling_gpt2.py:345-348 with :207, 243) on one MI355X
          reorder, index_select(0, beam_idx) of its five buffers and the lengths, copied back; fork_prompt8_s1024: 8 sequences behind a
          1024-token prompt with 64 own tokens each, the prompt appended and attended once and forked (once) against appended and
          attended by all 8 (each), with the pages in use and shared,
+  c4     (--case c4_*: 4-bit codes; HBFP4 at block 64) the attend leg (c4_gpt2s_b8_s1024, c4_gpt2s_b8_s4096) or the prompt leg
+         (c4_prompt_*) on HBFPKVCache(code_bits=4), contiguous (c4) and paged (c4_paged), against int8 and int8_paged: the same steps
+         on the int8 cache of the same tree, the four alternating in one process; the rows also hold the caches' nbytes().  On a tree
+         without code_bits the two int8 legs run alone: that is the parent's step for --parent-json,
 and, for the cache alone, the append of a prefill chunk of S tokens.  Method of bench_matmul.py: hipGraph replay, the median of the
 replays, the legs alternating round by round in one process.  (A captured append writes at the captured position: every replay redoes the
 same step, which is what is timed.)  On a tree without the cache the cache columns are null and "cache" says "absent".
@@ -433,6 +437,75 @@ def run_paged(name, iters, rounds, out, cps, page_tokens, only=None):
     _append_rows(out, rows)
 
 
+# name: the decode shape or the prompt case it runs with 4-bit codes
+C4 = {"c4_gpt2s_b8_s1024": "gpt2s_b8_s1024", "c4_gpt2s_b8_s4096": "gpt2s_b8_s4096", "c4_prompt_h32_d128_b1_t2048": "prompt_h32_d128_b1_t2048"}
+C4_LEGS = {"c4": dict(code_bits=4), "int8": {}, "c4_paged": dict(code_bits=4, paged=True), "int8_paged": dict(paged=True)}
+
+
+def run_c4(name, iters, rounds, out, cps, page_tokens, only=None):
+    """the legs c4, int8, c4_paged and int8_paged of a c4 case, bf16 and fp32, HBFP4 at block 64 (only: one leg alone, bf16: what a kernel
+    trace is taken from).  The steps are run_paged's: the attend leg of device_leg, or append(prompt) + attend(q, causal=True)"""
+    import torch
+    import quantization_sparsity_interplay_amd as bfpq
+    from quantization_sparsity_interplay_amd.bfp import bfp_ops
+    dev = "cuda:0"
+    base = C4[name]
+    prompt = base in PROMPT
+    if prompt:
+        batch, heads, kvh, T, D, PR = PROMPT[base]
+        lens, Tq = [T] * batch, T
+    else:
+        batch, heads, S, D = SHAPES[base]
+        lens, kvh, Tq = [S] * batch, heads, 1
+    c = CONFIGS["hbfp4_b64"]
+    scale = 1.0 / D ** 0.5
+    has_c4 = hasattr(bfp_ops.HBFPKVCache, 'code_bits')                  # (the parent of DESIGN 5s has the int8 legs only)
+    rows = []
+    for dname in DTYPES if only is None else ("bf16",):
+        dt = dict(bf16=torch.bfloat16, fp32=torch.float32)[dname]
+        gen = torch.Generator().manual_seed(1)
+        k, v = (torch.randn(batch, kvh, max(lens), D, generator=gen).to(dt).to(dev) for _ in range(2))
+        q = torch.randn(batch, heads, Tq, D, generator=gen).to(dt).to(dev)
+        i8 = bfp_ops.F_matmul_bfp(matrix_unit='int8', **bfpq.BFPConfig.hbfp(c['mant_bits'] + 1, c['block_size']).to_kwargs())
+        legs = {}
+        with torch.no_grad():
+            for leg, spec in C4_LEGS.items():
+                if only not in (None, leg) or ('code_bits' in spec and not has_c4):
+                    continue
+                mode = {key: val for key, val in spec.items() if key != 'paged'}
+                if spec.get('paged'):
+                    mode['page_tokens'] = page_tokens
+                if not prompt:
+                    legs[leg] = device_leg(i8, batch, heads, D, lens, k, v, q, dt, dev, iters, rounds, cps, attend=True, kv_heads=kvh, **mode)
+                    continue
+                if spec.get('paged'):
+                    mode['pages'] = batch * (T // page_tokens)
+                cache = i8.kv_cache(batch, heads, D, T, dtype=dt, device=dev, device_lengths=True, kv_heads=kvh, prompt_rows=PR, **mode)
+                if spec.get('paged'):
+                    reserve_interleaved(cache, lens)
+                cache.prepare_attend()
+
+                def step(cache=cache):
+                    cache.lengths.zero_()
+                    cache.append(k, v)
+                    return cache.attend(q, scale, causal=True)
+
+                legs[leg] = (cache, step)
+            med, spread = replay_times([step for _, step in legs.values()], iters, rounds)
+        row = dict(shape=name, batch=batch, heads=heads, kv_heads=kvh, lengths=list(lens), head_dim=D, dtype=dname, config="hbfp4_b64", iters=iters,
+                   rounds=rounds, chunks_per_split=cps, page_tokens=page_tokens)
+        ends = set()
+        for (leg, (cache, _)), m, sp in zip(legs.items(), med, spread):
+            assert cache.overflow.item() == 0
+            ends.add(tuple(cache.lengths.tolist()))
+            row.update({f"{leg}_us": m, f"{leg}_min_max_us": sp, f"{leg}_cache_bytes": cache.nbytes()})
+        assert len(ends) == 1
+        row["lengths_at_end"] = list(ends.pop())
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    _append_rows(out, rows)
+
+
 # name: (batch, heads, head_dim, S): a beam search's step; (batch, heads, head_dim, prompt tokens, own tokens, prompt_rows): a shared prompt
 FORK = {"fork_beam8_gpt2s_s1024": (8, 12, 64, 1024), "fork_beam8_h32_d128_s4096": (8, 32, 128, 4096),
         "fork_prompt8_s1024": (8, 12, 64, 1024, 64, 256)}
@@ -690,6 +763,10 @@ def merge_parent(out, parent_json):
         p = parent.get((r['shape'], r['dtype'], r['config']))
         if p is None:                                                     # (a case the parent cannot hold: the ragged batch)
             continue
+        if r['shape'] in C4:                                              # the parent's int8 steps, contiguous and paged
+            for leg in ("int8", "int8_paged"):
+                r.update({f"parent_{leg}_us": p[f"{leg}_us"], f"parent_{leg}_min_max_us": p[f"{leg}_min_max_us"]})
+            continue
         r.update(parent_fake_us=p['fake_us'], parent_fake_min_max_us=p['fake_min_max_us'], parent_int8_us=p['int8_us'],
                  parent_int8_min_max_us=p['int8_min_max_us'])
     json.dump(rows, open(out, "w"), indent=1)
@@ -697,10 +774,11 @@ def merge_parent(out, parent_json):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--case", choices=sorted(SHAPES) + sorted(RAGGED) + sorted(GQA) + sorted(PROMPT) + sorted(WINDOW) + sorted(WINDOW_PROMPT) + sorted(STARTS) + sorted(PAGED) + sorted(FORK))
+    ap.add_argument("--case", choices=sorted(SHAPES) + sorted(RAGGED) + sorted(GQA) + sorted(PROMPT) + sorted(WINDOW) + sorted(WINDOW_PROMPT) + sorted(STARTS) + sorted(PAGED) + sorted(FORK) + sorted(C4))
     ap.add_argument("--fork-leg", choices=("paged", "select", "once", "each"), help="with a fork_* case: that leg alone (a kernel trace)")
     ap.add_argument("--page-tokens", type=int, default=64, help="with a paged_* case: tokens per page (a multiple of 64)")
     ap.add_argument("--paged-leg", choices=("paged", "full"), help="with a paged_* case: that leg alone, bf16 (a kernel trace)")
+    ap.add_argument("--c4-leg", choices=tuple(C4_LEGS), help="with a c4_* case: that leg alone, bf16 (a kernel trace)")
     ap.add_argument("--window-leg", choices=("window", "starts", "full", "masked"), help="with a window_* / starts_* case: that leg alone, bf16 (a kernel trace)")
     ap.add_argument("--prompt-rows", type=int, help="with a prompt case: the panel size (default: the case's own)")
     ap.add_argument("--prompt-leg", choices=("prompt", "loop16", "matmul"), help="with a prompt case: that leg alone, bf16 (a kernel trace)")
@@ -731,6 +809,8 @@ def main():
         return run_fork_beam(a.case, a.iters, a.rounds, out, a.fork_leg)
     if a.case in FORK:
         return run_fork_prompt(a.case, min(a.iters, 4), a.rounds, out, a.fork_leg)
+    if a.case in C4:
+        return run_c4(a.case, min(a.iters, 4) if C4[a.case] in PROMPT else a.iters, a.rounds, out, a.chunks_per_split, a.page_tokens, a.c4_leg)
     if a.case in PAGED:
         return run_paged(a.case, min(a.iters, 4) if PAGED[a.case] in PROMPT else a.iters, a.rounds, out, a.chunks_per_split, a.page_tokens, a.paged_leg)
     if a.case in WINDOW or a.case in STARTS:
@@ -750,7 +830,7 @@ def main():
     if os.path.exists(out):
         os.remove(out)
     steps = [f"timeout -k 10 {a.timeout} {sys.executable} {os.path.abspath(__file__)} --case {s} --iters {a.iters} --rounds {a.rounds} --chunks-per-split {a.chunks_per_split} --out {out}"
-             for s in list(SHAPES) + list(RAGGED) + list(GQA) + list(PROMPT) + list(WINDOW) + list(WINDOW_PROMPT) + list(STARTS) + list(PAGED) + list(FORK)]
+             for s in list(SHAPES) + list(RAGGED) + list(GQA) + list(PROMPT) + list(WINDOW) + list(WINDOW_PROMPT) + list(STARTS) + list(PAGED) + list(FORK) + list(C4)]
     rc = subprocess.call(" && ".join(steps), shell=True)
     if rc == 0 and a.parent_json:
         merge_parent(out, a.parent_json)

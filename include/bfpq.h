@@ -666,6 +666,54 @@ int64_t bfpq_kv_rows_move_ws_bytes(int64_t n_jobs, int64_t kv_heads, int64_t D, 
 int bfpq_kv_rows_move(void* k_codes_dev, int8_t* k_exps_dev, void* v_codes_dev, int8_t* v_exps_dev, void* v_tail_dev, int32_t* lens_dev,
                       int32_t* overflow_dev, const int32_t* jobs_dev, int64_t n_jobs, void* stage_dev, int64_t stage_bytes, int64_t B,
                       int64_t kv_heads, int64_t D, int block_size, int dtype, int64_t page_tokens, int64_t pages, void* stream);
+/* A device-length cache that holds 4-bit codes (csrc/bfpq_kvcache.hip, the C4 instances).  What the reference keeps as layer_past
+ * (modeling_gpt2.py:345-348, 415-419; modeling_llama.py:385-409 for grouped queries) and quantizes again at every step is, for
+ * mant_bits <= 3, a tensor of codes in -7..7: the two code arrays then hold two codes to a byte and half the bytes,
+ *   k_codes [BH, cap, ldd / 2]   v_codes [BH, D, cap / 2]     (paged: [pages, heads, page_tokens, ldd / 2], [pages, heads, D, page_tokens / 2])
+ * element 2 k of a key row -- of a column of V: token 2 k -- in the low nibble of byte k and element 2 k + 1 in its high nibble, two's
+ * complement: the layout of bfpq_codes4_to_i8 and of bfpq_dequantize with code_bits 4.  The exponent arrays, v_tail, lens, overflow,
+ * starts, the page table, the workspaces and every size and pitch argument (ldd, cap, ldw, w_bstride: still counted in codes) are
+ * unchanged, and the NaN block marker is the exponent byte -128 as before.  The five entries are bfpq_kv_append_dev, bfpq_kv_bmm_dec_gqa,
+ * bfpq_kv_attend_gqa, bfpq_kv_attend_rows and bfpq_kv_rows_move with, in front of the stream: starts_dev and window where the _win entry
+ * has them (the two attends); cap (bfpq_kv_bmm_dec_cb, as bfpq_kv_bmm_dec_paged) and page_table_dev, page_tokens, pages as the _paged
+ * entry has them (all but bfpq_kv_rows_move_cb, which has them already) -- a NULL table with page_tokens == 0 and pages == 0 is the
+ * contiguous cache, and cap is then not read by bfpq_kv_bmm_dec_cb --; and code_bits, 8 or 4.  With code_bits 8 an entry is, argument
+ * for argument and launch for launch, the entry it extends (or its _win / _paged form).  With code_bits 4 the cached operand is loaded
+ * as half the bytes and widened to the same int8 matrix-unit operand in registers, and an append stores whole bytes only: every result
+ * -- the codes read back through bfpq_dequantize, the exponents, lens, overflow, the products, p and the context -- is bit for bit that
+ * of code_bits 8 on the same calls.  bfpq_kv_rows_move_cb copies kv_heads page_tokens ldd / 2 and kv_heads D page_tokens / 2 bytes of a
+ * page's codes (multiples of 16 still); bfpq_kv_rows_move_ws_bytes, bfpq_kv_lens_advance[_paged], bfpq_kv_ok and the workspace sizes
+ * serve both widths.  Errors as the entry each extends, after these, which return before anything is launched: code_bits not 4 or 8, or
+ * 4 with block_size != 64 or (where the entry has one) the cache's mant_bits / w_mant_bits > 3: BFPQ_E_ARG; a table, page_tokens or
+ * pages that are not all absent and not what the _paged entry takes: as there; starts_dev misaligned or window < 0: BFPQ_E_ARG; a
+ * paged cache with starts_dev or window != 0: BFPQ_E_UNSUPPORTED. */
+int bfpq_kv_append_cb(const void* k_new_dev, const void* v_new_dev, void* k_codes_dev, int8_t* k_exps_dev, void* v_codes_dev, int8_t* v_exps_dev,
+                      void* v_tail_dev, const int32_t* lens_dev, const int32_t* counts_dev, int32_t* overflow_dev, int64_t BH, int64_t heads,
+                      int64_t D, int64_t t, int64_t cap, int64_t limit, int64_t ldd, int dtype, int block_size, int mant_bits, double epsilon,
+                      const uint8_t* exp_win_dev, const int32_t* page_table_dev, int64_t page_tokens, int64_t pages, int code_bits,
+                      void* stream);
+int bfpq_kv_bmm_dec_cb(const void* x_dev, const void* wcodes_dev, const int8_t* wexp_dev, void* out_dev, const int32_t* lens_dev, int64_t B,
+                       int64_t heads, int64_t Tq, int64_t group, int64_t Kx, int64_t Nout, int64_t ldx, int64_t ldw, int64_t ldwe,
+                       int64_t w_bstride, int64_t ldo, int family, int dtype, int block_size, int x_mant_bits, int w_mant_bits, double epsilon,
+                       const uint8_t* exp_win_dev, void* ws_dev, int64_t ws_bytes, int64_t chunks_per_split, int64_t cap,
+                       const int32_t* page_table_dev, int64_t page_tokens, int64_t pages, int code_bits, void* stream);
+int bfpq_kv_attend_cb(const void* q_dev, const void* k_codes_dev, const int8_t* k_exps_dev, const void* v_codes_dev, const int8_t* v_exps_dev,
+                      void* out_dev, void* p_dev, const int32_t* lens_dev, int64_t BH, int64_t heads, int64_t Tq, int64_t group, int64_t D,
+                      int64_t max_len, int64_t cap, int64_t ldd, int64_t ldo, int64_t ldp, double scale, int causal, int dtype, int block_size,
+                      int x_mant_bits, int w_mant_bits, double epsilon, const uint8_t* exp_win_dev, void* score_ws_dev, int64_t score_ws_bytes,
+                      void* sum_ws_dev, int64_t sum_ws_bytes, int64_t chunks_per_split, const int32_t* starts_dev, int64_t window,
+                      const int32_t* page_table_dev, int64_t page_tokens, int64_t pages, int code_bits, void* stream);
+int bfpq_kv_attend_rows_cb(const void* q_dev, const void* k_codes_dev, const int8_t* k_exps_dev, const void* v_codes_dev, const int8_t* v_exps_dev,
+                           void* out_dev, void* p_dev, const int32_t* lens_dev, int64_t BH, int64_t heads, int64_t Tq, int64_t group, int64_t D,
+                           int64_t max_len, int64_t cap, int64_t ldd, int64_t ldo, int64_t ldp, double scale, int causal, int dtype,
+                           int block_size, int x_mant_bits, int w_mant_bits, double epsilon, const uint8_t* exp_win_dev, void* score_ws_dev,
+                           int64_t score_ws_bytes, void* sum_ws_dev, int64_t sum_ws_bytes, int64_t chunks_per_split, int64_t row0, int64_t rows,
+                           const int32_t* starts_dev, int64_t window, const int32_t* page_table_dev, int64_t page_tokens, int64_t pages,
+                           int code_bits, void* stream);
+int bfpq_kv_rows_move_cb(void* k_codes_dev, int8_t* k_exps_dev, void* v_codes_dev, int8_t* v_exps_dev, void* v_tail_dev, int32_t* lens_dev,
+                         int32_t* overflow_dev, const int32_t* jobs_dev, int64_t n_jobs, void* stage_dev, int64_t stage_bytes, int64_t B,
+                         int64_t kv_heads, int64_t D, int block_size, int dtype, int64_t page_tokens, int64_t pages, int code_bits,
+                         void* stream);
 /* ---- 2:4-compressed packed weights (format sp24) and their few-token product on v_smfmac_i32_16x16x64_i8 -------------------------
  * A weight pruned N:M with M = 4, N <= 2 along K (_structured_N_M_sparsity, reference bfp_ops.py:73-91) and quantized to HBFP block 64
  * holds at most 2 non-zero codes per group of 4.  sp24 keeps those two codes and their 2-bit positions, tiled for the decode kernel

@@ -1264,7 +1264,7 @@ def _gen_matmul_i8_op(bfp_args, matrix_unit):
 
     def kv_cache(batch, heads, head_dim, capacity, dtype=torch.bfloat16, device='cuda', **mode):
         """an HBFPKVCache under this op's bfp_args; its products count in matmul_stats.cache_calls.  mode: device_lengths=True (and
-        chunks_per_split), kv_heads, prompt_rows, window, starts, page_tokens and pages as HBFPKVCache takes them"""
+        chunks_per_split), kv_heads, prompt_rows, window, starts, page_tokens, pages and code_bits as HBFPKVCache takes them"""
         return HBFPKVCache(batch, heads, head_dim, capacity, dtype=dtype, stats=stats, **mode, **dict(bfp_args, device=device))
 
     bfp_op.__name__ = fake.__name__
@@ -1430,11 +1430,25 @@ class HBFPKVCache:
         cache.page_refs                     # the counts, a host list (a copy)
 
     release(b) and reset() return a shared page to the pool when its last owner lets go.  No kernel of the cache changes: they read
-    the table at launch.  What is not protected is said at reorder()."""
+    the table at launch.  What is not protected is said at reorder().
+
+    code_bits=4 (4-bit codes; needs mant_bits <= 3, device_lengths=True and block_size 64): a code of mant_bits <= 3 lies in
+    -7..7, so the two code buffers hold two to a byte -- k_codes [.., cap, ldd / 2], two codes of a key row along D; v_codes
+    [.., D, cap / 2], two codes of a column along the tokens; element 2 k in the low nibble of byte k, 2 k + 1 in the high one, two's
+    complement: PackedBFP's layout, what native.dequantize(.., code_bits=4) reads -- and half the bytes, paged or not: per token and
+    kv head at D 64, 32 + 1 + 32 + 1 = 66 bytes where the int8 cache takes 130 and bf16 K and V 256.  The exponent buffers, v_tail,
+    lengths, overflow, starts, the page table and the workspaces are unchanged.  The codes are the same integers in a narrower store:
+    the kernels load half the bytes and widen them to the same int8 matrix-unit operand in registers, and every result -- scores(),
+    context(), attend() on both routes, keys(), values(), lengths, overflow -- is bit for bit that of the cache without it on the same
+    calls.  Composes with kv_heads, prompt_rows, max_len, causal, return_probs, chunks_per_split, with starts / window (contiguous) and
+    with page_tokens / pages, fork() and reorder() included.  cache.code_bits reports it.  None or 8 (the default) is the cache above in
+    every respect: the same entries, kernels, buffers and bytes.  Blocks 32 and 16 (a lane's share of a block there is 8 or 4 codes,
+    so 4- and 2-byte loads) and the host-length cache are not built: ValueError."""
 
     window = None                  # no window, and ...
     starts = None                  # ... no starts, unless the constructor is given them
     pages = None                   # no pages either: native.KVPages(page_table, P, N, capacity) of a paged cache
+    code_bits = 8                  # int8 codes, unless the constructor is given code_bits=4
 
     @staticmethod
     def prompt_rows_max(batch, heads, capacity):
@@ -1443,11 +1457,25 @@ class HBFPKVCache:
 
     def __init__(self, batch, heads, head_dim, capacity, dtype=torch.bfloat16, device='cuda', stats=None, device_lengths=False,
                  chunks_per_split=0, max_query_rows=native.KV_DEC_MAX_TOKENS, kv_heads=None, prompt_rows=0, window=None, starts=False,
-                 page_tokens=None, pages=None, **bfp_args):
+                 page_tokens=None, pages=None, code_bits=None, **bfp_args):
         a = unpack_bfp_args(bfp_args)
         if bfp_args:
             raise TypeError(f"HBFPKVCache: unknown arguments {sorted(bfp_args)}")
         kv_cache_config_check(a, head_dim)
+        if code_bits is not None and (isinstance(code_bits, bool) or not isinstance(code_bits, int)):
+            raise TypeError(f"HBFPKVCache: code_bits must be None, 8 or 4 (got {code_bits!r})")
+        if code_bits not in (None, 8, 4):
+            raise ValueError(f"HBFPKVCache: code_bits must be None, 8 or 4 (got {code_bits})")
+        if code_bits == 4:
+            if a['mant_bits'] > native.KV_C4_MAX_MANT:
+                raise ValueError(f"HBFPKVCache: code_bits=4 holds codes in -7..7: mant_bits must be <= {native.KV_C4_MAX_MANT} "
+                                 f"(got {a['mant_bits']})")
+            if a['block_size'] != 64:
+                raise ValueError(f"HBFPKVCache: code_bits=4 with block_size {a['block_size']} is not built (blocks 32 and 16 need 4- and "
+                                 "2-byte loads of a lane's share of a block: a later change); block_size must be 64")
+            if not device_lengths:
+                raise ValueError("HBFPKVCache: code_bits=4 needs device_lengths=True (the host-length cache stays as it is)")
+            self.code_bits = 4
         if dtype not in native.DTYPE_CODE:
             raise TypeError(f"HBFPKVCache: unsupported dtype {dtype}")
         if batch < 1 or heads < 1 or capacity < 1:
@@ -1521,7 +1549,8 @@ class HBFPKVCache:
         B, H, D, cap, blk = batch, kv_heads, head_dim, self.cap, self.block
         z = lambda *shape, dt=torch.int8: torch.zeros(shape, dtype=dt, device=device)
         HB, hc = (pages, page_tokens) if page_tokens else (B, cap)   # the buffers' leading dimension: the pool's pages, or the sequences
-        self.buffers = dict(k_codes=z(HB, H, hc, native.code_pitch(D)), k_exps=z(HB, H, hc, D // blk), v_codes=z(HB, H, D, hc),
+        cpb = 8 // self.code_bits                                 # codes per byte of the two code buffers
+        self.buffers = dict(k_codes=z(HB, H, hc, native.code_pitch(D) // cpb), k_exps=z(HB, H, hc, D // blk), v_codes=z(HB, H, D, hc // cpb),
                             v_exps=z(HB, H, D, hc // blk), v_tail=z(B, H, blk, D, dt=dtype))
         for name, t in self.buffers.items():
             setattr(self, name, t)
@@ -1758,7 +1787,7 @@ class HBFPKVCache:
             return
         native.kv_rows_move(self.k_codes, self.k_exps, self.v_codes, self.v_exps, self.v_tail, self.lengths, self.overflow,
                             self._table_dev[B * width:n].view(len(jobs), native.KV_JOB_WORDS), self._move_ws, self.kv_heads, self.block,
-                            self.pages)
+                            self.pages, code_bits=self.code_bits)
 
     def fork(self, src, dst, tokens=None):
         """sequence(s) dst -- an int or distinct ints, none of them src -- become copies of sequence src that share its full pages
@@ -1864,7 +1893,8 @@ class HBFPKVCache:
                                        or counts.device != self.k_codes.device or not counts.is_contiguous()):
                 raise ValueError(f"HBFPKVCache.append: counts must be a contiguous int32 tensor [{self.batch}] on {self.k_codes.device}")
             native.kv_append_dev(k.contiguous(), v.contiguous(), self.k_codes, self.k_exps, self.v_codes, self.v_exps, self.v_tail, self.lengths,
-                                 counts, self.overflow, self.kv_heads, self.capacity, self.block, self.mant_bits, self.epsilon, pages=self.pages)
+                                 counts, self.overflow, self.kv_heads, self.capacity, self.block, self.mant_bits, self.epsilon, pages=self.pages,
+                                 code_bits=self.code_bits)
             return None
         if self.length + t > self.capacity:
             raise ValueError(f"HBFPKVCache.append: {self.length} + {t} tokens exceed the capacity {self.capacity}")
@@ -1890,7 +1920,7 @@ class HBFPKVCache:
             if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= self.capacity:
                 raise ValueError(f"HBFPKVCache.scores: max_len must be an int in 1..{self.capacity} (got {max_len!r})")
             out = native.kv_bmm_dec_dev(x, self.k_codes, self.k_exps, native.KV_QK, n, self.head_cap, self.lengths, self.kv_heads, self.block,
-                                        self.mant_bits, self.epsilon, group=self.group, pages=self.pages)
+                                        self.mant_bits, self.epsilon, group=self.group, pages=self.pages, code_bits=self.code_bits)
             self.stats.cache_calls += 1
             return self._result(out, Tq)
         S, D, BH, R, m = self.length, self.head_dim, x.shape[0], x.shape[1], self.mant_bits   # R = group * Tq rows per kv head
@@ -1920,7 +1950,7 @@ class HBFPKVCache:
                 raise ValueError(f"HBFPKVCache.context: {Tq} query rows, the workspace was made for max_query_rows={self.max_query_rows}")
             out = native.kv_bmm_dec_dev(x, self.v_codes, self.v_exps, native.KV_PV, self.head_dim, self.head_dim, self.lengths, self.kv_heads,
                                         self.block, self.mant_bits, self.epsilon, ws=self._ws, chunks_per_split=self.chunks_per_split,
-                                        group=self.group, pages=self.pages)
+                                        group=self.group, pages=self.pages, code_bits=self.code_bits)
             self.stats.cache_calls += 1
             return self._result(out, Tq)
         if not isinstance(p, torch.Tensor) or p.dim() != 4 or p.shape[-1] != self.length or self.length < 1:
@@ -1977,14 +2007,14 @@ class HBFPKVCache:
             out, p = native.kv_attend_rows(x, self.k_codes, self.k_exps, self.v_codes, self.v_exps, self.lengths, self.kv_heads, n, float(scale),
                                            bool(causal), self.block, self.mant_bits, self.epsilon, self._rows_ws, self.prompt_rows,
                                            return_probs=bool(return_probs), group=self.group, starts=self.starts, window=self.window,
-                                           pages=self.pages)
+                                           pages=self.pages, code_bits=self.code_bits)
             self.stats.cache_calls += 2
             out = self._result(out, Tq)
             return (out, self._result(p, Tq)) if return_probs else out
         out, p = native.kv_attend(x, self.k_codes, self.k_exps, self.v_codes, self.v_exps, self.lengths, self.kv_heads, n, float(scale),
                                   bool(causal), self.block, self.mant_bits, self.epsilon, self._att_ws, self._ws,
                                   chunks_per_split=self.chunks_per_split, return_probs=bool(return_probs), group=self.group,
-                                  starts=self.starts, window=self.window, pages=self.pages)
+                                  starts=self.starts, window=self.window, pages=self.pages, code_bits=self.code_bits)
         self.stats.cache_calls += 2
         out = self._result(out, Tq)
         return (out, self._result(p, Tq)) if return_probs else out
@@ -2012,27 +2042,29 @@ class HBFPKVCache:
     def keys(self, b=None):
         """the cached keys dequantized, [B, kv_heads, S, D]; with device_lengths those of sequence b, [1, kv_heads, lengths[b], D]"""
         b0, nb, S = self._held(b)
-        BH, D = nb * self.kv_heads, self.head_dim
+        BH, D, cb = nb * self.kv_heads, self.head_dim, self.code_bits
+        Dc = D * cb // 8                                          # bytes of a row's D codes
         if self.pages is not None:
             kc, ke = (self._gathered(t, b, S, 2) for t in (self.k_codes, self.k_exps))   # [kv_heads, tokens, .]
-            c, e = kc[:, :S, :D].reshape(BH * S, D), ke[:, :S].reshape(BH * S, D // self.block)
-            return native.dequantize(c, e, D, self.dtype, self.block, self.mant_bits, 8).view(nb, self.kv_heads, S, D)
-        c = self.k_codes[b0:b0 + nb].view(BH, self.cap, -1)[:, :S, :D].reshape(BH * S, D)
+            c, e = kc[:, :S, :Dc].reshape(BH * S, Dc), ke[:, :S].reshape(BH * S, D // self.block)
+            return native.dequantize(c, e, D, self.dtype, self.block, self.mant_bits, cb).view(nb, self.kv_heads, S, D)
+        c = self.k_codes[b0:b0 + nb].view(BH, self.cap, -1)[:, :S, :Dc].reshape(BH * S, Dc)
         e = self.k_exps[b0:b0 + nb].view(BH, self.cap, -1)[:, :S].reshape(BH * S, D // self.block)
-        return native.dequantize(c, e, D, self.dtype, self.block, self.mant_bits, 8).view(nb, self.kv_heads, S, D)
+        return native.dequantize(c, e, D, self.dtype, self.block, self.mant_bits, cb).view(nb, self.kv_heads, S, D)
 
     def values(self, b=None):
         """the cached values dequantized, [B, kv_heads, S, D]; with device_lengths those of sequence b, [1, kv_heads, lengths[b], D]"""
         b0, nb, S = self._held(b)
-        BH, D, blk = nb * self.kv_heads, self.head_dim, self.block
+        BH, D, blk, cb = nb * self.kv_heads, self.head_dim, self.block, self.code_bits
         Sp = (S + blk - 1) // blk * blk
+        Sc = Sp * cb // 8                                         # bytes of a column's Sp codes
         if self.pages is not None:
-            c = self._gathered(self.v_codes, b, S, 3).reshape(BH * D, -1)[:, :Sp].contiguous()
+            c = self._gathered(self.v_codes, b, S, 3).reshape(BH * D, -1)[:, :Sc].contiguous()
             e = self._gathered(self.v_exps, b, S, 3).reshape(BH * D, -1)[:, :Sp // blk].contiguous()
         else:
-            c = self.v_codes[b0:b0 + nb].view(BH * D, self.cap)[:, :Sp].contiguous()
+            c = self.v_codes[b0:b0 + nb].view(BH * D, -1)[:, :Sc].contiguous()
             e = self.v_exps[b0:b0 + nb].view(BH * D, -1)[:, :Sp // blk].contiguous()
-        v = native.dequantize(c, e, Sp, self.dtype, blk, self.mant_bits, 8)[:, :S]
+        v = native.dequantize(c, e, Sp, self.dtype, blk, self.mant_bits, cb)[:, :S]
         return v.reshape(nb, self.kv_heads, D, S).transpose(-1, -2)
 
 

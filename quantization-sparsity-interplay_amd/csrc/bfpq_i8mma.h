@@ -132,6 +132,24 @@ __device__ __forceinline__ void pack_codes(const uint32_t (&raw)[NE], int n, con
     }
 }
 
+// 8 two's-complement nibbles (value j in nibble j: element 2 k in the low nibble of byte k, 2 k + 1 in its high one) -> 8 int8 bytes in
+// order (the A operand).  Shared by the 2:4 kernels and the 4-bit KV cache
+__device__ __forceinline__ v2i nibbles_to_i8(uint32_t w)
+{
+    // per byte: n -> ((n ^ 8) + 0x78) ^ 0x80 is n sign-extended (no carry leaves the byte: (n ^ 8) + 0x78 <= 0x87)
+    const uint32_t lo = (((w & 0x0f0f0f0fu) ^ 0x08080808u) + 0x78787878u) ^ 0x80808080u;          // values 0, 2, 4, 6
+    const uint32_t hi = ((((w >> 4) & 0x0f0f0f0fu) ^ 0x08080808u) + 0x78787878u) ^ 0x80808080u;   // values 1, 3, 5, 7
+    return v2i{(int)__builtin_amdgcn_perm(hi, lo, 0x05010400u), (int)__builtin_amdgcn_perm(hi, lo, 0x07030602u)};
+}
+
+// ... and back: 8 int8 codes in -8..7, four to a word in order (pack_codes), as one word of nibbles.  The even elements' bytes go side
+// by side into one word and the odd ones' into another; the low nibble of every byte comes from the first, the high one from the second
+__device__ __forceinline__ uint32_t i8_to_nibbles(uint32_t c0123, uint32_t c4567)
+{
+    const uint32_t ev = __builtin_amdgcn_perm(c4567, c0123, 0x06040200u), od = __builtin_amdgcn_perm(c4567, c0123, 0x07050301u);
+    return (ev & 0x0f0f0f0fu) | ((od << 4) & 0xf0f0f0f0u);
+}
+
 // host side: f(std::integral_constant<int, BLK>{}) for a block of 16, 32 or 64, and the argument checks of the entries
 template <class F> void with_block(int block_size, F&& f)
 {

@@ -62,6 +62,12 @@
 // (head_tile: as a scalar) and the next unit's ahead of this unit's loads.  v_tail stays per sequence.  An entry outside the pool is
 // refused by the append (seq_take_at) and clamped by head_at; it is never dereferenced.  The instances without PG never read the
 // descriptor and are the code they were.
+//
+// 4-bit codes: the C4 instances behind the bfpq_kv_*_cb entries, block 64 of the device-length modes.  For mant_bits <= 3
+// the two code tensors hold two codes to a byte (the layout of PackedBFP); the append stores whole bytes, the products load half the
+// bytes and widen them to the int8 operand in registers (k_kv_bmm_dec keeps the prefetched chunk packed; the panel kernels widen on
+// the way into LDS), and from the MFMA on a C4 instance is its int8 twin's code on the same integers.  The instances without C4 are
+// the code they were.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "bfpq.h"
@@ -154,8 +160,30 @@ __device__ __forceinline__ typename I8Blk<BLK>::op_t quant_operand(const uint32_
     else return (long)(((uint64_t)pk[1] << 32) | pk[0]);
 }
 
+// ---- 4-bit codes (the C4 instances): with mant_bits <= 3 a code lies in -7..7 and the two code tensors hold two to a byte --
+// element 2 k of a key row (of a V column: token 2 k) in the low nibble of byte k, 2 k + 1 in its high nibble, two's complement: the
+// layout of PackedBFP and native.dequantize(.., code_bits=4).  Every offset the kernels form counts codes; a C4 instance halves it where
+// it becomes an address (each is even).  A lane's 16 codes of a block are 8 bytes as loaded and become the int8 cache's MFMA operand in
+// registers (widen), so from the MFMA on a C4 instance is its int8 twin's code on the same integers.  A byte is written whole by one
+// thread (narrow): nothing reads, modifies and writes one.  Block 64 and the device-length modes only; the instances without C4 never
+// see any of this and are the code they were
+__device__ __forceinline__ v4i widen(uint2 p)
+{
+    const v2i a = nibbles_to_i8(p.x), b = nibbles_to_i8(p.y);
+    return v4i{a.x, a.y, b.x, b.y};
+}
+__device__ __forceinline__ v4i widen(v4i a) { return a; }        // (the int8 cache: the operand as loaded)
+__device__ __forceinline__ long widen(long a) { return a; }
+// the 16 codes at code offset off of a 4-bit code tensor, widened
+__device__ __forceinline__ v4i load_c4(const int8_t* __restrict__ codes, size_t off)
+{
+    return widen(*reinterpret_cast<const uint2*>(codes + (off >> 1)));
+}
+// 16 int8 codes, four to a word (pack_codes), as their 8 bytes of nibbles
+__device__ __forceinline__ uint2 narrow(const uint32_t (&pk)[4]) { return make_uint2(i8_to_nibbles(pk[0], pk[1]), i8_to_nibbles(pk[2], pk[3])); }
+
 // one token block tb of one 64-column slice of V
-template <int DT, bool PG>
+template <int DT, bool PG, bool C4>
 __device__ __forceinline__ void v_block(const typename Traits<DT>::raw_t* __restrict__ vnew, typename Traits<DT>::raw_t* __restrict__ tail,
                                         int8_t* __restrict__ vcodes, int8_t* __restrict__ vexps, int bh, int tb, int d0, int D, int pos, int t,
                                         int tn, int cap, int block, int mant_bits, float eps_dt, const uint8_t* s_win, uint32_t* s_val, uint32_t* s_max,
@@ -208,8 +236,9 @@ __device__ __forceinline__ void v_block(const typename Traits<DT>::raw_t* __rest
         tbl = sl / block;
     }
     if (d0 + d < D) {
-        int8_t* const dst = vcodes + (hb * D + d0 + d) * cap + tbl * block + sq * per;
-        if (per == 16) *reinterpret_cast<uint4*>(dst) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
+        int8_t* const dst = vcodes + (C4 ? ((hb * D + d0 + d) * cap + tbl * block + sq * per) >> 1 : (hb * D + d0 + d) * cap + tbl * block + sq * per);
+        if constexpr (C4) *reinterpret_cast<uint2*>(dst) = narrow(pk);   // (block 64: per == 16, the thread's 16 tokens are 8 whole bytes)
+        else if (per == 16) *reinterpret_cast<uint4*>(dst) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
         else if (per == 8) *reinterpret_cast<uint2*>(dst) = make_uint2(pk[0], pk[1]);
         else *reinterpret_cast<uint32_t*>(dst) = pk[0];
         if (sq == 0) vexps[(hb * D + d0 + d) * (cap / block) + tbl] = sat_exp(bs);
@@ -242,7 +271,8 @@ __device__ __forceinline__ int seq_take_at(const Pages& pg, const int32_t* __res
 // DEV: the position and the count of head bh are those of its sequence bh / heads, read from device memory (lens, counts or null); t is
 // then the row pitch of k_new / v_new and the most a sequence can take, and the grid is sized for the worst position
 // PG (DEV only): cap is a page's tokens and a token's rows lie where head_at says
-template <int DT, bool DEV, bool PG = false>
+// C4 (DEV and block 64 only): the code tensors hold nibbles; a thread's 16 codes are stored as 8 bytes
+template <int DT, bool DEV, bool PG = false, bool C4 = false>
 __global__ void __launch_bounds__(256) k_kv_append(const void* __restrict__ knew, const void* __restrict__ vnew, int8_t* __restrict__ kcodes,
                                                    int8_t* __restrict__ kexps, int8_t* __restrict__ vcodes, int8_t* __restrict__ vexps,
                                                    void* __restrict__ vtail, int BH, int D, int pos, int t, int cap, int ldd, int block,
@@ -251,6 +281,7 @@ __global__ void __launch_bounds__(256) k_kv_append(const void* __restrict__ knew
                                                    int32_t* __restrict__ overflow, int heads, int limit, Pages pg)
 {
     static_assert(!PG || DEV, "a paged cache keeps its lengths on the device");
+    static_assert(!C4 || DEV, "4-bit codes are the device-length cache's");
     using Tr = Traits<DT>;
     using raw_t = typename Tr::raw_t;
     __shared__ uint8_t s_win[BFPQ_EXP_WIN_ENTRIES];
@@ -291,7 +322,8 @@ __global__ void __launch_bounds__(256) k_kv_append(const void* __restrict__ knew
                 int sl;
                 r = (size_t)head_at<true>(pg, bh, heads, pos + i, sl) * cap + sl;
             }
-            *reinterpret_cast<uint4*>(kcodes + r * ldd + seg * 16) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
+            if constexpr (C4) *reinterpret_cast<uint2*>(kcodes + ((r * ldd + seg * 16) >> 1)) = narrow(pk);
+            else *reinterpret_cast<uint4*>(kcodes + r * ldd + seg * 16) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
             if (seg % per == 0) kexps[r * (D / block) + seg / per] = sat_exp(bs);
         }
         return;
@@ -310,7 +342,7 @@ __global__ void __launch_bounds__(256) k_kv_append(const void* __restrict__ knew
     const int n = (z == 0 && last != first) ? 2 : 1;
     for (int it = 0; it < n; it++) {
         if (it) __syncthreads();                                          // (the first block's tile and tail rows have been read)
-        v_block<DT, PG>(reinterpret_cast<const raw_t*>(vnew), reinterpret_cast<raw_t*>(vtail), vcodes, vexps, bh, it ? last : first + z, dt * kTD, D,
+        v_block<DT, PG, C4>(reinterpret_cast<const raw_t*>(vnew), reinterpret_cast<raw_t*>(vtail), vcodes, vexps, bh, it ? last : first + z, dt * kTD, D,
                         pos, cnt, t, cap, block, mant_bits, eps_dt, s_win, s_val, s_max, pg, heads);
     }
 }
@@ -381,7 +413,9 @@ template <int DT, bool WIN = false> __device__ __forceinline__ void att_scores(v
 // AGPRs and run 1)
 // PG (family qk of a paged cache; not with WIN): wbs is a page's tokens; the 16 TM <= 64 keys of a wave lie in one page, whose head
 // (head_tile) gives the base of the wave's codes and exponents, its rows counted from the page's first token
-template <int BLK, int DT, int TM, int MODE, bool GRP = false, bool WIN = false, bool PG = false>
+// C4 (block 64, not kHost): w holds nibbles.  The chunk in use and the prefetched one stay packed, 2 words per operand instead of 4,
+// and are widened right before the MFMA
+template <int BLK, int DT, int TM, int MODE, bool GRP = false, bool WIN = false, bool PG = false, bool C4 = false>
 __global__ void __launch_bounds__(256, WIN && BLK == 64 ? 2 : 1) k_kv_bmm_dec(const void* __restrict__ x, const int8_t* __restrict__ wc, const int8_t* __restrict__ we,
                                                     void* __restrict__ out, int B, int Tq, int Kx, int Nout, int ldx, int ldw, int ldwe, int wbs,
                                                     int ldo, int xm, int wm, float eps_dt, const uint8_t* __restrict__ exp_win,
@@ -394,6 +428,8 @@ __global__ void __launch_bounds__(256, WIN && BLK == 64 ? 2 : 1) k_kv_bmm_dec(co
     using raw_t = typename Tr::raw_t;
     static_assert(!WIN || MODE == kAtt, "a first key is attention's");
     static_assert(!PG || (MODE != kHost && !WIN), "a paged cache keeps its lengths on the device and has no first key");
+    static_assert(!C4 || (BLK == 64 && MODE != kHost), "4-bit codes: block 64 of a device-length cache");
+    using ld_t = std::conditional_t<C4, uint2, op_t>;            // a lane's codes of a block as loaded
     constexpr bool DEV = MODE != kHost;
     constexpr int ODT = MODE == kAtt ? BFPQ_F32 : DT;            // the output's element type
     constexpr int NBS = 64 / BLK;                                // blocks per 64-byte chunk
@@ -454,18 +490,22 @@ __global__ void __launch_bounds__(256, WIN && BLK == 64 ? 2 : 1) k_kv_bmm_dec(co
         if constexpr (WIN) {
             if (n0 + 16 * TM <= wave_min(tok ? first() : 0x7fffffff)) continue;   // (wave-uniform) no row of the tile sees a key of this wave
         }
-        const int8_t* const wcb = wc + hb * wbs * ldw;
+        const int8_t* const wcb = wc + (C4 ? (hb * wbs * ldw) >> 1 : hb * wbs * ldw);
         const int8_t* const web = we + hb * wbs * ldwe;
         const raw_t* const xr = reinterpret_cast<const raw_t*>(x) + ((size_t)b * R + (tok ? row : 0)) * ldx;
 
         // chunk c: the lane's w codes, the exponents of its four output rows (byte s of a word = block s of the chunk) and its x elements
-        auto load = [&](int c, op_t (&aF)[TM][NBS], uint32_t (&ew)[TM][4], uint32_t (&xv)[NBS][NE]) __attribute__((always_inline)) {
+        auto load = [&](int c, ld_t (&aF)[TM][NBS], uint32_t (&ew)[TM][4], uint32_t (&xv)[NBS][NE]) __attribute__((always_inline)) {
 #pragma unroll
             for (int i = 0; i < TM; i++) {
 #pragma unroll
                 for (int s = 0; s < NBS; s++) {
-                    aF[i][s] = *reinterpret_cast<const op_t*>(wcb + offW[i] + (c << 6) + s * BLK);
-                    if (!Blk::a_live(q)) aF[i][s] = op_t{};
+                    if constexpr (C4) {
+                        aF[i][s] = *reinterpret_cast<const uint2*>(wcb + ((offW[i] + (c << 6)) >> 1));
+                    } else {
+                        aF[i][s] = *reinterpret_cast<const op_t*>(wcb + offW[i] + (c << 6) + s * BLK);
+                        if (!Blk::a_live(q)) aF[i][s] = op_t{};
+                    }
                 }
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
@@ -489,7 +529,7 @@ __global__ void __launch_bounds__(256, WIN && BLK == 64 ? 2 : 1) k_kv_bmm_dec(co
 #pragma unroll
         for (int i = 0; i < TM; i++) acc[i][0] = acc[i][1] = v2f{0.f, 0.f};
 
-        op_t aF[TM][NBS], aN[TM][NBS];
+        ld_t aF[TM][NBS], aN[TM][NBS];
         uint32_t ew[TM][4], ewN[TM][4], xv[NBS][NE], xN[NBS][NE];
         load(0, aF, ew, xv);
 #pragma unroll 1
@@ -507,7 +547,7 @@ __global__ void __launch_bounds__(256, WIN && BLK == 64 ? 2 : 1) k_kv_bmm_dec(co
                     for (int i = 0; i < TM; i++) {
                         v2f sw01, sw23;
                         weight_scales(exp_byte(ew[i][0], sh), exp_byte(ew[i][1], sh), exp_byte(ew[i][2], sh), exp_byte(ew[i][3], sh), wm, sw01, sw23);
-                        rescale(Blk::mfma(aF[i][s], bF, magic), sx, nm, sw01, sw23, acc[i][0], acc[i][1]);
+                        rescale(Blk::mfma(widen(aF[i][s]), bF, magic), sx, nm, sw01, sw23, acc[i][0], acc[i][1]);
                     }
                 }
             }
@@ -712,7 +752,8 @@ __device__ __forceinline__ void form_p(const float* __restrict__ srow, int k0, i
 //
 // PG (not with WIN): cap is a page's tokens; a 64-token chunk lies in one page, whose head is fetched once per chunk (head_tile), the
 // next chunk's ahead of this chunk's loads.
-template <int BLK, int DT, bool ATT, bool GRP = false, bool WIN = false, bool PG = false>
+// C4 (block 64): vc holds nibbles, widened as they are loaded.
+template <int BLK, int DT, bool ATT, bool GRP = false, bool WIN = false, bool PG = false, bool C4 = false>
 __global__ void __launch_bounds__(256) k_kv_pv_split(const void* __restrict__ x, const int8_t* __restrict__ vc, int32_t* __restrict__ sums,
                                                      int8_t* __restrict__ xexp, const int32_t* __restrict__ lens, int heads, int Tq, int L,
                                                      int D, int ldx, int cap, int nbw, int cps, int xvec, int xm, float eps_dt,
@@ -721,6 +762,7 @@ __global__ void __launch_bounds__(256) k_kv_pv_split(const void* __restrict__ x,
 {
     static_assert(!WIN || ATT, "a first key is attention's");
     static_assert(!PG || !WIN, "a paged cache has no first key");
+    static_assert(!C4 || BLK == 64, "4-bit codes: block 64");
     using Blk = I8Blk<BLK>;
     using op_t = typename Blk::op_t;
     using Tr = Traits<DT>;
@@ -815,20 +857,23 @@ __global__ void __launch_bounds__(256) k_kv_pv_split(const void* __restrict__ x,
 
     const int n0 = ((int)blockIdx.x * 4 + w) * 16;
     if (n0 >= D) return;                                         // (wave-uniform; no barrier below.  D % 16 == 0: 16 whole columns)
-    const int8_t* const wrow = vc + ((size_t)bh * D + n0 + r) * cap + Blk::lane(q);
+    const int8_t* const wrow = C4 ? vc + ((((size_t)bh * D + n0 + r) * cap + Blk::lane(q)) >> 1) : vc + ((size_t)bh * D + n0 + r) * cap + Blk::lane(q);
     const v4i magic = {MAGIC_I, MAGIC_I, MAGIC_I, MAGIC_I};
     const size_t o0 = ((size_t)bh * R + r0 + (tok ? r : 0)) * nbw;
     for (int c = c0; c < c1; c++) {
-        const int8_t* wch = wrow + (c << 6);                     // the lane's codes of the chunk
+        const int8_t* wch = wrow + (C4 ? c << 5 : c << 6);       // the lane's codes of the chunk
         if constexpr (PG) {
-            wch = vc + ((size_t)hbN * D + n0 + r) * cap + slN + Blk::lane(q);
+            if constexpr (C4) wch = vc + ((((size_t)hbN * D + n0 + r) * cap + slN + Blk::lane(q)) >> 1);
+            else wch = vc + ((size_t)hbN * D + n0 + r) * cap + slN + Blk::lane(q);
             if (c + 1 < c1) hbN = head_tile<true>(pg, bh, heads, (c + 1) << 6, slN);
         }
 #pragma unroll
         for (int s = 0; s < NBS; s++) {
             const int j = c * NBS + s;
             if (j >= nb) break;                                  // (wave-uniform)
-            op_t aF = *reinterpret_cast<const op_t*>(wch + s * BLK);
+            op_t aF;
+            if constexpr (C4) aF = widen(*reinterpret_cast<const uint2*>(wch));
+            else aF = *reinterpret_cast<const op_t*>(wch + s * BLK);
             if (!Blk::a_live(q)) aF = op_t{};
             const v4i d = Blk::mfma(aF, s_b[c - c0][s][l], magic);
             if (tok) {
@@ -937,7 +982,9 @@ template <int BLK> struct LdsOp {
 // out the tiles below its own rows' least; those columns are not written and the softmax does not read them.
 // PG (not with WIN): cap is a page's tokens; a tile of 64 keys lies in one page, whose head is fetched once per tile (head_tile), the
 // next tile's ahead of this tile's loads.
-template <int BLK, int DT, bool WIN = false, bool PG = false>
+// C4 (block 64): kc holds nibbles.  They are widened on the way into LDS -- once per workgroup, not once per wave at the fragment read --
+// so s_k holds the int8 operands and everything after the tile's load is the int8 instance's code; the LDS bytes stay what they were.
+template <int BLK, int DT, bool WIN = false, bool PG = false, bool C4 = false>
 __global__ void __launch_bounds__(256) k_kv_qk_rows(const void* __restrict__ x, const int8_t* __restrict__ kc, const int8_t* __restrict__ ke,
                                                     float* __restrict__ ws, int Tq, int D, int Nout, int ldd, int cap, int pitch, int xm, int wm,
                                                     float eps_dt, const uint8_t* __restrict__ exp_win, const int32_t* __restrict__ lens, int heads,
@@ -945,6 +992,7 @@ __global__ void __launch_bounds__(256) k_kv_qk_rows(const void* __restrict__ x, 
                                                     int window, Pages pg)
 {
     static_assert(!PG || !WIN, "a paged cache has no first key");
+    static_assert(!C4 || BLK == 64, "4-bit codes: block 64");
     using Blk = I8Blk<BLK>;
     using op_t = typename Blk::op_t;
     using Tr = Traits<DT>;
@@ -1008,7 +1056,8 @@ __global__ void __launch_bounds__(256) k_kv_qk_rows(const void* __restrict__ x, 
         const int8_t* const keb = ke + k0 * nbd;
         for (int idx = tid; idx < 4 * nbd * LN; idx += 256) {    // idx = (16-key tile i, block j, lane slot)
             const int ls = idx % LN, j = (idx / LN) % nbd, i = idx / (LN * nbd);
-            s_k[idx] = *reinterpret_cast<const op_t*>(kcb + (size_t)(16 * i + (ls & 15)) * ldd + j * BLK + Blk::lane(ls >> 4));
+            if constexpr (C4) s_k[idx] = load_c4(kc, (k0 + 16 * i + (ls & 15)) * ldd + j * BLK + Blk::lane(ls >> 4));
+            else s_k[idx] = *reinterpret_cast<const op_t*>(kcb + (size_t)(16 * i + (ls & 15)) * ldd + j * BLK + Blk::lane(ls >> 4));
         }
         for (int idx = tid; idx < 64 * nbd; idx += 256) s_ke[(idx % nbd) * 64 + idx / nbd] = keb[idx];
         __syncthreads();
@@ -1054,7 +1103,8 @@ __global__ void __launch_bounds__(256) k_kv_qk_rows(const void* __restrict__ x, 
 // below a row's first key too.
 // PG (not with WIN): cap is a page's tokens and ldve its blocks; a 64-token chunk lies in one page, whose head is fetched once per chunk
 // (head_tile), the next chunk's ahead of this chunk's loads; the zero-block terms look up the page of their block.
-template <int BLK, int DT, bool WIN = false, bool PG = false>
+// C4 (block 64): vc holds nibbles, widened on the way into LDS as in k_kv_qk_rows.
+template <int BLK, int DT, bool WIN = false, bool PG = false, bool C4 = false>
 __global__ void __launch_bounds__(256) k_kv_pv_rows(const float* __restrict__ ws, const int8_t* __restrict__ vc, const int8_t* __restrict__ ve,
                                                     void* __restrict__ out, void* __restrict__ pout, const int32_t* __restrict__ lens, int heads,
                                                     int Tq, int L, int D, int pitch, int cap, int ldve, int ldo, int ldp, int xm, int wm,
@@ -1062,6 +1112,7 @@ __global__ void __launch_bounds__(256) k_kv_pv_rows(const float* __restrict__ ws
                                                     const int32_t* __restrict__ starts, int window, Pages pg)
 {
     static_assert(!PG || !WIN, "a paged cache has no first key");
+    static_assert(!C4 || BLK == 64, "4-bit codes: block 64");
     using Blk = I8Blk<BLK>;
     using op_t = typename Blk::op_t;
     using Tr = Traits<DT>;
@@ -1141,14 +1192,16 @@ __global__ void __launch_bounds__(256) k_kv_pv_rows(const float* __restrict__ ws
             if (c + 1 < nchw) hbN = head_tile<true>(pg, bh, heads, (c + 1) << 6, slN);
             for (int idx = tid; idx < ndt * NBS * LN; idx += 256) {
                 const int ls = idx % LN, s = (idx / LN) % NBS, i = idx / (LN * NBS);
-                s_v[idx] = *reinterpret_cast<const op_t*>(vc + ((size_t)hb * D + 16 * i + (ls & 15)) * cap + t0 + s * BLK + Blk::lane(ls >> 4));
+                if constexpr (C4) s_v[idx] = load_c4(vc, ((size_t)hb * D + 16 * i + (ls & 15)) * cap + t0 + s * BLK + Blk::lane(ls >> 4));
+                else s_v[idx] = *reinterpret_cast<const op_t*>(vc + ((size_t)hb * D + 16 * i + (ls & 15)) * cap + t0 + s * BLK + Blk::lane(ls >> 4));
             }
             for (int idx = tid; idx < NBS * D; idx += 256)
                 s_ve[idx] = c * NBS + idx / D < nb ? ve[((size_t)hb * D + idx % D) * ldve + t0 / BLK + idx / D] : (int8_t)0;
         } else {
             for (int idx = tid; idx < ndt * NBS * LN; idx += 256) {  // idx = (16-column tile i, block s of the chunk, lane slot)
                 const int ls = idx % LN, s = (idx / LN) % NBS, i = idx / (LN * NBS);
-                s_v[idx] = *reinterpret_cast<const op_t*>(vc + ((size_t)bh * D + 16 * i + (ls & 15)) * cap + (c << 6) + s * BLK + Blk::lane(ls >> 4));
+                if constexpr (C4) s_v[idx] = load_c4(vc, ((size_t)bh * D + 16 * i + (ls & 15)) * cap + (c << 6) + s * BLK + Blk::lane(ls >> 4));
+                else s_v[idx] = *reinterpret_cast<const op_t*>(vc + ((size_t)bh * D + 16 * i + (ls & 15)) * cap + (c << 6) + s * BLK + Blk::lane(ls >> 4));
             }
             for (int idx = tid; idx < NBS * D; idx += 256) {
                 const int j = c * NBS + idx / D;
@@ -1224,33 +1277,42 @@ __global__ void __launch_bounds__(256) k_kv_pv_rows(const float* __restrict__ ws
 
 constexpr int64_t kLim = (int64_t)1 << 31;
 
+// f(std::true_type{}) or f(std::false_type{}) for a flag known at run time
+template <class F> void with_flag(bool on, F&& f)
+{
+    if (on) f(std::true_type{});
+    else f(std::false_type{});
+}
+
 // the tiles of 16 rows a head's group * Tq rows make
 inline int64_t row_tiles(int64_t Tq, int64_t group) { return (Tq * group + 15) / 16; }
 
 // the qk product of a device-length cache (arguments checked by the entries): MODE kDev writes the dtype, kAtt the fp32 softmax input.
 // x [B, group * Tq, ldx]; group > 1 runs the GRP instances, WIN (kAtt) those with a first key per row (starts or null, window or 0)
-// pages (or null; not with WIN): the PG instances, w_bstride then a page's tokens
+// pages (or null; not with WIN): the PG instances, w_bstride then a page's tokens.  c4: the C4 instances (block 64, checked by the entries)
 template <int MODE, bool WIN = false>
 void qk_dev(const void* x, const void* wcodes, const int8_t* wexp, void* out, const int32_t* lens, int64_t B, int64_t heads, int64_t Tq,
             int64_t group, int64_t Kx, int64_t Nout, int64_t ldx, int64_t ldw, int64_t ldwe, int64_t w_bstride, int64_t ldo, int dtype, int block_size, int xm, int wm,
             float eps_dt, const uint8_t* exp_win, float scale, int causal, hipStream_t s, const int32_t* starts = nullptr, int window = 0,
-            const Pages* pages = nullptr)
+            const Pages* pages = nullptr, bool c4 = false)
 {
     const int64_t ny = B * row_tiles(Tq, group);
     const unsigned gy = (unsigned)(ny < 65535 ? ny : 65535);
     with_block(block_size, [&](auto blk) {
         with_dtype(dtype, [&](auto dt) {
-            auto go = [&](auto grp, auto paged) {
+            auto go = [&](auto grp, auto paged, auto nib) {
                 constexpr int TM = decltype(blk)::value == 64 ? 4 : 2;
-                constexpr bool PG = decltype(paged)::value;
-                hipLaunchKernelGGL((k_kv_bmm_dec<decltype(blk)::value, decltype(dt)::value, TM, MODE, decltype(grp)::value, WIN && !PG, PG>),
-                                   dim3((unsigned)((Nout + 64 * TM - 1) / (64 * TM)), gy), dim3(256), 0, s, x, (const int8_t*)wcodes, wexp, out, (int)B,
-                                   (int)Tq, (int)Kx, (int)Nout, (int)ldx, (int)ldw, (int)ldwe, (int)w_bstride, (int)ldo, xm, wm, eps_dt, exp_win, lens,
-                                   (int)heads, scale, causal, (int)group, starts, window, PG ? *pages : Pages{});
+                constexpr bool PG = decltype(paged)::value, C4 = decltype(nib)::value;
+                if constexpr (!C4 || decltype(blk)::value == 64)
+                    hipLaunchKernelGGL((k_kv_bmm_dec<decltype(blk)::value, decltype(dt)::value, TM, MODE, decltype(grp)::value, WIN && !PG, PG, C4>),
+                                       dim3((unsigned)((Nout + 64 * TM - 1) / (64 * TM)), gy), dim3(256), 0, s, x, (const int8_t*)wcodes, wexp, out, (int)B,
+                                       (int)Tq, (int)Kx, (int)Nout, (int)ldx, (int)ldw, (int)ldwe, (int)w_bstride, (int)ldo, xm, wm, eps_dt, exp_win, lens,
+                                       (int)heads, scale, causal, (int)group, starts, window, PG ? *pages : Pages{});
             };
-            if (pages) group > 1 ? go(std::true_type{}, std::true_type{}) : go(std::false_type{}, std::true_type{});
-            else if (group > 1) go(std::true_type{}, std::false_type{});
-            else go(std::false_type{}, std::false_type{});
+            if (c4) with_flag(group > 1, [&](auto grp) { with_flag(pages != nullptr, [&](auto paged) { go(grp, paged, std::true_type{}); }); });
+            else if (pages) group > 1 ? go(std::true_type{}, std::true_type{}, std::false_type{}) : go(std::false_type{}, std::true_type{}, std::false_type{});
+            else if (group > 1) go(std::true_type{}, std::false_type{}, std::false_type{});
+            else go(std::false_type{}, std::false_type{}, std::false_type{});
         });
     });
 }
@@ -1262,7 +1324,7 @@ template <bool ATT, bool WIN = false>
 int pv_dev(const void* x, const void* wcodes, const int8_t* wexp, void* out, const int32_t* lens, int64_t B, int64_t heads, int64_t Tq,
            int64_t group, int64_t Kx, int64_t D, int64_t ldx, int64_t ldw, int64_t ldwe, int64_t ldo, int dtype, int block_size, int xm, int wm, float eps_dt,
            const uint8_t* exp_win, void* ws, int64_t chunks_per_split, void* pout, int64_t ldp, int causal, hipStream_t s,
-           const int32_t* starts = nullptr, int window = 0, const Pages* pages = nullptr)
+           const int32_t* starts = nullptr, int window = 0, const Pages* pages = nullptr, bool c4 = false)
 {
     const int64_t nb = (Kx + block_size - 1) / block_size, nch = (Kx + 63) / 64, dg = (D + 63) / 64;
     const int64_t R = group * Tq, gz = B * row_tiles(Tq, group);  // a workgroup per (head, row tile) on the grid's z
@@ -1276,16 +1338,18 @@ int pv_dev(const void* x, const void* wcodes, const int8_t* wexp, void* out, con
     const int xvec = !ATT && (reinterpret_cast<uintptr_t>(x) & 15u) == 0 && (ldx * bfpq_dev::dtype_size(dtype)) % 16 == 0;
     with_block(block_size, [&](auto blk) {
         with_dtype(dtype, [&](auto dt) {
-            auto go = [&](auto grp, auto paged) {
-                constexpr bool PG = decltype(paged)::value;
-                hipLaunchKernelGGL((k_kv_pv_split<decltype(blk)::value, decltype(dt)::value, ATT, decltype(grp)::value, WIN && !PG, PG>),
-                                   dim3((unsigned)dg, (unsigned)slices, (unsigned)gz), dim3(256), 0, s, x, (const int8_t*)wcodes, sums, xexp, lens,
-                                   (int)heads, (int)Tq, (int)Kx, (int)D, (int)ldx, (int)ldw, (int)nb, (int)cps, xvec, xm, eps_dt, exp_win, pout,
-                                   (int)ldp, causal, (int)group, starts, window, PG ? *pages : Pages{});
+            auto go = [&](auto grp, auto paged, auto nib) {
+                constexpr bool PG = decltype(paged)::value, C4 = decltype(nib)::value;
+                if constexpr (!C4 || decltype(blk)::value == 64)
+                    hipLaunchKernelGGL((k_kv_pv_split<decltype(blk)::value, decltype(dt)::value, ATT, decltype(grp)::value, WIN && !PG, PG, C4>),
+                                       dim3((unsigned)dg, (unsigned)slices, (unsigned)gz), dim3(256), 0, s, x, (const int8_t*)wcodes, sums, xexp, lens,
+                                       (int)heads, (int)Tq, (int)Kx, (int)D, (int)ldx, (int)ldw, (int)nb, (int)cps, xvec, xm, eps_dt, exp_win, pout,
+                                       (int)ldp, causal, (int)group, starts, window, PG ? *pages : Pages{});
             };
-            if (pages) group > 1 ? go(std::true_type{}, std::true_type{}) : go(std::false_type{}, std::true_type{});
-            else if (group > 1) go(std::true_type{}, std::false_type{});
-            else go(std::false_type{}, std::false_type{});
+            if (c4) with_flag(group > 1, [&](auto grp) { with_flag(pages != nullptr, [&](auto paged) { go(grp, paged, std::true_type{}); }); });
+            else if (pages) group > 1 ? go(std::true_type{}, std::true_type{}, std::false_type{}) : go(std::false_type{}, std::true_type{}, std::false_type{});
+            else if (group > 1) go(std::true_type{}, std::false_type{}, std::false_type{});
+            else go(std::false_type{}, std::false_type{}, std::false_type{});
         });
     });
     const int rc = (int)hipGetLastError();
@@ -1364,12 +1428,18 @@ inline Pages pages_arg(const int32_t* table, int64_t page_tokens, int64_t pages,
     return Pages{table, (int)(cap / page_tokens), (int)page_tokens, (int)pages};
 }
 
-// bfpq_kv_attend_gqa (win false: starts and window are unread) and bfpq_kv_attend_gqa_win
+// the _cb entries: the code tensors hold int8 codes (8) or, at block 64 and mant_bits <= 3, nibbles (4)
+inline bool code_bits_ok(int code_bits, int block_size, int mant_bits)
+{
+    return code_bits == 8 || (code_bits == 4 && block_size == 64 && mant_bits <= 3);
+}
+
+// bfpq_kv_attend_gqa (win false: starts and window are unread), bfpq_kv_attend_gqa_win, _paged and (c4) _cb
 int attend_gqa(const void* q, const void* k_codes, const int8_t* k_exps, const void* v_codes, const int8_t* v_exps, void* out, void* p_out,
                const int32_t* lens, int64_t BH, int64_t heads, int64_t Tq, int64_t group, int64_t D, int64_t max_len, int64_t cap, int64_t ldd,
                int64_t ldo, int64_t ldp, double scale, int causal, int dtype, int block_size, int x_mant_bits, int w_mant_bits, double epsilon,
                const uint8_t* exp_win, void* score_ws, int64_t score_ws_bytes, void* sum_ws, int64_t sum_ws_bytes, int64_t chunks_per_split,
-               bool win, const int32_t* starts, int64_t window, void* stream, const Pages* pages = nullptr)
+               bool win, const int32_t* starts, int64_t window, void* stream, const Pages* pages = nullptr, bool c4 = false)
 {
     if (!att_values_ok(dtype, block_size, x_mant_bits, w_mant_bits, BH, heads, Tq, group, chunks_per_split, causal, scale) ||
         (win && !win_values_ok(starts, window)) || (pages && !pages_values_ok(pages->tokens, pages->count, cap)))
@@ -1391,12 +1461,12 @@ int attend_gqa(const void* q, const void* k_codes, const int8_t* k_exps, const v
     auto go = [&](auto w) {
         constexpr bool WIN = decltype(w)::value;
         qk_dev<kAtt, WIN>(q, k_codes, k_exps, score_ws, lens, BH, heads, Tq, group, D, max_len, D, ldd, D / block_size, hcap, pitch, dtype, block_size,
-                          x_mant_bits, w_mant_bits, eps_dt, exp_win, (float)scale, causal, s, starts, win_arg(window), pages);
+                          x_mant_bits, w_mant_bits, eps_dt, exp_win, (float)scale, causal, s, starts, win_arg(window), pages, c4);
         const int rc = (int)hipGetLastError();
         if (rc) return rc;
         return pv_dev<true, WIN>(score_ws, v_codes, v_exps, out, lens, BH, heads, Tq, group, max_len, D, pitch, hcap, hcap / block_size, ldo, dtype,
                                  block_size, x_mant_bits, w_mant_bits, eps_dt, exp_win, sum_ws, chunks_per_split, p_out, ldp, causal, s, starts,
-                                 win_arg(window), pages);
+                                 win_arg(window), pages, c4);
     };
     return win && (starts || win_arg(window)) ? go(std::true_type{}) : go(std::false_type{});
 }
@@ -1406,7 +1476,7 @@ int attend_rows(const void* q, const void* k_codes, const int8_t* k_exps, const 
                 const int32_t* lens, int64_t BH, int64_t heads, int64_t Tq, int64_t group, int64_t D, int64_t max_len, int64_t cap, int64_t ldd,
                 int64_t ldo, int64_t ldp, double scale, int causal, int dtype, int block_size, int x_mant_bits, int w_mant_bits, double epsilon,
                 const uint8_t* exp_win, void* score_ws, int64_t score_ws_bytes, int64_t chunks_per_split, int64_t row0, int64_t rows, bool win,
-                const int32_t* starts, int64_t window, void* stream, const Pages* pages = nullptr)
+                const int32_t* starts, int64_t window, void* stream, const Pages* pages = nullptr, bool c4 = false)
 {
     if (!att_values_ok(dtype, block_size, x_mant_bits, w_mant_bits, BH, heads, Tq, group, chunks_per_split, causal, scale) || row0 < 0 || rows < 0 ||
         row0 > Tq || rows > Tq - row0 || (win && !win_values_ok(starts, window)) || (pages && !pages_values_ok(pages->tokens, pages->count, cap)))
@@ -1425,30 +1495,37 @@ int attend_rows(const void* q, const void* k_codes, const int8_t* k_exps, const 
     hipStream_t s = (hipStream_t)stream;
     const int64_t nbd = D / block_size, hcap = pages ? pages->tokens : cap;   // (hcap: tokens of a head of the cache tensors)
     const size_t lds_qk = (size_t)(2 * 64 * D + 128 * nbd), lds_pv = (size_t)(64 * D + 64 / block_size * D);   // <= 36 KiB at D = 256
-    auto go = [&](auto w, auto paged) {
-        constexpr bool WIN = decltype(w)::value, PG = decltype(paged)::value;
+    auto go = [&](auto w, auto paged, auto nib) {
+        constexpr bool WIN = decltype(w)::value, PG = decltype(paged)::value, C4 = decltype(nib)::value;
         with_block(block_size, [&](auto blk) {
             with_dtype(dtype, [&](auto dt) {
-                hipLaunchKernelGGL((k_kv_qk_rows<decltype(blk)::value, decltype(dt)::value, WIN, PG>), dim3((unsigned)(BH * nwg)), dim3(256), lds_qk, s,
-                                   q, (const int8_t*)k_codes, k_exps, (float*)score_ws, (int)Tq, (int)D, (int)max_len, (int)ldd, (int)hcap, (int)pitch,
-                                   x_mant_bits, w_mant_bits, eps_dt, exp_win, lens, (int)heads, (float)scale, causal, (int)group, (int)row0, (int)rows,
-                                   starts, win_arg(window), PG ? *pages : Pages{});
+                if constexpr (!C4 || decltype(blk)::value == 64)
+                    hipLaunchKernelGGL((k_kv_qk_rows<decltype(blk)::value, decltype(dt)::value, WIN, PG, C4>), dim3((unsigned)(BH * nwg)), dim3(256), lds_qk,
+                                       s, q, (const int8_t*)k_codes, k_exps, (float*)score_ws, (int)Tq, (int)D, (int)max_len, (int)ldd, (int)hcap, (int)pitch,
+                                       x_mant_bits, w_mant_bits, eps_dt, exp_win, lens, (int)heads, (float)scale, causal, (int)group, (int)row0, (int)rows,
+                                       starts, win_arg(window), PG ? *pages : Pages{});
             });
         });
         const int rc = (int)hipGetLastError();
         if (rc) return rc;
         with_block(block_size, [&](auto blk) {
             with_dtype(dtype, [&](auto dt) {
-                hipLaunchKernelGGL((k_kv_pv_rows<decltype(blk)::value, decltype(dt)::value, WIN, PG>), dim3((unsigned)(BH * nwg)), dim3(256), lds_pv, s,
-                                   (const float*)score_ws, (const int8_t*)v_codes, v_exps, out, p_out, lens, (int)heads, (int)Tq, (int)max_len, (int)D,
-                                   (int)pitch, (int)hcap, (int)(hcap / block_size), (int)ldo, (int)ldp, x_mant_bits, w_mant_bits, eps_dt, exp_win,
-                                   causal, (int)group, (int)row0, (int)rows, starts, win_arg(window), PG ? *pages : Pages{});
+                if constexpr (!C4 || decltype(blk)::value == 64)
+                    hipLaunchKernelGGL((k_kv_pv_rows<decltype(blk)::value, decltype(dt)::value, WIN, PG, C4>), dim3((unsigned)(BH * nwg)), dim3(256), lds_pv,
+                                       s, (const float*)score_ws, (const int8_t*)v_codes, v_exps, out, p_out, lens, (int)heads, (int)Tq, (int)max_len, (int)D,
+                                       (int)pitch, (int)hcap, (int)(hcap / block_size), (int)ldo, (int)ldp, x_mant_bits, w_mant_bits, eps_dt, exp_win,
+                                       causal, (int)group, (int)row0, (int)rows, starts, win_arg(window), PG ? *pages : Pages{});
             });
         });
         return (int)hipGetLastError();
     };
-    if (pages) return go(std::false_type{}, std::true_type{});
-    return win && (starts || win_arg(window)) ? go(std::true_type{}, std::false_type{}) : go(std::false_type{}, std::false_type{});
+    const bool first_keys = win && (starts || win_arg(window));
+    if (c4) {
+        if (pages) return go(std::false_type{}, std::true_type{}, std::true_type{});
+        return first_keys ? go(std::true_type{}, std::false_type{}, std::true_type{}) : go(std::false_type{}, std::false_type{}, std::true_type{});
+    }
+    if (pages) return go(std::false_type{}, std::true_type{}, std::false_type{});
+    return first_keys ? go(std::true_type{}, std::false_type{}, std::false_type{}) : go(std::false_type{}, std::false_type{}, std::false_type{});
 }
 
 }  // namespace
@@ -1513,11 +1590,11 @@ int bfpq_kv_bmm_dec(const void* x, const void* wcodes, const int8_t* wexp, void*
     return (int)hipGetLastError();
 }
 
-// bfpq_kv_append_dev (pages null) and bfpq_kv_append_paged
+// bfpq_kv_append_dev (pages null), bfpq_kv_append_paged and (c4) bfpq_kv_append_cb
 static int append_dev(const void* k_new, const void* v_new, void* k_codes, int8_t* k_exps, void* v_codes, int8_t* v_exps, void* v_tail,
                       const int32_t* lens, const int32_t* counts, int32_t* overflow, int64_t BH, int64_t heads, int64_t D, int64_t t,
                       int64_t cap, int64_t limit, int64_t ldd, int dtype, int block_size, int mant_bits, double epsilon,
-                      const uint8_t* exp_win, void* stream, const Pages* pages)
+                      const uint8_t* exp_win, void* stream, const Pages* pages, bool c4 = false)
 {
     if (!dtype_ok(dtype) || !i8_block_ok(block_size) || !i8_mant_ok(mant_bits) || BH < 0 || t < 0 || heads < 1 || BH % heads != 0 ||
         (pages && !pages_values_ok(pages->tokens, pages->count, cap)))
@@ -1538,15 +1615,16 @@ static int append_dev(const void* k_new, const void* v_new, void* k_codes, int8_
     if (nkb + nvb >= kLim) return BFPQ_E_UNSUPPORTED;
     const float eps_dt = bfpq_dev::h_round((float)epsilon, dtype);
     with_dtype(dtype, [&](auto dt) {
-        auto go = [&](auto paged) {
+        auto go = [&](auto paged, auto nib) {
             constexpr bool PG = decltype(paged)::value;           // (PG: the kernel's cap is a page's tokens)
-            hipLaunchKernelGGL((k_kv_append<decltype(dt)::value, true, PG>), dim3((unsigned)(nkb + nvb)), dim3(256), 0, (hipStream_t)stream, k_new,
+            hipLaunchKernelGGL((k_kv_append<decltype(dt)::value, true, PG, decltype(nib)::value>), dim3((unsigned)(nkb + nvb)), dim3(256), 0, (hipStream_t)stream, k_new,
                                v_new, (int8_t*)k_codes, k_exps, (int8_t*)v_codes, v_exps, v_tail, (int)BH, (int)D, 0, (int)t,
                                (int)(PG ? pages->tokens : cap), (int)ldd, block_size, mant_bits, eps_dt, exp_win, (int)nkb, (int)zc, lens, counts,
                                overflow, (int)heads, (int)limit, PG ? *pages : Pages{});
         };
-        if (pages) go(std::true_type{});
-        else go(std::false_type{});
+        if (c4) with_flag(pages != nullptr, [&](auto paged) { go(paged, std::true_type{}); });
+        else if (pages) go(std::true_type{}, std::false_type{});
+        else go(std::false_type{}, std::false_type{});
     });
     return (int)hipGetLastError();
 }
@@ -1596,7 +1674,8 @@ int64_t bfpq_kv_dec_ws_bytes(int64_t B, int64_t Tq, int64_t D, int64_t L, int bl
 static int bmm_dec_gqa(const void* x, const void* wcodes, const int8_t* wexp, void* out, const int32_t* lens, int64_t B, int64_t heads,
                        int64_t Tq, int64_t group, int64_t Kx, int64_t Nout, int64_t ldx, int64_t ldw, int64_t ldwe, int64_t w_bstride,
                        int64_t ldo, int family, int dtype, int block_size, int x_mant_bits, int w_mant_bits, double epsilon,
-                       const uint8_t* exp_win, void* ws, int64_t ws_bytes, int64_t chunks_per_split, void* stream, const Pages* pages, int64_t cap)
+                       const uint8_t* exp_win, void* ws, int64_t ws_bytes, int64_t chunks_per_split, void* stream, const Pages* pages, int64_t cap,
+                       bool c4 = false)
 {
     if (!dec_values_ok(dtype, block_size, x_mant_bits, w_mant_bits, family, B, Tq, Nout, Kx) || heads < 1 || B % heads != 0 || group < 1 ||
         chunks_per_split < 0 || (pages && !pages_values_ok(pages->tokens, pages->count, cap)))
@@ -1623,7 +1702,7 @@ static int bmm_dec_gqa(const void* x, const void* wcodes, const int8_t* wexp, vo
     hipStream_t s = (hipStream_t)stream;
     if (family == BFPQ_KV_QK) {
         qk_dev<kDev>(x, wcodes, wexp, out, lens, B, heads, Tq, group, Kx, Nout, ldx, ldw, ldwe, w_bstride, ldo, dtype, block_size, x_mant_bits, w_mant_bits,
-                     eps_dt, exp_win, 1.f, 0, s, nullptr, 0, pages);
+                     eps_dt, exp_win, 1.f, 0, s, nullptr, 0, pages, c4);
         return (int)hipGetLastError();
     }
     // p v: w_bstride == Nout == D rows per head (the sums are laid out by D); a workgroup per (head, row tile) on the grid's z
@@ -1631,7 +1710,7 @@ static int bmm_dec_gqa(const void* x, const void* wcodes, const int8_t* wexp, vo
     if (w_bstride != Nout || B * row_tiles(Tq, group) > 65535 || need < 0 || ws_bytes < need) return BFPQ_E_UNSUPPORTED;
     if (!ws || !aligned16(ws)) return BFPQ_E_ARG;
     return pv_dev<false>(x, wcodes, wexp, out, lens, B, heads, Tq, group, Kx, Nout, ldx, ldw, ldwe, ldo, dtype, block_size, x_mant_bits, w_mant_bits,
-                         eps_dt, exp_win, ws, chunks_per_split, nullptr, 0, 0, s, nullptr, 0, pages);
+                         eps_dt, exp_win, ws, chunks_per_split, nullptr, 0, 0, s, nullptr, 0, pages, c4);
 }
 
 int bfpq_kv_bmm_dec_gqa(const void* x, const void* wcodes, const int8_t* wexp, void* out, const int32_t* lens, int64_t B, int64_t heads,
@@ -1787,5 +1866,69 @@ int bfpq_kv_attend_rows_paged(const void* q, const void* k_codes, const int8_t* 
                        nullptr, 0, stream, &pg);
 }
 #undef BFPQ_PAGES_OR_RETURN
+
+// ---- the _cb entries: the entry each extends with the window and the paged arguments it lacks and code_bits in front of the
+// stream.  A null page_table with page_tokens == 0 and pages == 0 is the contiguous cache; with code_bits == 8 the launch is the one of
+// the entry it extends
+#define BFPQ_CB_OR_RETURN(cap, mant)                                                                       \
+    if (!code_bits_ok(code_bits, block_size, mant)) return BFPQ_E_ARG;                                     \
+    const bool paged = page_table || page_tokens != 0 || pages != 0;                                       \
+    if (paged && !pages_values_ok(page_tokens, pages, cap)) return BFPQ_E_ARG;                             \
+    if (paged && (page_tokens >= kLim || pages >= kLim || (cap) >= kLim)) return BFPQ_E_UNSUPPORTED;       \
+    const Pages pg = paged ? pages_arg(page_table, page_tokens, pages, cap) : Pages{};                     \
+    const Pages* const pgp = paged ? &pg : nullptr
+
+int bfpq_kv_append_cb(const void* k_new, const void* v_new, void* k_codes, int8_t* k_exps, void* v_codes, int8_t* v_exps, void* v_tail,
+                      const int32_t* lens, const int32_t* counts, int32_t* overflow, int64_t BH, int64_t heads, int64_t D, int64_t t, int64_t cap,
+                      int64_t limit, int64_t ldd, int dtype, int block_size, int mant_bits, double epsilon, const uint8_t* exp_win,
+                      const int32_t* page_table, int64_t page_tokens, int64_t pages, int code_bits, void* stream)
+{
+    BFPQ_CB_OR_RETURN(cap, mant_bits);
+    return append_dev(k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, lens, counts, overflow, BH, heads, D, t, cap, limit, ldd, dtype,
+                      block_size, mant_bits, epsilon, exp_win, stream, pgp, code_bits == 4);
+}
+
+int bfpq_kv_bmm_dec_cb(const void* x, const void* wcodes, const int8_t* wexp, void* out, const int32_t* lens, int64_t B, int64_t heads, int64_t Tq,
+                       int64_t group, int64_t Kx, int64_t Nout, int64_t ldx, int64_t ldw, int64_t ldwe, int64_t w_bstride, int64_t ldo, int family,
+                       int dtype, int block_size, int x_mant_bits, int w_mant_bits, double epsilon, const uint8_t* exp_win, void* ws,
+                       int64_t ws_bytes, int64_t chunks_per_split, int64_t cap, const int32_t* page_table, int64_t page_tokens, int64_t pages,
+                       int code_bits, void* stream)
+{
+    BFPQ_CB_OR_RETURN(cap, w_mant_bits);
+    return bmm_dec_gqa(x, wcodes, wexp, out, lens, B, heads, Tq, group, Kx, Nout, ldx, ldw, ldwe, w_bstride, ldo, family, dtype, block_size,
+                       x_mant_bits, w_mant_bits, epsilon, exp_win, ws, ws_bytes, chunks_per_split, stream, pgp, paged ? cap : 0, code_bits == 4);
+}
+
+int bfpq_kv_attend_cb(const void* q, const void* k_codes, const int8_t* k_exps, const void* v_codes, const int8_t* v_exps, void* out, void* p_out,
+                      const int32_t* lens, int64_t BH, int64_t heads, int64_t Tq, int64_t group, int64_t D, int64_t max_len, int64_t cap,
+                      int64_t ldd, int64_t ldo, int64_t ldp, double scale, int causal, int dtype, int block_size, int x_mant_bits,
+                      int w_mant_bits, double epsilon, const uint8_t* exp_win, void* score_ws, int64_t score_ws_bytes, void* sum_ws,
+                      int64_t sum_ws_bytes, int64_t chunks_per_split, const int32_t* starts, int64_t window, const int32_t* page_table,
+                      int64_t page_tokens, int64_t pages, int code_bits, void* stream)
+{
+    BFPQ_CB_OR_RETURN(cap, w_mant_bits);
+    if (!win_values_ok(starts, window)) return BFPQ_E_ARG;
+    if (paged && (starts || window != 0)) return BFPQ_E_UNSUPPORTED;   // (a paged cache has no first key)
+    return attend_gqa(q, k_codes, k_exps, v_codes, v_exps, out, p_out, lens, BH, heads, Tq, group, D, max_len, cap, ldd, ldo, ldp, scale, causal, dtype,
+                      block_size, x_mant_bits, w_mant_bits, epsilon, exp_win, score_ws, score_ws_bytes, sum_ws, sum_ws_bytes, chunks_per_split,
+                      true, starts, window, stream, pgp, code_bits == 4);
+}
+
+int bfpq_kv_attend_rows_cb(const void* q, const void* k_codes, const int8_t* k_exps, const void* v_codes, const int8_t* v_exps, void* out,
+                           void* p_out, const int32_t* lens, int64_t BH, int64_t heads, int64_t Tq, int64_t group, int64_t D, int64_t max_len,
+                           int64_t cap, int64_t ldd, int64_t ldo, int64_t ldp, double scale, int causal, int dtype, int block_size,
+                           int x_mant_bits, int w_mant_bits, double epsilon, const uint8_t* exp_win, void* score_ws, int64_t score_ws_bytes,
+                           void* sum_ws, int64_t sum_ws_bytes, int64_t chunks_per_split, int64_t row0, int64_t rows, const int32_t* starts,
+                           int64_t window, const int32_t* page_table, int64_t page_tokens, int64_t pages, int code_bits, void* stream)
+{
+    (void)sum_ws; (void)sum_ws_bytes;
+    BFPQ_CB_OR_RETURN(cap, w_mant_bits);
+    if (!win_values_ok(starts, window)) return BFPQ_E_ARG;
+    if (paged && (starts || window != 0)) return BFPQ_E_UNSUPPORTED;
+    return attend_rows(q, k_codes, k_exps, v_codes, v_exps, out, p_out, lens, BH, heads, Tq, group, D, max_len, cap, ldd, ldo, ldp, scale, causal,
+                       dtype, block_size, x_mant_bits, w_mant_bits, epsilon, exp_win, score_ws, score_ws_bytes, chunks_per_split, row0, rows, true,
+                       starts, window, stream, pgp, code_bits == 4);
+}
+#undef BFPQ_CB_OR_RETURN
 
 }  // extern "C"

@@ -130,10 +130,12 @@ int64_t bfpq_kv_rows_move_ws_bytes(int64_t n_jobs, int64_t kv_heads, int64_t D, 
     return n_jobs * tail_bytes(kv_heads, D, block_size, dtype) + (n_jobs * 4 + 15) / 16 * 16;   // the v_tail rows, then the lengths
 }
 
-int bfpq_kv_rows_move(void* k_codes, int8_t* k_exps, void* v_codes, int8_t* v_exps, void* v_tail, int32_t* lens, int32_t* overflow,
-                      const int32_t* jobs_dev, int64_t n_jobs, void* stage_dev, int64_t stage_bytes, int64_t B, int64_t kv_heads, int64_t D,
-                      int block_size, int dtype, int64_t page_tokens, int64_t pages, void* stream)
+// bfpq_kv_rows_move (code_bits 8) and bfpq_kv_rows_move_cb: with 4-bit codes a page of k_codes and of v_codes is half the bytes
+static int rows_move(void* k_codes, int8_t* k_exps, void* v_codes, int8_t* v_exps, void* v_tail, int32_t* lens, int32_t* overflow,
+                     const int32_t* jobs_dev, int64_t n_jobs, void* stage_dev, int64_t stage_bytes, int64_t B, int64_t kv_heads, int64_t D,
+                     int block_size, int dtype, int64_t page_tokens, int64_t pages, int code_bits, void* stream)
 {
+    if (code_bits != 8 && !(code_bits == 4 && block_size == 64)) return BFPQ_E_ARG;
     if (!dtype_ok(dtype) || !block_ok(block_size) || n_jobs < 0 || B < 1 || kv_heads < 1 || page_tokens < 64 || page_tokens % 64 != 0 ||
         pages < 1)
         return BFPQ_E_ARG;
@@ -149,9 +151,9 @@ int bfpq_kv_rows_move(void* k_codes, int8_t* k_exps, void* v_codes, int8_t* v_ex
     const int64_t need = bfpq_kv_rows_move_ws_bytes(n_jobs, kv_heads, D, block_size, dtype);
     if (need < 0 || stage_bytes < need) return BFPQ_E_ARG;
     MoveShape sh;
-    sh.piece[0] = kv_heads * page_tokens * ldd;
+    sh.piece[0] = kv_heads * page_tokens * ldd * code_bits / 8;   // (page_tokens % 64 == ldd % 64 == 0: halves are multiples of 16 too)
     sh.piece[1] = kv_heads * page_tokens * (D / block_size);
-    sh.piece[2] = kv_heads * D * page_tokens;
+    sh.piece[2] = kv_heads * D * page_tokens * code_bits / 8;
     sh.piece[3] = kv_heads * D * (page_tokens / block_size);
     sh.tail = tail_bytes(kv_heads, D, block_size, dtype);
     sh.B = (int)B;
@@ -166,6 +168,22 @@ int bfpq_kv_rows_move(void* k_codes, int8_t* k_exps, void* v_codes, int8_t* v_ex
     hipLaunchKernelGGL(k_kv_rows_place, dim3((unsigned)n_jobs, (unsigned)split_of(sh.tail)), dim3(256), 0, s, v_tail, lens, jobs_dev, (int)n_jobs,
                        (const void*)stage_dev, sh);
     return (int)hipGetLastError();
+}
+
+int bfpq_kv_rows_move(void* k_codes, int8_t* k_exps, void* v_codes, int8_t* v_exps, void* v_tail, int32_t* lens, int32_t* overflow,
+                      const int32_t* jobs_dev, int64_t n_jobs, void* stage_dev, int64_t stage_bytes, int64_t B, int64_t kv_heads, int64_t D,
+                      int block_size, int dtype, int64_t page_tokens, int64_t pages, void* stream)
+{
+    return rows_move(k_codes, k_exps, v_codes, v_exps, v_tail, lens, overflow, jobs_dev, n_jobs, stage_dev, stage_bytes, B, kv_heads, D, block_size,
+                     dtype, page_tokens, pages, 8, stream);
+}
+
+int bfpq_kv_rows_move_cb(void* k_codes, int8_t* k_exps, void* v_codes, int8_t* v_exps, void* v_tail, int32_t* lens, int32_t* overflow,
+                         const int32_t* jobs_dev, int64_t n_jobs, void* stage_dev, int64_t stage_bytes, int64_t B, int64_t kv_heads, int64_t D,
+                         int block_size, int dtype, int64_t page_tokens, int64_t pages, int code_bits, void* stream)
+{
+    return rows_move(k_codes, k_exps, v_codes, v_exps, v_tail, lens, overflow, jobs_dev, n_jobs, stage_dev, stage_bytes, B, kv_heads, D, block_size,
+                     dtype, page_tokens, pages, code_bits, stream);
 }
 
 }  // extern "C"

@@ -166,15 +166,6 @@ __global__ void __launch_bounds__(256) k_sp24_unpack(const uint8_t* __restrict__
     }
 }
 
-// 8 two's-complement nibbles (value j in nibble j) -> 8 int8 bytes in order (the A operand)
-__device__ __forceinline__ v2i nibbles_to_i8(uint32_t w)
-{
-    // per byte: n -> ((n ^ 8) + 0x78) ^ 0x80 is n sign-extended (no carry leaves the byte: (n ^ 8) + 0x78 <= 0x87)
-    const uint32_t lo = (((w & 0x0f0f0f0fu) ^ 0x08080808u) + 0x78787878u) ^ 0x80808080u;          // values 0, 2, 4, 6
-    const uint32_t hi = ((((w >> 4) & 0x0f0f0f0fu) ^ 0x08080808u) + 0x78787878u) ^ 0x80808080u;   // values 1, 3, 5, 7
-    return v2i{(int)__builtin_amdgcn_perm(hi, lo, 0x05010400u), (int)__builtin_amdgcn_perm(hi, lo, 0x07030602u)};
-}
-
 // 8 exponent bytes p[0..7] of a row as two exp4 dwords (cnt < 8: the bytes from cnt on are not read and give 0)
 __device__ __forceinline__ void exps8(const int8_t* p, bool dwords, int cnt, uint32_t (&d)[2])
 {

@@ -137,6 +137,15 @@ PROTOTYPES = {
                                          _i64, _vp, _i64, _i64, _vp]),
     "bfpq_kv_rows_move_ws_bytes": (_i64, [_i64, _i64, _i64, _i32, _i32]),
     "bfpq_kv_rows_move": (_i32, [_vp] * 8 + [_i64, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _i64, _i64, _vp]),
+    # the _cb entries (4-bit codes): the entry each extends + [starts, window] + [cap] + [page_table, page_tokens, pages] + code_bits
+    "bfpq_kv_append_cb": (_i32, [_vp] * 10 + [_i64] * 7 + [_i32, _i32, _i32, _dbl, _vp, _vp, _i64, _i64, _i32, _vp]),
+    "bfpq_kv_bmm_dec_cb": (_i32, [_vp] * 5 + [_i64] * 11 + [_i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i32,
+                                  _vp]),
+    "bfpq_kv_attend_cb": (_i32, [_vp] * 8 + [_i64] * 10 + [_dbl, _i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp,
+                                 _i64, _i64, _i32, _vp]),
+    "bfpq_kv_attend_rows_cb": (_i32, [_vp] * 8 + [_i64] * 10 + [_dbl, _i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64,
+                                      _vp, _i64, _vp, _i64, _i64, _i32, _vp]),
+    "bfpq_kv_rows_move_cb": (_i32, [_vp] * 8 + [_i64, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _i64, _i64, _i32, _vp]),
 }
 
 
@@ -1438,6 +1447,27 @@ class KVPages(collections.namedtuple("KVPages", "table tokens count capacity")):
         return _ptr(self.table), int(self.tokens), int(self.count)
 
 
+def _kv_page_args(pages):
+    """(page_table, page_tokens, pages) of the _cb entries: a KVPages', or those of the contiguous cache"""
+    return (None, 0, 0) if pages is None else pages.args()
+
+
+KV_C4_MAX_MANT = 3             # 4-bit codes hold -7..7: mant_bits <= 3 (and block 64)
+
+
+def _kv_code_bits(what, code_bits, block_size, mant_bits):
+    """code_bits of a KV cache's code buffers: 8 (int8 codes) or 4 (two to a byte; block 64 and mant_bits <= 3).  Returns the codes per byte"""
+    if isinstance(code_bits, bool) or not isinstance(code_bits, int):
+        raise TypeError(f"{what}: code_bits must be 8 or 4 (got {code_bits!r})")
+    if code_bits == 8:
+        return 1
+    if code_bits != 4:
+        raise ValueError(f"{what}: code_bits must be 8 or 4 (got {code_bits})")
+    if int(block_size) != 64 or (mant_bits is not None and int(mant_bits) > KV_C4_MAX_MANT):
+        raise ValueError(f"{what}: code_bits=4 needs block_size 64 and mant_bits <= {KV_C4_MAX_MANT} (got {block_size}, {mant_bits})")
+    return 2
+
+
 def _kv_pages(what, pages, B, heads, dev):
     """the checks on a KVPages of B sequences; returns the heads the code buffers hold"""
     if not isinstance(pages, KVPages):
@@ -1449,23 +1479,24 @@ def _kv_pages(what, pages, B, heads, dev):
     return N * heads
 
 
-def _kv_buffers(what, BH, D, block_size, k_codes, k_exps, v_codes, v_exps, v_tail, dev, held=None):
+def _kv_buffers(what, BH, D, block_size, k_codes, k_exps, v_codes, v_exps, v_tail, dev, held=None, per_byte=1):
     """the checks of kv_append on the five cache buffers (held: the heads the code and exponent buffers hold, where not BH: a paged
-    cache); returns (cap, ldd)"""
+    cache; per_byte: codes per byte of the two code buffers, whose last dimension is then ldd / per_byte, cap / per_byte); returns
+    (cap, ldd), counted in codes"""
     if block_size not in (64,) + I8_BLOCKS:
         raise ValueError(f"{what}: block_size must be 16, 32 or 64 (got {block_size})")
     if k_codes.dim() < 2 or v_codes.dim() < 2:
         raise ValueError(f"{what} takes k_codes [..., cap, ldd] and v_codes [..., D, cap]")
-    cap, ldd = k_codes.shape[-2], k_codes.shape[-1]
+    cap, ldd = k_codes.shape[-2], k_codes.shape[-1] * per_byte
     nbd, nbc = D // block_size, cap // block_size
     HB = BH if held is None else held
-    sizes = dict(k_codes=(k_codes, HB * cap * ldd), k_exps=(k_exps, HB * cap * nbd), v_codes=(v_codes, HB * D * cap), v_exps=(v_exps, HB * D * nbc),
-                 v_tail=(v_tail, BH * block_size * D))
+    sizes = dict(k_codes=(k_codes, HB * cap * ldd // per_byte), k_exps=(k_exps, HB * cap * nbd), v_codes=(v_codes, HB * D * cap // per_byte),
+                 v_exps=(v_exps, HB * D * nbc), v_tail=(v_tail, BH * block_size * D))
     for name, (buf, numel) in sizes.items():
         if buf.device != dev or not buf.is_contiguous() or buf.numel() != numel or (name != "v_tail" and buf.dtype != torch.int8):
             raise ValueError(f"{what}: {name} must be contiguous on {dev} with {numel} elements"
                              f"{'' if name == 'v_tail' else ' of int8'} (got {tuple(buf.shape)}, {buf.dtype}, {buf.device})")
-    if v_codes.shape[-1] != cap:
+    if v_codes.shape[-1] * per_byte != cap:
         raise ValueError(f"{what} takes v_codes [..., D, cap] with k_codes' capacity")
     return cap, ldd
 
@@ -1476,7 +1507,7 @@ def _kv_int32(what, name, t, numel, dev):
                          f"(got {tuple(getattr(t, 'shape', ()))}, {getattr(t, 'dtype', None)}, {getattr(t, 'device', None)})")
 
 
-def _kv_new(what, k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, block_size, heads=None, pages=None):
+def _kv_new(what, k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, block_size, heads=None, pages=None, per_byte=1):
     """the checks kv_append and kv_append_dev share on the new rows and the cache buffers; returns (BH, t, D, cap, ldd)"""
     require_device_tensor(k_new, "k_new")
     require_device_tensor(v_new, "v_new")
@@ -1488,7 +1519,7 @@ def _kv_new(what, k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, block_
     if heads is not None and (heads < 1 or BH % heads):
         raise ValueError(f"{what}: {BH} heads in all are no multiple of heads = {heads}")
     held = None if pages is None else _kv_pages(what, pages, BH // heads, heads, k_new.device)
-    cap, ldd = _kv_buffers(what, BH, D, block_size, k_codes, k_exps, v_codes, v_exps, v_tail, k_new.device, held)
+    cap, ldd = _kv_buffers(what, BH, D, block_size, k_codes, k_exps, v_codes, v_exps, v_tail, k_new.device, held, per_byte)
     if not k_new.is_contiguous() or not v_new.is_contiguous():
         raise ValueError(f"{what} takes contiguous k_new / v_new")
     return BH, t, D, cap, ldd
@@ -1506,13 +1537,16 @@ def kv_append(k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, pos, block
 
 
 def kv_append_dev(k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, lengths, counts, overflow, heads, limit, block_size, mant_bits,
-                  epsilon, pages=None):
+                  epsilon, pages=None, code_bits=8):
     """kv_append at the positions lengths [B] (int32, on the device) holds, sequence b = head // heads taking the first counts[b] of the t
     rows (counts None: all), then lengths advanced by a second launch (bfpq_kv_append_dev, bfpq_kv_lens_advance).  A sequence that would
     pass `limit` tokens is left untouched and overflow[0] set to 1.  Nothing is read back.  pages (a KVPages): the buffers are a pool of
-    pages (bfpq_kv_append_paged, bfpq_kv_lens_advance_paged), and a sequence one of whose tokens has no page is refused likewise."""
+    pages (bfpq_kv_append_paged, bfpq_kv_lens_advance_paged), and a sequence one of whose tokens has no page is refused likewise.
+    code_bits=4 (block 64, mant_bits <= 3): k_codes [.., cap, ldd / 2] and v_codes [.., D, cap / 2] hold two codes to a byte
+    (bfpq_kv_append_cb, paged or not); 8 is the call above in every respect."""
     heads = int(heads)
-    BH, t, D, cap, ldd = _kv_new("kv_append_dev", k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, block_size, heads, pages)
+    per_byte = _kv_code_bits("kv_append_dev", code_bits, block_size, mant_bits)
+    BH, t, D, cap, ldd = _kv_new("kv_append_dev", k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, block_size, heads, pages, per_byte)
     dev, B = k_new.device, BH // heads
     _kv_int32("kv_append_dev", "lengths", lengths, B, dev)
     _kv_int32("kv_append_dev", "overflow", overflow, 1, dev)
@@ -1520,6 +1554,17 @@ def kv_append_dev(k_new, v_new, k_codes, k_exps, v_codes, v_exps, v_tail, length
         _kv_int32("kv_append_dev", "counts", counts, B, dev)
     with torch.cuda.device(dev):
         L, stream = load_library(), _stream(k_new)
+        if code_bits == 4:
+            check(L.bfpq_kv_append_cb(_ptr(k_new), _ptr(v_new), _ptr(k_codes), _ptr(k_exps), _ptr(v_codes), _ptr(v_exps), _ptr(v_tail),
+                                      _ptr(lengths), _ptr(counts), _ptr(overflow), BH, heads, D, t, cap if pages is None else int(pages.capacity),
+                                      int(limit), ldd, DTYPE_CODE[k_new.dtype], int(block_size), int(mant_bits), float(epsilon),
+                                      _ptr(exp_window_dev(k_new.dtype, dev)), *_kv_page_args(pages), 4, stream), "bfpq_kv_append_cb")
+            if pages is None:
+                check(L.bfpq_kv_lens_advance(_ptr(lengths), _ptr(counts), B, t, int(limit), stream), "bfpq_kv_lens_advance")
+            else:
+                check(L.bfpq_kv_lens_advance_paged(_ptr(lengths), _ptr(counts), B, t, int(limit), int(pages.capacity), *pages.args(), stream),
+                      "bfpq_kv_lens_advance_paged")
+            return
         if pages is not None:
             check(L.bfpq_kv_append_paged(_ptr(k_new), _ptr(v_new), _ptr(k_codes), _ptr(k_exps), _ptr(v_codes), _ptr(v_exps), _ptr(v_tail),
                                          _ptr(lengths), _ptr(counts), _ptr(overflow), BH, heads, D, t, int(pages.capacity), int(limit), ldd,
@@ -1545,16 +1590,18 @@ def kv_rows_move_ws_bytes(n_jobs, kv_heads, D, block_size, dtype):
     return n
 
 
-def kv_rows_move(k_codes, k_exps, v_codes, v_exps, v_tail, lengths, overflow, jobs, stage, kv_heads, block_size, pages):
+def kv_rows_move(k_codes, k_exps, v_codes, v_exps, v_tail, lengths, overflow, jobs, stage, kv_heads, block_size, pages, code_bits=8):
     """the device side of a reorder of a paged cache's sequences (bfpq_kv_rows_move, include/bfpq.h): jobs int32 [n, 5] on the device
     (src_row, dst_row, src_page, dst_page, tokens); per job the open page copied into a fresh one, and v_tail and the length of src_row
     moved to dst_row through `stage` (uint8, kv_rows_move_ws_bytes(n, ...)), the length only where it equals `tokens` (else 0, and
-    overflow[0] set).  Two launches; nothing is read back.  pages: the cache's KVPages"""
+    overflow[0] set).  Two launches; nothing is read back.  pages: the cache's KVPages.  code_bits=4: the code buffers hold two codes
+    to a byte and a page's copy is half the bytes (bfpq_kv_rows_move_cb)"""
+    per_byte = _kv_code_bits("kv_rows_move", code_bits, block_size, None)
     require_device_tensor(v_tail, "v_tail")
     dev, B = v_tail.device, lengths.numel()
     D = v_tail.shape[-1]
     held = _kv_pages("kv_rows_move", pages, B, kv_heads, dev)
-    _kv_buffers("kv_rows_move", B * kv_heads, D, block_size, k_codes, k_exps, v_codes, v_exps, v_tail, dev, held)
+    _kv_buffers("kv_rows_move", B * kv_heads, D, block_size, k_codes, k_exps, v_codes, v_exps, v_tail, dev, held, per_byte)
     _kv_int32("kv_rows_move", "lengths", lengths, B, dev)
     _kv_int32("kv_rows_move", "overflow", overflow, 1, dev)
     if not isinstance(jobs, torch.Tensor) or jobs.dim() != 2 or jobs.shape[1] != KV_JOB_WORDS:
@@ -1564,6 +1611,12 @@ def kv_rows_move(k_codes, k_exps, v_codes, v_exps, v_tail, lengths, overflow, jo
     if not isinstance(stage, torch.Tensor) or stage.dtype != torch.uint8 or stage.device != dev or not stage.is_contiguous():
         raise ValueError(f"kv_rows_move: stage must be a contiguous uint8 tensor on {dev}")
     with torch.cuda.device(dev):
+        if code_bits == 4:
+            check(load_library().bfpq_kv_rows_move_cb(_ptr(k_codes), _ptr(k_exps), _ptr(v_codes), _ptr(v_exps), _ptr(v_tail), _ptr(lengths),
+                                                      _ptr(overflow), _ptr(jobs), n, _ptr(stage), stage.numel(), B, int(kv_heads), D,
+                                                      int(block_size), DTYPE_CODE[v_tail.dtype], int(pages.tokens), int(pages.count), 4,
+                                                      _stream(v_tail)), "bfpq_kv_rows_move_cb")
+            return
         check(load_library().bfpq_kv_rows_move(_ptr(k_codes), _ptr(k_exps), _ptr(v_codes), _ptr(v_exps), _ptr(v_tail), _ptr(lengths),
                                                _ptr(overflow), _ptr(jobs), n, _ptr(stage), stage.numel(), B, int(kv_heads), D, int(block_size),
                                                DTYPE_CODE[v_tail.dtype], int(pages.tokens), int(pages.count), _stream(v_tail)),
@@ -1602,22 +1655,23 @@ def _kv_rows(what, x, form, group=1, heads=1):
 
 
 def _kv_operand(what, BH, w_bstride, wc, we, dev):   # (a paged cache: BH the heads the pool holds)
-    """one cached operand of kv_bmm_dec / kv_bmm_dec_dev: contiguous codes and exponents of BH x w_bstride rows"""
+    """one cached operand of kv_bmm_dec / kv_bmm_dec_dev: contiguous codes and exponents of BH x w_bstride rows (4-bit codes: the rows
+    are half as long, which is the last dimension that this reads)"""
     for name, buf in (("codes", wc), ("exponents", we)):
         if buf.device != dev or buf.dtype != torch.int8 or not buf.is_contiguous() or buf.numel() < BH * int(w_bstride) * buf.shape[-1]:
             raise ValueError(f"{what}: the cached {name} must be contiguous int8 on {dev} with {BH} x {w_bstride} rows "
                              f"(got {tuple(buf.shape)}, {buf.dtype}, {buf.device})")
 
 
-def _kv_cached(what, BH, D, block_size, k_codes, k_exps, v_codes, v_exps, dev):
+def _kv_cached(what, BH, D, block_size, k_codes, k_exps, v_codes, v_exps, dev, per_byte=1):
     """the four code and exponent buffers of BH cached heads (a paged cache: the heads the pool holds, of a page's tokens each) as the
-    attend entries take them; returns (cap, ldd)"""
+    attend entries take them (per_byte: as _kv_buffers); returns (cap, ldd), counted in codes"""
     if k_codes.dim() < 2 or v_codes.dim() < 2:
         raise ValueError(f"{what} takes k_codes [..., cap, ldd] and v_codes [..., D, cap]")
-    cap, ldd = k_codes.shape[-2], k_codes.shape[-1]
+    cap, ldd = k_codes.shape[-2], k_codes.shape[-1] * per_byte
     nbd, nbc = D // int(block_size), cap // int(block_size)
-    for name, buf, numel in (("k_codes", k_codes, BH * cap * ldd), ("k_exps", k_exps, BH * cap * nbd), ("v_codes", v_codes, BH * D * cap),
-                             ("v_exps", v_exps, BH * D * nbc)):
+    for name, buf, numel in (("k_codes", k_codes, BH * cap * ldd // per_byte), ("k_exps", k_exps, BH * cap * nbd),
+                             ("v_codes", v_codes, BH * D * cap // per_byte), ("v_exps", v_exps, BH * D * nbc)):
         if buf.device != dev or buf.dtype != torch.int8 or not buf.is_contiguous() or buf.numel() != numel:
             raise ValueError(f"{what}: {name} must be contiguous int8 on {dev} with {numel} elements "
                              f"(got {tuple(buf.shape)}, {buf.dtype}, {buf.device})")
@@ -1639,15 +1693,17 @@ def _kv_scale(what, scale):
 
 
 def kv_bmm_dec_dev(x, wc, we, family, bound, w_bstride, lengths, heads, block_size, mant_bits, epsilon, ws=None, chunks_per_split=0, group=1,
-                   pages=None):
+                   pages=None, code_bits=8):
     """kv_bmm_dec with head b's cached length read from lengths[b // heads] on the device (bfpq_kv_bmm_dec_gqa).  KV_QK: x [BH, Tq, D],
     bound = max_len; returns [BH, Tq, max_len], -inf from the length on.  KV_PV: x [BH, Tq, L], bound = D; returns [BH, Tq, D]; ws: a
     uint8 tensor of at least kv_dec_ws_bytes(BH, Tq, D, L, block_size) bytes; chunks_per_split: 64-token chunks per slice of the
     contraction, 0 = the library's choice (the result does not depend on it).  group > 1 (grouped-query attention): the BH cached heads
     serve `group` query heads each, x and the result hold group * Tq rows per cached head -- query head r // Tq of the group, token
     r % Tq -- and the workspace is that of BH * group heads.  pages (a KVPages): wc / we are a pool of pages (bfpq_kv_bmm_dec_paged),
-    w_bstride for KV_QK a page's tokens."""
+    w_bstride for KV_QK a page's tokens.  code_bits=4 (block 64, mant_bits <= 3): wc holds two codes to a byte, its rows half as long
+    (bfpq_kv_bmm_dec_cb, paged or not); the result is that of the int8 codes, bit for bit."""
     x, BH, R, Tq, Kx, heads = _kv_rows("kv_bmm_dec_dev", x, "x [BH, Tq, Kx]", group, heads)
+    per_byte = _kv_code_bits("kv_bmm_dec_dev", code_bits, block_size, mant_bits)
     dev = x.device
     _kv_operand("kv_bmm_dec_dev", BH if pages is None else _kv_pages("kv_bmm_dec_dev", pages, BH // heads, heads, dev), w_bstride, wc, we, dev)
     _kv_int32("kv_bmm_dec_dev", "lengths", lengths, BH // heads, dev)
@@ -1658,10 +1714,13 @@ def kv_bmm_dec_dev(x, wc, we, family, bound, w_bstride, lengths, heads, block_si
     ldo = (Nout + 3) // 4 * 4
     with torch.cuda.device(dev):
         out = torch.empty((BH, R, ldo), dtype=x.dtype, device=dev)
-        args = (_ptr(x), _ptr(wc), _ptr(we), _ptr(out), _ptr(lengths), BH, heads, Tq, group, Kx, Nout, Kx, wc.shape[-1], we.shape[-1],
+        args = (_ptr(x), _ptr(wc), _ptr(we), _ptr(out), _ptr(lengths), BH, heads, Tq, group, Kx, Nout, Kx, wc.shape[-1] * per_byte, we.shape[-1],
                 int(w_bstride), ldo, int(family), DTYPE_CODE[x.dtype], int(block_size), int(mant_bits), int(mant_bits), float(epsilon),
                 _ptr(exp_window_dev(x.dtype, dev)), _ptr(ws if family == KV_PV else None), ws_bytes, int(chunks_per_split))
-        if pages is None:
+        if code_bits == 4:
+            check(load_library().bfpq_kv_bmm_dec_cb(*args, 0 if pages is None else int(pages.capacity), *_kv_page_args(pages), 4, _stream(x)),
+                  "bfpq_kv_bmm_dec_cb")
+        elif pages is None:
             check(load_library().bfpq_kv_bmm_dec_gqa(*args, _stream(x)), "bfpq_kv_bmm_dec_gqa")
         else:
             check(load_library().bfpq_kv_bmm_dec_paged(*args, int(pages.capacity), *pages.args(), _stream(x)), "bfpq_kv_bmm_dec_paged")
@@ -1687,32 +1746,34 @@ def _kv_window(what, BH, heads, starts, window, dev):
     return starts, window
 
 
-def _kv_paged_cached(what, pages, starts, window, BH, heads, D, block_size, k_codes, k_exps, v_codes, v_exps, dev):
+def _kv_paged_cached(what, pages, starts, window, BH, heads, D, block_size, k_codes, k_exps, v_codes, v_exps, dev, per_byte=1):
     """_kv_cached for the attend entries, on a pool of pages where `pages` is given; returns (the cap the entry takes, ldd)"""
     if pages is None:
-        return _kv_cached(what, BH, D, block_size, k_codes, k_exps, v_codes, v_exps, dev)
+        return _kv_cached(what, BH, D, block_size, k_codes, k_exps, v_codes, v_exps, dev, per_byte)
     if starts is not None or window:
         raise NotImplementedError(f"{what}: a paged cache takes no starts and no window")
     held = _kv_pages(what, pages, BH // heads, heads, dev)
-    P, ldd = _kv_cached(what, held, D, block_size, k_codes, k_exps, v_codes, v_exps, dev)
+    P, ldd = _kv_cached(what, held, D, block_size, k_codes, k_exps, v_codes, v_exps, dev, per_byte)
     if P != int(pages.tokens):
         raise ValueError(f"{what}: the buffers hold heads of {P} tokens, a page has {pages.tokens}")
     return int(pages.capacity), ldd
 
 
 def kv_attend(q, k_codes, k_exps, v_codes, v_exps, lengths, heads, max_len, scale, causal, block_size, mant_bits, epsilon, score_ws, sum_ws,
-              chunks_per_split=0, return_probs=False, group=1, starts=None, window=None, pages=None):
+              chunks_per_split=0, return_probs=False, group=1, starts=None, window=None, pages=None, code_bits=8):
     """scores, scale, softmax and context of q [BH, Tq, D] against a device-length cache in three launches (bfpq_kv_attend_gqa): returns
     (context [BH, Tq, D], p [BH, Tq, max_len] or None).  score_ws / sum_ws: contiguous uint8 tensors of at least
     kv_attend_ws_bytes(BH, Tq, max_len) / kv_dec_ws_bytes(BH, Tq, D, max_len, block_size) bytes.  Nothing is read back.  group > 1: rows
     and workspaces as kv_bmm_dec_dev takes them (q, the context and p hold group * Tq rows per cached head; causal goes by the token).
     starts (int32 [BH // heads] on the device) and / or window (an int >= 1): the rows see the keys from max(starts[b], what they see
     minus window) on (bfpq_kv_attend_gqa_win); with neither, the call and its kernels are the ones without.  pages (a KVPages; with neither
-    starts nor window): the buffers are a pool of pages (bfpq_kv_attend_paged)."""
+    starts nor window): the buffers are a pool of pages (bfpq_kv_attend_paged).  code_bits=4 (block 64, mant_bits <= 3): the code buffers
+    hold two codes to a byte (bfpq_kv_attend_cb, with or without starts / window / pages); the bits are those of the int8 codes."""
     q, BH, R, Tq, D, heads = _kv_rows("kv_attend", q, "q [BH, Tq, D]", group, heads)
+    per_byte = _kv_code_bits("kv_attend", code_bits, block_size, mant_bits)
     dev = q.device
     starts, window = _kv_window("kv_attend", BH, heads, starts, window, dev)
-    cap, ldd = _kv_paged_cached("kv_attend", pages, starts, window, BH, heads, D, block_size, k_codes, k_exps, v_codes, v_exps, dev)
+    cap, ldd = _kv_paged_cached("kv_attend", pages, starts, window, BH, heads, D, block_size, k_codes, k_exps, v_codes, v_exps, dev, per_byte)
     _kv_int32("kv_attend", "lengths", lengths, BH // heads, dev)
     max_len, scale = int(max_len), _kv_scale("kv_attend", scale)
     score_bytes = _kv_ws("kv_attend", "score_ws", score_ws, kv_attend_ws_bytes(BH * group, Tq, max_len), dev)
@@ -1723,7 +1784,9 @@ def kv_attend(q, k_codes, k_exps, v_codes, v_exps, lengths, heads, max_len, scal
         args = (_ptr(q), _ptr(k_codes), _ptr(k_exps), _ptr(v_codes), _ptr(v_exps), _ptr(out), _ptr(p), _ptr(lengths), BH, heads, Tq, group, D,
                 max_len, cap, ldd, D, max_len, scale, int(bool(causal)), DTYPE_CODE[q.dtype], int(block_size), int(mant_bits), int(mant_bits),
                 float(epsilon), _ptr(exp_window_dev(q.dtype, dev)), _ptr(score_ws), score_bytes, _ptr(sum_ws), sum_bytes, int(chunks_per_split))
-        if pages is not None:
+        if code_bits == 4:
+            check(load_library().bfpq_kv_attend_cb(*args, _ptr(starts), window, *_kv_page_args(pages), 4, _stream(q)), "bfpq_kv_attend_cb")
+        elif pages is not None:
             check(load_library().bfpq_kv_attend_paged(*args, *pages.args(), _stream(q)), "bfpq_kv_attend_paged")
         elif starts is None and not window:
             check(load_library().bfpq_kv_attend_gqa(*args, _stream(q)), "bfpq_kv_attend_gqa")
@@ -1744,19 +1807,21 @@ def kv_attend_rows_ws_bytes(BH, P, max_len):
 
 
 def kv_attend_rows(q, k_codes, k_exps, v_codes, v_exps, lengths, heads, max_len, scale, causal, block_size, mant_bits, epsilon, score_ws,
-                   panel_rows, return_probs=False, group=1, starts=None, window=None, pages=None):
+                   panel_rows, return_probs=False, group=1, starts=None, window=None, pages=None, code_bits=8):
     """kv_attend for any number of query rows (bfpq_kv_attend_rows): q [BH, group * Tq, D] is walked in panels of panel_rows tokens per
     query head, two launches per panel, the panel's fp32 score rows in score_ws (a contiguous uint8 tensor of at least
     kv_attend_rows_ws_bytes(BH * group, min(panel_rows, Tq), max_len) bytes).  Returns (context [BH, group * Tq, D], p
     [BH, group * Tq, max_len] or None); row for row kv_attend's bits.  Nothing is read back.  starts, window: as kv_attend
-    (bfpq_kv_attend_rows_win); pages: as kv_attend (bfpq_kv_attend_rows_paged)."""
+    (bfpq_kv_attend_rows_win); pages: as kv_attend (bfpq_kv_attend_rows_paged); code_bits: as kv_attend (bfpq_kv_attend_rows_cb)."""
     q, BH, R, Tq, D, heads = _kv_rows("kv_attend_rows", q, "q [BH, Tq, D]", group, heads)
+    per_byte = _kv_code_bits("kv_attend_rows", code_bits, block_size, mant_bits)
     panel_rows = int(panel_rows)
     if panel_rows < 1:
         raise ValueError(f"kv_attend_rows: panel_rows must be >= 1 (got {panel_rows})")
     dev = q.device
     starts, window = _kv_window("kv_attend_rows", BH, heads, starts, window, dev)
-    cap, ldd = _kv_paged_cached("kv_attend_rows", pages, starts, window, BH, heads, D, block_size, k_codes, k_exps, v_codes, v_exps, dev)
+    cap, ldd = _kv_paged_cached("kv_attend_rows", pages, starts, window, BH, heads, D, block_size, k_codes, k_exps, v_codes, v_exps, dev,
+                                per_byte)
     _kv_int32("kv_attend_rows", "lengths", lengths, BH // heads, dev)
     max_len, scale = int(max_len), _kv_scale("kv_attend_rows", scale)
     score_bytes = _kv_ws("kv_attend_rows", "score_ws", score_ws, kv_attend_rows_ws_bytes(BH * group, min(panel_rows, Tq), max_len), dev)
@@ -1768,7 +1833,9 @@ def kv_attend_rows(q, k_codes, k_exps, v_codes, v_exps, lengths, heads, max_len,
             args = (_ptr(q), _ptr(k_codes), _ptr(k_exps), _ptr(v_codes), _ptr(v_exps), _ptr(out), _ptr(p), _ptr(lengths), BH, heads, Tq, group, D,
                     max_len, cap, ldd, D, max_len, scale, int(bool(causal)), DTYPE_CODE[q.dtype], int(block_size), int(mant_bits), int(mant_bits),
                     float(epsilon), win, _ptr(score_ws), score_bytes, None, 0, 0, row0, min(panel_rows, Tq - row0))
-            if pages is not None:
+            if code_bits == 4:
+                check(L.bfpq_kv_attend_rows_cb(*args, _ptr(starts), window, *_kv_page_args(pages), 4, stream), "bfpq_kv_attend_rows_cb")
+            elif pages is not None:
                 check(L.bfpq_kv_attend_rows_paged(*args, *pages.args(), stream), "bfpq_kv_attend_rows_paged")
             elif starts is None and not window:
                 check(L.bfpq_kv_attend_rows(*args, stream), "bfpq_kv_attend_rows")
